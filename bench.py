@@ -9,17 +9,26 @@ of the found record).  K steps run back to back on the resident points (the outp
 input point of the next).  value = curves processed by all ranks / max-over-ranks time — the figure the
 reference prints as "Stage 1 took" (ecm.c:1315-1317), inverted.
 
-Launch:  python bench.py --gpus N --steps K --warmup W
+Launch:  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
   * N > 1 without WORLD_SIZE in the environment: this process touches no GPU; it starts N ranks through
     torch.distributed.run (one process per GPU, RCCL) as a child process and relays rank 0's line.
   * under torch.distributed.run (RANK/LOCAL_RANK/WORLD_SIZE set): --gpus must equal WORLD_SIZE.
   * every rank works on its own 4096 curves (weak scaling: N = 8 is BASELINE configs[3]).
 
-Time budget (--budget-s, default 450 s): the step count is derived from the first warm-up step so that
-warm-up + timed steps + the CPU baseline stay inside it ("steps_requested" records what was asked for);
-the extras run only while budget is left.  Rank 0 prints ONE JSON line on stdout.
+Steps: exactly K timed steps after W warm-up steps (at least one warm-up step runs, even with --warmup 0: the
+first launch loads the code objects).  A plain run does only that and prints the line; --full adds the
+stage-2 pass, the CPU baseline and the extras below, which run only while the wall-clock budget
+(--budget-s, default 450 s) lasts.  Rank 0 prints ONE JSON line on stdout.
 
-Extra objects on the line:
+--dump-outputs DIR: after the timed steps, what the last step handed its caller, as float64 arrays in
+DIR/<name>.npy (a rank r of a world > 1 writes <name>_rank<r>.npy): X.npy and Z.npy, the de-Montgomeryised
+stage-1 point of every curve (rows = curves, columns = little-endian limbs of the reference's limb format,
+exact in float64), factor_flag.npy (1 where the device factor scan found gcd(Z, N) > 1), curve.npy (global
+curve index of each row; sigma = 1000 + index) and found.npy (curves with a factor on this rank, lowest
+global curve with a factor or -1).  Above 64 MB the rows are a fixed seeded sample of the curves.  The
+inputs depend only on the arguments, so two builds can be compared output for output.
+
+Extra objects on the line (roofline and ranks always, the others only with --full):
   roofline      VALU-issue roofline of the dominant kernel: achieved integer multiply-adds
                 (v_mad_u64_u32, the instruction the multiply is built from) per second against the gfx950
                 issue peak; the same in SURVEY.md §8d units (52-bit limb products).  Kernel time from HIP
@@ -52,6 +61,7 @@ sys.path.insert(0, os.path.join(ROOT, "avx-ecm_amd"))
 PEAK_MAD_PER_S = 256 * 4 * 16 * 2.4e9      # CUs x SIMDs x lanes/clk (v_mad_u64_u32: 4 clk per wave64) x Hz
 PEAK_FMA64_PER_S = 256 * 4 * 16 * 2.4e9    # v_fma_f64 issues at the same rate (78.6 TFLOP/s datasheet)
 KERNEL_NAMES = {1: "k_stage1<%d>", 2: "k_stage1_pair<%d>", 8: "k_stage1_quad<%d>"}
+DUMP_LIMIT_BYTES = 63 * 10 ** 6           # --dump-outputs: rows of all files together (64 MB with the headers)
 
 
 def kernel_name(lanes, dev_limbs):
@@ -137,17 +147,31 @@ def cpu_baseline(n, b1, budget_s=30.0):
     return out
 
 
-def plan_steps(steps, warmup, t_probe, avail_s):
-    """(further warm-up steps, timed steps) after the probe step, which is warm-up step 1: what was asked
-    for if it fits into avail_s at t_probe seconds per step, else at most one more warm-up step and as many
-    timed steps as fit (at least 1)"""
-    steps = max(1, steps)
-    more_warm = max(0, warmup - 1)
-    afford = int(avail_s / max(t_probe, 1e-6))
-    if more_warm + steps > afford:
-        more_warm = min(more_warm, 1)
-        steps = max(1, min(steps, afford - more_warm))
-    return more_warm, steps
+def dump_rows(batch, bytes_per_row, limit=DUMP_LIMIT_BYTES):
+    """rows of a --dump-outputs file set: every curve, or a fixed seeded sample when they would exceed the limit"""
+    if batch * bytes_per_row <= limit:
+        return list(range(batch))
+    return sorted(random.Random(0).sample(range(batch), limit // bytes_per_row))
+
+
+def dump_outputs(eng, out_dir, suffix, lo, nfound, first_global):
+    """--dump-outputs: the stage-1 points, factor flags and found record of the last timed step (see the docstring)"""
+    import numpy as np
+    X, Z = eng.download_points_plain()
+    db, nw = eng.cfg.digitbits, eng.cfg.nwords
+    mask = (1 << db) - 1
+    rows = dump_rows(eng.batch, 8 * (2 * nw + 2))
+
+    def limbs(vals):
+        return np.array([[(vals[k] >> (db * j)) & mask for j in range(nw)] for k in rows], dtype=np.float64)
+
+    arrays = {"X": limbs(X), "Z": limbs(Z),
+              "factor_flag": np.array([1.0 if eng.curve_flag(1, k) else 0.0 for k in rows], dtype=np.float64),
+              "curve": np.array([lo + k for k in rows], dtype=np.float64),
+              "found": np.array([nfound, -1 if first_global is None else first_global], dtype=np.float64)}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), arr)
 
 
 def free_port():
@@ -223,17 +247,25 @@ def main():
     ap.add_argument("--curves", type=int, default=4096, help="curves per GPU per step (BASELINE configs[1]: 4096)")
     ap.add_argument("--bits", type=int, default=415)
     ap.add_argument("--b1", type=int, default=1000000)
-    ap.add_argument("--budget-s", type=float, default=450.0, help="wall-clock budget of the whole run")
+    ap.add_argument("--full", action="store_true", help="after the headline, also the stage-2 pass (--b2), the CPU baseline "
+                    "and the extras (saturated / config2 / bits624 / config4 / special_form); off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy")
+    ap.add_argument("--budget-s", type=float, default=450.0, help="wall-clock budget of a --full run: the CPU baseline and "
+                    "the extras run only while it lasts")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip saturated / config2 / config4 / special_form")
     ap.add_argument("--lanes", type=int, default=0, help="lanes per curve in stage 1: 0 = library's choice, 1, 2, 8, 32")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for --gpus > 1 (nccl = RCCL; "
                     "gloo only to rehearse the multi-rank control flow)")
-    ap.add_argument("--b2", type=int, default=100000000, help="after the timed stage-1 steps, one stage-2 pass to this B2 on "
-                    "every rank's resident batch (BASELINE configs[3]: B2 = 1e8), reported separately as \"stage2\"; "
+    ap.add_argument("--b2", type=int, default=100000000, help="with --full: after the timed stage-1 steps, one stage-2 pass to "
+                    "this B2 on every rank's resident batch (BASELINE configs[3]: B2 = 1e8), reported separately as \"stage2\"; "
                     "0 = none.  Not part of the metric, outside the timed region")
     ap.add_argument("--no-engine", action="store_true", help="rehearsal without a GPU: launcher + collectives only")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if a.no_engine and a.dump_outputs:
+        ap.error("--dump-outputs needs the engine: --no-engine computes nothing")
     t_begin = time.perf_counter()
 
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
@@ -296,9 +328,10 @@ def main():
     collectives = [0]          # found-record all-reduces that really went through the process group
 
     prepared = []
+    with_stage2 = a.full and a.b2 > a.b1 and not a.no_engine
 
     def step():
-        if a.b2 > a.b1 and not a.no_engine and not prepared:
+        if with_stage2 and not prepared:
             # probe step only: the pair map of [B1, B2) is made on the host while the device runs stage 1
             # (gecm_stage2_prepare; kept in the context for the stage-2 pass after the timed region)
             eng.stage1(a.b1, sync=False)
@@ -317,17 +350,12 @@ def main():
         if dist is not None:
             collectives[0] += 1
 
-    # ---- step count from the budget: one probe step (the first warm-up step, or an extra one) ----
+    # ---- warm-up: step 1 runs even with --warmup 0 (first launch; its time is the probe the --full extras budget with) ----
     t0 = time.perf_counter()
-    step()                                   # warm-up step 1 (run even with --warmup 0: it is the probe)
+    step()
     t_probe = allmax(time.perf_counter() - t0)
-    cpu_reserve = 0.0 if (a.no_cpu_baseline or world > 1) else 40.0
-    avail = a.budget_s - (time.perf_counter() - t_begin) - cpu_reserve - 10.0
-    # identical on every rank: t_probe is the max over ranks, and rank 0's clock decides
-    avail = allmax(avail if rank == 0 else -1e30)
-    more_warm, steps = plan_steps(a.steps, a.warmup, t_probe, avail)
-    warmup = 1 + more_warm
-    for _ in range(more_warm):
+    warmup, steps = max(1, a.warmup), a.steps
+    for _ in range(warmup - 1):
         step()
     kernel_ms.clear()
     barrier()
@@ -336,6 +364,9 @@ def main():
         step()
     barrier()
     dt = allmax(time.perf_counter() - t0)
+
+    if a.dump_outputs:
+        dump_outputs(eng, a.dump_outputs, "" if world == 1 else "_rank%d" % rank, lo, found_log[-1][0], found_log[-1][1])
 
     st = eng.stage1_stats()
     cfg = eng.cfg
@@ -357,7 +388,7 @@ def main():
         world_reported = None
 
     stage2 = None
-    if a.b2 > a.b1 and not a.no_engine:
+    if with_stage2:
         # not part of the metric: one pass of the stage-2 continuation on every rank's resident batch
         barrier()
         t2 = time.perf_counter()
@@ -463,7 +494,7 @@ def main():
     def left():
         return a.budget_s - (time.perf_counter() - t_begin)
 
-    if rank == 0 and world == 1 and not a.no_engine:
+    if rank == 0 and world == 1 and not a.no_engine and a.full:
         # ---- rank 0 at N = 1 only: the other ranks would wait at the barrier ----
         if not a.no_cpu_baseline:
             try:

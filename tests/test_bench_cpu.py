@@ -30,12 +30,12 @@ def test_host_cores_positive():
     assert 1 <= _bench().host_cores() <= 64
 
 
-def test_plan_steps_keeps_request_when_it_fits_and_shrinks_otherwise():
+def test_dump_rows_are_all_curves_or_a_fixed_sample_under_the_limit():
     b = _bench()
-    assert b.plan_steps(20, 5, 4.0, 400.0) == (4, 20)          # the driver's flags at 4 s per step: 96 s, fits
-    assert b.plan_steps(20, 5, 25.3, 400.0) == (1, 14)         # round 1's 131072-curve step would not have
-    assert b.plan_steps(20, 5, 500.0, 400.0) == (0, 1) or b.plan_steps(20, 5, 500.0, 400.0) == (1, 1)
-    assert b.plan_steps(3, 0, 1.0, 100.0) == (0, 3)
+    assert b.dump_rows(4096, 144) == list(range(4096))
+    rows = b.dump_rows(10 ** 6, 144)
+    assert len(rows) * 144 <= b.DUMP_LIMIT_BYTES < 64 * 10 ** 6 and rows == sorted(set(rows))
+    assert rows == b.dump_rows(10 ** 6, 144)                  # the same sample every run
 
 
 def _run_bench(*args):
@@ -73,6 +73,19 @@ def test_eight_ranks_rehearsal_line_checks_itself():
     assert [x["rank"] for x in r["per_rank"]] == list(range(8))
     assert r["found_record_allreduces_per_rank_timed_and_warmup"] == [3] * 8
     assert "gloo" in d["config"]["parallelism"]
+
+
+def test_steps_and_warmup_are_what_was_asked_for():
+    """--steps is the number of timed steps whatever the budget; warm-up step 1 runs even with --warmup 0"""
+    p, lines = _run_bench("--gpus", "1", "--no-engine", "--steps", "7", "--warmup", "2", "--budget-s", "0.01")
+    assert p.returncode == 0, p.stderr[-2000:]
+    d = lines[0]
+    assert d["steps"] == 7 and d["warmup"] == 2 and d["steps_requested"] == 7
+    assert not set(d) & {"stage2", "cpu_baseline", "saturated", "config2", "bits624", "config4", "special_form"}
+    p, lines = _run_bench("--gpus", "1", "--no-engine", "--steps", "3", "--warmup", "0")
+    assert p.returncode == 0 and lines[0]["steps"] == 3 and lines[0]["warmup"] == 1
+    p, lines = _run_bench("--gpus", "1", "--no-engine", "--steps", "0")
+    assert p.returncode != 0 and not lines
 
 
 def test_single_process_line_says_there_is_no_collective():

@@ -2,6 +2,7 @@
 the RCCL process group, so init, barrier and the found-record all-reduce on device tensors run on hardware)."""
 import json
 import os
+import random
 import subprocess
 import sys
 
@@ -10,8 +11,9 @@ import pytest
 from conftest import ROOT
 
 pytestmark = pytest.mark.gpu
+# --full for the stage-2 pass to --b2; the extras and the CPU baseline stay off
 ARGS = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--b1", "20000", "--b2", "400000", "--curves", "256", "--no-extras",
-        "--no-cpu-baseline"]
+        "--no-cpu-baseline", "--full"]
 
 
 def _line(cmd):
@@ -32,6 +34,37 @@ def test_bench_line_has_the_contract_s_fields():
     assert d["config"]["curves_per_gpu"] == 256 and d["config"]["lanes_per_curve"] == 32
     assert set(("bound", "achieved", "peak", "unit", "frac", "traffic", "kernel", "kernel_ms_avg")) <= set(d["roofline"])
     assert d["stage2"]["B2"] == 400000 and d["stage2"]["seconds"] > 0
+
+
+def test_plain_bench_times_the_steps_asked_for_and_dumps_the_last_step_s_outputs(tmp_path):
+    """without --full: the headline only (no stage 2, no CPU baseline, no extras), exactly --steps timed steps; the dumped
+    points are the engine's own after warm-up + timed stage-1 passes on the same batch, and a second run dumps the same"""
+    import numpy as np
+    args = ["--gpus", "1", "--steps", "3", "--warmup", "1", "--b1", "20000", "--curves", "256"]
+    runs = []
+    for k in range(2):
+        out = tmp_path / ("run%d" % k)
+        d = _line([sys.executable, "bench.py"] + args + ["--dump-outputs", str(out)])
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0
+        assert not set(d) & {"stage2", "cpu_baseline", "saturated", "config2", "bits624", "config4", "special_form"}
+        arrs = {n: np.load(out / (n + ".npy")) for n in ("X", "Z", "factor_flag", "curve", "found")}
+        assert all(a.dtype == np.float64 for a in arrs.values())
+        runs.append(arrs)
+    assert all(np.array_equal(runs[0][n], runs[1][n]) for n in runs[0])
+    X, Z = runs[0]["X"], runs[0]["Z"]
+    assert X.shape == Z.shape and X.shape[0] == 256 and list(runs[0]["curve"]) == list(range(256))
+    assert runs[0]["found"][0] == runs[0]["factor_flag"].sum()
+    import pyecm
+    n = random.Random(415).getrandbits(415) | (1 << 414) | 1
+    eng = pyecm.Engine(n, digitbits=52, device=0)
+    eng.build_curves(list(range(1000, 1000 + 256)))
+    eng.set_lanes_per_curve(0)
+    for _ in range(1 + 3):
+        eng.stage1(20000)
+    ex, ez = eng.download_points_plain()
+    eng.close()
+    val = lambda row: sum(int(v) << (52 * j) for j, v in enumerate(row))
+    assert [val(r) for r in X] == ex and [val(r) for r in Z] == ez
 
 
 def test_bench_as_a_rank_under_torch_distributed_run():

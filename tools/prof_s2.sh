@@ -8,7 +8,7 @@ rm -rf "$out"
 mkdir -p "$out"
 cd /tmp && export TMPDIR=/tmp
 export GECM_LIB=$1
-rocprofv3 --kernel-trace --stats --output-format csv -d "$out" -- python3 "$root/bench.py" --curves "$2" --b1 100000 --b2 100000000 --steps 1 --warmup 0 --no-extras --no-cpu-baseline > "$out/bench.json" 2> "$out/bench.err"
+rocprofv3 --kernel-trace --stats --output-format csv -d "$out" -- python3 "$root/bench.py" --full --curves "$2" --b1 100000 --b2 100000000 --steps 1 --warmup 0 --no-extras --no-cpu-baseline > "$out/bench.json" 2> "$out/bench.err"
 f=$(ls "$out"/*/*kernel_stats.csv | head -1)
 [ -n "$f" ] || { echo "no kernel_stats.csv under $out (see $out/bench.err)" >&2; exit 1; }
 echo "== $3"; python3 - "$f" <<'PY'
