@@ -141,7 +141,6 @@ __device__ __forceinline__ void run_tape(const uint32_t *__restrict__ tape, uint
         // (1,762,907 of 1,902,102 steps) and comes in long runs.  Straight-line code with no
         // operand selection; only A, B, C are live around it.
         // ecm.c:617-630 (swap), 683-713: T = B + A (C); (B,T,C) <- (T,C,B)
-#ifndef GECM_NO_FASTPATH
         while ((op & ~GECM_OP_SWAP) == (GECM_OP_STEP | GECM_OP_RULE3)) {
             if (op & GECM_OP_SWAP) {
                 Pt<NL> t = A;
@@ -169,7 +168,6 @@ __device__ __forceinline__ void run_tape(const uint32_t *__restrict__ tape, uint
             op = nxt;
             nxt = (pc + 1 < tape_len) ? fetch(pc + 1) : GECM_OP_NOP;
         }
-#endif
         if (op == GECM_OP_NOP) continue;
         // Slow path (rules 4, 5, 9, PRAC_BEGIN, PRAC_END: 14% of the events).  Every one of them is
         // "T = B' + A' (difference C'), D = 2A'" for a renaming (A',B',C') of the three points, so

@@ -56,7 +56,7 @@ int gecm_dev_set_rowconst(gecm_dev *d, int nq, int rows, const uint32_t *words);
 int gecm_dev_fform_generic_limbs(int nl);
 void gecm_dev_set_fform(gecm_dev *d, int form);   /* +1: 2^k - 1, -1: 2^k + 1, 2: 2^k - c (limbs 0, 1 below F), 0: off */
 int gecm_dev_last_lanes(gecm_dev *d);
-/* name of the stage-1 kernel the last launch ran, as rocprofv3 prints it ("k_stage1_rowp<1, 16>") */
+/* name of the stage-1 kernel the last launch ran, as rocprofv3 prints it ("k_stage1_row<1, 16, false>") */
 const char *gecm_dev_last_kernel(gecm_dev *d);
 int gecm_dev_sync(gecm_dev *d);
 float gecm_dev_last_kernel_ms(gecm_dev *d);

@@ -36,9 +36,6 @@ extern "C" const int *gecm_dev_supported_nl(void) { return k_supported_nl; }
 #define GECM_S2_WAVES_PER_SIMD 16         // wavefronts per SIMD a pair-walk launch is cut up for (gecm_dev_s2_init)
 #endif
 #define GECM_S2_MAX_SLICES 64
-#ifndef GECM_ROW_DEFAULT_SMALL
-#define GECM_ROW_DEFAULT_SMALL 0   // 32-lane kernel variant for batches up to 2 wavefronts per SIMD (row_a_lds)
-#endif
 struct gecm_dev {
     int device = 0;
     int nl = 0;
@@ -369,20 +366,14 @@ extern "C" int gecm_dev_auto_lanes(gecm_dev *d)
     return (r == 0 || r > full / 4 * 3) ? 1 : 2;
 }
 
-/* 32-lane kernel, how the scanned operand of a multiply reaches its row (csrc/gecm_row.hpp): 0 = DPP broadcasts, 1 =
- * ds_swizzle through the LDS crossbar (best from 3 wavefronts per SIMD up, tools/row_check.py), 2 = point forms kept in
- * LDS and read one multiply ahead (k_stage1_rowp: the fewest VALU instructions; what a batch at up to 2 wavefronts per
- * SIMD — BASELINE configs[1] — is short of).  GECM_ROW_ALDS=0/1/2 overrides for experiments. */
-static int row_a_lds(const gecm_dev *d)
+/* 32-lane kernel, how the scanned operand of a multiply reaches its row (csrc/gecm_row.hpp): DPP broadcasts, or
+ * (true) ds_swizzle through the LDS crossbar.  Two or three limbs per lane: the DPP rows (operand limbs two per
+ * v_mov_b64_dpp) beat the crossbar by 8-12 % at every batch size from 4096 to 16,384 curves
+ * (profiles/r03/mid_batch_rows.txt); one limb per lane: DPP up to two wavefronts per SIMD (4096 curves: 262 against
+ * 284 ms), the crossbar from there (6144: 363 against 373; equal from 8192 on, tools/row_check.py). */
+static bool row_a_lds(const gecm_dev *d)
 {
-    const char *e = getenv("GECM_ROW_ALDS");
-    if (e && e[0] >= '0' && e[0] <= '2' && !e[1]) return e[0] - '0';
-    /* two or three limbs per lane: the DPP rows (operand limbs two per v_mov_b64_dpp, gecm_row.hpp) beat the crossbar
-     * variant by 8-12 % at every batch size from 4096 to 16,384 curves (profiles/r03/mid_batch_rows.txt); one limb per
-     * lane: DPP up to two wavefronts per SIMD (4096 curves: 262 against 284 ms), the crossbar from there (6144: 363
-     * against 373; equal from 8192 on) */
-    if (d->row_nq >= 2) return 0;
-    return d->stride > (size_t)d->cus * 16 ? 1 : GECM_ROW_DEFAULT_SMALL;
+    return d->row_nq == 1 && d->stride > (size_t)d->cus * 16;
 }
 
 extern "C" int gecm_dev_last_lanes(gecm_dev *d) { return d->last_lanes; }
@@ -423,9 +414,7 @@ extern "C" int gecm_dev_stage1(gecm_dev *d, int lanes_per_curve)
     d->last_lanes = lanes_per_curve;
     {
         char nm[96];
-        const int mode = row_a_lds(d);
-        if (lanes_per_curve == 32 && mode == 2) snprintf(nm, sizeof nm, "k_stage1_rowp<%d, %d>", d->row_nq, d->row_rows);
-        else if (lanes_per_curve == 32) snprintf(nm, sizeof nm, "k_stage1_row<%d, %d, %s>", d->row_nq, d->row_rows, mode ? "true" : "false");
+        if (lanes_per_curve == 32) snprintf(nm, sizeof nm, "k_stage1_row<%d, %d, %s>", d->row_nq, d->row_rows, row_a_lds(d) ? "true" : "false");
         else if (lanes_per_curve == 8) snprintf(nm, sizeof nm, "k_stage1_quad<%d>", d->nl);
         else if (d->fform) snprintf(nm, sizeof nm, "%s<%d, Mod%c<%d> >", lanes_per_curve == 2 ? "k_stage1_pair_f" : "k_stage1_f", d->nl,
                                     d->fform == 2 ? 'C' : d->fform > 0 ? 'F' : 'P', d->nl);

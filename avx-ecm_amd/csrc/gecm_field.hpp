@@ -101,12 +101,7 @@ template <int K>
 __device__ __forceinline__ void mad_chain_v(uint64_t &acc, const uint32_t (&x)[K], const uint32_t (&y)[K])
 {
     static_assert(K >= 1 && K <= 14, "one asm statement takes at most 30 operands");
-#ifdef GECM_CXX_MAD
-#pragma unroll
-    for (int k = 0; k < K; k++) acc += (uint64_t)x[k] * (uint64_t)y[k];
-#else
     GECM_MAD_CASES("v")
-#endif
 }
 
 // the same with wave-uniform y[k] (limbs of the modulus)
@@ -114,12 +109,7 @@ template <int K>
 __device__ __forceinline__ void mad_chain_s(uint64_t &acc, const uint32_t (&x)[K], const uint32_t (&y)[K])
 {
     static_assert(K >= 1 && K <= 14, "one asm statement takes at most 30 operands");
-#ifdef GECM_CXX_MAD
-#pragma unroll
-    for (int k = 0; k < K; k++) acc += (uint64_t)x[k] * (uint64_t)y[k];
-#else
     GECM_MAD_CASES("s")
-#endif
 }
 
 template <int K> struct IC { static constexpr int value = K; };

@@ -113,8 +113,6 @@ k_stage1_pair_f(const uint32_t *__restrict__ tape, uint32_t tape_len, uint32_t *
 }
 
 // Eight lanes per curve (gecm_quad.hpp).
-#define GECM_HAS_QUAD 1
-#if GECM_HAS_QUAD
 // 256-thread workgroups (four independent wavefronts): this kernel needs about 65 registers, and one-wavefront
 // workgroups of such a kernel are not spread evenly by a cold dispatcher — see gecm_rowk.hip; its first launch of a
 // process measured 745 ms against 483 ms at 8192 curves.
@@ -143,7 +141,6 @@ k_stage1_quad(const uint32_t *__restrict__ tape, uint32_t tape_len, uint32_t *__
     run_tape_quad<NL>(tape, tape_len, P, S, stride, cidx, l, isZ, m);
     feq_store<NL>(mine, stride, cidx, l, P);    // lazy representative; k_canon makes it canonical
 }
-#endif
 
 // canonical Montgomery form of X, Z in place (the tail of k_stage1, for kernels that leave lazy values)
 template <int NL>
@@ -374,16 +371,11 @@ extern "C" int CAT(gecm_launch_stage1_quad_, GECM_NL)(void *stream, const gecm_m
                                                       uint32_t tape_len, uint32_t *X, uint32_t *Z,
                                                       const uint32_t *S, size_t stride, const uint32_t *modq)
 {
-#if GECM_HAS_QUAD
     hipLaunchKernelGGL(k_stage1_quad<GECM_NL>, dim3((unsigned)(stride / 32)), dim3(256), 0, (hipStream_t)stream, tape,   // stride: a multiple of 64
                        tape_len, X, Z, S, stride, modq, mc->rho);
     hipLaunchKernelGGL(k_canon<GECM_NL>, dim3((unsigned)(stride / 64)), dim3(64), 0, (hipStream_t)stream, X, Z, stride,
                        make_args<GECM_NL>(mc));
     return 0;
-#else
-    (void)stream; (void)mc; (void)tape; (void)tape_len; (void)X; (void)Z; (void)S; (void)stride; (void)modq;
-    return -1;
-#endif
 }
 
 extern "C" void CAT(gecm_launch_canon_, GECM_NL)(void *stream, const gecm_modconst *mc, uint32_t *X, uint32_t *Z,

@@ -29,11 +29,6 @@
 #include "gecm_curve.hpp"
 #include "gecm_rowk.h"
 
-#ifndef GECM_ROW_DPP_ROWS
-#define GECM_ROW_DPP_ROWS 48    /* rows of a multiply whose operand limb is broadcast by DPP (the rest: ds_swizzle).
-                                   Measured at 4096 curves x 415 bits, B1 = 1e5: all rows 271 ms, 4 rows 279 ms */
-#endif
-
 template <int NQ>
 struct FeR {
     int32_t v[NQ];
@@ -120,14 +115,17 @@ __device__ __forceinline__ int64_t smad16_smad(int32_t x, int64_t add, int32_t y
     return r;
 }
 
-// r = a*b/R' mod (modulus of m), R' = 2^(28*ROWS): ROWS = the limbs in use (a multiple of NQ, at most 16*NQ; limbs
-// from ROWS up are zero in every operand and in the modulus, so their rows would add nothing).  Operand limbs |.| < 2^29; result limbs in [-2^27-4, 2^27+4]
-// (top limb: whatever the value needs), |result| < |a||b|/R' + modulus.
-// ALDS: the limbs of a are broadcast through the LDS crossbar (ds_swizzle: no VALU issue slot; with ONE limb per lane best
-// from 3 wavefronts per SIMD up) instead of DPP row_newbcast (best at 2, and at every batch size with 2-3 limbs per lane).
+// r = a*b/R' mod (modulus of m), R' = 2^(28*ROWS): ROWS = the limbs in use (at most 16*NQ; limbs from ROWS up are
+// zero in every operand and in the modulus, so their rows would add nothing).  Operand limbs |.| < 2^29; result limbs in
+// [-2^27-4, 2^27+4] (top limb: whatever the value needs), |result| < |a||b|/R' + modulus.
+// Three forms: one limb per lane with the limbs of a broadcast by DPP row_newbcast (best up to 2 wavefronts per SIMD),
+// one limb per lane with ALDS: through the LDS crossbar (ds_swizzle: no VALU issue slot; best from 3 wavefronts per SIMD
+// up), and two or three limbs per lane, by DPP (best at every batch size: profiles/r03/mid_batch_rows.txt).
 template <int NQ, int ROWS, bool RHO1, bool ALDS>
 __device__ __forceinline__ void fer_mul(FeR<NQ> &r, const FeR<NQ> &a, const FeR<NQ> &b, const RowMod<NQ> &m)
 {
+    static_assert(ROWS > 16 * (NQ - 1) && ROWS <= 16 * NQ, "the limbs in use fill the lanes but for the last one");
+    static_assert(!ALDS || NQ == 1, "the crossbar form is for one limb per lane");
     int32_t a4[NQ], b4[NQ];
 #pragma unroll
     for (int t = 0; t < NQ; t++) {
@@ -136,23 +134,14 @@ __device__ __forceinline__ void fer_mul(FeR<NQ> &r, const FeR<NQ> &a, const FeR<
     }
     // The limbs of 4a reach the lanes of the row one per row of the multiply.  A DPP read of a register that a
     // VALU instruction has just written needs two independent instructions in between; a row has two such places
-    // (multiply-add -> digit broadcast, multiply-add -> hand-over), i.e. four instruction slots, and the requests
-    // for later rows' limbs are what fills them:
-    //   * rows 0 .. ND-1 get their limb by DPP row_newbcast, requested one row ahead (a VALU instruction, ready at
-    //     once: the operand a is only known when the multiply starts);
-    //   * rows ND .. get theirs by ds_swizzle through the LDS crossbar (no VALU issue slot, but ~70 cycles), all
-    //     requested in the slots of the first rows.
-    // ALDS (3 or more wavefronts per SIMD hide the start-up latency): every limb by ds_swizzle, requested up front.
-    static_assert(ROWS > 16 * (NQ - 1) && ROWS <= 16 * NQ, "the limbs in use fill the lanes but for the last one");
-    constexpr int ND = ALDS ? 0 : (GECM_ROW_DPP_ROWS < ROWS ? GECM_ROW_DPP_ROWS : ROWS);
-#ifndef GECM_ROW_OLD_NQ2
-    // (ROWS need not be a multiple of NQ here — 31 rows for 831 bits, 38 for 1023 —; the crossbar variant below wants whole
-    // lanes, so a shape with a partly used last lane runs these rows whatever ALDS says)
-    constexpr bool CROWS = (NQ == 2 || NQ == 3) && ((!ALDS && ND == ROWS) || ROWS % NQ != 0);
-    if constexpr (CROWS) {
-        // Two or three limbs per lane: the multiply-adds are written in C and the compiler places them (it knows how
-        // many instructions lie between a result and the DPP move that reads it; an asm statement counts as none and
-        // is padded).  Two things keep a row at 3 + 2 NQ multiply-adds and 3 DPP moves: the hand-over "16 x high
+    // (multiply-add -> digit broadcast, multiply-add -> hand-over), and the DPP requests for the next row's limbs
+    // are what fills them (a VALU instruction, ready at once: the operand a is only known when the multiply starts).
+    // ALDS (3 or more wavefronts per SIMD hide the ~70 cycles of the crossbar): every limb by ds_swizzle, requested
+    // up front.
+    if constexpr (NQ >= 2) {
+        // Two or three limbs per lane (ROWS need not be a multiple of NQ: 31 rows for 831 bits, 38 for 1023): the
+        // multiply-adds are written in C and the compiler places them (it knows how many instructions lie between a
+        // result and the DPP move that reads it; an asm statement counts as none and is padded).  Two things keep a row at 3 + 2 NQ multiply-adds and 3 DPP moves: the hand-over "16 x high
         // part" multiplies by m.c16, a 16 the compiler cannot see through (it would otherwise spend a shift, a mask
         // and a 64-bit add on it), and the slot the window shift has emptied starts from {lo, 0} as the addend of its
         // first product.  Per row at NQ = 2: 8 VALU instructions and no s_nop where the round-2 form had 9 and two.
@@ -210,7 +199,7 @@ __device__ __forceinline__ void fer_mul(FeR<NQ> &r, const FeR<NQ> &a, const FeR<
                 __builtin_amdgcn_sched_barrier(0);
             }
         });
-        // balanced normalisation as below, in the accumulators' own scale: u16 = 16 x (value + carry + 2^27) has the limb
+        // balanced normalisation, in the accumulators' own scale: u16 = 16 x (value + carry + 2^27) has the limb
         // (+ 2^27) in bits 4..31 of its low register and the carry AS its high register
         int32_t lo[NQ];
         int32_t carry = 0;
@@ -227,157 +216,59 @@ __device__ __forceinline__ void fer_mul(FeR<NQ> &r, const FeR<NQ> &a, const FeR<
         r.v[0] = lo[0] + below;
 #pragma unroll
         for (int t = 1; t < NQ; t++) r.v[t] = lo[t];
-        return;
-    }
-#endif
-    int32_t Ab[ROWS];
-#ifndef GECM_ROW_OLD_NQ2
-    static_assert(CROWS || ROWS % NQ == 0, "these rows rotate the slots back to where they started: whole lanes");
-#endif
-#ifndef GECM_ROW_NO_PAIR_BCAST
-    // One limb per lane, all rows by DPP: the limbs travel TWO per move.  Every lane first takes the limb of the lane
-    // above next to its own (one row_shl:1 per multiply); a 64-bit move (v_mov_b64_dpp, row_newbcast — the one control
-    // it knows) from lane 2k then brings limbs 2k and 2k + 1: 8 moves + 1 instead of 16 for the 416-bit class.
-    constexpr bool PAIRS = NQ == 1 && !ALDS && ND == ROWS;
-    int64_t a01 = 0;
-    if constexpr (PAIRS)
-        a01 = (int64_t)(((uint64_t)row_dpp<GECM_DPP_ROW_SHL1>((uint32_t)a4[0]) << 32) | (uint32_t)a4[0]);
-#else
-    constexpr bool PAIRS = false;
-    const int64_t a01 = 0;
-#endif
-    auto request = [&](auto jc) {
-        constexpr int j = decltype(jc)::value;
-        if constexpr (PAIRS) {
-            if constexpr (j < ROWS && j % 2 == 0) {
+    } else {
+        // One limb per lane.  DPP: the limbs travel TWO per move.  Every lane first takes the limb of the lane above
+        // next to its own (one row_shl:1 per multiply); a 64-bit move (v_mov_b64_dpp, row_newbcast — the one control it
+        // knows) from lane 2k then brings limbs 2k and 2k + 1: 8 moves + 1 instead of 16 for the 416-bit class.
+        int32_t Ab[ROWS];
+        int64_t a01 = 0;
+        if constexpr (!ALDS) a01 = (int64_t)(((uint64_t)row_dpp<GECM_DPP_ROW_SHL1>((uint32_t)a4[0]) << 32) | (uint32_t)a4[0]);
+        auto request = [&](auto jc) {
+            constexpr int j = decltype(jc)::value;
+            if constexpr (ALDS) {
+                Ab[j] = (int32_t)row_bcast_lds<j>((uint32_t)a4[0]);
+            } else if constexpr (j % 2 == 0) {
                 const int64_t P = row_bcast64<j>(a01);
                 Ab[j] = (int32_t)(uint32_t)P;
                 if constexpr (j + 1 < ROWS) Ab[j + 1] = (int32_t)(P >> 32);
             }
-        } else if constexpr (j < ND) Ab[j] = (int32_t)row_bcast<j / NQ>((uint32_t)a4[j % NQ]);
-        else if constexpr (j < ROWS) Ab[j] = (int32_t)row_bcast_lds<j / NQ>((uint32_t)a4[j % NQ]);
-    };
-    // slot plan: row i < ND: first place = DPP request for row i+1 (if that is a DPP row) else one LDS request;
-    // second place = two LDS requests.  Rows >= ND: one LDS request in the first place, two in the second, until
-    // all are out.  LDS requests go out in row order (the crossbar answers in order).
-    if constexpr (ALDS) static_for<0, ROWS>(request);
-    else request(IC<0>{});
-    int64_t T[NQ];                    // 16 x the window; logical slot t of row i lives in T[(t + i) % NQ]
+        };
+        if constexpr (ALDS) static_for<0, ROWS>(request);
+        else request(IC<0>{});
+        // 16 x this lane's slot of the window.  (An array zeroed in a loop rather than a scalar: the compiler schedules
+        // the rows differently when the accumulator is a plain variable from the start.)
+        int64_t T[NQ];
 #pragma unroll
-    for (int t = 0; t < NQ; t++) T[t] = 0;
-    static_for<0, ROWS>([&](auto ic) {
-        constexpr int i = decltype(ic)::value;
-        constexpr int rot = i % NQ, nxt = (i + 1) % NQ;
-        // LDS requests issued before this row: 2 per row in the second place, plus 1 in the first place of every
-        // row from ND-1 on (whose next row is not a DPP row)
-        constexpr int first_lds = (i + 1 < ND) ? 0 : 1;
-        constexpr int before = ND + 2 * i + (i >= ND ? i - ND + 1 : 0);
-        // (the multiply-add into the lowest slot was fused with the previous row's hand-over, except in row 0)
-        if constexpr (i == 0) {
-            if constexpr (NQ == 1) T[0] = smad0(Ab[0], b4[0]);
-            else smad(T[rot], Ab[0], b4[0]);
-        }
-#pragma unroll
-        for (int t = 1; t < NQ; t++) smad(T[(t + rot) % NQ], Ab[i], b4[t]);
-        if constexpr (!ALDS) {
-            __builtin_amdgcn_sched_barrier(0);
-            if constexpr (i + 1 < ND) request(IC<i + 1>{});
-            else request(IC<before>{});
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        uint32_t qs = (uint32_t)T[rot];                     // 16 x (column mod 2^28)
-        if (!RHO1) qs *= m.rho;                             // 16 x the digit (mod 2^32)
-        const uint32_t Q = row_bcast<0>(qs);
-#pragma unroll
-        for (int t = 0; t < NQ; t++) umad(T[(t + rot) % NQ], Q, m.n[t]);
-        if constexpr (!ALDS) {
-            __builtin_amdgcn_sched_barrier(0);
-            request(IC<before + first_lds>{});
-            request(IC<before + first_lds + 1>{});
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        // the window moves down one limb: the low register of the lowest slot (zero on lane 0 by the choice of
-        // the digit) becomes the top slot of the lane below, its high register (the part above 28 bits) is
-        // added, times 16, to this lane's next slot — which is the next row's lowest slot and gets that row's
-        // first product in the same statement
-        const int32_t hi = (int32_t)(T[rot] >> 32);
-        const uint32_t lo = row_dpp<GECM_DPP_ROW_SHL1>((uint32_t)T[rot]);
-        T[rot] = (int64_t)(uint64_t)lo;
-        if constexpr (i + 1 < ROWS) T[nxt] = smad16_smad(hi, T[nxt], Ab[i + 1], b4[0]);
-        else T[nxt] = smad16(hi, T[nxt]);
-    });
-    // balanced normalisation.  Inside the lane the slots still hold whole column sums (only the lowest slot is
-    // folded per row), so the carry runs through them in 64 bits; the top slot is a fresh 28-bit hand-over, so
-    // what leaves the lane is small and goes to the lane above carry-save: limb = centred low 28 bits + carry.
-    if constexpr (NQ == 1) {
-        // in the accumulator's own scale: u16 = 16 x (value + 2^27) has the limb (+ 2^27) in bits 4..31 of its low register
-        // and what leaves the lane AS its high register; the neighbour's carry comes in on the add itself (DPP)
+        for (int t = 0; t < NQ; t++) T[t] = 0;
+        static_for<0, ROWS>([&](auto ic) {
+            constexpr int i = decltype(ic)::value;
+            // (the multiply-add was fused with the previous row's hand-over, except in row 0)
+            if constexpr (i == 0) T[0] = smad0(Ab[0], b4[0]);
+            if constexpr (!ALDS) {
+                __builtin_amdgcn_sched_barrier(0);
+                if constexpr (i + 1 < ROWS) request(IC<i + 1>{});
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            uint32_t qs = (uint32_t)T[0];                       // 16 x (column mod 2^28)
+            if (!RHO1) qs *= m.rho;                             // 16 x the digit (mod 2^32)
+            const uint32_t Q = row_bcast<0>(qs);
+            umad(T[0], Q, m.n[0]);
+            if constexpr (!ALDS) __builtin_amdgcn_sched_barrier(0);    // the hand-over stays after the digit's product
+            // the window moves down one limb: the low register (zero on lane 0 by the choice of the digit) goes to the
+            // lane below, the high register (the part above 28 bits) is added, times 16, to what comes from the lane
+            // above, in the same statement as the next row's first product
+            const int32_t hi = (int32_t)(T[0] >> 32);
+            const uint32_t lo = row_dpp<GECM_DPP_ROW_SHL1>((uint32_t)T[0]);
+            if constexpr (i + 1 < ROWS) T[0] = smad16_smad(hi, (int64_t)(uint64_t)lo, Ab[i + 1], b4[0]);
+            else T[0] = smad16(hi, (int64_t)(uint64_t)lo);
+        });
+        // balanced normalisation in the accumulator's own scale: u16 = 16 x (value + 2^27) has the limb (+ 2^27) in
+        // bits 4..31 of its low register and what leaves the lane AS its high register; the neighbour's carry comes in
+        // on the add itself (DPP)
         const int64_t u16 = T[0] + (int64_t)(1u << 31);
         const int32_t lim = (int32_t)(((uint32_t)u16 >> 4) & GECM_LIMB_MASK) - (1 << 27);
         r.v[0] = lim + (int32_t)row_dpp<GECM_DPP_ROW_SHR1>((uint32_t)(u16 >> 32));
-        return;
     }
-    int32_t lo[NQ];
-    int64_t carry = 0;
-#pragma unroll
-    for (int t = 0; t < NQ - 1; t++) {
-        const int64_t u = (T[t] >> 4) + carry + (1 << 27);
-        carry = u >> GECM_LIMB_BITS;
-        lo[t] = (int32_t)((uint32_t)u & GECM_LIMB_MASK) - (1 << 27);
-    }
-    const int32_t ut = (int32_t)(T[NQ - 1] >> 4) + (int32_t)carry + (1 << 27);
-    lo[NQ - 1] = (int32_t)((uint32_t)ut & GECM_LIMB_MASK) - (1 << 27);
-    const int32_t below = (int32_t)row_dpp<GECM_DPP_ROW_SHR1>((uint32_t)(ut >> GECM_LIMB_BITS));
-    r.v[0] = lo[0] + below;
-#pragma unroll
-    for (int t = 1; t < NQ; t++) r.v[t] = lo[t];
-}
-
-// The same multiply with the limbs of 4a ALREADY in every lane of the row (Ab[j] = 4 x limb j of a): no operand
-// broadcast in the rows at all.  This is what the multiplies of the LDS-prefetch kernel run (run_tape_row_lds below):
-// their broadcast operand is a point form that was written to LDS when the point was made and is read back, four
-// limbs per ds_read_b128 with every lane of a row reading the same address, one multiply ahead of its use.
-template <int NQ, int ROWS, bool RHO1>
-__device__ __forceinline__ void fer_mul_pre(FeR<NQ> &r, const int32_t (&Ab)[ROWS], const FeR<NQ> &b, const RowMod<NQ> &m)
-{
-    static_assert(ROWS % NQ == 0 && ROWS <= 16 * NQ, "whole lanes, at most 16 of them");
-    int32_t b4[NQ];
-#pragma unroll
-    for (int t = 0; t < NQ; t++) b4[t] = (int32_t)((uint32_t)b.v[t] << 2);
-    int64_t T[NQ];
-#pragma unroll
-    for (int t = 0; t < NQ; t++) T[t] = 0;
-    static_for<0, ROWS>([&](auto ic) {
-        constexpr int i = decltype(ic)::value;
-        constexpr int rot = i % NQ, nxt = (i + 1) % NQ;
-        if constexpr (i == 0) smad(T[rot], Ab[0], b4[0]);
-#pragma unroll
-        for (int t = 1; t < NQ; t++) smad(T[(t + rot) % NQ], Ab[i], b4[t]);
-        uint32_t qs = (uint32_t)T[rot];
-        if (!RHO1) qs *= m.rho;
-        const uint32_t Q = row_bcast<0>(qs);
-#pragma unroll
-        for (int t = 0; t < NQ; t++) umad(T[(t + rot) % NQ], Q, m.n[t]);
-        const int32_t hi = (int32_t)(T[rot] >> 32);
-        const uint32_t lo = row_dpp<GECM_DPP_ROW_SHL1>((uint32_t)T[rot]);
-        T[rot] = (int64_t)(uint64_t)lo;
-        if constexpr (i + 1 < ROWS) T[nxt] = smad16_smad(hi, T[nxt], Ab[i + 1], b4[0]);
-        else T[nxt] = smad16(hi, T[nxt]);
-    });
-    int32_t lo[NQ];
-    int64_t carry = 0;
-#pragma unroll
-    for (int t = 0; t < NQ - 1; t++) {
-        const int64_t u = (T[t] >> 4) + carry + (1 << 27);
-        carry = u >> GECM_LIMB_BITS;
-        lo[t] = (int32_t)((uint32_t)u & GECM_LIMB_MASK) - (1 << 27);
-    }
-    const int32_t ut = (int32_t)(T[NQ - 1] >> 4) + (int32_t)carry + (1 << 27);
-    lo[NQ - 1] = (int32_t)((uint32_t)ut & GECM_LIMB_MASK) - (1 << 27);
-    const int32_t below = (int32_t)row_dpp<GECM_DPP_ROW_SHR1>((uint32_t)(ut >> GECM_LIMB_BITS));
-    r.v[0] = lo[0] + below;
-#pragma unroll
-    for (int t = 1; t < NQ; t++) r.v[t] = lo[t];
 }
 
 // A point coordinate as the tape interpreter keeps it: its own limbs and the three combinations with the other
@@ -546,290 +437,18 @@ __device__ __forceinline__ void run_tape_row(const uint32_t *__restrict__ tape, 
     }
 }
 
-// ==== experiment kept for the record (round 3; off unless GECM_ROW_LDS_VARIANT is defined: tools/ab build) ============
-// Measured slower than the DPP kernel above by 3-4 % at 415, 623 and 831 bits and equal at 1023 (4096 curves,
-// profiles/r03/rowp_lds_prefetch_ab_4096_curves.txt, profiles/r03/ab_tape_and_lds_variants.txt): DESIGN.md §5c.
-#ifndef GECM_ROW_WG_WAVES
-#define GECM_ROW_WG_WAVES 4
-#endif
-#ifdef GECM_ROW_LDS_VARIANT
-// The op tape, read two events ahead through the vector memory path: a buffer load with a wave-uniform offset is
-// counted by vmcnt, which nothing else in the loop uses, so it is requested at the top of an event and waited for at its
-// end, for free.  (A scalar load shares lgkmcnt with the LDS requests and returns out of order: with one in flight
-// every LDS wait of the event would have to drain the whole queue, the operand limbs requested for later included.)
-struct TapeAhead {
-#ifndef GECM_ROW_TAPE_SMEM
-    __amdgpu_buffer_rsrc_t rsrc;
-    uint32_t len;
-    uint32_t pend;        // the word holding the byte requested last
-    __device__ __forceinline__ void open(const uint32_t *tape, uint32_t tape_len)
-    {
-        len = tape_len;
-        rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)tape, 0, (int)((tape_len + 3u) & ~3u), 0x00020000);
-        pend = 0;
-    }
-    __device__ __forceinline__ void request(uint32_t pc) { pend = __builtin_amdgcn_raw_buffer_load_b32(rsrc, 0, (int)(pc & ~3u), 0); }
-    __device__ __forceinline__ uint32_t take(uint32_t pc) const      // the byte at pc (the one requested), NOP past the end
-    {
-        const uint32_t b = __builtin_amdgcn_readfirstlane((pend >> ((pc & 3u) * 8u)) & 0xffu);
-        return pc < len ? b : GECM_OP_NOP;
-    }
-#else   // A/B: the scalar load of rounds 1-2, issued when the byte is taken
-    const uint32_t *tp;
-    uint32_t len;
-    __device__ __forceinline__ void open(const uint32_t *tape, uint32_t tape_len) { tp = tape; len = tape_len; }
-    __device__ __forceinline__ void request(uint32_t) {}
-    __device__ __forceinline__ uint32_t take(uint32_t pc) const
-    {
-        if (pc >= len) return GECM_OP_NOP;
-        const uint32_t w = tp[pc >> 2];
-        return __builtin_amdgcn_readfirstlane((w >> ((pc & 3u) * 8u)) & 0xffu);
-    }
-#endif
-};
-
-// ---- the LDS-prefetch variant (BC = 2) ----------------------------------------------------------------------------
-// In a multiply a*b/R' the limbs of ONE operand have to reach all 16 lanes of the row: 16 v_mov_b32_dpp per multiply,
-// a sixth of its VALU instructions, in a kernel that is bound by VALU issue.  Two of the three
-// multiplies of a point addition have an operand that is OLD when the multiply starts:
-//   level 1  (x_B -+ z_B)(x_A +- z_A): one of A, B is the point the previous step made, the other is older;
-//   level 3  (U +- V)^2 * (z_C | x_C): C is two steps old.
-// (The product is the same integer whichever operand is scanned, and so is everything computed from it.)  Those
-// operands are therefore taken from LDS: when a point is made, the three forms the formulas read it in (sd, ds, oth,
-// times 4) go to a slot of LDS — one ds_write per form, LDS pipe — and the multiply that needs one as its broadcast
-// operand reads it back with ds_read_b128, every lane of the row reading the same 16 bytes (a broadcast, no bank
-// conflict), requested ONE MULTIPLY AHEAD so that nothing waits for it.  The squaring in the middle (both operands
-// fresh) and the 14 % of tape events outside the rule-3 loop keep the DPP multiply.
-// tools/lds_bcast_ubench.hip (profiles/r03/lds_bcast_ubench_gfx950.txt): a 16-row body costs 900 cycles per wavefront
-// at two wavefronts per SIMD with the DPP broadcast, 700 with the limbs in registers, 824 with the four reads, their
-// wait and 16 register copies this kernel does not need.
-// LDS holds, per DPP row of the workgroup, GECM_ROW_SLOTS point slots of 3 forms of 16*NQ limbs; a slot is written
-// when its point is made and never changed; A, B, C name slots (wave-uniform numbers) as they name registers.
-#ifndef GECM_ROW_WG_WAVES
-#define GECM_ROW_WG_WAVES 4
-#endif
-#define GECM_ROW_SLOTS 5
-#define GECM_ROW_WG_ROWS (4 * GECM_ROW_WG_WAVES)
-template <int NQ>
-struct RowSlots {
-    int32_t f[GECM_ROW_SLOTS][3][16 * NQ];      // [slot][sd, ds, oth][limb]: one DPP row's points
-};
-
-template <int NQ>
-__device__ __forceinline__ void lds_put_forms(RowSlots<NQ> *L, uint32_t slot, uint32_t l, const PtR<NQ> &p)
-{
-#pragma unroll
-    for (int t = 0; t < NQ; t++) {
-        L->f[slot][0][NQ * l + t] = (int32_t)((uint32_t)p.sd.v[t] << 2);
-        L->f[slot][1][NQ * l + t] = (int32_t)((uint32_t)p.ds.v[t] << 2);
-        L->f[slot][2][NQ * l + t] = (int32_t)((uint32_t)p.oth.v[t] << 2);
-    }
-}
-
-// the first ROWS limbs of one form into every lane: ceil(ROWS/4) reads of 16 bytes at the same address in all lanes
-template <int NQ, int ROWS>
-__device__ __forceinline__ void lds_get_form(int32_t (&Ab)[ROWS], const RowSlots<NQ> *L, uint32_t slot, uint32_t form)
-{
-    typedef int32_t v4 __attribute__((ext_vector_type(4)));
-    const v4 *src = reinterpret_cast<const v4 *>(&L->f[slot][form][0]);
-    constexpr int N4 = (ROWS + 3) / 4;
-#pragma unroll
-    for (int k = 0; k < N4; k++) {
-        const v4 v = src[k];
-        if (4 * k + 0 < ROWS) Ab[4 * k + 0] = v.x;
-        if (4 * k + 1 < ROWS) Ab[4 * k + 1] = v.y;
-        if (4 * k + 2 < ROWS) Ab[4 * k + 2] = v.z;
-        if (4 * k + 3 < ROWS) Ab[4 * k + 3] = v.w;
-    }
-}
-
-// two slots none of A, B, C names (five slots, at most three in use)
-__device__ __forceinline__ void free_slots(uint32_t sA, uint32_t sB, uint32_t sC, uint32_t &f0, uint32_t &f1)
-{
-    uint32_t mask = ~((1u << sA) | (1u << sB) | (1u << sC)) & ((1u << GECM_ROW_SLOTS) - 1u);
-    f0 = (uint32_t)__builtin_ctz(mask);
-    mask &= mask - 1u;
-    f1 = (uint32_t)__builtin_ctz(mask);
-}
-
-template <int NQ, int ROWS>
-__device__ __forceinline__ void run_tape_row_lds(const uint32_t *__restrict__ tape, uint32_t tape_len, PtR<NQ> &A,
-                                                 const FeR<NQ> &s4, bool isZ, const RowSign &g, const RowMod<NQ> &m,
-                                                 RowSlots<NQ> *L, uint32_t l)
-{
-    PtR<NQ> B = A, C = A;
-    uint32_t sA = 0, sB = 0, sC = 0;
-    lds_put_forms<NQ>(L, 0, l, A);
-    auto is_fast = [](uint32_t op) { return (op & ~GECM_OP_SWAP) == (GECM_OP_STEP | GECM_OP_RULE3); };
-    TapeAhead rd;
-    rd.open(tape, tape_len);
-    rd.request(0);
-    uint32_t op = rd.take(0);
-    rd.request(1);
-    uint32_t nxt = rd.take(1);
-    uint32_t pc = 0;
-    while (pc < tape_len) {
-        if (is_fast(op)) {
-            // T = B + A (C); (B, T, C) <- (T, C, B), after the optional exchange of A and B (ecm.c:617-630, 683-713).
-            // Level 1's scanned operand is the OLDER of the two points: the A of before the exchange — its ds form if
-            // the exchange happens (it is B then), its sd form if not.
-            int32_t Ab1[ROWS], Ab3[ROWS];
-            lds_get_form<NQ, ROWS>(Ab1, L, sA, (op & GECM_OP_SWAP) ? 1u : 0u);
-            do {
-                rd.request(pc + 2);
-                const bool sw = (op & GECM_OP_SWAP) != 0;
-                if (sw) {
-                    PtR<NQ> t = A;
-                    A = B;
-                    B = t;
-                    const uint32_t ts = sA;
-                    sA = sB;
-                    sB = ts;
-                }
-                lds_get_form<NQ, ROWS>(Ab3, L, sC, 2u);              // level 3's operand, two multiplies ahead
-                __builtin_amdgcn_sched_barrier(0);
-                FeR<NQ> b1, w, t, e;
-#pragma unroll
-                for (int i = 0; i < NQ; i++) b1.v[i] = sw ? A.sd.v[i] : B.ds.v[i];
-                fer_mul_pre<NQ, ROWS, true>(w, Ab1, b1, m);          // X: U      Z: V
-                fer_other<NQ>(t, w);
-                fer_sum_diff<NQ>(e, t, w, g);                        // X: V + U  Z: U - V
-                __builtin_amdgcn_sched_barrier(0);
-                // the next step's level-1 operand: A stays where it is, the form follows that step's exchange.
-                // Requested whatever the next tape byte is (a branch here would leave the number of LDS requests in
-                // flight unknown to the compiler's wait placement, which then waits for all of them at once).
-                lds_get_form<NQ, ROWS>(Ab1, L, sA, (nxt & GECM_OP_SWAP) ? 1u : 0u);
-                __builtin_amdgcn_sched_barrier(0);
-                fer_mul<NQ, ROWS, true, false>(e, e, e, m);
-                PtR<NQ> T;
-                fer_mul_pre<NQ, ROWS, true>(T.own, Ab3, e, m);
-                row_forms<NQ>(T, g);
-                uint32_t f0, f1;
-                free_slots(sA, sB, sC, f0, f1);
-                lds_put_forms<NQ>(L, f0, l, T);
-                C = B;
-                sC = sB;
-                B = T;
-                sB = f0;
-                pc++;
-                op = nxt;
-                nxt = rd.take(pc + 1);
-            } while (is_fast(op));
-            continue;
-        }
-        rd.request(pc + 2);
-        if (op != GECM_OP_NOP) {
-            const uint32_t rule = op & GECM_OP_RULE_MASK;
-            const bool is_step = op >= GECM_OP_STEP;
-            const bool do_add = op != GECM_OP_PRAC_BEGIN;
-            const bool do_dup = op != GECM_OP_PRAC_END;
-            if (is_step && (op & GECM_OP_SWAP)) {
-                PtR<NQ> t = A;
-                A = B;
-                B = t;
-                const uint32_t ts = sA;
-                sA = sB;
-                sB = ts;
-            }
-            if (is_step && rule == GECM_OP_RULE5) {
-                PtR<NQ> t = B;
-                B = C;
-                C = t;
-                const uint32_t ts = sB;
-                sB = sC;
-                sC = ts;
-            } else if (is_step && rule == GECM_OP_RULE9) {
-                PtR<NQ> t = A;
-                A = B;
-                B = C;
-                C = t;
-                const uint32_t ts = sA;
-                sA = sB;
-                sB = sC;
-                sC = ts;
-            } else if (op == GECM_OP_PRAC_BEGIN) {
-                B = A;
-                C = A;
-                sB = sA;
-                sC = sA;
-            }
-            PtR<NQ> T, D;
-            uint32_t sT, sD;
-            free_slots(sA, sB, sC, sT, sD);
-            if (do_add) {
-                row_add<NQ, ROWS, false>(T, B.ds, A.sd, C.oth, isZ, g, m);
-                lds_put_forms<NQ>(L, sT, l, T);
-            }
-            if (do_dup) {
-                row_dup<NQ, ROWS, false>(D, A.sd, s4, isZ, g, m);
-                lds_put_forms<NQ>(L, sD, l, D);
-            }
-            if (op == GECM_OP_PRAC_END) {
-                A = T;
-                sA = sT;
-            } else if (op == GECM_OP_PRAC_BEGIN) {
-                A = D;
-                sA = sD;
-            } else if (rule == GECM_OP_RULE4) {
-                B = T;
-                sB = sT;
-                A = D;
-                sA = sD;
-            } else if (rule == GECM_OP_RULE5) {
-                PtR<NQ> t = C;
-                const uint32_t ts = sC;
-                C = T;
-                sC = sT;
-                B = t;
-                sB = ts;
-                A = D;
-                sA = sD;
-            } else {
-                PtR<NQ> oldA = C;
-                const uint32_t so = sC;
-                C = T;
-                sC = sT;
-                B = D;
-                sB = sD;
-                A = oldA;
-                sA = so;
-            }
-        }
-        pc++;
-        op = nxt;
-        nxt = rd.take(pc + 1);
-    }
-}
-
-#endif   // GECM_ROW_LDS_VARIANT
-
 // Constants of the row kernel, one array of GECM_ROW_WORDS words per kind, limb j at word j (zero padded):
 //   [0] N' = m*N, = -1 mod 2^28      [1] N      [2] c_in = R'^2 / R mod N (entry conversion: x R -> x R')
 //   [3] R mod N (exit conversion)    [4] K' of N (bias that makes the exit value's limbs non-negative)
 // (GECM_ROW_WORDS, GECM_ROW_KINDS: gecm_rowk.h)
 
 // The whole stage-1 kernel body for one lane.  nl = limbs per residue in the device buffers (R = 2^(28*nl)).
-// BC: how the scanned operand of a multiply reaches the lanes of its row — 0: DPP row_newbcast in the rows' wait
-// states; 1: ds_swizzle, all requested at the top of the multiply (3 or more wavefronts per SIMD); 2: from LDS, read one
-// multiply ahead, in the two multiplies of a point addition whose operand is old (run_tape_row_lds; `slots` = this
-// workgroup's LDS, otherwise unused).
-template <int NQ, int ROWS, int BC>
+// ALDS: the scanned operand of a multiply reaches the lanes of its row through the LDS crossbar (fer_mul).
+template <int NQ, int ROWS, bool ALDS>
 __device__ __forceinline__ void stage1_row(const uint32_t *__restrict__ tape, uint32_t tape_len, uint32_t *__restrict__ X,
                                            uint32_t *__restrict__ Z, const uint32_t *__restrict__ S, size_t stride,
-                                           uint32_t nl, const uint32_t *__restrict__ rc, uint32_t rho_n,
-                                           void *slots_ = nullptr)
+                                           uint32_t nl, const uint32_t *__restrict__ rc, uint32_t rho_n)
 {
-#ifdef GECM_ROW_LDS_VARIANT
-    RowSlots<NQ> *slots = static_cast<RowSlots<NQ> *>(slots_);
-#else
-    (void)slots_;
-#endif
-    constexpr bool ALDS = BC == 1;
-#ifdef GECM_ROW_PRIO
-    // experiment (tools/build_row_variant.sh): with 8 wavefronts per workgroup, wavefronts w and w + 4 share a SIMD;
-    // give one of each pair a higher issue priority so that it runs as if alone and the other fills its gaps
-    if ((threadIdx.x >> 8) & 1u) __builtin_amdgcn_s_setprio(GECM_ROW_PRIO);
-#endif
     const uint32_t cidx = (blockIdx.x * blockDim.x + threadIdx.x) >> 5;      // wavefronts of a workgroup are independent
     const uint32_t l = threadIdx.x & 15u;
     const bool isZ = (threadIdx.x & 16u) != 0;
@@ -860,11 +479,7 @@ __device__ __forceinline__ void stage1_row(const uint32_t *__restrict__ tape, ui
     row_forms<NQ>(P, g);
     fer_load<NQ>(t, S, stride, cidx, l, nl);
     fer_mul<NQ, ROWS, true, ALDS>(s4, t, cin, mp);
-#ifdef GECM_ROW_LDS_VARIANT
-    if constexpr (BC == 2) run_tape_row_lds<NQ, ROWS>(tape, tape_len, P, s4, isZ, g, mp, slots + (threadIdx.x >> 4), l);
-    else
-#endif
-        run_tape_row<NQ, ROWS, ALDS>(tape, tape_len, P, s4, isZ, g, mp);
+    run_tape_row<NQ, ROWS, ALDS>(tape, tape_len, P, s4, isZ, g, mp);
     fer_mul<NQ, ROWS, false, ALDS>(t, P.own, one, mn);                    // x*R' -> x*R (mod N), in (-N/16, 17N/16)
     // + K' (a multiple of N with every limb >= 2^28 - 1): all limbs positive; then one carry-save pass
     uint32_t u[NQ];

@@ -183,7 +183,7 @@ int gecm_get_lanes_per_curve(const gecm_ctx *ctx);
  * cut between two prac() calls; *done of *total have finished.  Callable from the launching thread between
  * gecm_stage1 / gecm_stage1_range and gecm_sync (the reference prints "accumulating prime" every 8192 primes). */
 int gecm_stage1_progress(const gecm_ctx *ctx, uint32_t *done, uint32_t *total);
-/* the stage-1 kernel the last launch ran, by the name rocprofv3 prints for it ("k_stage1_rowp<1, 16>", "k_stage1<15>"):
+/* the stage-1 kernel the last launch ran, by the name rocprofv3 prints for it ("k_stage1_row<1, 16, false>", "k_stage1<15>"):
  * what a profile of the run has to be matched against */
 int gecm_last_kernel_name(const gecm_ctx *ctx, char *buf, size_t len);
 /* milliseconds of the last stage-1 kernel, from HIP events on the context's stream */

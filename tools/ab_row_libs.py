@@ -2,7 +2,7 @@
 """Interleaved A/B of the 32-lane stage-1 kernel between shared libraries (GECM_LIB), separate processes on the same
 GPU box: 4096 curves (AB_CURVES=n for another batch), B1 = 1e5, three passes each (the first discarded), repeated three
 times; save lines compared.
-usage: ab_row_libs.py libA.so libB.so@2 ... [-- bits ...]      (lib@m: GECM_ROW_ALDS=m, the operand-broadcast variant)"""
+usage: ab_row_libs.py libA.so libB.so ... [-- bits ...]"""
 import hashlib, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CODE = r'''
@@ -27,9 +27,7 @@ for bits in bits_list:
     shas = set()
     for rnd in range(3):
         for l in libs:
-            env = dict(os.environ, GECM_LIB=os.path.join(ROOT, "avx-ecm_amd", l.split("@")[0]))
-            if "@" in l:
-                env["GECM_ROW_ALDS"] = l.split("@")[1]
+            env = dict(os.environ, GECM_LIB=os.path.join(ROOT, "avx-ecm_amd", l))
             p = subprocess.run([sys.executable, "-c", CODE % (ROOT, bits)], env=env, capture_output=True, text=True)
             last = p.stdout.strip().splitlines()[-1]
             ms = eval(last.split("]")[0] + "]")

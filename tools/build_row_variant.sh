@@ -1,7 +1,7 @@
 #!/bin/bash
 # Build avx-ecm_amd/libgecm_<name>.so: the shipped objects with the 32-lane stage-1 object (csrc/gecm_rowk.hip)
 # recompiled with extra flags, for A/B runs with tools/ab_row_libs.py (GECM_LIB picks the library).
-# usage: tools/build_row_variant.sh <name> "<extra hipcc flags>"      e.g.  prio8 "-DGECM_ROW_WG_WAVES=8 -DGECM_ROW_PRIO=3"
+# usage: tools/build_row_variant.sh <name> "<extra hipcc flags>"      e.g.  wg8 "-DGECM_ROW_WG_WAVES=8"
 set -e
 cd "$(dirname "$0")/../avx-ecm_amd"
 name=$1; shift
