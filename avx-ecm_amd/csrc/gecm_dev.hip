@@ -1,9 +1,10 @@
 // gecm_dev.hip — device management for libgecm (gfx950 / MI355X only): buffers, stream, events,
-// dispatch to the per-limb-count kernel launchers of gecm_kernels.hip.
+// dispatch to the kernel launchers of gecm_kernels.hip through the two tables of the limb count (gecm_launch.h).
 #include "gecm_dev.h"
 #include "gecm_launch.h"
 #include "gecm_tape.h"
 #include <hip/hip_runtime.h>
+#include <array>
 #include <cstdlib>
 #include <cstdio>
 #include <cstring>
@@ -25,12 +26,34 @@ extern "C" const char *gecm_dev_error(void) { return g_err.c_str(); }
     } while (0)
 
 // ---------------------------------------------------------------- host side
-static const int k_supported_nl[] = {
-#define X(n) n,
+// the kernel tables of every built limb count (gecm_kernels.hip: one accessor per object)
+struct nl_kernels {
+    int nl;
+    const gecm_kernels_p1 *(*p1)(void);
+    const gecm_kernels_p2 *(*p2)(void);
+};
+static const nl_kernels k_kernels[] = {
+#define X(n) {n, gecm_kernels_##n##_p1, gecm_kernels_##n##_p2},
     GECM_NL_LIST(X)
 #undef X
-    0};
-extern "C" const int *gecm_dev_supported_nl(void) { return k_supported_nl; }
+};
+
+static const nl_kernels *kernels_for(int nl)
+{
+    for (const auto &k : k_kernels)
+        if (k.nl == nl) return &k;
+    return nullptr;
+}
+
+extern "C" const int *gecm_dev_supported_nl(void)
+{
+    static const auto nls = [] {
+        std::array<int, sizeof k_kernels / sizeof k_kernels[0] + 1> a{};   // zero-terminated
+        for (size_t i = 0; i + 1 < a.size(); i++) a[i] = k_kernels[i].nl;
+        return a;
+    }();
+    return nls.data();
+}
 
 #ifndef GECM_S2_WAVES_PER_SIMD
 #define GECM_S2_WAVES_PER_SIMD 16         // wavefronts per SIMD a pair-walk launch is cut up for (gecm_dev_s2_init)
@@ -39,6 +62,8 @@ extern "C" const int *gecm_dev_supported_nl(void) { return k_supported_nl; }
 struct gecm_dev {
     int device = 0;
     int nl = 0;
+    const gecm_kernels_p1 *k1 = nullptr;   // the launchers of this limb count
+    const gecm_kernels_p2 *k2 = nullptr;
     std::vector<uint32_t> n, kp, one;
     uint32_t rho = 0;
     size_t ncurves = 0, stride = 0;
@@ -79,22 +104,17 @@ struct gecm_dev {
 #define GECM_MANIFEST "unset"
 #endif
 extern "C" const char *gecm_manifest_rowk(void);
-#define X(n) extern "C" const char *gecm_manifest_k_##n##_p1(void); extern "C" const char *gecm_manifest_k_##n##_p2(void);
-GECM_NL_LIST(X)
-#undef X
 extern "C" const char *gecm_dev_manifest(void)
 {
     static std::string m;
     if (m.empty()) {
         std::string k;
         bool mixed = false;
-#define X(n)                                                                       \
-        for (const char *h : {gecm_manifest_k_##n##_p1(), gecm_manifest_k_##n##_p2()}) { \
-            if (k.empty()) k = h;                                                  \
-            else if (k != h) mixed = true;                                         \
-        }
-        GECM_NL_LIST(X)
-#undef X
+        for (const auto &kt : k_kernels)
+            for (const char *h : {kt.p1()->manifest, kt.p2()->manifest}) {
+                if (k.empty()) k = h;
+                else if (k != h) mixed = true;
+            }
         std::string t = std::string("K:") + (mixed ? "MIXED" : k) + " R:" + gecm_manifest_rowk() + " D:" + GECM_MANIFEST;
 #ifdef GECM_DEV_NL15
         t += " DEV-BUILD(416-bit class only)";
@@ -126,9 +146,8 @@ static gecm_modconst modconst(const gecm_dev *d)
 extern "C" int gecm_dev_open(gecm_dev **out, int device, int nl, const uint32_t *n, const uint32_t *kp,
                              const uint32_t *one, uint32_t rho)
 {
-    bool ok = false;
-    for (const int *p = k_supported_nl; *p; p++) ok |= (*p == nl);
-    if (!ok) {
+    const auto *kt = kernels_for(nl);
+    if (!kt) {
         g_err = "gecm_dev_open: unsupported limb count " + std::to_string(nl);
         return -2;
     }
@@ -145,6 +164,8 @@ extern "C" int gecm_dev_open(gecm_dev **out, int device, int nl, const uint32_t 
     d->device = device;
     d->cus = cus;
     d->nl = nl;
+    d->k1 = kt->p1();
+    d->k2 = kt->p2();
     d->n.assign(n, n + nl);
     d->kp.assign(kp, kp + nl);
     d->one.assign(one, one + nl);
@@ -197,8 +218,8 @@ static void free_s2(gecm_dev *d)
 
 extern "C" void gecm_dev_close(gecm_dev *d)
 {
-    if (d) for (hipEvent_t e : d->cut_events) (void)hipEventDestroy(e);
     if (!d) return;
+    for (hipEvent_t e : d->cut_events) (void)hipEventDestroy(e);
     (void)hipSetDevice(d->device);
     free_state(d);
     free_s2(d);
@@ -381,12 +402,8 @@ extern "C" const char *gecm_dev_last_kernel(gecm_dev *d) { return d->last_kernel
 
 extern "C" int gecm_dev_fform_generic_limbs(int nl)
 {
-    switch (nl) {
-#define X(n) case n: return gecm_fform_generic_limbs_##n();
-        GECM_NL_LIST(X)
-#undef X
-    }
-    return -1;
+    const auto *kt = kernels_for(nl);
+    return kt ? kt->p1()->fform_generic_limbs : -1;
 }
 
 extern "C" void gecm_dev_set_fform(gecm_dev *d, int form) { d->fform = form == 2 ? 2 : form > 0 ? 1 : form < 0 ? -1 : 0; }
@@ -398,29 +415,30 @@ extern "C" int gecm_dev_stage1(gecm_dev *d, int lanes_per_curve)
         g_err = "gecm_dev_stage1: no curves or no tape";
         return -2;
     }
-    if (lanes_per_curve == 0) lanes_per_curve = gecm_dev_auto_lanes(d);
-    if (lanes_per_curve != 1 && lanes_per_curve != 2 && lanes_per_curve != 8 && lanes_per_curve != 32) {
+    const int lanes = lanes_per_curve ? lanes_per_curve : gecm_dev_auto_lanes(d);
+    char nm[96];   // the kernel's name as rocprofv3 prints it
+    if (lanes == 32) {
+        if (d->fform || !d->row_nq) {
+            g_err = "gecm_dev_stage1: no 32-lane kernel for this modulus";
+            return -2;
+        }
+        snprintf(nm, sizeof nm, "k_stage1_row<%d, %d, %s>", d->row_nq, d->row_rows, row_a_lds(d) ? "true" : "false");
+    } else if (lanes == 8) {
+        if (d->fform || !d->dModQ) {
+            g_err = "gecm_dev_stage1: no eight-lane kernel for this modulus";
+            return -2;
+        }
+        snprintf(nm, sizeof nm, "k_stage1_quad<%d>", d->nl);
+    } else if (lanes == 1 || lanes == 2) {
+        if (d->fform) snprintf(nm, sizeof nm, "%s<%d, Mod%c<%d> >", lanes == 2 ? "k_stage1_pair_f" : "k_stage1_f", d->nl,
+                               d->fform == 2 ? 'C' : d->fform > 0 ? 'F' : 'P', d->nl);
+        else snprintf(nm, sizeof nm, "%s<%d>", lanes == 2 ? "k_stage1_pair" : "k_stage1", d->nl);
+    } else {
         g_err = "gecm_dev_stage1: lanes per curve must be 0 (auto), 1, 2, 8 or 32";
         return -2;
     }
-    if (lanes_per_curve == 32 && (d->fform || !d->row_nq)) {
-        g_err = "gecm_dev_stage1: no 32-lane kernel for this modulus";
-        return -2;
-    }
-    if (lanes_per_curve == 8 && (d->fform || !d->dModQ)) {
-        g_err = "gecm_dev_stage1: no eight-lane kernel for this modulus";
-        return -2;
-    }
-    d->last_lanes = lanes_per_curve;
-    {
-        char nm[96];
-        if (lanes_per_curve == 32) snprintf(nm, sizeof nm, "k_stage1_row<%d, %d, %s>", d->row_nq, d->row_rows, row_a_lds(d) ? "true" : "false");
-        else if (lanes_per_curve == 8) snprintf(nm, sizeof nm, "k_stage1_quad<%d>", d->nl);
-        else if (d->fform) snprintf(nm, sizeof nm, "%s<%d, Mod%c<%d> >", lanes_per_curve == 2 ? "k_stage1_pair_f" : "k_stage1_f", d->nl,
-                                    d->fform == 2 ? 'C' : d->fform > 0 ? 'F' : 'P', d->nl);
-        else snprintf(nm, sizeof nm, "%s<%d>", lanes_per_curve == 2 ? "k_stage1_pair" : "k_stage1", d->nl);
-        d->last_kernel = nm;
-    }
+    d->last_lanes = lanes;
+    d->last_kernel = nm;
     gecm_modconst mc = modconst(d);
     HIPCHK(hipEventRecord(d->ev0, d->stream));
     d->cut_launches = d->tape_cuts.size() - 1;
@@ -430,43 +448,18 @@ extern "C" int gecm_dev_stage1(gecm_dev *d, int lanes_per_curve)
         d->cut_events.push_back(e);
     }
     for (size_t cut = 0; cut + 1 < d->tape_cuts.size(); cut++) {
-    const uint32_t *tp = d->dTape + d->tape_cuts[cut] / 4;
-    const uint32_t tl = (uint32_t)(d->tape_cuts[cut + 1] - d->tape_cuts[cut]);
-    switch (d->nl) {
-#define X(n)                                                                                     \
-    case n:                                                                                      \
-        if (lanes_per_curve == 32) {                                                             \
-            if (gecm_launch_stage1_row(d->stream, d->row_nq, d->row_rows, tp, tl,    \
-                                       d->dX, d->dZ, d->dS, d->stride, (uint32_t)d->nl,          \
-                                       d->dRowC, d->rho,                                 \
-                                       row_a_lds(d))) {                                      \
-                g_err = "gecm_dev_stage1: no 32-lane kernel for this limb count";                \
-                return -2;                                                                       \
-            }                                                                                    \
-            gecm_launch_canon_##n(d->stream, &mc, d->dX, d->dZ, d->stride);                      \
-        } else if (lanes_per_curve == 8) {                                                              \
-            if (gecm_launch_stage1_quad_##n(d->stream, &mc, tp, tl,     \
-                                            d->dX, d->dZ, d->dS, d->stride, d->dModQ)) {         \
-                g_err = "gecm_dev_stage1: no eight-lane kernel for this limb count";             \
-                return -2;                                                                       \
-            }                                                                                    \
-        } else if (d->fform)                                                                     \
-            gecm_launch_stage1_f_##n(d->stream, &mc, tp, tl, d->dX,     \
-                                     d->dZ, d->dS, d->stride, lanes_per_curve, d->fform);       \
-        else if (lanes_per_curve == 2)                                                           \
-            gecm_launch_stage1_pair_##n(d->stream, &mc, tp, tl, d->dX,  \
-                                        d->dZ, d->dS, d->stride);                                \
-        else                                                                                     \
-            gecm_launch_stage1_##n(d->stream, &mc, tp, tl, d->dX,       \
-                                   d->dZ, d->dS, d->stride);                                     \
-        break;
-        GECM_NL_LIST(X)
-#undef X
-    default:
-        g_err = "unsupported nl";
-        return -2;
-    }
-    HIPCHK(hipEventRecord(d->cut_events[cut], d->stream));
+        const uint32_t *tp = d->dTape + d->tape_cuts[cut] / 4;
+        const uint32_t tl = (uint32_t)(d->tape_cuts[cut + 1] - d->tape_cuts[cut]);
+        if (lanes == 32) {
+            if (gecm_launch_stage1_row(d->stream, d->row_nq, d->row_rows, tp, tl, d->dX, d->dZ, d->dS, d->stride,
+                                       (uint32_t)d->nl, d->dRowC, d->rho, row_a_lds(d))) {
+                g_err = "gecm_dev_stage1: no 32-lane kernel for this limb count";
+                return -2;
+            }
+        } else
+            d->k1->stage1(d->stream, &mc, tp, tl, d->dX, d->dZ, d->dS, d->stride, d->dModQ, lanes, d->fform);
+        if (lanes >= 8) d->k1->canon(d->stream, &mc, d->dX, d->dZ, d->stride);   // the 8- and 32-lane kernels leave lazy values
+        HIPCHK(hipEventRecord(d->cut_events[cut], d->stream));
     }
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(d->ev1, d->stream));
@@ -514,14 +507,7 @@ extern "C" int gecm_dev_download_plain(gecm_dev *d, uint32_t *x, uint32_t *z)
 {
     HIPCHK(hipSetDevice(d->device));
     gecm_modconst mc = modconst(d);
-    switch (d->nl) {
-#define X(n)                                                                                   \
-    case n:                                                                                    \
-        gecm_launch_from_mont_##n(d->stream, &mc, d->dX, d->dZ, d->dT0, d->dT1, d->stride);    \
-        break;
-        GECM_NL_LIST(X)
-#undef X
-    }
+    d->k1->from_mont(d->stream, &mc, d->dX, d->dZ, d->dT0, d->dT1, d->stride);
     HIPCHK(hipGetLastError());
     if (download_soa(d, x, d->dT0)) return -1;
     if (download_soa(d, z, d->dT1)) return -1;
@@ -533,27 +519,17 @@ extern "C" int gecm_dev_l0(gecm_dev *d, int op, const uint32_t *a, const uint32_
                            uint32_t *dd, size_t count, const uint32_t *fix)
 {
     HIPCHK(hipSetDevice(d->device));
-    size_t keep = d->ncurves;
     if (gecm_dev_resize(d, count)) return -1;
     // reuse the state buffers: X<-a, Z<-b, outputs T0, T1
     if (upload_soa(d, d->dX, a)) return -1;
     if (upload_soa(d, d->dZ, b ? b : a)) return -1;
     gecm_modconst mc = modconst(d);
-    switch (d->nl) {
-#define X(n)                                                                                      \
-    case n:                                                                                       \
-        gecm_launch_l0_##n(d->stream, &mc, op, d->dX, d->dZ, d->dT0, d->dT1, d->stride,           \
-                           fix ? fix : d->one.data());                                            \
-        break;
-        GECM_NL_LIST(X)
-#undef X
-    }
+    d->k1->l0(d->stream, &mc, op, d->dX, d->dZ, d->dT0, d->dT1, d->stride, fix ? fix : d->one.data());
     HIPCHK(hipGetLastError());
     if (download_soa(d, c, d->dT0)) return -1;
     if (op == GECM_L0_ADDSUB && dd)
         if (download_soa(d, dd, d->dT1)) return -1;
     HIPCHK(hipStreamSynchronize(d->stream));
-    (void)keep;
     return 0;
 }
 
@@ -680,7 +656,8 @@ extern "C" int gecm_dev_s2_init(gecm_dev *d, const uint32_t *keep, size_t keep_w
     }
     HIPCHK(hipMemsetAsync(d->dFail, 0, coord * (K > 1 ? K + 1 : 1), d->stream));
     HIPCHK(hipMemsetAsync(d->dPbX, 0, coord, d->stream));        // entry 0 (unused) defined
-    gecm_s2_init_args a;
+    gecm_s2_init_launch L;
+    S2InitArgs &a = L.a;
     a.X = d->dX; a.Z = d->dZ; a.S = d->dS;
     a.PbX = d->dPbX;
     a.bx = d->dBlk; a.bz = d->dBlk + (coord / 4) * GECM_S2_BLK; a.bp = d->dBlk + (coord / 4) * 2 * GECM_S2_BLK;
@@ -696,17 +673,10 @@ extern "C" int gecm_dev_s2_init(gecm_dev *d, const uint32_t *keep, size_t keep_w
         a.kbx = d->dKBlk; a.kbz = d->dKBlk + kw; a.kbp = d->dKBlk + 2 * kw;
         a.PdKX = d->dPdK; a.PdKZ = d->dPdK + coord / 4;
     }
+    L.slices = d->s2_slices;
     gecm_modconst mc = modconst(d);
     HIPCHK(hipEventRecord(d->ev0, d->stream));
-    switch (d->nl) {
-#define X(n)                                             \
-    case n:                                              \
-        gecm_launch_s2_init_##n(d->stream, &mc, &a);     \
-        if (d->s2_slices > 1) gecm_launch_s2_acc_init_##n(d->stream, &mc, d->dAcc, d->s2_slices, d->stride); \
-        break;
-        GECM_NL_LIST(X)
-#undef X
-    }
+    d->k2->s2_init(d->stream, &mc, &L);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(d->ev1, d->stream));
     d->timed = true;
@@ -735,14 +705,15 @@ extern "C" int gecm_dev_s2_pair(gecm_dev *d, const uint32_t *steps, uint32_t nst
         HIPCHK(hipMemcpyAsync(d->dSteps, steps, (size_t)nsteps * 8, hipMemcpyHostToDevice, d->stream));
     d->steps_id = tape_id;
     d->steps_n = nsteps;
-    gecm_s2_pair_args a;
+    gecm_s2_pair_launch L;
+    S2PairArgs &a = L.a;
     a.X = d->dX; a.Z = d->dZ; a.S = d->dS; a.PbX = d->dPbX; a.npb = (uint32_t)d->s2_npb;
     a.PdX = d->dPd; a.PdZ = d->dPd + coord / 4;
     const size_t cw = coord / 4;
     a.gx = d->dPa; a.gz = a.gx + cw * ((size_t)G + 2); a.gp = a.gz + cw * ((size_t)G + 2); a.ring = a.gp + cw * (size_t)G;
-    a.acc = d->dAcc; a.fail = d->dFail; a.steps = d->dSteps; a.host_steps = steps;
+    a.acc = d->dAcc; a.fail = d->dFail; a.steps = d->dSteps; L.host_steps = steps;
     a.nsteps = nsteps; a.D = D; a.G = G; a.ring_size = ring_size; a.A0 = A0; a.stride = d->stride;
-    a.slices = d->s2_slices;
+    L.slices = d->s2_slices;
     a.K = d->s2_K; a.Gs = (uint32_t)(G / d->s2_K + 1);
     a.kgx = a.kgz = a.kgp = nullptr; a.PdKX = a.PdKZ = nullptr;
     if (d->s2_K > 1) {
@@ -752,14 +723,7 @@ extern "C" int gecm_dev_s2_pair(gecm_dev *d, const uint32_t *steps, uint32_t nst
     }
     gecm_modconst mc = modconst(d);
     HIPCHK(hipEventRecord(d->ev0, d->stream));
-    switch (d->nl) {
-#define X(n)                                             \
-    case n:                                              \
-        gecm_launch_s2_pair_##n(d->stream, &mc, &a);     \
-        break;
-        GECM_NL_LIST(X)
-#undef X
-    }
+    d->k2->s2_pair(d->stream, &mc, &L);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(d->ev1, d->stream));
     d->timed = true;
@@ -798,14 +762,7 @@ extern "C" int gecm_dev_gcd_scan(gecm_dev *d, int which, uint32_t *flags, uint32
         d->flags_cap = d->stride;
     }
     gecm_modconst mc = modconst(d);
-    switch (d->nl) {
-#define X(n)                                                                             \
-    case n:                                                                              \
-        gecm_launch_gcd_scan_##n(d->stream, &mc, src, d->dT0, d->dFlags, d->stride);     \
-        break;
-        GECM_NL_LIST(X)
-#undef X
-    }
+    d->k1->gcd_scan(d->stream, &mc, src, d->dT0, d->dFlags, d->stride);
     HIPCHK(hipGetLastError());
     if (flags && d->ncurves)
         HIPCHK(hipMemcpyAsync(flags, d->dFlags, d->ncurves * 4, hipMemcpyDeviceToHost, d->stream));

@@ -7,6 +7,7 @@
 #include "gecm_stage2.hpp"
 #include "gecm_quad.hpp"
 #include <hip/hip_runtime.h>
+#include <type_traits>
 
 #ifndef GECM_NL
 #error "compile with -DGECM_NL=<limbs>"
@@ -278,12 +279,13 @@ __global__ void __launch_bounds__(64, 2) k_s2_merge(uint32_t *acc, uint32_t slic
 }
 
 #endif
-// ---------------------------------------------------------------- launchers (C linkage)
-template <int NL>
-static ModArgs<NL> make_args(const gecm_modconst *mc)
+// ---------------------------------------------------------------- launchers (gecm_launch.h)
+// ModArgs, ModArgsS or S2Const from the host's copy of the modulus constants
+template <class A>
+static A mod_args(const gecm_modconst *mc)
 {
-    ModArgs<NL> a;
-    for (int i = 0; i < NL; i++) {
+    A a;
+    for (int i = 0; i < GECM_NL; i++) {
         a.m.n[i] = mc->n[i];
         a.m.kp[i] = mc->kp[i];
         a.one.v[i] = mc->one[i];
@@ -292,17 +294,10 @@ static ModArgs<NL> make_args(const gecm_modconst *mc)
     return a;
 }
 
-template <int NL>
-static S2Const<NL> make_s2(const gecm_modconst *mc)
+static S2Const<GECM_NL> s2_const(const gecm_modconst *mc)
 {
-    S2Const<NL> k;
-    for (int i = 0; i < NL; i++) {
-        k.m.n[i] = mc->n[i];
-        k.m.kp[i] = mc->kp[i];
-        k.one.v[i] = mc->one[i];
-        k.r3.v[i] = mc->r3[i];
-    }
-    k.m.rho = mc->rho;
+    S2Const<GECM_NL> k = mod_args<S2Const<GECM_NL>>(mc);
+    for (int i = 0; i < GECM_NL; i++) k.r3.v[i] = mc->r3[i];
     k.inv_iters = mc->inv_iters;
     return k;
 }
@@ -314,136 +309,109 @@ static S2Const<NL> make_s2(const gecm_modconst *mc)
 #ifndef GECM_MANIFEST
 #define GECM_MANIFEST "unset"
 #endif
-extern "C" const char *CAT(CAT(CAT(gecm_manifest_k_, GECM_NL), _p), GECM_PART)(void) { return GECM_MANIFEST; }
 
 #if GECM_HAS_PART(1)
-extern "C" void CAT(gecm_launch_stage1_, GECM_NL)(void *stream, const gecm_modconst *mc, const uint32_t *tape,
-                                                   uint32_t tape_len, uint32_t *X, uint32_t *Z,
-                                                   const uint32_t *S, size_t stride)
-{
-    hipLaunchKernelGGL(k_stage1<GECM_NL>, dim3((unsigned)(stride / 64)), dim3(64), 0, (hipStream_t)stream, tape,
-                       tape_len, X, Z, S, stride, make_args<GECM_NL>(mc));
-}
-
+// one or two lanes per curve; MOD = ModK<GECM_NL> for a generic modulus
 template <class MOD>
-static void launch_stage1_special(void *stream, const gecm_modconst *mc, const uint32_t *tape, uint32_t tape_len,
-                                  uint32_t *X, uint32_t *Z, const uint32_t *S, size_t stride, int lanes)
+static void launch_stage1_mod(hipStream_t stream, const gecm_modconst *mc, const uint32_t *tape, uint32_t tape_len,
+                              uint32_t *X, uint32_t *Z, const uint32_t *S, size_t stride, int lanes)
 {
-    ModArgsS<GECM_NL, MOD> a;
-    for (int i = 0; i < GECM_NL; i++) {
-        a.m.n[i] = mc->n[i];
-        a.m.kp[i] = mc->kp[i];
-        a.one.v[i] = mc->one[i];
+    const dim3 grid((unsigned)(stride / (lanes == 2 ? 32 : 64))), block(64);
+    if constexpr (std::is_same<MOD, ModK<GECM_NL>>::value) {
+        const auto a = mod_args<ModArgs<GECM_NL>>(mc);
+        if (lanes == 2) hipLaunchKernelGGL(k_stage1_pair<GECM_NL>, grid, block, 0, stream, tape, tape_len, X, Z, S, stride, a);
+        else hipLaunchKernelGGL(k_stage1<GECM_NL>, grid, block, 0, stream, tape, tape_len, X, Z, S, stride, a);
+    } else {
+        const auto a = mod_args<ModArgsS<GECM_NL, MOD>>(mc);
+        if (lanes == 2) hipLaunchKernelGGL((k_stage1_pair_f<GECM_NL, MOD>), grid, block, 0, stream, tape, tape_len, X, Z, S, stride, a);
+        else hipLaunchKernelGGL((k_stage1_f<GECM_NL, MOD>), grid, block, 0, stream, tape, tape_len, X, Z, S, stride, a);
     }
-    a.m.rho = mc->rho;
-    if (lanes == 2)
-        hipLaunchKernelGGL((k_stage1_pair_f<GECM_NL, MOD>), dim3((unsigned)(stride / 32)), dim3(64), 0,
-                           (hipStream_t)stream, tape, tape_len, X, Z, S, stride, a);
-    else
-        hipLaunchKernelGGL((k_stage1_f<GECM_NL, MOD>), dim3((unsigned)(stride / 64)), dim3(64), 0, (hipStream_t)stream,
-                           tape, tape_len, X, Z, S, stride, a);
 }
 
-/* form: +1 = modulus 2^k - 1 (F-form), -1 = modulus 2^k + 1 (P-form), 2 = modulus 2^k - c (C-form) */
-extern "C" void CAT(gecm_launch_stage1_f_, GECM_NL)(void *stream, const gecm_modconst *mc, const uint32_t *tape,
-                                                     uint32_t tape_len, uint32_t *X, uint32_t *Z,
-                                                     const uint32_t *S, size_t stride, int lanes, int form)
+static void launch_stage1(void *stream, const gecm_modconst *mc, const uint32_t *tape, uint32_t tape_len, uint32_t *X,
+                          uint32_t *Z, const uint32_t *S, size_t stride, const uint32_t *modq, int lanes, int form)
 {
-    if (form == 2) {
-        if constexpr (FPolicy<GECM_NL>::NF >= 3) launch_stage1_special<ModC<GECM_NL>>(stream, mc, tape, tape_len, X, Z, S, stride, lanes);
-    } else if (form > 0) launch_stage1_special<ModF<GECM_NL>>(stream, mc, tape, tape_len, X, Z, S, stride, lanes);
-    else launch_stage1_special<ModP<GECM_NL>>(stream, mc, tape, tape_len, X, Z, S, stride, lanes);
+    const hipStream_t s = (hipStream_t)stream;
+    if (lanes == 8)
+        hipLaunchKernelGGL(k_stage1_quad<GECM_NL>, dim3((unsigned)(stride / 32)), dim3(256), 0, s, tape, tape_len, X, Z, S,   // stride: a multiple of 64
+                           stride, modq, mc->rho);
+    else if (form == 2) {
+        if constexpr (FPolicy<GECM_NL>::NF >= 3) launch_stage1_mod<ModC<GECM_NL>>(s, mc, tape, tape_len, X, Z, S, stride, lanes);
+    } else if (form > 0) launch_stage1_mod<ModF<GECM_NL>>(s, mc, tape, tape_len, X, Z, S, stride, lanes);
+    else if (form < 0) launch_stage1_mod<ModP<GECM_NL>>(s, mc, tape, tape_len, X, Z, S, stride, lanes);
+    else launch_stage1_mod<ModK<GECM_NL>>(s, mc, tape, tape_len, X, Z, S, stride, lanes);
 }
 
-extern "C" int CAT(gecm_fform_generic_limbs_, GECM_NL)(void) { return FPolicy<GECM_NL>::G; }
-
-extern "C" void CAT(gecm_launch_stage1_pair_, GECM_NL)(void *stream, const gecm_modconst *mc, const uint32_t *tape,
-                                                        uint32_t tape_len, uint32_t *X, uint32_t *Z,
-                                                        const uint32_t *S, size_t stride)
-{
-    hipLaunchKernelGGL(k_stage1_pair<GECM_NL>, dim3((unsigned)(stride / 32)), dim3(64), 0, (hipStream_t)stream,
-                       tape, tape_len, X, Z, S, stride, make_args<GECM_NL>(mc));
-}
-
-/* returns 0 if launched, -1 if this limb count has no eight-lane kernel.  modq = device array of 80 words:
- * limbs 0..39 of N then of K' (zero padded), read per lane. */
-extern "C" int CAT(gecm_launch_stage1_quad_, GECM_NL)(void *stream, const gecm_modconst *mc, const uint32_t *tape,
-                                                      uint32_t tape_len, uint32_t *X, uint32_t *Z,
-                                                      const uint32_t *S, size_t stride, const uint32_t *modq)
-{
-    hipLaunchKernelGGL(k_stage1_quad<GECM_NL>, dim3((unsigned)(stride / 32)), dim3(256), 0, (hipStream_t)stream, tape,   // stride: a multiple of 64
-                       tape_len, X, Z, S, stride, modq, mc->rho);
-    hipLaunchKernelGGL(k_canon<GECM_NL>, dim3((unsigned)(stride / 64)), dim3(64), 0, (hipStream_t)stream, X, Z, stride,
-                       make_args<GECM_NL>(mc));
-    return 0;
-}
-
-extern "C" void CAT(gecm_launch_canon_, GECM_NL)(void *stream, const gecm_modconst *mc, uint32_t *X, uint32_t *Z,
-                                                  size_t stride)
+static void launch_canon(void *stream, const gecm_modconst *mc, uint32_t *X, uint32_t *Z, size_t stride)
 {
     hipLaunchKernelGGL(k_canon<GECM_NL>, dim3((unsigned)(stride / 64)), dim3(64), 0, (hipStream_t)stream, X, Z, stride,
-                       make_args<GECM_NL>(mc));
+                       mod_args<ModArgs<GECM_NL>>(mc));
 }
 
-extern "C" void CAT(gecm_launch_from_mont_, GECM_NL)(void *stream, const gecm_modconst *mc, const uint32_t *X,
-                                                      const uint32_t *Z, uint32_t *ox, uint32_t *oz,
-                                                      size_t stride)
+static void launch_from_mont(void *stream, const gecm_modconst *mc, const uint32_t *X, const uint32_t *Z, uint32_t *ox,
+                             uint32_t *oz, size_t stride)
 {
     hipLaunchKernelGGL(k_from_mont<GECM_NL>, dim3((unsigned)(stride / 64)), dim3(64), 0, (hipStream_t)stream, X, Z,
-                       ox, oz, stride, make_args<GECM_NL>(mc));
+                       ox, oz, stride, mod_args<ModArgs<GECM_NL>>(mc));
 }
 
-extern "C" void CAT(gecm_launch_l0_, GECM_NL)(void *stream, const gecm_modconst *mc, int op, const uint32_t *A,
-                                               const uint32_t *B, uint32_t *C, uint32_t *D, size_t stride,
-                                               const uint32_t *fix)
+static void launch_l0(void *stream, const gecm_modconst *mc, int op, const uint32_t *A, const uint32_t *B, uint32_t *C,
+                      uint32_t *D, size_t stride, const uint32_t *fix)
 {
     Fe<GECM_NL> f;
     for (int i = 0; i < GECM_NL; i++) f.v[i] = fix[i];
     hipLaunchKernelGGL(k_l0<GECM_NL>, dim3((unsigned)(stride / 64)), dim3(64), 0, (hipStream_t)stream, op, A, B, C,
-                       D, stride, make_args<GECM_NL>(mc), f);
+                       D, stride, mod_args<ModArgs<GECM_NL>>(mc), f);
+}
+
+static void launch_gcd_scan(void *stream, const gecm_modconst *mc, const uint32_t *V, uint32_t *G, uint32_t *flags,
+                            size_t stride)
+{
+    hipLaunchKernelGGL(k_gcd_scan<GECM_NL>, dim3((unsigned)(stride / 64)), dim3(64), 0, (hipStream_t)stream, V, G, flags,
+                       stride, s2_const(mc));
+}
+
+extern "C" const gecm_kernels_p1 *CAT(CAT(gecm_kernels_, GECM_NL), _p1)(void)
+{
+    static const gecm_kernels_p1 t = {launch_stage1, launch_canon, launch_from_mont, launch_l0, launch_gcd_scan,
+                                      FPolicy<GECM_NL>::G, GECM_MANIFEST};
+    return &t;
 }
 #endif
 #if GECM_HAS_PART(2)
-extern "C" void CAT(gecm_launch_s2_init_, GECM_NL)(void *stream, const gecm_modconst *mc, const gecm_s2_init_args *h)
+static void launch_s2_init(void *stream, const gecm_modconst *mc, const gecm_s2_init_launch *h)
 {
-    S2InitArgs a;
-    a.X = h->X; a.Z = h->Z; a.S = h->S; a.PbX = h->PbX; a.bx = h->bx; a.bz = h->bz; a.bp = h->bp;
-    a.PdX = h->PdX; a.PdZ = h->PdZ; a.acc = h->acc; a.fail = h->fail; a.keep = h->keep;
-    a.umax = h->umax; a.D = h->D; a.npb = h->npb; a.stride = h->stride;
-    a.K = h->K; a.tgt = h->tgt; a.tgt_off = h->tgt_off; a.kbx = h->kbx; a.kbz = h->kbz; a.kbp = h->kbp;
-    a.PdKX = h->PdKX; a.PdKZ = h->PdKZ;
-    if (h->K > 1)
-        hipLaunchKernelGGL(k_s2_init_k<GECM_NL>, dim3((unsigned)(h->stride / 64 * h->K)), dim3(64), 0, (hipStream_t)stream, a,
-                           make_s2<GECM_NL>(mc));
+    const S2InitArgs &a = h->a;
+    const S2Const<GECM_NL> k = s2_const(mc);
+    const dim3 grid((unsigned)(a.stride / 64)), block(64);
+    if (a.K > 1)
+        hipLaunchKernelGGL(k_s2_init_k<GECM_NL>, dim3((unsigned)(a.stride / 64 * a.K)), block, 0, (hipStream_t)stream, a, k);
     else
-        hipLaunchKernelGGL(k_s2_init<GECM_NL>, dim3((unsigned)(h->stride / 64)), dim3(64), 0, (hipStream_t)stream, a,
-                           make_s2<GECM_NL>(mc));
+        hipLaunchKernelGGL(k_s2_init<GECM_NL>, grid, block, 0, (hipStream_t)stream, a, k);
+    // the pair walk's other accumulators (slice 0 is acc itself, set by the table build)
+    if (h->slices > 1)
+        hipLaunchKernelGGL(k_s2_merge<GECM_NL>, grid, block, 0, (hipStream_t)stream, a.acc, h->slices, a.stride, 1, k);
 }
 
-extern "C" void CAT(gecm_launch_s2_pair_, GECM_NL)(void *stream, const gecm_modconst *mc, const gecm_s2_pair_args *h)
+static void launch_s2_pair(void *stream, const gecm_modconst *mc, const gecm_s2_pair_launch *h)
 {
-    S2PairArgs a;
-    a.X = h->X; a.Z = h->Z; a.S = h->S; a.PbX = h->PbX; a.npb = h->npb; a.PdX = h->PdX; a.PdZ = h->PdZ;
-    a.gx = h->gx; a.gz = h->gz; a.gp = h->gp; a.ring = h->ring; a.acc = h->acc; a.fail = h->fail;
-    a.steps = h->steps; a.nsteps = h->nsteps; a.D = h->D; a.G = h->G; a.ring_size = h->ring_size; a.A0 = h->A0;
-    a.stride = h->stride;
-    a.K = h->K; a.Gs = h->Gs; a.kgx = h->kgx; a.kgz = h->kgz; a.kgp = h->kgp; a.PdKX = h->PdKX; a.PdKZ = h->PdKZ;
+    const S2PairArgs &a = h->a;
     // the tape on the host decides the launch sequence: one k_s2_gen per "generate" mark, one
     // k_s2_pairs per run of pairs between marks (~84 + 84 launches per 1e8 range)
-    const dim3 grid((unsigned)(h->stride / 64)), block(64);
-    const dim3 pgrid((unsigned)(h->stride / 64), h->slices ? h->slices : 1);
-    const S2Const<GECM_NL> k = make_s2<GECM_NL>(mc);
+    const dim3 grid((unsigned)(a.stride / 64)), block(64);
+    const dim3 pgrid((unsigned)(a.stride / 64), h->slices ? h->slices : 1);
+    const S2Const<GECM_NL> k = s2_const(mc);
     // a "generate" mark with bit 31 set in its count is a single-chain chunk (the reference's last batch of the range,
-    // gecm_stage2_pair); the others use K sub-sequences per curve when the batch is small (h->K > 1)
-    const dim3 kgrid((unsigned)(h->stride / 64 * (h->K ? h->K : 1)));
+    // gecm_stage2_pair); the others use K sub-sequences per curve when the batch is small (a.K > 1)
+    const dim3 kgrid((unsigned)(a.stride / 64 * (a.K ? a.K : 1)));
     uint32_t generated = 0, i = 0, kprev = 1;
-    while (i < h->nsteps) {
+    while (i < a.nsteps) {
         if (h->host_steps[2 * i] == S2_STEP_GEN) {
             const uint32_t word = h->host_steps[2 * i + 1];
             const uint32_t n = word & 0x7fffffffu;
-            if (h->K > 1 && !(word & 0x80000000u)) {
+            if (a.K > 1 && !(word & 0x80000000u)) {
                 hipLaunchKernelGGL(k_s2_gen_k<GECM_NL>, kgrid, block, 0, (hipStream_t)stream, a, generated, n, k);
-                kprev = h->K;
+                kprev = a.K;
             } else {
                 hipLaunchKernelGGL(k_s2_gen<GECM_NL>, grid, block, 0, (hipStream_t)stream, a, generated, n, generated ? kprev : 1u, k);
                 kprev = 1;
@@ -452,27 +420,18 @@ extern "C" void CAT(gecm_launch_s2_pair_, GECM_NL)(void *stream, const gecm_modc
             i++;
         } else {
             uint32_t j = i;
-            while (j < h->nsteps && h->host_steps[2 * j] != S2_STEP_GEN) j++;
+            while (j < a.nsteps && h->host_steps[2 * j] != S2_STEP_GEN) j++;
             hipLaunchKernelGGL(k_s2_pairs<GECM_NL>, pgrid, block, 0, (hipStream_t)stream, a, i, j - i, k);
             i = j;
         }
     }
     if (h->slices > 1)
-        hipLaunchKernelGGL(k_s2_merge<GECM_NL>, grid, block, 0, (hipStream_t)stream, h->acc, h->slices, h->stride, 0, k);
+        hipLaunchKernelGGL(k_s2_merge<GECM_NL>, grid, block, 0, (hipStream_t)stream, a.acc, h->slices, a.stride, 0, k);
 }
 
-extern "C" void CAT(gecm_launch_s2_acc_init_, GECM_NL)(void *stream, const gecm_modconst *mc, uint32_t *acc,
-                                                        uint32_t slices, size_t stride)
+extern "C" const gecm_kernels_p2 *CAT(CAT(gecm_kernels_, GECM_NL), _p2)(void)
 {
-    hipLaunchKernelGGL(k_s2_merge<GECM_NL>, dim3((unsigned)(stride / 64)), dim3(64), 0, (hipStream_t)stream, acc, slices,
-                       stride, 1, make_s2<GECM_NL>(mc));
-}
-#endif
-#if GECM_HAS_PART(1)
-extern "C" void CAT(gecm_launch_gcd_scan_, GECM_NL)(void *stream, const gecm_modconst *mc, const uint32_t *V,
-                                                     uint32_t *G, uint32_t *flags, size_t stride)
-{
-    hipLaunchKernelGGL(k_gcd_scan<GECM_NL>, dim3((unsigned)(stride / 64)), dim3(64), 0, (hipStream_t)stream, V, G, flags,
-                       stride, make_s2<GECM_NL>(mc));
+    static const gecm_kernels_p2 t = {launch_s2_init, launch_s2_pair, GECM_MANIFEST};
+    return &t;
 }
 #endif

@@ -1,11 +1,9 @@
-/* gecm_launch.h — per-limb-count kernel launchers (one object file per GECM_NL). */
+/* gecm_launch.h — the kernel launchers of one limb count (gecm_kernels.hip, two objects per GECM_NL), reached through
+ * one table of function pointers per object, and the stage-2 kernel arguments they pass on. */
 #ifndef GECM_LAUNCH_H
 #define GECM_LAUNCH_H
 #include <stddef.h>
 #include <stdint.h>
-#ifdef __cplusplus
-extern "C" {
-#endif
 
 /* limb counts built into the library; keep in sync with the Makefile's NLS */
 #ifdef GECM_DEV_NL15
@@ -19,65 +17,88 @@ typedef struct {
     uint32_t rho, inv_iters;
 } gecm_modconst;
 
-typedef struct {
-    const uint32_t *X, *Z, *S;
-    uint32_t *PbX, *bx, *bz, *bp, *PdX, *PdZ, *acc, *fail;
-    const uint32_t *keep;
+/* Stage-2 kernel arguments (csrc/gecm_stage2.hpp), passed by value: the type names are part of the kernel symbols. */
+struct S2InitArgs {
+    const uint32_t *X, *Z, *S;       // Q = P after stage 1 (Montgomery form), s = (A+2)/4
+    uint32_t *PbX;                   // out: normalised baby steps, entries 0..npb-1 (0 unused)
+    uint32_t *bx, *bz, *bp;          // block scratch, S2_BLK entries each
+    uint32_t *PdX, *PdZ;             // out: Pd = [D]Q
+    uint32_t *acc;                   // out: accumulator = one
+    uint32_t *fail;                  // per-curve gcd record of a failed inversion (zeroed by host)
+    const uint32_t *keep;            // bitmap over j: bit j set iff map[j] > 0
     uint32_t umax, D, npb;
     size_t stride;
-    /* K > 1: K sub-sequences per curve (csrc/gecm_stage2.hpp, s2_init_k) */
+    // K sub-sequences per curve (small batches, s2_init_k): table index of the i-th kept member of sub-sequence r
+    // at tgt[tgt_off[r] + i]; block scratch kbx/kbz/kbp per (curve block, r); PdK = [K*D]Q for the giant steps
     uint32_t K;
     const uint32_t *tgt, *tgt_off;
-    uint32_t *kbx, *kbz, *kbp, *PdKX, *PdKZ;
-} gecm_s2_init_args;
+    uint32_t *kbx, *kbz, *kbp;
+    uint32_t *PdKX, *PdKZ;
+};
 
-typedef struct {
-    const uint32_t *X, *Z, *S, *PbX, *PdX, *PdZ;
+struct S2PairArgs {
+    const uint32_t *X, *Z, *S;       // Q, s
+    const uint32_t *PbX;             // normalised baby steps
     uint32_t npb;
-    uint32_t *gx, *gz, *gp, *ring, *acc, *fail;
-    const uint32_t *steps;        /* device copy of the tape */
-    const uint32_t *host_steps;   /* host copy: the launcher splits it at the "generate" marks */
+    const uint32_t *PdX, *PdZ;       // Pd = [D]Q
+    uint32_t *gx, *gz;               // chunk scratch: X, Z of the giant steps being generated, G+2 entries
+                                     // (entries 0,1 = the last two steps of the previous chunk)
+    uint32_t *gp;                    // prefix products, G entries
+    uint32_t *ring;                  // X/Z of the giant steps, ring of `ring_size` entries (power of two)
+    uint32_t *acc;                   // in/out accumulator
+    uint32_t *fail;
+    const uint32_t *steps;           // pair tape, 2 words per step (see S2_STEP_GEN)
     uint32_t nsteps, D, G, ring_size;
-    uint32_t slices;              /* accumulators per curve: each run of pairs is cut into this many slices */
-    uint64_t A0;
+    uint64_t A0;                     // multiplier of the first giant step: 2*amin*D   ecm.c:2378
     size_t stride;
-    /* K > 1: giant steps with K sub-sequences per curve (giant_chunk_k); Gs = entries per sub-sequence and chunk */
+    // K sub-sequences per curve (giant_chunk_k): scratch per (curve block, r) with Gs + 2 / Gs entries, the stride
+    // point [K*D]Q, and one failure plane per sub-sequence after plane 0
     uint32_t K, Gs;
     uint32_t *kgx, *kgz, *kgp;
     const uint32_t *PdKX, *PdKZ;
-} gecm_s2_pair_args;
+};
 
-#define GECM_DECL(nl)                                                                                     \
-    void gecm_launch_stage1_##nl(void *stream, const gecm_modconst *mc, const uint32_t *tape,             \
-                                 uint32_t tape_len, uint32_t *X, uint32_t *Z, const uint32_t *S,          \
-                                 size_t stride);                                                          \
-    void gecm_launch_stage1_pair_##nl(void *stream, const gecm_modconst *mc, const uint32_t *tape,        \
-                                      uint32_t tape_len, uint32_t *X, uint32_t *Z, const uint32_t *S,     \
-                                      size_t stride);                                                     \
-    void gecm_launch_stage1_f_##nl(void *stream, const gecm_modconst *mc, const uint32_t *tape,           \
-                                   uint32_t tape_len, uint32_t *X, uint32_t *Z, const uint32_t *S,        \
-                                   size_t stride, int lanes, int form);                                   \
-    int gecm_launch_stage1_quad_##nl(void *stream, const gecm_modconst *mc, const uint32_t *tape,         \
-                                     uint32_t tape_len, uint32_t *X, uint32_t *Z, const uint32_t *S,      \
-                                     size_t stride, const uint32_t *modq);                                \
-    void gecm_launch_canon_##nl(void *stream, const gecm_modconst *mc, uint32_t *X, uint32_t *Z,          \
-                                size_t stride);                                                           \
-    int gecm_fform_generic_limbs_##nl(void);                                                              \
-    void gecm_launch_from_mont_##nl(void *stream, const gecm_modconst *mc, const uint32_t *X,             \
-                                    const uint32_t *Z, uint32_t *ox, uint32_t *oz, size_t stride);        \
-    void gecm_launch_l0_##nl(void *stream, const gecm_modconst *mc, int op, const uint32_t *A,            \
-                             const uint32_t *B, uint32_t *C, uint32_t *D, size_t stride,                  \
-                             const uint32_t *fix);                                                        \
-    void gecm_launch_s2_init_##nl(void *stream, const gecm_modconst *mc, const gecm_s2_init_args *h);     \
-    void gecm_launch_s2_pair_##nl(void *stream, const gecm_modconst *mc, const gecm_s2_pair_args *h);     \
-    void gecm_launch_s2_acc_init_##nl(void *stream, const gecm_modconst *mc, uint32_t *acc,               \
-                                      uint32_t slices, size_t stride);                                    \
-    void gecm_launch_gcd_scan_##nl(void *stream, const gecm_modconst *mc, const uint32_t *V, uint32_t *G, \
-                                   uint32_t *flags, size_t stride);
-GECM_NL_LIST(GECM_DECL)
-#undef GECM_DECL
+/* what the stage-2 launchers need besides the kernel arguments */
+struct gecm_s2_init_launch {
+    S2InitArgs a;
+    uint32_t slices;              /* accumulators per curve: with more than one, the launcher also sets them to one */
+};
 
-#ifdef __cplusplus
-}
-#endif
+struct gecm_s2_pair_launch {
+    S2PairArgs a;
+    const uint32_t *host_steps;   /* host copy of the tape: the launcher splits it at the "generate" marks */
+    uint32_t slices;              /* accumulators per curve: each run of pairs is cut into this many slices */
+};
+
+/* Part 1: stage 1, canonical form, de-Montgomeryisation, L0 operators, factor scan. */
+struct gecm_kernels_p1 {
+    /* lanes per curve 1 or 2 (form: 0 = generic modulus, +1 = 2^k - 1, -1 = 2^k + 1, 2 = 2^k - c), or 8 (generic
+     * moduli only; modq = device array of 80 words: limbs 0..39 of N then of K', zero padded, read per lane).  The
+     * eight-lane kernel leaves lazy values in X, Z: run canon afterwards. */
+    void (*stage1)(void *stream, const gecm_modconst *mc, const uint32_t *tape, uint32_t tape_len, uint32_t *X,
+                   uint32_t *Z, const uint32_t *S, size_t stride, const uint32_t *modq, int lanes, int form);
+    void (*canon)(void *stream, const gecm_modconst *mc, uint32_t *X, uint32_t *Z, size_t stride);
+    void (*from_mont)(void *stream, const gecm_modconst *mc, const uint32_t *X, const uint32_t *Z, uint32_t *ox,
+                      uint32_t *oz, size_t stride);
+    void (*l0)(void *stream, const gecm_modconst *mc, int op, const uint32_t *A, const uint32_t *B, uint32_t *C,
+               uint32_t *D, size_t stride, const uint32_t *fix);
+    void (*gcd_scan)(void *stream, const gecm_modconst *mc, const uint32_t *V, uint32_t *G, uint32_t *flags,
+                     size_t stride);
+    int fform_generic_limbs;      /* limbs of a 2^k -+ c modulus that are not 2^28 - 1 */
+    const char *manifest;         /* the hash of the sources the object was compiled from (Makefile: K_SHA) */
+};
+
+/* Part 2: stage 2. */
+struct gecm_kernels_p2 {
+    void (*s2_init)(void *stream, const gecm_modconst *mc, const gecm_s2_init_launch *h);
+    void (*s2_pair)(void *stream, const gecm_modconst *mc, const gecm_s2_pair_launch *h);
+    const char *manifest;
+};
+
+/* the accessors: gecm_kernels_<nl>_p1 and _p2, one in each object */
+#define GECM_KERNELS_DECL(nl)                                         \
+    extern "C" const gecm_kernels_p1 *gecm_kernels_##nl##_p1(void);   \
+    extern "C" const gecm_kernels_p2 *gecm_kernels_##nl##_p2(void);
+GECM_NL_LIST(GECM_KERNELS_DECL)
+#undef GECM_KERNELS_DECL
 #endif

@@ -11,7 +11,8 @@ extern "C" {
 
 /* 32 lanes per curve (csrc/gecm_row.hpp, gecm_rowk.hip): nq = limbs per lane, rows = rows of a multiply = limbs in use
  * (the nl + 1 limbs of N' = m*N: 831 bits are 31 rows), nl = limbs per residue of the device buffers, rc = device array
- * of GECM_ROW_KINDS x GECM_ROW_WORDS constants.  Leaves lazy values in X, Z (run gecm_launch_canon_<nl> afterwards).
+ * of GECM_ROW_KINDS x GECM_ROW_WORDS constants.  Leaves lazy values in X, Z (run k_canon afterwards: canon of
+ * gecm_launch.h's part-1 table).
  * a_lds: operand limbs are broadcast through the LDS crossbar instead of DPP (faster from 3 wavefronts per SIMD
  * up; nq = 1 only).  Returns -1 if (nq, rows) is not built, or if a_lds is set and nq != 1. */
 #define GECM_ROW_WORDS 48     /* words per constant array: limbs 0 .. 16*nq-1, zero padded */

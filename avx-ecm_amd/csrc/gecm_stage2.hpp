@@ -23,6 +23,7 @@
 //     ecm.c:2458-2502: 1,341 inversions at B2 = 1e8; here 84 + 31 for the table).
 #pragma once
 #include "gecm_curve.hpp"
+#include "gecm_launch.h"      // S2InitArgs, S2PairArgs
 
 #define S2_BLK 256
 
@@ -424,24 +425,6 @@ __device__ __forceinline__ void pt_ladder(Pt<NL> &P, uint64_t c, const Fe<NL> &s
     else pt_ladder_body(P, c, s4, m, m);
 }
 
-struct S2InitArgs {
-    const uint32_t *X, *Z, *S;       // Q = P after stage 1 (Montgomery form), s = (A+2)/4
-    uint32_t *PbX;                   // out: normalised baby steps, entries 0..npb-1 (0 unused)
-    uint32_t *bx, *bz, *bp;          // block scratch, S2_BLK entries each
-    uint32_t *PdX, *PdZ;             // out: Pd = [D]Q
-    uint32_t *acc;                   // out: accumulator = one
-    uint32_t *fail;                  // per-curve gcd record of a failed inversion (zeroed by host)
-    const uint32_t *keep;            // bitmap over j: bit j set iff map[j] > 0
-    uint32_t umax, D, npb;
-    size_t stride;
-    // K sub-sequences per curve (small batches, s2_init_k): table index of the i-th kept member of sub-sequence r
-    // at tgt[tgt_off[r] + i]; block scratch kbx/kbz/kbp per (curve block, r); PdK = [K*D]Q for the giant steps
-    uint32_t K;
-    const uint32_t *tgt, *tgt_off;
-    uint32_t *kbx, *kbz, *kbp;
-    uint32_t *PdKX, *PdKZ;
-};
-
 // ecm_stage2_init, ecm.c:2201-2340
 template <int NL>
 __device__ __forceinline__ void s2_init(const S2InitArgs &a, const S2Const<NL> &k, uint32_t idx)
@@ -559,28 +542,6 @@ __device__ __forceinline__ void s2_init_k(const S2InitArgs &a, const S2Const<NL>
         fe_store(a.acc, stride, idx, k.one);        // acc = one   ecm.c:2318
     }
 }
-
-struct S2PairArgs {
-    const uint32_t *X, *Z, *S;       // Q, s
-    const uint32_t *PbX;             // normalised baby steps
-    uint32_t npb;
-    const uint32_t *PdX, *PdZ;       // Pd = [D]Q
-    uint32_t *gx, *gz;               // chunk scratch: X, Z of the giant steps being generated, G+2 entries
-                                     // (entries 0,1 = the last two steps of the previous chunk)
-    uint32_t *gp;                    // prefix products, G entries
-    uint32_t *ring;                  // X/Z of the giant steps, ring of `ring_size` entries (power of two)
-    uint32_t *acc;                   // in/out accumulator
-    uint32_t *fail;
-    const uint32_t *steps;           // pair tape, 2 words per step (see S2_STEP_GEN)
-    uint32_t nsteps, D, G, ring_size;
-    uint64_t A0;                     // multiplier of the first giant step: 2*amin*D   ecm.c:2378
-    size_t stride;
-    // K sub-sequences per curve (giant_chunk_k): scratch per (curve block, r) with Gs + 2 / Gs entries, the stride
-    // point [K*D]Q, and one failure plane per sub-sequence after plane 0
-    uint32_t K, Gs;
-    uint32_t *kgx, *kgz, *kgp;
-    const uint32_t *PdKX, *PdKZ;
-};
 
 // tape word 0 == S2_STEP_GEN: generate the next `word 1` giant steps (continuing the sequence) and
 // normalise them into the ring.  Otherwise (slot, pb): acc *= ring[slot] - PbX[pb].
