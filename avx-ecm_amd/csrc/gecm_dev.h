@@ -72,6 +72,17 @@ int gecm_dev_download_plain(gecm_dev *d, uint32_t *x, uint32_t *z);
 int gecm_dev_l0(gecm_dev *d, int op, const uint32_t *a, const uint32_t *b, uint32_t *c, uint32_t *dd,
                 size_t count, const uint32_t *fix);
 
+/* ---- multi-modulus batches ----
+ * gecm_dev_set_multi: from now on every launch of this context takes its modulus per 64-curve block from the group
+ * tables, with 1 or 2 lanes per curve and one stage-2 sub-sequence per curve; the L0 operators are refused.  Call it
+ * right after gecm_dev_open.
+ * gecm_dev_set_groups: after gecm_dev_resize, the constants of ngroups moduli (n, kp, one, r3: nl limbs each,
+ * modulus g at [g*nl]; rho, inv_iters: one word each) and the modulus of every 64-curve block of the batch
+ * (stride / 64 entries, each < ngroups).  Copied before it returns. */
+void gecm_dev_set_multi(gecm_dev *d);
+int gecm_dev_set_groups(gecm_dev *d, uint32_t ngroups, const uint32_t *n, const uint32_t *kp, const uint32_t *one,
+                        const uint32_t *r3, const uint32_t *rho, const uint32_t *inv_iters, const uint32_t *block_group);
+
 /* ---- stage 2 (csrc/gecm_stage2.hpp) ----
  * r3 = R^3 mod N (28-bit limbs); inv_iters = batches of 28 division steps of the device inversion (fe_invert). */
 int gecm_dev_set_s2const(gecm_dev *d, const uint32_t *r3, uint32_t inv_iters);

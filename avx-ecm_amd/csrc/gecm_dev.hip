@@ -97,6 +97,12 @@ struct gecm_dev {
     int cus = 0;          // compute units of the device (4 SIMDs each)
     int last_lanes = 0;   // lanes per curve the last stage-1 launch used
     std::string last_kernel;   // and the kernel's name as rocprofv3 prints it
+    // multi-modulus context (gecm_dev_set_multi): one modulus per 64-curve block, constants in device memory
+    bool multi = false;
+    void *dGroups = nullptr;          // one packed constant set per modulus (gecm_kernels_p1::pack_group)
+    uint32_t *dBlockGroup = nullptr;  // modulus of every 64-curve block of the batch
+    size_t groups_cap = 0, blocks_cap = 0;
+    bool have_groups = false;
 };
 
 // ---- source manifest (Makefile): "K:<hash of the kernel objects' sources, or MIXED> R:<rowk> D:<this file>"
@@ -140,6 +146,8 @@ static gecm_modconst modconst(const gecm_dev *d)
     mc.r3 = d->r3.empty() ? d->one.data() : d->r3.data();
     mc.rho = d->rho;
     mc.inv_iters = d->inv_iters;
+    mc.groups = d->multi ? d->dGroups : nullptr;
+    mc.block_group = d->multi ? d->dBlockGroup : nullptr;
     return mc;
 }
 
@@ -229,6 +237,8 @@ extern "C" void gecm_dev_close(gecm_dev *d)
     (void)hipFree(d->dSteps);
     (void)hipFree(d->dFlags);
     (void)hipFree(d->dTape);
+    (void)hipFree(d->dGroups);
+    (void)hipFree(d->dBlockGroup);
     if (d->ev0) (void)hipEventDestroy(d->ev0);
     if (d->ev1) (void)hipEventDestroy(d->ev1);
     if (d->stream) (void)hipStreamDestroy(d->stream);
@@ -272,6 +282,7 @@ extern "C" int gecm_dev_resize(gecm_dev *d, size_t ncurves)
         d->stride = stride;
     }
     d->ncurves = ncurves;
+    d->have_groups = false;
     return 0;
 }
 
@@ -372,15 +383,15 @@ extern "C" int gecm_dev_auto_lanes(gecm_dev *d)
      * 14.4k); more limbs per lane up to 30 curves per CU and from 32 to 50 (831 bits: 31.9k against 29.7k curves/s at
      * 12,288), the eight-lane layout at exactly one or two wavefronts per SIMD in between (8192 curves: 32.7k against
      * 30.6k). */
-    if (!d->fform && d->row_nq && d->nl >= 10 && d->stride) {
+    if (!d->multi && !d->fform && d->row_nq && d->nl >= 10 && d->stride) {
         const size_t s = d->stride, cu = (size_t)d->cus;
         if (d->row_nq == 1 ? s <= cu * 56 : (s <= cu * 30 || (s > cu * 32 && s <= cu * 50))) return 32;
     }
     /* Below 10 limbs the 32-lane layout still has the shortest chain per curve (9 rows of 6 instructions): while the
      * batch leaves it at one wavefront per SIMD or less (8 curves per CU) it is latency that counts — 8 curves of a
      * 204-bit N at B1 = 3e6: 4.11 s against 7.15 s (eight lanes) and 8.42 s (two), tools/multirange_time.py. */
-    if (!d->fform && d->row_nq && d->nl < 10 && d->stride && d->stride <= (size_t)d->cus * 8) return 32;
-    if (!d->fform && d->dModQ && d->stride && d->stride <= (size_t)d->cus * (d->nl >= 19 ? 64 : 32)) return 8;
+    if (!d->multi && !d->fform && d->row_nq && d->nl < 10 && d->stride && d->stride <= (size_t)d->cus * 8) return 32;
+    if (!d->multi && !d->fform && d->dModQ && d->stride && d->stride <= (size_t)d->cus * (d->nl >= 19 ? 64 : 32)) return 8;
     if (d->nl >= 26) return 2;
     const size_t full = (size_t)d->cus * 4 * 128;
     const size_t r = d->stride % full;
@@ -415,9 +426,19 @@ extern "C" int gecm_dev_stage1(gecm_dev *d, int lanes_per_curve)
         g_err = "gecm_dev_stage1: no curves or no tape";
         return -2;
     }
+    if (d->multi && !d->have_groups) {
+        g_err = "gecm_dev_stage1: the moduli of the batch are not set (gecm_dev_set_groups)";
+        return -2;
+    }
     const int lanes = lanes_per_curve ? lanes_per_curve : gecm_dev_auto_lanes(d);
     char nm[96];   // the kernel's name as rocprofv3 prints it
-    if (lanes == 32) {
+    if (d->multi) {
+        if (lanes != 1 && lanes != 2) {
+            g_err = "gecm_dev_stage1: a multi-modulus batch runs with 1 or 2 lanes per curve";
+            return -2;
+        }
+        snprintf(nm, sizeof nm, "%s<%d>", lanes == 2 ? "k_stage1_pair_multi" : "k_stage1_multi", d->nl);
+    } else if (lanes == 32) {
         if (d->fform || !d->row_nq) {
             g_err = "gecm_dev_stage1: no 32-lane kernel for this modulus";
             return -2;
@@ -506,6 +527,10 @@ extern "C" int gecm_dev_download_mont(gecm_dev *d, uint32_t *X, uint32_t *Z)
 extern "C" int gecm_dev_download_plain(gecm_dev *d, uint32_t *x, uint32_t *z)
 {
     HIPCHK(hipSetDevice(d->device));
+    if (d->multi && !d->have_groups) {
+        g_err = "gecm_dev_download_plain: the moduli of the batch are not set";
+        return -2;
+    }
     gecm_modconst mc = modconst(d);
     d->k1->from_mont(d->stream, &mc, d->dX, d->dZ, d->dT0, d->dT1, d->stride);
     HIPCHK(hipGetLastError());
@@ -519,6 +544,10 @@ extern "C" int gecm_dev_l0(gecm_dev *d, int op, const uint32_t *a, const uint32_
                            uint32_t *dd, size_t count, const uint32_t *fix)
 {
     HIPCHK(hipSetDevice(d->device));
+    if (d->multi) {
+        g_err = "gecm_dev_l0: not available on a multi-modulus context";
+        return -2;
+    }
     if (gecm_dev_resize(d, count)) return -1;
     // reuse the state buffers: X<-a, Z<-b, outputs T0, T1
     if (upload_soa(d, d->dX, a)) return -1;
@@ -530,6 +559,49 @@ extern "C" int gecm_dev_l0(gecm_dev *d, int op, const uint32_t *a, const uint32_
     if (op == GECM_L0_ADDSUB && dd)
         if (download_soa(d, dd, d->dT1)) return -1;
     HIPCHK(hipStreamSynchronize(d->stream));
+    return 0;
+}
+
+// ---------------------------------------------------------------- multi-modulus batches
+extern "C" void gecm_dev_set_multi(gecm_dev *d) { d->multi = true; }
+
+extern "C" int gecm_dev_set_groups(gecm_dev *d, uint32_t ngroups, const uint32_t *n, const uint32_t *kp,
+                                   const uint32_t *one, const uint32_t *r3, const uint32_t *rho,
+                                   const uint32_t *inv_iters, const uint32_t *block_group)
+{
+    HIPCHK(hipSetDevice(d->device));
+    const size_t blocks = d->stride / 64, gb = d->k1->group_bytes, nl = (size_t)d->nl;
+    if (!d->multi || !ngroups || !blocks) {
+        g_err = "gecm_dev_set_groups: not a multi-modulus context, or no moduli or curves";
+        return -2;
+    }
+    for (size_t b = 0; b < blocks; b++)
+        if (block_group[b] >= ngroups) {
+            g_err = "gecm_dev_set_groups: block " + std::to_string(b) + " names modulus " + std::to_string(block_group[b]);
+            return -2;
+        }
+    std::vector<unsigned char> packed(gb * ngroups);
+    for (uint32_t g = 0; g < ngroups; g++) {
+        gecm_modconst mc = {n + g * nl, kp + g * nl, one + g * nl, r3 + g * nl, rho[g], inv_iters[g], nullptr, nullptr};
+        d->k1->pack_group(&mc, packed.data() + g * gb);
+    }
+    if (packed.size() > d->groups_cap) {
+        (void)hipFree(d->dGroups);
+        d->dGroups = nullptr;
+        HIPCHK(hipMalloc(&d->dGroups, packed.size()));
+        d->groups_cap = packed.size();
+    }
+    if (blocks > d->blocks_cap) {
+        (void)hipFree(d->dBlockGroup);
+        d->dBlockGroup = nullptr;
+        HIPCHK(hipMalloc(&d->dBlockGroup, blocks * sizeof(uint32_t)));
+        d->blocks_cap = blocks;
+    }
+    // synchronous: the host arrays may go away when this returns, and no launch may see half of them
+    HIPCHK(hipMemcpyAsync(d->dGroups, packed.data(), packed.size(), hipMemcpyHostToDevice, d->stream));
+    HIPCHK(hipMemcpyAsync(d->dBlockGroup, block_group, blocks * sizeof(uint32_t), hipMemcpyHostToDevice, d->stream));
+    HIPCHK(hipStreamSynchronize(d->stream));
+    d->have_groups = true;
     return 0;
 }
 
@@ -574,6 +646,7 @@ static uint32_t s2_subseq_for(const gecm_dev *d, size_t stride)
     // two wavefronts per SIMD is the target (4096 curves, B2 = 1e8: K = 1 1.14 s, 4 0.75 s, 16 and 32 0.64 s)
     const size_t waves = stride / 64, want = (size_t)d->cus * 4 * 2;
     uint32_t k = 1;
+    if (d->multi) return 1;    // multi-modulus contexts have no sub-sequence kernels
     while (k < 32 && waves * (k * 2) <= want) k *= 2;
     if (const char *e = getenv("GECM_S2_SUBSEQ")) {
         const long v = strtol(e, nullptr, 10);
@@ -601,12 +674,12 @@ extern "C" int gecm_dev_s2_init(gecm_dev *d, const uint32_t *keep, size_t keep_w
                                 uint32_t K)
 {
     HIPCHK(hipSetDevice(d->device));
-    if (!d->stride || d->r3.empty()) {
+    if (!d->stride || d->r3.empty() || (d->multi && !d->have_groups)) {
         g_err = "gecm_dev_s2_init: no curves or stage-2 constants not set";
         return -2;
     }
     const size_t coord = (size_t)d->nl * d->stride * sizeof(uint32_t);
-    if (K < 1 || K > 32 || (K & (K - 1)) || (K > 1 && (!tgt || !tgt_off))) {
+    if (K < 1 || K > 32 || (K & (K - 1)) || (K > 1 && (!tgt || !tgt_off)) || (d->multi && K != 1)) {
         g_err = "gecm_dev_s2_init: bad number of sub-sequences";
         return -2;
     }
@@ -751,7 +824,7 @@ extern "C" int gecm_dev_gcd_scan(gecm_dev *d, int which, uint32_t *flags, uint32
 {
     HIPCHK(hipSetDevice(d->device));
     const uint32_t *src = which == 0 ? d->dZ : d->dAcc;
-    if (!src || !d->stride || d->r3.empty()) {
+    if (!src || !d->stride || d->r3.empty() || (d->multi && !d->have_groups)) {
         g_err = "gecm_dev_gcd_scan: nothing to scan";
         return -2;
     }

@@ -7,6 +7,8 @@
 #include "gecm_stage2.hpp"
 #include "gecm_quad.hpp"
 #include <hip/hip_runtime.h>
+#include <cstddef>
+#include <cstring>
 #include <type_traits>
 
 #ifndef GECM_NL
@@ -24,30 +26,76 @@ struct ModArgs {
     ModK<NL> m;
     Fe<NL> one;   // R mod N, canonical
 };
+
+// Where a kernel finds the constants of its modulus.  A single-N launch passes ModArgs / S2Const by value; a
+// multi-modulus launch (one modulus per wavefront) passes ModGroups: one S2Const per modulus in device
+// memory and the modulus of every 64-curve block.  mod_consts() gives a kernel the constants of its curve block from
+// either source, as a reference the multiplies read as wave-uniform operands; each single-N kernel and its _multi twin
+// share one body (GECM_STAGE1_BODY and the like).
+template <int NL>
+struct ModGroups {
+    const S2Const<NL> *groups;    // read-only for the whole launch
+    const uint32_t *block_group;  // modulus of curve block b (curves 64b .. 64b+63)
+};
+static_assert(offsetof(S2Const<GECM_NL>, m) == offsetof(ModArgs<GECM_NL>, m) &&
+              offsetof(S2Const<GECM_NL>, one) == offsetof(ModArgs<GECM_NL>, one),
+              "ModArgs must be a prefix of S2Const: multi-modulus kernels read one through the other");
+
+template <class A>
+__device__ __forceinline__ const A &mod_consts(const A &a, uint32_t) { return a; }
+
+// The loads go through the constant address space: the constants are read-only while the kernel runs, so the
+// compiler fetches them with scalar loads at a wave-uniform address and may fetch them again where it needs them
+// instead of holding them in registers, as it does with kernel arguments.
+template <class A, int NL>
+__device__ __forceinline__ const A &mod_consts(const ModGroups<NL> &g, uint32_t block)
+{
+    typedef const __attribute__((address_space(4))) uint32_t c_u32;
+    typedef const __attribute__((address_space(4))) S2Const<NL> c_s2;
+    const uint32_t grp = ((c_u32 *)g.block_group)[block];
+    return *(const A *)(const S2Const<NL> *)((c_s2 *)g.groups + grp);
+}
 #if GECM_HAS_PART(1)
 // ---------------------------------------------------------------- stage 1
 // One curve per lane.  64-thread blocks (one wave): a CU holds 8 of them at 2 waves/SIMD, the
 // occupancy at which v_mad_u64_u32 issues back-to-back (profiles/r01_valu_ubench_gfx950.txt).
+// The body of k_stage1 and k_stage1_multi, with the constants in `a` (a ModArgs<NL>).  A macro, not a device function
+// over the constants source: through such a function the single-N kernels compiled to different code at some limb
+// counts (operand order, register choice, stack layout), and they must stay instruction for instruction what they
+// were.  The other single-N / multi pairs below share their bodies the same way.
+#define GECM_STAGE1_BODY                                                        \
+    uint32_t idx = blockIdx.x * 64u + threadIdx.x;                              \
+    Pt<NL> P;                                                                   \
+    fe_load(P.X, X, stride, idx);                                               \
+    fe_load(P.Z, Z, stride, idx);                                               \
+    constexpr bool CL = TapePolicy<NL>::c_in_lds;                               \
+    __shared__ uint32_t lds_c[CL ? 2 * NL * 64 : 1];                            \
+    CStore<NL, CL> cst;                                                         \
+    if constexpr (CL) cst.lds = lds_c + threadIdx.x;                            \
+    run_tape<NL>(tape, tape_len, P, S, stride, idx, a.m, cst);                  \
+    Fe<NL> ox, oz;                                                              \
+    fe_canonical_mont(ox, P.X, a.one, a.m);                                     \
+    fe_canonical_mont(oz, P.Z, a.one, a.m);                                     \
+    fe_store(X, stride, idx, ox);                                               \
+    fe_store(Z, stride, idx, oz);
+
 template <int NL>
 __global__ void __launch_bounds__(64, 2)
 k_stage1(const uint32_t *__restrict__ tape, uint32_t tape_len, uint32_t *__restrict__ X,
          uint32_t *__restrict__ Z, const uint32_t *__restrict__ S, size_t stride, ModArgs<NL> a)
 {
-    uint32_t idx = blockIdx.x * 64u + threadIdx.x;
-    Pt<NL> P;
-    fe_load(P.X, X, stride, idx);
-    fe_load(P.Z, Z, stride, idx);
-    constexpr bool CL = TapePolicy<NL>::c_in_lds;
-    __shared__ uint32_t lds_c[CL ? 2 * NL * 64 : 1];
-    CStore<NL, CL> cst;
-    if constexpr (CL) cst.lds = lds_c + threadIdx.x;
-    run_tape<NL>(tape, tape_len, P, S, stride, idx, a.m, cst);
-    Fe<NL> ox, oz;
-    fe_canonical_mont(ox, P.X, a.one, a.m);
-    fe_canonical_mont(oz, P.Z, a.one, a.m);
-    fe_store(X, stride, idx, ox);
-    fe_store(Z, stride, idx, oz);
+    GECM_STAGE1_BODY
 }
+
+template <int NL>
+__global__ void __launch_bounds__(64, 2)
+k_stage1_multi(const uint32_t *__restrict__ tape, uint32_t tape_len, uint32_t *__restrict__ X,
+               uint32_t *__restrict__ Z, const uint32_t *__restrict__ S, size_t stride, ModGroups<NL> g)
+{
+    const ModArgs<NL> &a = mod_consts<ModArgs<NL>>(g, blockIdx.x);
+    GECM_STAGE1_BODY
+}
+#undef GECM_STAGE1_BODY
 
 // Stage 1 modulo Mw = 2^k - 1 (gecm_field.hpp, "F-form"): the same interpreter, the REDC half of every
 // multiply replaced by the shift-and-subtract form.  Used by the host for N | 2^k - 1.
@@ -81,21 +129,35 @@ k_stage1_f(const uint32_t *__restrict__ tape, uint32_t tape_len, uint32_t *__res
 
 // Two lanes per curve (gecm_curve.hpp, "split-coordinate"): lane 2j works on X, lane 2j+1 on Z of
 // curve blockIdx.x*32 + j.  Chosen by the device layer for batches that leave SIMDs under-occupied.
+// (a macro for the reason given at GECM_STAGE1_BODY; the constants are in `a`, a ModArgs<NL>)
+#define GECM_STAGE1_PAIR_BODY                                                   \
+    const uint32_t cidx = blockIdx.x * 32u + (threadIdx.x >> 1);                \
+    const bool isZ = (threadIdx.x & 1u) != 0;                                   \
+    uint32_t *mine = isZ ? Z : X;                                               \
+    Fe<NL> P;                                                                   \
+    fe_load(P, mine, stride, cidx);                                             \
+    run_tape_pair<NL>(tape, tape_len, P, S, stride, cidx, isZ, a.m);            \
+    Fe<NL> o;                                                                   \
+    fe_canonical_mont(o, P, a.one, a.m);                                        \
+    fe_store(mine, stride, cidx, o);
+
 template <int NL>
 __global__ void __launch_bounds__(64, 2)
 k_stage1_pair(const uint32_t *__restrict__ tape, uint32_t tape_len, uint32_t *__restrict__ X,
               uint32_t *__restrict__ Z, const uint32_t *__restrict__ S, size_t stride, ModArgs<NL> a)
 {
-    const uint32_t cidx = blockIdx.x * 32u + (threadIdx.x >> 1);
-    const bool isZ = (threadIdx.x & 1u) != 0;
-    uint32_t *mine = isZ ? Z : X;
-    Fe<NL> P;
-    fe_load(P, mine, stride, cidx);
-    run_tape_pair<NL>(tape, tape_len, P, S, stride, cidx, isZ, a.m);
-    Fe<NL> o;
-    fe_canonical_mont(o, P, a.one, a.m);
-    fe_store(mine, stride, cidx, o);
+    GECM_STAGE1_PAIR_BODY
 }
+
+template <int NL>
+__global__ void __launch_bounds__(64, 2)
+k_stage1_pair_multi(const uint32_t *__restrict__ tape, uint32_t tape_len, uint32_t *__restrict__ X,
+                    uint32_t *__restrict__ Z, const uint32_t *__restrict__ S, size_t stride, ModGroups<NL> g)
+{
+    const ModArgs<NL> &a = mod_consts<ModArgs<NL>>(g, blockIdx.x >> 1);   // 32 curves per block
+    GECM_STAGE1_PAIR_BODY
+}
+#undef GECM_STAGE1_PAIR_BODY
 
 template <int NL, class MOD>
 __global__ void __launch_bounds__(64, 2)
@@ -144,34 +206,60 @@ k_stage1_quad(const uint32_t *__restrict__ tape, uint32_t tape_len, uint32_t *__
 }
 
 // canonical Montgomery form of X, Z in place (the tail of k_stage1, for kernels that leave lazy values)
+// (macros for the reason given at GECM_STAGE1_BODY; the constants are in `a`, a ModArgs<NL>)
+#define GECM_CANON_BODY                                                         \
+    uint32_t idx = blockIdx.x * 64u + threadIdx.x;                              \
+    Fe<NL> x, z, r;                                                             \
+    fe_load(x, X, stride, idx);                                                 \
+    fe_load(z, Z, stride, idx);                                                 \
+    fe_canonical_mont(r, x, a.one, a.m);                                        \
+    fe_store(X, stride, idx, r);                                                \
+    fe_canonical_mont(r, z, a.one, a.m);                                        \
+    fe_store(Z, stride, idx, r);
+
 template <int NL>
 __global__ void __launch_bounds__(64)
 k_canon(uint32_t *__restrict__ X, uint32_t *__restrict__ Z, size_t stride, ModArgs<NL> a)
 {
-    uint32_t idx = blockIdx.x * 64u + threadIdx.x;
-    Fe<NL> x, z, r;
-    fe_load(x, X, stride, idx);
-    fe_load(z, Z, stride, idx);
-    fe_canonical_mont(r, x, a.one, a.m);
-    fe_store(X, stride, idx, r);
-    fe_canonical_mont(r, z, a.one, a.m);
-    fe_store(Z, stride, idx, r);
+    GECM_CANON_BODY
 }
+
+template <int NL>
+__global__ void __launch_bounds__(64)
+k_canon_multi(uint32_t *__restrict__ X, uint32_t *__restrict__ Z, size_t stride, ModGroups<NL> g)
+{
+    const ModArgs<NL> &a = mod_consts<ModArgs<NL>>(g, blockIdx.x);
+    GECM_CANON_BODY
+}
+#undef GECM_CANON_BODY
+
+#define GECM_FROM_MONT_BODY                                                     \
+    uint32_t idx = blockIdx.x * 64u + threadIdx.x;                              \
+    Fe<NL> x, z, r;                                                             \
+    fe_load(x, X, stride, idx);                                                 \
+    fe_load(z, Z, stride, idx);                                                 \
+    fe_from_mont_canonical(r, x, a.m);                                          \
+    fe_store(ox, stride, idx, r);                                               \
+    fe_from_mont_canonical(r, z, a.m);                                          \
+    fe_store(oz, stride, idx, r);
 
 template <int NL>
 __global__ void __launch_bounds__(64)
 k_from_mont(const uint32_t *__restrict__ X, const uint32_t *__restrict__ Z, uint32_t *__restrict__ ox,
             uint32_t *__restrict__ oz, size_t stride, ModArgs<NL> a)
 {
-    uint32_t idx = blockIdx.x * 64u + threadIdx.x;
-    Fe<NL> x, z, r;
-    fe_load(x, X, stride, idx);
-    fe_load(z, Z, stride, idx);
-    fe_from_mont_canonical(r, x, a.m);
-    fe_store(ox, stride, idx, r);
-    fe_from_mont_canonical(r, z, a.m);
-    fe_store(oz, stride, idx, r);
+    GECM_FROM_MONT_BODY
 }
+
+template <int NL>
+__global__ void __launch_bounds__(64)
+k_from_mont_multi(const uint32_t *__restrict__ X, const uint32_t *__restrict__ Z, uint32_t *__restrict__ ox,
+                  uint32_t *__restrict__ oz, size_t stride, ModGroups<NL> g)
+{
+    const ModArgs<NL> &a = mod_consts<ModArgs<NL>>(g, blockIdx.x);
+    GECM_FROM_MONT_BODY
+}
+#undef GECM_FROM_MONT_BODY
 
 // ---------------------------------------------------------------- L0 test-level operators
 template <int NL>
@@ -210,25 +298,39 @@ k_l0(int op, const uint32_t *__restrict__ A, const uint32_t *__restrict__ B, uin
 // check_factor (ecm.c:2542-2557) for every curve on the device: g = gcd(v, N) by the same
 // fixed-iteration binary algorithm the stage-2 inversion uses; flag = 1 iff 1 < g < N.
 // v is any representative (Montgomery form or not: R is a power of two, N is odd).
+// (a macro for the reason given at GECM_STAGE1_BODY; the constants are in `k`, an S2Const<NL>)
+#define GECM_GCD_SCAN_BODY                                                      \
+    uint32_t idx = blockIdx.x * 64u + threadIdx.x;                              \
+    Fe<NL> v, c, t, g;                                                          \
+    fe_load(v, V, stride, idx);                                                 \
+    fe_canonical_mont(c, v, k.one, k.m);                                        \
+    fe_invert(t, g, c, k.m, k.inv_iters);                                       \
+    bool is_one = g.v[0] == 1u, is_n = true;                                    \
+    _Pragma("unroll")                                                           \
+    for (int i = 0; i < NL; i++) {                                              \
+        if (i > 0) is_one = is_one && g.v[i] == 0;                              \
+        is_n = is_n && g.v[i] == k.m.n[i];                                      \
+    }                                                                           \
+    fe_store(G, stride, idx, g);                                                \
+    flags[idx] = (!is_one && !is_n) ? 1u : 0u;
+
 template <int NL>
 __global__ void __launch_bounds__(64, 2)
 k_gcd_scan(const uint32_t *__restrict__ V, uint32_t *__restrict__ G, uint32_t *__restrict__ flags, size_t stride,
            S2Const<NL> k)
 {
-    uint32_t idx = blockIdx.x * 64u + threadIdx.x;
-    Fe<NL> v, c, t, g;
-    fe_load(v, V, stride, idx);
-    fe_canonical_mont(c, v, k.one, k.m);
-    fe_invert(t, g, c, k.m, k.inv_iters);
-    bool is_one = g.v[0] == 1u, is_n = true;
-#pragma unroll
-    for (int i = 0; i < NL; i++) {
-        if (i > 0) is_one = is_one && g.v[i] == 0;
-        is_n = is_n && g.v[i] == k.m.n[i];
-    }
-    fe_store(G, stride, idx, g);
-    flags[idx] = (!is_one && !is_n) ? 1u : 0u;
+    GECM_GCD_SCAN_BODY
 }
+
+template <int NL>
+__global__ void __launch_bounds__(64, 2)
+k_gcd_scan_multi(const uint32_t *__restrict__ V, uint32_t *__restrict__ G, uint32_t *__restrict__ flags, size_t stride,
+                 ModGroups<NL> groups)
+{
+    const S2Const<NL> &k = mod_consts<S2Const<NL>>(groups, blockIdx.x);
+    GECM_GCD_SCAN_BODY
+}
+#undef GECM_GCD_SCAN_BODY
 
 #endif
 #if GECM_HAS_PART(2)
@@ -237,6 +339,13 @@ template <int NL>
 __global__ void __launch_bounds__(64, 2) k_s2_init(S2InitArgs a, S2Const<NL> k)
 {
     s2_init<NL>(a, k, blockIdx.x * 64u + threadIdx.x);
+}
+
+// multi-modulus contexts run stage 2 with one sub-sequence per curve (K = 1): these four kernels are the whole path
+template <int NL>
+__global__ void __launch_bounds__(64, 2) k_s2_init_multi(S2InitArgs a, ModGroups<NL> g)
+{
+    s2_init<NL>(a, mod_consts<S2Const<NL>>(g, blockIdx.x), blockIdx.x * 64u + threadIdx.x);
 }
 
 // K sub-sequences per curve (small batches): block b works on curve block b / K, sub-sequence b % K
@@ -259,23 +368,48 @@ __global__ void __launch_bounds__(64, 2) k_s2_gen(S2PairArgs a, uint32_t first_a
     giant_chunk<NL>(a, first_abs, n, first_abs == 0, k, blockIdx.x * 64u + threadIdx.x, kprev);
 }
 
+template <int NL>
+__global__ void __launch_bounds__(64, 2) k_s2_gen_multi(S2PairArgs a, uint32_t first_abs, uint32_t n, ModGroups<NL> g)
+{
+    giant_chunk<NL>(a, first_abs, n, first_abs == 0, mod_consts<S2Const<NL>>(g, blockIdx.x), blockIdx.x * 64u + threadIdx.x);
+}
+
 // pair walk over tape entries [first, first+count)
+// (a macro for the reason given at GECM_STAGE1_BODY; the constants are in `k`, an S2Const<NL>)
+#define GECM_S2_PAIRS_BODY                                                      \
+    /* gridDim.y slices of the segment, one accumulator each (see s2_pairs) */  \
+    const uint32_t per = (count + gridDim.y - 1) / gridDim.y;                   \
+    const uint32_t off = blockIdx.y * per;                                      \
+    if (off >= count) return;                                                   \
+    const uint32_t n = count - off < per ? count - off : per;                   \
+    s2_pairs<NL>(a, first + off, n, k, blockIdx.x * 64u + threadIdx.x, a.acc + (size_t)blockIdx.y * NL * a.stride);
+
 template <int NL>
 __global__ void __launch_bounds__(64, 2) k_s2_pairs(S2PairArgs a, uint32_t first, uint32_t count, S2Const<NL> k)
 {
-    // gridDim.y slices of the segment, one accumulator each (see s2_pairs)
-    const uint32_t per = (count + gridDim.y - 1) / gridDim.y;
-    const uint32_t off = blockIdx.y * per;
-    if (off >= count) return;
-    const uint32_t n = count - off < per ? count - off : per;
-    s2_pairs<NL>(a, first + off, n, k, blockIdx.x * 64u + threadIdx.x, a.acc + (size_t)blockIdx.y * NL * a.stride);
+    GECM_S2_PAIRS_BODY
 }
+
+template <int NL>
+__global__ void __launch_bounds__(64, 2) k_s2_pairs_multi(S2PairArgs a, uint32_t first, uint32_t count, ModGroups<NL> g)
+{
+    const S2Const<NL> &k = mod_consts<S2Const<NL>>(g, blockIdx.x);
+    GECM_S2_PAIRS_BODY
+}
+#undef GECM_S2_PAIRS_BODY
 
 template <int NL>
 __global__ void __launch_bounds__(64, 2) k_s2_merge(uint32_t *acc, uint32_t slices, size_t stride, int init_only,
                                                     S2Const<NL> k)
 {
     s2_merge<NL>(acc, slices, stride, init_only != 0, k, blockIdx.x * 64u + threadIdx.x);
+}
+
+template <int NL>
+__global__ void __launch_bounds__(64, 2) k_s2_merge_multi(uint32_t *acc, uint32_t slices, size_t stride, int init_only,
+                                                          ModGroups<NL> g)
+{
+    s2_merge<NL>(acc, slices, stride, init_only != 0, mod_consts<S2Const<NL>>(g, blockIdx.x), blockIdx.x * 64u + threadIdx.x);
 }
 
 #endif
@@ -302,6 +436,11 @@ static S2Const<GECM_NL> s2_const(const gecm_modconst *mc)
     return k;
 }
 
+static ModGroups<GECM_NL> mod_groups(const gecm_modconst *mc)
+{
+    return ModGroups<GECM_NL>{(const S2Const<GECM_NL> *)mc->groups, mc->block_group};
+}
+
 #define CAT_(a, b) a##b
 #define CAT(a, b) CAT_(a, b)
 
@@ -318,6 +457,12 @@ static void launch_stage1_mod(hipStream_t stream, const gecm_modconst *mc, const
 {
     const dim3 grid((unsigned)(stride / (lanes == 2 ? 32 : 64))), block(64);
     if constexpr (std::is_same<MOD, ModK<GECM_NL>>::value) {
+        if (mc->groups) {
+            const auto g = mod_groups(mc);
+            if (lanes == 2) hipLaunchKernelGGL(k_stage1_pair_multi<GECM_NL>, grid, block, 0, stream, tape, tape_len, X, Z, S, stride, g);
+            else hipLaunchKernelGGL(k_stage1_multi<GECM_NL>, grid, block, 0, stream, tape, tape_len, X, Z, S, stride, g);
+            return;
+        }
         const auto a = mod_args<ModArgs<GECM_NL>>(mc);
         if (lanes == 2) hipLaunchKernelGGL(k_stage1_pair<GECM_NL>, grid, block, 0, stream, tape, tape_len, X, Z, S, stride, a);
         else hipLaunchKernelGGL(k_stage1<GECM_NL>, grid, block, 0, stream, tape, tape_len, X, Z, S, stride, a);
@@ -344,15 +489,24 @@ static void launch_stage1(void *stream, const gecm_modconst *mc, const uint32_t 
 
 static void launch_canon(void *stream, const gecm_modconst *mc, uint32_t *X, uint32_t *Z, size_t stride)
 {
-    hipLaunchKernelGGL(k_canon<GECM_NL>, dim3((unsigned)(stride / 64)), dim3(64), 0, (hipStream_t)stream, X, Z, stride,
-                       mod_args<ModArgs<GECM_NL>>(mc));
+    const dim3 grid((unsigned)(stride / 64)), block(64);
+    if (mc->groups)
+        hipLaunchKernelGGL(k_canon_multi<GECM_NL>, grid, block, 0, (hipStream_t)stream, X, Z, stride, mod_groups(mc));
+    else
+        hipLaunchKernelGGL(k_canon<GECM_NL>, grid, block, 0, (hipStream_t)stream, X, Z, stride,
+                           mod_args<ModArgs<GECM_NL>>(mc));
 }
 
 static void launch_from_mont(void *stream, const gecm_modconst *mc, const uint32_t *X, const uint32_t *Z, uint32_t *ox,
                              uint32_t *oz, size_t stride)
 {
-    hipLaunchKernelGGL(k_from_mont<GECM_NL>, dim3((unsigned)(stride / 64)), dim3(64), 0, (hipStream_t)stream, X, Z,
-                       ox, oz, stride, mod_args<ModArgs<GECM_NL>>(mc));
+    const dim3 grid((unsigned)(stride / 64)), block(64);
+    if (mc->groups)
+        hipLaunchKernelGGL(k_from_mont_multi<GECM_NL>, grid, block, 0, (hipStream_t)stream, X, Z, ox, oz, stride,
+                           mod_groups(mc));
+    else
+        hipLaunchKernelGGL(k_from_mont<GECM_NL>, grid, block, 0, (hipStream_t)stream, X, Z, ox, oz, stride,
+                           mod_args<ModArgs<GECM_NL>>(mc));
 }
 
 static void launch_l0(void *stream, const gecm_modconst *mc, int op, const uint32_t *A, const uint32_t *B, uint32_t *C,
@@ -367,14 +521,24 @@ static void launch_l0(void *stream, const gecm_modconst *mc, int op, const uint3
 static void launch_gcd_scan(void *stream, const gecm_modconst *mc, const uint32_t *V, uint32_t *G, uint32_t *flags,
                             size_t stride)
 {
-    hipLaunchKernelGGL(k_gcd_scan<GECM_NL>, dim3((unsigned)(stride / 64)), dim3(64), 0, (hipStream_t)stream, V, G, flags,
-                       stride, s2_const(mc));
+    const dim3 grid((unsigned)(stride / 64)), block(64);
+    if (mc->groups)
+        hipLaunchKernelGGL(k_gcd_scan_multi<GECM_NL>, grid, block, 0, (hipStream_t)stream, V, G, flags, stride,
+                           mod_groups(mc));
+    else
+        hipLaunchKernelGGL(k_gcd_scan<GECM_NL>, grid, block, 0, (hipStream_t)stream, V, G, flags, stride, s2_const(mc));
+}
+
+static void pack_group(const gecm_modconst *mc, void *out)
+{
+    const S2Const<GECM_NL> k = s2_const(mc);
+    memcpy(out, &k, sizeof k);
 }
 
 extern "C" const gecm_kernels_p1 *CAT(CAT(gecm_kernels_, GECM_NL), _p1)(void)
 {
     static const gecm_kernels_p1 t = {launch_stage1, launch_canon, launch_from_mont, launch_l0, launch_gcd_scan,
-                                      FPolicy<GECM_NL>::G, GECM_MANIFEST};
+                                      FPolicy<GECM_NL>::G, pack_group, sizeof(S2Const<GECM_NL>), GECM_MANIFEST};
     return &t;
 }
 #endif
@@ -384,6 +548,13 @@ static void launch_s2_init(void *stream, const gecm_modconst *mc, const gecm_s2_
     const S2InitArgs &a = h->a;
     const S2Const<GECM_NL> k = s2_const(mc);
     const dim3 grid((unsigned)(a.stride / 64)), block(64);
+    if (mc->groups) {                 // K = 1 (gecm_dev_s2_init)
+        const auto g = mod_groups(mc);
+        hipLaunchKernelGGL(k_s2_init_multi<GECM_NL>, grid, block, 0, (hipStream_t)stream, a, g);
+        if (h->slices > 1)
+            hipLaunchKernelGGL(k_s2_merge_multi<GECM_NL>, grid, block, 0, (hipStream_t)stream, a.acc, h->slices, a.stride, 1, g);
+        return;
+    }
     if (a.K > 1)
         hipLaunchKernelGGL(k_s2_init_k<GECM_NL>, dim3((unsigned)(a.stride / 64 * a.K)), block, 0, (hipStream_t)stream, a, k);
     else
@@ -404,12 +575,15 @@ static void launch_s2_pair(void *stream, const gecm_modconst *mc, const gecm_s2_
     // a "generate" mark with bit 31 set in its count is a single-chain chunk (the reference's last batch of the range,
     // gecm_stage2_pair); the others use K sub-sequences per curve when the batch is small (a.K > 1)
     const dim3 kgrid((unsigned)(a.stride / 64 * (a.K ? a.K : 1)));
+    const ModGroups<GECM_NL> g = mc->groups ? mod_groups(mc) : ModGroups<GECM_NL>{};   // multi-modulus: K = 1
     uint32_t generated = 0, i = 0, kprev = 1;
     while (i < a.nsteps) {
         if (h->host_steps[2 * i] == S2_STEP_GEN) {
             const uint32_t word = h->host_steps[2 * i + 1];
             const uint32_t n = word & 0x7fffffffu;
-            if (a.K > 1 && !(word & 0x80000000u)) {
+            if (mc->groups)
+                hipLaunchKernelGGL(k_s2_gen_multi<GECM_NL>, grid, block, 0, (hipStream_t)stream, a, generated, n, g);
+            else if (a.K > 1 && !(word & 0x80000000u)) {
                 hipLaunchKernelGGL(k_s2_gen_k<GECM_NL>, kgrid, block, 0, (hipStream_t)stream, a, generated, n, k);
                 kprev = a.K;
             } else {
@@ -421,12 +595,19 @@ static void launch_s2_pair(void *stream, const gecm_modconst *mc, const gecm_s2_
         } else {
             uint32_t j = i;
             while (j < a.nsteps && h->host_steps[2 * j] != S2_STEP_GEN) j++;
-            hipLaunchKernelGGL(k_s2_pairs<GECM_NL>, pgrid, block, 0, (hipStream_t)stream, a, i, j - i, k);
+            if (mc->groups)
+                hipLaunchKernelGGL(k_s2_pairs_multi<GECM_NL>, pgrid, block, 0, (hipStream_t)stream, a, i, j - i, g);
+            else
+                hipLaunchKernelGGL(k_s2_pairs<GECM_NL>, pgrid, block, 0, (hipStream_t)stream, a, i, j - i, k);
             i = j;
         }
     }
-    if (h->slices > 1)
-        hipLaunchKernelGGL(k_s2_merge<GECM_NL>, grid, block, 0, (hipStream_t)stream, a.acc, h->slices, a.stride, 0, k);
+    if (h->slices > 1) {
+        if (mc->groups)
+            hipLaunchKernelGGL(k_s2_merge_multi<GECM_NL>, grid, block, 0, (hipStream_t)stream, a.acc, h->slices, a.stride, 0, g);
+        else
+            hipLaunchKernelGGL(k_s2_merge<GECM_NL>, grid, block, 0, (hipStream_t)stream, a.acc, h->slices, a.stride, 0, k);
+    }
 }
 
 extern "C" const gecm_kernels_p2 *CAT(CAT(gecm_kernels_, GECM_NL), _p2)(void)

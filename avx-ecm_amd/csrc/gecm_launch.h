@@ -15,6 +15,10 @@
 typedef struct {
     const uint32_t *n, *kp, *one, *r3;
     uint32_t rho, inv_iters;
+    /* multi-modulus launch, else NULL: device array of the moduli's constants (pack_group), and the
+     * modulus of every 64-curve block; the launchers then run the kernels' _multi instantiations */
+    const void *groups;
+    const uint32_t *block_group;
 } gecm_modconst;
 
 /* Stage-2 kernel arguments (csrc/gecm_stage2.hpp), passed by value: the type names are part of the kernel symbols. */
@@ -75,6 +79,7 @@ struct gecm_kernels_p1 {
     /* lanes per curve 1 or 2 (form: 0 = generic modulus, +1 = 2^k - 1, -1 = 2^k + 1, 2 = 2^k - c), or 8 (generic
      * moduli only; modq = device array of 80 words: limbs 0..39 of N then of K', zero padded, read per lane).  The
      * eight-lane kernel leaves lazy values in X, Z: run canon afterwards. */
+    /* a multi-modulus mc takes lanes 1 or 2 and form 0 only */
     void (*stage1)(void *stream, const gecm_modconst *mc, const uint32_t *tape, uint32_t tape_len, uint32_t *X,
                    uint32_t *Z, const uint32_t *S, size_t stride, const uint32_t *modq, int lanes, int form);
     void (*canon)(void *stream, const gecm_modconst *mc, uint32_t *X, uint32_t *Z, size_t stride);
@@ -85,10 +90,14 @@ struct gecm_kernels_p1 {
     void (*gcd_scan)(void *stream, const gecm_modconst *mc, const uint32_t *V, uint32_t *G, uint32_t *flags,
                      size_t stride);
     int fform_generic_limbs;      /* limbs of a 2^k -+ c modulus that are not 2^28 - 1 */
+    /* one modulus's constants (n, kp, one, r3, rho, inv_iters of mc) as the multi-modulus kernels read them from device
+     * memory: group_bytes bytes at out */
+    void (*pack_group)(const gecm_modconst *mc, void *out);
+    size_t group_bytes;
     const char *manifest;         /* the hash of the sources the object was compiled from (Makefile: K_SHA) */
 };
 
-/* Part 2: stage 2. */
+/* Part 2: stage 2 (a multi-modulus mc takes K = 1 only). */
 struct gecm_kernels_p2 {
     void (*s2_init)(void *stream, const gecm_modconst *mc, const gecm_s2_init_launch *h);
     void (*s2_pair)(void *stream, const gecm_modconst *mc, const gecm_s2_pair_launch *h);

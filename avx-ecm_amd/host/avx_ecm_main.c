@@ -111,6 +111,7 @@ typedef struct {
     gecm_ctx *ctx;
     uint64_t *sigma;
     size_t ncurves, first;     /* this GPU's slice of the pass: distinct curves first .. first+ncurves */
+    size_t koff;               /* context index of distinct curve `first` (0; a multi-modulus pass: the input's first) */
     uint64_t B1;
     uint32_t range;
     int rc;
@@ -318,7 +319,11 @@ static void locate(const pass_t *ps, size_t b, size_t l, int *g, size_t *k)
     const run_t *R = ps->run;
     const size_t u = b * R->ub + (R->fixed_sigma ? l % VECLEN : l);
     for (int i = 0; i < R->gpus; i++)
-        if (u >= ps->jobs[i].first && u < ps->jobs[i].first + ps->jobs[i].ncurves) { *g = i; *k = u - ps->jobs[i].first; return; }
+        if (u >= ps->jobs[i].first && u < ps->jobs[i].first + ps->jobs[i].ncurves) {
+            *g = i;
+            *k = u - ps->jobs[i].first + ps->jobs[i].koff;
+            return;
+        }
     *g = 0; *k = 0;
 }
 
@@ -374,7 +379,8 @@ static void *fmt_run(void *arg)
     for (size_t u = f->lo; u < f->hi; u++) {
         int g = 0;
         while (g + 1 < R->gpus && u >= f->ps->jobs[g].first + f->ps->jobs[g].ncurves) g++;
-        int n = gecm_format_resume_line(f->ps->jobs[g].ctx, u - f->ps->jobs[g].first, f->b1_field, line, sizeof line);
+        int n = gecm_format_resume_line(f->ps->jobs[g].ctx, u - f->ps->jobs[g].first + f->ps->jobs[g].koff, f->b1_field, line,
+                                        sizeof line);
         f->lines[u] = n > 0 ? strdup(line) : NULL;
     }
     return NULL;
@@ -640,13 +646,15 @@ static void pass_release(pass_t *ps)
     memset(ps, 0, sizeof *ps);
 }
 
-int main(int argc, char **argv)
+/* one input, the reference's command line: avx-ecm input curves B1 [threads] [B2] [sigma] */
+static int run_single(int argc, char **argv)
 {
     if (argc < 4) {
         printf("usage: avx-ecm $input $numcurves $B1 [$threads] [$B2] [$sigma]\n");   /* main.c:382 */
         return 1;
     }
     static run_t R;
+    memset(&R, 0, sizeof R);
     R.t_start = now();
     printf("starting process %d\n", (int)getpid());                               /* main.c:391 */
     /* main.c:393-457: evaluate the expression, recognise Cunningham-type inputs, strip algebraic factors */
@@ -830,5 +838,189 @@ int main(int argc, char **argv)
     for (int s = 0; s < slots; s++)
         for (int g = 0; g < gpus; g++) gecm_destroy(ctx[s][g]);
     printf("Process took %1.4f seconds.\n", now() - R.t_start);                    /* ecm.c:1538 */
+    free(R.rd);
     return R.failed ? 2 : 0;
+}
+
+/* ---- avx-ecm -f FILE curves B1 [threads] [B2] [sigma]: a list of inputs ----------------------------------------------
+ * The files come out as running `avx-ecm <input> curves B1 threads B2 sigma` for every line in turn, in the same
+ * directory: per input, save_b1.txt up to and including its first batch with a factor, and that batch's factor lines
+ * in ecm_results.txt.  Consecutive inputs run together in multi-modulus passes (include/gecm.h gecm_create_multi) of up
+ * to FULL_BATCH curves on the first GPU; an input the reference works on modulo 2^k -/+ c, one that does not fit a
+ * pass, and every input of a run with a checkpoint (B1 above 99999989) go through the one-input path, in their place. */
+typedef struct {
+    char *expr;
+    char ndec[MPL_MAXL * 10 + 16];
+    char log[65536];
+} input_t;
+
+/* the inputs of one multi-modulus pass; returns 0, or 2 after a device or library error */
+static int multi_pass(input_t **in, size_t n, run_t *R, size_t ucurves)
+{
+    const char **ns = (const char **)malloc(n * sizeof *ns);
+    uint64_t *sigma = (uint64_t *)malloc(n * ucurves * sizeof *sigma);
+    uint32_t *which = (uint32_t *)malloc(n * ucurves * sizeof *which);
+    if (!ns || !sigma || !which) { fprintf(stderr, "out of memory\n"); exit(2); }
+    for (size_t i = 0; i < n; i++) {
+        ns[i] = in[i]->ndec;
+        for (size_t u = 0; u < ucurves; u++) {
+            uint64_t *sg = &sigma[i * ucurves + u];
+            if (R->fixed_sigma) *sg = R->sigma0 + u;                                  /* as run_single's pass 0 */
+            else do { *sg = lcg_rand(&R->lcg); } while (*sg < 6);
+            which[i * ucurves + u] = (uint32_t)i;
+        }
+    }
+    gecm_ctx *mc = NULL;
+    int rc = gecm_create_multi(&mc, 0, ns, n, GECM_CLI_DIGITBITS);
+    if (rc == 0) rc = gecm_build_curves_multi(mc, sigma, which, n * ucurves) < 0;
+    if (rc == 0) rc = gecm_stage1(mc, R->B1) || gecm_sync(mc) || gecm_scan_factors(mc, 1, NULL) < 0;
+    if (rc == 0 && R->do_stage2) rc = gecm_stage2(mc, R->B2, 0, 0) || gecm_scan_factors(mc, 2, NULL) < 0;
+    if (rc) {
+        fprintf(stderr, "%s\n", gecm_last_error());
+        gecm_destroy(mc);
+        free(ns); free(sigma); free(which);
+        return 2;
+    }
+    /* every input as the one-input path writes it: a pass of all its batches on one context */
+    for (size_t i = 0; i < n; i++) {
+        static pass_t ps;
+        memset(&ps, 0, sizeof ps);
+        ps.run = R;
+        ps.nb = R->nbatches;
+        ps.ucurves = ucurves;
+        ps.jobs[0].ctx = mc;
+        ps.jobs[0].ncurves = ucurves;
+        ps.jobs[0].koff = i * ucurves;
+        ps.jobs[0].sigma = sigma;
+        fputs(in[i]->log, stdout);             /* "gen: ...", "commencing parallel ecm on ..." */
+        size_t bstar = ps.nb;
+        for (size_t b = 0; b < ps.nb; b++)
+            if (batch_flagged(&ps, 1, b) || (R->do_stage2 && batch_flagged(&ps, 2, b))) { bstar = b; break; }
+        const int found = bstar < ps.nb;
+        const size_t nwrite = found ? bstar + 1 : ps.nb;
+        char **lines = format_lines(&ps, R->B1, nwrite * R->ub);
+        text_t res = {0, 0, 0}, out = {0, 0, 0};
+        if (found) {
+            factor_lines(&ps, 1, bstar, R->B1, &res, &out);
+            if (R->do_stage2) factor_lines(&ps, 2, bstar, R->B2, &res, &out);
+        }
+        if (out.len) fputs(out.buf, stdout);
+        FILE *save = fopen("save_b1.txt", "a");
+        if (save && lines) { write_batches(&ps, save, lines, 0, nwrite); fclose(save); }
+        else printf("could not open save_b1.txt for appending, Stage 1 data will not be saved\n");
+        if (res.len) {
+            FILE *o = fopen("ecm_results.txt", "a");
+            if (o) { fputs(res.buf, o); fclose(o); }
+        }
+        fflush(stdout);
+        free_lines(lines, ucurves);
+        free(res.buf); free(out.buf);
+    }
+    printf("multi-modulus pass: %zu inputs, %zu curves each, stage 1%s, %1.4f seconds of kernels after stage 1\n", n,
+           ucurves, R->do_stage2 ? " and stage 2" : "", gecm_last_kernel_ms(mc) / 1000.0);
+    gecm_destroy(mc);
+    free(ns); free(sigma); free(which);
+    return 0;
+}
+
+static int run_file(int argc, char **argv)
+{
+    static const char *usage = "usage: avx-ecm -f $file $numcurves $B1 [$threads] [$B2] [$sigma]\n"
+                               "       (one input expression per line; blank lines and lines starting with # are skipped)\n";
+    if (argc < 5) { printf("%s", usage); return 1; }
+    FILE *f = fopen(argv[2], "r");
+    if (!f) { printf("cannot read %s\n%s", argv[2], usage); return 1; }
+    size_t ninputs = 0, cap_in = 0;
+    char **exprs = NULL;
+    static char buf[1 << 16];
+    while (fgets(buf, sizeof buf, f)) {
+        char *p = buf, *e;
+        while (*p == ' ' || *p == '\t') p++;
+        e = p + strlen(p);
+        while (e > p && (e[-1] == '\n' || e[-1] == '\r' || e[-1] == ' ' || e[-1] == '\t')) *--e = 0;
+        if (!*p || *p == '#') continue;
+        if (ninputs == cap_in) {
+            cap_in = cap_in ? 2 * cap_in : 64;
+            exprs = (char **)realloc(exprs, cap_in * sizeof *exprs);
+            if (!exprs) { fprintf(stderr, "out of memory\n"); return 2; }
+        }
+        exprs[ninputs++] = strdup(p);
+    }
+    fclose(f);
+    if (!ninputs) { printf("%s holds no input\n%s", argv[2], usage); return 1; }
+
+    /* the run's parameters, as run_single reads them */
+    static run_t R;
+    memset(&R, 0, sizeof R);
+    R.t_start = now();
+    size_t numcurves = strtoul(argv[3], NULL, 10);
+    R.B1 = strtoull(argv[4], NULL, 10);
+    R.B2 = 100ULL * R.B1;
+    R.threads = 1;
+    R.do_stage2 = 1;
+    if (argc > 5) R.threads = atoi(argv[5]);
+    if (argc > 6) R.B2 = strtoull(argv[6], NULL, 10);
+    if (argc > 7) R.sigma0 = strtoull(argv[7], NULL, 10);
+    if (R.B2 <= R.B1) { R.do_stage2 = 0; R.B2 = R.B1; }
+    if (R.threads < 1) R.threads = 1;
+    R.fixed_sigma = R.sigma0 > 0;
+    if (numcurves == 0 || R.B1 < 2 || R.B1 > 1000000000000ULL) { printf("need curves >= 1 and 2 <= B1 <= 1e12\n"); return 1; }
+    if (numcurves < (size_t)R.threads) numcurves = (size_t)R.threads;
+    R.per_thread = numcurves / (size_t)R.threads + (numcurves % (size_t)R.threads != 0);
+    R.nbatches = (R.per_thread + VECLEN - 1) / VECLEN;
+    R.ub = R.fixed_sigma ? VECLEN : (size_t)VECLEN * (size_t)R.threads;
+    R.gpus = 1;
+    R.lcg = (uint64_t)(R.t_start * 1e6) * 0x9E3779B97F4A7C15ULL + (uint64_t)getpid();
+    const size_t ucurves = R.nbatches * R.ub, padded = (ucurves + 63) / 64 * 64;
+    if (gecm_device_count() < 1) { fprintf(stderr, "no HIP device visible\n"); return 2; }
+    printf("starting process %d: %zu inputs from %s\n", (int)getpid(), ninputs, argv[2]);
+    size_t cap = FULL_BATCH;
+    if (getenv("GECM_PASS_CURVES") && atol(getenv("GECM_PASS_CURVES")) > 0) cap = (size_t)atol(getenv("GECM_PASS_CURVES"));
+    const int multi_ok = R.B1 <= 99999989ULL && padded <= cap;    /* one prime range, no checkpoint; one input fits */
+
+    /* the one-input path's argument list for input i: argv with "-f FILE" replaced by the input */
+    char *sargv[8];
+    const int sargc = argc - 1;
+    sargv[0] = argv[0];
+    for (int a = 3; a < argc && a < 8; a++) sargv[a - 1] = argv[a];
+    input_t **pend = (input_t **)calloc(ninputs, sizeof *pend);
+    if (!pend) { fprintf(stderr, "out of memory\n"); return 2; }
+    size_t npend = 0;
+    int rc = 0;
+    for (size_t i = 0; i <= ninputs && rc != 2; i++) {
+        input_t *in = NULL;
+        int alone = 1;
+        if (i < ninputs && multi_ok) {
+            in = (input_t *)calloc(1, sizeof *in);
+            if (!in) { fprintf(stderr, "out of memory\n"); return 2; }
+            in->expr = exprs[i];
+            gecm_input_info inf;
+            alone = gecm_prepare_input(in->expr, GECM_CLI_DIGITBITS, in->ndec, sizeof in->ndec, &inf, in->log, sizeof in->log) ||
+                    inf.ref_special_reduction;
+        }
+        /* the pending pass goes first when this input cannot join it */
+        if (npend && (i == ninputs || alone || (npend + 1) * padded > cap)) {
+            rc = multi_pass(pend, npend, &R, ucurves);
+            for (size_t k = 0; k < npend; k++) free(pend[k]);
+            npend = 0;
+            if (rc == 2) break;
+        }
+        if (i == ninputs) break;
+        if (!alone) { pend[npend++] = in; continue; }
+        free(in);
+        sargv[1] = exprs[i];
+        const int r1 = run_single(sargc, sargv);
+        if (r1 > rc) rc = r1;
+    }
+    for (size_t i = 0; i < ninputs; i++) free(exprs[i]);
+    free(exprs);
+    free(pend);
+    printf("Process took %1.4f seconds.\n", now() - R.t_start);
+    return rc;
+}
+
+int main(int argc, char **argv)
+{
+    if (argc > 1 && strcmp(argv[1], "-f") == 0) return run_file(argc, argv);
+    return run_single(argc, argv);
 }

@@ -131,7 +131,37 @@ struct gecm_ctx {
     uint32_t ff_tape_range;
     mpl_t ff_M, ff_r_mod_m;  /* Mw; 2^(28 ff_nl) mod Mw */
     uint32_t *ff_n28;        /* n, kp, one for dev_f */
+    uint32_t inv_iters;      /* batches of 28 division steps after which the device inversion has converged for N */
+    /* multi-modulus context (gecm_create_multi): one host-only context per modulus holds its N and
+     * constants (at this context's limb count); the curves are grouped by modulus, each group padded to whole
+     * wavefronts of 64, and the batch arrays are in that device order.  The caller numbers curves in its own order. */
+    int multi;
+    size_t ngroups;
+    gecm_ctx **grp;
+    uint32_t *gconst;        /* the moduli's n, kp, one, r3 ([4][ngroups][nl]), then rho and inv_iters [ngroups] each */
+    size_t nuser;            /* curves the caller built */
+    uint32_t *slot;          /* caller's curve -> device position */
+    uint32_t *pos_user;      /* device position -> caller's curve, GECM_PAD for padding */
+    uint32_t *pos_grp;       /* device position -> modulus */
+    size_t *goff;            /* first device position of each modulus */
 };
+#define GECM_PAD 0xffffffffu
+
+/* multi-modulus contexts (at the end of this file): the host-only context of curve k's modulus, viewing the batch
+ * at that modulus's positions (stage 1 or 2: the results that stage needs fetched first), *kk = the curve there; NULL
+ * with the status in multi_err */
+static __thread int multi_err;
+static gecm_ctx *multi_curve(gecm_ctx *c, size_t k, int stage, size_t *kk);
+static int multi_scan(gecm_ctx *c, int stage, size_t *first);
+
+/* what a multi-modulus context cannot do: the reference radix (NWORDS) differs from modulus to modulus, and the L0
+ * operators, uploaded points and the special forms work modulo one N */
+static int multi_refuse(const char *fn)
+{
+    set_err("%s: not available on a multi-modulus context (gecm_create_multi)", fn);
+    return GECM_ERR_STATE;
+}
+
 
 static int pick_nl(int nbits)
 {
@@ -249,20 +279,14 @@ static void row_setup(gecm_ctx *c)
     (void)gecm_dev_set_rowconst(c->dev, nq, L, w);
 }
 
-int gecm_create(gecm_ctx **out, int device, const char *n_str, int digitbits)
+/* N and everything derived from it, at nl limbs (0: the fewest that hold N); `who` prefixes the error texts.  Nothing on
+ * the device.  On error c holds nothing to free. */
+static int ctx_setup_n(gecm_ctx *c, const char *who, const char *n_str, int digitbits, int nl)
 {
-    if (!out || !n_str || (digitbits != 52 && digitbits != 32)) {
-        set_err("gecm_create: bad argument (digitbits must be 52 or 32)");
-        return GECM_ERR_ARG;
-    }
-    gecm_ctx *c = (gecm_ctx *)calloc(1, sizeof *c);
-    if (!c) return GECM_ERR_NOMEM;
     if (mpl_set_str(&c->N, n_str) || !mpl_is_odd(&c->N) || mpl_cmp_u64(&c->N, 3) < 0) {
-        set_err("gecm_create: N must be an odd integer >= 3 (decimal or 0x-hex)");
-        free(c);
+        set_err("%s: N must be an odd integer >= 3 (decimal or 0x-hex)", who);
         return GECM_ERR_ARG;
     }
-    c->device = device;
     c->digitbits = digitbits;
     c->nbits = mpl_bits(&c->N);
     /* main.c:465-483: MAXBITS = smallest multiple of 208 (128) strictly greater than bitlen */
@@ -270,13 +294,12 @@ int gecm_create(gecm_ctx **out, int device, const char *n_str, int digitbits)
     c->maxbits = step;
     while (c->maxbits <= c->nbits) c->maxbits += step;
     c->nwords = c->maxbits / digitbits;
-    c->nl = pick_nl(c->nbits);
-    if (!c->nl || c->maxbits + 64 > MPL_MAXL * 16) {
-        set_err("gecm_create: N of %d bits is larger than this build supports", c->nbits);
-        free(c);
+    c->nl = nl ? nl : pick_nl(c->nbits);
+    if (!pick_nl(c->nbits) || c->maxbits + 64 > MPL_MAXL * 16) {
+        set_err("%s: N of %d bits is larger than this build supports", who, c->nbits);
         return GECM_ERR_ARG;
     }
-    int nl = c->nl;
+    nl = c->nl;
     unsigned rint_bits = (unsigned)(LIMB_BITS * nl), rref_bits = (unsigned)c->maxbits;
     mpl_t t, inv;
     pow2_mod(&c->rref_mod_n, rref_bits, &c->N);
@@ -295,31 +318,47 @@ int gecm_create(gecm_ctx **out, int device, const char *n_str, int digitbits)
     c->rho_ref = digitbits == 52 ? (nhat & 0xfffffffffffffull) : (nhat & 0xffffffffull);
     c->rho28 = (uint32_t)(nhat & ((1u << LIMB_BITS) - 1));
     c->n28 = (uint32_t *)calloc((size_t)nl * 4, sizeof(uint32_t));
-    if (!c->n28) { free(c); return GECM_ERR_NOMEM; }
+    if (!c->n28) return GECM_ERR_NOMEM;
     c->kp28 = c->n28 + nl;
     c->one28 = c->kp28 + nl;
     c->fix28 = c->one28 + nl;
     mpl_to_limbs32(c->n28, 1, nl, LIMB_BITS, &c->N);
     mpl_to_limbs32(c->one28, 1, nl, LIMB_BITS, &c->rint_mod_n);
-    if (make_kp(c->kp28, &c->N, nl)) { free(c->n28); free(c); return GECM_ERR_NOMEM; }
+    if (make_kp(c->kp28, &c->N, nl)) { free(c->n28); c->n28 = NULL; return GECM_ERR_NOMEM; }
     /* fix = Rint^2 / Rref mod N = Rint * ref_to_int */
     mpl_mulmod(&t, &c->rint_mod_n, &c->ref_to_int, &c->N);
     mpl_to_limbs32(c->fix28, 1, nl, LIMB_BITS, &t);
-    if (gecm_dev_open(&c->dev, device, nl, c->n28, c->kp28, c->one28, c->rho28)) {
-        set_err("gecm_create: %s", gecm_dev_error());
-        free(c->n28);
-        free(c);
-        return GECM_ERR_DEVICE;
-    }
     /* R^3 mod N for the device inversion (csrc/gecm_stage2.hpp: fe_inv_mont) */
     c->r3_28 = (uint32_t *)calloc((size_t)nl, sizeof(uint32_t));
-    if (!c->r3_28) { gecm_destroy(c); return GECM_ERR_NOMEM; }
+    if (!c->r3_28) { free(c->n28); c->n28 = NULL; return GECM_ERR_NOMEM; }
     mpl_mulmod(&t, &c->rint_mod_n, &c->rint_mod_n, &c->N);
     mpl_mulmod(&t, &t, &c->rint_mod_n, &c->N);
     mpl_to_limbs32(c->r3_28, 1, nl, LIMB_BITS, &t);
     /* batches of 28 division steps after which the device inversion has converged for a modulus of nbits bits:
      * the bound of the "half-delta" variant, floor((45907 bits + 26313) / 19929), +1, rounded up to whole batches */
-    gecm_dev_set_s2const(c->dev, c->r3_28, (uint32_t)((((45907ull * (unsigned)c->nbits + 26313ull) / 19929ull + 1) + 27) / 28));
+    c->inv_iters = (uint32_t)((((45907ull * (unsigned)c->nbits + 26313ull) / 19929ull + 1) + 27) / 28);
+    return GECM_OK;
+}
+
+int gecm_create(gecm_ctx **out, int device, const char *n_str, int digitbits)
+{
+    if (!out || !n_str || (digitbits != 52 && digitbits != 32)) {
+        set_err("gecm_create: bad argument (digitbits must be 52 or 32)");
+        return GECM_ERR_ARG;
+    }
+    gecm_ctx *c = (gecm_ctx *)calloc(1, sizeof *c);
+    if (!c) return GECM_ERR_NOMEM;
+    int rc = ctx_setup_n(c, "gecm_create", n_str, digitbits, 0);
+    if (rc) { free(c); return rc; }
+    c->device = device;
+    if (gecm_dev_open(&c->dev, device, c->nl, c->n28, c->kp28, c->one28, c->rho28)) {
+        set_err("gecm_create: %s", gecm_dev_error());
+        free(c->r3_28);
+        free(c->n28);
+        free(c);
+        return GECM_ERR_DEVICE;
+    }
+    gecm_dev_set_s2const(c->dev, c->r3_28, c->inv_iters);
     row_setup(c);
     ff_setup(c);
     *out = c;
@@ -334,6 +373,10 @@ static void free_batch(gecm_ctx *c)
     c->hg[0] = c->hg[1] = NULL;
     c->scan_valid[0] = c->scan_valid[1] = 0;
     c->sigma = NULL; c->bad = NULL; c->hx = c->hz = NULL; c->hacc = c->hfail = NULL;
+    free(c->slot); free(c->pos_user); free(c->pos_grp); free(c->goff);
+    c->slot = c->pos_user = c->pos_grp = NULL;
+    c->goff = NULL;
+    c->nuser = 0;
     c->have_acc = 0; c->s2_ready = 0;
     c->batch = 0;
     c->have_plain = 0;
@@ -369,6 +412,10 @@ void gecm_destroy(gecm_ctx *c)
     if (c->ptp_valid) free(c->ptp.words);
     free(c->r3_28);
     free(c->n28);
+    for (size_t g = 0; g < c->ngroups; g++)
+        if (c->grp[g]) { free(c->grp[g]->r3_28); free(c->grp[g]->n28); free(c->grp[g]); }   /* host-only views */
+    free(c->grp);
+    free(c->gconst);
     free(c);
 }
 
@@ -378,6 +425,7 @@ void gecm_destroy(gecm_ctx *c)
 int gecm_set_report_modulus(gecm_ctx *c, const char *n_str)
 {
     if (!c) return GECM_ERR_ARG;
+    if (c && c->multi) return multi_refuse("gecm_set_report_modulus");
     if (!n_str) { c->have_report = 0; return GECM_OK; }
     mpl_t r, m;
     if (mpl_set_str(&r, n_str) || mpl_cmp_u64(&r, 1) <= 0) { set_err("gecm_set_report_modulus: bad number"); return GECM_ERR_ARG; }
@@ -423,6 +471,8 @@ int gecm_device_memory(gecm_ctx *c, uint64_t *free_bytes, uint64_t *total_bytes)
 uint64_t gecm_batch_bytes(const gecm_ctx *c, size_t curves, int with_stage2, uint64_t B1, uint32_t D, uint32_t U)
 {
     if (!c || !curves) return 0;
+    /* multi-modulus: every modulus's curves padded to whole wavefronts, at most 63 more per modulus that has curves */
+    if (c->multi) curves += 63 * (curves < c->ngroups ? curves : c->ngroups);
     uint32_t npb = 0;
     if (with_stage2) {
         if (!D) D = gecm_s2_default_D(B1 ? B1 : 1000000);
@@ -461,6 +511,7 @@ static void vec_put(const gecm_ctx *c, void *vec, size_t batch, size_t lane, con
 int gecm_get_one(const gecm_ctx *c, void *one_limbs)
 {
     if (!c || !one_limbs) return GECM_ERR_ARG;
+    if (c && c->multi) return multi_refuse("gecm_get_one");
     vec_put(c, one_limbs, 1, 0, &c->rref_mod_n);
     return GECM_OK;
 }
@@ -468,6 +519,7 @@ int gecm_get_one(const gecm_ctx *c, void *one_limbs)
 /* ---- L0 ------------------------------------------------------------------------------------ */
 static int l0_call(gecm_ctx *c, int op, const void *a, const void *b, void *r0, void *r1, size_t batch)
 {
+    if (c && c->multi) return multi_refuse("the L0 operators");
     if (!c || !a || !r0 || batch == 0) { set_err("L0: bad argument"); return GECM_ERR_ARG; }
     if (!c->dev_l0 &&
         gecm_dev_open(&c->dev_l0, c->device, c->nl, c->n28, c->kp28, c->one28, c->rho28)) {
@@ -673,6 +725,7 @@ static int host_threads(void)
 int gecm_build_curves(gecm_ctx *c, const uint64_t *sigma, size_t batch)
 {
     if (!c || !sigma || batch == 0) { set_err("gecm_build_curves: bad argument"); return GECM_ERR_ARG; }
+    if (c && c->multi) return multi_refuse("gecm_build_curves");
     /* inputs are checked before the context takes the new batch: after an error it holds no batch at all (the
      * phase functions then return GECM_ERR_STATE instead of running on memory nothing was uploaded to) */
     for (size_t i = 0; i < batch; i++)
@@ -721,6 +774,7 @@ int gecm_build_curves(gecm_ctx *c, const uint64_t *sigma, size_t batch)
 int gecm_upload_points(gecm_ctx *c, const void *X, const void *Z, const void *s, size_t batch)
 {
     if (!c || !X || !Z || !s || batch == 0) { set_err("gecm_upload_points: bad argument"); return GECM_ERR_ARG; }
+    if (c && c->multi) return multi_refuse("gecm_upload_points");
     int rc = alloc_batch(c, batch);
     if (rc) return rc;
     int nl = c->nl;
@@ -940,6 +994,7 @@ int gecm_stage1(gecm_ctx *c, uint64_t B1)
 int gecm_set_special_form(gecm_ctx *c, int on)
 {
     if (!c) return GECM_ERR_ARG;
+    if (c && c->multi) return multi_refuse("gecm_set_special_form");
     c->ff_on = on != 0;
     return GECM_OK;
 }
@@ -957,6 +1012,10 @@ int gecm_set_lanes_per_curve(gecm_ctx *c, int lanes)
 {
     if (!c || (lanes != 0 && lanes != 1 && lanes != 2 && lanes != 8 && lanes != 32)) {
         set_err("gecm_set_lanes_per_curve: lanes must be 0 (auto), 1, 2, 8 or 32");
+        return GECM_ERR_ARG;
+    }
+    if (c->multi && lanes != 0 && lanes != 1 && lanes != 2) {
+        set_err("gecm_set_lanes_per_curve: a multi-modulus context runs with 0 (auto), 1 or 2 lanes per curve");
         return GECM_ERR_ARG;
     }
     c->lanes_per_curve = lanes;
@@ -1005,6 +1064,7 @@ int gecm_get_stage1_stats(const gecm_ctx *c, gecm_stage1_stats *st)
 
 int gecm_download_points(gecm_ctx *c, void *X, void *Z)
 {
+    if (c && c->multi) return multi_refuse("gecm_download_points");
     if (c && c->ff_pending) { int rcs = ff_settle(c); if (rcs) return rcs; }
     if (!c || !X || !Z || c->batch == 0) return GECM_ERR_ARG;
     size_t batch = c->batch, words = (size_t)c->nl * batch;
@@ -1036,6 +1096,7 @@ static int fetch_plain(gecm_ctx *c)
 int gecm_download_points_plain(gecm_ctx *c, void *x, void *z)
 {
     if (!c || !x || !z) return GECM_ERR_ARG;
+    if (c && c->multi) return multi_refuse("gecm_download_points_plain");
     int rc = fetch_plain(c);
     if (rc) return rc;
     for (size_t i = 0; i < c->batch; i++) {
@@ -1055,6 +1116,11 @@ int gecm_format_save_line(gecm_ctx *c, size_t k, char *buf, size_t buflen)
 
 int gecm_format_resume_line(gecm_ctx *c, size_t k, uint64_t b1_label, char *buf, size_t buflen)
 {
+    if (c && c->multi) {
+        size_t kk;
+        gecm_ctx *s = multi_curve(c, k, 1, &kk);
+        return s ? gecm_format_resume_line(s, kk, b1_label, buf, buflen) : multi_err;
+    }
     if (!c || !buf || k >= c->batch) return GECM_ERR_ARG;
     int rc = fetch_plain(c);
     if (rc) return rc;
@@ -1074,6 +1140,11 @@ int gecm_format_resume_line(gecm_ctx *c, size_t k, uint64_t b1_label, char *buf,
 
 int gecm_stage1_factor(gecm_ctx *c, size_t k, char *dec, size_t declen, int *is_prp)
 {
+    if (c && c->multi) {
+        size_t kk;
+        gecm_ctx *s = multi_curve(c, k, 1, &kk);
+        return s ? gecm_stage1_factor(s, kk, dec, declen, is_prp) : multi_err;
+    }
     if (!c || k >= c->batch) return GECM_ERR_ARG;
     int rc = fetch_plain(c);
     if (rc) return rc;
@@ -1403,6 +1474,7 @@ static void fail_record(gecm_ctx *c, size_t k, mpl_t *g)
 int gecm_download_acc(gecm_ctx *c, void *acc)
 {
     if (!c || !acc) return GECM_ERR_ARG;
+    if (c && c->multi) return multi_refuse("gecm_download_acc");
     int rc = fetch_acc(c);
     if (rc) return rc;
     for (size_t i = 0; i < c->batch; i++) {
@@ -1416,6 +1488,11 @@ int gecm_download_acc(gecm_ctx *c, void *acc)
 
 int gecm_stage2_factor(gecm_ctx *c, size_t k, char *dec, size_t declen, int *is_prp)
 {
+    if (c && c->multi) {
+        size_t kk;
+        gecm_ctx *s = multi_curve(c, k, 2, &kk);
+        return s ? gecm_stage2_factor(s, kk, dec, declen, is_prp) : multi_err;
+    }
     if (!c || k >= c->batch) return GECM_ERR_ARG;
     int rc = fetch_acc(c);
     if (rc) return rc;
@@ -1448,6 +1525,7 @@ int gecm_scan_factors(gecm_ctx *c, int stage, size_t *first)
 {
     if (c && c->ff_pending) { int rcs = ff_settle(c); if (rcs) return rcs; }
     if (!c || c->batch == 0 || (stage != 1 && stage != 2)) { set_err("gecm_scan_factors: bad argument"); return GECM_ERR_ARG; }
+    if (c->multi) return multi_scan(c, stage, first);
     if (stage == 2 && !c->s2_ready) { set_err("gecm_scan_factors: no stage-2 state"); return GECM_ERR_STATE; }
     uint32_t **f = &c->flags[stage - 1], **hg = &c->hg[stage - 1];
     if (!*f) *f = (uint32_t *)calloc(c->batch, sizeof(uint32_t));
@@ -1500,8 +1578,260 @@ int gecm_scan_factors(gecm_ctx *c, int stage, size_t *first)
 
 int gecm_curve_flag(const gecm_ctx *c, int stage, size_t k)
 {
+    if (c && c->multi) {
+        if (k >= c->nuser) return 0;
+        k = c->slot[k];
+    }
     if (!c || (stage != 1 && stage != 2) || k >= c->batch || !c->flags[stage - 1]) return 0;
     return (int)c->flags[stage - 1][k];
+}
+
+/* ---- multi-modulus contexts ------------------------------------------------ */
+int gecm_create_multi(gecm_ctx **out, int device, const char *const *n_strs, size_t count, int digitbits)
+{
+    if (!out || !n_strs || (digitbits != 52 && digitbits != 32)) {
+        set_err("gecm_create_multi: bad argument (digitbits must be 52 or 32)");
+        return GECM_ERR_ARG;
+    }
+    if (count == 0) { set_err("gecm_create_multi: the list of moduli is empty"); return GECM_ERR_ARG; }
+    if (count > 0xfffffffe) { set_err("gecm_create_multi: %zu moduli, more than a 32-bit modulus index holds", count); return GECM_ERR_ARG; }
+    gecm_ctx *c = (gecm_ctx *)calloc(1, sizeof *c);
+    gecm_ctx **grp = (gecm_ctx **)calloc(count, sizeof *grp);
+    if (!c || !grp) { free(c); free(grp); return GECM_ERR_NOMEM; }
+    c->grp = grp;
+    c->ngroups = count;
+    c->multi = 1;
+    c->device = device;
+    /* every N on its own first: the largest decides the limb count; then every N again at that count */
+    int maxbits = 0, rc = GECM_OK;
+    size_t largest = 0;
+    char who[64];
+    for (size_t g = 0; g < count && !rc; g++) {
+        snprintf(who, sizeof who, "gecm_create_multi: N[%zu]", g);
+        mpl_t n;
+        if (!n_strs[g] || mpl_set_str(&n, n_strs[g]) || !mpl_is_odd(&n) || mpl_cmp_u64(&n, 3) < 0) {
+            set_err("%s must be an odd integer >= 3 (decimal or 0x-hex)", who);
+            rc = GECM_ERR_ARG;
+        } else if (!pick_nl(mpl_bits(&n))) {
+            set_err("%s of %d bits is larger than this build supports", who, mpl_bits(&n));
+            rc = GECM_ERR_ARG;
+        } else if (mpl_bits(&n) > maxbits) {
+            maxbits = mpl_bits(&n);
+            largest = g;
+        }
+    }
+    const int nl = rc ? 0 : pick_nl(maxbits);
+    for (size_t g = 0; g < count && !rc; g++) {
+        snprintf(who, sizeof who, "gecm_create_multi: N[%zu]", g);
+        grp[g] = (gecm_ctx *)calloc(1, sizeof **grp);
+        if (!grp[g]) { rc = GECM_ERR_NOMEM; break; }
+        rc = ctx_setup_n(grp[g], who, n_strs[g], digitbits, nl);
+    }
+    /* the context itself: the largest N (what gecm_get_config reports) and the device */
+    if (!rc) rc = ctx_setup_n(c, "gecm_create_multi", n_strs[largest], digitbits, nl);
+    if (!rc) {
+        c->gconst = (uint32_t *)calloc((size_t)4 * count * nl + 2 * count, sizeof(uint32_t));
+        if (!c->gconst) rc = GECM_ERR_NOMEM;
+    }
+    if (!rc) {
+        uint32_t *rho = c->gconst + (size_t)4 * count * nl, *iters = rho + count;
+        for (size_t g = 0; g < count; g++) {
+            for (int q = 0; q < 4; q++)        /* n, kp, one, r3 */
+                memcpy(c->gconst + ((size_t)q * count + g) * nl, q < 3 ? grp[g]->n28 + (size_t)q * nl : grp[g]->r3_28,
+                       (size_t)nl * sizeof(uint32_t));
+            rho[g] = grp[g]->rho28;
+            iters[g] = grp[g]->inv_iters;
+        }
+        if (gecm_dev_open(&c->dev, device, nl, c->n28, c->kp28, c->one28, c->rho28)) {
+            set_err("gecm_create_multi: %s", gecm_dev_error());
+            rc = GECM_ERR_DEVICE;
+        }
+    }
+    if (rc) { gecm_destroy(c); return rc; }
+    gecm_dev_set_multi(c->dev);
+    gecm_dev_set_s2const(c->dev, c->r3_28, c->inv_iters);
+    *out = c;
+    return GECM_OK;
+}
+
+size_t gecm_moduli(const gecm_ctx *c) { return c ? (c->multi ? c->ngroups : 1) : 0; }
+
+/* the modulus's context as a view of the batch at its positions, the flags of the context copied in */
+static gecm_ctx *view_group(gecm_ctx *c, uint32_t g)
+{
+    gecm_ctx *s = c->grp[g];
+    const size_t off = c->goff[g];
+    s->batch = c->batch;
+    s->sigma = c->sigma + off;
+    s->bad = c->bad + off;
+    s->hx = c->hx + off; s->hz = c->hz + off;
+    s->hacc = c->hacc + off; s->hfail = c->hfail + off;
+    s->fail_planes = c->fail_planes;
+    for (int i = 0; i < 2; i++) {
+        s->flags[i] = c->flags[i] ? c->flags[i] + off : NULL;
+        s->hg[i] = c->hg[i] ? c->hg[i] + off : NULL;
+        s->scan_valid[i] = c->scan_valid[i];
+    }
+    s->have_plain = c->have_plain;
+    s->have_acc = c->have_acc;
+    s->s2_ready = c->s2_ready;
+    s->B1 = c->B1;
+    return s;
+}
+
+static gecm_ctx *multi_curve(gecm_ctx *c, size_t k, int stage, size_t *kk)
+{
+    if (c->batch == 0 || k >= c->nuser) { set_err("curve %zu: no such curve in the batch", k); multi_err = GECM_ERR_ARG; return NULL; }
+    int rc = stage == 1 ? fetch_plain(c) : stage == 2 ? fetch_acc(c) : GECM_OK;
+    if (rc) { multi_err = rc; return NULL; }
+    const size_t pos = c->slot[k];
+    *kk = pos - c->goff[c->pos_grp[pos]];
+    return view_group(c, c->pos_grp[pos]);
+}
+
+int gecm_build_curves_multi(gecm_ctx *c, const uint64_t *sigma, const uint32_t *modulus_index, size_t batch)
+{
+    if (!c || !sigma || !modulus_index || batch == 0) { set_err("gecm_build_curves_multi: bad argument"); return GECM_ERR_ARG; }
+    if (!c->multi) { set_err("gecm_build_curves_multi: not a multi-modulus context (gecm_create_multi)"); return GECM_ERR_STATE; }
+    if (batch >= GECM_PAD) { set_err("gecm_build_curves_multi: batch too large"); return GECM_ERR_ARG; }
+    for (size_t i = 0; i < batch; i++) {
+        if (sigma[i] < 6) { set_err("gecm_build_curves_multi: sigma[%zu] < 6", i); return GECM_ERR_ARG; }
+        if (modulus_index[i] >= c->ngroups) {
+            set_err("gecm_build_curves_multi: modulus_index[%zu] = %u, the context has %zu moduli", i, modulus_index[i], c->ngroups);
+            return GECM_ERR_ARG;
+        }
+    }
+    /* positions: the moduli in order, each one's curves in the caller's order, padded to a multiple of 64 */
+    const size_t ng = c->ngroups;
+    size_t *cnt = (size_t *)calloc(ng, sizeof(size_t)), *goff = (size_t *)calloc(ng, sizeof(size_t));
+    if (!cnt || !goff) { free(cnt); free(goff); return GECM_ERR_NOMEM; }
+    for (size_t i = 0; i < batch; i++) cnt[modulus_index[i]]++;
+    size_t total = 0;
+    for (size_t g = 0; g < ng; g++) { goff[g] = total; total += (cnt[g] + 63) / 64 * 64; }
+    int rc = alloc_batch(c, total);
+    uint32_t *slot = (uint32_t *)malloc(batch * sizeof(uint32_t)), *pos_user = (uint32_t *)malloc(total * sizeof(uint32_t));
+    uint32_t *pos_grp = (uint32_t *)malloc(total * sizeof(uint32_t)), *blocks = (uint32_t *)malloc(total / 64 * sizeof(uint32_t));
+    const size_t words = (size_t)c->nl * total;
+    uint32_t *hX = (uint32_t *)calloc(words * 3, 4);           /* padding stays zero: computed, never read */
+    if (!rc && (!slot || !pos_user || !pos_grp || !blocks || !hX)) rc = GECM_ERR_NOMEM;
+    if (rc) {
+        free(cnt); free(goff); free(slot); free(pos_user); free(pos_grp); free(blocks); free(hX);
+        free_batch(c);
+        return rc;
+    }
+    c->slot = slot; c->pos_user = pos_user; c->pos_grp = pos_grp; c->goff = goff; c->nuser = batch;
+    for (size_t g = 0; g < ng; g++)
+        for (size_t p = goff[g]; p < goff[g] + (cnt[g] + 63) / 64 * 64; p++) {
+            pos_grp[p] = (uint32_t)g;
+            pos_user[p] = GECM_PAD;
+            blocks[p / 64] = (uint32_t)g;
+        }
+    memset(cnt, 0, ng * sizeof(size_t));
+    for (size_t i = 0; i < batch; i++) {
+        const uint32_t g = modulus_index[i];
+        const size_t p = goff[g] + cnt[g]++;
+        slot[i] = (uint32_t)p;
+        pos_user[p] = (uint32_t)i;
+        c->sigma[p] = sigma[i];
+    }
+    /* the Suyama construction modulus by modulus (build_slice on the modulus's view, host threads as gecm_build_curves) */
+    int anybad = 0;
+    for (size_t g = 0; g < ng && !rc; g++) {
+        if (!cnt[g]) continue;
+        gecm_ctx *s = view_group(c, (uint32_t)g);
+        int nt = host_threads();
+        if ((size_t)nt > cnt[g] / 256 + 1) nt = (int)(cnt[g] / 256 + 1);
+        build_job jobs[64];
+        pthread_t th[64];
+        for (int t = 0; t < nt; t++) {
+            jobs[t].c = s; jobs[t].sigma = s->sigma; jobs[t].batch = total;
+            jobs[t].lo = cnt[g] * (size_t)t / (size_t)nt;
+            jobs[t].hi = cnt[g] * (size_t)(t + 1) / (size_t)nt;
+            jobs[t].hX = hX + goff[g]; jobs[t].hZ = hX + words + goff[g]; jobs[t].hS = hX + 2 * words + goff[g];
+            jobs[t].fX = jobs[t].fZ = jobs[t].fS = NULL;
+        }
+        for (int t = 1; t < nt; t++)
+            if (pthread_create(&th[t], NULL, build_slice, &jobs[t])) { build_slice(&jobs[t]); th[t] = 0; }
+        build_slice(&jobs[0]);
+        for (int t = 0; t < nt; t++) {
+            if (t > 0 && th[t]) pthread_join(th[t], NULL);
+            if (jobs[t].rc) rc = jobs[t].rc;
+            anybad |= jobs[t].anybad;
+        }
+    }
+    free(cnt);
+    if (!rc && gecm_dev_upload(c->dev, hX, hX + words, hX + 2 * words)) rc = GECM_ERR_DEVICE;
+    if (!rc) {
+        const uint32_t *q = c->gconst;
+        const size_t w = ng * (size_t)c->nl;
+        if (gecm_dev_set_groups(c->dev, (uint32_t)ng, q, q + w, q + 2 * w, q + 3 * w, q + 4 * w, q + 4 * w + ng, blocks))
+            rc = GECM_ERR_DEVICE;
+    }
+    free(hX);
+    free(blocks);
+    if (rc) {
+        if (rc == GECM_ERR_DEVICE) set_err("gecm_build_curves_multi: %s", gecm_dev_error());
+        free_batch(c);
+        return rc;
+    }
+    return anybad ? 1 : GECM_OK;
+}
+
+int gecm_curve_modulus(const gecm_ctx *c, size_t k)
+{
+    if (!c || !c->multi || k >= c->nuser) { set_err("gecm_curve_modulus: no such curve in a multi-modulus batch"); return GECM_ERR_ARG; }
+    return (int)c->pos_grp[c->slot[k]];
+}
+
+int gecm_curve_acc(gecm_ctx *c, size_t k, char *hex, size_t hexlen)
+{
+    if (!c || !hex) return GECM_ERR_ARG;
+    gecm_ctx *s = c;
+    size_t kk = k;
+    if (c->multi) {
+        if (!(s = multi_curve(c, k, 2, &kk))) return multi_err;
+    } else {
+        if (k >= c->batch) return GECM_ERR_ARG;
+        int rc = fetch_acc(c);
+        if (rc) return rc;
+    }
+    mpl_t v;
+    mpl_from_limbs32(&v, s->hacc + kk, s->batch, s->nl, LIMB_BITS);
+    mpl_mulmod(&v, &v, &s->int_to_ref, &s->N);                   /* what gecm_download_acc returns for the curve */
+    static __thread char tmp[MPL_MAXL * 10 + 2];
+    int n = mpl_get_hex(tmp, &v);
+    if (n < 0 || (size_t)n >= hexlen) { set_err("gecm_curve_acc: buffer too small"); return GECM_ERR_ARG; }
+    memcpy(hex, tmp, (size_t)n + 1);
+    return n;
+}
+
+/* gecm_scan_factors of a multi-modulus context: the device scan compares every curve with its own N; the failure
+ * records of stage 2 are settled against the curve's modulus; padding is never flagged */
+static int multi_scan(gecm_ctx *c, int stage, size_t *first)
+{
+    if (stage == 2 && !c->s2_ready) { set_err("gecm_scan_factors: no stage-2 state"); return GECM_ERR_STATE; }
+    uint32_t **f = &c->flags[stage - 1], **hg = &c->hg[stage - 1];
+    if (!*f) *f = (uint32_t *)calloc(c->batch, sizeof(uint32_t));
+    if (!*hg) *hg = (uint32_t *)calloc(c->batch * (size_t)c->nl, sizeof(uint32_t));
+    if (!*f || !*hg) return GECM_ERR_NOMEM;
+    if (gecm_dev_gcd_scan(c->dev, stage - 1, *f, *hg)) { set_err("gecm_scan_factors: %s", gecm_dev_error()); return GECM_ERR_DEVICE; }
+    int rc = stage == 1 ? fetch_plain(c) : fetch_acc(c);
+    if (rc) return rc;
+    size_t n = 0, lo = c->nuser;
+    for (size_t p = 0; p < c->batch; p++) {
+        if (c->pos_user[p] == GECM_PAD) { (*f)[p] = 0; continue; }
+        if (stage == 2) {                              /* a failed batch inversion also marks its curve (ecm.c:1927-1939) */
+            const uint32_t g = c->pos_grp[p];
+            gecm_ctx *s = view_group(c, g);
+            mpl_t r;
+            fail_record(s, p - c->goff[g], &r);
+            if (!mpl_is_zero(&r)) (*f)[p] = (mpl_cmp_u64(&r, 1) > 0 && mpl_cmp(&r, &s->N) != 0);
+        }
+        if ((*f)[p]) { n++; if (c->pos_user[p] < lo) lo = c->pos_user[p]; }
+    }
+    c->scan_valid[stage - 1] = 1;
+    if (first) *first = lo;
+    return (int)(n > 0x7fffffff ? 0x7fffffff : n);
 }
 
 /* the hash of the host sources this object was compiled from (Makefile: H_SHA); gecm_version() compares them */

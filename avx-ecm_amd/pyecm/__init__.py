@@ -118,6 +118,14 @@ EXPORTS += ["gecm_stage2_init", "gecm_pair_primes", "gecm_pairmap_release", "gec
             "gecm_get_stage2_stats", "gecm_download_acc", "gecm_stage2_factor"]
 
 
+_sig("gecm_create_multi", c_int, ctypes.POINTER(c_void_p), c_int, ctypes.POINTER(c_char_p), c_size_t, c_int)
+_sig("gecm_build_curves_multi", c_int, c_void_p, ctypes.POINTER(c_u64), ctypes.POINTER(ctypes.c_uint32), c_size_t)
+_sig("gecm_moduli", c_size_t, c_void_p)
+_sig("gecm_curve_modulus", c_int, c_void_p, c_size_t)
+_sig("gecm_curve_acc", c_int, c_void_p, c_size_t, c_char_p, c_size_t)
+EXPORTS += ["gecm_create_multi", "gecm_build_curves_multi", "gecm_moduli", "gecm_curve_modulus", "gecm_curve_acc"]
+
+
 class GecmError(RuntimeError):
     pass
 
@@ -381,3 +389,41 @@ class Engine:
         buf = ctypes.create_string_buffer(256)
         _chk(lib.gecm_device_name(self._h, buf, len(buf)), "gecm_device_name")
         return buf.value.decode()
+
+
+class MultiEngine(Engine):
+    """One multi-modulus gecm_ctx: curves on many numbers in one batch.  Curve k is the k-th sigma of
+    build_curves; every per-curve call works against that curve's own number.  The calls that need one N (L0
+    operators, uploaded points, reference-radix downloads, special forms, report modulus) raise GecmError."""
+
+    def __init__(self, ns, digitbits=52, device=0):
+        self._h = c_void_p()
+        strs = [str(n).encode() for n in ns]
+        arr = (c_char_p * max(1, len(strs)))(*strs)
+        _chk(lib.gecm_create_multi(ctypes.byref(self._h), device, arr, len(strs), digitbits), "gecm_create_multi")
+        self.cfg = Config()
+        _chk(lib.gecm_get_config(self._h, ctypes.byref(self.cfg)), "gecm_get_config")
+        self.ns = [int(str(n), 0) if isinstance(n, str) else int(n) for n in ns]
+        self.n = max(self.ns)
+        self.batch = 0
+
+    def build_curves(self, sigmas, which):
+        """curve k: sigma sigmas[k] on number ns[which[k]]"""
+        if len(which) != len(sigmas):
+            raise ValueError("build_curves: one modulus index per sigma")
+        arr = (c_u64 * len(sigmas))(*sigmas)
+        idx = (ctypes.c_uint32 * len(which))(*which)
+        self.batch = len(sigmas)
+        return _chk(lib.gecm_build_curves_multi(self._h, arr, idx, len(sigmas)), "gecm_build_curves_multi")
+
+    def modulus_of(self, k):
+        return _chk(lib.gecm_curve_modulus(self._h, k), "gecm_curve_modulus")
+
+    def acc(self, k):
+        """curve k's stage-2 accumulator: the value Engine(ns[modulus_of(k)]).download_acc() gives for it"""
+        buf = ctypes.create_string_buffer(1024)
+        _chk(lib.gecm_curve_acc(self._h, k, buf, len(buf)), "gecm_curve_acc")
+        return int(buf.value.decode(), 16)
+
+    def accs(self):
+        return [self.acc(k) for k in range(self.batch)]

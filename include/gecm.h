@@ -282,6 +282,33 @@ int gecm_download_acc(gecm_ctx *ctx, void *acc);
  * factor if 1 < g < N, else 0.                                                                  */
 int gecm_stage2_factor(gecm_ctx *ctx, size_t k, char *dec, size_t declen, int *is_prp);
 
+/* ---- multi-modulus batches --------------------------------------------------
+ * One context for curves on many numbers at once: the way to pretest a list of composites (aliquot or Cunningham
+ * cofactors, NFS leftovers) with a few thousand curves each without leaving most of the chip idle.
+ * gecm_create_multi: count numbers (decimal or 0x-hex; each odd, > 1 and within the size cap of gecm_create).  The
+ *   device limb count is the one the largest needs; each number gets its own constants at that count.
+ * gecm_build_curves_multi: curve i has sigma[i] on number modulus_index[i] (< count), in any order.  The library
+ *   groups the curves by number and pads each group to whole wavefronts of 64 curves: padding lanes are computed and
+ *   dropped, so a list with 8 curves per number runs at 1/8 of the chip's throughput (gecm_batch_bytes counts the
+ *   padding, at most 63 curves per number).  Returns 1 like gecm_build_curves when a denominator was not invertible.
+ * Curve indices k of every per-curve call are the caller's i.  These work per curve against that curve's number,
+ * exactly as they do on a single-N context of it: gecm_stage1, gecm_stage1_range, gecm_sync, gecm_stage2*,
+ * gecm_format_save_line, gecm_format_resume_line, gecm_stage1_factor, gecm_stage2_factor, gecm_scan_factors (*first:
+ * the lowest flagged caller index), gecm_curve_flag.  Stage 1 runs with 1 or 2 lanes per curve (0 = chosen by batch
+ * size as for one number), stage 2 with one sub-sequence per curve.
+ * GECM_ERR_STATE on a multi-modulus context: the L0 operators, gecm_get_one, gecm_upload_points, gecm_download_points,
+ * gecm_download_points_plain, gecm_download_acc (the reference radix differs from number to number),
+ * gecm_build_curves, gecm_set_special_form, gecm_set_report_modulus; gecm_build_curves_multi on a single-N context.
+ * gecm_get_config describes the largest number.                                                                     */
+int gecm_create_multi(gecm_ctx **out, int device, const char *const *n_strs, size_t count, int digitbits);
+int gecm_build_curves_multi(gecm_ctx *ctx, const uint64_t *sigma, const uint32_t *modulus_index, size_t batch);
+/* numbers of the context (1 for a single-N context), and the number curve k runs on */
+size_t gecm_moduli(const gecm_ctx *ctx);
+int gecm_curve_modulus(const gecm_ctx *ctx, size_t k);
+/* the stage-2 accumulator of curve k as the integer gecm_download_acc returns for it on a single-N context of its
+ * number (reference Montgomery radix, canonical), in lower-case hex without prefix; returns the digit count */
+int gecm_curve_acc(gecm_ctx *ctx, size_t k, char *hex, size_t hexlen);
+
 #ifdef __cplusplus
 }
 #endif
