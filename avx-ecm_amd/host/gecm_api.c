@@ -1,25 +1,23 @@
-/* gecm_api.c — public C ABI of libgecm (include/gecm.h): host logic in C above the HIP device
- * layer (csrc/gecm_dev.h).  Mirrors the reference's setup and phase functions:
- *   Montgomery constants        main.c:597-640
- *   NWORDS/MAXBITS rule         main.c:465-483
- *   build_one_curve             ecm.c:1548-1803
+/* gecm_api.c — public C ABI of libgecm (include/gecm.h): the contexts, their batch state and the phase functions, in
+ * C above the HIP device layer (csrc/gecm_dev.h).  What depends on one number N alone — its constants, the curve
+ * construction, failure records, the factor report — is gecm_mod.c, which knows neither device nor context; a context
+ * holds the gecm_mod of its number, a multi-modulus context one more per modulus, and curve_at() leads from a caller's
+ * curve to its modulus and its place in the batch arrays.  Mirrors the reference's phase functions:
  *   ecm_stage1                  ecm.c:1806-1854 (tape built by gecm_plan.c, run by the device)
- *   save line / check_factor    ecm.c:1319-1388, 2542-2557
+ *   save line                   ecm.c:1372-1380
  */
 #include "../../include/gecm.h"
 #include "../csrc/gecm_dev.h"
 #include "gecm_plan.h"
 #include "gecm_pair.h"
-#include "mpl.h"
+#include "gecm_mod.h"
 #include "cunningham.h"
 #include <pthread.h>
-#include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include <unistd.h>
 
-#define LIMB_BITS 28
 /* stage 2: giant steps per device chunk (one inversion each) and ring size (power of two >= chunk + 2L) */
 #define S2_GIANT_CHUNK 512u
 #define S2_RING 1024u
@@ -29,15 +27,8 @@
 #define GECM_B1_MAX 1000000000000ull
 #define gecm_stage1_ranges_u(b1) gecm_stage1_ranges_plan(b1)
 
-static __thread char g_err[512];
-static void set_err(const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof g_err, fmt, ap);
-    va_end(ap);
-}
-const char *gecm_last_error(void) { return g_err; }
+#define set_err gecm_mod_set_err
+const char *gecm_last_error(void) { return gecm_mod_err; }
 /* "libgecm 0.3 (gfx950) K:<hash> R:<hash> D:<hash> H:<hash>": the hashes of the sources the objects inside this
  * library were compiled from (avx-ecm_amd/Makefile: kernels, 32-lane kernels, device layer, host C), MIXED where
  * objects of one group disagree.  tests/test_abi_cpu.py and __graft_entry__.smoke() recompute them from the tree. */
@@ -49,14 +40,15 @@ const char *gecm_manifest_host_gecm_pair(void);
 const char *gecm_manifest_host_mpl(void);
 const char *gecm_manifest_host_calc_lite(void);
 const char *gecm_manifest_host_cunningham(void);
+const char *gecm_manifest_host_gecm_mod(void);
 const char *gecm_version(void)
 {
     static char v[256];
     if (!v[0]) {
-        const char *h[5] = {gecm_manifest_host_gecm_plan(), gecm_manifest_host_gecm_pair(), gecm_manifest_host_mpl(),
-                            gecm_manifest_host_calc_lite(), gecm_manifest_host_cunningham()};
+        const char *h[6] = {gecm_manifest_host_gecm_plan(), gecm_manifest_host_gecm_pair(), gecm_manifest_host_mpl(),
+                            gecm_manifest_host_calc_lite(), gecm_manifest_host_cunningham(), gecm_manifest_host_gecm_mod()};
         int mixed = 0;
-        for (int i = 0; i < 5; i++) mixed |= strcmp(h[i], GECM_MANIFEST) != 0;
+        for (int i = 0; i < 6; i++) mixed |= strcmp(h[i], GECM_MANIFEST) != 0;
         snprintf(v, sizeof v, "libgecm 0.3 (gfx950) %s H:%s", gecm_dev_manifest(), mixed ? "MIXED" : GECM_MANIFEST);
     }
     return v;
@@ -64,17 +56,8 @@ const char *gecm_version(void)
 int gecm_device_count(void) { return gecm_dev_count(); }
 
 struct gecm_ctx {
-    int device, digitbits, nwords, maxbits, nbits, nl;
-    mpl_t N;
-    mpl_t N_report;      /* gecm_set_report_modulus: the number the save lines name and factors are looked for in */
-    int have_report;
-    mpl_t rref_mod_n;    /* 2^(digitbits*nwords) mod N  = the reference's "one" */
-    mpl_t rint_mod_n;    /* 2^(28*nl) mod N */
-    mpl_t ref_to_int;    /* Rint * Rref^-1 mod N : x*Rref -> x*Rint by plain modular multiply */
-    mpl_t int_to_ref;    /* Rref * Rint^-1 mod N */
-    uint64_t rho_ref;
-    uint32_t rho28;
-    uint32_t *n28, *kp28, *one28, *fix28; /* fix28 = Rint^2/Rref mod N (see gecm_dev_l0) */
+    int device;
+    gecm_mod mod;        /* the context's number; of a multi-modulus context the largest (what gecm_get_config reports) */
     gecm_dev *dev, *dev_l0;
     /* current batch */
     size_t batch;
@@ -99,7 +82,6 @@ struct gecm_ctx {
     uint64_t pf_B1;
     uint32_t pf_range;
     /* stage 2 */
-    uint32_t *r3_28;
     gecm_s2_plan s2;
     int s2_ready;
     uint32_t *hacc, *hfail;
@@ -131,28 +113,19 @@ struct gecm_ctx {
     uint32_t ff_tape_range;
     mpl_t ff_M, ff_r_mod_m;  /* Mw; 2^(28 ff_nl) mod Mw */
     uint32_t *ff_n28;        /* n, kp, one for dev_f */
-    uint32_t inv_iters;      /* batches of 28 division steps after which the device inversion has converged for N */
-    /* multi-modulus context (gecm_create_multi): one host-only context per modulus holds its N and
-     * constants (at this context's limb count); the curves are grouped by modulus, each group padded to whole
-     * wavefronts of 64, and the batch arrays are in that device order.  The caller numbers curves in its own order. */
+    /* multi-modulus context (gecm_create_multi): grp[] holds every modulus's N and constants (at this
+     * context's limb count); the curves are grouped by modulus, each group padded to whole wavefronts of 64, and the
+     * batch arrays are in that device order.  The caller numbers curves in its own order (curve_at). */
     int multi;
     size_t ngroups;
-    gecm_ctx **grp;
+    gecm_mod *grp;
     uint32_t *gconst;        /* the moduli's n, kp, one, r3 ([4][ngroups][nl]), then rho and inv_iters [ngroups] each */
     size_t nuser;            /* curves the caller built */
     uint32_t *slot;          /* caller's curve -> device position */
     uint32_t *pos_user;      /* device position -> caller's curve, GECM_PAD for padding */
     uint32_t *pos_grp;       /* device position -> modulus */
-    size_t *goff;            /* first device position of each modulus */
 };
 #define GECM_PAD 0xffffffffu
-
-/* multi-modulus contexts (at the end of this file): the host-only context of curve k's modulus, viewing the batch
- * at that modulus's positions (stage 1 or 2: the results that stage needs fetched first), *kk = the curve there; NULL
- * with the status in multi_err */
-static __thread int multi_err;
-static gecm_ctx *multi_curve(gecm_ctx *c, size_t k, int stage, size_t *kk);
-static int multi_scan(gecm_ctx *c, int stage, size_t *first);
 
 /* what a multi-modulus context cannot do: the reference radix (NWORDS) differs from modulus to modulus, and the L0
  * operators, uploaded points and the special forms work modulo one N */
@@ -162,39 +135,12 @@ static int multi_refuse(const char *fn)
     return GECM_ERR_STATE;
 }
 
-
 static int pick_nl(int nbits)
 {
     int need = (nbits + 5 + LIMB_BITS - 1) / LIMB_BITS;   /* R = 2^(28 nl) >= 32 N */
     for (const int *p = gecm_dev_supported_nl(); *p; p++)
         if (*p >= need) return *p;
     return 0;
-}
-
-/* K' for the lazy subtraction (csrc/gecm_field.hpp): K = 2^j * mod in [R/32, R/16), written with every
- * limb in [2^28-1, 2^29): +2^28 at limb 0, +2^28-1 in the middle, -1 at the top. */
-static int make_kp(uint32_t *kp, const mpl_t *mod, int nl)
-{
-    mpl_t K;
-    uint32_t *kl = (uint32_t *)calloc((size_t)nl, sizeof(uint32_t));
-    if (!kl) return -1;
-    mpl_shl(&K, mod, (unsigned)(LIMB_BITS * nl - 4 - mpl_bits(mod)));
-    mpl_to_limbs32(kl, 1, nl, LIMB_BITS, &K);
-    for (int i = 0; i < nl; i++) {
-        if (i == 0) kp[i] = kl[i] + (1u << LIMB_BITS);
-        else if (i < nl - 1) kp[i] = kl[i] + (1u << LIMB_BITS) - 1;
-        else kp[i] = kl[i] - 1;
-    }
-    free(kl);
-    return 0;
-}
-
-static void pow2_mod(mpl_t *r, unsigned e, const mpl_t *m)
-{
-    mpl_t t;
-    mpl_set_u64(&t, 1);
-    mpl_shl(&t, &t, e);
-    mpl_mod(r, &t, m);
 }
 
 /* N | 2^k - 1, N | 2^k + 1 or N | 2^k - c with c below one reference limb (the reference's isMersenne == +1 / -1 / c,
@@ -204,7 +150,7 @@ static void pow2_mod(mpl_t *r, unsigned e, const mpl_t *m)
 static void ff_setup(gecm_ctx *c)
 {
     cunningham_form f;
-    cunningham_detect(&f, &c->N, c->digitbits);
+    cunningham_detect(&f, &c->mod.N, c->mod.digitbits);
     if ((f.form != 1 && f.form != -1 && f.form != 2) || f.k < 64) return;
     if (f.form == 2 && (f.c < 3 || !(f.c & 1))) return;              /* 2^k - c with c odd, c > 1 (c = 1 is form +1) */
     const int mbits = f.form < 0 ? f.k + 1 : f.k;
@@ -214,15 +160,15 @@ static void ff_setup(gecm_ctx *c)
     if (G < 0 || f.k < LIMB_BITS * (nlf - G)) return;                 /* limbs below nl-G must be F..F / 1,0..0 */
     if (f.form == 2 && nlf - G < 3) return;                          /* limbs 0, 1 carry c - 1: one pure F limb above */
     /* multiply-adds per modular multiplication: about nl^2 + G*nl (+ 3 nl for 2^k - c) against 2 nl^2 + nl */
-    if ((double)(nlf * nlf + (G + (f.form == 2 ? 3 : 0)) * nlf) * 1.15 > (double)(2 * c->nl * c->nl + c->nl)) return;
+    if ((double)(nlf * nlf + (G + (f.form == 2 ? 3 : 0)) * nlf) * 1.15 > (double)(2 * c->mod.nl * c->mod.nl + c->mod.nl)) return;
     mpl_t one, t;
     mpl_set_u64(&one, 1);
     mpl_shl(&c->ff_M, &one, (unsigned)f.k);
     if (f.form == 2) { mpl_set_u64(&t, f.c); mpl_sub(&c->ff_M, &c->ff_M, &t); }
     else if (f.form > 0) mpl_sub(&c->ff_M, &c->ff_M, &one);
     else mpl_add(&c->ff_M, &c->ff_M, &one);
-    { mpl_t r; mpl_mod(&r, &c->ff_M, &c->N); if (!mpl_is_zero(&r)) return; }   /* N | Mw, or nothing below holds */
-    pow2_mod(&c->ff_r_mod_m, (unsigned)(LIMB_BITS * nlf), &c->ff_M);
+    { mpl_t r; mpl_mod(&r, &c->ff_M, &c->mod.N); if (!mpl_is_zero(&r)) return; }   /* N | Mw, or nothing below holds */
+    gecm_mod_pow2(&c->ff_r_mod_m, (unsigned)(LIMB_BITS * nlf), &c->ff_M);
     c->ff_n28 = (uint32_t *)calloc((size_t)nlf * 3, sizeof(uint32_t));
     if (!c->ff_n28) return;
     mpl_to_limbs32(c->ff_n28, 1, nlf, LIMB_BITS, &c->ff_M);
@@ -236,7 +182,7 @@ static void ff_setup(gecm_ctx *c)
         mpl_sub(&inv, &two28, &inv);
         rho = (uint32_t)mpl_get_u64(&inv);
     }
-    if (make_kp(c->ff_n28 + nlf, &c->ff_M, nlf) ||
+    if (gecm_mod_make_kp(c->ff_n28 + nlf, &c->ff_M, nlf) ||
         gecm_dev_open(&c->dev_f, c->device, nlf, c->ff_n28, c->ff_n28 + nlf, c->ff_n28 + 2 * nlf, rho)) {
         free(c->ff_n28);
         c->ff_n28 = NULL;
@@ -257,7 +203,7 @@ static void ff_setup(gecm_ctx *c)
  * (modulo N itself) turns it back.  Not an error if it cannot be set up: the other layouts cover every N. */
 static void row_setup(gecm_ctx *c)
 {
-    const int nl = c->nl;
+    const int nl = c->mod.nl;
     int nq, L;                                        /* L = rows of a multiply = limbs in use: 28 (nl + 1) >= bits(N') + 5 */
     gecm_row_shape(nl, &nq, &L);
     if (nq > GECM_ROW_MAXNQ) return;
@@ -265,79 +211,18 @@ static void row_setup(gecm_ctx *c)
     memset(w, 0, sizeof w);
     mpl_t two28, inv, m, np, t;
     mpl_set_u64(&two28, 1u << LIMB_BITS);
-    if (!mpl_invmod(&inv, &c->N, &two28)) return;
+    if (!mpl_invmod(&inv, &c->mod.N, &two28)) return;
     mpl_sub(&m, &two28, &inv);                        /* m = -N^-1 mod 2^28, in [1, 2^28) */
-    mpl_mul(&np, &m, &c->N);
+    mpl_mul(&np, &m, &c->mod.N);
     if (mpl_bits(&np) + 5 > LIMB_BITS * L) return;
     mpl_to_limbs32(w + 0 * GECM_ROW_WORDS, 1, L, LIMB_BITS, &np);
     if (w[0] != (1u << LIMB_BITS) - 1u) return;
-    memcpy(w + 1 * GECM_ROW_WORDS, c->n28, (size_t)nl * sizeof(uint32_t));
-    pow2_mod(&t, (unsigned)(2 * LIMB_BITS * L - LIMB_BITS * nl), &c->N);
+    memcpy(w + 1 * GECM_ROW_WORDS, c->mod.n28, (size_t)nl * sizeof(uint32_t));
+    gecm_mod_pow2(&t, (unsigned)(2 * LIMB_BITS * L - LIMB_BITS * nl), &c->mod.N);
     mpl_to_limbs32(w + 2 * GECM_ROW_WORDS, 1, nl, LIMB_BITS, &t);
-    memcpy(w + 3 * GECM_ROW_WORDS, c->one28, (size_t)nl * sizeof(uint32_t));
-    memcpy(w + 4 * GECM_ROW_WORDS, c->kp28, (size_t)nl * sizeof(uint32_t));
+    memcpy(w + 3 * GECM_ROW_WORDS, c->mod.one28, (size_t)nl * sizeof(uint32_t));
+    memcpy(w + 4 * GECM_ROW_WORDS, c->mod.kp28, (size_t)nl * sizeof(uint32_t));
     (void)gecm_dev_set_rowconst(c->dev, nq, L, w);
-}
-
-/* N and everything derived from it, at nl limbs (0: the fewest that hold N); `who` prefixes the error texts.  Nothing on
- * the device.  On error c holds nothing to free. */
-static int ctx_setup_n(gecm_ctx *c, const char *who, const char *n_str, int digitbits, int nl)
-{
-    if (mpl_set_str(&c->N, n_str) || !mpl_is_odd(&c->N) || mpl_cmp_u64(&c->N, 3) < 0) {
-        set_err("%s: N must be an odd integer >= 3 (decimal or 0x-hex)", who);
-        return GECM_ERR_ARG;
-    }
-    c->digitbits = digitbits;
-    c->nbits = mpl_bits(&c->N);
-    /* main.c:465-483: MAXBITS = smallest multiple of 208 (128) strictly greater than bitlen */
-    int step = digitbits == 52 ? 208 : 128;
-    c->maxbits = step;
-    while (c->maxbits <= c->nbits) c->maxbits += step;
-    c->nwords = c->maxbits / digitbits;
-    c->nl = nl ? nl : pick_nl(c->nbits);
-    if (!pick_nl(c->nbits) || c->maxbits + 64 > MPL_MAXL * 16) {
-        set_err("%s: N of %d bits is larger than this build supports", who, c->nbits);
-        return GECM_ERR_ARG;
-    }
-    nl = c->nl;
-    unsigned rint_bits = (unsigned)(LIMB_BITS * nl), rref_bits = (unsigned)c->maxbits;
-    mpl_t t, inv;
-    pow2_mod(&c->rref_mod_n, rref_bits, &c->N);
-    pow2_mod(&c->rint_mod_n, rint_bits, &c->N);
-    mpl_invmod(&inv, &c->rref_mod_n, &c->N);
-    mpl_mulmod(&c->ref_to_int, &c->rint_mod_n, &inv, &c->N);
-    mpl_invmod(&inv, &c->rint_mod_n, &c->N);
-    mpl_mulmod(&c->int_to_ref, &c->rref_mod_n, &inv, &c->N);
-    /* rho = -N^-1 mod 2^digitbits (main.c:627-628, 636-640) and mod 2^28 */
-    mpl_t two64;
-    mpl_set_u64(&two64, 1);
-    mpl_shl(&two64, &two64, 64);
-    mpl_invmod(&inv, &c->N, &two64);
-    mpl_sub(&t, &two64, &inv);
-    uint64_t nhat = mpl_get_u64(&t);
-    c->rho_ref = digitbits == 52 ? (nhat & 0xfffffffffffffull) : (nhat & 0xffffffffull);
-    c->rho28 = (uint32_t)(nhat & ((1u << LIMB_BITS) - 1));
-    c->n28 = (uint32_t *)calloc((size_t)nl * 4, sizeof(uint32_t));
-    if (!c->n28) return GECM_ERR_NOMEM;
-    c->kp28 = c->n28 + nl;
-    c->one28 = c->kp28 + nl;
-    c->fix28 = c->one28 + nl;
-    mpl_to_limbs32(c->n28, 1, nl, LIMB_BITS, &c->N);
-    mpl_to_limbs32(c->one28, 1, nl, LIMB_BITS, &c->rint_mod_n);
-    if (make_kp(c->kp28, &c->N, nl)) { free(c->n28); c->n28 = NULL; return GECM_ERR_NOMEM; }
-    /* fix = Rint^2 / Rref mod N = Rint * ref_to_int */
-    mpl_mulmod(&t, &c->rint_mod_n, &c->ref_to_int, &c->N);
-    mpl_to_limbs32(c->fix28, 1, nl, LIMB_BITS, &t);
-    /* R^3 mod N for the device inversion (csrc/gecm_stage2.hpp: fe_inv_mont) */
-    c->r3_28 = (uint32_t *)calloc((size_t)nl, sizeof(uint32_t));
-    if (!c->r3_28) { free(c->n28); c->n28 = NULL; return GECM_ERR_NOMEM; }
-    mpl_mulmod(&t, &c->rint_mod_n, &c->rint_mod_n, &c->N);
-    mpl_mulmod(&t, &t, &c->rint_mod_n, &c->N);
-    mpl_to_limbs32(c->r3_28, 1, nl, LIMB_BITS, &t);
-    /* batches of 28 division steps after which the device inversion has converged for a modulus of nbits bits:
-     * the bound of the "half-delta" variant, floor((45907 bits + 26313) / 19929), +1, rounded up to whole batches */
-    c->inv_iters = (uint32_t)((((45907ull * (unsigned)c->nbits + 26313ull) / 19929ull + 1) + 27) / 28);
-    return GECM_OK;
 }
 
 int gecm_create(gecm_ctx **out, int device, const char *n_str, int digitbits)
@@ -348,17 +233,16 @@ int gecm_create(gecm_ctx **out, int device, const char *n_str, int digitbits)
     }
     gecm_ctx *c = (gecm_ctx *)calloc(1, sizeof *c);
     if (!c) return GECM_ERR_NOMEM;
-    int rc = ctx_setup_n(c, "gecm_create", n_str, digitbits, 0);
+    int rc = gecm_mod_setup(&c->mod, "gecm_create", n_str, digitbits, 0, pick_nl);
     if (rc) { free(c); return rc; }
     c->device = device;
-    if (gecm_dev_open(&c->dev, device, c->nl, c->n28, c->kp28, c->one28, c->rho28)) {
+    if (gecm_dev_open(&c->dev, device, c->mod.nl, c->mod.n28, c->mod.kp28, c->mod.one28, c->mod.rho28)) {
         set_err("gecm_create: %s", gecm_dev_error());
-        free(c->r3_28);
-        free(c->n28);
+        gecm_mod_free(&c->mod);
         free(c);
         return GECM_ERR_DEVICE;
     }
-    gecm_dev_set_s2const(c->dev, c->r3_28, c->inv_iters);
+    gecm_dev_set_s2const(c->dev, c->mod.r3_28, c->mod.inv_iters);
     row_setup(c);
     ff_setup(c);
     *out = c;
@@ -373,9 +257,8 @@ static void free_batch(gecm_ctx *c)
     c->hg[0] = c->hg[1] = NULL;
     c->scan_valid[0] = c->scan_valid[1] = 0;
     c->sigma = NULL; c->bad = NULL; c->hx = c->hz = NULL; c->hacc = c->hfail = NULL;
-    free(c->slot); free(c->pos_user); free(c->pos_grp); free(c->goff);
+    free(c->slot); free(c->pos_user); free(c->pos_grp);
     c->slot = c->pos_user = c->pos_grp = NULL;
-    c->goff = NULL;
     c->nuser = 0;
     c->have_acc = 0; c->s2_ready = 0;
     c->batch = 0;
@@ -410,10 +293,8 @@ void gecm_destroy(gecm_ctx *c)
     gecm_s2_plan_free(&c->s2);
     drop_kept_pairmap(c);
     if (c->ptp_valid) free(c->ptp.words);
-    free(c->r3_28);
-    free(c->n28);
-    for (size_t g = 0; g < c->ngroups; g++)
-        if (c->grp[g]) { free(c->grp[g]->r3_28); free(c->grp[g]->n28); free(c->grp[g]); }   /* host-only views */
+    gecm_mod_free(&c->mod);
+    for (size_t g = 0; g < c->ngroups; g++) gecm_mod_free(&c->grp[g]);
     free(c->grp);
     free(c->gconst);
     free(c);
@@ -426,35 +307,27 @@ int gecm_set_report_modulus(gecm_ctx *c, const char *n_str)
 {
     if (!c) return GECM_ERR_ARG;
     if (c && c->multi) return multi_refuse("gecm_set_report_modulus");
-    if (!n_str) { c->have_report = 0; return GECM_OK; }
+    if (!n_str) { c->mod.have_report = 0; return GECM_OK; }
     mpl_t r, m;
     if (mpl_set_str(&r, n_str) || mpl_cmp_u64(&r, 1) <= 0) { set_err("gecm_set_report_modulus: bad number"); return GECM_ERR_ARG; }
-    mpl_mod(&m, &c->N, &r);
+    mpl_mod(&m, &c->mod.N, &r);
     if (!mpl_is_zero(&m)) { set_err("gecm_set_report_modulus: the number must divide the context's modulus"); return GECM_ERR_ARG; }
-    c->N_report = r;
-    c->have_report = 1;
+    c->mod.N_report = r;
+    c->mod.have_report = 1;
     c->scan_valid[0] = c->scan_valid[1] = 0;
     return GECM_OK;
-}
-
-static const mpl_t *report_n(const gecm_ctx *c) { return c->have_report ? &c->N_report : &c->N; }
-
-/* g = gcd(value, context modulus) -> the factor of the report modulus it holds */
-static void to_report(const gecm_ctx *c, mpl_t *g)
-{
-    if (c->have_report && !mpl_is_zero(g)) { mpl_t t = *g; mpl_gcd(g, &t, &c->N_report); }
 }
 
 int gecm_get_config(const gecm_ctx *c, gecm_config *cfg)
 {
     if (!c || !cfg) return GECM_ERR_ARG;
-    cfg->digitbits = c->digitbits;
-    cfg->nwords = c->nwords;
-    cfg->maxbits = c->maxbits;
-    cfg->nbits = c->nbits;
-    cfg->dev_limbs = c->nl;
+    cfg->digitbits = c->mod.digitbits;
+    cfg->nwords = c->mod.nwords;
+    cfg->maxbits = c->mod.maxbits;
+    cfg->nbits = c->mod.nbits;
+    cfg->dev_limbs = c->mod.nl;
     cfg->device = c->device;
-    cfg->rho = c->rho_ref;
+    cfg->rho = c->mod.rho_ref;
     return GECM_OK;
 }
 
@@ -496,23 +369,23 @@ int gecm_device_name(gecm_ctx *c, char *buf, size_t len)
 }
 
 /* ---- reference vec layout <-> mpl ---------------------------------------------------------- */
-static void vec_get(const gecm_ctx *c, mpl_t *r, const void *vec, size_t batch, size_t lane)
+static void vec_get(const gecm_mod *m, mpl_t *r, const void *vec, size_t batch, size_t lane)
 {
-    if (c->digitbits == 52) mpl_from_limbs64(r, (const uint64_t *)vec + lane, batch, c->nwords, 52);
-    else mpl_from_limbs32(r, (const uint32_t *)vec + lane, batch, c->nwords, 32);
+    if (m->digitbits == 52) mpl_from_limbs64(r, (const uint64_t *)vec + lane, batch, m->nwords, 52);
+    else mpl_from_limbs32(r, (const uint32_t *)vec + lane, batch, m->nwords, 32);
 }
 
-static void vec_put(const gecm_ctx *c, void *vec, size_t batch, size_t lane, const mpl_t *v)
+static void vec_put(const gecm_mod *m, void *vec, size_t batch, size_t lane, const mpl_t *v)
 {
-    if (c->digitbits == 52) mpl_to_limbs64((uint64_t *)vec + lane, batch, c->nwords, 52, v);
-    else mpl_to_limbs32((uint32_t *)vec + lane, batch, c->nwords, 32, v);
+    if (m->digitbits == 52) mpl_to_limbs64((uint64_t *)vec + lane, batch, m->nwords, 52, v);
+    else mpl_to_limbs32((uint32_t *)vec + lane, batch, m->nwords, 32, v);
 }
 
 int gecm_get_one(const gecm_ctx *c, void *one_limbs)
 {
     if (!c || !one_limbs) return GECM_ERR_ARG;
     if (c && c->multi) return multi_refuse("gecm_get_one");
-    vec_put(c, one_limbs, 1, 0, &c->rref_mod_n);
+    vec_put(&c->mod, one_limbs, 1, 0, &c->mod.rref_mod_n);
     return GECM_OK;
 }
 
@@ -522,34 +395,34 @@ static int l0_call(gecm_ctx *c, int op, const void *a, const void *b, void *r0, 
     if (c && c->multi) return multi_refuse("the L0 operators");
     if (!c || !a || !r0 || batch == 0) { set_err("L0: bad argument"); return GECM_ERR_ARG; }
     if (!c->dev_l0 &&
-        gecm_dev_open(&c->dev_l0, c->device, c->nl, c->n28, c->kp28, c->one28, c->rho28)) {
+        gecm_dev_open(&c->dev_l0, c->device, c->mod.nl, c->mod.n28, c->mod.kp28, c->mod.one28, c->mod.rho28)) {
         set_err("L0: %s", gecm_dev_error());
         return GECM_ERR_DEVICE;
     }
-    int nl = c->nl;
+    int nl = c->mod.nl;
     size_t words = (size_t)nl * batch;
     uint32_t *ha = (uint32_t *)malloc(words * 4 * 4);
     if (!ha) return GECM_ERR_NOMEM;
     uint32_t *hb = ha + words, *hc = hb + words, *hd = hc + words;
     mpl_t v;
     for (size_t i = 0; i < batch; i++) {
-        vec_get(c, &v, a, batch, i);
-        if (mpl_cmp(&v, &c->N) >= 0) { free(ha); set_err("L0: operand a[%zu] not < N", i); return GECM_ERR_ARG; }
+        vec_get(&c->mod, &v, a, batch, i);
+        if (mpl_cmp(&v, &c->mod.N) >= 0) { free(ha); set_err("L0: operand a[%zu] not < N", i); return GECM_ERR_ARG; }
         mpl_to_limbs32(ha + i, batch, nl, LIMB_BITS, &v);
         if (b) {
-            vec_get(c, &v, b, batch, i);
-            if (mpl_cmp(&v, &c->N) >= 0) { free(ha); set_err("L0: operand b[%zu] not < N", i); return GECM_ERR_ARG; }
+            vec_get(&c->mod, &v, b, batch, i);
+            if (mpl_cmp(&v, &c->mod.N) >= 0) { free(ha); set_err("L0: operand b[%zu] not < N", i); return GECM_ERR_ARG; }
         }
         mpl_to_limbs32(hb + i, batch, nl, LIMB_BITS, &v);
     }
-    int rc = gecm_dev_l0(c->dev_l0, op, ha, hb, hc, hd, batch, c->fix28);
+    int rc = gecm_dev_l0(c->dev_l0, op, ha, hb, hc, hd, batch, c->mod.fix28);
     if (rc) { free(ha); set_err("L0: %s", gecm_dev_error()); return GECM_ERR_DEVICE; }
     for (size_t i = 0; i < batch; i++) {
         mpl_from_limbs32(&v, hc + i, batch, nl, LIMB_BITS);
-        vec_put(c, r0, batch, i, &v);
+        vec_put(&c->mod, r0, batch, i, &v);
         if (op == GECM_L0_ADDSUB) {
             mpl_from_limbs32(&v, hd + i, batch, nl, LIMB_BITS);
-            vec_put(c, r1, batch, i, &v);
+            vec_put(&c->mod, r1, batch, i, &v);
         }
     }
     free(ha);
@@ -583,10 +456,10 @@ static int alloc_batch(gecm_ctx *c, size_t batch)
     free_batch(c);
     c->sigma = (uint64_t *)calloc(batch, sizeof(uint64_t));
     c->bad = (uint8_t *)calloc(batch, 1);
-    c->hx = (uint32_t *)calloc(batch * (size_t)c->nl, 4);
-    c->hz = (uint32_t *)calloc(batch * (size_t)c->nl, 4);
-    c->hacc = (uint32_t *)calloc(batch * (size_t)c->nl, 4);
-    c->hfail = (uint32_t *)calloc(batch * (size_t)c->nl, 4);
+    c->hx = (uint32_t *)calloc(batch * (size_t)c->mod.nl, 4);
+    c->hz = (uint32_t *)calloc(batch * (size_t)c->mod.nl, 4);
+    c->hacc = (uint32_t *)calloc(batch * (size_t)c->mod.nl, 4);
+    c->hfail = (uint32_t *)calloc(batch * (size_t)c->mod.nl, 4);
     c->fail_planes = 1;
     if (!c->sigma || !c->bad || !c->hx || !c->hz || !c->hacc || !c->hfail) { free_batch(c); return GECM_ERR_NOMEM; }
     c->batch = batch;
@@ -595,120 +468,6 @@ static int alloc_batch(gecm_ctx *c, size_t batch)
     c->ff_loaded = 0;
     if (c->dev_f && gecm_dev_resize(c->dev_f, batch)) { set_err("%s", gecm_dev_error()); return GECM_ERR_DEVICE; }
     return GECM_OK;
-}
-
-/* Suyama curve for one sigma up to (but not including) the two modular inversions
- * (ecm.c:1587-1641, 1717-1722): outputs x3 = u^3 mod n, z3 = v^3 mod n, num = (v-u)^3 (3u+v) mod n,
- * den = 16 u^3 v mod n. */
-static void suyama_pre(const mpl_t *n, uint64_t sigma, mpl_t *x3, mpl_t *z3, mpl_t *num, mpl_t *den)
-{
-    mpl_t u, v, t1, t2, t3, t4;
-    mpl_set_u64(&v, sigma);
-    mpl_shl(&v, &v, 2);                 /* v = 4 sigma            ecm.c:1588-1589 */
-    mpl_set_u64(&u, sigma);
-    mpl_mul(&u, &u, &u);
-    mpl_set_u64(&t1, 5);
-    mpl_sub(&u, &u, &t1);               /* u = sigma^2 - 5        ecm.c:1596-1598 */
-    mpl_mul(&t1, &u, &u);
-    mpl_mul(&t1, &t1, &u);
-    mpl_mod(x3, &t1, n);                /* x = u^3                ecm.c:1601-1603 */
-    mpl_mul(&t1, &v, &v);
-    mpl_mul(&t1, &t1, &v);
-    mpl_mod(z3, &t1, n);                /* z = v^3                ecm.c:1607-1609 */
-    /* (v - u) mod n                                               ecm.c:1615-1623 */
-    mpl_t um, vm;
-    mpl_mod(&um, &u, n);
-    mpl_mod(&vm, &v, n);
-    mpl_submod(&t1, &vm, &um, n);
-    mpl_mulmod(&t2, &t1, &t1, n);
-    mpl_mulmod(&t4, &t2, &t1, n);       /* (v-u)^3                ecm.c:1626-1629 */
-    mpl_mul_u64(&t3, &u, 3);
-    mpl_add(&t3, &t3, &v);
-    mpl_mod(&t3, &t3, n);               /* 3u + v                 ecm.c:1632-1634 */
-    mpl_mulmod(num, &t3, &t4, n);       /* a = (v-u)^3 (3u+v)     ecm.c:1637-1638 */
-    mpl_mul_u64(&t2, x3, 16);
-    mpl_mul(&t2, &t2, &v);
-    mpl_mod(den, &t2, n);               /* 16 u^3 v               ecm.c:1718-1720 */
-}
-
-/* One worker's slice [lo, hi) of the batch: the whole Suyama construction for those curves.
- * The two inversions per curve, mpz_invert(16u^3v) ecm.c:1745 and mpz_invert(v^3) ecm.c:1759, share the
- * modulus, so each slice does Montgomery's simultaneous inversion: one extended Euclid per slice
- * instead of two per curve.  Inverses mod N are unique, so the values are the ones GMP returns. */
-typedef struct {
-    gecm_ctx *c;
-    const uint64_t *sigma;
-    size_t batch, lo, hi;
-    uint32_t *hX, *hZ, *hS;
-    uint32_t *fX, *fZ, *fS;   /* the same three values for the F-form context (NULL if unused) */
-    int anybad, rc;
-} build_job;
-
-static void *build_slice(void *arg)
-{
-    build_job *j = (build_job *)arg;
-    gecm_ctx *c = j->c;
-    const size_t cnt = j->hi - j->lo, m = 2 * cnt, batch = j->batch;
-    const int nl = c->nl;
-    j->rc = 0;
-    j->anybad = 0;
-    if (cnt == 0) return NULL;
-    mpl_t *x3 = (mpl_t *)malloc(cnt * sizeof(mpl_t) * 2);
-    mpl_t *dens = (mpl_t *)malloc(m * sizeof(mpl_t));
-    mpl_t *pref = (mpl_t *)malloc(m * sizeof(mpl_t));
-    if (!x3 || !dens || !pref) { free(x3); free(dens); free(pref); j->rc = GECM_ERR_NOMEM; return NULL; }
-    mpl_t *num = x3 + cnt;
-    for (size_t i = 0; i < cnt; i++)
-        suyama_pre(&c->N, j->sigma[j->lo + i], &x3[i], &dens[2 * i + 1], &num[i], &dens[2 * i]);
-    int batch_ok = 1;
-    pref[0] = dens[0];
-    for (size_t i = 1; i < m; i++) mpl_mulmod(&pref[i], &pref[i - 1], &dens[i], &c->N);
-    mpl_t inv, t;
-    if (!mpl_invmod(&inv, &pref[m - 1], &c->N)) batch_ok = 0;
-    mpl_t *invs = pref;   /* overwritten back to front */
-    if (batch_ok) {
-        for (size_t i = m - 1; i > 0; i--) {
-            mpl_mulmod(&t, &inv, &pref[i - 1], &c->N);      /* dens[i]^-1 */
-            mpl_mulmod(&inv, &inv, &dens[i], &c->N);
-            invs[i] = t;
-        }
-        invs[0] = inv;
-    } else {
-        /* Some denominator shares a factor with N.  The reference ignores mpz_invert's return
-         * value (ecm.c:1745, 1759); GMP leaves the destination untouched on failure, so the
-         * reference goes on with the STALE operand: t2 = 16*u^3 (ecm.c:1718) in place of
-         * (16u^3v)^-1 and t1 = (v-u)^3(3u+v) (ecm.c:1637) in place of (v^3)^-1.  Reproduced here so
-         * that such curves still give the reference's residues bit for bit; the lane is also
-         * flagged (a non-invertible denominator means gcd(denominator, N) is a factor). */
-        for (size_t i = 0; i < m; i++)
-            if (!mpl_invmod(&invs[i], &dens[i], &c->N)) {
-                c->bad[j->lo + i / 2] = 1;
-                j->anybad = 1;
-                if ((i & 1) == 0) { mpl_mul_u64(&t, &x3[i / 2], 16); mpl_mod(&invs[i], &t, &c->N); }
-                else invs[i] = num[i / 2];
-            }
-    }
-    for (size_t i = 0; i < cnt; i++) {
-        mpl_t A, X, Xm, Sm;
-        const size_t k = j->lo + i;
-        mpl_mulmod(&A, &num[i], &invs[2 * i], &c->N);          /* b = a / 16u^3v   ecm.c:1752-1753 */
-        mpl_mulmod(&X, &x3[i], &invs[2 * i + 1], &c->N);       /* X = u^3 / v^3, Z = 1  ecm.c:1759-1761 */
-        /* into Montgomery form (ecm.c:1763-1772), internal radix */
-        mpl_mulmod(&Xm, &X, &c->rint_mod_n, &c->N);
-        mpl_mulmod(&Sm, &A, &c->rint_mod_n, &c->N);
-        mpl_to_limbs32(j->hX + k, batch, nl, LIMB_BITS, &Xm);
-        mpl_to_limbs32(j->hZ + k, batch, nl, LIMB_BITS, &c->rint_mod_n);
-        mpl_to_limbs32(j->hS + k, batch, nl, LIMB_BITS, &Sm);
-        if (j->fX) {           /* plain residues mod N, lifted to Montgomery form modulo Mw = 2^k - 1 */
-            mpl_mulmod(&Xm, &X, &c->ff_r_mod_m, &c->ff_M);
-            mpl_mulmod(&Sm, &A, &c->ff_r_mod_m, &c->ff_M);
-            mpl_to_limbs32(j->fX + k, batch, c->ff_nl, LIMB_BITS, &Xm);
-            mpl_to_limbs32(j->fZ + k, batch, c->ff_nl, LIMB_BITS, &c->ff_r_mod_m);
-            mpl_to_limbs32(j->fS + k, batch, c->ff_nl, LIMB_BITS, &Sm);
-        }
-    }
-    free(x3); free(dens); free(pref);
-    return NULL;
 }
 
 static int host_threads(void)
@@ -722,6 +481,42 @@ static int host_threads(void)
     return (int)n;
 }
 
+/* fn(arg, lo, hi) over the slices of [0, n), 256 or more items each, on up to host_threads() threads (a thread that
+ * cannot be started: its slice runs here).  Returns an error (< 0) of some slice, else the OR of the slices' results. */
+typedef struct {
+    int (*fn)(void *arg, size_t lo, size_t hi);
+    void *arg;
+    size_t lo, hi;
+    int ret;
+} slice_job;
+
+static void *slice_run(void *job)
+{
+    slice_job *j = (slice_job *)job;
+    j->ret = j->fn(j->arg, j->lo, j->hi);
+    return NULL;
+}
+
+static int run_slices(size_t n, int (*fn)(void *arg, size_t lo, size_t hi), void *arg)
+{
+    int nt = host_threads();
+    if ((size_t)nt > n / 256 + 1) nt = (int)(n / 256 + 1);
+    slice_job jobs[64];
+    pthread_t th[64];
+    for (int t = 0; t < nt; t++)
+        jobs[t] = (slice_job){fn, arg, n * (size_t)t / (size_t)nt, n * (size_t)(t + 1) / (size_t)nt, 0};
+    for (int t = 1; t < nt; t++)
+        if (pthread_create(&th[t], NULL, slice_run, &jobs[t])) { slice_run(&jobs[t]); th[t] = 0; }
+    slice_run(&jobs[0]);
+    int err = 0, any = 0;
+    for (int t = 0; t < nt; t++) {
+        if (t > 0 && th[t]) pthread_join(th[t], NULL);
+        if (jobs[t].ret < 0) err = jobs[t].ret;
+        any |= jobs[t].ret;
+    }
+    return err ? err : any;
+}
+
 int gecm_build_curves(gecm_ctx *c, const uint64_t *sigma, size_t batch)
 {
     if (!c || !sigma || batch == 0) { set_err("gecm_build_curves: bad argument"); return GECM_ERR_ARG; }
@@ -733,33 +528,16 @@ int gecm_build_curves(gecm_ctx *c, const uint64_t *sigma, size_t batch)
     int rc = alloc_batch(c, batch);
     if (rc) return rc;
     memcpy(c->sigma, sigma, batch * sizeof(uint64_t));
-    size_t words = (size_t)c->nl * batch;
+    size_t words = (size_t)c->mod.nl * batch;
     uint32_t *hX = (uint32_t *)calloc(words * 3, 4);
     if (!hX) { free_batch(c); return GECM_ERR_NOMEM; }
     const size_t fwords = c->dev_f ? (size_t)c->ff_nl * batch : 0;
     uint32_t *fX = fwords ? (uint32_t *)calloc(fwords * 3, 4) : NULL;
     if (fwords && !fX) { free(hX); free_batch(c); return GECM_ERR_NOMEM; }
-    int nt = host_threads();
-    if ((size_t)nt > batch / 256 + 1) nt = (int)(batch / 256 + 1);
-    build_job jobs[64];
-    pthread_t th[64];
-    for (int t = 0; t < nt; t++) {
-        jobs[t].c = c; jobs[t].sigma = sigma; jobs[t].batch = batch;
-        jobs[t].lo = batch * (size_t)t / (size_t)nt;
-        jobs[t].hi = batch * (size_t)(t + 1) / (size_t)nt;
-        jobs[t].hX = hX; jobs[t].hZ = hX + words; jobs[t].hS = hX + 2 * words;
-        jobs[t].fX = fX; jobs[t].fZ = fX ? fX + fwords : NULL; jobs[t].fS = fX ? fX + 2 * fwords : NULL;
-    }
-    for (int t = 1; t < nt; t++)
-        if (pthread_create(&th[t], NULL, build_slice, &jobs[t])) { build_slice(&jobs[t]); th[t] = 0; }
-    build_slice(&jobs[0]);
-    int anybad = 0;
-    for (int t = 0; t < nt; t++) {
-        if (t > 0 && th[t]) pthread_join(th[t], NULL);
-        if (jobs[t].rc) rc = jobs[t].rc;
-        anybad |= jobs[t].anybad;
-    }
-    if (rc) { free(hX); free(fX); free_batch(c); return rc; }
+    gecm_mod_build b = {&c->mod, sigma, c->bad, batch, 0, hX, hX + words, hX + 2 * words, &c->ff_M, &c->ff_r_mod_m, c->ff_nl,
+                        fX, fX ? fX + fwords : NULL, fX ? fX + 2 * fwords : NULL};
+    const int built = run_slices(batch, gecm_mod_build_slice, &b);
+    if (built < 0) { free(hX); free(fX); free_batch(c); return built; }
     rc = gecm_dev_upload(c->dev, hX, hX + words, hX + 2 * words);
     if (!rc && fX) {
         rc = gecm_dev_upload(c->dev_f, fX, fX + fwords, fX + 2 * fwords);
@@ -768,7 +546,7 @@ int gecm_build_curves(gecm_ctx *c, const uint64_t *sigma, size_t batch)
     free(hX);
     free(fX);
     if (rc) { set_err("%s", gecm_dev_error()); free_batch(c); return GECM_ERR_DEVICE; }
-    return anybad ? 1 : GECM_OK;
+    return built;
 }
 
 int gecm_upload_points(gecm_ctx *c, const void *X, const void *Z, const void *s, size_t batch)
@@ -777,7 +555,7 @@ int gecm_upload_points(gecm_ctx *c, const void *X, const void *Z, const void *s,
     if (c && c->multi) return multi_refuse("gecm_upload_points");
     int rc = alloc_batch(c, batch);
     if (rc) return rc;
-    int nl = c->nl;
+    int nl = c->mod.nl;
     size_t words = (size_t)nl * batch;
     uint32_t *h = (uint32_t *)calloc(words * 3, 4);
     if (!h) { free_batch(c); return GECM_ERR_NOMEM; }
@@ -785,14 +563,14 @@ int gecm_upload_points(gecm_ctx *c, const void *X, const void *Z, const void *s,
     for (int k = 0; k < 3; k++)
         for (size_t i = 0; i < batch; i++) {
             mpl_t v;
-            vec_get(c, &v, src[k], batch, i);
-            if (mpl_cmp(&v, &c->N) >= 0) {
+            vec_get(&c->mod, &v, src[k], batch, i);
+            if (mpl_cmp(&v, &c->mod.N) >= 0) {
                 free(h);
                 free_batch(c);                 /* the context holds no batch after a rejected upload */
                 set_err("gecm_upload_points: operand not < N");
                 return GECM_ERR_ARG;
             }
-            mpl_mulmod(&v, &v, &c->ref_to_int, &c->N);
+            mpl_mulmod(&v, &v, &c->mod.ref_to_int, &c->mod.N);
             mpl_to_limbs32(h + (size_t)k * words + i, batch, nl, LIMB_BITS, &v);
         }
     rc = gecm_dev_upload(c->dev, h, h + words, h + 2 * words);
@@ -801,12 +579,12 @@ int gecm_upload_points(gecm_ctx *c, const void *X, const void *Z, const void *s,
         const size_t fwords = (size_t)c->ff_nl * batch;
         uint32_t *f = (uint32_t *)calloc(fwords * 3, 4);
         mpl_t rinv;
-        if (f && mpl_invmod(&rinv, &c->rint_mod_n, &c->N)) {
+        if (f && mpl_invmod(&rinv, &c->mod.rint_mod_n, &c->mod.N)) {
             for (int k = 0; k < 3; k++)
                 for (size_t i = 0; i < batch; i++) {
                     mpl_t v;
                     mpl_from_limbs32(&v, h + (size_t)k * words + i, batch, nl, LIMB_BITS);
-                    mpl_mulmod(&v, &v, &rinv, &c->N);
+                    mpl_mulmod(&v, &v, &rinv, &c->mod.N);
                     mpl_mulmod(&v, &v, &c->ff_r_mod_m, &c->ff_M);
                     mpl_to_limbs32(f + (size_t)k * fwords + i, batch, c->ff_nl, LIMB_BITS, &v);
                 }
@@ -825,29 +603,24 @@ int gecm_upload_points(gecm_ctx *c, const void *X, const void *Z, const void *s,
  * in the main context as if stage 1 had run there.  Everything after stage 1 (save lines, factor scan,
  * stage 2) then works on residues modulo N as always. */
 typedef struct {
-    gecm_ctx *c;
-    const uint32_t *fx, *fz;
-    uint32_t *hX, *hZ;
-    size_t lo, hi;
+    const gecm_ctx *c;
+    uint32_t *f;              /* fx, fz [ff_nl][batch], then hX, hZ [nl][batch] */
 } settle_job;
 
-static void *settle_slice(void *arg)
+static int settle_slice(void *arg, size_t lo, size_t hi)
 {
-    settle_job *j = (settle_job *)arg;
-    gecm_ctx *c = j->c;
-    const size_t batch = c->batch;
-    for (size_t i = j->lo; i < j->hi; i++) {
-        mpl_t v;
-        mpl_from_limbs32(&v, j->fx + i, batch, c->ff_nl, LIMB_BITS);
-        mpl_mod(&v, &v, &c->N);
-        mpl_mulmod(&v, &v, &c->rint_mod_n, &c->N);
-        mpl_to_limbs32(j->hX + i, batch, c->nl, LIMB_BITS, &v);
-        mpl_from_limbs32(&v, j->fz + i, batch, c->ff_nl, LIMB_BITS);
-        mpl_mod(&v, &v, &c->N);
-        mpl_mulmod(&v, &v, &c->rint_mod_n, &c->N);
-        mpl_to_limbs32(j->hZ + i, batch, c->nl, LIMB_BITS, &v);
-    }
-    return NULL;
+    const settle_job *j = (const settle_job *)arg;
+    const gecm_ctx *c = j->c;
+    const size_t batch = c->batch, fwords = (size_t)c->ff_nl * batch, words = (size_t)c->mod.nl * batch;
+    for (size_t i = lo; i < hi; i++)
+        for (int q = 0; q < 2; q++) {                /* x, z */
+            mpl_t v;
+            mpl_from_limbs32(&v, j->f + q * fwords + i, batch, c->ff_nl, LIMB_BITS);
+            mpl_mod(&v, &v, &c->mod.N);
+            mpl_mulmod(&v, &v, &c->mod.rint_mod_n, &c->mod.N);
+            mpl_to_limbs32(j->f + 2 * fwords + q * words + i, batch, c->mod.nl, LIMB_BITS, &v);
+        }
+    return 0;
 }
 
 static int ff_settle(gecm_ctx *c)
@@ -856,25 +629,12 @@ static int ff_settle(gecm_ctx *c)
     c->ff_pending = 0;
     if (gecm_dev_sync(c->dev_f)) { set_err("%s", gecm_dev_error()); return GECM_ERR_DEVICE; }
     c->last_ms = gecm_dev_last_kernel_ms(c->dev_f);
-    const size_t batch = c->batch, fwords = (size_t)c->ff_nl * batch, words = (size_t)c->nl * batch;
+    const size_t batch = c->batch, fwords = (size_t)c->ff_nl * batch, words = (size_t)c->mod.nl * batch;
     uint32_t *f = (uint32_t *)calloc(2 * fwords + 2 * words, 4);
     if (!f) return GECM_ERR_NOMEM;
     if (gecm_dev_download_plain(c->dev_f, f, f + fwords)) { free(f); set_err("%s", gecm_dev_error()); return GECM_ERR_DEVICE; }
-    int nt = host_threads();
-    if ((size_t)nt > batch / 256 + 1) nt = (int)(batch / 256 + 1);
-    settle_job jobs[64];
-    pthread_t th[64];
-    for (int t = 0; t < nt; t++) {
-        jobs[t].c = c; jobs[t].fx = f; jobs[t].fz = f + fwords;
-        jobs[t].hX = f + 2 * fwords; jobs[t].hZ = f + 2 * fwords + words;
-        jobs[t].lo = batch * (size_t)t / (size_t)nt;
-        jobs[t].hi = batch * (size_t)(t + 1) / (size_t)nt;
-    }
-    for (int t = 1; t < nt; t++)
-        if (pthread_create(&th[t], NULL, settle_slice, &jobs[t])) { settle_slice(&jobs[t]); th[t] = 0; }
-    settle_slice(&jobs[0]);
-    for (int t = 1; t < nt; t++)
-        if (th[t]) pthread_join(th[t], NULL);
+    settle_job j = {c, f};
+    run_slices(batch, settle_slice, &j);
     int rc = gecm_dev_upload_xz(c->dev, f + 2 * fwords, f + 2 * fwords + words);
     free(f);
     if (rc) { set_err("%s", gecm_dev_error()); return GECM_ERR_DEVICE; }
@@ -1067,7 +827,7 @@ int gecm_download_points(gecm_ctx *c, void *X, void *Z)
     if (c && c->multi) return multi_refuse("gecm_download_points");
     if (c && c->ff_pending) { int rcs = ff_settle(c); if (rcs) return rcs; }
     if (!c || !X || !Z || c->batch == 0) return GECM_ERR_ARG;
-    size_t batch = c->batch, words = (size_t)c->nl * batch;
+    size_t batch = c->batch, words = (size_t)c->mod.nl * batch;
     uint32_t *h = (uint32_t *)malloc(words * 2 * 4);
     if (!h) return GECM_ERR_NOMEM;
     if (gecm_dev_download_mont(c->dev, h, h + words)) { free(h); set_err("%s", gecm_dev_error()); return GECM_ERR_DEVICE; }
@@ -1075,9 +835,9 @@ int gecm_download_points(gecm_ctx *c, void *X, void *Z)
     for (int k = 0; k < 2; k++)
         for (size_t i = 0; i < batch; i++) {
             mpl_t v;
-            mpl_from_limbs32(&v, h + (size_t)k * words + i, batch, c->nl, LIMB_BITS);
-            mpl_mulmod(&v, &v, &c->int_to_ref, &c->N);
-            vec_put(c, dst[k], batch, i, &v);
+            mpl_from_limbs32(&v, h + (size_t)k * words + i, batch, c->mod.nl, LIMB_BITS);
+            mpl_mulmod(&v, &v, &c->mod.int_to_ref, &c->mod.N);
+            vec_put(&c->mod, dst[k], batch, i, &v);
         }
     free(h);
     return GECM_OK;
@@ -1101,12 +861,22 @@ int gecm_download_points_plain(gecm_ctx *c, void *x, void *z)
     if (rc) return rc;
     for (size_t i = 0; i < c->batch; i++) {
         mpl_t v;
-        mpl_from_limbs32(&v, c->hx + i, c->batch, c->nl, LIMB_BITS);
-        vec_put(c, x, c->batch, i, &v);
-        mpl_from_limbs32(&v, c->hz + i, c->batch, c->nl, LIMB_BITS);
-        vec_put(c, z, c->batch, i, &v);
+        mpl_from_limbs32(&v, c->hx + i, c->batch, c->mod.nl, LIMB_BITS);
+        vec_put(&c->mod, x, c->batch, i, &v);
+        mpl_from_limbs32(&v, c->hz + i, c->batch, c->mod.nl, LIMB_BITS);
+        vec_put(&c->mod, z, c->batch, i, &v);
     }
     return GECM_OK;
+}
+
+/* The modulus of the caller's curve k and its position in the batch arrays (stride c->batch); NULL if there is no
+ * such curve.  Reads the context only: the per-curve calls may run on several threads at once. */
+static const gecm_mod *curve_at(const gecm_ctx *c, size_t k, size_t *pos)
+{
+    if (!c->multi) { *pos = k; return k < c->batch ? &c->mod : NULL; }
+    if (c->batch == 0 || k >= c->nuser) { set_err("curve %zu: no such curve in the batch", k); return NULL; }
+    *pos = c->slot[k];
+    return &c->grp[c->pos_grp[*pos]];
 }
 
 int gecm_format_save_line(gecm_ctx *c, size_t k, char *buf, size_t buflen)
@@ -1116,36 +886,30 @@ int gecm_format_save_line(gecm_ctx *c, size_t k, char *buf, size_t buflen)
 
 int gecm_format_resume_line(gecm_ctx *c, size_t k, uint64_t b1_label, char *buf, size_t buflen)
 {
-    if (c && c->multi) {
-        size_t kk;
-        gecm_ctx *s = multi_curve(c, k, 1, &kk);
-        return s ? gecm_format_resume_line(s, kk, b1_label, buf, buflen) : multi_err;
-    }
-    if (!c || !buf || k >= c->batch) return GECM_ERR_ARG;
+    size_t pos;
+    const gecm_mod *m = c && buf ? curve_at(c, k, &pos) : NULL;
+    if (!m) return GECM_ERR_ARG;
     int rc = fetch_plain(c);
     if (rc) return rc;
     static __thread char hn[MPL_MAXL * 10 + 2], hxs[MPL_MAXL * 10 + 2], hzs[MPL_MAXL * 10 + 2];
     mpl_t v;
-    mpl_get_hex(hn, report_n(c));
-    mpl_from_limbs32(&v, c->hx + k, c->batch, c->nl, LIMB_BITS);
+    mpl_get_hex(hn, report_n(m));
+    mpl_from_limbs32(&v, c->hx + pos, c->batch, m->nl, LIMB_BITS);
     mpl_get_hex(hxs, &v);
-    mpl_from_limbs32(&v, c->hz + k, c->batch, c->nl, LIMB_BITS);
+    mpl_from_limbs32(&v, c->hz + pos, c->batch, m->nl, LIMB_BITS);
     mpl_get_hex(hzs, &v);
     /* ecm.c:1372-1380 */
     int n = snprintf(buf, buflen, "METHOD=ECM; SIGMA=%llu; B1=%llu; N=0x%s; X=0x%s; Z=0x%s; PROGRAM=AVX-ECM;\n",
-                     (unsigned long long)c->sigma[k], (unsigned long long)b1_label, hn, hxs, hzs);
+                     (unsigned long long)c->sigma[pos], (unsigned long long)b1_label, hn, hxs, hzs);
     if (n < 0 || (size_t)n >= buflen) { set_err("gecm_format_save_line: buffer too small"); return GECM_ERR_ARG; }
     return n;
 }
 
 int gecm_stage1_factor(gecm_ctx *c, size_t k, char *dec, size_t declen, int *is_prp)
 {
-    if (c && c->multi) {
-        size_t kk;
-        gecm_ctx *s = multi_curve(c, k, 1, &kk);
-        return s ? gecm_stage1_factor(s, kk, dec, declen, is_prp) : multi_err;
-    }
-    if (!c || k >= c->batch) return GECM_ERR_ARG;
+    size_t pos;
+    const gecm_mod *m = c ? curve_at(c, k, &pos) : NULL;
+    if (!m) return GECM_ERR_ARG;
     int rc = fetch_plain(c);
     if (rc) return rc;
     mpl_t z, g;
@@ -1153,23 +917,12 @@ int gecm_stage1_factor(gecm_ctx *c, size_t k, char *dec, size_t declen, int *is_
      * gcd(z R mod N, N) = gcd(z, N) because R is a power of two and N is odd.  If the device scan
      * of this batch has run, its gcd is used; otherwise it is computed here. */
     if (c->scan_valid[0] && c->hg[0]) {
-        mpl_from_limbs32(&g, c->hg[0] + k, c->batch, c->nl, LIMB_BITS);
+        mpl_from_limbs32(&g, c->hg[0] + pos, c->batch, m->nl, LIMB_BITS);
     } else {
-        mpl_from_limbs32(&z, c->hz + k, c->batch, c->nl, LIMB_BITS);
-        mpl_gcd(&g, &z, &c->N);
+        mpl_from_limbs32(&z, c->hz + pos, c->batch, m->nl, LIMB_BITS);
+        mpl_gcd(&g, &z, &m->N);
     }
-    to_report(c, &g);
-    if (mpl_cmp_u64(&g, 1) > 0 && mpl_cmp(&g, report_n(c)) != 0) {
-        static __thread char tmp[MPL_MAXL * 10 + 16];
-        int n = mpl_get_dec(tmp, &g);
-        if (dec && declen) {
-            if ((size_t)n >= declen) { set_err("gecm_stage1_factor: buffer too small"); return GECM_ERR_ARG; }
-            memcpy(dec, tmp, (size_t)n + 1);
-        }
-        if (is_prp) *is_prp = mpl_probab_prime(&g, 3);   /* ecm.c:1346 */
-        return 1;
-    }
-    return 0;
+    return gecm_mod_factor(m, &g, "gecm_stage1_factor", dec, declen, is_prp);
 }
 
 /* ---- stage 2 -------------------------------------------------------------------------------- */
@@ -1223,7 +976,7 @@ int gecm_stage2_init(gecm_ctx *c, uint32_t D, uint32_t U)
      * context still has its old stage-2 state, untouched */
     const uint32_t planes = K > 1 ? K + 1 : 1;
     if (planes != c->fail_planes || !c->hfail) {
-        uint32_t *nf = (uint32_t *)calloc(c->batch * (size_t)c->nl * planes, 4);
+        uint32_t *nf = (uint32_t *)calloc(c->batch * (size_t)c->mod.nl * planes, 4);
         if (!nf) { free(tgt); return GECM_ERR_NOMEM; }
         free(c->hfail);
         c->hfail = nf;
@@ -1443,34 +1196,6 @@ static int fetch_acc(gecm_ctx *c)
     return GECM_OK;
 }
 
-/* The failed-inversion record of curve k.  The reference overwrites its accumulator with gcd(product of the batch, N)
- * every time a batch inversion fails (ecm.c:1925-1939): what its scan finds in the end is the gcd of the LAST failing
- * batch (times later cross products).  Plane 0 holds that gcd for the single-chain inversions — after gecm_stage2_pair
- * the last chunk of the range, cut to be exactly the reference's last batch — and decides when it holds one.  Otherwise
- * the sub-sequences' planes stand for one batch inverted in K pieces: the gcd of N with the PRODUCT of their records
- * is the gcd of the whole batch's product (for a product that covers N that is N itself — "no factor", which is
- * what the reference finds then too: its batch product is 0 modulo N).  Every record is passed through gcd(., N)
- * first: what comes out divides N. */
-static void fail_record(gecm_ctx *c, size_t k, mpl_t *g)
-{
-    const size_t plane = c->batch * (size_t)c->nl;
-    mpl_t t, prod, gp;
-    mpl_from_limbs32(&t, c->hfail + k, c->batch, c->nl, LIMB_BITS);
-    if (!mpl_is_zero(&t)) { mpl_gcd(g, &t, &c->N); return; }
-    mpl_set_u64(g, 0);
-    if (c->fail_planes <= 1) return;
-    mpl_set_u64(&prod, 0);
-    for (uint32_t p = 1; p < c->fail_planes; p++) {
-        mpl_from_limbs32(&t, c->hfail + p * plane + k, c->batch, c->nl, LIMB_BITS);
-        if (mpl_is_zero(&t)) continue;
-        mpl_gcd(&gp, &t, &c->N);
-        if (mpl_is_zero(&prod)) prod = gp;
-        else mpl_mulmod(&prod, &prod, &gp, &c->N);
-        if (mpl_is_zero(&prod)) { prod = c->N; break; }       /* the product covers N: gcd = N, "no factor" */
-    }
-    if (!mpl_is_zero(&prod)) mpl_gcd(g, &prod, &c->N);
-}
-
 int gecm_download_acc(gecm_ctx *c, void *acc)
 {
     if (!c || !acc) return GECM_ERR_ARG;
@@ -1479,98 +1204,73 @@ int gecm_download_acc(gecm_ctx *c, void *acc)
     if (rc) return rc;
     for (size_t i = 0; i < c->batch; i++) {
         mpl_t v;
-        mpl_from_limbs32(&v, c->hacc + i, c->batch, c->nl, LIMB_BITS);
-        mpl_mulmod(&v, &v, &c->int_to_ref, &c->N);
-        vec_put(c, acc, c->batch, i, &v);
+        mpl_from_limbs32(&v, c->hacc + i, c->batch, c->mod.nl, LIMB_BITS);
+        mpl_mulmod(&v, &v, &c->mod.int_to_ref, &c->mod.N);
+        vec_put(&c->mod, acc, c->batch, i, &v);
     }
     return GECM_OK;
 }
 
 int gecm_stage2_factor(gecm_ctx *c, size_t k, char *dec, size_t declen, int *is_prp)
 {
-    if (c && c->multi) {
-        size_t kk;
-        gecm_ctx *s = multi_curve(c, k, 2, &kk);
-        return s ? gecm_stage2_factor(s, kk, dec, declen, is_prp) : multi_err;
-    }
-    if (!c || k >= c->batch) return GECM_ERR_ARG;
+    size_t pos;
+    const gecm_mod *m = c ? curve_at(c, k, &pos) : NULL;
+    if (!m) return GECM_ERR_ARG;
     int rc = fetch_acc(c);
     if (rc) return rc;
     mpl_t a, g;
-    fail_record(c, k, &g);
+    gecm_mod_fail_record(m, c->hfail, c->fail_planes, c->batch, pos, &g);
     if (mpl_is_zero(&g)) {
         if (c->scan_valid[1] && c->hg[1]) {
-            mpl_from_limbs32(&g, c->hg[1] + k, c->batch, c->nl, LIMB_BITS);
+            mpl_from_limbs32(&g, c->hg[1] + pos, c->batch, m->nl, LIMB_BITS);
         } else {
-            mpl_from_limbs32(&a, c->hacc + k, c->batch, c->nl, LIMB_BITS);
-            mpl_gcd(&g, &a, &c->N);                  /* check_factor, ecm.c:2542-2557 */
+            mpl_from_limbs32(&a, c->hacc + pos, c->batch, m->nl, LIMB_BITS);
+            mpl_gcd(&g, &a, &m->N);                  /* check_factor, ecm.c:2542-2557 */
         }
     }
-    to_report(c, &g);
-    if (mpl_cmp_u64(&g, 1) > 0 && mpl_cmp(&g, report_n(c)) != 0) {
-        static __thread char tmp[MPL_MAXL * 10 + 16];
-        int n = mpl_get_dec(tmp, &g);
-        if (dec && declen) {
-            if ((size_t)n >= declen) { set_err("gecm_stage2_factor: buffer too small"); return GECM_ERR_ARG; }
-            memcpy(dec, tmp, (size_t)n + 1);
-        }
-        if (is_prp) *is_prp = mpl_probab_prime(&g, 3);
-        return 1;
-    }
-    return 0;
+    return gecm_mod_factor(m, &g, "gecm_stage2_factor", dec, declen, is_prp);
 }
 
-/* ---- device factor scan ------------------------------------------------------------------- */
+/* ---- device factor scan -------------------------------------------------------------------
+ * The device compares every curve with its own N.  Of a multi-modulus batch the padding is never flagged, and `first`
+ * is in the caller's numbering. */
 int gecm_scan_factors(gecm_ctx *c, int stage, size_t *first)
 {
     if (c && c->ff_pending) { int rcs = ff_settle(c); if (rcs) return rcs; }
     if (!c || c->batch == 0 || (stage != 1 && stage != 2)) { set_err("gecm_scan_factors: bad argument"); return GECM_ERR_ARG; }
-    if (c->multi) return multi_scan(c, stage, first);
     if (stage == 2 && !c->s2_ready) { set_err("gecm_scan_factors: no stage-2 state"); return GECM_ERR_STATE; }
     uint32_t **f = &c->flags[stage - 1], **hg = &c->hg[stage - 1];
     if (!*f) *f = (uint32_t *)calloc(c->batch, sizeof(uint32_t));
-    if (!*hg) *hg = (uint32_t *)calloc(c->batch * (size_t)c->nl, sizeof(uint32_t));
+    if (!*hg) *hg = (uint32_t *)calloc(c->batch * (size_t)c->mod.nl, sizeof(uint32_t));
     if (!*f || !*hg) return GECM_ERR_NOMEM;
     if (gecm_dev_gcd_scan(c->dev, stage - 1, *f, *hg)) { set_err("gecm_scan_factors: %s", gecm_dev_error()); return GECM_ERR_DEVICE; }
-    size_t n = 0, lo = c->batch;
-    if (stage == 1) {
-        /* x, z come to the host with the scan: everything a caller does next (save lines, factors of the flagged
-         * curves) is then host work, off the device's queue */
-        int rc = fetch_plain(c);
-        if (rc) return rc;
-    }
-    if (stage == 2) {
-        /* a failed batch inversion also marks its curve (ecm.c:1927-1939) */
-        int rc = fetch_acc(c);
-        if (rc) return rc;
-        for (size_t k = 0; k < c->batch; k++) {
-            mpl_t g;
-            fail_record(c, k, &g);
-            if (!mpl_is_zero(&g)) {
-                to_report(c, &g);
-                (*f)[k] = (mpl_cmp_u64(&g, 1) > 0 && mpl_cmp(&g, report_n(c)) != 0);
-            }
+    /* stage 1: x, z come to the host with the scan: everything a caller does next (save lines, factors of the flagged
+     * curves) is then host work, off the device's queue */
+    int rc = stage == 1 ? fetch_plain(c) : fetch_acc(c);
+    if (rc) return rc;
+    size_t n = 0, lo = c->multi ? c->nuser : c->batch;
+    for (size_t p = 0; p < c->batch; p++) {
+        const gecm_mod *m = &c->mod;
+        size_t user = p;
+        if (c->multi) {
+            if (c->pos_user[p] == GECM_PAD) { (*f)[p] = 0; continue; }
+            m = &c->grp[c->pos_grp[p]];
+            user = c->pos_user[p];
         }
+        mpl_t fr, g;
+        mpl_set_u64(&fr, 0);
+        if (stage == 2) {                              /* a failed batch inversion also marks its curve (ecm.c:1927-1939) */
+            gecm_mod_fail_record(m, c->hfail, c->fail_planes, c->batch, p, &fr);
+            if (!mpl_is_zero(&fr)) (*f)[p] = to_report(m, &fr);
+        }
+        if (m->have_report && (*f)[p] && mpl_is_zero(&fr)) {
+            /* the device looked for factors of the context's modulus: keep the curves whose gcd shares one with the
+             * report modulus (gcd(gcd(v, Mw), N) = gcd(v, N) for N | Mw); a failure record decides if there is one */
+            mpl_from_limbs32(&g, *hg + p, c->batch, m->nl, LIMB_BITS);
+            if (!mpl_is_zero(&g) && !to_report(m, &g)) (*f)[p] = 0;
+        }
+        if ((*f)[p]) { n++; if (user < lo) lo = user; }
     }
-    if (c->have_report)
-        /* the device looked for factors of the context's modulus: keep the curves whose gcd shares one with the
-         * report modulus (gcd(gcd(v, Mw), N) = gcd(v, N) for N | Mw) */
-        for (size_t k = 0; k < c->batch; k++)
-            if ((*f)[k]) {
-                mpl_t g;
-                mpl_from_limbs32(&g, *hg + k, c->batch, c->nl, LIMB_BITS);
-                if (mpl_is_zero(&g)) continue;            /* flagged by a failure record, settled above */
-                to_report(c, &g);
-                if (!(mpl_cmp_u64(&g, 1) > 0 && mpl_cmp(&g, report_n(c)) != 0)) {
-                    /* stage 2: the failure record decides if there is one */
-                    mpl_t fr;
-                    mpl_set_u64(&fr, 0);
-                    if (stage == 2) fail_record(c, k, &fr);
-                    if (mpl_is_zero(&fr)) (*f)[k] = 0;
-                }
-            }
-    for (size_t k = 0; k < c->batch; k++)
-        if ((*f)[k]) { n++; if (k < lo) lo = k; }
     c->scan_valid[stage - 1] = 1;
     if (first) *first = lo;
     return (int)(n > 0x7fffffff ? 0x7fffffff : n);
@@ -1578,12 +1278,9 @@ int gecm_scan_factors(gecm_ctx *c, int stage, size_t *first)
 
 int gecm_curve_flag(const gecm_ctx *c, int stage, size_t k)
 {
-    if (c && c->multi) {
-        if (k >= c->nuser) return 0;
-        k = c->slot[k];
-    }
-    if (!c || (stage != 1 && stage != 2) || k >= c->batch || !c->flags[stage - 1]) return 0;
-    return (int)c->flags[stage - 1][k];
+    size_t pos;
+    if (!c || (stage != 1 && stage != 2) || !c->flags[stage - 1] || !curve_at(c, k, &pos)) return 0;
+    return (int)c->flags[stage - 1][pos];
 }
 
 /* ---- multi-modulus contexts ------------------------------------------------ */
@@ -1596,7 +1293,7 @@ int gecm_create_multi(gecm_ctx **out, int device, const char *const *n_strs, siz
     if (count == 0) { set_err("gecm_create_multi: the list of moduli is empty"); return GECM_ERR_ARG; }
     if (count > 0xfffffffe) { set_err("gecm_create_multi: %zu moduli, more than a 32-bit modulus index holds", count); return GECM_ERR_ARG; }
     gecm_ctx *c = (gecm_ctx *)calloc(1, sizeof *c);
-    gecm_ctx **grp = (gecm_ctx **)calloc(count, sizeof *grp);
+    gecm_mod *grp = (gecm_mod *)calloc(count, sizeof *grp);
     if (!c || !grp) { free(c); free(grp); return GECM_ERR_NOMEM; }
     c->grp = grp;
     c->ngroups = count;
@@ -1623,12 +1320,10 @@ int gecm_create_multi(gecm_ctx **out, int device, const char *const *n_strs, siz
     const int nl = rc ? 0 : pick_nl(maxbits);
     for (size_t g = 0; g < count && !rc; g++) {
         snprintf(who, sizeof who, "gecm_create_multi: N[%zu]", g);
-        grp[g] = (gecm_ctx *)calloc(1, sizeof **grp);
-        if (!grp[g]) { rc = GECM_ERR_NOMEM; break; }
-        rc = ctx_setup_n(grp[g], who, n_strs[g], digitbits, nl);
+        rc = gecm_mod_setup(&grp[g], who, n_strs[g], digitbits, nl, pick_nl);
     }
     /* the context itself: the largest N (what gecm_get_config reports) and the device */
-    if (!rc) rc = ctx_setup_n(c, "gecm_create_multi", n_strs[largest], digitbits, nl);
+    if (!rc) rc = gecm_mod_setup(&c->mod, "gecm_create_multi", n_strs[largest], digitbits, nl, pick_nl);
     if (!rc) {
         c->gconst = (uint32_t *)calloc((size_t)4 * count * nl + 2 * count, sizeof(uint32_t));
         if (!c->gconst) rc = GECM_ERR_NOMEM;
@@ -1637,57 +1332,24 @@ int gecm_create_multi(gecm_ctx **out, int device, const char *const *n_strs, siz
         uint32_t *rho = c->gconst + (size_t)4 * count * nl, *iters = rho + count;
         for (size_t g = 0; g < count; g++) {
             for (int q = 0; q < 4; q++)        /* n, kp, one, r3 */
-                memcpy(c->gconst + ((size_t)q * count + g) * nl, q < 3 ? grp[g]->n28 + (size_t)q * nl : grp[g]->r3_28,
+                memcpy(c->gconst + ((size_t)q * count + g) * nl, q < 3 ? grp[g].n28 + (size_t)q * nl : grp[g].r3_28,
                        (size_t)nl * sizeof(uint32_t));
-            rho[g] = grp[g]->rho28;
-            iters[g] = grp[g]->inv_iters;
+            rho[g] = grp[g].rho28;
+            iters[g] = grp[g].inv_iters;
         }
-        if (gecm_dev_open(&c->dev, device, nl, c->n28, c->kp28, c->one28, c->rho28)) {
+        if (gecm_dev_open(&c->dev, device, nl, c->mod.n28, c->mod.kp28, c->mod.one28, c->mod.rho28)) {
             set_err("gecm_create_multi: %s", gecm_dev_error());
             rc = GECM_ERR_DEVICE;
         }
     }
     if (rc) { gecm_destroy(c); return rc; }
     gecm_dev_set_multi(c->dev);
-    gecm_dev_set_s2const(c->dev, c->r3_28, c->inv_iters);
+    gecm_dev_set_s2const(c->dev, c->mod.r3_28, c->mod.inv_iters);
     *out = c;
     return GECM_OK;
 }
 
 size_t gecm_moduli(const gecm_ctx *c) { return c ? (c->multi ? c->ngroups : 1) : 0; }
-
-/* the modulus's context as a view of the batch at its positions, the flags of the context copied in */
-static gecm_ctx *view_group(gecm_ctx *c, uint32_t g)
-{
-    gecm_ctx *s = c->grp[g];
-    const size_t off = c->goff[g];
-    s->batch = c->batch;
-    s->sigma = c->sigma + off;
-    s->bad = c->bad + off;
-    s->hx = c->hx + off; s->hz = c->hz + off;
-    s->hacc = c->hacc + off; s->hfail = c->hfail + off;
-    s->fail_planes = c->fail_planes;
-    for (int i = 0; i < 2; i++) {
-        s->flags[i] = c->flags[i] ? c->flags[i] + off : NULL;
-        s->hg[i] = c->hg[i] ? c->hg[i] + off : NULL;
-        s->scan_valid[i] = c->scan_valid[i];
-    }
-    s->have_plain = c->have_plain;
-    s->have_acc = c->have_acc;
-    s->s2_ready = c->s2_ready;
-    s->B1 = c->B1;
-    return s;
-}
-
-static gecm_ctx *multi_curve(gecm_ctx *c, size_t k, int stage, size_t *kk)
-{
-    if (c->batch == 0 || k >= c->nuser) { set_err("curve %zu: no such curve in the batch", k); multi_err = GECM_ERR_ARG; return NULL; }
-    int rc = stage == 1 ? fetch_plain(c) : stage == 2 ? fetch_acc(c) : GECM_OK;
-    if (rc) { multi_err = rc; return NULL; }
-    const size_t pos = c->slot[k];
-    *kk = pos - c->goff[c->pos_grp[pos]];
-    return view_group(c, c->pos_grp[pos]);
-}
 
 int gecm_build_curves_multi(gecm_ctx *c, const uint64_t *sigma, const uint32_t *modulus_index, size_t batch)
 {
@@ -1711,7 +1373,7 @@ int gecm_build_curves_multi(gecm_ctx *c, const uint64_t *sigma, const uint32_t *
     int rc = alloc_batch(c, total);
     uint32_t *slot = (uint32_t *)malloc(batch * sizeof(uint32_t)), *pos_user = (uint32_t *)malloc(total * sizeof(uint32_t));
     uint32_t *pos_grp = (uint32_t *)malloc(total * sizeof(uint32_t)), *blocks = (uint32_t *)malloc(total / 64 * sizeof(uint32_t));
-    const size_t words = (size_t)c->nl * total;
+    const size_t words = (size_t)c->mod.nl * total;
     uint32_t *hX = (uint32_t *)calloc(words * 3, 4);           /* padding stays zero: computed, never read */
     if (!rc && (!slot || !pos_user || !pos_grp || !blocks || !hX)) rc = GECM_ERR_NOMEM;
     if (rc) {
@@ -1719,7 +1381,7 @@ int gecm_build_curves_multi(gecm_ctx *c, const uint64_t *sigma, const uint32_t *
         free_batch(c);
         return rc;
     }
-    c->slot = slot; c->pos_user = pos_user; c->pos_grp = pos_grp; c->goff = goff; c->nuser = batch;
+    c->slot = slot; c->pos_user = pos_user; c->pos_grp = pos_grp; c->nuser = batch;
     for (size_t g = 0; g < ng; g++)
         for (size_t p = goff[g]; p < goff[g] + (cnt[g] + 63) / 64 * 64; p++) {
             pos_grp[p] = (uint32_t)g;
@@ -1734,36 +1396,21 @@ int gecm_build_curves_multi(gecm_ctx *c, const uint64_t *sigma, const uint32_t *
         pos_user[p] = (uint32_t)i;
         c->sigma[p] = sigma[i];
     }
-    /* the Suyama construction modulus by modulus (build_slice on the modulus's view, host threads as gecm_build_curves) */
+    /* the Suyama construction modulus by modulus: what gecm_build_curves does for its one */
     int anybad = 0;
     for (size_t g = 0; g < ng && !rc; g++) {
-        if (!cnt[g]) continue;
-        gecm_ctx *s = view_group(c, (uint32_t)g);
-        int nt = host_threads();
-        if ((size_t)nt > cnt[g] / 256 + 1) nt = (int)(cnt[g] / 256 + 1);
-        build_job jobs[64];
-        pthread_t th[64];
-        for (int t = 0; t < nt; t++) {
-            jobs[t].c = s; jobs[t].sigma = s->sigma; jobs[t].batch = total;
-            jobs[t].lo = cnt[g] * (size_t)t / (size_t)nt;
-            jobs[t].hi = cnt[g] * (size_t)(t + 1) / (size_t)nt;
-            jobs[t].hX = hX + goff[g]; jobs[t].hZ = hX + words + goff[g]; jobs[t].hS = hX + 2 * words + goff[g];
-            jobs[t].fX = jobs[t].fZ = jobs[t].fS = NULL;
-        }
-        for (int t = 1; t < nt; t++)
-            if (pthread_create(&th[t], NULL, build_slice, &jobs[t])) { build_slice(&jobs[t]); th[t] = 0; }
-        build_slice(&jobs[0]);
-        for (int t = 0; t < nt; t++) {
-            if (t > 0 && th[t]) pthread_join(th[t], NULL);
-            if (jobs[t].rc) rc = jobs[t].rc;
-            anybad |= jobs[t].anybad;
-        }
+        gecm_mod_build b = {&c->grp[g], c->sigma + goff[g], c->bad, total, goff[g], hX, hX + words, hX + 2 * words,
+                            NULL, NULL, 0, NULL, NULL, NULL};
+        const int built = run_slices(cnt[g], gecm_mod_build_slice, &b);
+        if (built < 0) rc = built;
+        else anybad |= built;
     }
+    free(goff);
     free(cnt);
     if (!rc && gecm_dev_upload(c->dev, hX, hX + words, hX + 2 * words)) rc = GECM_ERR_DEVICE;
     if (!rc) {
         const uint32_t *q = c->gconst;
-        const size_t w = ng * (size_t)c->nl;
+        const size_t w = ng * (size_t)c->mod.nl;
         if (gecm_dev_set_groups(c->dev, (uint32_t)ng, q, q + w, q + 2 * w, q + 3 * w, q + 4 * w, q + 4 * w + ng, blocks))
             rc = GECM_ERR_DEVICE;
     }
@@ -1785,53 +1432,19 @@ int gecm_curve_modulus(const gecm_ctx *c, size_t k)
 
 int gecm_curve_acc(gecm_ctx *c, size_t k, char *hex, size_t hexlen)
 {
-    if (!c || !hex) return GECM_ERR_ARG;
-    gecm_ctx *s = c;
-    size_t kk = k;
-    if (c->multi) {
-        if (!(s = multi_curve(c, k, 2, &kk))) return multi_err;
-    } else {
-        if (k >= c->batch) return GECM_ERR_ARG;
-        int rc = fetch_acc(c);
-        if (rc) return rc;
-    }
+    size_t pos;
+    const gecm_mod *m = c && hex ? curve_at(c, k, &pos) : NULL;
+    if (!m) return GECM_ERR_ARG;
+    int rc = fetch_acc(c);
+    if (rc) return rc;
     mpl_t v;
-    mpl_from_limbs32(&v, s->hacc + kk, s->batch, s->nl, LIMB_BITS);
-    mpl_mulmod(&v, &v, &s->int_to_ref, &s->N);                   /* what gecm_download_acc returns for the curve */
+    mpl_from_limbs32(&v, c->hacc + pos, c->batch, m->nl, LIMB_BITS);
+    mpl_mulmod(&v, &v, &m->int_to_ref, &m->N);                   /* what gecm_download_acc returns for the curve */
     static __thread char tmp[MPL_MAXL * 10 + 2];
     int n = mpl_get_hex(tmp, &v);
     if (n < 0 || (size_t)n >= hexlen) { set_err("gecm_curve_acc: buffer too small"); return GECM_ERR_ARG; }
     memcpy(hex, tmp, (size_t)n + 1);
     return n;
-}
-
-/* gecm_scan_factors of a multi-modulus context: the device scan compares every curve with its own N; the failure
- * records of stage 2 are settled against the curve's modulus; padding is never flagged */
-static int multi_scan(gecm_ctx *c, int stage, size_t *first)
-{
-    if (stage == 2 && !c->s2_ready) { set_err("gecm_scan_factors: no stage-2 state"); return GECM_ERR_STATE; }
-    uint32_t **f = &c->flags[stage - 1], **hg = &c->hg[stage - 1];
-    if (!*f) *f = (uint32_t *)calloc(c->batch, sizeof(uint32_t));
-    if (!*hg) *hg = (uint32_t *)calloc(c->batch * (size_t)c->nl, sizeof(uint32_t));
-    if (!*f || !*hg) return GECM_ERR_NOMEM;
-    if (gecm_dev_gcd_scan(c->dev, stage - 1, *f, *hg)) { set_err("gecm_scan_factors: %s", gecm_dev_error()); return GECM_ERR_DEVICE; }
-    int rc = stage == 1 ? fetch_plain(c) : fetch_acc(c);
-    if (rc) return rc;
-    size_t n = 0, lo = c->nuser;
-    for (size_t p = 0; p < c->batch; p++) {
-        if (c->pos_user[p] == GECM_PAD) { (*f)[p] = 0; continue; }
-        if (stage == 2) {                              /* a failed batch inversion also marks its curve (ecm.c:1927-1939) */
-            const uint32_t g = c->pos_grp[p];
-            gecm_ctx *s = view_group(c, g);
-            mpl_t r;
-            fail_record(s, p - c->goff[g], &r);
-            if (!mpl_is_zero(&r)) (*f)[p] = (mpl_cmp_u64(&r, 1) > 0 && mpl_cmp(&r, &s->N) != 0);
-        }
-        if ((*f)[p]) { n++; if (c->pos_user[p] < lo) lo = c->pos_user[p]; }
-    }
-    c->scan_valid[stage - 1] = 1;
-    if (first) *first = lo;
-    return (int)(n > 0x7fffffff ? 0x7fffffff : n);
 }
 
 /* the hash of the host sources this object was compiled from (Makefile: H_SHA); gecm_version() compares them */

@@ -1,0 +1,261 @@
+/* gecm_mod.c — the device-free part of the host library (gecm_mod.h): the constants of one number, the curve
+ * construction, failure records and the factor report.  Mirrors the reference's
+ *   Montgomery constants        main.c:597-640
+ *   NWORDS/MAXBITS rule         main.c:465-483
+ *   build_one_curve             ecm.c:1548-1803
+ *   check_factor                ecm.c:1319-1388, 2542-2557
+ */
+#include "gecm_mod.h"
+#include "../../include/gecm.h"
+#include <stdarg.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+__thread char gecm_mod_err[512];
+void gecm_mod_set_err(const char *fmt, ...)
+{
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(gecm_mod_err, sizeof gecm_mod_err, fmt, ap);
+    va_end(ap);
+}
+
+/* K' for the lazy subtraction (csrc/gecm_field.hpp): K = 2^j * mod in [R/32, R/16), written with every
+ * limb in [2^28-1, 2^29): +2^28 at limb 0, +2^28-1 in the middle, -1 at the top. */
+int gecm_mod_make_kp(uint32_t *kp, const mpl_t *mod, int nl)
+{
+    mpl_t K;
+    uint32_t *kl = (uint32_t *)calloc((size_t)nl, sizeof(uint32_t));
+    if (!kl) return -1;
+    mpl_shl(&K, mod, (unsigned)(LIMB_BITS * nl - 4 - mpl_bits(mod)));
+    mpl_to_limbs32(kl, 1, nl, LIMB_BITS, &K);
+    for (int i = 0; i < nl; i++) {
+        if (i == 0) kp[i] = kl[i] + (1u << LIMB_BITS);
+        else if (i < nl - 1) kp[i] = kl[i] + (1u << LIMB_BITS) - 1;
+        else kp[i] = kl[i] - 1;
+    }
+    free(kl);
+    return 0;
+}
+
+void gecm_mod_pow2(mpl_t *r, unsigned e, const mpl_t *m)
+{
+    mpl_t t;
+    mpl_set_u64(&t, 1);
+    mpl_shl(&t, &t, e);
+    mpl_mod(r, &t, m);
+}
+
+int gecm_mod_setup(gecm_mod *m, const char *who, const char *n_str, int digitbits, int nl, int (*pick_nl)(int nbits))
+{
+    if (mpl_set_str(&m->N, n_str) || !mpl_is_odd(&m->N) || mpl_cmp_u64(&m->N, 3) < 0) {
+        gecm_mod_set_err("%s: N must be an odd integer >= 3 (decimal or 0x-hex)", who);
+        return GECM_ERR_ARG;
+    }
+    m->digitbits = digitbits;
+    m->nbits = mpl_bits(&m->N);
+    /* main.c:465-483: MAXBITS = smallest multiple of 208 (128) strictly greater than bitlen */
+    int step = digitbits == 52 ? 208 : 128;
+    m->maxbits = step;
+    while (m->maxbits <= m->nbits) m->maxbits += step;
+    m->nwords = m->maxbits / digitbits;
+    m->nl = nl ? nl : pick_nl(m->nbits);
+    if (!pick_nl(m->nbits) || m->maxbits + 64 > MPL_MAXL * 16) {
+        gecm_mod_set_err("%s: N of %d bits is larger than this build supports", who, m->nbits);
+        return GECM_ERR_ARG;
+    }
+    nl = m->nl;
+    unsigned rint_bits = (unsigned)(LIMB_BITS * nl), rref_bits = (unsigned)m->maxbits;
+    mpl_t t, inv;
+    gecm_mod_pow2(&m->rref_mod_n, rref_bits, &m->N);
+    gecm_mod_pow2(&m->rint_mod_n, rint_bits, &m->N);
+    mpl_invmod(&inv, &m->rref_mod_n, &m->N);
+    mpl_mulmod(&m->ref_to_int, &m->rint_mod_n, &inv, &m->N);
+    mpl_invmod(&inv, &m->rint_mod_n, &m->N);
+    mpl_mulmod(&m->int_to_ref, &m->rref_mod_n, &inv, &m->N);
+    /* rho = -N^-1 mod 2^digitbits (main.c:627-628, 636-640) and mod 2^28 */
+    mpl_t two64;
+    mpl_set_u64(&two64, 1);
+    mpl_shl(&two64, &two64, 64);
+    mpl_invmod(&inv, &m->N, &two64);
+    mpl_sub(&t, &two64, &inv);
+    uint64_t nhat = mpl_get_u64(&t);
+    m->rho_ref = digitbits == 52 ? (nhat & 0xfffffffffffffull) : (nhat & 0xffffffffull);
+    m->rho28 = (uint32_t)(nhat & ((1u << LIMB_BITS) - 1));
+    m->n28 = (uint32_t *)calloc((size_t)nl * 5, sizeof(uint32_t));
+    if (!m->n28) return GECM_ERR_NOMEM;
+    m->kp28 = m->n28 + nl;
+    m->one28 = m->kp28 + nl;
+    m->fix28 = m->one28 + nl;
+    m->r3_28 = m->fix28 + nl;
+    mpl_to_limbs32(m->n28, 1, nl, LIMB_BITS, &m->N);
+    mpl_to_limbs32(m->one28, 1, nl, LIMB_BITS, &m->rint_mod_n);
+    if (gecm_mod_make_kp(m->kp28, &m->N, nl)) { gecm_mod_free(m); return GECM_ERR_NOMEM; }
+    /* fix = Rint^2 / Rref mod N = Rint * ref_to_int */
+    mpl_mulmod(&t, &m->rint_mod_n, &m->ref_to_int, &m->N);
+    mpl_to_limbs32(m->fix28, 1, nl, LIMB_BITS, &t);
+    /* R^3 mod N for the device inversion (csrc/gecm_stage2.hpp: fe_inv_mont) */
+    mpl_mulmod(&t, &m->rint_mod_n, &m->rint_mod_n, &m->N);
+    mpl_mulmod(&t, &t, &m->rint_mod_n, &m->N);
+    mpl_to_limbs32(m->r3_28, 1, nl, LIMB_BITS, &t);
+    /* batches of 28 division steps after which the device inversion has converged for a modulus of nbits bits:
+     * the bound of the "half-delta" variant, floor((45907 bits + 26313) / 19929), +1, rounded up to whole batches */
+    m->inv_iters = (uint32_t)((((45907ull * (unsigned)m->nbits + 26313ull) / 19929ull + 1) + 27) / 28);
+    return GECM_OK;
+}
+
+void gecm_mod_free(gecm_mod *m)
+{
+    free(m->n28);                          /* kp28 .. r3_28 are parts of it */
+    m->n28 = NULL;
+}
+
+/* Suyama curve for one sigma up to (but not including) the two modular inversions
+ * (ecm.c:1587-1641, 1717-1722): outputs x3 = u^3 mod n, z3 = v^3 mod n, num = (v-u)^3 (3u+v) mod n,
+ * den = 16 u^3 v mod n. */
+static void suyama_pre(const mpl_t *n, uint64_t sigma, mpl_t *x3, mpl_t *z3, mpl_t *num, mpl_t *den)
+{
+    mpl_t u, v, t1, t2, t3, t4;
+    mpl_set_u64(&v, sigma);
+    mpl_shl(&v, &v, 2);                 /* v = 4 sigma            ecm.c:1588-1589 */
+    mpl_set_u64(&u, sigma);
+    mpl_mul(&u, &u, &u);
+    mpl_set_u64(&t1, 5);
+    mpl_sub(&u, &u, &t1);               /* u = sigma^2 - 5        ecm.c:1596-1598 */
+    mpl_mul(&t1, &u, &u);
+    mpl_mul(&t1, &t1, &u);
+    mpl_mod(x3, &t1, n);                /* x = u^3                ecm.c:1601-1603 */
+    mpl_mul(&t1, &v, &v);
+    mpl_mul(&t1, &t1, &v);
+    mpl_mod(z3, &t1, n);                /* z = v^3                ecm.c:1607-1609 */
+    /* (v - u) mod n                                               ecm.c:1615-1623 */
+    mpl_t um, vm;
+    mpl_mod(&um, &u, n);
+    mpl_mod(&vm, &v, n);
+    mpl_submod(&t1, &vm, &um, n);
+    mpl_mulmod(&t2, &t1, &t1, n);
+    mpl_mulmod(&t4, &t2, &t1, n);       /* (v-u)^3                ecm.c:1626-1629 */
+    mpl_mul_u64(&t3, &u, 3);
+    mpl_add(&t3, &t3, &v);
+    mpl_mod(&t3, &t3, n);               /* 3u + v                 ecm.c:1632-1634 */
+    mpl_mulmod(num, &t3, &t4, n);       /* a = (v-u)^3 (3u+v)     ecm.c:1637-1638 */
+    mpl_mul_u64(&t2, x3, 16);
+    mpl_mul(&t2, &t2, &v);
+    mpl_mod(den, &t2, n);               /* 16 u^3 v               ecm.c:1718-1720 */
+}
+
+/* One worker's slice [lo, hi): the whole Suyama construction for those curves.
+ * The two inversions per curve, mpz_invert(16u^3v) ecm.c:1745 and mpz_invert(v^3) ecm.c:1759, share the
+ * modulus, so each slice does Montgomery's simultaneous inversion: one extended Euclid per slice
+ * instead of two per curve.  Inverses mod N are unique, so the values are the ones GMP returns. */
+int gecm_mod_build_slice(void *build, size_t lo, size_t hi)
+{
+    const gecm_mod_build *j = (const gecm_mod_build *)build;
+    const gecm_mod *c = j->m;
+    const size_t cnt = hi - lo, m = 2 * cnt, batch = j->batch;
+    const int nl = c->nl;
+    int anybad = 0;
+    if (cnt == 0) return 0;
+    mpl_t *x3 = (mpl_t *)malloc(cnt * sizeof(mpl_t) * 2);
+    mpl_t *dens = (mpl_t *)malloc(m * sizeof(mpl_t));
+    mpl_t *pref = (mpl_t *)malloc(m * sizeof(mpl_t));
+    if (!x3 || !dens || !pref) { free(x3); free(dens); free(pref); return GECM_ERR_NOMEM; }
+    mpl_t *num = x3 + cnt;
+    for (size_t i = 0; i < cnt; i++)
+        suyama_pre(&c->N, j->sigma[lo + i], &x3[i], &dens[2 * i + 1], &num[i], &dens[2 * i]);
+    int batch_ok = 1;
+    pref[0] = dens[0];
+    for (size_t i = 1; i < m; i++) mpl_mulmod(&pref[i], &pref[i - 1], &dens[i], &c->N);
+    mpl_t inv, t;
+    if (!mpl_invmod(&inv, &pref[m - 1], &c->N)) batch_ok = 0;
+    mpl_t *invs = pref;   /* overwritten back to front */
+    if (batch_ok) {
+        for (size_t i = m - 1; i > 0; i--) {
+            mpl_mulmod(&t, &inv, &pref[i - 1], &c->N);      /* dens[i]^-1 */
+            mpl_mulmod(&inv, &inv, &dens[i], &c->N);
+            invs[i] = t;
+        }
+        invs[0] = inv;
+    } else {
+        /* Some denominator shares a factor with N.  The reference ignores mpz_invert's return
+         * value (ecm.c:1745, 1759); GMP leaves the destination untouched on failure, so the
+         * reference goes on with the STALE operand: t2 = 16*u^3 (ecm.c:1718) in place of
+         * (16u^3v)^-1 and t1 = (v-u)^3(3u+v) (ecm.c:1637) in place of (v^3)^-1.  Reproduced here so
+         * that such curves still give the reference's residues bit for bit; the lane is also
+         * flagged (a non-invertible denominator means gcd(denominator, N) is a factor). */
+        for (size_t i = 0; i < m; i++)
+            if (!mpl_invmod(&invs[i], &dens[i], &c->N)) {
+                j->bad[j->off + lo + i / 2] = 1;
+                anybad = 1;
+                if ((i & 1) == 0) { mpl_mul_u64(&t, &x3[i / 2], 16); mpl_mod(&invs[i], &t, &c->N); }
+                else invs[i] = num[i / 2];
+            }
+    }
+    for (size_t i = 0; i < cnt; i++) {
+        mpl_t A, X, Xm, Sm;
+        const size_t k = j->off + lo + i;
+        mpl_mulmod(&A, &num[i], &invs[2 * i], &c->N);          /* b = a / 16u^3v   ecm.c:1752-1753 */
+        mpl_mulmod(&X, &x3[i], &invs[2 * i + 1], &c->N);       /* X = u^3 / v^3, Z = 1  ecm.c:1759-1761 */
+        /* into Montgomery form (ecm.c:1763-1772), internal radix */
+        mpl_mulmod(&Xm, &X, &c->rint_mod_n, &c->N);
+        mpl_mulmod(&Sm, &A, &c->rint_mod_n, &c->N);
+        mpl_to_limbs32(j->hX + k, batch, nl, LIMB_BITS, &Xm);
+        mpl_to_limbs32(j->hZ + k, batch, nl, LIMB_BITS, &c->rint_mod_n);
+        mpl_to_limbs32(j->hS + k, batch, nl, LIMB_BITS, &Sm);
+        if (j->fX) {           /* plain residues mod N, lifted to Montgomery form modulo Mw = 2^k - 1 */
+            mpl_mulmod(&Xm, &X, j->ff_r_mod_m, j->ff_M);
+            mpl_mulmod(&Sm, &A, j->ff_r_mod_m, j->ff_M);
+            mpl_to_limbs32(j->fX + k, batch, j->ff_nl, LIMB_BITS, &Xm);
+            mpl_to_limbs32(j->fZ + k, batch, j->ff_nl, LIMB_BITS, j->ff_r_mod_m);
+            mpl_to_limbs32(j->fS + k, batch, j->ff_nl, LIMB_BITS, &Sm);
+        }
+    }
+    free(x3); free(dens); free(pref);
+    return anybad;
+}
+
+/* The reference overwrites its accumulator with gcd(product of the batch, N) every time a batch inversion fails
+ * (ecm.c:1925-1939): what its scan finds in the end is the gcd of the LAST failing batch (times later cross products).
+ * Plane 0 holds that gcd for the single-chain inversions — after gecm_stage2_pair the last chunk of the range, cut to
+ * be exactly the reference's last batch — and decides when it holds one.  Otherwise the sub-sequences' planes stand
+ * for one batch inverted in K pieces: the gcd of N with the PRODUCT of their records is the gcd of the whole batch's
+ * product (for a product that covers N that is N itself — "no factor", which is what the reference finds then too:
+ * its batch product is 0 modulo N).  Every record is passed through gcd(., N) first: what comes out divides N. */
+void gecm_mod_fail_record(const gecm_mod *m, const uint32_t *hfail, uint32_t planes, size_t batch, size_t k, mpl_t *g)
+{
+    const size_t plane = batch * (size_t)m->nl;
+    mpl_t t, prod, gp;
+    mpl_from_limbs32(&t, hfail + k, batch, m->nl, LIMB_BITS);
+    if (!mpl_is_zero(&t)) { mpl_gcd(g, &t, &m->N); return; }
+    mpl_set_u64(g, 0);
+    if (planes <= 1) return;
+    mpl_set_u64(&prod, 0);
+    for (uint32_t p = 1; p < planes; p++) {
+        mpl_from_limbs32(&t, hfail + p * plane + k, batch, m->nl, LIMB_BITS);
+        if (mpl_is_zero(&t)) continue;
+        mpl_gcd(&gp, &t, &m->N);
+        if (mpl_is_zero(&prod)) prod = gp;
+        else mpl_mulmod(&prod, &prod, &gp, &m->N);
+        if (mpl_is_zero(&prod)) { prod = m->N; break; }       /* the product covers N: gcd = N, "no factor" */
+    }
+    if (!mpl_is_zero(&prod)) mpl_gcd(g, &prod, &m->N);
+}
+
+int gecm_mod_factor(const gecm_mod *m, mpl_t *g, const char *who, char *dec, size_t declen, int *is_prp)
+{
+    if (!to_report(m, g)) return 0;
+    static __thread char tmp[MPL_MAXL * 10 + 16];
+    int n = mpl_get_dec(tmp, g);
+    if (dec && declen) {
+        if ((size_t)n >= declen) { gecm_mod_set_err("%s: buffer too small", who); return GECM_ERR_ARG; }
+        memcpy(dec, tmp, (size_t)n + 1);
+    }
+    if (is_prp) *is_prp = mpl_probab_prime(g, 3);   /* ecm.c:1346 */
+    return 1;
+}
+
+/* the hash of the host sources this object was compiled from (Makefile: H_SHA); gecm_version() compares them */
+#ifdef GECM_MANIFEST_FN
+const char *GECM_MANIFEST_FN(void) { return GECM_MANIFEST; }
+#endif

@@ -1,0 +1,67 @@
+/* gecm_mod.h — one number N and everything derived from it, and the host work that needs nothing else: the Suyama
+ * curve construction, the failed-inversion records of stage 2, the factor report.  No device, no batch state: a
+ * context (gecm_api.c) holds one gecm_mod, a multi-modulus context one more per modulus. */
+#ifndef GECM_MOD_H
+#define GECM_MOD_H
+#include "mpl.h"
+
+#define LIMB_BITS 28
+
+typedef struct {
+    int digitbits, nwords, maxbits, nbits, nl;
+    mpl_t N;
+    mpl_t N_report;      /* gecm_set_report_modulus: the number the save lines name and factors are looked for in */
+    int have_report;
+    mpl_t rref_mod_n;    /* 2^(digitbits*nwords) mod N  = the reference's "one" */
+    mpl_t rint_mod_n;    /* 2^(28*nl) mod N */
+    mpl_t ref_to_int;    /* Rint * Rref^-1 mod N : x*Rref -> x*Rint by plain modular multiply */
+    mpl_t int_to_ref;    /* Rref * Rint^-1 mod N */
+    uint64_t rho_ref;
+    uint32_t rho28;
+    uint32_t *n28, *kp28, *one28, *fix28; /* fix28 = Rint^2/Rref mod N (see gecm_dev_l0) */
+    uint32_t *r3_28;     /* Rint^3 mod N for the device inversion */
+    uint32_t inv_iters;  /* batches of 28 division steps after which the device inversion has converged for N */
+} gecm_mod;
+
+/* the calling thread's error text (gecm_last_error) */
+extern __thread char gecm_mod_err[512];
+void gecm_mod_set_err(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
+
+/* N and everything derived from it, at nl limbs (0: pick_nl(bits of N), which also says — with 0 — that N is too
+ * large); `who` prefixes the error texts.  On error m holds nothing to free. */
+int gecm_mod_setup(gecm_mod *m, const char *who, const char *n_str, int digitbits, int nl, int (*pick_nl)(int nbits));
+void gecm_mod_free(gecm_mod *m);
+int gecm_mod_make_kp(uint32_t *kp, const mpl_t *mod, int nl);
+void gecm_mod_pow2(mpl_t *r, unsigned e, const mpl_t *m);       /* 2^e mod m */
+
+static inline const mpl_t *report_n(const gecm_mod *m) { return m->have_report ? &m->N_report : &m->N; }
+
+/* g = gcd(value, N) -> the factor of the report modulus it holds; is it a proper one? */
+static inline int to_report(const gecm_mod *m, mpl_t *g)
+{
+    if (m->have_report && !mpl_is_zero(g)) { mpl_t t = *g; mpl_gcd(g, &t, &m->N_report); }
+    return mpl_cmp_u64(g, 1) > 0 && mpl_cmp(g, report_n(m)) != 0;
+}
+
+/* The Suyama construction for curves [lo, hi) of `sigma`, written to position off + k of arrays of stride `batch`
+ * (gecm_mod_build_slice).  fX != NULL: the same three values once more in Montgomery form modulo ff_M. */
+typedef struct {
+    const gecm_mod *m;
+    const uint64_t *sigma;
+    uint8_t *bad;             /* [batch], set where a denominator does not invert */
+    size_t batch, off;
+    uint32_t *hX, *hZ, *hS;   /* [nl][batch] */
+    const mpl_t *ff_M, *ff_r_mod_m;
+    int ff_nl;
+    uint32_t *fX, *fZ, *fS;   /* [ff_nl][batch] */
+} gecm_mod_build;
+/* GECM_ERR_NOMEM, 1 if some curve was marked bad, else 0 */
+int gecm_mod_build_slice(void *build, size_t lo, size_t hi);
+
+/* the failed-inversion record of the curve at position k of hfail ([planes][nl][batch]): 0 or a divisor of N */
+void gecm_mod_fail_record(const gecm_mod *m, const uint32_t *hfail, uint32_t planes, size_t batch, size_t k, mpl_t *g);
+
+/* g = gcd(value, N): 1 with the decimal string and PRP test if it holds a proper factor of the report modulus,
+ * else 0; GECM_ERR_ARG "<who>: buffer too small" */
+int gecm_mod_factor(const gecm_mod *m, mpl_t *g, const char *who, char *dec, size_t declen, int *is_prp);
+#endif

@@ -1,9 +1,11 @@
 /* tools/host_sanitize.c — the host-side logic of libgecm (everything that runs without a device) under
  * AddressSanitizer + UBSan.  Built and run by tools/host_sanitize.sh on the CPU; GPU sanitizers are not
  * available on the pool.  Exercises: expression evaluator and input preparation with random and
- * hostile strings, mpl arithmetic identities, the stage-1 tape compiler, the stage-2 plan and PAIR. */
+ * hostile strings, mpl arithmetic identities, the stage-1 tape compiler, the stage-2 plan and PAIR, the constants of
+ * a modulus and the curve construction. */
 #include "../avx-ecm_amd/host/calc_lite.h"
 #include "../avx-ecm_amd/host/cunningham.h"
+#include "../avx-ecm_amd/host/gecm_mod.h"
 #include "../avx-ecm_amd/host/gecm_pair.h"
 #include "../avx-ecm_amd/host/gecm_plan.h"
 #include "../avx-ecm_amd/host/mpl.h"
@@ -14,6 +16,8 @@
 
 static uint64_t rng = 88172645463325252ull;
 static uint64_t rnd(void) { rng ^= rng << 13; rng ^= rng >> 7; rng ^= rng << 17; return rng; }
+
+static int need_nl(int nbits) { return (nbits + 5 + 27) / 28; }   /* R = 2^(28 nl) >= 32 N */
 
 int main(void)
 {
@@ -135,6 +139,51 @@ int main(void)
             }
             free(z);
             gecm_s2_plan_free(&p);
+        }
+    }
+    /* 6. gecm_mod: N's constants at every limb count of the build (n28 is N; K' is K = 2^j N in [R/32, R/16) with every
+     * limb below the top one in [2^28 - 1, 2^29)), and the curve construction, last modulo 3*5*7*11*13, where denominators do not invert and build_slice goes on
+     * with the reference's stale operands */
+    {
+        const int nls[] = {8, 10, 12, 14, 15, 17, 19, 21, 23, 26, 28, 30, 32, 34, 37, 8};
+        const size_t cases = sizeof nls / sizeof *nls;
+        uint64_t sig[300];
+        for (int i = 0; i < 300; i++) sig[i] = 6 + (uint64_t)i;
+        for (size_t q = 0; q < cases; q++) {
+            const int nl = nls[q], last = q == cases - 1;
+            gecm_mod m;
+            mpl_t n, t, k;
+            memset(&m, 0, sizeof m);
+            n.n = nl;                                   /* 28 nl - 5 bits, odd */
+            for (int i = 0; i < nl; i++) n.d[i] = (uint32_t)rnd();
+            n.d[nl - 1] |= 0x80000000u;
+            mpl_shr(&n, &n, (unsigned)(4 * nl + 5));
+            n.d[0] |= 1;
+            if (last) mpl_set_u64(&n, 15015);
+            mpl_get_dec(ndec, &n);
+            if (gecm_mod_setup(&m, "sanitize", ndec, 52, nl, need_nl)) { printf("mod_setup: %s\n", gecm_mod_err); return 1; }
+            mpl_from_limbs32(&t, m.n28, 1, nl, LIMB_BITS);
+            int good = !mpl_cmp(&t, &n);
+            mpl_set_u64(&t, 0);
+            for (int i = nl - 1; i >= 0; i--) {
+                if (i < nl - 1) good &= m.kp28[i] >= (1u << LIMB_BITS) - 1 && m.kp28[i] < (2u << LIMB_BITS);
+                mpl_shl(&t, &t, LIMB_BITS);
+                mpl_add_u64(&t, &t, m.kp28[i]);
+            }
+            mpl_shl(&k, &n, (unsigned)(LIMB_BITS * nl - 4 - mpl_bits(&n)));
+            good &= !mpl_cmp(&t, &k);
+            if (!good) { printf("mod_setup: n28 or kp28 wrong at %d limbs\n", nl); return 1; }
+            if (nl == 15 || last) {
+                uint32_t *h = (uint32_t *)calloc((size_t)900 * nl, sizeof(uint32_t));
+                uint8_t bad[300] = {0};
+                gecm_mod_build b = {&m, sig, bad, 300, 0, h, h + 300 * nl, h + 600 * nl, NULL, NULL, 0, NULL, NULL, NULL};
+                int rc = h ? gecm_mod_build_slice(&b, 0, 300) : -1, nbad = 0;
+                for (int i = 0; i < 300; i++) nbad += bad[i];
+                printf("build_slice at %d limbs: rc=%d bad=%d\n", nl, rc, nbad);
+                if (rc != (nbad > 0) || (last && !nbad)) { printf("build_slice: wrong bad flags\n"); return 1; }
+                free(h);
+            }
+            gecm_mod_free(&m);
         }
     }
     size_t np;
