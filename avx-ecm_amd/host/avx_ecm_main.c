@@ -76,7 +76,7 @@ typedef struct {
     uint64_t lo, hi;
     uint32_t D, U;
     gecm_pairs pm;
-    int valid, rc;
+    int valid;
     int settled;               /* made or failed: the job threads wait for this before they prepare their tapes */
     int claimed;               /* some pass has taken on making it */
     pthread_mutex_t mu;
@@ -84,6 +84,9 @@ typedef struct {
 } first_range_t;
 
 /* ---- run-wide state ------------------------------------------------------------------------- */
+enum { GPU, OUT };             /* what passes take turns on: the GPUs, and the files and stdout */
+enum { DONE, FOUND, FAILED };  /* how a pass leaves a turn */
+
 typedef struct {
     uint64_t B1, B2, sigma0;
     int do_stage2, threads, fixed_sigma;
@@ -94,12 +97,12 @@ typedef struct {
     size_t ub;                 /* distinct curves per reference batch: 8 (fixed sigma) or 8*threads */
     first_range_t fr;
     gecm_stage1_range_desc *rd;   /* what vececm prints and decides around each prime range (made once, on a helper thread) */
-    pthread_t rd_thread;
-    int rd_pending, rd_rc;
+    int rd_rc;
+    char rd_err[512];          /* gecm_last_error() of the helper thread (the text is thread-local) */
     /* pipeline: passes take the GPUs and write their output in pass order */
     pthread_mutex_t mu;
     pthread_cond_t cv;
-    size_t gpu_turn, out_turn;
+    size_t turn[2];            /* the pass whose turn it is on the GPUs / on the output */
     size_t found_pass;         /* the pass that found a factor (SIZE_MAX: none yet): later passes are not run, not written */
     int failed;
     uint64_t lcg;
@@ -107,11 +110,42 @@ typedef struct {
 } run_t;
 
 typedef struct {
-    int gpu;
+    char *buf;
+    size_t len, cap;
+} text_t;
+
+/* ---- the curves of one input's batches and where each lives: all that formatting and writing them needs ---- */
+typedef struct {
     gecm_ctx *ctx;
-    uint64_t *sigma;
-    size_t ncurves, first;     /* this GPU's slice of the pass: distinct curves first .. first+ncurves */
+    const uint64_t *sigma;     /* by context index */
+    size_t ncurves, first;     /* this context's slice: distinct curves first .. first+ncurves */
     size_t koff;               /* context index of distinct curve `first` (0; a multi-modulus pass: the input's first) */
+} part_t;
+
+/* checkpoints (several prime ranges): per range written, its lines in (batch, thread, lane) order and the factor lines
+ * of the first flagged batch */
+typedef struct {
+    char **lines;              /* ucurves resume lines (distinct curves) */
+    size_t first_flagged;      /* batch (within the pass), or nb if none */
+    text_t res;                /* ecm_results.txt lines of that batch */
+} ck_t;
+
+typedef struct {
+    const run_t *run;
+    size_t b0, nb;             /* reference batches b0 .. b0+nb of the run */
+    size_t ucurves;            /* distinct curves = nb * ub */
+    int nparts;
+    part_t part[MAX_GPUS];
+    int nck;
+    ck_t *ck;
+    long ck_offset;            /* where this pass's part of checkpoint.txt starts */
+} view_t;
+
+/* ---- what only the pipeline needs: the per-GPU jobs of a pass, its thread, its place in the order, its log ---- */
+typedef struct job_t {
+    int gpu;
+    const part_t *part;
+    int (*step)(struct job_t *);
     uint64_t B1;
     uint32_t range;
     int rc;
@@ -123,32 +157,15 @@ typedef struct {
 } job_t;
 
 typedef struct {
-    char *buf;
-    size_t len, cap;
-} text_t;
-
-typedef struct {
-    run_t *run;
+    run_t *run;                /* NULL: no pass in this slot */
     size_t index;              /* pass number */
-    int slot;
-    size_t b0, nb;             /* reference batches b0 .. b0+nb of the run */
-    size_t ucurves;            /* distinct curves of the pass = nb * ub */
+    view_t v;
     uint64_t *sigma;
     job_t jobs[MAX_GPUS];
     text_t log;                /* this pass's stdout, released in pass order */
     int live;                  /* not pipelined: print as it happens */
-    /* checkpoints (several prime ranges): per range written, its lines in (batch, thread, lane) order and the
-     * factor lines of the first flagged batch */
-    int nck;
-    struct ck_t {
-        uint64_t last_prime;
-        char **lines;          /* ucurves resume lines (distinct curves) */
-        size_t first_flagged;  /* batch (within the pass), or nb if none */
-        text_t res, out;       /* ecm_results.txt lines / stdout lines of that batch */
-    } *ck;
-    long ck_offset;            /* where this pass's part of checkpoint.txt starts */
     pthread_t th;
-    double t_build, t_stage1, t_s2init, t_s2;
+    int threaded;              /* th is a thread to join */
 } pass_t;
 
 static void text_add(text_t *t, const char *s, size_t n)
@@ -166,27 +183,37 @@ static void text_add(text_t *t, const char *s, size_t n)
     t->buf[t->len] = 0;
 }
 
-static void text_printf(text_t *t, const char *fmt, ...)
+static void text_vprintf(text_t *t, const char *fmt, va_list ap)
 {
     char tmp[8192];
+    int n = vsnprintf(tmp, sizeof tmp, fmt, ap);
+    if (n > 0) text_add(t, tmp, (size_t)n < sizeof tmp ? (size_t)n : sizeof tmp - 1);
+}
+
+static void text_printf(text_t *t, const char *fmt, ...)
+{
     va_list ap;
     va_start(ap, fmt);
-    int n = vsnprintf(tmp, sizeof tmp, fmt, ap);
+    text_vprintf(t, fmt, ap);
     va_end(ap);
-    if (n > 0) text_add(t, tmp, (size_t)n < sizeof tmp ? (size_t)n : sizeof tmp - 1);
 }
 
 /* a line of this pass's stdout */
 static void plog(pass_t *ps, const char *fmt, ...)
 {
-    char tmp[8192];
     va_list ap;
     va_start(ap, fmt);
-    int n = vsnprintf(tmp, sizeof tmp, fmt, ap);
+    text_vprintf(&ps->log, fmt, ap);
     va_end(ap);
-    if (n <= 0) return;
-    if (ps->live) { fputs(tmp, stdout); fflush(stdout); }
-    else text_add(&ps->log, tmp, (size_t)n < sizeof tmp ? (size_t)n : sizeof tmp - 1);
+    if (ps->live && ps->log.len) { fputs(ps->log.buf, stdout); fflush(stdout); ps->log.len = 0; }
+}
+
+/* an environment knob that counts something: its value, 0 when unset or not positive */
+static long env_count(const char *name)
+{
+    const char *s = getenv(name);
+    const long v = s ? atol(s) : 0;
+    return v > 0 ? v : 0;
 }
 
 /* the sieved interval, prime count, first and last prime and checkpoint decision of every stage-1 range: 0.25 s of
@@ -196,93 +223,78 @@ static void *describe_ranges(void *arg)
     run_t *R = (run_t *)arg;
     for (int r = 0; r < R->nranges && !R->rd_rc; r++)
         R->rd_rc = gecm_stage1_describe_range(R->B1, R->B2, (uint32_t)r, &R->rd[r]);
+    if (R->rd_rc) snprintf(R->rd_err, sizeof R->rd_err, "%s", gecm_last_error());
     return NULL;
 }
 
 /* ---- per-GPU jobs of a pass ----------------------------------------------------------------- */
-static void *job_build(void *p)
+static int step_build(job_t *j)
+{
+    return gecm_build_curves(j->part->ctx, j->part->sigma, j->part->ncurves);
+}
+
+static int step_stage1(job_t *j)
+{
+    gecm_ctx *ctx = j->part->ctx;
+    int rc = gecm_stage1_range(ctx, j->B1, j->range);                     /* returns after the launch */
+    if (rc == 0 && j->fr) {
+        /* while the kernel runs: this context's launch tape of the first stage-2 range, as soon as the pass
+         * thread has the pair map (0.13 s of host time; later passes find it kept) */
+        first_range_t *fr = j->fr;
+        pthread_mutex_lock(&fr->mu);
+        while (!fr->settled) pthread_cond_wait(&fr->cv, &fr->mu);
+        pthread_mutex_unlock(&fr->mu);
+        if (fr->valid)
+            (void)gecm_stage2_pair_prepare(ctx, fr->D, fr->U, fr->pm.steps, fr->pm.pairmap_v, fr->pm.pairmap_u, fr->pm.amin);
+    }
+    if (rc == 0 && j->progress) {
+        /* a 1e8 prime range is 13 launches of up to minutes each: say where it is (the reference prints
+         * "accumulating prime" every 8192 primes, ecm.c:1834-1842) */
+        uint32_t done = 0, total = 0, shown = 0;
+        while (gecm_stage1_progress(ctx, &done, &total) == 0 && total > 1 && done < total) {
+            if (done != shown) { printf("stage 1, range %u: launch %u of %u done\r", j->range, done, total); fflush(stdout); shown = done; }
+            usleep(200000);
+        }
+    }
+    if (rc == 0) rc = gecm_sync(ctx);
+    if (rc == 0) j->kernel_ms += gecm_last_kernel_ms(ctx);
+    /* the device factor scan and the download of x, z belong to the GPU's turn (the next pass's kernel would
+     * keep them waiting); formatting happens later, off the GPU */
+    if (rc == 0 && gecm_scan_factors(ctx, 1, NULL) < 0) rc = -1;
+    return rc;
+}
+
+static int step_stage2_init(job_t *j)
+{
+    const int rc = gecm_stage2_init(j->part->ctx, 0, 0);                  /* ecm.c:1401-1407 */
+    return rc ? rc : gecm_sync(j->part->ctx);
+}
+
+static int step_stage2_pair(job_t *j)
+{
+    const int rc = gecm_stage2_pair(j->part->ctx, j->pm->steps, j->pm->pairmap_v, j->pm->pairmap_u, j->pm->amin);   /* ecm.c:1460 */
+    return rc ? rc : gecm_sync(j->part->ctx);
+}
+
+static int step_stage2_scan(job_t *j)
+{
+    return gecm_scan_factors(j->part->ctx, 2, NULL) < 0 ? -1 : 0;
+}
+
+/* the thread of a job: nothing to do without curves; the error text is taken here, on the thread that made it
+ * (gecm_last_error() is thread-local) */
+static void *job_run(void *p)
 {
     job_t *j = (job_t *)p;
-    j->rc = j->ncurves ? gecm_build_curves(j->ctx, j->sigma, j->ncurves) : 0;
+    j->rc = j->part->ncurves ? j->step(j) : 0;
     if (j->rc < 0) snprintf(j->err, sizeof j->err, "%s", gecm_last_error());
-    return NULL;
-}
-
-static void *job_stage1(void *p)
-{
-    job_t *j = (job_t *)p;
-    j->rc = 0;
-    if (j->ncurves) {
-        j->rc = gecm_stage1_range(j->ctx, j->B1, j->range);               /* returns after the launch */
-        if (j->rc == 0 && j->fr) {
-            /* while the kernel runs: this context's launch tape of the first stage-2 range, as soon as the pass
-             * thread has the pair map (0.13 s of host time; later passes find it kept) */
-            first_range_t *fr = j->fr;
-            pthread_mutex_lock(&fr->mu);
-            while (!fr->settled) pthread_cond_wait(&fr->cv, &fr->mu);
-            pthread_mutex_unlock(&fr->mu);
-            if (fr->valid)
-                (void)gecm_stage2_pair_prepare(j->ctx, fr->D, fr->U, fr->pm.steps, fr->pm.pairmap_v, fr->pm.pairmap_u, fr->pm.amin);
-        }
-        if (j->rc == 0 && j->progress) {
-            /* a 1e8 prime range is 13 launches of up to minutes each: say where it is (the reference prints
-             * "accumulating prime" every 8192 primes, ecm.c:1834-1842) */
-            uint32_t done = 0, total = 0, shown = 0;
-            while (gecm_stage1_progress(j->ctx, &done, &total) == 0 && total > 1 && done < total) {
-                if (done != shown) { printf("stage 1, range %u: launch %u of %u done\r", j->range, done, total); fflush(stdout); shown = done; }
-                usleep(200000);
-            }
-        }
-        if (j->rc == 0) j->rc = gecm_sync(j->ctx);
-        if (j->rc == 0) j->kernel_ms += gecm_last_kernel_ms(j->ctx);
-        /* the device factor scan and the download of x, z belong to the GPU's turn (the next pass's kernel would
-         * keep them waiting); formatting happens later, off the GPU */
-        if (j->rc == 0 && gecm_scan_factors(j->ctx, 1, NULL) < 0) j->rc = -1;
-        if (j->rc < 0) snprintf(j->err, sizeof j->err, "%s", gecm_last_error());
-    }
-    return NULL;
-}
-
-static void *job_stage2_init(void *p)
-{
-    job_t *j = (job_t *)p;
-    j->rc = 0;
-    if (j->ncurves) {
-        j->rc = gecm_stage2_init(j->ctx, 0, 0);                           /* ecm.c:1401-1407 */
-        if (j->rc == 0) j->rc = gecm_sync(j->ctx);
-        if (j->rc < 0) snprintf(j->err, sizeof j->err, "%s", gecm_last_error());
-    }
-    return NULL;
-}
-
-static void *job_stage2_pair(void *p)
-{
-    job_t *j = (job_t *)p;
-    j->rc = 0;
-    if (j->ncurves) {
-        j->rc = gecm_stage2_pair(j->ctx, j->pm->steps, j->pm->pairmap_v, j->pm->pairmap_u, j->pm->amin);   /* ecm.c:1460 */
-        if (j->rc == 0) j->rc = gecm_sync(j->ctx);
-        if (j->rc < 0) snprintf(j->err, sizeof j->err, "%s", gecm_last_error());
-    }
-    return NULL;
-}
-
-static void *job_stage2_scan(void *p)
-{
-    job_t *j = (job_t *)p;
-    j->rc = 0;
-    if (j->ncurves && gecm_scan_factors(j->ctx, 2, NULL) < 0) {
-        j->rc = -1;
-        snprintf(j->err, sizeof j->err, "%s", gecm_last_error());
-    }
     return NULL;
 }
 
 static void make_first_range(first_range_t *fr)
 {
     if (!fr->valid) {
-        fr->rc = gecm_pair_primes(&fr->pm, fr->lo, fr->hi, fr->D, fr->U);
-        fr->valid = fr->rc == 0;
+        fr->valid = gecm_pair_primes(&fr->pm, fr->lo, fr->hi, fr->D, fr->U) == 0;
     }
     pthread_mutex_lock(&fr->mu);
     fr->settled = 1;
@@ -290,19 +302,16 @@ static void make_first_range(first_range_t *fr)
     pthread_mutex_unlock(&fr->mu);
 }
 
-static int run_all(job_t *jobs, int n, void *(*fn)(void *), first_range_t *meanwhile, int make_it)
+static int run_all(job_t *jobs, int n, int (*step)(job_t *), first_range_t *meanwhile, int make_it)
 {
     pthread_t th[MAX_GPUS];
-    for (int i = 0; i < n; i++) jobs[i].fr = meanwhile;
-    if (meanwhile && make_it) {              /* every job on a thread of its own, the host work here */
-        for (int i = 0; i < n; i++) pthread_create(&th[i], NULL, fn, &jobs[i]);
-        make_first_range(meanwhile);
-        for (int i = 0; i < n; i++) pthread_join(th[i], NULL);
-    } else {
-        for (int i = 1; i < n; i++) pthread_create(&th[i], NULL, fn, &jobs[i]);
-        fn(&jobs[0]);
-        for (int i = 1; i < n; i++) pthread_join(th[i], NULL);
-    }
+    for (int i = 0; i < n; i++) { jobs[i].step = step; jobs[i].fr = meanwhile; }
+    /* job 0 on this thread — unless the map is to be made: then every job on a thread of its own, the host work here */
+    const int here = !(meanwhile && make_it);
+    for (int i = here; i < n; i++) pthread_create(&th[i], NULL, job_run, &jobs[i]);
+    if (here) job_run(&jobs[0]);
+    else make_first_range(meanwhile);
+    for (int i = here; i < n; i++) pthread_join(th[i], NULL);
     for (int i = 0; i < n; i++)
         if (jobs[i].rc < 0) {
             fprintf(stderr, "GPU %d: %s\n", jobs[i].gpu, jobs[i].err);
@@ -312,49 +321,52 @@ static int run_all(job_t *jobs, int n, void *(*fn)(void *), first_range_t *meanw
 }
 
 /* ---- where a line of the reference's files comes from ------------------------------------------
- * Line `l` (0 .. 8*threads) of batch b of a pass is distinct curve b*ub + (fixed sigma ? l % 8 : l) of the pass:
- * which job holds it, and at which index. */
-static void locate(const pass_t *ps, size_t b, size_t l, int *g, size_t *k)
+ * Line `l` (0 .. 8*threads) of batch b of a view is distinct curve b*ub + (fixed sigma ? l % 8 : l) of the view ... */
+static inline size_t line_curve(const run_t *R, size_t b, size_t l)
 {
-    const run_t *R = ps->run;
-    const size_t u = b * R->ub + (R->fixed_sigma ? l % VECLEN : l);
-    for (int i = 0; i < R->gpus; i++)
-        if (u >= ps->jobs[i].first && u < ps->jobs[i].first + ps->jobs[i].ncurves) {
-            *g = i;
-            *k = u - ps->jobs[i].first + ps->jobs[i].koff;
-            return;
-        }
-    *g = 0; *k = 0;
+    return b * R->ub + (R->fixed_sigma ? l % VECLEN : l);
 }
 
-static int batch_flagged(const pass_t *ps, int stage, size_t b)
+/* ... and distinct curve u is held by one of the view's contexts: which, and at which index */
+static const part_t *locate(const view_t *v, size_t u, size_t *k)
 {
-    const run_t *R = ps->run;
-    for (size_t u = b * R->ub; u < (b + 1) * R->ub; u++) {
-        int g; size_t k;
-        locate(ps, b, u - b * R->ub, &g, &k);
-        if (gecm_curve_flag(ps->jobs[g].ctx, stage, k)) return 1;
+    for (int i = 0; i < v->nparts; i++)
+        if (u >= v->part[i].first && u < v->part[i].first + v->part[i].ncurves) {
+            *k = u - v->part[i].first + v->part[i].koff;
+            return &v->part[i];
+        }
+    *k = 0;
+    return &v->part[0];
+}
+
+/* the first of batches 0 .. upto with a curve flagged after stage 1 (stages = 2: after either stage); upto if none */
+static size_t first_flagged(const view_t *v, size_t upto, int stages)
+{
+    for (size_t u = 0; u < upto * v->run->ub; u++) {
+        size_t k;
+        const part_t *p = locate(v, u, &k);
+        if (gecm_curve_flag(p->ctx, 1, k) || (stages > 1 && gecm_curve_flag(p->ctx, 2, k))) return u / v->run->ub;
     }
-    return 0;
+    return upto;
 }
 
 /* the factor lines of batch b (ecm.c:1336-1367 for stage 1, 1485-1522 for stage 2): stdout and ecm_results.txt text.
- * b1_label: the number printed as "B1 = " / "B2 = ". */
-static void factor_lines(pass_t *ps, int stage, size_t b, uint64_t label, text_t *res, text_t *out)
+ * label: the number printed as "B1 = " / "B2 = ". */
+static void factor_lines(const view_t *v, int stage, size_t b, uint64_t label, text_t *res, text_t *out)
 {
-    const run_t *R = ps->run;
+    const run_t *R = v->run;
     static __thread char fac[4096];
     for (size_t l = 0; l < (size_t)VECLEN * (size_t)R->threads; l++) {
-        int g; size_t k;
-        locate(ps, b, l, &g, &k);
-        if (!gecm_curve_flag(ps->jobs[g].ctx, stage, k)) continue;
+        size_t k;
+        const part_t *p = locate(v, line_curve(R, b, l), &k);
+        if (!gecm_curve_flag(p->ctx, stage, k)) continue;
         int prp = 0;
-        int r = stage == 1 ? gecm_stage1_factor(ps->jobs[g].ctx, k, fac, sizeof fac, &prp)
-                           : gecm_stage2_factor(ps->jobs[g].ctx, k, fac, sizeof fac, &prp);
+        int r = stage == 1 ? gecm_stage1_factor(p->ctx, k, fac, sizeof fac, &prp)
+                           : gecm_stage2_factor(p->ctx, k, fac, sizeof fac, &prp);
         if (r != 1) continue;
         const size_t j = l / VECLEN, i = l % VECLEN;
-        const size_t curve = (size_t)R->threads * VECLEN * (ps->b0 + b) + l;       /* threads*curve + j*VECLEN + i */
-        const unsigned long sg = (unsigned long)ps->jobs[g].sigma[k];
+        const size_t curve = (size_t)R->threads * VECLEN * (v->b0 + b) + l;        /* threads*curve + j*VECLEN + i */
+        const unsigned long sg = (unsigned long)p->sigma[k];
         text_printf(out, "\nfound %s%d factor %s in stage %d (B%d = %lu): thread %zu, vec %zu, sigma %lu\n", prp ? "PRP" : "C",
                     gecm_sizeinbase10(fac), fac, stage, stage, (unsigned long)label, j, i, sg);
         text_printf(res, "\nfound %s%d factor %s in stage %d (B%d = %lu): curve %zu, thread %zu, vec %zu, sigma %lu\n",
@@ -362,10 +374,10 @@ static void factor_lines(pass_t *ps, int stage, size_t b, uint64_t label, text_t
     }
 }
 
-/* resume lines of the pass's distinct curves, formatted by worker threads (gecm_format_resume_line only reads the
+/* resume lines of the view's distinct curves, formatted by worker threads (gecm_format_resume_line only reads the
  * downloaded x, z) */
 typedef struct {
-    pass_t *ps;
+    const view_t *v;
     uint64_t b1_field;
     size_t lo, hi;
     char **lines;
@@ -375,28 +387,26 @@ static void *fmt_run(void *arg)
 {
     fmt_job *f = (fmt_job *)arg;
     static __thread char line[16384];
-    const run_t *R = f->ps->run;
     for (size_t u = f->lo; u < f->hi; u++) {
-        int g = 0;
-        while (g + 1 < R->gpus && u >= f->ps->jobs[g].first + f->ps->jobs[g].ncurves) g++;
-        int n = gecm_format_resume_line(f->ps->jobs[g].ctx, u - f->ps->jobs[g].first + f->ps->jobs[g].koff, f->b1_field, line,
-                                        sizeof line);
+        size_t k;
+        const part_t *p = locate(f->v, u, &k);
+        int n = gecm_format_resume_line(p->ctx, k, f->b1_field, line, sizeof line);
         f->lines[u] = n > 0 ? strdup(line) : NULL;
     }
     return NULL;
 }
 
-static char **format_lines(pass_t *ps, uint64_t b1_field, size_t upto)
+static char **format_lines(const view_t *v, uint64_t b1_field, size_t upto)
 {
-    char **lines = (char **)calloc(ps->ucurves ? ps->ucurves : 1, sizeof(char *));
-    if (!lines) return NULL;
+    char **lines = (char **)calloc(v->ucurves ? v->ucurves : 1, sizeof(char *));
+    if (!lines) { fprintf(stderr, "out of memory\n"); return NULL; }
     long ncpu = sysconf(_SC_NPROCESSORS_ONLN);
     int nt = ncpu > 16 ? 16 : ncpu < 1 ? 1 : (int)ncpu;
     if ((size_t)nt > upto / 512 + 1) nt = (int)(upto / 512 + 1);
     fmt_job fj[16];
     pthread_t th[16];
     for (int t = 0; t < nt; t++) {
-        fj[t].ps = ps; fj[t].b1_field = b1_field; fj[t].lines = lines;
+        fj[t].v = v; fj[t].b1_field = b1_field; fj[t].lines = lines;
         fj[t].lo = upto * (size_t)t / (size_t)nt;
         fj[t].hi = upto * (size_t)(t + 1) / (size_t)nt;
     }
@@ -408,13 +418,12 @@ static char **format_lines(pass_t *ps, uint64_t b1_field, size_t upto)
     return lines;
 }
 
-/* batches 0 .. nbatches of `lines` to f in the reference's order: per batch, thread by thread, lane by lane */
-static void write_batches(const pass_t *ps, FILE *f, char **lines, size_t b_from, size_t b_to)
+/* batches b_from .. b_to of `lines` to f in the reference's order: per batch, thread by thread, lane by lane */
+static void write_batches(const view_t *v, FILE *f, char **lines, size_t b_from, size_t b_to)
 {
-    const run_t *R = ps->run;
     for (size_t b = b_from; b < b_to; b++)
-        for (size_t l = 0; l < (size_t)VECLEN * (size_t)R->threads; l++) {
-            const size_t u = b * R->ub + (R->fixed_sigma ? l % VECLEN : l);
+        for (size_t l = 0; l < (size_t)VECLEN * (size_t)v->run->threads; l++) {
+            const size_t u = line_curve(v->run, b, l);
             if (lines[u]) fputs(lines[u], f);
         }
 }
@@ -426,63 +435,158 @@ static void free_lines(char **lines, size_t n)
     free(lines);
 }
 
-/* ---- one pass --------------------------------------------------------------------------------- */
-static void pass_fail(pass_t *ps)
+/* ---- what a view writes ------------------------------------------------------------------------
+ * What the reference would have written for these batches, one after the other: the first batch in which anything
+ * was found — at a checkpoint, after stage 1 or after stage 2 — is the last one written. */
+typedef struct {
+    size_t bstar, nwrite;      /* the first batch with a factor (nb: none); batches to write */
+    int found;
+    char **lines;
+    text_t res, out1, out2;    /* ecm_results.txt lines; stdout lines after stage 1 / after stage 2 */
+} output_t;
+
+/* Known from the device scans alone, so a pass settles it before the GPUs go on: a pass behind a factor is not even
+ * started. */
+static void output_settle(const view_t *v, output_t *o)
 {
-    run_t *R = ps->run;
+    memset(o, 0, sizeof *o);
+    o->bstar = v->nb;
+    for (int c = 0; c < v->nck; c++)
+        if (v->ck[c].first_flagged < o->bstar) o->bstar = v->ck[c].first_flagged;
+    o->bstar = first_flagged(v, o->bstar, v->run->do_stage2 ? 2 : 1);
+    o->found = o->bstar < v->nb;
+    o->nwrite = o->found ? o->bstar + 1 : v->nb;
+}
+
+/* host work, off the GPU: the resume lines and the factor text; 0, or -1 without memory */
+static int output_format(const view_t *v, output_t *o)
+{
+    const run_t *R = v->run;
+    o->lines = format_lines(v, R->B1, o->nwrite * R->ub);
+    if (!o->lines) return -1;
+    if (o->found) {
+        for (int c = 0; c < v->nck; c++)
+            if (v->ck[c].first_flagged == o->bstar && v->ck[c].res.len) text_add(&o->res, v->ck[c].res.buf, v->ck[c].res.len);
+        factor_lines(v, 1, o->bstar, R->B1, &o->res, &o->out1);
+        if (R->do_stage2) factor_lines(v, 2, o->bstar, R->B2, &o->res, &o->out2);
+    }
+    return 0;
+}
+
+/* files and stdout; log, s2log: what else the view has to say before and after save_b1.txt (or NULL) */
+static void output_write(const view_t *v, const output_t *o, const char *log, const char *s2log)
+{
+    if (log) fputs(log, stdout);
+    if (o->out1.len) fputs(o->out1.buf, stdout);
+    FILE *save = fopen("save_b1.txt", "a");
+    if (save) { write_batches(v, save, o->lines, 0, o->nwrite); fclose(save); }
+    else printf("could not open save_b1.txt for appending, Stage 1 data will not be saved\n");
+    if (s2log) fputs(s2log, stdout);
+    if (o->out2.len) fputs(o->out2.buf, stdout);
+    if (o->res.len) {
+        FILE *f = fopen("ecm_results.txt", "a");
+        if (f) { fputs(o->res.buf, f); fclose(f); }
+    }
+    /* checkpoint.txt of a pass of several batches: the reference has them batch by batch (all ranges of batch
+     * 0, then batch 1, ...) and nothing after the batch that found a factor */
+    if (v->nck && (v->nb > 1 || o->found)) {
+        FILE *cf = fopen("checkpoint.txt", "r+");
+        if (cf) {
+            if (ftruncate(fileno(cf), v->ck_offset) == 0) {
+                fseek(cf, 0, SEEK_END);
+                for (size_t b = 0; b < o->nwrite; b++)
+                    for (int c = 0; c < v->nck; c++) write_batches(v, cf, v->ck[c].lines, b, b + 1);
+            }
+            fclose(cf);
+        }
+    }
+    fflush(stdout);
+}
+
+static void output_release(const view_t *v, output_t *o)
+{
+    free_lines(o->lines, v->ucurves);
+    free(o->res.buf); free(o->out1.buf); free(o->out2.buf);
+}
+
+/* ---- the order of the passes --------------------------------------------------------------------
+ * Every pass — run, skipped or failed — waits for its turn on the GPUs and then on the output and leaves each exactly
+ * once, in that order: the counters only go up, so a failed run cannot leave a pass waiting. */
+
+/* wait until it is pass i's turn on x (or the run failed); nonzero when the pass is not to take it: an earlier pass
+ * found a factor, or the run failed */
+static int turn_wait(run_t *R, int x, size_t i)
+{
     pthread_mutex_lock(&R->mu);
-    R->failed = 1;
-    if (R->gpu_turn <= ps->index) R->gpu_turn = ps->index + 1;
-    if (R->out_turn <= ps->index) R->out_turn = ps->index + 1;
+    while (R->turn[x] != i && !R->failed) pthread_cond_wait(&R->cv, &R->mu);
+    const int stop = R->found_pass < i || R->failed;
+    pthread_mutex_unlock(&R->mu);
+    return stop;
+}
+
+/* pass i is done with x, and how: FOUND a factor, FAILED, or just DONE */
+static void turn_done(run_t *R, int x, size_t i, int how)
+{
+    pthread_mutex_lock(&R->mu);
+    if (how == FOUND && R->found_pass > i) R->found_pass = i;
+    if (how == FAILED) R->failed = 1;
+    if (R->turn[x] <= i) R->turn[x] = i + 1;
     pthread_cond_broadcast(&R->cv);
     pthread_mutex_unlock(&R->mu);
 }
 
-static void *pass_run(void *arg)
+static void pass_fail(pass_t *ps)
 {
-    pass_t *ps = (pass_t *)arg;
+    turn_done(ps->run, GPU, ps->index, FAILED);
+    turn_done(ps->run, OUT, ps->index, FAILED);
+}
+
+/* ---- one pass --------------------------------------------------------------------------------- */
+
+/* ecm.c:1236-1312: the batch goes to checkpoint.txt with the last prime in the B1 field; factors are looked for and
+ * reported as after stage 1 proper.  Written now (a checkpoint is for the crash that may follow), all batches of the
+ * pass; put into the reference's order when the pass is over. */
+static int pass_checkpoint(pass_t *ps, uint64_t last_prime)
+{
+    view_t *v = &ps->v;
+    ck_t *ck = &v->ck[v->nck];
+    memset(ck, 0, sizeof *ck);
+    ck->lines = format_lines(v, last_prime, v->ucurves);
+    if (!ck->lines) return -1;
+    ck->first_flagged = first_flagged(v, v->nb, 1);
+    if (ck->first_flagged < v->nb) {
+        text_t out = {0, 0, 0};
+        factor_lines(v, 1, ck->first_flagged, last_prime, &ck->res, &out);
+        if (out.len) plog(ps, "%s", out.buf);
+        free(out.buf);
+    }
+    FILE *cf = fopen("checkpoint.txt", "a");
+    if (cf) {
+        plog(ps, "Saving checkpoint after p=%lu\n", (unsigned long)last_prime);                    /* ecm.c:1244 */
+        if (v->nck == 0) { fseek(cf, 0, SEEK_END); v->ck_offset = ftell(cf); }
+        write_batches(v, cf, ck->lines, 0, v->nb);
+        fclose(cf);
+    } else
+        plog(ps, "could not open checkpoint.txt for appending, Stage 1 data will not be saved\n");
+    v->nck++;
+    return 0;
+}
+
+/* stage 1 of the pass's batches, prime range by prime range (ecm.c:1209-1312); 0, or -1 after an error */
+static int pass_stage1(pass_t *ps)
+{
     run_t *R = ps->run;
     const int G = R->gpus;
-    const size_t lines_per_batch = (size_t)VECLEN * (size_t)R->threads;
-    double t;
-
-    /* host: the curves (ecm.c:1177-1204) */
-    t = now();
-    if (run_all(ps->jobs, G, job_build, NULL, 0)) { pass_fail(ps); return NULL; }
-    ps->t_build = now() - t;
-
-    /* the GPUs, in pass order */
-    pthread_mutex_lock(&R->mu);
-    while (R->gpu_turn != ps->index && !R->failed) pthread_cond_wait(&R->cv, &R->mu);
-    const int stop = R->found_pass < ps->index || R->failed;
-    pthread_mutex_unlock(&R->mu);
-    if (stop) {                                   /* an earlier pass found a factor: this one is not run at all */
-        pthread_mutex_lock(&R->mu);
-        R->gpu_turn = ps->index + 1;
-        pthread_cond_broadcast(&R->cv);
-        while (R->out_turn != ps->index && !R->failed) pthread_cond_wait(&R->cv, &R->mu);
-        R->out_turn = ps->index + 1;
-        pthread_cond_broadcast(&R->cv);
-        pthread_mutex_unlock(&R->mu);
-        return NULL;
-    }
-    plog(ps, "\nCommencing curves %zu-%zu of %zu\n", lines_per_batch * ps->b0, lines_per_batch * (ps->b0 + ps->nb) - 1,
-         (size_t)R->threads * R->per_thread);                                                      /* ecm.c:1201 */
-    plog(ps, "Building curves took %1.4f seconds.\n", ps->t_build);                                /* ecm.c:1204 */
-    t = now();
+    const double t = now();
     gecm_stage1_stats st;
     memset(&st, 0, sizeof st);
-    pthread_mutex_lock(&R->mu);
-    if (R->rd_pending) { pthread_join(R->rd_thread, NULL); R->rd_pending = 0; }
-    pthread_mutex_unlock(&R->mu);
-    if (R->rd_rc) { fprintf(stderr, "%s\n", gecm_last_error()); pass_fail(ps); return NULL; }
-    for (int r = 0; r < R->nranges; r++) {                                                         /* ecm.c:1209-1312 */
-        const gecm_stage1_range_desc rd = R->rd[r];
+    for (int r = 0; r < R->nranges; r++) {
+        const gecm_stage1_range_desc *rd = &R->rd[r];
         /* the reference sieves range 0 once before its first batch (ecm.c:1139-1146) and again whenever a batch
          * starts after a later range was loaded (ecm.c:1160-1173) */
         if (r > 0 || R->nranges > 1)
-            plog(ps, "Found %lu primes in range [%lu : %lu]\n", (unsigned long)rd.nprimes, (unsigned long)rd.lo, (unsigned long)rd.hi);   /* ecm.c:1228 */
-        plog(ps, "Commencing Stage 1 @ prime %lu\n", (unsigned long)rd.first_prime);               /* ecm.c:1233 */
+            plog(ps, "Found %lu primes in range [%lu : %lu]\n", (unsigned long)rd->nprimes, (unsigned long)rd->lo, (unsigned long)rd->hi);   /* ecm.c:1228 */
+        plog(ps, "Commencing Stage 1 @ prime %lu\n", (unsigned long)rd->first_prime);              /* ecm.c:1233 */
         for (int g = 0; g < G; g++) { ps->jobs[g].B1 = R->B1; ps->jobs[g].range = (uint32_t)r; ps->jobs[g].progress = ps->live && g == 0; }
         int make_map = 0;
         first_range_t *fr = NULL;
@@ -492,158 +596,153 @@ static void *pass_run(void *arg)
             if (!fr->claimed) { fr->claimed = 1; make_map = 1; }
             pthread_mutex_unlock(&fr->mu);
         }
-        if (run_all(ps->jobs, G, job_stage1, fr, make_map)) { pass_fail(ps); return NULL; }
-        gecm_get_stage1_stats(ps->jobs[0].ctx, &st);
+        if (run_all(ps->jobs, G, step_stage1, fr, make_map)) return -1;
+        gecm_get_stage1_stats(ps->v.part[0].ctx, &st);
         plog(ps, "\nStage 1 completed at prime %lu with %lu point-adds and %lu point-doubles\n",
              (unsigned long)st.last_prime, (unsigned long)st.ptadds, (unsigned long)st.ptdups);     /* ecm.c:1849 */
-        if (rd.checkpoint) {
-            /* ecm.c:1236-1312: the batch goes to checkpoint.txt with the last prime in the B1 field; factors are
-             * looked for and reported as after stage 1 proper.  Written now (a checkpoint is for the crash that
-             * may follow), all batches of the pass; put into the reference's order when the pass is over. */
-            struct ck_t *ck = &ps->ck[ps->nck];
-            memset(ck, 0, sizeof *ck);
-            ck->last_prime = rd.last_prime;
-            ck->lines = format_lines(ps, rd.last_prime, ps->ucurves);
-            ck->first_flagged = ps->nb;
-            for (size_t b = 0; b < ps->nb; b++)
-                if (batch_flagged(ps, 1, b)) { ck->first_flagged = b; break; }
-            if (ck->first_flagged < ps->nb) {
-                factor_lines(ps, 1, ck->first_flagged, rd.last_prime, &ck->res, &ck->out);
-                if (ck->out.len) plog(ps, "%s", ck->out.buf);
-            }
-            FILE *cf = fopen("checkpoint.txt", "a");
-            if (cf) {
-                plog(ps, "Saving checkpoint after p=%lu\n", (unsigned long)rd.last_prime);         /* ecm.c:1244 */
-                if (ps->nck == 0) { fseek(cf, 0, SEEK_END); ps->ck_offset = ftell(cf); }
-                if (ck->lines) write_batches(ps, cf, ck->lines, 0, ps->nb);
-                fclose(cf);
-            } else
-                plog(ps, "could not open checkpoint.txt for appending, Stage 1 data will not be saved\n");
-            ps->nck++;
-        }
+        if (rd->checkpoint && pass_checkpoint(ps, rd->last_prime)) return -1;
     }
-    ps->t_stage1 = now() - t;
-    plog(ps, "Stage 1 took %1.4f seconds\n", ps->t_stage1);                                         /* ecm.c:1317 */
-    plog(ps, "(%.1f curves/sec; kernel %.1f ms on GPU 0)\n", (double)ps->ucurves / ps->t_stage1, ps->jobs[0].kernel_ms);
+    const double t_stage1 = now() - t;
+    plog(ps, "Stage 1 took %1.4f seconds\n", t_stage1);                                             /* ecm.c:1317 */
+    plog(ps, "(%.1f curves/sec; kernel %.1f ms on GPU 0)\n", (double)ps->v.ucurves / t_stage1, ps->jobs[0].kernel_ms);
+    return 0;
+}
 
+/* stage 2 (ecm.c:1394-1528); what it prints goes to s2log, which comes after save_b1.txt; 0, or -1 after an error */
+static int pass_stage2(pass_t *ps, text_t *s2log)
+{
+    run_t *R = ps->run;
+    const int G = R->gpus;
+    gecm_ctx *ctx0 = ps->v.part[0].ctx;
     gecm_stage2_stats s2;
     memset(&s2, 0, sizeof s2);
+    const double t = now();
+    if (run_all(ps->jobs, G, step_stage2_init, NULL, 0)) return -1;                                /* ecm.c:1401-1421 */
+    text_printf(s2log, "Stage 2 Init took %1.4f seconds\n", now() - t);                            /* ecm.c:1421 */
+    gecm_get_stage2_stats(ctx0, &s2);
+    uint32_t rcount = 0;
+    for (uint32_t i = 0; i < 2 * s2.D; i++) {                                                      /* main.c:874-882: R - 3 */
+        uint32_t a = i, b = 2 * s2.D;
+        while (b) { uint32_t rr = a % b; a = b; b = rr; }
+        rcount += a == 1;
+    }
+    const first_range_t *fr = &R->fr;
+    for (uint64_t p = R->B1; p < R->B2; p += PRIME_RANGE) {                                        /* ecm.c:1424-1476 */
+        const uint64_t hi = p + PRIME_RANGE < R->B2 ? p + PRIME_RANGE : R->B2;
+        gecm_pairs pm;
+        const int shared = fr->valid && p == fr->lo && hi == fr->hi && s2.D == fr->D && s2.U == fr->U;
+        text_printf(s2log, "commencing pair on range %lu:%lu\n", (unsigned long)p, (unsigned long)hi);       /* ecm.c:2568 */
+        if (shared) pm = fr->pm;
+        else if (gecm_pair_primes(&pm, p, hi, s2.D, s2.U)) { fprintf(stderr, "%s\n", gecm_last_error()); return -1; }
+        text_printf(s2log, "%u pairs found from %u primes (ratio = %1.2f)\n", pm.pairs, pm.primes,
+                    pm.primes ? (double)pm.pairs / (double)pm.primes : 0.0);                       /* ecm.c:2904-2905 */
+        text_printf(s2log, "\ncommencing stage 2 at A=%lu\nw = %u, R = %u, L = %u, U = %d, umax = %u, amin = %u\n",
+                    2ul * (unsigned long)pm.amin * s2.D, s2.D, rcount, s2.L, (int)s2.U, s2.U * s2.D, pm.amin);   /* ecm.c:2440-2442 */
+        for (int g = 0; g < G; g++) ps->jobs[g].pm = &pm;
+        const int rc = run_all(ps->jobs, G, step_stage2_pair, NULL, 0);
+        if (!shared) gecm_pairmap_release(&pm);
+        if (rc) return -1;
+        gecm_get_stage2_stats(ctx0, &s2);
+        text_printf(s2log, "\nlast amin: %u\n", s2.amin_last);                                     /* ecm.c:1462 */
+    }
+    if (run_all(ps->jobs, G, step_stage2_scan, NULL, 0)) return -1;
+    text_printf(s2log, "\nStage 2 took %1.4f seconds\n", now() - t);                               /* ecm.c:1481 */
+    text_printf(s2log, "performed %lu pt-adds, %lu inversions, and %lu pair-muls in stage 2\n",
+                (unsigned long)s2.ptadds, (unsigned long)s2.numinv, (unsigned long)s2.paired);     /* ecm.c:1482 */
+    return 0;
+}
+
+static void *pass_run(void *arg)
+{
+    pass_t *ps = (pass_t *)arg;
+    run_t *R = ps->run;
+    const view_t *v = &ps->v;
+    const size_t i = ps->index, lines_per_batch = (size_t)VECLEN * (size_t)R->threads;
     text_t s2log = {0, 0, 0};
-    if (R->do_stage2) {                                                                            /* ecm.c:1394-1528 */
-        t = now();
-        if (run_all(ps->jobs, G, job_stage2_init, NULL, 0)) { pass_fail(ps); return NULL; }        /* ecm.c:1401-1421 */
-        ps->t_s2init = now() - t;
-        text_printf(&s2log, "Stage 2 Init took %1.4f seconds\n", ps->t_s2init);                    /* ecm.c:1421 */
-        gecm_get_stage2_stats(ps->jobs[0].ctx, &s2);
-        uint32_t rcount = 0;
-        for (uint32_t i = 0; i < 2 * s2.D; i++) {                                                  /* main.c:874-882: R - 3 */
-            uint32_t a = i, b = 2 * s2.D;
-            while (b) { uint32_t rr = a % b; a = b; b = rr; }
-            rcount += a == 1;
-        }
-        first_range_t *fr = &R->fr;
-        for (uint64_t p = R->B1; p < R->B2; p += PRIME_RANGE) {                                    /* ecm.c:1424-1476 */
-            const uint64_t hi = p + PRIME_RANGE < R->B2 ? p + PRIME_RANGE : R->B2;
-            gecm_pairs pm;
-            const int shared = fr->valid && p == fr->lo && hi == fr->hi && s2.D == fr->D && s2.U == fr->U;
-            text_printf(&s2log, "commencing pair on range %lu:%lu\n", (unsigned long)p, (unsigned long)hi);   /* ecm.c:2568 */
-            if (shared) pm = fr->pm;
-            else if (gecm_pair_primes(&pm, p, hi, s2.D, s2.U)) { fprintf(stderr, "%s\n", gecm_last_error()); pass_fail(ps); return NULL; }
-            text_printf(&s2log, "%u pairs found from %u primes (ratio = %1.2f)\n", pm.pairs, pm.primes,
-                        pm.primes ? (double)pm.pairs / (double)pm.primes : 0.0);                   /* ecm.c:2904-2905 */
-            text_printf(&s2log, "\ncommencing stage 2 at A=%lu\nw = %u, R = %u, L = %u, U = %d, umax = %u, amin = %u\n",
-                        2ul * (unsigned long)pm.amin * s2.D, s2.D, rcount, s2.L, (int)s2.U, s2.U * s2.D, pm.amin);   /* ecm.c:2440-2442 */
-            for (int g = 0; g < G; g++) ps->jobs[g].pm = &pm;
-            if (run_all(ps->jobs, G, job_stage2_pair, NULL, 0)) { pass_fail(ps); return NULL; }
-            if (!shared) gecm_pairmap_release(&pm);
-            gecm_get_stage2_stats(ps->jobs[0].ctx, &s2);
-            text_printf(&s2log, "\nlast amin: %u\n", s2.amin_last);                                /* ecm.c:1462 */
-        }
-        if (run_all(ps->jobs, G, job_stage2_scan, NULL, 0)) { pass_fail(ps); return NULL; }
-        ps->t_s2 = now() - t;
-        text_printf(&s2log, "\nStage 2 took %1.4f seconds\n", ps->t_s2);                           /* ecm.c:1481 */
-        text_printf(&s2log, "performed %lu pt-adds, %lu inversions, and %lu pair-muls in stage 2\n",
-                    (unsigned long)s2.ptadds, (unsigned long)s2.numinv, (unsigned long)s2.paired); /* ecm.c:1482 */
-    }
-    /* What the reference would have written for these batches, one after the other: the first batch in which anything
-     * was found — at a checkpoint, after stage 1 or after stage 2 — is the last one written.  Known from the device
-     * scans alone, so it is settled before the GPUs go on: a pass behind a factor is not even started. */
-    size_t bstar = ps->nb;
-    for (int c = 0; c < ps->nck; c++)
-        if (ps->ck[c].first_flagged < bstar) bstar = ps->ck[c].first_flagged;
-    for (size_t b = 0; b < bstar; b++)
-        if (batch_flagged(ps, 1, b) || (R->do_stage2 && batch_flagged(ps, 2, b))) { bstar = b; break; }
-    const int found = bstar < ps->nb;
-    /* the GPUs go to the next pass */
-    pthread_mutex_lock(&R->mu);
-    if (found && R->found_pass > ps->index) R->found_pass = ps->index;
-    R->gpu_turn = ps->index + 1;
-    pthread_cond_broadcast(&R->cv);
-    pthread_mutex_unlock(&R->mu);
+    output_t o = {0};
+    int failed = 1;
 
-    const size_t nwrite = found ? bstar + 1 : ps->nb;
-    char **lines = format_lines(ps, R->B1, nwrite * R->ub);
-    text_t res = {0, 0, 0}, out1 = {0, 0, 0}, out2 = {0, 0, 0};
-    if (found) {
-        for (int c = 0; c < ps->nck; c++)
-            if (ps->ck[c].first_flagged == bstar && ps->ck[c].res.len) text_add(&res, ps->ck[c].res.buf, ps->ck[c].res.len);
-        factor_lines(ps, 1, bstar, R->B1, &res, &out1);
-        if (R->do_stage2) factor_lines(ps, 2, bstar, R->B2, &res, &out2);
-    }
+    /* host: the curves (ecm.c:1177-1204) */
+    double t_build = now();
+    if (run_all(ps->jobs, R->gpus, step_build, NULL, 0)) goto out;
+    t_build = now() - t_build;
 
+    /* the GPUs, in pass order */
+    if (turn_wait(R, GPU, i)) {                   /* an earlier pass found a factor: this one is not run at all */
+        turn_done(R, GPU, i, DONE);
+        (void)turn_wait(R, OUT, i);
+        turn_done(R, OUT, i, DONE);
+        return NULL;
+    }
+    plog(ps, "\nCommencing curves %zu-%zu of %zu\n", lines_per_batch * v->b0, lines_per_batch * (v->b0 + v->nb) - 1,
+         (size_t)R->threads * R->per_thread);                                                      /* ecm.c:1201 */
+    plog(ps, "Building curves took %1.4f seconds.\n", t_build);                                    /* ecm.c:1204 */
+    if (pass_stage1(ps) || (R->do_stage2 && pass_stage2(ps, &s2log))) goto out;
+    output_settle(v, &o);
+    turn_done(R, GPU, i, o.found ? FOUND : DONE);   /* the GPUs go to the next pass */
+
+    if (output_format(v, &o)) goto out;
     /* files and stdout, in pass order */
-    pthread_mutex_lock(&R->mu);
-    while (R->out_turn != ps->index && !R->failed) pthread_cond_wait(&R->cv, &R->mu);
-    const int skip = R->found_pass < ps->index || R->failed;
-    pthread_mutex_unlock(&R->mu);
-    if (!skip) {
-        if (!ps->live && ps->log.len) fputs(ps->log.buf, stdout);
-        if (out1.len) fputs(out1.buf, stdout);
-        FILE *save = fopen("save_b1.txt", "a");
-        if (save) { write_batches(ps, save, lines, 0, nwrite); fclose(save); }
-        else printf("could not open save_b1.txt for appending, Stage 1 data will not be saved\n");
-        if (s2log.len) fputs(s2log.buf, stdout);
-        if (out2.len) fputs(out2.buf, stdout);
-        if (res.len) {
-            FILE *o = fopen("ecm_results.txt", "a");
-            if (o) { fputs(res.buf, o); fclose(o); }
-        }
-        /* checkpoint.txt of a pass of several batches: the reference has them batch by batch (all ranges of batch
-         * 0, then batch 1, ...) and nothing after the batch that found a factor */
-        if (ps->nck && (ps->nb > 1 || found)) {
-            FILE *cf = fopen("checkpoint.txt", "r+");
-            if (cf) {
-                if (ftruncate(fileno(cf), ps->ck_offset) == 0) {
-                    fseek(cf, 0, SEEK_END);
-                    for (size_t b = 0; b < nwrite; b++)
-                        for (int c = 0; c < ps->nck; c++)
-                            if (ps->ck[c].lines) write_batches(ps, cf, ps->ck[c].lines, b, b + 1);
-                }
-                fclose(cf);
-            }
-        }
-        fflush(stdout);
-    }
-    pthread_mutex_lock(&R->mu);
-    R->out_turn = ps->index + 1;
-    pthread_cond_broadcast(&R->cv);
-    pthread_mutex_unlock(&R->mu);
-    free_lines(lines, ps->ucurves);
-    free(res.buf); free(out1.buf); free(out2.buf); free(s2log.buf);
+    if (!turn_wait(R, OUT, i)) output_write(v, &o, ps->live ? NULL : ps->log.buf, s2log.buf);
+    turn_done(R, OUT, i, DONE);
+    failed = 0;
+out:
+    if (failed) pass_fail(ps);
+    output_release(v, &o);
+    free(s2log.buf);
     return NULL;
 }
 
-static void pass_release(pass_t *ps)
+/* wait for the pass of a slot, if there is one, and release what it holds */
+static void pass_join(pass_t *ps)
 {
-    for (int c = 0; c < ps->nck; c++) {
-        free_lines(ps->ck[c].lines, ps->ucurves);
-        free(ps->ck[c].res.buf);
-        free(ps->ck[c].out.buf);
+    if (!ps->run) return;
+    if (ps->threaded) pthread_join(ps->th, NULL);
+    for (int c = 0; c < ps->v.nck; c++) {
+        free_lines(ps->v.ck[c].lines, ps->v.ucurves);
+        free(ps->v.ck[c].res.buf);
     }
-    free(ps->ck);
+    free(ps->v.ck);
     free(ps->sigma);
     free(ps->log.buf);
     memset(ps, 0, sizeof *ps);
+}
+
+/* curves B1 [threads] [B2] [sigma], argv[0] being curves: the reference's rules for them, and what follows from them
+ * for the whole run (R->t_start is set already: the seed takes it); 0, or 1 after saying what is wrong */
+static int parse_run(run_t *R, int argc, char **argv)
+{
+    size_t numcurves = strtoul(argv[0], NULL, 10);
+    R->B1 = strtoull(argv[1], NULL, 10);
+    R->B2 = 100ULL * R->B1;                                                       /* main.c:462 */
+    R->threads = 1;
+    R->do_stage2 = 1;
+    if (argc > 2) R->threads = atoi(argv[2]);
+    if (argc > 3) R->B2 = strtoull(argv[3], NULL, 10);
+    if (argc > 4) R->sigma0 = strtoull(argv[4], NULL, 10);
+    if (R->B2 <= R->B1) { R->do_stage2 = 0; R->B2 = R->B1; }                      /* main.c:548-552 */
+    if (R->threads < 1) R->threads = 1;
+    R->fixed_sigma = R->sigma0 > 0;                                               /* main.c:754-770 */
+    if (numcurves == 0 || R->B1 < 2 || R->B1 > 1000000000000ULL) { printf("need curves >= 1 and 2 <= B1 <= 1e12\n"); return 1; }
+    /* main.c:585-589: at least one curve per thread, the same number on every thread; ecm.c:1151: every thread
+     * runs whole vectors of VECLEN curves, so "10 curves" on one thread writes 16 resume lines there and here */
+    if (numcurves < (size_t)R->threads) numcurves = (size_t)R->threads;
+    R->per_thread = numcurves / (size_t)R->threads + (numcurves % (size_t)R->threads != 0);
+    R->nbatches = (R->per_thread + VECLEN - 1) / VECLEN;
+    R->ub = R->fixed_sigma ? VECLEN : (size_t)VECLEN * (size_t)R->threads;
+    R->lcg = (uint64_t)(R->t_start * 1e6) * 0x9E3779B97F4A7C15ULL + (uint64_t)getpid();
+    return 0;
+}
+
+/* one context per GPU of a slot, on `modulus`, reporting against `report` if that is another number; 0 or 2 */
+static int make_contexts(gecm_ctx **ctx, int n, int devices, const char *modulus, const char *report)
+{
+    for (int g = 0; g < n; g++)
+        if (gecm_create(&ctx[g], g % devices, modulus, GECM_CLI_DIGITBITS) || (report && gecm_set_report_modulus(ctx[g], report))) {
+            fprintf(stderr, "%s\n", gecm_last_error());
+            return 2;
+        }
+    return 0;
 }
 
 /* one input, the reference's command line: avx-ecm input curves B1 [threads] [B2] [sigma] */
@@ -665,49 +764,31 @@ static int run_single(int argc, char **argv)
         printf("input must evaluate to an odd integer >= 3 (operators + - * / %% ^ ! # fib() luc())\n");
         return 1;
     }
-    size_t numcurves = strtoul(argv[2], NULL, 10);
-    R.B1 = strtoull(argv[3], NULL, 10);
-    R.B2 = 100ULL * R.B1;                                                         /* main.c:462 */
-    R.threads = 1;
-    R.do_stage2 = 1;
-    if (argc > 4) R.threads = atoi(argv[4]);
-    if (argc > 5) R.B2 = strtoull(argv[5], NULL, 10);
-    if (argc > 6) R.sigma0 = strtoull(argv[6], NULL, 10);
-    if (R.B2 <= R.B1) { R.do_stage2 = 0; R.B2 = R.B1; }                           /* main.c:548-552 */
-    if (R.threads < 1) R.threads = 1;
-    R.fixed_sigma = R.sigma0 > 0;                                                 /* main.c:754-770 */
-    int have = gecm_device_count();
-    if (have < 1) { fprintf(stderr, "no HIP device visible\n"); return 2; }
-    int gpus = have;
-    if (getenv("GECM_GPUS") && atoi(getenv("GECM_GPUS")) > 0 && atoi(getenv("GECM_GPUS")) < gpus) gpus = atoi(getenv("GECM_GPUS"));
+    if (parse_run(&R, argc - 2, argv + 2)) return 1;
+    int gpus = gecm_device_count();
+    if (gpus < 1) { fprintf(stderr, "no HIP device visible\n"); return 2; }
+    if (env_count("GECM_GPUS") && env_count("GECM_GPUS") < gpus) gpus = (int)env_count("GECM_GPUS");
     /* GECM_CONTEXTS_PER_GPU=k (rehearsal knob): k contexts, each with its host thread, on every device used — the
      * multi-context path of this driver on a box with one GPU.  Nothing is gained by it. */
-    int per_gpu = 1;
-    if (getenv("GECM_CONTEXTS_PER_GPU") && atoi(getenv("GECM_CONTEXTS_PER_GPU")) > 1) per_gpu = atoi(getenv("GECM_CONTEXTS_PER_GPU"));
+    const int per_gpu = env_count("GECM_CONTEXTS_PER_GPU") > 1 ? (int)env_count("GECM_CONTEXTS_PER_GPU") : 1;
     const int devices = gpus;
     gpus *= per_gpu;
     if (gpus > MAX_GPUS) gpus = MAX_GPUS;
     R.gpus = gpus;
-    if (numcurves == 0 || R.B1 < 2 || R.B1 > 1000000000000ULL) { printf("need curves >= 1 and 2 <= B1 <= 1e12\n"); return 1; }
     R.nranges = gecm_stage1_ranges(R.B1);
-    /* main.c:585-589: at least one curve per thread, the same number on every thread; ecm.c:1151: every thread
-     * runs whole vectors of VECLEN curves, so "10 curves" on one thread writes 16 resume lines there and here */
-    if (numcurves < (size_t)R.threads) numcurves = (size_t)R.threads;
-    R.per_thread = numcurves / (size_t)R.threads + (numcurves % (size_t)R.threads != 0);
-    R.nbatches = (R.per_thread + VECLEN - 1) / VECLEN;
-    R.ub = R.fixed_sigma ? VECLEN : (size_t)VECLEN * (size_t)R.threads;
 
     fputs(prep_log, stdout);          /* "gen: ...", "removing algebraic ...", "commencing parallel ecm on ..." */
     R.rd = (gecm_stage1_range_desc *)calloc((size_t)R.nranges, sizeof *R.rd);
     if (!R.rd) { fprintf(stderr, "out of memory\n"); return 2; }
-    R.rd_pending = pthread_create(&R.rd_thread, NULL, describe_ranges, &R) == 0;
-    if (!R.rd_pending) describe_ranges(&R);
+    pthread_t rd_thread;
+    const int rd_pending = pthread_create(&rd_thread, NULL, describe_ranges, &R) == 0;
+    if (!rd_pending) describe_ranges(&R);
     /* Special-form inputs for which the reference leaves REDC (main.c:505-527, 642-684): it then works modulo
      * Mw = 2^k - 1, 2^k + 1 or 2^k - c throughout, curve construction included, and keeps the number given for the "N="
      * of its files and for its factor checks (ecm.c:1111-1118).  Same here: the contexts are made on Mw and report
      * against N (gecm_set_report_modulus); the files come out as the reference's, byte for byte. */
     static char mwdec[MPL_MAXL * 10 + 16];
-    const char *modulus = ndec;
+    const char *modulus = ndec, *report = NULL;
     if (inf.ref_special_reduction) {
         mpl_t mw, t;
         mpl_set_u64(&mw, 1);
@@ -716,12 +797,10 @@ static int run_single(int argc, char **argv)
         else { mpl_set_u64(&t, inf.form > 1 ? (uint64_t)inf.c : 1); mpl_sub(&mw, &mw, &t); }
         mpl_get_dec(mwdec, &mw);
         modulus = mwdec;
+        report = ndec;
     }
     static gecm_ctx *ctx[2][MAX_GPUS];
-    for (int g = 0; g < gpus; g++) {
-        if (gecm_create(&ctx[0][g], g % devices, modulus, GECM_CLI_DIGITBITS)) { fprintf(stderr, "%s\n", gecm_last_error()); return 2; }
-        if (inf.ref_special_reduction && gecm_set_report_modulus(ctx[0][g], ndec)) { fprintf(stderr, "%s\n", gecm_last_error()); return 2; }
-    }
+    if (make_contexts(ctx[0], gpus, devices, modulus, report)) return 2;
     /* passes: as many reference batches as fit FULL_BATCH distinct curves per GPU — or what the device's memory takes
      * (the stage-2 table of 1024-bit curves is 1.1 MB per curve: 149 GB for a full batch).  GECM_PASS_CURVES (distinct
      * curves per pass over all GPUs) overrides it for tests. */
@@ -731,8 +810,7 @@ static int run_single(int argc, char **argv)
     size_t fit = FULL_BATCH;
     while (fit > 64 && mem_free && gecm_batch_bytes(ctx[0][0], fit, R.do_stage2, R.B1, 0, 0) > budget) fit = fit / 2 / 64 * 64;
     if (fit < 64) fit = 64;
-    size_t cap = fit * (size_t)gpus;
-    if (getenv("GECM_PASS_CURVES") && atol(getenv("GECM_PASS_CURVES")) > 0) cap = (size_t)atol(getenv("GECM_PASS_CURVES"));
+    const size_t cap = env_count("GECM_PASS_CURVES") ? (size_t)env_count("GECM_PASS_CURVES") : fit * (size_t)gpus;
     size_t batches_per_pass = cap / R.ub;
     if (batches_per_pass < 1) batches_per_pass = 1;
     const size_t npasses = (R.nbatches + batches_per_pass - 1) / batches_per_pass;
@@ -744,11 +822,7 @@ static int run_single(int argc, char **argv)
     /* (B1 in (99999989, 1e8] is one range WITH a checkpoint, ecm.c:1237: checkpoint.txt is appended to inside a pass's
      * turn on the GPU and put in order when the pass is written, which two passes in flight would do to each other) */
     const int slots = (npasses > 1 && R.nranges == 1 && R.B1 <= 99999989ULL && room && !getenv("GECM_NO_PIPELINE")) ? 2 : 1;
-    for (int s = 1; s < slots; s++)
-        for (int g = 0; g < gpus; g++) {
-            if (gecm_create(&ctx[s][g], g % devices, modulus, GECM_CLI_DIGITBITS)) { fprintf(stderr, "%s\n", gecm_last_error()); return 2; }
-            if (inf.ref_special_reduction && gecm_set_report_modulus(ctx[s][g], ndec)) { fprintf(stderr, "%s\n", gecm_last_error()); return 2; }
-        }
+    if (slots > 1 && make_contexts(ctx[1], gpus, devices, modulus, report)) return 2;
     gecm_config cfg;
     gecm_get_config(ctx[0][0], &cfg);
     char devname[256];
@@ -783,57 +857,49 @@ static int run_single(int argc, char **argv)
     R.fr.hi = R.B1 + PRIME_RANGE < R.B2 ? R.B1 + PRIME_RANGE : R.B2;
     R.fr.D = gecm_s2_default_D(R.B1);
     R.fr.U = GECM_S2_DEFAULT_U;
-    R.lcg = (uint64_t)(R.t_start * 1e6) * 0x9E3779B97F4A7C15ULL + (uint64_t)getpid();
     R.found_pass = (size_t)-1;
 
-    if (R.rd_pending) { pthread_join(R.rd_thread, NULL); R.rd_pending = 0; }
-    if (!R.rd_rc && R.nranges == 1)                                                /* ecm.c:1139-1146 */
+    if (rd_pending) pthread_join(rd_thread, NULL);
+    if (R.rd_rc) { fprintf(stderr, "%s\n", R.rd_err); return 2; }
+    if (R.nranges == 1)                                                            /* ecm.c:1139-1146 */
         printf("Found %lu primes in range [%lu : %lu]\n", (unsigned long)R.rd[0].nprimes, (unsigned long)R.rd[0].lo, (unsigned long)R.rd[0].hi);
     static pass_t pass[2];
-    int running[2] = {0, 0};
     for (size_t pi = 0; pi < npasses; pi++) {
         const int s = (int)(pi % (size_t)slots);
-        if (running[s]) { pthread_join(pass[s].th, NULL); pass_release(&pass[s]); running[s] = 0; }
+        pass_t *ps = &pass[s];
+        pass_join(ps);                            /* the pass before the last one, when there are two slots */
         pthread_mutex_lock(&R.mu);
         const int stop = R.found_pass != (size_t)-1 || R.failed;
         pthread_mutex_unlock(&R.mu);
         if (stop) break;
-        pass_t *ps = &pass[s];
-        memset(ps, 0, sizeof *ps);
+        view_t *v = &ps->v;
         ps->run = &R;
+        v->run = &R;
         ps->index = pi;
-        ps->slot = s;
         ps->live = slots == 1;
-        ps->b0 = pi * batches_per_pass;
-        ps->nb = R.nbatches - ps->b0 < batches_per_pass ? R.nbatches - ps->b0 : batches_per_pass;
-        ps->ucurves = ps->nb * R.ub;
-        ps->sigma = (uint64_t *)malloc(ps->ucurves * sizeof(uint64_t));
-        ps->ck = (struct ck_t *)calloc((size_t)R.nranges + 1, sizeof(struct ck_t));
-        if (!ps->sigma || !ps->ck) { fprintf(stderr, "out of memory\n"); return 2; }
-        for (size_t u = 0; u < ps->ucurves; u++) {
+        v->b0 = pi * batches_per_pass;
+        v->nb = R.nbatches - v->b0 < batches_per_pass ? R.nbatches - v->b0 : batches_per_pass;
+        v->ucurves = v->nb * R.ub;
+        ps->sigma = (uint64_t *)malloc(v->ucurves * sizeof(uint64_t));
+        v->ck = (ck_t *)calloc((size_t)R.nranges + 1, sizeof(ck_t));
+        if (!ps->sigma || !v->ck) { fprintf(stderr, "out of memory\n"); return 2; }
+        for (size_t u = 0; u < v->ucurves; u++) {
             /* fixed sigma: lane i of every thread of batch b runs sigma + 8 b + i (main.c:761, ecm.c:1187) */
-            if (R.fixed_sigma) ps->sigma[u] = R.sigma0 + VECLEN * ps->b0 + u;
+            if (R.fixed_sigma) ps->sigma[u] = R.sigma0 + VECLEN * v->b0 + u;
             else do { ps->sigma[u] = lcg_rand(&R.lcg); } while (ps->sigma[u] < 6);   /* ecm.c:1564-1570 */
         }
         /* host-side split: GPU g owns distinct curves [n*g/G, n*(g+1)/G) of this pass */
+        v->nparts = gpus;
         for (int g = 0; g < gpus; g++) {
-            const size_t lo = ps->ucurves * (size_t)g / (size_t)gpus, hi = ps->ucurves * (size_t)(g + 1) / (size_t)gpus;
+            const size_t lo = v->ucurves * (size_t)g / (size_t)gpus, hi = v->ucurves * (size_t)(g + 1) / (size_t)gpus;
+            v->part[g] = (part_t){ctx[s][g], ps->sigma + lo, hi - lo, lo, 0};
             ps->jobs[g].gpu = g;
-            ps->jobs[g].ctx = ctx[s][g];
-            ps->jobs[g].first = lo;
-            ps->jobs[g].ncurves = hi - lo;
-            ps->jobs[g].sigma = ps->sigma + lo;
+            ps->jobs[g].part = &v->part[g];
         }
-        if (pthread_create(&ps->th, NULL, pass_run, ps)) { pass_run(ps); pass_release(ps); }
-        else running[s] = 1;
+        ps->threaded = pthread_create(&ps->th, NULL, pass_run, ps) == 0;
+        if (!ps->threaded) pass_run(ps);
     }
-    for (size_t k = 0; k < 2; k++) {
-        /* in pass order: the older of the two first */
-        const int s = (int)((npasses + k) % 2);
-        if (s < slots && running[s]) { pthread_join(pass[s].th, NULL); pass_release(&pass[s]); running[s] = 0; }
-    }
-    for (int s = 0; s < 2; s++)
-        if (running[s]) { pthread_join(pass[s].th, NULL); pass_release(&pass[s]); }
+    for (int s = 0; s < 2; s++) pass_join(&pass[s]);
     if (R.fr.valid) gecm_pairmap_release(&R.fr.pm);
     for (int s = 0; s < slots; s++)
         for (int g = 0; g < gpus; g++) gecm_destroy(ctx[s][g]);
@@ -849,7 +915,6 @@ static int run_single(int argc, char **argv)
  * to FULL_BATCH curves on the first GPU; an input the reference works on modulo 2^k -/+ c, one that does not fit a
  * pass, and every input of a run with a checkpoint (B1 above 99999989) go through the one-input path, in their place. */
 typedef struct {
-    char *expr;
     char ndec[MPL_MAXL * 10 + 16];
     char log[65536];
 } input_t;
@@ -875,52 +940,23 @@ static int multi_pass(input_t **in, size_t n, run_t *R, size_t ucurves)
     if (rc == 0) rc = gecm_build_curves_multi(mc, sigma, which, n * ucurves) < 0;
     if (rc == 0) rc = gecm_stage1(mc, R->B1) || gecm_sync(mc) || gecm_scan_factors(mc, 1, NULL) < 0;
     if (rc == 0 && R->do_stage2) rc = gecm_stage2(mc, R->B2, 0, 0) || gecm_scan_factors(mc, 2, NULL) < 0;
-    if (rc) {
-        fprintf(stderr, "%s\n", gecm_last_error());
-        gecm_destroy(mc);
-        free(ns); free(sigma); free(which);
-        return 2;
-    }
+    if (rc) fprintf(stderr, "%s\n", gecm_last_error());
     /* every input as the one-input path writes it: a pass of all its batches on one context */
-    for (size_t i = 0; i < n; i++) {
-        static pass_t ps;
-        memset(&ps, 0, sizeof ps);
-        ps.run = R;
-        ps.nb = R->nbatches;
-        ps.ucurves = ucurves;
-        ps.jobs[0].ctx = mc;
-        ps.jobs[0].ncurves = ucurves;
-        ps.jobs[0].koff = i * ucurves;
-        ps.jobs[0].sigma = sigma;
-        fputs(in[i]->log, stdout);             /* "gen: ...", "commencing parallel ecm on ..." */
-        size_t bstar = ps.nb;
-        for (size_t b = 0; b < ps.nb; b++)
-            if (batch_flagged(&ps, 1, b) || (R->do_stage2 && batch_flagged(&ps, 2, b))) { bstar = b; break; }
-        const int found = bstar < ps.nb;
-        const size_t nwrite = found ? bstar + 1 : ps.nb;
-        char **lines = format_lines(&ps, R->B1, nwrite * R->ub);
-        text_t res = {0, 0, 0}, out = {0, 0, 0};
-        if (found) {
-            factor_lines(&ps, 1, bstar, R->B1, &res, &out);
-            if (R->do_stage2) factor_lines(&ps, 2, bstar, R->B2, &res, &out);
-        }
-        if (out.len) fputs(out.buf, stdout);
-        FILE *save = fopen("save_b1.txt", "a");
-        if (save && lines) { write_batches(&ps, save, lines, 0, nwrite); fclose(save); }
-        else printf("could not open save_b1.txt for appending, Stage 1 data will not be saved\n");
-        if (res.len) {
-            FILE *o = fopen("ecm_results.txt", "a");
-            if (o) { fputs(res.buf, o); fclose(o); }
-        }
-        fflush(stdout);
-        free_lines(lines, ucurves);
-        free(res.buf); free(out.buf);
+    for (size_t i = 0; i < n && !rc; i++) {
+        const view_t v = {.run = R, .nb = R->nbatches, .ucurves = ucurves, .nparts = 1,
+                          .part = {{mc, sigma, ucurves, 0, i * ucurves}}};
+        output_t o;
+        output_settle(&v, &o);
+        rc = output_format(&v, &o);
+        if (!rc) output_write(&v, &o, in[i]->log, NULL);   /* log: "gen: ...", "commencing parallel ecm on ..." */
+        output_release(&v, &o);
     }
-    printf("multi-modulus pass: %zu inputs, %zu curves each, stage 1%s, %1.4f seconds of kernels after stage 1\n", n,
-           ucurves, R->do_stage2 ? " and stage 2" : "", gecm_last_kernel_ms(mc) / 1000.0);
+    if (!rc)
+        printf("multi-modulus pass: %zu inputs, %zu curves each, stage 1%s, %1.4f seconds of kernels after stage 1\n", n,
+               ucurves, R->do_stage2 ? " and stage 2" : "", gecm_last_kernel_ms(mc) / 1000.0);
     gecm_destroy(mc);
     free(ns); free(sigma); free(which);
-    return 0;
+    return rc ? 2 : 0;
 }
 
 static int run_file(int argc, char **argv)
@@ -949,33 +985,14 @@ static int run_file(int argc, char **argv)
     fclose(f);
     if (!ninputs) { printf("%s holds no input\n%s", argv[2], usage); return 1; }
 
-    /* the run's parameters, as run_single reads them */
     static run_t R;
     memset(&R, 0, sizeof R);
     R.t_start = now();
-    size_t numcurves = strtoul(argv[3], NULL, 10);
-    R.B1 = strtoull(argv[4], NULL, 10);
-    R.B2 = 100ULL * R.B1;
-    R.threads = 1;
-    R.do_stage2 = 1;
-    if (argc > 5) R.threads = atoi(argv[5]);
-    if (argc > 6) R.B2 = strtoull(argv[6], NULL, 10);
-    if (argc > 7) R.sigma0 = strtoull(argv[7], NULL, 10);
-    if (R.B2 <= R.B1) { R.do_stage2 = 0; R.B2 = R.B1; }
-    if (R.threads < 1) R.threads = 1;
-    R.fixed_sigma = R.sigma0 > 0;
-    if (numcurves == 0 || R.B1 < 2 || R.B1 > 1000000000000ULL) { printf("need curves >= 1 and 2 <= B1 <= 1e12\n"); return 1; }
-    if (numcurves < (size_t)R.threads) numcurves = (size_t)R.threads;
-    R.per_thread = numcurves / (size_t)R.threads + (numcurves % (size_t)R.threads != 0);
-    R.nbatches = (R.per_thread + VECLEN - 1) / VECLEN;
-    R.ub = R.fixed_sigma ? VECLEN : (size_t)VECLEN * (size_t)R.threads;
-    R.gpus = 1;
-    R.lcg = (uint64_t)(R.t_start * 1e6) * 0x9E3779B97F4A7C15ULL + (uint64_t)getpid();
+    if (parse_run(&R, argc - 3, argv + 3)) return 1;
     const size_t ucurves = R.nbatches * R.ub, padded = (ucurves + 63) / 64 * 64;
     if (gecm_device_count() < 1) { fprintf(stderr, "no HIP device visible\n"); return 2; }
     printf("starting process %d: %zu inputs from %s\n", (int)getpid(), ninputs, argv[2]);
-    size_t cap = FULL_BATCH;
-    if (getenv("GECM_PASS_CURVES") && atol(getenv("GECM_PASS_CURVES")) > 0) cap = (size_t)atol(getenv("GECM_PASS_CURVES"));
+    const size_t cap = env_count("GECM_PASS_CURVES") ? (size_t)env_count("GECM_PASS_CURVES") : FULL_BATCH;
     const int multi_ok = R.B1 <= 99999989ULL && padded <= cap;    /* one prime range, no checkpoint; one input fits */
 
     /* the one-input path's argument list for input i: argv with "-f FILE" replaced by the input */
@@ -993,9 +1010,8 @@ static int run_file(int argc, char **argv)
         if (i < ninputs && multi_ok) {
             in = (input_t *)calloc(1, sizeof *in);
             if (!in) { fprintf(stderr, "out of memory\n"); return 2; }
-            in->expr = exprs[i];
             gecm_input_info inf;
-            alone = gecm_prepare_input(in->expr, GECM_CLI_DIGITBITS, in->ndec, sizeof in->ndec, &inf, in->log, sizeof in->log) ||
+            alone = gecm_prepare_input(exprs[i], GECM_CLI_DIGITBITS, in->ndec, sizeof in->ndec, &inf, in->log, sizeof in->log) ||
                     inf.ref_special_reduction;
         }
         /* the pending pass goes first when this input cannot join it */
