@@ -71,6 +71,10 @@ int gecm_dev_download_plain(gecm_dev *d, uint32_t *x, uint32_t *z);
  * ABI returns results in the reference's own Montgomery radix. */
 int gecm_dev_l0(gecm_dev *d, int op, const uint32_t *a, const uint32_t *b, uint32_t *c, uint32_t *dd,
                 size_t count, const uint32_t *fix);
+/* test-level inversion of `count` independent residues with the stage-2 inversion (fe_inv_mont; needs
+ * gecm_dev_set_s2const).  a canonical; inv = the inverse as fe_inv_mont returns it, multiplied by the constant `fix`
+ * (internal Montgomery form) and canonical, or 0 where gcd(a, N) != 1; g = gcd(a, N), a plain integer. */
+int gecm_dev_l0_inv(gecm_dev *d, const uint32_t *a, uint32_t *inv, uint32_t *g, size_t count, const uint32_t *fix);
 
 /* ---- multi-modulus batches ----
  * gecm_dev_set_multi: from now on every launch of this context takes its modulus per 64-curve block from the group

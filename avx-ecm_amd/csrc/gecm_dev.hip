@@ -562,6 +562,25 @@ extern "C" int gecm_dev_l0(gecm_dev *d, int op, const uint32_t *a, const uint32_
     return 0;
 }
 
+extern "C" int gecm_dev_l0_inv(gecm_dev *d, const uint32_t *a, uint32_t *inv, uint32_t *g, size_t count, const uint32_t *fix)
+{
+    HIPCHK(hipSetDevice(d->device));
+    if (d->multi || d->r3.empty() || !fix) {
+        g_err = "gecm_dev_l0_inv: needs a single-modulus context with its inversion constants (gecm_dev_set_s2const)";
+        return -2;
+    }
+    if (gecm_dev_resize(d, count)) return -1;
+    // as gecm_dev_l0: X<-a, outputs T0 (inverse), T1 (gcd); the padding lanes invert 0
+    if (upload_soa(d, d->dX, a)) return -1;
+    gecm_modconst mc = modconst(d);
+    d->k1->l0_inv(d->stream, &mc, d->dX, d->dT0, d->dT1, d->stride, fix);
+    HIPCHK(hipGetLastError());
+    if (download_soa(d, inv, d->dT0)) return -1;
+    if (download_soa(d, g, d->dT1)) return -1;
+    HIPCHK(hipStreamSynchronize(d->stream));
+    return 0;
+}
+
 // ---------------------------------------------------------------- multi-modulus batches
 extern "C" void gecm_dev_set_multi(gecm_dev *d) { d->multi = true; }
 

@@ -293,6 +293,26 @@ k_l0(int op, const uint32_t *__restrict__ A, const uint32_t *__restrict__ B, uin
     }
 }
 
+// The sixth test-level operator: the device inversion on chosen inputs, through the routine every stage-2 batch
+// inversion goes through (fe_inv_mont: fe_invert with the modulus's inv_iters, the R^3 step, the failure record).
+// A = x Rref canonical; fe_inv_mont reads it as (x Rref/Rint) Rint and gives x^-1 Rint^2/Rref, which `fix` =
+// Rref^2/Rint takes to x^-1 Rref; 0 where the inverse does not exist.  G = gcd(A, N) as a plain integer: 1, or the
+// failure record stage 2 would keep.  A kernel of its own so that k_l0 stays what it was.
+template <int NL>
+__global__ void __launch_bounds__(64, 2)
+k_l0_inv(const uint32_t *__restrict__ A, uint32_t *__restrict__ C, uint32_t *__restrict__ G, size_t stride, S2Const<NL> k,
+         Fe<NL> fix)
+{
+    uint32_t idx = blockIdx.x * 64u + threadIdx.x;
+    Fe<NL> x, t, r, g1;
+    fe_load(x, A, stride, idx);
+#pragma unroll
+    for (int i = 0; i < NL; i++) g1.v[i] = (i == 0) ? 1u : 0u;
+    fe_store(G, stride, idx, g1);
+    fe_inv_mont(t, x, k, G, stride, idx);
+    fe_canonical_mont(r, t, fix, k.m);
+    fe_store(C, stride, idx, r);
+}
 
 // ---------------------------------------------------------------- factor scan
 // check_factor (ecm.c:2542-2557) for every curve on the device: g = gcd(v, N) by the same
@@ -518,6 +538,15 @@ static void launch_l0(void *stream, const gecm_modconst *mc, int op, const uint3
                        D, stride, mod_args<ModArgs<GECM_NL>>(mc), f);
 }
 
+static void launch_l0_inv(void *stream, const gecm_modconst *mc, const uint32_t *A, uint32_t *C, uint32_t *G, size_t stride,
+                          const uint32_t *fix)
+{
+    Fe<GECM_NL> f;
+    for (int i = 0; i < GECM_NL; i++) f.v[i] = fix[i];
+    hipLaunchKernelGGL(k_l0_inv<GECM_NL>, dim3((unsigned)(stride / 64)), dim3(64), 0, (hipStream_t)stream, A, C, G, stride,
+                       s2_const(mc), f);
+}
+
 static void launch_gcd_scan(void *stream, const gecm_modconst *mc, const uint32_t *V, uint32_t *G, uint32_t *flags,
                             size_t stride)
 {
@@ -537,7 +566,7 @@ static void pack_group(const gecm_modconst *mc, void *out)
 
 extern "C" const gecm_kernels_p1 *CAT(CAT(gecm_kernels_, GECM_NL), _p1)(void)
 {
-    static const gecm_kernels_p1 t = {launch_stage1, launch_canon, launch_from_mont, launch_l0, launch_gcd_scan,
+    static const gecm_kernels_p1 t = {launch_stage1, launch_canon, launch_from_mont, launch_l0, launch_l0_inv, launch_gcd_scan,
                                       FPolicy<GECM_NL>::G, pack_group, sizeof(S2Const<GECM_NL>), GECM_MANIFEST};
     return &t;
 }

@@ -87,6 +87,9 @@ struct gecm_kernels_p1 {
                       uint32_t *oz, size_t stride);
     void (*l0)(void *stream, const gecm_modconst *mc, int op, const uint32_t *A, const uint32_t *B, uint32_t *C,
                uint32_t *D, size_t stride, const uint32_t *fix);
+    /* the test-level inversion (single modulus only): C = the inverse of A in the radix `fix` sets, or 0; G = gcd(A, N) */
+    void (*l0_inv)(void *stream, const gecm_modconst *mc, const uint32_t *A, uint32_t *C, uint32_t *G, size_t stride,
+                   const uint32_t *fix);
     void (*gcd_scan)(void *stream, const gecm_modconst *mc, const uint32_t *V, uint32_t *G, uint32_t *flags,
                      size_t stride);
     int fform_generic_limbs;      /* limbs of a 2^k -+ c modulus that are not 2^28 - 1 */

@@ -450,6 +450,41 @@ int gecm_vecaddsubmod(gecm_ctx *c, const void *a, const void *b, void *sum, void
     return (b && diff) ? l0_call(c, GECM_L0_ADDSUB, a, b, sum, diff, batch) : GECM_ERR_ARG;
 }
 
+/* The device inversion on chosen inputs: fe_inv_mont with this modulus's inv_iters, as every stage-2 batch inversion
+ * runs it.  Operands go to the device as they come, in the reference radix; finv28 brings the result back to it. */
+int gecm_vecinvmod(gecm_ctx *c, const void *a, void *inv, void *gcd, size_t batch)
+{
+    if (c && c->multi) return multi_refuse("the L0 operators");
+    if (!c || !a || !inv || !gcd || batch == 0) { set_err("L0: bad argument"); return GECM_ERR_ARG; }
+    if (!c->dev_l0 &&
+        gecm_dev_open(&c->dev_l0, c->device, c->mod.nl, c->mod.n28, c->mod.kp28, c->mod.one28, c->mod.rho28)) {
+        set_err("L0: %s", gecm_dev_error());
+        return GECM_ERR_DEVICE;
+    }
+    gecm_dev_set_s2const(c->dev_l0, c->mod.r3_28, c->mod.inv_iters);
+    int nl = c->mod.nl;
+    size_t words = (size_t)nl * batch;
+    uint32_t *ha = (uint32_t *)malloc(words * 4 * 3);
+    if (!ha) return GECM_ERR_NOMEM;
+    uint32_t *hi = ha + words, *hg = hi + words;
+    mpl_t v;
+    for (size_t i = 0; i < batch; i++) {
+        vec_get(&c->mod, &v, a, batch, i);
+        if (mpl_cmp(&v, &c->mod.N) >= 0) { free(ha); set_err("L0: operand a[%zu] not < N", i); return GECM_ERR_ARG; }
+        mpl_to_limbs32(ha + i, batch, nl, LIMB_BITS, &v);
+    }
+    int rc = gecm_dev_l0_inv(c->dev_l0, ha, hi, hg, batch, c->mod.finv28);
+    if (rc) { free(ha); set_err("L0: %s", gecm_dev_error()); return GECM_ERR_DEVICE; }
+    for (size_t i = 0; i < batch; i++) {
+        mpl_from_limbs32(&v, hi + i, batch, nl, LIMB_BITS);
+        vec_put(&c->mod, inv, batch, i, &v);
+        mpl_from_limbs32(&v, hg + i, batch, nl, LIMB_BITS);
+        vec_put(&c->mod, gcd, batch, i, &v);
+    }
+    free(ha);
+    return GECM_OK;
+}
+
 /* ---- phase 0 -------------------------------------------------------------------------------- */
 static int alloc_batch(gecm_ctx *c, size_t batch)
 {

@@ -83,12 +83,13 @@ int gecm_mod_setup(gecm_mod *m, const char *who, const char *n_str, int digitbit
     uint64_t nhat = mpl_get_u64(&t);
     m->rho_ref = digitbits == 52 ? (nhat & 0xfffffffffffffull) : (nhat & 0xffffffffull);
     m->rho28 = (uint32_t)(nhat & ((1u << LIMB_BITS) - 1));
-    m->n28 = (uint32_t *)calloc((size_t)nl * 5, sizeof(uint32_t));
+    m->n28 = (uint32_t *)calloc((size_t)nl * 6, sizeof(uint32_t));
     if (!m->n28) return GECM_ERR_NOMEM;
     m->kp28 = m->n28 + nl;
     m->one28 = m->kp28 + nl;
     m->fix28 = m->one28 + nl;
     m->r3_28 = m->fix28 + nl;
+    m->finv28 = m->r3_28 + nl;
     mpl_to_limbs32(m->n28, 1, nl, LIMB_BITS, &m->N);
     mpl_to_limbs32(m->one28, 1, nl, LIMB_BITS, &m->rint_mod_n);
     if (gecm_mod_make_kp(m->kp28, &m->N, nl)) { gecm_mod_free(m); return GECM_ERR_NOMEM; }
@@ -99,6 +100,10 @@ int gecm_mod_setup(gecm_mod *m, const char *who, const char *n_str, int digitbit
     mpl_mulmod(&t, &m->rint_mod_n, &m->rint_mod_n, &m->N);
     mpl_mulmod(&t, &t, &m->rint_mod_n, &m->N);
     mpl_to_limbs32(m->r3_28, 1, nl, LIMB_BITS, &t);
+    /* the device inverts x Rref, read as (x Rref/Rint) Rint, to x^-1 Rint^2/Rref: times Rref^2/Rint, Montgomery-wise, is
+     * x^-1 Rref */
+    mpl_mulmod(&t, &m->rref_mod_n, &m->int_to_ref, &m->N);
+    mpl_to_limbs32(m->finv28, 1, nl, LIMB_BITS, &t);
     /* batches of 28 division steps after which the device inversion has converged for a modulus of nbits bits:
      * the bound of the "half-delta" variant, floor((45907 bits + 26313) / 19929), +1, rounded up to whole batches */
     m->inv_iters = (uint32_t)((((45907ull * (unsigned)m->nbits + 26313ull) / 19929ull + 1) + 27) / 28);
@@ -107,7 +112,7 @@ int gecm_mod_setup(gecm_mod *m, const char *who, const char *n_str, int digitbit
 
 void gecm_mod_free(gecm_mod *m)
 {
-    free(m->n28);                          /* kp28 .. r3_28 are parts of it */
+    free(m->n28);                          /* kp28 .. finv28 are parts of it */
     m->n28 = NULL;
 }
 

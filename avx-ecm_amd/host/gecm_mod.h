@@ -20,6 +20,7 @@ typedef struct {
     uint32_t rho28;
     uint32_t *n28, *kp28, *one28, *fix28; /* fix28 = Rint^2/Rref mod N (see gecm_dev_l0) */
     uint32_t *r3_28;     /* Rint^3 mod N for the device inversion */
+    uint32_t *finv28;    /* Rref^2/Rint mod N (see gecm_vecinvmod) */
     uint32_t inv_iters;  /* batches of 28 division steps after which the device inversion has converged for N */
 } gecm_mod;
 

@@ -55,6 +55,8 @@ _sig("gecm_vecsqrmod", c_int, c_void_p, c_void_p, c_void_p, c_size_t)
 _sig("gecm_vecaddmod", c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t)
 _sig("gecm_vecsubmod", c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t)
 _sig("gecm_vecaddsubmod", c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t)
+_sig("gecm_vecinvmod", c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t)
+EXPORTS += ["gecm_vecinvmod"]
 _sig("gecm_build_curves", c_int, c_void_p, ctypes.POINTER(c_u64), c_size_t)
 _sig("gecm_upload_points", c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t)
 _sig("gecm_stage1", c_int, c_void_p, c_u64)
@@ -228,6 +230,14 @@ class Engine:
         s, d = self.empty(n), self.empty(n)
         _chk(lib.gecm_vecaddsubmod(self._h, self.pack(a), self.pack(b), s, d, n), "gecm_vecaddsubmod")
         return self.unpack(s, n), self.unpack(d, n)
+
+    def vecinvmod(self, a):
+        """(inv, gcd) of the device inversion: inv[i] = x^-1 R mod N for a[i] = x R mod N (0 where none exists),
+        gcd[i] = gcd(a[i], N)"""
+        n = len(a)
+        inv, g = self.empty(n), self.empty(n)
+        _chk(lib.gecm_vecinvmod(self._h, self.pack(a), inv, g, n), "gecm_vecinvmod")
+        return self.unpack(inv, n), self.unpack(g, n)
 
     # ---- L1 ----
     def build_curves(self, sigmas):

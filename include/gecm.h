@@ -71,7 +71,7 @@ uint64_t gecm_batch_bytes(const gecm_ctx *ctx, size_t curves, int with_stage2, u
 /* "one" = R mod N in the reference limb format, single value (monty->one, main.c:633-634) */
 int gecm_get_one(const gecm_ctx *ctx, void *one_limbs);
 
-/* ---- L0: the five vector operators (avx_ecm.h:205-209) -------------------------------------
+/* ---- L0: the five vector operators (avx_ecm.h:205-209), and the device inversion -----------
  * Test-level exports: same semantics as vecmulmod52/vecsqrmod52/vecaddmod52/vecsubmod52/
  * vec_simul_addsub52 (vecarith52.c:2438, 3317, 4550, 4684, 4877) and their 32-bit twins
  * (vecarith.c:221, 889, 2806, 2870, 2726): inputs canonical, outputs canonical, Montgomery
@@ -81,6 +81,12 @@ int gecm_vecsqrmod(gecm_ctx *ctx, const void *a, void *c, size_t batch);
 int gecm_vecaddmod(gecm_ctx *ctx, const void *a, const void *b, void *c, size_t batch);
 int gecm_vecsubmod(gecm_ctx *ctx, const void *a, const void *b, void *c, size_t batch);
 int gecm_vecaddsubmod(gecm_ctx *ctx, const void *a, const void *b, void *sum, void *diff, size_t batch);
+/* A sixth test-level operator with no counterpart among the reference's function pointers (it inverts on the host,
+ * mpz_invert, ecm.c:1919-1950): the device's own modular inversion, the routine every stage-2 batch inversion and the
+ * factor scan run, on inputs of the caller's choice.  a as above (canonical, a = x * 2^(DIGITBITS*NWORDS) mod N);
+ * inv[i] = x^-1 * 2^(DIGITBITS*NWORDS) mod N, canonical, or 0 when gcd(a_i, N) != 1; gcd[i] = gcd(a_i, N) as a plain
+ * integer in the same vec layout (N for a_i = 0).  inv and gcd must not alias each other.                      */
+int gecm_vecinvmod(gecm_ctx *ctx, const void *a, void *inv, void *gcd, size_t batch);
 
 /* ---- L1 phase 0: curve construction (build_one_curve, ecm.c:1548-1803) ---------------------
  * Suyama parametrisation from sigma[0..batch): the context computes X, Z (=1), s = (A+2)/4 on the
@@ -296,8 +302,8 @@ int gecm_stage2_factor(gecm_ctx *ctx, size_t k, char *dec, size_t declen, int *i
  * gecm_format_save_line, gecm_format_resume_line, gecm_stage1_factor, gecm_stage2_factor, gecm_scan_factors (*first:
  * the lowest flagged caller index), gecm_curve_flag.  Stage 1 runs with 1 or 2 lanes per curve (0 = chosen by batch
  * size as for one number), stage 2 with one sub-sequence per curve.
- * GECM_ERR_STATE on a multi-modulus context: the L0 operators, gecm_get_one, gecm_upload_points, gecm_download_points,
- * gecm_download_points_plain, gecm_download_acc (the reference radix differs from number to number),
+ * GECM_ERR_STATE on a multi-modulus context: the L0 operators (gecm_vecinvmod among them), gecm_get_one,
+ * gecm_upload_points, gecm_download_points, gecm_download_points_plain, gecm_download_acc (the reference radix differs from number to number),
  * gecm_build_curves, gecm_set_special_form, gecm_set_report_modulus; gecm_build_curves_multi on a single-N context.
  * gecm_get_config describes the largest number.                                                                     */
 int gecm_create_multi(gecm_ctx **out, int device, const char *const *n_strs, size_t count, int digitbits);
