@@ -2,7 +2,8 @@
 sizes.  Inputs without small factors are built from Mersenne primes so that no curve hits the
 degenerate "factor already found" path.  Checks: L0 operators against Python integers (the
 mathematical definition the reference's operators satisfy, verified in tests/golden/l0.json),
-stage 1 and stage 2 against the oracle."""
+stage 1 and stage 2 against the oracle.  The stage-1 checks here run in the library's choice of layout, which is 32 lanes
+per curve at these batch sizes; the matrix of layouts, limb counts and moduli is tests/test_gpu_layouts.py."""
 import ctypes
 import math
 import os
