@@ -39,6 +39,10 @@ int gecm_dev_resize(gecm_dev *d, size_t ncurves);
 size_t gecm_dev_stride(gecm_dev *d);
 int gecm_dev_upload(gecm_dev *d, const uint32_t *X, const uint32_t *Z, const uint32_t *S);
 int gecm_dev_upload_xz(gecm_dev *d, const uint32_t *X, const uint32_t *Z);   /* X, Z only; S untouched */
+/* X, Z from canonical PLAIN residues x, z in [0, N) ([limb][curve], not Montgomery form): the device multiplies each by
+ * r2 = R^2 mod N (nl limbs; a multi-modulus context takes every block's from its group constants and ignores r2).
+ * S untouched; the padding lanes get x = z = 1.  Synchronous. */
+int gecm_dev_upload_plain(gecm_dev *d, const uint32_t *x, const uint32_t *z, const uint32_t *r2);
 int gecm_dev_set_tape(gecm_dev *d, const uint8_t *tape, size_t len);
 /* stage 1: asynchronous on the context's stream; HIP events bracket the kernel */
 /* lanes_per_curve: 1 = one curve per lane, 2 = X and Z of a curve on two adjacent lanes (for batches
@@ -80,12 +84,13 @@ int gecm_dev_l0_inv(gecm_dev *d, const uint32_t *a, uint32_t *inv, uint32_t *g, 
  * gecm_dev_set_multi: from now on every launch of this context takes its modulus per 64-curve block from the group
  * tables, with 1 or 2 lanes per curve and one stage-2 sub-sequence per curve; the L0 operators are refused.  Call it
  * right after gecm_dev_open.
- * gecm_dev_set_groups: after gecm_dev_resize, the constants of ngroups moduli (n, kp, one, r3: nl limbs each,
+ * gecm_dev_set_groups: after gecm_dev_resize, the constants of ngroups moduli (n, kp, one, r3, r2: nl limbs each,
  * modulus g at [g*nl]; rho, inv_iters: one word each) and the modulus of every 64-curve block of the batch
  * (stride / 64 entries, each < ngroups).  Copied before it returns. */
 void gecm_dev_set_multi(gecm_dev *d);
 int gecm_dev_set_groups(gecm_dev *d, uint32_t ngroups, const uint32_t *n, const uint32_t *kp, const uint32_t *one,
-                        const uint32_t *r3, const uint32_t *rho, const uint32_t *inv_iters, const uint32_t *block_group);
+                        const uint32_t *r3, const uint32_t *rho, const uint32_t *inv_iters, const uint32_t *r2,
+                        const uint32_t *block_group);
 
 /* ---- stage 2 (csrc/gecm_stage2.hpp) ----
  * r3 = R^3 mod N (28-bit limbs); inv_iters = batches of 28 division steps of the device inversion (fe_invert). */

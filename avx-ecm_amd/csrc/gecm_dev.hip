@@ -148,6 +148,7 @@ static gecm_modconst modconst(const gecm_dev *d)
     mc.inv_iters = d->inv_iters;
     mc.groups = d->multi ? d->dGroups : nullptr;
     mc.block_group = d->multi ? d->dBlockGroup : nullptr;
+    mc.r2 = nullptr;
     return mc;
 }
 
@@ -319,6 +320,35 @@ extern "C" int gecm_dev_upload_xz(gecm_dev *d, const uint32_t *X, const uint32_t
     HIPCHK(hipSetDevice(d->device));
     if (upload_soa(d, d->dX, X)) return -1;
     if (upload_soa(d, d->dZ, Z)) return -1;
+    HIPCHK(hipStreamSynchronize(d->stream));
+    return 0;
+}
+
+// Plain residues into the batch: x, z canonical in [0, N), host [limb][ncurves]; X = x R mod N, Z = z R mod N by the
+// to_mont kernel, through the scratch planes the downloads use.  The padding lanes get x = z = 1.
+extern "C" int gecm_dev_upload_plain(gecm_dev *d, const uint32_t *x, const uint32_t *z, const uint32_t *r2)
+{
+    HIPCHK(hipSetDevice(d->device));
+    if (d->multi ? !d->have_groups : !r2) {
+        g_err = d->multi ? "gecm_dev_upload_plain: the moduli of the batch are not set" : "gecm_dev_upload_plain: R^2 mod N missing";
+        return -2;
+    }
+    if (!d->stride) {
+        g_err = "gecm_dev_upload_plain: no batch";
+        return -2;
+    }
+    if (upload_soa(d, d->dT0, x)) return -1;
+    if (upload_soa(d, d->dT1, z)) return -1;
+    const size_t pad = d->stride - d->ncurves;        // at most 63: limb 0 of the padding lanes, set to 1
+    const std::vector<uint32_t> ones(pad ? pad : 1, 1u);
+    if (pad) {
+        HIPCHK(hipMemcpyAsync(d->dT0 + d->ncurves, ones.data(), pad * sizeof(uint32_t), hipMemcpyHostToDevice, d->stream));
+        HIPCHK(hipMemcpyAsync(d->dT1 + d->ncurves, ones.data(), pad * sizeof(uint32_t), hipMemcpyHostToDevice, d->stream));
+    }
+    gecm_modconst mc = modconst(d);
+    mc.r2 = r2;
+    d->k1->to_mont(d->stream, &mc, d->dT0, d->dT1, d->dX, d->dZ, d->stride);
+    HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(d->stream));
     return 0;
 }
@@ -586,7 +616,7 @@ extern "C" void gecm_dev_set_multi(gecm_dev *d) { d->multi = true; }
 
 extern "C" int gecm_dev_set_groups(gecm_dev *d, uint32_t ngroups, const uint32_t *n, const uint32_t *kp,
                                    const uint32_t *one, const uint32_t *r3, const uint32_t *rho,
-                                   const uint32_t *inv_iters, const uint32_t *block_group)
+                                   const uint32_t *inv_iters, const uint32_t *r2, const uint32_t *block_group)
 {
     HIPCHK(hipSetDevice(d->device));
     const size_t blocks = d->stride / 64, gb = d->k1->group_bytes, nl = (size_t)d->nl;
@@ -601,7 +631,8 @@ extern "C" int gecm_dev_set_groups(gecm_dev *d, uint32_t ngroups, const uint32_t
         }
     std::vector<unsigned char> packed(gb * ngroups);
     for (uint32_t g = 0; g < ngroups; g++) {
-        gecm_modconst mc = {n + g * nl, kp + g * nl, one + g * nl, r3 + g * nl, rho[g], inv_iters[g], nullptr, nullptr};
+        gecm_modconst mc = {n + g * nl, kp + g * nl, one + g * nl, r3 + g * nl, rho[g], inv_iters[g], nullptr, nullptr,
+                            r2 + g * nl};
         d->k1->pack_group(&mc, packed.data() + g * gb);
     }
     if (packed.size() > d->groups_cap) {

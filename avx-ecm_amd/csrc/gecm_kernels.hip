@@ -32,11 +32,20 @@ struct ModArgs {
 // memory and the modulus of every 64-curve block.  mod_consts() gives a kernel the constants of its curve block from
 // either source, as a reference the multiplies read as wave-uniform operands; each single-N kernel and its _multi twin
 // share one body (GECM_STAGE1_BODY and the like).
+// One modulus's constants block in device memory: S2Const, then what only the multi-modulus kernels without a by-value
+// twin of it need.  New fields go at the end: the kernels that read a prefix keep their offsets.
+template <int NL>
+struct GroupConst {
+    S2Const<NL> k;
+    Fe<NL> r2;    // R^2 mod N  (plain residue -> Montgomery form, k_to_mont_multi)
+};
+
 template <int NL>
 struct ModGroups {
-    const S2Const<NL> *groups;    // read-only for the whole launch
+    const GroupConst<NL> *groups; // read-only for the whole launch
     const uint32_t *block_group;  // modulus of curve block b (curves 64b .. 64b+63)
 };
+static_assert(offsetof(GroupConst<GECM_NL>, k) == 0, "S2Const must be a prefix of GroupConst");
 static_assert(offsetof(S2Const<GECM_NL>, m) == offsetof(ModArgs<GECM_NL>, m) &&
               offsetof(S2Const<GECM_NL>, one) == offsetof(ModArgs<GECM_NL>, one),
               "ModArgs must be a prefix of S2Const: multi-modulus kernels read one through the other");
@@ -51,9 +60,9 @@ template <class A, int NL>
 __device__ __forceinline__ const A &mod_consts(const ModGroups<NL> &g, uint32_t block)
 {
     typedef const __attribute__((address_space(4))) uint32_t c_u32;
-    typedef const __attribute__((address_space(4))) S2Const<NL> c_s2;
+    typedef const __attribute__((address_space(4))) GroupConst<NL> c_grp;
     const uint32_t grp = ((c_u32 *)g.block_group)[block];
-    return *(const A *)(const S2Const<NL> *)((c_s2 *)g.groups + grp);
+    return *(const A *)(const GroupConst<NL> *)((c_grp *)g.groups + grp);
 }
 #if GECM_HAS_PART(1)
 // ---------------------------------------------------------------- stage 1
@@ -261,6 +270,41 @@ k_from_mont_multi(const uint32_t *__restrict__ X, const uint32_t *__restrict__ Z
 }
 #undef GECM_FROM_MONT_BODY
 
+// The inverse: canonical plain residues x, z in [0, N) -> X = x R mod N, Z = z R mod N, canonical, by one multiply with
+// R^2 mod N each (x R^2 / R < N^2/R + N < 2N, then one conditional subtract).  The constants are in `a`, a ModArgs<NL>,
+// and R^2 mod N in `r2`.
+#define GECM_TO_MONT_BODY                                                       \
+    uint32_t idx = blockIdx.x * 64u + threadIdx.x;                              \
+    Fe<NL> x, z, r;                                                             \
+    fe_load(x, ix, stride, idx);                                                \
+    fe_load(z, iz, stride, idx);                                                \
+    fe_mul(r, x, r2, a.m);                                                      \
+    fe_cond_sub_n(r, a.m);                                                      \
+    fe_store(X, stride, idx, r);                                                \
+    fe_mul(r, z, r2, a.m);                                                      \
+    fe_cond_sub_n(r, a.m);                                                      \
+    fe_store(Z, stride, idx, r);
+
+template <int NL>
+__global__ void __launch_bounds__(64)
+k_to_mont(const uint32_t *__restrict__ ix, const uint32_t *__restrict__ iz, uint32_t *__restrict__ X,
+          uint32_t *__restrict__ Z, size_t stride, ModArgs<NL> a, Fe<NL> r2)
+{
+    GECM_TO_MONT_BODY
+}
+
+template <int NL>
+__global__ void __launch_bounds__(64)
+k_to_mont_multi(const uint32_t *__restrict__ ix, const uint32_t *__restrict__ iz, uint32_t *__restrict__ X,
+                uint32_t *__restrict__ Z, size_t stride, ModGroups<NL> g)
+{
+    const GroupConst<NL> &c = mod_consts<GroupConst<NL>>(g, blockIdx.x);
+    const ModArgs<NL> &a = *(const ModArgs<NL> *)&c;
+    const Fe<NL> &r2 = c.r2;
+    GECM_TO_MONT_BODY
+}
+#undef GECM_TO_MONT_BODY
+
 // ---------------------------------------------------------------- L0 test-level operators
 template <int NL>
 __global__ void __launch_bounds__(64)
@@ -458,7 +502,7 @@ static S2Const<GECM_NL> s2_const(const gecm_modconst *mc)
 
 static ModGroups<GECM_NL> mod_groups(const gecm_modconst *mc)
 {
-    return ModGroups<GECM_NL>{(const S2Const<GECM_NL> *)mc->groups, mc->block_group};
+    return ModGroups<GECM_NL>{(const GroupConst<GECM_NL> *)mc->groups, mc->block_group};
 }
 
 #define CAT_(a, b) a##b
@@ -529,6 +573,21 @@ static void launch_from_mont(void *stream, const gecm_modconst *mc, const uint32
                            mod_args<ModArgs<GECM_NL>>(mc));
 }
 
+static void launch_to_mont(void *stream, const gecm_modconst *mc, const uint32_t *ix, const uint32_t *iz, uint32_t *X,
+                           uint32_t *Z, size_t stride)
+{
+    const dim3 grid((unsigned)(stride / 64)), block(64);
+    if (mc->groups) {
+        hipLaunchKernelGGL(k_to_mont_multi<GECM_NL>, grid, block, 0, (hipStream_t)stream, ix, iz, X, Z, stride,
+                           mod_groups(mc));
+        return;
+    }
+    Fe<GECM_NL> r2;
+    for (int i = 0; i < GECM_NL; i++) r2.v[i] = mc->r2[i];
+    hipLaunchKernelGGL(k_to_mont<GECM_NL>, grid, block, 0, (hipStream_t)stream, ix, iz, X, Z, stride,
+                       mod_args<ModArgs<GECM_NL>>(mc), r2);
+}
+
 static void launch_l0(void *stream, const gecm_modconst *mc, int op, const uint32_t *A, const uint32_t *B, uint32_t *C,
                       uint32_t *D, size_t stride, const uint32_t *fix)
 {
@@ -560,14 +619,17 @@ static void launch_gcd_scan(void *stream, const gecm_modconst *mc, const uint32_
 
 static void pack_group(const gecm_modconst *mc, void *out)
 {
-    const S2Const<GECM_NL> k = s2_const(mc);
-    memcpy(out, &k, sizeof k);
+    GroupConst<GECM_NL> c;
+    c.k = s2_const(mc);
+    for (int i = 0; i < GECM_NL; i++) c.r2.v[i] = mc->r2[i];
+    memcpy(out, &c, sizeof c);
 }
 
 extern "C" const gecm_kernels_p1 *CAT(CAT(gecm_kernels_, GECM_NL), _p1)(void)
 {
-    static const gecm_kernels_p1 t = {launch_stage1, launch_canon, launch_from_mont, launch_l0, launch_l0_inv, launch_gcd_scan,
-                                      FPolicy<GECM_NL>::G, pack_group, sizeof(S2Const<GECM_NL>), GECM_MANIFEST};
+    static const gecm_kernels_p1 t = {launch_stage1, launch_canon, launch_from_mont, launch_to_mont, launch_l0, launch_l0_inv,
+                                      launch_gcd_scan, FPolicy<GECM_NL>::G, pack_group, sizeof(GroupConst<GECM_NL>),
+                                      GECM_MANIFEST};
     return &t;
 }
 #endif

@@ -19,6 +19,7 @@ typedef struct {
      * modulus of every 64-curve block; the launchers then run the kernels' _multi instantiations */
     const void *groups;
     const uint32_t *block_group;
+    const uint32_t *r2;          /* R^2 mod N: to_mont of a single-modulus launch, and pack_group */
 } gecm_modconst;
 
 /* Stage-2 kernel arguments (csrc/gecm_stage2.hpp), passed by value: the type names are part of the kernel symbols. */
@@ -85,6 +86,9 @@ struct gecm_kernels_p1 {
     void (*canon)(void *stream, const gecm_modconst *mc, uint32_t *X, uint32_t *Z, size_t stride);
     void (*from_mont)(void *stream, const gecm_modconst *mc, const uint32_t *X, const uint32_t *Z, uint32_t *ox,
                       uint32_t *oz, size_t stride);
+    /* the inverse: canonical plain residues ix, iz in [0, N) -> canonical Montgomery form in X, Z (needs mc->r2) */
+    void (*to_mont)(void *stream, const gecm_modconst *mc, const uint32_t *ix, const uint32_t *iz, uint32_t *X,
+                    uint32_t *Z, size_t stride);
     void (*l0)(void *stream, const gecm_modconst *mc, int op, const uint32_t *A, const uint32_t *B, uint32_t *C,
                uint32_t *D, size_t stride, const uint32_t *fix);
     /* the test-level inversion (single modulus only): C = the inverse of A in the radix `fix` sets, or 0; G = gcd(A, N) */
@@ -93,7 +97,7 @@ struct gecm_kernels_p1 {
     void (*gcd_scan)(void *stream, const gecm_modconst *mc, const uint32_t *V, uint32_t *G, uint32_t *flags,
                      size_t stride);
     int fform_generic_limbs;      /* limbs of a 2^k -+ c modulus that are not 2^28 - 1 */
-    /* one modulus's constants (n, kp, one, r3, rho, inv_iters of mc) as the multi-modulus kernels read them from device
+    /* one modulus's constants (n, kp, one, r3, rho, inv_iters, r2 of mc) as the multi-modulus kernels read them from device
      * memory: group_bytes bytes at out */
     void (*pack_group)(const gecm_modconst *mc, void *out);
     size_t group_bytes;

@@ -1,6 +1,8 @@
 /* avx_ecm_main.c — the avx-ecm command line on top of libgecm.
  *
  *     avx-ecm input curves B1 [threads] [B2] [sigma]
+ *     avx-ecm -f FILE curves B1 [threads] [B2] [sigma]      (a list of inputs, run_file)
+ *     avx-ecm -r FILE B1 [B2]                               (go on from resume lines, run_resume)
  *
  * Same positional arguments as the reference (main.c:380-384, 459-460, 537-559) and the same FILES, byte for byte:
  * save_b1.txt (GMP-ECM resume lines, ecm.c:1372-1380), ecm_results.txt (factor lines, ecm.c:1356-1367, 1510-1522)
@@ -107,6 +109,10 @@ typedef struct {
     int failed;
     uint64_t lcg;
     double t_start;
+    /* avx-ecm -r: the passes start from the lines of a file (resume_t), stage 1 goes on at first_range (nranges:
+     * it is complete, the lines are save lines: nothing is added to save_b1.txt and stage-1 factors are old news) */
+    const struct resume_t *res;
+    int first_range, s1_complete;
 } run_t;
 
 typedef struct {
@@ -154,6 +160,8 @@ typedef struct job_t {
     first_range_t *fr;         /* stage 1: the first range's map, being made on the pass thread meanwhile (or NULL) */
     double kernel_ms;
     int progress;              /* print the launches of a long stage 1 as they finish (GPU 0 of a pass that prints live) */
+    const void *rx, *rz;       /* -r: the plain residues of the part's curves (vec layout), and what stage 1 has done */
+    uint64_t b1_done;
 } job_t;
 
 typedef struct {
@@ -166,6 +174,7 @@ typedef struct {
     int live;                  /* not pipelined: print as it happens */
     pthread_t th;
     int threaded;              /* th is a thread to join */
+    void *rx, *rz;             /* -r: the residues its one job starts from */
 } pass_t;
 
 static void text_add(text_t *t, const char *s, size_t n)
@@ -231,6 +240,14 @@ static void *describe_ranges(void *arg)
 static int step_build(job_t *j)
 {
     return gecm_build_curves(j->part->ctx, j->part->sigma, j->part->ncurves);
+}
+
+/* -r: the curves of the lines; save lines (stage 1 complete) get the factor scan a stage 1 would have ended with */
+static int step_resume(job_t *j)
+{
+    int rc = gecm_resume_points(j->part->ctx, j->part->sigma, j->rx, j->rz, j->part->ncurves, j->b1_done);
+    if (rc >= 0 && j->b1_done && gecm_scan_factors(j->part->ctx, 1, NULL) < 0) rc = -1;
+    return rc;
 }
 
 static int step_stage1(job_t *j)
@@ -342,7 +359,7 @@ static const part_t *locate(const view_t *v, size_t u, size_t *k)
 /* the first of batches 0 .. upto with a curve flagged after stage 1 (stages = 2: after either stage); upto if none */
 static size_t first_flagged(const view_t *v, size_t upto, int stages)
 {
-    for (size_t u = 0; u < upto * v->run->ub; u++) {
+    for (size_t u = 0; u < upto * v->run->ub && u < v->ucurves; u++) {   /* (-r: the last batch may be short) */
         size_t k;
         const part_t *p = locate(v, u, &k);
         if (gecm_curve_flag(p->ctx, 1, k) || (stages > 1 && gecm_curve_flag(p->ctx, 2, k))) return u / v->run->ub;
@@ -358,6 +375,7 @@ static void factor_lines(const view_t *v, int stage, size_t b, uint64_t label, t
     static __thread char fac[4096];
     for (size_t l = 0; l < (size_t)VECLEN * (size_t)R->threads; l++) {
         size_t k;
+        if (line_curve(R, b, l) >= v->ucurves) continue;
         const part_t *p = locate(v, line_curve(R, b, l), &k);
         if (!gecm_curve_flag(p->ctx, stage, k)) continue;
         int prp = 0;
@@ -424,7 +442,7 @@ static void write_batches(const view_t *v, FILE *f, char **lines, size_t b_from,
     for (size_t b = b_from; b < b_to; b++)
         for (size_t l = 0; l < (size_t)VECLEN * (size_t)v->run->threads; l++) {
             const size_t u = line_curve(v->run, b, l);
-            if (lines[u]) fputs(lines[u], f);
+            if (u < v->ucurves && lines[u]) fputs(lines[u], f);
         }
 }
 
@@ -462,12 +480,12 @@ static void output_settle(const view_t *v, output_t *o)
 static int output_format(const view_t *v, output_t *o)
 {
     const run_t *R = v->run;
-    o->lines = format_lines(v, R->B1, o->nwrite * R->ub);
+    o->lines = format_lines(v, R->B1, o->nwrite * R->ub < v->ucurves ? o->nwrite * R->ub : v->ucurves);
     if (!o->lines) return -1;
     if (o->found) {
         for (int c = 0; c < v->nck; c++)
             if (v->ck[c].first_flagged == o->bstar && v->ck[c].res.len) text_add(&o->res, v->ck[c].res.buf, v->ck[c].res.len);
-        factor_lines(v, 1, o->bstar, R->B1, &o->res, &o->out1);
+        if (!R->s1_complete) factor_lines(v, 1, o->bstar, R->B1, &o->res, &o->out1);
         if (R->do_stage2) factor_lines(v, 2, o->bstar, R->B2, &o->res, &o->out2);
     }
     return 0;
@@ -478,9 +496,9 @@ static void output_write(const view_t *v, const output_t *o, const char *log, co
 {
     if (log) fputs(log, stdout);
     if (o->out1.len) fputs(o->out1.buf, stdout);
-    FILE *save = fopen("save_b1.txt", "a");
+    FILE *save = v->run->s1_complete ? NULL : fopen("save_b1.txt", "a");
     if (save) { write_batches(v, save, o->lines, 0, o->nwrite); fclose(save); }
-    else printf("could not open save_b1.txt for appending, Stage 1 data will not be saved\n");
+    else if (!v->run->s1_complete) printf("could not open save_b1.txt for appending, Stage 1 data will not be saved\n");
     if (s2log) fputs(s2log, stdout);
     if (o->out2.len) fputs(o->out2.buf, stdout);
     if (o->res.len) {
@@ -580,7 +598,7 @@ static int pass_stage1(pass_t *ps)
     const double t = now();
     gecm_stage1_stats st;
     memset(&st, 0, sizeof st);
-    for (int r = 0; r < R->nranges; r++) {
+    for (int r = R->first_range; r < R->nranges; r++) {
         const gecm_stage1_range_desc *rd = &R->rd[r];
         /* the reference sieves range 0 once before its first batch (ecm.c:1139-1146) and again whenever a batch
          * starts after a later range was loaded (ecm.c:1160-1173) */
@@ -664,7 +682,7 @@ static void *pass_run(void *arg)
 
     /* host: the curves (ecm.c:1177-1204) */
     double t_build = now();
-    if (run_all(ps->jobs, R->gpus, step_build, NULL, 0)) goto out;
+    if (run_all(ps->jobs, R->gpus, R->res ? step_resume : step_build, NULL, 0)) goto out;
     t_build = now() - t_build;
 
     /* the GPUs, in pass order */
@@ -677,7 +695,7 @@ static void *pass_run(void *arg)
     plog(ps, "\nCommencing curves %zu-%zu of %zu\n", lines_per_batch * v->b0, lines_per_batch * (v->b0 + v->nb) - 1,
          (size_t)R->threads * R->per_thread);                                                      /* ecm.c:1201 */
     plog(ps, "Building curves took %1.4f seconds.\n", t_build);                                    /* ecm.c:1204 */
-    if (pass_stage1(ps) || (R->do_stage2 && pass_stage2(ps, &s2log))) goto out;
+    if ((!R->s1_complete && pass_stage1(ps)) || (R->do_stage2 && pass_stage2(ps, &s2log))) goto out;
     output_settle(v, &o);
     turn_done(R, GPU, i, o.found ? FOUND : DONE);   /* the GPUs go to the next pass */
 
@@ -704,6 +722,8 @@ static void pass_join(pass_t *ps)
     }
     free(ps->v.ck);
     free(ps->sigma);
+    free(ps->rx);
+    free(ps->rz);
     free(ps->log.buf);
     memset(ps, 0, sizeof *ps);
 }
@@ -743,6 +763,140 @@ static int make_contexts(gecm_ctx **ctx, int n, int devices, const char *modulus
             return 2;
         }
     return 0;
+}
+
+/* ---- avx-ecm -r: the lines of a resume file --------------------------------------------------------------------
+ * One group = consecutive lines on one N.  The text stays as read; rec points into it. */
+typedef struct {
+    char *text;
+    gecm_resume_rec rec;
+} rline_t;
+
+typedef struct resume_t {
+    const rline_t *lines;      /* of the group the run is on */
+    size_t nlines;
+} resume_t;
+
+/* a number of a line as an integer (the parser has checked its digits and its length) */
+static void rnum(mpl_t *v, const gecm_resume_num *n)
+{
+    static __thread char tmp[MPL_MAXL * 10 + 16];
+    if (!n->digits) { mpl_set_u64(v, 1); return; }              /* Z absent */
+    const size_t off = n->base == 16 ? 2 : 0;
+    memcpy(tmp, "0x", off);
+    memcpy(tmp + off, n->digits, n->len);
+    tmp[off + n->len] = 0;
+    if (mpl_set_str(v, tmp)) mpl_set_u64(v, 0);
+}
+
+/* x and z of `count` lines as vec operands of a context with this configuration */
+static int pack_residues(const gecm_config *cfg, const rline_t *lines, size_t count, size_t lane0, size_t batch, void *x, void *z)
+{
+    for (size_t i = 0; i < count; i++)
+        for (int q = 0; q < 2; q++) {
+            mpl_t v;
+            rnum(&v, q ? &lines[i].rec.z : &lines[i].rec.x);
+            if (cfg->digitbits == 52) mpl_to_limbs64((uint64_t *)(q ? z : x) + lane0 + i, batch, cfg->nwords, 52, &v);
+            else mpl_to_limbs32((uint32_t *)(q ? z : x) + lane0 + i, batch, cfg->nwords, 32, &v);
+        }
+    return 0;
+}
+
+/* the sigmas and residues of a pass of a resumed run: lines b0*ub .. of the group, fewer in a last, short batch */
+static int resume_pass_input(pass_t *ps, const gecm_ctx *ctx)
+{
+    const run_t *R = ps->run;
+    view_t *v = &ps->v;
+    const size_t first = v->b0 * R->ub;
+    if (first + v->ucurves > R->res->nlines) v->ucurves = R->res->nlines - first;
+    gecm_config cfg;
+    gecm_get_config(ctx, &cfg);
+    const size_t bytes = v->ucurves * (size_t)cfg.nwords * (cfg.digitbits == 52 ? 8 : 4);
+    ps->rx = malloc(bytes);
+    ps->rz = malloc(bytes);
+    if (!ps->rx || !ps->rz) { fprintf(stderr, "out of memory\n"); return -1; }
+    for (size_t u = 0; u < v->ucurves; u++) ps->sigma[u] = R->res->lines[first + u].rec.sigma;
+    return pack_residues(&cfg, R->res->lines + first, v->ucurves, 0, v->ucurves, ps->rx, ps->rz);
+}
+
+/* the passes of a run, in order, on one or two sets of contexts: batches_per_pass reference batches each; 2 at once when
+ * memory runs out */
+static int run_passes(run_t *R, gecm_ctx *ctx[2][MAX_GPUS], int gpus, int slots, size_t batches_per_pass)
+{
+    static pass_t pass[2];
+    const size_t npasses = (R->nbatches + batches_per_pass - 1) / batches_per_pass;
+    for (size_t pi = 0; pi < npasses; pi++) {
+        const int s = (int)(pi % (size_t)slots);
+        pass_t *ps = &pass[s];
+        pass_join(ps);                            /* the pass before the last one, when there are two slots */
+        pthread_mutex_lock(&R->mu);
+        const int stop = R->found_pass != (size_t)-1 || R->failed;
+        pthread_mutex_unlock(&R->mu);
+        if (stop) break;
+        view_t *v = &ps->v;
+        ps->run = R;
+        v->run = R;
+        ps->index = pi;
+        ps->live = slots == 1;
+        v->b0 = pi * batches_per_pass;
+        v->nb = R->nbatches - v->b0 < batches_per_pass ? R->nbatches - v->b0 : batches_per_pass;
+        v->ucurves = v->nb * R->ub;
+        ps->sigma = (uint64_t *)malloc(v->ucurves * sizeof(uint64_t));
+        v->ck = (ck_t *)calloc((size_t)R->nranges + 1, sizeof(ck_t));
+        if (!ps->sigma || !v->ck) { fprintf(stderr, "out of memory\n"); return 2; }
+        if (R->res && resume_pass_input(ps, ctx[s][0])) return 2;
+        for (size_t u = 0; u < v->ucurves && !R->res; u++) {
+            /* fixed sigma: lane i of every thread of batch b runs sigma + 8 b + i (main.c:761, ecm.c:1187) */
+            if (R->fixed_sigma) ps->sigma[u] = R->sigma0 + VECLEN * v->b0 + u;
+            else do { ps->sigma[u] = lcg_rand(&R->lcg); } while (ps->sigma[u] < 6);   /* ecm.c:1564-1570 */
+        }
+        /* host-side split: GPU g owns distinct curves [n*g/G, n*(g+1)/G) of this pass */
+        v->nparts = gpus;
+        for (int g = 0; g < gpus; g++) {
+            const size_t lo = v->ucurves * (size_t)g / (size_t)gpus, hi = v->ucurves * (size_t)(g + 1) / (size_t)gpus;
+            v->part[g] = (part_t){ctx[s][g], ps->sigma + lo, hi - lo, lo, 0};
+            ps->jobs[g].gpu = g;
+            ps->jobs[g].part = &v->part[g];
+            ps->jobs[g].rx = ps->rx;                  /* -r runs on one context: its part is the pass */
+            ps->jobs[g].rz = ps->rz;
+            ps->jobs[g].b1_done = R->s1_complete ? R->B1 : 0;
+        }
+        ps->threaded = pthread_create(&ps->th, NULL, pass_run, ps) == 0;
+        if (!ps->threaded) pass_run(ps);
+    }
+    for (int s = 0; s < 2; s++) pass_join(&pass[s]);
+    return 0;
+}
+
+/* Reference batches per pass: as many as fit FULL_BATCH distinct curves per GPU — or what the device's memory takes
+ * (the stage-2 table of 1024-bit curves is 1.1 MB per curve: 149 GB for a full batch).  GECM_PASS_CURVES (distinct
+ * curves per pass over all GPUs) overrides it for tests.  *mem_free: what the device reports free (0: unknown);
+ * *budget: the part of it one context may fill. */
+static size_t pass_batches(const run_t *R, gecm_ctx *c, int gpus, int per_gpu, uint64_t *mem_free, uint64_t *budget)
+{
+    uint64_t mem_total = 0;
+    *mem_free = 0;
+    (void)gecm_device_memory(c, mem_free, &mem_total);
+    *budget = *mem_free / 10 * 9 / (uint64_t)per_gpu;
+    size_t fit = FULL_BATCH;
+    while (fit > 64 && *mem_free && gecm_batch_bytes(c, fit, R->do_stage2, R->B1, 0, 0) > *budget) fit = fit / 2 / 64 * 64;
+    if (fit < 64) fit = 64;
+    const size_t cap = env_count("GECM_PASS_CURVES") ? (size_t)env_count("GECM_PASS_CURVES") : fit * (size_t)gpus;
+    return cap / R->ub ? cap / R->ub : 1;
+}
+
+/* what the passes of a run share, before the first one starts: the locks, and the first prime range of stage 2 */
+static void run_begin(run_t *R)
+{
+    pthread_mutex_init(&R->fr.mu, NULL);
+    pthread_cond_init(&R->fr.cv, NULL);
+    pthread_mutex_init(&R->mu, NULL);
+    pthread_cond_init(&R->cv, NULL);
+    R->fr.lo = R->B1;
+    R->fr.hi = R->B1 + PRIME_RANGE < R->B2 ? R->B1 + PRIME_RANGE : R->B2;
+    R->fr.D = gecm_s2_default_D(R->B1);
+    R->fr.U = GECM_S2_DEFAULT_U;
+    R->found_pass = (size_t)-1;
 }
 
 /* one input, the reference's command line: avx-ecm input curves B1 [threads] [B2] [sigma] */
@@ -801,18 +955,8 @@ static int run_single(int argc, char **argv)
     }
     static gecm_ctx *ctx[2][MAX_GPUS];
     if (make_contexts(ctx[0], gpus, devices, modulus, report)) return 2;
-    /* passes: as many reference batches as fit FULL_BATCH distinct curves per GPU — or what the device's memory takes
-     * (the stage-2 table of 1024-bit curves is 1.1 MB per curve: 149 GB for a full batch).  GECM_PASS_CURVES (distinct
-     * curves per pass over all GPUs) overrides it for tests. */
-    uint64_t mem_free = 0, mem_total = 0;
-    (void)gecm_device_memory(ctx[0][0], &mem_free, &mem_total);
-    const uint64_t budget = mem_free / 10 * 9 / (uint64_t)per_gpu;
-    size_t fit = FULL_BATCH;
-    while (fit > 64 && mem_free && gecm_batch_bytes(ctx[0][0], fit, R.do_stage2, R.B1, 0, 0) > budget) fit = fit / 2 / 64 * 64;
-    if (fit < 64) fit = 64;
-    const size_t cap = env_count("GECM_PASS_CURVES") ? (size_t)env_count("GECM_PASS_CURVES") : fit * (size_t)gpus;
-    size_t batches_per_pass = cap / R.ub;
-    if (batches_per_pass < 1) batches_per_pass = 1;
+    uint64_t mem_free, budget;
+    const size_t batches_per_pass = pass_batches(&R, ctx[0][0], gpus, per_gpu, &mem_free, &budget);
     const size_t npasses = (R.nbatches + batches_per_pass - 1) / batches_per_pass;
     /* two sets of contexts when there is more than one pass to overlap (one prime range only: with several, a pass
      * takes minutes to hours and its checkpoints are written as it goes) — and when two passes' worth of device memory
@@ -849,57 +993,13 @@ static int run_single(int argc, char **argv)
     printf("Initialization took %1.4f seconds.\n", now() - R.t_start);             /* main.c:776 */
     fflush(stdout);
 
-    pthread_mutex_init(&R.fr.mu, NULL);
-    pthread_cond_init(&R.fr.cv, NULL);
-    pthread_mutex_init(&R.mu, NULL);
-    pthread_cond_init(&R.cv, NULL);
-    R.fr.lo = R.B1;
-    R.fr.hi = R.B1 + PRIME_RANGE < R.B2 ? R.B1 + PRIME_RANGE : R.B2;
-    R.fr.D = gecm_s2_default_D(R.B1);
-    R.fr.U = GECM_S2_DEFAULT_U;
-    R.found_pass = (size_t)-1;
+    run_begin(&R);
 
     if (rd_pending) pthread_join(rd_thread, NULL);
     if (R.rd_rc) { fprintf(stderr, "%s\n", R.rd_err); return 2; }
     if (R.nranges == 1)                                                            /* ecm.c:1139-1146 */
         printf("Found %lu primes in range [%lu : %lu]\n", (unsigned long)R.rd[0].nprimes, (unsigned long)R.rd[0].lo, (unsigned long)R.rd[0].hi);
-    static pass_t pass[2];
-    for (size_t pi = 0; pi < npasses; pi++) {
-        const int s = (int)(pi % (size_t)slots);
-        pass_t *ps = &pass[s];
-        pass_join(ps);                            /* the pass before the last one, when there are two slots */
-        pthread_mutex_lock(&R.mu);
-        const int stop = R.found_pass != (size_t)-1 || R.failed;
-        pthread_mutex_unlock(&R.mu);
-        if (stop) break;
-        view_t *v = &ps->v;
-        ps->run = &R;
-        v->run = &R;
-        ps->index = pi;
-        ps->live = slots == 1;
-        v->b0 = pi * batches_per_pass;
-        v->nb = R.nbatches - v->b0 < batches_per_pass ? R.nbatches - v->b0 : batches_per_pass;
-        v->ucurves = v->nb * R.ub;
-        ps->sigma = (uint64_t *)malloc(v->ucurves * sizeof(uint64_t));
-        v->ck = (ck_t *)calloc((size_t)R.nranges + 1, sizeof(ck_t));
-        if (!ps->sigma || !v->ck) { fprintf(stderr, "out of memory\n"); return 2; }
-        for (size_t u = 0; u < v->ucurves; u++) {
-            /* fixed sigma: lane i of every thread of batch b runs sigma + 8 b + i (main.c:761, ecm.c:1187) */
-            if (R.fixed_sigma) ps->sigma[u] = R.sigma0 + VECLEN * v->b0 + u;
-            else do { ps->sigma[u] = lcg_rand(&R.lcg); } while (ps->sigma[u] < 6);   /* ecm.c:1564-1570 */
-        }
-        /* host-side split: GPU g owns distinct curves [n*g/G, n*(g+1)/G) of this pass */
-        v->nparts = gpus;
-        for (int g = 0; g < gpus; g++) {
-            const size_t lo = v->ucurves * (size_t)g / (size_t)gpus, hi = v->ucurves * (size_t)(g + 1) / (size_t)gpus;
-            v->part[g] = (part_t){ctx[s][g], ps->sigma + lo, hi - lo, lo, 0};
-            ps->jobs[g].gpu = g;
-            ps->jobs[g].part = &v->part[g];
-        }
-        ps->threaded = pthread_create(&ps->th, NULL, pass_run, ps) == 0;
-        if (!ps->threaded) pass_run(ps);
-    }
-    for (int s = 0; s < 2; s++) pass_join(&pass[s]);
+    if (run_passes(&R, ctx, gpus, slots, batches_per_pass)) return 2;
     if (R.fr.valid) gecm_pairmap_release(&R.fr.pm);
     for (int s = 0; s < slots; s++)
         for (int g = 0; g < gpus; g++) gecm_destroy(ctx[s][g]);
@@ -919,15 +1019,61 @@ typedef struct {
     char log[65536];
 } input_t;
 
-/* the inputs of one multi-modulus pass; returns 0, or 2 after a device or library error */
+/* One multi-modulus pass: input i has count[i] curves, the caller's curves first[i] .. of sigma / which; rl != NULL
+ * (-r): the curves start from the lines' residues, stage 1 complete.  Every input is written as the one-input path
+ * writes it: a pass of all its batches on one context.  Returns 0, or 2 after a device or library error. */
+static int multi_run(const char **ns, const char *const *logs, size_t n, run_t *R, const uint64_t *sigma, const uint32_t *which,
+                     const size_t *first, const size_t *count, size_t total, const rline_t *rl)
+{
+    gecm_ctx *mc = NULL;
+    void *rx = NULL, *rz = NULL;
+    int rc = gecm_create_multi(&mc, 0, ns, n, GECM_CLI_DIGITBITS);
+    if (rc == 0 && rl) {
+        gecm_config cfg;
+        gecm_get_config(mc, &cfg);
+        const size_t bytes = total * (size_t)cfg.nwords * (cfg.digitbits == 52 ? 8 : 4);
+        rx = malloc(bytes);
+        rz = malloc(bytes);
+        if (!rx || !rz) { fprintf(stderr, "out of memory\n"); exit(2); }
+        pack_residues(&cfg, rl, total, 0, total, rx, rz);
+        rc = gecm_resume_points_multi(mc, sigma, which, rx, rz, total, R->B1) < 0 || gecm_scan_factors(mc, 1, NULL) < 0;
+    } else if (rc == 0) {
+        rc = gecm_build_curves_multi(mc, sigma, which, total) < 0;
+        if (rc == 0) rc = gecm_stage1(mc, R->B1) || gecm_sync(mc) || gecm_scan_factors(mc, 1, NULL) < 0;
+    }
+    if (rc == 0 && R->do_stage2) rc = gecm_stage2(mc, R->B2, 0, 0) || gecm_scan_factors(mc, 2, NULL) < 0;
+    if (rc) fprintf(stderr, "%s\n", gecm_last_error());
+    for (size_t i = 0; i < n && !rc; i++) {
+        const view_t v = {.run = R, .nb = (count[i] + R->ub - 1) / R->ub, .ucurves = count[i], .nparts = 1,
+                          .part = {{mc, sigma, count[i], 0, first[i]}}};
+        output_t o;
+        output_settle(&v, &o);
+        rc = output_format(&v, &o);
+        if (!rc) output_write(&v, &o, logs ? logs[i] : NULL, NULL);   /* log: "gen: ...", "commencing parallel ecm on ..." */
+        output_release(&v, &o);
+    }
+    if (!rc)
+        printf("multi-modulus pass: %zu inputs, %zu curves%s, %s%s, %1.4f seconds of kernels after stage 1\n", n,
+               rl ? total : count[0], rl ? " in all" : " each", rl ? "resumed after stage 1" : "stage 1",
+               R->do_stage2 ? " and stage 2" : "", gecm_last_kernel_ms(mc) / 1000.0);
+    gecm_destroy(mc);
+    free(rx); free(rz);
+    return rc ? 2 : 0;
+}
+
+/* the inputs of one multi-modulus pass of -f, ucurves curves each */
 static int multi_pass(input_t **in, size_t n, run_t *R, size_t ucurves)
 {
-    const char **ns = (const char **)malloc(n * sizeof *ns);
+    const char **ns = (const char **)malloc(n * sizeof *ns), **logs = (const char **)malloc(n * sizeof *logs);
     uint64_t *sigma = (uint64_t *)malloc(n * ucurves * sizeof *sigma);
     uint32_t *which = (uint32_t *)malloc(n * ucurves * sizeof *which);
-    if (!ns || !sigma || !which) { fprintf(stderr, "out of memory\n"); exit(2); }
+    size_t *first = (size_t *)malloc(2 * n * sizeof *first), *count = first ? first + n : NULL;
+    if (!ns || !logs || !sigma || !which || !first) { fprintf(stderr, "out of memory\n"); exit(2); }
     for (size_t i = 0; i < n; i++) {
         ns[i] = in[i]->ndec;
+        logs[i] = in[i]->log;
+        first[i] = i * ucurves;
+        count[i] = ucurves;
         for (size_t u = 0; u < ucurves; u++) {
             uint64_t *sg = &sigma[i * ucurves + u];
             if (R->fixed_sigma) *sg = R->sigma0 + u;                                  /* as run_single's pass 0 */
@@ -935,28 +1081,9 @@ static int multi_pass(input_t **in, size_t n, run_t *R, size_t ucurves)
             which[i * ucurves + u] = (uint32_t)i;
         }
     }
-    gecm_ctx *mc = NULL;
-    int rc = gecm_create_multi(&mc, 0, ns, n, GECM_CLI_DIGITBITS);
-    if (rc == 0) rc = gecm_build_curves_multi(mc, sigma, which, n * ucurves) < 0;
-    if (rc == 0) rc = gecm_stage1(mc, R->B1) || gecm_sync(mc) || gecm_scan_factors(mc, 1, NULL) < 0;
-    if (rc == 0 && R->do_stage2) rc = gecm_stage2(mc, R->B2, 0, 0) || gecm_scan_factors(mc, 2, NULL) < 0;
-    if (rc) fprintf(stderr, "%s\n", gecm_last_error());
-    /* every input as the one-input path writes it: a pass of all its batches on one context */
-    for (size_t i = 0; i < n && !rc; i++) {
-        const view_t v = {.run = R, .nb = R->nbatches, .ucurves = ucurves, .nparts = 1,
-                          .part = {{mc, sigma, ucurves, 0, i * ucurves}}};
-        output_t o;
-        output_settle(&v, &o);
-        rc = output_format(&v, &o);
-        if (!rc) output_write(&v, &o, in[i]->log, NULL);   /* log: "gen: ...", "commencing parallel ecm on ..." */
-        output_release(&v, &o);
-    }
-    if (!rc)
-        printf("multi-modulus pass: %zu inputs, %zu curves each, stage 1%s, %1.4f seconds of kernels after stage 1\n", n,
-               ucurves, R->do_stage2 ? " and stage 2" : "", gecm_last_kernel_ms(mc) / 1000.0);
-    gecm_destroy(mc);
-    free(ns); free(sigma); free(which);
-    return rc ? 2 : 0;
+    const int rc = multi_run(ns, logs, n, R, sigma, which, first, count, n * ucurves, NULL);
+    free(ns); free(logs); free(sigma); free(which); free(first);
+    return rc;
 }
 
 static int run_file(int argc, char **argv)
@@ -1035,8 +1162,218 @@ static int run_file(int argc, char **argv)
     return rc;
 }
 
+/* ---- avx-ecm -r FILE B1 [B2]: go on from save_b1.txt or checkpoint.txt lines ------------------------------------------
+ * FILE holds resume lines (gecm_parse_resume_line: ours, the reference's, GMP-ECM -save).  Consecutive lines on one N are
+ * a group, its lines the curves of a one-thread run in order: line k is "curve k, thread 0, vec k mod VECLEN", and the
+ * run stops after the first VECLEN lines with a factor among them, as every run here does.  The B1 field says where the
+ * lines stand (gecm_stage1_resume_range): checkpoint lines of a run to B1 go through the remaining prime ranges
+ * (checkpoint.txt after each, as a run from the start), then save_b1.txt, then stage 2 if B2 > B1; save lines (field =
+ * B1) go to stage 2 alone and save_b1.txt is left as it is.  One N: the one-input path, on the first GPU.  Several N:
+ * multi-modulus passes packed as -f packs its inputs — stage 2 only, a multi pass stays within one prime range — and a
+ * group too large for one takes the one-input path.  A number's lines stand together: the same N in two places, with
+ * another between, is refused.  Everything is checked before anything runs or is written. */
+static const char *resume_usage = "usage: avx-ecm -r $file $B1 [$B2]\n"
+                                  "       (resume lines as in save_b1.txt / checkpoint.txt, or of a GMP-ECM -save file)\n";
+
+typedef struct {
+    size_t first, count;       /* lines of the file */
+    uint32_t range;            /* the range stage 1 goes on with; the range count: complete */
+    char ndec[MPL_MAXL * 10 + 16];
+} rgroup_t;
+
+/* one group on the one-input path */
+static int resume_single(const rgroup_t *g, const rline_t *lines, char **rargv, int rargc)
+{
+    static run_t R;
+    memset(&R, 0, sizeof R);
+    R.t_start = now();
+    if (parse_run(&R, rargc, rargv)) return 1;
+    const resume_t res = {lines + g->first, g->count};
+    R.res = &res;
+    R.gpus = 1;
+    R.nranges = gecm_stage1_ranges(R.B1);
+    R.first_range = (int)g->range;
+    R.s1_complete = R.first_range >= R.nranges;
+    R.rd = (gecm_stage1_range_desc *)calloc((size_t)R.nranges, sizeof *R.rd);
+    if (!R.rd) { fprintf(stderr, "out of memory\n"); return 2; }
+    for (int r = R.first_range; r < R.nranges && !R.rd_rc; r++)
+        R.rd_rc = gecm_stage1_describe_range(R.B1, R.B2, (uint32_t)r, &R.rd[r]);
+    if (R.rd_rc) { fprintf(stderr, "%s\n", gecm_last_error()); return 2; }
+    static gecm_ctx *ctx[2][MAX_GPUS];
+    if (make_contexts(ctx[0], 1, 1, g->ndec, NULL)) return 2;
+    uint64_t mem_free, budget;
+    const size_t batches_per_pass = pass_batches(&R, ctx[0][0], 1, 1, &mem_free, &budget);
+    printf("resuming %zu curves on N = %s %s\n", g->count, g->ndec, R.s1_complete ? "after stage 1" : "inside stage 1");
+    run_begin(&R);
+    if (run_passes(&R, ctx, 1, 1, batches_per_pass)) return 2;
+    if (R.fr.valid) gecm_pairmap_release(&R.fr.pm);
+    gecm_destroy(ctx[0][0]);
+    free(R.rd);
+    return R.failed ? 2 : 0;
+}
+
+static int run_resume(int argc, char **argv)
+{
+    if (argc < 4) { printf("%s", resume_usage); return 1; }
+    FILE *f = fopen(argv[2], "r");
+    if (!f) { printf("cannot read %s\n%s", argv[2], resume_usage); return 1; }
+    /* the run's arguments through the one parser: curves B1 threads [B2], one thread, the curve count per group */
+    char ncurves[32] = "1", one[] = "1";
+    char *rargv[4] = {ncurves, argv[3], one, argc > 4 ? argv[4] : NULL};
+    const int rargc = argc > 4 ? 4 : 3;
+    static run_t R0;
+    memset(&R0, 0, sizeof R0);
+    if (parse_run(&R0, rargc, rargv)) { fclose(f); return 1; }
+
+    rline_t *lines = NULL;
+    rgroup_t *groups = NULL;
+    size_t nlines = 0, cap_lines = 0, ngroups = 0, cap_groups = 0, lineno = 0;
+    char *text = NULL, *pending = NULL;           /* pending: the text of a line that is not counted in nlines yet */
+    size_t text_cap = 0;
+    int bad = 0, oom = 0;
+    mpl_t n_cur, n, v;
+    while (!bad && !oom && getline(&text, &text_cap, f) > 0) {
+        lineno++;
+        gecm_resume_rec rec;
+        const int rc = gecm_parse_resume_line(text, &rec);
+        if (rc == 1) continue;
+        if (rc) { printf("%s line %zu: %s\n", argv[2], lineno, gecm_last_error()); bad = 1; break; }
+        if (nlines == cap_lines) {
+            cap_lines = cap_lines ? 2 * cap_lines : 1024;
+            rline_t *more = (rline_t *)realloc(lines, cap_lines * sizeof *lines);
+            if (!more) { oom = 1; break; }
+            lines = more;
+        }
+        rline_t *l = &lines[nlines];
+        l->text = pending = strdup(text);
+        if (!l->text || gecm_parse_resume_line(l->text, &l->rec)) { oom = 1; break; }   /* (it parsed a moment ago) */
+        rnum(&n, &l->rec.n);
+        if (!ngroups || mpl_cmp(&n, &n_cur) != 0) {
+            if (ngroups == cap_groups) {
+                cap_groups = cap_groups ? 2 * cap_groups : 16;
+                rgroup_t *more = (rgroup_t *)realloc(groups, cap_groups * sizeof *groups);
+                if (!more) { oom = 1; break; }
+                groups = more;
+            }
+            if (!mpl_is_odd(&n) || mpl_cmp_u64(&n, 3) < 0) { printf("%s line %zu: field N must be an odd number >= 3\n", argv[2], lineno); bad = 1; break; }
+            rgroup_t *g = &groups[ngroups];
+            g->first = nlines;
+            g->count = 0;
+            mpl_get_dec(g->ndec, &n);
+            /* a number's lines stand together: the same N further down would be a second modulus of one multi pass */
+            for (size_t k = 0; k < ngroups && !bad; k++)
+                if (strcmp(groups[k].ndec, g->ndec) == 0) {
+                    printf("%s line %zu: lines on this N stand further up as well (line %zu of the resume lines on), with another "
+                           "N between: put the lines on one number together\n", argv[2], lineno, groups[k].first + 1);
+                    bad = 1;
+                }
+            if (bad) break;
+            ngroups++;
+            n_cur = n;
+            /* what the B1 field says about a run to B1: the one refusal that names what is not offered */
+            if (gecm_stage1_resume_range(R0.B1, l->rec.b1, &g->range)) {
+                printf("%s line %zu: B1 field %lu is neither B1 = %lu nor a checkpoint of a run to it: stage 1 is extended from "
+                       "no other B1 (the reference's stage 1 is not a product of prime powers cut at that prime)\n",
+                       argv[2], lineno, (unsigned long)l->rec.b1, (unsigned long)R0.B1);
+                bad = 1;
+                break;
+            }
+        }
+        rgroup_t *g = &groups[ngroups - 1];
+        if (l->rec.b1 != lines[g->first].rec.b1) {
+            printf("%s line %zu: B1 field %lu differs from the %lu of the lines on this N before it\n", argv[2], lineno,
+                   (unsigned long)l->rec.b1, (unsigned long)lines[g->first].rec.b1);
+            bad = 1;
+            break;
+        }
+        for (int q = 0; q < 2 && !bad; q++) {
+            rnum(&v, q ? &l->rec.z : &l->rec.x);
+            if (mpl_cmp(&v, &n) >= 0) {
+                printf("%s line %zu: %c is not below N.  The reference's special-form runs store residues modulo 2^k -/+ c next "
+                       "to N=; such files are resumed through the library: a context on 2^k -/+ c plus gecm_set_report_modulus\n",
+                       argv[2], lineno, q ? 'Z' : 'X');
+                bad = 1;
+            }
+        }
+        if (bad) break;
+        g->count++;
+        nlines++;
+        pending = NULL;
+    }
+    fclose(f);
+    free(text);
+    free(pending);
+    if (oom) { fprintf(stderr, "out of memory\n"); bad = 1; }
+    const uint32_t nranges = (uint32_t)gecm_stage1_ranges(R0.B1);
+    if (!bad && !nlines) { printf("%s holds no resume line\n%s", argv[2], resume_usage); bad = 1; }
+    for (size_t i = 0; i < ngroups && !bad; i++) {
+        if (groups[i].range >= nranges && !R0.do_stage2) {
+            printf("stage 1 of these lines is complete at B1 = %lu: nothing to do without B2 > B1\n%s", (unsigned long)R0.B1, resume_usage);
+            bad = 1;
+        } else if (groups[i].range < nranges && ngroups > 1) {
+            printf("%s holds lines on %zu numbers with prime ranges of stage 1 left: several numbers are resumed after stage 1 "
+                   "only (a multi-modulus pass stays within one prime range); resume them one file per number\n", argv[2], ngroups);
+            bad = 1;
+        }
+    }
+    int rc = oom ? 2 : bad ? 1 : 0;
+    if (!bad && gecm_device_count() < 1) { fprintf(stderr, "no HIP device visible\n"); rc = 2; }
+    if (rc == 0) {
+        printf("starting process %d: %zu resume lines on %zu number(s) from %s\n", (int)getpid(), nlines, ngroups, argv[2]);
+        const size_t cap = env_count("GECM_PASS_CURVES") ? (size_t)env_count("GECM_PASS_CURVES") : FULL_BATCH;
+        R0.t_start = now();
+        R0.s1_complete = 1;                        /* the multi passes: stage 2 only */
+        R0.nbatches = 0;
+        size_t p0 = 0, padded = 0;                 /* the pending multi pass: groups p0 .. i, their padded size */
+        for (size_t i = 0; i <= ngroups && rc != 2; i++) {
+            const size_t pad_i = i < ngroups ? (groups[i].count + 63) / 64 * 64 : 0;
+            const int alone = i < ngroups && (ngroups == 1 || pad_i > cap);
+            if (i > p0 && (i == ngroups || alone || padded + pad_i > cap)) {
+                const size_t n_in = i - p0, total = groups[i - 1].first + groups[i - 1].count - groups[p0].first;
+                const char **ns = (const char **)malloc(n_in * sizeof *ns);
+                uint64_t *sigma = (uint64_t *)malloc(total * sizeof *sigma);
+                uint32_t *which = (uint32_t *)malloc(total * sizeof *which);
+                size_t *first = (size_t *)malloc(2 * n_in * sizeof *first);
+                if (!ns || !sigma || !which || !first) {
+                    fprintf(stderr, "out of memory\n");
+                    free(ns); free(sigma); free(which); free(first);
+                    rc = 2;
+                    break;
+                }
+                for (size_t k = 0; k < n_in; k++) {
+                    const rgroup_t *g = &groups[p0 + k];
+                    ns[k] = g->ndec;
+                    first[k] = g->first - groups[p0].first;
+                    first[n_in + k] = g->count;
+                    for (size_t u = 0; u < g->count; u++) {
+                        sigma[first[k] + u] = lines[g->first + u].rec.sigma;
+                        which[first[k] + u] = (uint32_t)k;
+                    }
+                }
+                const int r1 = multi_run(ns, NULL, n_in, &R0, sigma, which, first, first + n_in, total, lines + groups[p0].first);
+                if (r1 > rc) rc = r1;
+                free(ns); free(sigma); free(which); free(first);
+                p0 = i;
+                padded = 0;
+            }
+            if (i == ngroups || rc == 2) break;
+            if (!alone) { padded += pad_i; continue; }
+            snprintf(ncurves, sizeof ncurves, "%zu", groups[i].count);
+            const int r1 = resume_single(&groups[i], lines, rargv, rargc);
+            if (r1 > rc) rc = r1;
+            p0 = i + 1;
+        }
+        printf("Process took %1.4f seconds.\n", now() - R0.t_start);
+    }
+    for (size_t i = 0; i < nlines; i++) free(lines[i].text);
+    free(lines);
+    free(groups);
+    return rc;
+}
+
 int main(int argc, char **argv)
 {
     if (argc > 1 && strcmp(argv[1], "-f") == 0) return run_file(argc, argv);
+    if (argc > 1 && strcmp(argv[1], "-r") == 0) return run_resume(argc, argv);
     return run_single(argc, argv);
 }

@@ -41,14 +41,16 @@ const char *gecm_manifest_host_mpl(void);
 const char *gecm_manifest_host_calc_lite(void);
 const char *gecm_manifest_host_cunningham(void);
 const char *gecm_manifest_host_gecm_mod(void);
+const char *gecm_manifest_host_gecm_resume(void);
 const char *gecm_version(void)
 {
     static char v[256];
     if (!v[0]) {
-        const char *h[6] = {gecm_manifest_host_gecm_plan(), gecm_manifest_host_gecm_pair(), gecm_manifest_host_mpl(),
-                            gecm_manifest_host_calc_lite(), gecm_manifest_host_cunningham(), gecm_manifest_host_gecm_mod()};
+        const char *h[7] = {gecm_manifest_host_gecm_plan(), gecm_manifest_host_gecm_pair(), gecm_manifest_host_mpl(),
+                            gecm_manifest_host_calc_lite(), gecm_manifest_host_cunningham(), gecm_manifest_host_gecm_mod(),
+                            gecm_manifest_host_gecm_resume()};
         int mixed = 0;
-        for (int i = 0; i < 6; i++) mixed |= strcmp(h[i], GECM_MANIFEST) != 0;
+        for (int i = 0; i < 7; i++) mixed |= strcmp(h[i], GECM_MANIFEST) != 0;
         snprintf(v, sizeof v, "libgecm 0.3 (gfx950) %s H:%s", gecm_dev_manifest(), mixed ? "MIXED" : GECM_MANIFEST);
     }
     return v;
@@ -119,7 +121,7 @@ struct gecm_ctx {
     int multi;
     size_t ngroups;
     gecm_mod *grp;
-    uint32_t *gconst;        /* the moduli's n, kp, one, r3 ([4][ngroups][nl]), then rho and inv_iters [ngroups] each */
+    uint32_t *gconst;        /* the moduli's n, kp, one, r3, r2 ([5][ngroups][nl]), then rho and inv_iters [ngroups] each */
     size_t nuser;            /* curves the caller built */
     uint32_t *slot;          /* caller's curve -> device position */
     uint32_t *pos_user;      /* device position -> caller's curve, GECM_PAD for padding */
@@ -552,14 +554,33 @@ static int run_slices(size_t n, int (*fn)(void *arg, size_t lo, size_t hi), void
     return err ? err : any;
 }
 
-int gecm_build_curves(gecm_ctx *c, const uint64_t *sigma, size_t batch)
+/* plain residues for the batch just built (gecm_resume_points): px, pz canonical in [0, N), [nl][batch] in device
+ * order; X, Z of the build are replaced by their Montgomery forms, made on the device.  A special-form twin takes the
+ * same residues (x < N <= Mw) with its own R^2 mod Mw and stays loaded. */
+static int upload_plain(gecm_ctx *c, const uint32_t *px, const uint32_t *pz)
 {
-    if (!c || !sigma || batch == 0) { set_err("gecm_build_curves: bad argument"); return GECM_ERR_ARG; }
-    if (c && c->multi) return multi_refuse("gecm_build_curves");
-    /* inputs are checked before the context takes the new batch: after an error it holds no batch at all (the
-     * phase functions then return GECM_ERR_STATE instead of running on memory nothing was uploaded to) */
-    for (size_t i = 0; i < batch; i++)
-        if (sigma[i] < 6) { set_err("gecm_build_curves: sigma[%zu] < 6", i); return GECM_ERR_ARG; }
+    if (gecm_dev_upload_plain(c->dev, px, pz, c->multi ? NULL : gecm_mod_r2(&c->mod))) return GECM_ERR_DEVICE;
+    if (!c->dev_f || !c->ff_loaded) return GECM_OK;
+    const size_t batch = c->batch, fwords = (size_t)c->ff_nl * batch;
+    uint32_t *f = (uint32_t *)calloc(2 * fwords + (size_t)c->ff_nl, 4);
+    if (!f) return GECM_ERR_NOMEM;
+    mpl_t v;
+    for (size_t i = 0; i < batch; i++) {
+        mpl_from_limbs32(&v, px + i, batch, c->mod.nl, LIMB_BITS);
+        mpl_to_limbs32(f + i, batch, c->ff_nl, LIMB_BITS, &v);
+        mpl_from_limbs32(&v, pz + i, batch, c->mod.nl, LIMB_BITS);
+        mpl_to_limbs32(f + fwords + i, batch, c->ff_nl, LIMB_BITS, &v);
+    }
+    mpl_mulmod(&v, &c->ff_r_mod_m, &c->ff_r_mod_m, &c->ff_M);
+    mpl_to_limbs32(f + 2 * fwords, 1, c->ff_nl, LIMB_BITS, &v);
+    const int rc = gecm_dev_upload_plain(c->dev_f, f, f + fwords, f + 2 * fwords);
+    free(f);
+    return rc ? GECM_ERR_DEVICE : GECM_OK;
+}
+
+/* gecm_build_curves after its checks; px != NULL: gecm_resume_points, the points are px, pz (upload_plain) */
+static int build_single(gecm_ctx *c, const uint64_t *sigma, size_t batch, const uint32_t *px, const uint32_t *pz)
+{
     int rc = alloc_batch(c, batch);
     if (rc) return rc;
     memcpy(c->sigma, sigma, batch * sizeof(uint64_t));
@@ -581,7 +602,23 @@ int gecm_build_curves(gecm_ctx *c, const uint64_t *sigma, size_t batch)
     free(hX);
     free(fX);
     if (rc) { set_err("%s", gecm_dev_error()); free_batch(c); return GECM_ERR_DEVICE; }
+    if (px && (rc = upload_plain(c, px, pz)) != 0) {
+        if (rc == GECM_ERR_DEVICE) set_err("%s", gecm_dev_error());
+        free_batch(c);
+        return rc;
+    }
     return built;
+}
+
+int gecm_build_curves(gecm_ctx *c, const uint64_t *sigma, size_t batch)
+{
+    if (!c || !sigma || batch == 0) { set_err("gecm_build_curves: bad argument"); return GECM_ERR_ARG; }
+    if (c && c->multi) return multi_refuse("gecm_build_curves");
+    /* inputs are checked before the context takes the new batch: after an error it holds no batch at all (the
+     * phase functions then return GECM_ERR_STATE instead of running on memory nothing was uploaded to) */
+    for (size_t i = 0; i < batch; i++)
+        if (sigma[i] < 6) { set_err("gecm_build_curves: sigma[%zu] < 6", i); return GECM_ERR_ARG; }
+    return build_single(c, sigma, batch, NULL, NULL);
 }
 
 int gecm_upload_points(gecm_ctx *c, const void *X, const void *Z, const void *s, size_t batch)
@@ -1360,15 +1397,15 @@ int gecm_create_multi(gecm_ctx **out, int device, const char *const *n_strs, siz
     /* the context itself: the largest N (what gecm_get_config reports) and the device */
     if (!rc) rc = gecm_mod_setup(&c->mod, "gecm_create_multi", n_strs[largest], digitbits, nl, pick_nl);
     if (!rc) {
-        c->gconst = (uint32_t *)calloc((size_t)4 * count * nl + 2 * count, sizeof(uint32_t));
+        c->gconst = (uint32_t *)calloc((size_t)5 * count * nl + 2 * count, sizeof(uint32_t));
         if (!c->gconst) rc = GECM_ERR_NOMEM;
     }
     if (!rc) {
-        uint32_t *rho = c->gconst + (size_t)4 * count * nl, *iters = rho + count;
+        uint32_t *rho = c->gconst + (size_t)5 * count * nl, *iters = rho + count;
         for (size_t g = 0; g < count; g++) {
-            for (int q = 0; q < 4; q++)        /* n, kp, one, r3 */
-                memcpy(c->gconst + ((size_t)q * count + g) * nl, q < 3 ? grp[g].n28 + (size_t)q * nl : grp[g].r3_28,
-                       (size_t)nl * sizeof(uint32_t));
+            for (int q = 0; q < 5; q++)        /* n, kp, one, r3, r2 */
+                memcpy(c->gconst + ((size_t)q * count + g) * nl,
+                       q < 3 ? grp[g].n28 + (size_t)q * nl : q == 3 ? grp[g].r3_28 : gecm_mod_r2(&grp[g]), (size_t)nl * sizeof(uint32_t));
             rho[g] = grp[g].rho28;
             iters[g] = grp[g].inv_iters;
         }
@@ -1386,18 +1423,27 @@ int gecm_create_multi(gecm_ctx **out, int device, const char *const *n_strs, siz
 
 size_t gecm_moduli(const gecm_ctx *c) { return c ? (c->multi ? c->ngroups : 1) : 0; }
 
-int gecm_build_curves_multi(gecm_ctx *c, const uint64_t *sigma, const uint32_t *modulus_index, size_t batch)
+/* the checks gecm_build_curves_multi and gecm_resume_points_multi make on their common arguments */
+static int multi_args(const gecm_ctx *c, const char *who, const uint64_t *sigma, const uint32_t *modulus_index, size_t batch)
 {
-    if (!c || !sigma || !modulus_index || batch == 0) { set_err("gecm_build_curves_multi: bad argument"); return GECM_ERR_ARG; }
-    if (!c->multi) { set_err("gecm_build_curves_multi: not a multi-modulus context (gecm_create_multi)"); return GECM_ERR_STATE; }
-    if (batch >= GECM_PAD) { set_err("gecm_build_curves_multi: batch too large"); return GECM_ERR_ARG; }
+    if (!c || !sigma || !modulus_index || batch == 0) { set_err("%s: bad argument", who); return GECM_ERR_ARG; }
+    if (!c->multi) { set_err("%s: not a multi-modulus context (gecm_create_multi)", who); return GECM_ERR_STATE; }
+    if (batch >= GECM_PAD) { set_err("%s: batch too large", who); return GECM_ERR_ARG; }
     for (size_t i = 0; i < batch; i++) {
-        if (sigma[i] < 6) { set_err("gecm_build_curves_multi: sigma[%zu] < 6", i); return GECM_ERR_ARG; }
+        if (sigma[i] < 6) { set_err("%s: sigma[%zu] < 6", who, i); return GECM_ERR_ARG; }
         if (modulus_index[i] >= c->ngroups) {
-            set_err("gecm_build_curves_multi: modulus_index[%zu] = %u, the context has %zu moduli", i, modulus_index[i], c->ngroups);
+            set_err("%s: modulus_index[%zu] = %u, the context has %zu moduli", who, i, modulus_index[i], c->ngroups);
             return GECM_ERR_ARG;
         }
     }
+    return GECM_OK;
+}
+
+/* gecm_build_curves_multi after its checks; ux != NULL: gecm_resume_points_multi, the points are the plain residues ux,
+ * uz ([nl][batch], the caller's order), the padding gets x = z = 1 */
+static int build_multi(gecm_ctx *c, const char *who, const uint64_t *sigma, const uint32_t *modulus_index, size_t batch,
+                       const uint32_t *ux, const uint32_t *uz)
+{
     /* positions: the moduli in order, each one's curves in the caller's order, padded to a multiple of 64 */
     const size_t ng = c->ngroups;
     size_t *cnt = (size_t *)calloc(ng, sizeof(size_t)), *goff = (size_t *)calloc(ng, sizeof(size_t));
@@ -1446,17 +1492,113 @@ int gecm_build_curves_multi(gecm_ctx *c, const uint64_t *sigma, const uint32_t *
     if (!rc) {
         const uint32_t *q = c->gconst;
         const size_t w = ng * (size_t)c->mod.nl;
-        if (gecm_dev_set_groups(c->dev, (uint32_t)ng, q, q + w, q + 2 * w, q + 3 * w, q + 4 * w, q + 4 * w + ng, blocks))
+        if (gecm_dev_set_groups(c->dev, (uint32_t)ng, q, q + w, q + 2 * w, q + 3 * w, q + 5 * w, q + 5 * w + ng, q + 4 * w, blocks))
             rc = GECM_ERR_DEVICE;
+    }
+    if (!rc && ux) {
+        uint32_t *dx = hX, *dz = hX + words;                     /* the build's X, Z: dropped */
+        memset(hX, 0, words * 2 * sizeof(uint32_t));
+        for (size_t p = 0; p < total; p++) {
+            const uint32_t i = pos_user[p];
+            if (i == GECM_PAD) { dx[p] = dz[p] = 1; continue; }
+            for (size_t l = 0; l < (size_t)c->mod.nl; l++) {
+                dx[l * total + p] = ux[l * batch + i];
+                dz[l * total + p] = uz[l * batch + i];
+            }
+        }
+        rc = upload_plain(c, dx, dz);
     }
     free(hX);
     free(blocks);
     if (rc) {
-        if (rc == GECM_ERR_DEVICE) set_err("gecm_build_curves_multi: %s", gecm_dev_error());
+        if (rc == GECM_ERR_DEVICE) set_err("%s: %s", who, gecm_dev_error());
         free_batch(c);
         return rc;
     }
     return anybad ? 1 : GECM_OK;
+}
+
+int gecm_build_curves_multi(gecm_ctx *c, const uint64_t *sigma, const uint32_t *modulus_index, size_t batch)
+{
+    const int rc = multi_args(c, "gecm_build_curves_multi", sigma, modulus_index, batch);
+    return rc ? rc : build_multi(c, "gecm_build_curves_multi", sigma, modulus_index, batch, NULL, NULL);
+}
+
+/* ---- resume ------------------------------------------------------------------- */
+/* The caller's plain x, z (vec layout of the context) as 28-bit limb planes [nl][batch] in the caller's order, each
+ * checked against its curve's N; worker threads, the first offending curve recorded for the error text. */
+typedef struct {
+    const gecm_ctx *c;
+    const void *src[2];
+    const uint32_t *modulus_index;   /* NULL: every curve on c->mod */
+    size_t batch;
+    uint32_t *planes;                /* x then z */
+    size_t first_bad;                /* batch: none */
+} plain_job;
+
+static int plain_slice(void *arg, size_t lo, size_t hi)
+{
+    plain_job *j = (plain_job *)arg;
+    const gecm_ctx *c = j->c;
+    const size_t words = (size_t)c->mod.nl * j->batch;
+    for (size_t i = lo; i < hi; i++) {
+        const gecm_mod *m = j->modulus_index ? &c->grp[j->modulus_index[i]] : &c->mod;
+        for (int q = 0; q < 2; q++) {
+            mpl_t v;
+            vec_get(&c->mod, &v, j->src[q], j->batch, i);          /* the context's NWORDS: the largest number's */
+            if (mpl_cmp(&v, &m->N) >= 0) {
+                size_t seen = __atomic_load_n(&j->first_bad, __ATOMIC_RELAXED);
+                while (i < seen && !__atomic_compare_exchange_n(&j->first_bad, &seen, i, 0, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) {}
+                return 1;
+            }
+            mpl_to_limbs32(j->planes + (size_t)q * words + i, j->batch, c->mod.nl, LIMB_BITS, &v);
+        }
+    }
+    return 0;
+}
+
+/* what both resume calls do once their context kind is settled; idx NULL on a single-N context */
+static int resume_points(gecm_ctx *c, const char *who, const uint64_t *sigma, const uint32_t *idx, const void *x,
+                         const void *z, size_t batch, uint64_t b1_done)
+{
+    if (!x || !z) { set_err("%s: bad argument", who); return GECM_ERR_ARG; }
+    if (b1_done == 1 || b1_done > GECM_B1_MAX) { set_err("%s: b1_done must be 0 or a B1 in [2, %llu]", who, (unsigned long long)GECM_B1_MAX); return GECM_ERR_ARG; }
+    const size_t words = (size_t)c->mod.nl * batch;
+    uint32_t *planes = (uint32_t *)calloc(words * 2, 4);
+    if (!planes) return GECM_ERR_NOMEM;
+    plain_job j = {c, {x, z}, idx, batch, planes, batch};
+    const int bad = run_slices(batch, plain_slice, &j);
+    if (bad) {
+        free(planes);
+        if (bad < 0) return bad;
+        set_err("%s: x[%zu] or z[%zu] is not below the curve's N", who, j.first_bad, j.first_bad);
+        return GECM_ERR_ARG;                      /* the previous batch is untouched */
+    }
+    const int built = idx ? build_multi(c, who, sigma, idx, batch, planes, planes + words)
+                          : build_single(c, sigma, batch, planes, planes + words);
+    free(planes);
+    if (built < 0) return built;
+    /* mid stage 1 (the caller goes on with gecm_stage1_range), or stage 1 taken as finished at b1_done; the counters
+     * start over: they count the ranges run from here */
+    c->B1 = b1_done;
+    c->s1_ptadds = c->s1_ptdups = c->s1_last_prime = c->s1_tape_len = 0;
+    return built;
+}
+
+int gecm_resume_points(gecm_ctx *c, const uint64_t *sigma, const void *x, const void *z, size_t batch, uint64_t b1_done)
+{
+    if (!c || !sigma || batch == 0) { set_err("gecm_resume_points: bad argument"); return GECM_ERR_ARG; }
+    if (c->multi) return multi_refuse("gecm_resume_points");
+    for (size_t i = 0; i < batch; i++)
+        if (sigma[i] < 6) { set_err("gecm_resume_points: sigma[%zu] < 6", i); return GECM_ERR_ARG; }
+    return resume_points(c, "gecm_resume_points", sigma, NULL, x, z, batch, b1_done);
+}
+
+int gecm_resume_points_multi(gecm_ctx *c, const uint64_t *sigma, const uint32_t *modulus_index, const void *x,
+                             const void *z, size_t batch, uint64_t b1_done)
+{
+    const int rc = multi_args(c, "gecm_resume_points_multi", sigma, modulus_index, batch);
+    return rc ? rc : resume_points(c, "gecm_resume_points_multi", sigma, modulus_index, x, z, batch, b1_done);
 }
 
 int gecm_curve_modulus(const gecm_ctx *c, size_t k)

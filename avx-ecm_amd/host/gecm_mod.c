@@ -83,7 +83,7 @@ int gecm_mod_setup(gecm_mod *m, const char *who, const char *n_str, int digitbit
     uint64_t nhat = mpl_get_u64(&t);
     m->rho_ref = digitbits == 52 ? (nhat & 0xfffffffffffffull) : (nhat & 0xffffffffull);
     m->rho28 = (uint32_t)(nhat & ((1u << LIMB_BITS) - 1));
-    m->n28 = (uint32_t *)calloc((size_t)nl * 6, sizeof(uint32_t));
+    m->n28 = (uint32_t *)calloc((size_t)nl * 7, sizeof(uint32_t));
     if (!m->n28) return GECM_ERR_NOMEM;
     m->kp28 = m->n28 + nl;
     m->one28 = m->kp28 + nl;
@@ -104,6 +104,9 @@ int gecm_mod_setup(gecm_mod *m, const char *who, const char *n_str, int digitbit
      * x^-1 Rref */
     mpl_mulmod(&t, &m->rref_mod_n, &m->int_to_ref, &m->N);
     mpl_to_limbs32(m->finv28, 1, nl, LIMB_BITS, &t);
+    /* R^2 mod N: one Montgomery multiply by it takes a plain residue x to x R (csrc/gecm_kernels.hip: k_to_mont) */
+    mpl_mulmod(&t, &m->rint_mod_n, &m->rint_mod_n, &m->N);
+    mpl_to_limbs32(gecm_mod_r2(m), 1, nl, LIMB_BITS, &t);
     /* batches of 28 division steps after which the device inversion has converged for a modulus of nbits bits:
      * the bound of the "half-delta" variant, floor((45907 bits + 26313) / 19929), +1, rounded up to whole batches */
     m->inv_iters = (uint32_t)((((45907ull * (unsigned)m->nbits + 26313ull) / 19929ull + 1) + 27) / 28);
@@ -112,7 +115,7 @@ int gecm_mod_setup(gecm_mod *m, const char *who, const char *n_str, int digitbit
 
 void gecm_mod_free(gecm_mod *m)
 {
-    free(m->n28);                          /* kp28 .. finv28 are parts of it */
+    free(m->n28);                          /* kp28 .. finv28 and gecm_mod_r2 are parts of it */
     m->n28 = NULL;
 }
 

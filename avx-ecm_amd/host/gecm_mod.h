@@ -23,6 +23,9 @@ typedef struct {
     uint32_t *finv28;    /* Rref^2/Rint mod N (see gecm_vecinvmod) */
     uint32_t inv_iters;  /* batches of 28 division steps after which the device inversion has converged for N */
 } gecm_mod;
+/* Rint^2 mod N, nl limbs: plain residue -> Montgomery form on the device (gecm_resume_points).  The last part of the
+ * n28 block, after finv28, without a pointer of its own: tests/test_inverse_model_cpu.py mirrors the struct as it is. */
+static inline uint32_t *gecm_mod_r2(const gecm_mod *m) { return m->finv28 + m->nl; }
 
 /* the calling thread's error text (gecm_last_error) */
 extern __thread char gecm_mod_err[512];

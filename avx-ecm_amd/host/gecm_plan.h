@@ -53,6 +53,7 @@ int gecm_stage1_range_info(gecm_range_info *ri, uint64_t B1, uint64_t B2, uint32
 /* Test hook (not in include/gecm.h): another PRIME_RANGE for the three functions above, so that tests walk the
  * multi-range path at small B1 next to the oracle run the same way; 0 restores 1e8.  Process-wide. */
 void gecm_plan_set_prime_range_for_tests(uint64_t range);
+uint64_t gecm_plan_prime_range(void);                        /* PRIME_RANGE in force: 1e8, or the test hook's */
 
 #ifdef __cplusplus
 }

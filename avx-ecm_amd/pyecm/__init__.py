@@ -3,6 +3,7 @@
 Plumbing only: every call goes straight to the shared library; there is no Python fallback.
 If libgecm.so is missing or fails to load, importing this module raises.
 """
+import collections
 import ctypes
 import os
 
@@ -128,6 +129,22 @@ _sig("gecm_curve_acc", c_int, c_void_p, c_size_t, c_char_p, c_size_t)
 EXPORTS += ["gecm_create_multi", "gecm_build_curves_multi", "gecm_moduli", "gecm_curve_modulus", "gecm_curve_acc"]
 
 
+class ResumeNum(ctypes.Structure):
+    _fields_ = [("digits", c_void_p), ("len", c_size_t), ("base", c_int)]
+
+
+class ResumeRec(ctypes.Structure):
+    _fields_ = [("sigma", c_u64), ("b1", c_u64), ("n", ResumeNum), ("x", ResumeNum), ("z", ResumeNum)]
+
+
+_sig("gecm_parse_resume_line", c_int, c_char_p, ctypes.POINTER(ResumeRec))
+_sig("gecm_stage1_resume_range", c_int, c_u64, c_u64, ctypes.POINTER(ctypes.c_uint32))
+_sig("gecm_resume_points", c_int, c_void_p, ctypes.POINTER(c_u64), c_void_p, c_void_p, c_size_t, c_u64)
+_sig("gecm_resume_points_multi", c_int, c_void_p, ctypes.POINTER(c_u64), ctypes.POINTER(ctypes.c_uint32), c_void_p,
+     c_void_p, c_size_t, c_u64)
+EXPORTS += ["gecm_parse_resume_line", "gecm_stage1_resume_range", "gecm_resume_points", "gecm_resume_points_multi"]
+
+
 class GecmError(RuntimeError):
     pass
 
@@ -156,6 +173,31 @@ def describe_range(b1, b2, r):
     d = RangeDesc()
     _chk(lib.gecm_stage1_describe_range(b1, b2, r, ctypes.byref(d)), "gecm_stage1_describe_range")
     return d
+
+
+# one save_b1.txt / checkpoint.txt / GMP-ECM -save line: b1 is the line's B1 field, z is 1 where the line has no Z
+ResumeLine = collections.namedtuple("ResumeLine", "sigma b1 n x z")
+
+
+def parse_resume_line(line):
+    """ResumeLine of one resume line, None for a line to skip (blank or '#'); GecmError names the field that is wrong"""
+    raw = line.encode() if isinstance(line, str) else bytes(line)
+    buf = ctypes.create_string_buffer(raw)
+    rec = ResumeRec()
+    if _chk(lib.gecm_parse_resume_line(buf, ctypes.byref(rec)), "gecm_parse_resume_line") == 1:
+        return None
+
+    def num(f):
+        off = f.digits - ctypes.addressof(buf)
+        return int(raw[off:off + f.len], f.base)
+    return ResumeLine(rec.sigma, rec.b1, num(rec.n), num(rec.x), num(rec.z) if rec.z.digits else 1)
+
+
+def stage1_resume_range(b1, field):
+    """the range a run to b1 goes on with from lines whose B1 field is `field`; stage1_ranges(b1) = stage 1 is complete"""
+    r = ctypes.c_uint32(0)
+    _chk(lib.gecm_stage1_resume_range(b1, field, ctypes.byref(r)), "gecm_stage1_resume_range")
+    return r.value
 
 
 class Engine:
@@ -249,6 +291,40 @@ class Engine:
         self.batch = len(X)
         _chk(lib.gecm_upload_points(self._h, self.pack(X), self.pack(Z), self.pack(s), len(X)), "gecm_upload_points")
 
+    def resume(self, sigmas, xs, zs, b1_done=0):
+        """start from the plain residues of save or checkpoint lines: mid stage 1 (go on with stage1_range), or with
+        b1_done = B1 as after stage1(B1)"""
+        if not len(sigmas) == len(xs) == len(zs):
+            raise ValueError("resume: one x and one z per sigma")
+        self._fits(xs, zs)
+        arr = (c_u64 * len(sigmas))(*sigmas)
+        self.batch = len(sigmas)
+        return _chk(lib.gecm_resume_points(self._h, arr, self.pack(xs), self.pack(zs), len(sigmas), b1_done),
+                    "gecm_resume_points")
+
+    def _fits(self, *vecs):
+        # pack() keeps the low MAXBITS bits: what does not fit them is no residue of this context
+        if any(v < 0 or v >> self.cfg.maxbits for vec in vecs for v in vec):
+            raise ValueError("resume: a residue is negative or longer than the context's %d bits" % self.cfg.maxbits)
+
+    def _line_moduli(self):
+        # the N that this context's lines carry: the report modulus, if one is set (read here, not when it is set)
+        rep = getattr(self, "_report_modulus", None)
+        return [self.n if rep is None else int(rep, 0) if isinstance(rep, str) else int(rep)]
+
+    def _resume_recs(self, recs, ns, b1_done):
+        return self.resume([r.sigma for r in recs], [r.x for r in recs], [r.z for r in recs], b1_done=b1_done)
+
+    def resume_lines(self, lines, b1_done=0):
+        """resume() from the text of resume lines (skipped lines dropped); every N must be the context's (on a
+        MultiEngine: one of its numbers, which decides the curve's modulus)"""
+        recs = [r for r in map(parse_resume_line, lines) if r is not None]
+        ns = self._line_moduli()
+        for k, r in enumerate(recs):
+            if r.n not in ns:
+                raise ValueError("resume_lines: line %d is on N = %d, not a number of this context" % (k, r.n))
+        return self._resume_recs(recs, ns, b1_done)
+
     def stage1(self, b1, sync=True):
         _chk(lib.gecm_stage1(self._h, b1), "gecm_stage1")
         if sync:
@@ -303,6 +379,7 @@ class Engine:
         """save lines name n and factors are reported of n (a divisor of the context's modulus): the reference's
         special-form runs, which work modulo 2^k -/+ 1 or 2^k - c and report against the number given"""
         _chk(lib.gecm_set_report_modulus(self._h, None if n is None else str(n).encode()), "gecm_set_report_modulus")
+        self._report_modulus = n
 
     def stage1_progress(self):
         """(launches finished, launches made) of the stage-1 call in flight"""
@@ -404,7 +481,7 @@ class Engine:
 class MultiEngine(Engine):
     """One multi-modulus gecm_ctx: curves on many numbers in one batch.  Curve k is the k-th sigma of
     build_curves; every per-curve call works against that curve's own number.  The calls that need one N (L0
-    operators, uploaded points, reference-radix downloads, special forms, report modulus) raise GecmError."""
+    operators, reference-radix uploads and downloads, special forms, report modulus) raise GecmError."""
 
     def __init__(self, ns, digitbits=52, device=0):
         self._h = c_void_p()
@@ -425,6 +502,24 @@ class MultiEngine(Engine):
         idx = (ctypes.c_uint32 * len(which))(*which)
         self.batch = len(sigmas)
         return _chk(lib.gecm_build_curves_multi(self._h, arr, idx, len(sigmas)), "gecm_build_curves_multi")
+
+    def resume(self, sigmas, which, xs, zs, b1_done=0):
+        """Engine.resume with curve k on number ns[which[k]]; xs, zs below that number"""
+        if not len(sigmas) == len(which) == len(xs) == len(zs):
+            raise ValueError("resume: one modulus index, one x and one z per sigma")
+        self._fits(xs, zs)
+        arr = (c_u64 * len(sigmas))(*sigmas)
+        idx = (ctypes.c_uint32 * len(which))(*which)
+        self.batch = len(sigmas)
+        return _chk(lib.gecm_resume_points_multi(self._h, arr, idx, self.pack(xs), self.pack(zs), len(sigmas), b1_done),
+                    "gecm_resume_points_multi")
+
+    def _line_moduli(self):
+        return self.ns
+
+    def _resume_recs(self, recs, ns, b1_done):
+        return self.resume([r.sigma for r in recs], [ns.index(r.n) for r in recs], [r.x for r in recs],
+                           [r.z for r in recs], b1_done=b1_done)
 
     def modulus_of(self, k):
         return _chk(lib.gecm_curve_modulus(self._h, k), "gecm_curve_modulus")

@@ -303,7 +303,7 @@ int gecm_stage2_factor(gecm_ctx *ctx, size_t k, char *dec, size_t declen, int *i
  * the lowest flagged caller index), gecm_curve_flag.  Stage 1 runs with 1 or 2 lanes per curve (0 = chosen by batch
  * size as for one number), stage 2 with one sub-sequence per curve.
  * GECM_ERR_STATE on a multi-modulus context: the L0 operators (gecm_vecinvmod among them), gecm_get_one,
- * gecm_upload_points, gecm_download_points, gecm_download_points_plain, gecm_download_acc (the reference radix differs from number to number),
+ * gecm_upload_points (given points go in through gecm_resume_points_multi), gecm_download_points, gecm_download_points_plain, gecm_download_acc (the reference radix differs from number to number),
  * gecm_build_curves, gecm_set_special_form, gecm_set_report_modulus; gecm_build_curves_multi on a single-N context.
  * gecm_get_config describes the largest number.                                                                     */
 int gecm_create_multi(gecm_ctx **out, int device, const char *const *n_strs, size_t count, int digitbits);
@@ -314,6 +314,49 @@ int gecm_curve_modulus(const gecm_ctx *ctx, size_t k);
 /* the stage-2 accumulator of curve k as the integer gecm_download_acc returns for it on a single-N context of its
  * number (reference Montgomery radix, canonical), in lower-case hex without prefix; returns the digit count */
 int gecm_curve_acc(gecm_ctx *ctx, size_t k, char *hex, size_t hexlen);
+
+/* ---- resume: save_b1.txt and checkpoint.txt lines back into a context ------------
+ * gecm_parse_resume_line reads one line "METHOD=ECM; SIGMA=...; B1=...; N=...; X=...; Z=...; PROGRAM=...;" — ours
+ * (ecm.c:1295-1305, 1372-1380) or one of a GMP-ECM -save file: fields in any order, unknown fields (CHECKSUM, PROGRAM,
+ * WHO, TIME, X0, Y0, Y, COMMENT, ...) ignored, numbers decimal or 0x-hex, Z absent = 1, PARAM absent or 0 (GMP-ECM's
+ * PARAM 0 is the Suyama sigma of the reference), CRLF and a missing last ';' accepted.  Pure host code: no context, no
+ * allocation; N, X, Z come back as (pointer to the first digit, digit count, base 10 | 16) into the caller's line.
+ * Returns GECM_OK, 1 for a line to skip (blank, or starting with '#'), or GECM_ERR_ARG with a text that names the
+ * field: METHOD other than ECM, PARAM other than 0, SIGMA, B1, N or X missing, empty or given twice, SIGMA < 6 or beyond 64 bits, an N
+ * that is an expression, anything but digits inside a number, a number longer than the library computes with.     */
+typedef struct {
+    const char *digits;     /* first digit (after "0x" for base 16); NULL: the field was absent (z only: Z = 1) */
+    size_t len;
+    int base;               /* 10 | 16 */
+} gecm_resume_num;
+typedef struct {
+    uint64_t sigma, b1;     /* the B1 field: B1 of a save line, the last prime of the range done of a checkpoint line */
+    gecm_resume_num n, x, z;
+} gecm_resume_rec;
+int gecm_parse_resume_line(const char *line, gecm_resume_rec *rec);
+/* The range a run to B1 goes on with from lines whose B1 field is b1_field.  b1_field == B1: *range =
+ * gecm_stage1_ranges(B1), stage 1 is complete (save lines).  Else the r + 1 for which range r of a run to B1 ends at
+ * prime b1_field and writes a checkpoint (gecm_stage1_describe_range(B1, B1, r): last_prime, checkpoint); that can be
+ * the range count too — the reference also checkpoints a last range whose last prime lies below B1 — and X, Z then are
+ * the final residues.  Anything else: GECM_ERR_ARG, "not a checkpoint of a run to B1 = ...".  The B1 field of a
+ * checkpoint says nothing else: the reference's stage 1 is not one prime-power product cut at that prime (every range
+ * runs the 2-power doublings again and skips its first prime), so lines are resumed by the run that wrote them only. */
+int gecm_stage1_resume_range(uint64_t B1, uint64_t b1_field, uint32_t *range);
+/* Phase 0 from given points: curve i has sigma[i] and the PLAIN canonical residues x[i], z[i] in [0, N) of a save or
+ * checkpoint line, as vec operands of the context's layout (data[lane + limb*batch], NWORDS limbs of DIGITBITS bits; on
+ * a multi-modulus context the NWORDS of gecm_get_config, the largest number's) — not in Montgomery form: the device
+ * converts.  s = (A+2)/4 is built from sigma exactly as gecm_build_curves / gecm_build_curves_multi build it (same
+ * failure records, same return value 1 when a denominator was not invertible, same stale operand).  Checked before the
+ * context gives up its previous batch: sigma >= 6, x, z < the curve's N (GECM_ERR_ARG); the _multi form on a single-N
+ * context and the other on a multi-modulus one return GECM_ERR_STATE.  A failure after that leaves no batch.
+ * b1_done = 0: the context is mid stage 1; the caller goes on with gecm_stage1_range(ctx, B1, r) for the r of
+ * gecm_stage1_resume_range, and gecm_stage2* answer "run stage 1 first".  b1_done = B1 > 0: stage 1 is taken as
+ * finished at B1 — save lines, factor scan, gecm_stage2_prepare, gecm_stage2_init, gecm_stage2 work as after
+ * gecm_stage1(B1).  gecm_get_stage1_stats of a resumed context counts only the ranges run since the resume.
+ * A context with a special-form multiply (gecm_set_special_form) keeps it for the remaining ranges.                */
+int gecm_resume_points(gecm_ctx *ctx, const uint64_t *sigma, const void *x, const void *z, size_t batch, uint64_t b1_done);
+int gecm_resume_points_multi(gecm_ctx *ctx, const uint64_t *sigma, const uint32_t *modulus_index, const void *x,
+                             const void *z, size_t batch, uint64_t b1_done);
 
 #ifdef __cplusplus
 }
