@@ -43,6 +43,21 @@ int gecm_dev_upload_xz(gecm_dev *d, const uint32_t *X, const uint32_t *Z);   /* 
  * r2 = R^2 mod N (nl limbs; a multi-modulus context takes every block's from its group constants and ignores r2).
  * S untouched; the padding lanes get x = z = 1.  Synchronous. */
 int gecm_dev_upload_plain(gecm_dev *d, const uint32_t *x, const uint32_t *z, const uint32_t *r2);
+/* canonical Montgomery-form S = (A+2)/4 of the batch */
+int gecm_dev_download_s(gecm_dev *d, uint32_t *S);
+/* ---- curve construction on the device (csrc/gecm_kernels.hip: k_build) ----
+ * gecm_dev_set_r2: R^2 mod N (nl limbs) of a single-modulus context, kept for gecm_dev_build.
+ * gecm_dev_build: the Suyama curves of sigma[0 .. count) into X, Z, S of the batch; count is what gecm_dev_resize was
+ * given (a multi-modulus context: after gecm_dev_set_groups, sigma in device order, any value in the padding).  Needs
+ * gecm_dev_set_s2const.  flags[i] = 1 where a denominator of curve i had no inverse.  Synchronous; the kernel's own time
+ * is gecm_dev_last_build_ms.
+ * gecm_dev_fill_twin: X, Z, S of dst (a context modulo Mw, N | Mw, on the same device with a batch of the same size)
+ * from those of src, on the device: out of src's Montgomery form, the limb planes copied (zero-filled or cut to dst's
+ * limb count), into dst's with r2 = dst's R^2 mod Mw.  Synchronous. */
+int gecm_dev_set_r2(gecm_dev *d, const uint32_t *r2);
+int gecm_dev_build(gecm_dev *d, const uint64_t *sigma, size_t count, uint32_t *flags);
+float gecm_dev_last_build_ms(gecm_dev *d);
+int gecm_dev_fill_twin(gecm_dev *dst, gecm_dev *src, const uint32_t *r2);
 int gecm_dev_set_tape(gecm_dev *d, const uint8_t *tape, size_t len);
 /* stage 1: asynchronous on the context's stream; HIP events bracket the kernel */
 /* lanes_per_curve: 1 = one curve per lane, 2 = X and Z of a curve on two adjacent lanes (for batches

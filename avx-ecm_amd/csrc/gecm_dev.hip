@@ -103,6 +103,11 @@ struct gecm_dev {
     uint32_t *dBlockGroup = nullptr;  // modulus of every 64-curve block of the batch
     size_t groups_cap = 0, blocks_cap = 0;
     bool have_groups = false;
+    // curve construction on the device (gecm_dev_build)
+    std::vector<uint32_t> r2;         // R^2 mod N of a single-modulus context (gecm_dev_set_r2)
+    uint64_t *dSigma = nullptr;
+    size_t sigma_cap = 0;
+    float build_ms = 0.f;
 };
 
 // ---- source manifest (Makefile): "K:<hash of the kernel objects' sources, or MIXED> R:<rowk> D:<this file>"
@@ -240,6 +245,7 @@ extern "C" void gecm_dev_close(gecm_dev *d)
     (void)hipFree(d->dTape);
     (void)hipFree(d->dGroups);
     (void)hipFree(d->dBlockGroup);
+    (void)hipFree(d->dSigma);
     if (d->ev0) (void)hipEventDestroy(d->ev0);
     if (d->ev1) (void)hipEventDestroy(d->ev1);
     if (d->stream) (void)hipStreamDestroy(d->stream);
@@ -350,6 +356,104 @@ extern "C" int gecm_dev_upload_plain(gecm_dev *d, const uint32_t *x, const uint3
     d->k1->to_mont(d->stream, &mc, d->dT0, d->dT1, d->dX, d->dZ, d->stride);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(d->stream));
+    return 0;
+}
+
+extern "C" int gecm_dev_download_s(gecm_dev *d, uint32_t *S)
+{
+    HIPCHK(hipSetDevice(d->device));
+    if (!d->stride) {
+        g_err = "gecm_dev_download_s: no batch";
+        return -2;
+    }
+    if (download_soa(d, S, d->dS)) return -1;
+    HIPCHK(hipStreamSynchronize(d->stream));
+    return 0;
+}
+
+// ---------------------------------------------------------------- curve construction
+extern "C" int gecm_dev_set_r2(gecm_dev *d, const uint32_t *r2)
+{
+    d->r2.assign(r2, r2 + d->nl);
+    return 0;
+}
+
+extern "C" float gecm_dev_last_build_ms(gecm_dev *d) { return d->build_ms; }
+
+extern "C" int gecm_dev_build(gecm_dev *d, const uint64_t *sigma, size_t count, uint32_t *flags)
+{
+    HIPCHK(hipSetDevice(d->device));
+    if (!d->stride || count != d->ncurves || !sigma || !flags) {
+        g_err = "gecm_dev_build: no batch of that many curves (gecm_dev_resize)";
+        return -2;
+    }
+    if (d->r3.empty() || (d->multi ? !d->have_groups : d->r2.empty())) {
+        g_err = d->multi ? "gecm_dev_build: the moduli of the batch are not set" : "gecm_dev_build: inversion constants or R^2 mod N missing";
+        return -2;
+    }
+    if (d->sigma_cap < d->stride) {
+        (void)hipFree(d->dSigma);
+        d->dSigma = nullptr;
+        d->sigma_cap = 0;
+        HIPCHK(hipMalloc(&d->dSigma, d->stride * sizeof(uint64_t)));
+        d->sigma_cap = d->stride;
+    }
+    if (d->flags_cap < d->stride) {
+        (void)hipFree(d->dFlags);
+        d->dFlags = nullptr;
+        d->flags_cap = 0;
+        HIPCHK(hipMalloc(&d->dFlags, d->stride * 4));
+        d->flags_cap = d->stride;
+    }
+    // the padding lanes build sigma = 0: computed, never flagged or read
+    HIPCHK(hipMemsetAsync(d->dSigma, 0, d->stride * sizeof(uint64_t), d->stream));
+    HIPCHK(hipMemcpyAsync(d->dSigma, sigma, count * sizeof(uint64_t), hipMemcpyHostToDevice, d->stream));
+    gecm_modconst mc = modconst(d);
+    mc.r2 = d->r2.empty() ? nullptr : d->r2.data();
+    HIPCHK(hipEventRecord(d->ev0, d->stream));
+    d->k1->build(d->stream, &mc, d->dSigma, d->dX, d->dZ, d->dS, d->dFlags, d->stride);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(d->ev1, d->stream));
+    HIPCHK(hipMemcpyAsync(flags, d->dFlags, count * 4, hipMemcpyDeviceToHost, d->stream));
+    HIPCHK(hipStreamSynchronize(d->stream));
+    HIPCHK(hipEventElapsedTime(&d->build_ms, d->ev0, d->ev1));
+    d->timed = false;
+    return 0;
+}
+
+extern "C" int gecm_dev_fill_twin(gecm_dev *dst, gecm_dev *src, const uint32_t *r2)
+{
+    HIPCHK(hipSetDevice(src->device));
+    if (dst->device != src->device || !src->stride || dst->stride != src->stride || dst->ncurves != src->ncurves ||
+        src->multi || dst->multi || !r2) {
+        g_err = "gecm_dev_fill_twin: the two contexts do not hold batches of one size on one device";
+        return -2;
+    }
+    HIPCHK(hipStreamSynchronize(dst->stream));    // the copies below run on src's stream
+    const int common = src->nl < dst->nl ? src->nl : dst->nl;
+    const size_t row = src->stride * sizeof(uint32_t);
+    gecm_modconst ms = modconst(src), md = modconst(dst);
+    md.r2 = r2;
+    // src's planes out of Montgomery form into its scratch planes, then limb plane by limb plane into dst's
+    auto lift = [&](const uint32_t *a, const uint32_t *b) -> int {
+        src->k1->from_mont(src->stream, &ms, a, b, src->dT0, src->dT1, src->stride);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemsetAsync(dst->dT0, 0, row * dst->nl, src->stream));
+        HIPCHK(hipMemsetAsync(dst->dT1, 0, row * dst->nl, src->stream));
+        HIPCHK(hipMemcpyAsync(dst->dT0, src->dT0, row * common, hipMemcpyDeviceToDevice, src->stream));
+        HIPCHK(hipMemcpyAsync(dst->dT1, src->dT1, row * common, hipMemcpyDeviceToDevice, src->stream));
+        HIPCHK(hipStreamSynchronize(src->stream));
+        return 0;
+    };
+    if (lift(src->dX, src->dZ)) return -1;
+    dst->k1->to_mont(dst->stream, &md, dst->dT0, dst->dT1, dst->dX, dst->dZ, dst->stride);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(dst->stream));
+    if (lift(src->dS, src->dS)) return -1;
+    // S twice: the kernel makes two planes at a time, the second copy goes to the scratch plane it does not read
+    dst->k1->to_mont(dst->stream, &md, dst->dT0, dst->dT0, dst->dS, dst->dT1, dst->stride);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(dst->stream));
     return 0;
 }
 

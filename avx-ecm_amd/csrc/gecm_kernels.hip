@@ -396,6 +396,138 @@ k_gcd_scan_multi(const uint32_t *__restrict__ V, uint32_t *__restrict__ G, uint3
 }
 #undef GECM_GCD_SCAN_BODY
 
+// ---------------------------------------------------------------- curve construction
+// The Suyama construction of one curve per lane (build_one_curve, ecm.c:1548-1803; on the host: suyama_pre and the tail
+// of gecm_mod_build_slice), in Montgomery arithmetic: out come the words the host path uploads, X = (u^3 / v^3) R,
+// Z = R, S = ((v-u)^3 (3u+v) / 16 u^3 v) R, canonical in [0, N), and one flag per curve.
+//   sigma R = mont(sigma, R^2) with sigma's 64 bits in three limbs: the multiply takes any operand below 1.675 K
+//   (gecm_field.hpp) and K >= R/32 >= 2^219, so sigma >= N needs no reduction first; the small constants 3, 4, 5, 16
+//   enter the same way.  u = sigma^2 - 5 leaves fe_sub lazy and is passed through one multiply by R mod N before it is
+//   subtracted itself (fe_sub wants a normalised subtrahend).  Every other operand of a multiply is a product
+//   (< 0.675 K), a sum of two (< 1.35 K) or a difference of two (< 1.675 K).
+// One inversion serves both quotients: (16u^3v * v^3)^-1 times v^3 and times 16u^3v.  Inverses are unique, so this is
+// what the reference's two mpz_invert calls return (ecm.c:1745, 1759) whenever both exist.  A lane whose shared
+// inversion fails inverts the two denominators one by one; a denominator without an inverse gets the reference's stale
+// operand in the inverse's place — 16 u^3 for (16u^3v)^-1, (v-u)^3(3u+v) for (v^3)^-1, see gecm_mod_build_slice — and
+// the curve is flagged.
+// Live set: u^3, 16u^3 and the numerator wait in the X, Z and S planes while the inversion runs, so two residues are
+// live across it.  The multiplies are the out-of-line ones of the stage-2 ladders (ModKOut) at every limb count: a
+// build is some thirty multiplies next to an inversion of about fifty multiplies' worth, run once per batch, and
+// inlined they added more to the build time of an object than the rest of its kernels.
+template <int NL>
+__device__ __forceinline__ void fe_small(Fe<NL> &r, uint32_t c)
+{
+#pragma unroll
+    for (int i = 0; i < NL; i++) r.v[i] = (i == 0) ? c : 0u;
+}
+
+// r = the inverse of the Montgomery-form value a, in Montgomery form (fe_inv_mont without its failure record)
+template <int NL>
+__device__ __forceinline__ bool build_invert(Fe<NL> &r, const Fe<NL> &a, const S2Const<NL> &k, const ModKOut<NL> &mm)
+{
+    Fe<NL> c, t, g;
+    fe_mul(c, a, k.one, mm);
+    fe_cond_sub_n(c, k.m);                        // canonical x R
+    const bool ok = fe_invert(t, g, c, k.m, k.inv_iters);
+    fe_mul(r, t, k.r3, mm);                       // (x R)^-1 R^3 / R = x^-1 R
+    return ok;
+}
+
+template <int NL>
+__device__ __forceinline__ void build_curve(uint64_t sg, uint32_t *__restrict__ X, uint32_t *__restrict__ Z,
+                                            uint32_t *__restrict__ S, uint32_t *__restrict__ flags, size_t stride,
+                                            uint32_t idx, const S2Const<NL> &k, const Fe<NL> &r2)
+{
+    static_assert(NL >= 3, "sigma takes three limbs");
+    const ModKOut<NL> mm{k.m};
+    Fe<NL> t, u, v, w, den, z3;
+    fe_small(t, (uint32_t)sg & GECM_LIMB_MASK);
+    t.v[1] = (uint32_t)(sg >> GECM_LIMB_BITS) & GECM_LIMB_MASK;
+    t.v[2] = (uint32_t)(sg >> (2 * GECM_LIMB_BITS));
+    fe_mul(w, t, r2, mm);                         // sigma R
+    fe_small(t, 4u);
+    fe_mul(t, t, r2, mm);
+    fe_mul(v, w, t, mm);                          // v = 4 sigma            ecm.c:1588-1589
+    fe_sqr(u, w, mm);
+    fe_small(t, 5u);
+    fe_mul(t, t, r2, mm);
+    fe_sub(u, u, t, mm);
+    fe_mul(u, u, k.one, mm);                      // u = sigma^2 - 5        ecm.c:1596-1598, normalised limbs
+    fe_sqr(t, u, mm);
+    fe_mul(w, t, u, mm);                          // x = u^3                ecm.c:1601-1603
+    fe_store(X, stride, idx, w);
+    fe_small(t, 16u);
+    fe_mul(t, t, r2, mm);
+    fe_mul(w, w, t, mm);                          // 16 u^3                 ecm.c:1718
+    fe_store(Z, stride, idx, w);
+    fe_mul(den, w, v, mm);                        // 16 u^3 v               ecm.c:1718-1720
+    fe_sqr(t, v, mm);
+    fe_mul(z3, t, v, mm);                         // z = v^3                ecm.c:1607-1609
+    fe_small(t, 3u);
+    fe_mul(t, t, r2, mm);
+    fe_mul(t, t, u, mm);
+    fe_add(t, t, v);                              // 3u + v                 ecm.c:1632-1634
+    fe_sub(w, v, u, mm);                          // v - u                  ecm.c:1615-1623
+    fe_sqr(u, w, mm);
+    fe_mul(w, u, w, mm);                          // (v-u)^3                ecm.c:1626-1629
+    fe_mul(w, w, t, mm);                          // a = (v-u)^3 (3u+v)     ecm.c:1637-1638
+    fe_store(S, stride, idx, w);
+
+    Fe<NL> di, zi;                                // (16u^3v)^-1 and (v^3)^-1, or what stands for them
+    uint32_t flag = 0;
+    fe_mul(t, den, z3, mm);
+    if (build_invert(w, t, k, mm)) {
+        fe_mul(di, w, z3, mm);
+        fe_mul(zi, w, den, mm);
+    } else {
+        if (!build_invert(di, den, k, mm)) {      // ecm.c:1745
+            fe_load(di, Z, stride, idx);
+            flag = 1;
+        }
+        if (!build_invert(zi, z3, k, mm)) {       // ecm.c:1759
+            fe_load(zi, S, stride, idx);
+            flag = 1;
+        }
+    }
+    fe_load(t, S, stride, idx);
+    fe_mul(t, t, di, mm);                         // b = a / 16u^3v         ecm.c:1752-1753
+    fe_mul(t, t, k.one, mm);
+    fe_cond_sub_n(t, k.m);
+    fe_store(S, stride, idx, t);
+    fe_load(t, X, stride, idx);
+    fe_mul(t, t, zi, mm);                         // X = u^3 / v^3, Z = 1   ecm.c:1759-1761
+    fe_mul(t, t, k.one, mm);
+    fe_cond_sub_n(t, k.m);
+    fe_store(X, stride, idx, t);
+    fe_store(Z, stride, idx, k.one);
+    flags[idx] = flag;
+}
+
+// (a macro for the reason given at GECM_STAGE1_BODY; the constants are in `k`, an S2Const<NL>, and R^2 mod N in `r2`)
+#define GECM_BUILD_BODY                                                         \
+    const uint32_t idx = blockIdx.x * 64u + threadIdx.x;                        \
+    build_curve<NL>(sigma[idx], X, Z, S, flags, stride, idx, k, r2);
+
+template <int NL>
+__global__ void __launch_bounds__(64, 2)
+k_build(const uint64_t *__restrict__ sigma, uint32_t *__restrict__ X, uint32_t *__restrict__ Z, uint32_t *__restrict__ S,
+        uint32_t *__restrict__ flags, size_t stride, S2Const<NL> k, Fe<NL> r2)
+{
+    GECM_BUILD_BODY
+}
+
+template <int NL>
+__global__ void __launch_bounds__(64, 2)
+k_build_multi(const uint64_t *__restrict__ sigma, uint32_t *__restrict__ X, uint32_t *__restrict__ Z,
+              uint32_t *__restrict__ S, uint32_t *__restrict__ flags, size_t stride, ModGroups<NL> groups)
+{
+    const GroupConst<NL> &c = mod_consts<GroupConst<NL>>(groups, blockIdx.x);
+    const S2Const<NL> &k = c.k;
+    const Fe<NL> &r2 = c.r2;
+    GECM_BUILD_BODY
+}
+#undef GECM_BUILD_BODY
+
 #endif
 #if GECM_HAS_PART(2)
 // ---------------------------------------------------------------- stage 2
@@ -617,6 +749,20 @@ static void launch_gcd_scan(void *stream, const gecm_modconst *mc, const uint32_
         hipLaunchKernelGGL(k_gcd_scan<GECM_NL>, grid, block, 0, (hipStream_t)stream, V, G, flags, stride, s2_const(mc));
 }
 
+static void launch_build(void *stream, const gecm_modconst *mc, const uint64_t *sigma, uint32_t *X, uint32_t *Z, uint32_t *S,
+                         uint32_t *flags, size_t stride)
+{
+    const dim3 grid((unsigned)(stride / 64)), block(64);
+    if (mc->groups) {
+        hipLaunchKernelGGL(k_build_multi<GECM_NL>, grid, block, 0, (hipStream_t)stream, sigma, X, Z, S, flags, stride,
+                           mod_groups(mc));
+        return;
+    }
+    Fe<GECM_NL> r2;
+    for (int i = 0; i < GECM_NL; i++) r2.v[i] = mc->r2[i];
+    hipLaunchKernelGGL(k_build<GECM_NL>, grid, block, 0, (hipStream_t)stream, sigma, X, Z, S, flags, stride, s2_const(mc), r2);
+}
+
 static void pack_group(const gecm_modconst *mc, void *out)
 {
     GroupConst<GECM_NL> c;
@@ -628,7 +774,7 @@ static void pack_group(const gecm_modconst *mc, void *out)
 extern "C" const gecm_kernels_p1 *CAT(CAT(gecm_kernels_, GECM_NL), _p1)(void)
 {
     static const gecm_kernels_p1 t = {launch_stage1, launch_canon, launch_from_mont, launch_to_mont, launch_l0, launch_l0_inv,
-                                      launch_gcd_scan, FPolicy<GECM_NL>::G, pack_group, sizeof(GroupConst<GECM_NL>),
+                                      launch_gcd_scan, launch_build, FPolicy<GECM_NL>::G, pack_group, sizeof(GroupConst<GECM_NL>),
                                       GECM_MANIFEST};
     return &t;
 }

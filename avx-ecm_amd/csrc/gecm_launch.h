@@ -75,7 +75,7 @@ struct gecm_s2_pair_launch {
     uint32_t slices;              /* accumulators per curve: each run of pairs is cut into this many slices */
 };
 
-/* Part 1: stage 1, canonical form, de-Montgomeryisation, L0 operators, factor scan. */
+/* Part 1: stage 1, canonical form, de-Montgomeryisation, L0 operators, factor scan, curve construction. */
 struct gecm_kernels_p1 {
     /* lanes per curve 1 or 2 (form: 0 = generic modulus, +1 = 2^k - 1, -1 = 2^k + 1, 2 = 2^k - c), or 8 (generic
      * moduli only; modq = device array of 80 words: limbs 0..39 of N then of K', zero padded, read per lane).  The
@@ -96,6 +96,11 @@ struct gecm_kernels_p1 {
                    const uint32_t *fix);
     void (*gcd_scan)(void *stream, const gecm_modconst *mc, const uint32_t *V, uint32_t *G, uint32_t *flags,
                      size_t stride);
+    /* the Suyama construction on the device: sigma[stride] (64-bit, device memory) -> X, Z, S of the batch, canonical, and
+     * flags[curve] = 1 where a denominator had no inverse (needs mc->r3, inv_iters and r2; a multi-modulus mc takes every
+     * block's from its group constants) */
+    void (*build)(void *stream, const gecm_modconst *mc, const uint64_t *sigma, uint32_t *X, uint32_t *Z, uint32_t *S,
+                  uint32_t *flags, size_t stride);
     int fform_generic_limbs;      /* limbs of a 2^k -+ c modulus that are not 2^28 - 1 */
     /* one modulus's constants (n, kp, one, r3, rho, inv_iters, r2 of mc) as the multi-modulus kernels read them from device
      * memory: group_bytes bytes at out */

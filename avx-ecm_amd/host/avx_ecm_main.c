@@ -236,6 +236,16 @@ static void *describe_ranges(void *arg)
     return NULL;
 }
 
+/* Where the driver's contexts build their curves: the files are byte for byte the same either way, so this is a matter
+ * of time alone (DESIGN.md §15 has the measurement behind the default).  GECM_CURVE_BUILD=host|device overrides it. */
+#define CLI_CURVE_BUILD GECM_BUILD_HOST
+static int set_curve_build(gecm_ctx *ctx)
+{
+    const char *s = getenv("GECM_CURVE_BUILD");
+    const int where = !s ? CLI_CURVE_BUILD : !strcmp(s, "device") ? GECM_BUILD_DEVICE : !strcmp(s, "host") ? GECM_BUILD_HOST : -1;
+    return gecm_set_curve_build(ctx, where);
+}
+
 /* ---- per-GPU jobs of a pass ----------------------------------------------------------------- */
 static int step_build(job_t *j)
 {
@@ -758,7 +768,8 @@ static int parse_run(run_t *R, int argc, char **argv)
 static int make_contexts(gecm_ctx **ctx, int n, int devices, const char *modulus, const char *report)
 {
     for (int g = 0; g < n; g++)
-        if (gecm_create(&ctx[g], g % devices, modulus, GECM_CLI_DIGITBITS) || (report && gecm_set_report_modulus(ctx[g], report))) {
+        if (gecm_create(&ctx[g], g % devices, modulus, GECM_CLI_DIGITBITS) || (report && gecm_set_report_modulus(ctx[g], report)) ||
+            set_curve_build(ctx[g])) {
             fprintf(stderr, "%s\n", gecm_last_error());
             return 2;
         }
@@ -1028,6 +1039,7 @@ static int multi_run(const char **ns, const char *const *logs, size_t n, run_t *
     gecm_ctx *mc = NULL;
     void *rx = NULL, *rz = NULL;
     int rc = gecm_create_multi(&mc, 0, ns, n, GECM_CLI_DIGITBITS);
+    if (rc == 0) rc = set_curve_build(mc);
     if (rc == 0 && rl) {
         gecm_config cfg;
         gecm_get_config(mc, &cfg);

@@ -106,6 +106,7 @@ struct gecm_ctx {
     uint64_t s2_ptadds, s2_numinv, s2_paired, s2_devinv;
     uint32_t s2_amin_last;
     int lanes_per_curve;     /* 0 = auto, 1, 2, 8, 32 (gecm_set_lanes_per_curve) */
+    int build_where, build_used;   /* GECM_BUILD_HOST / _DEVICE: asked for (gecm_set_curve_build), used by the last build */
     /* F-form stage 1 for N | 2^k - 1: a second device context working modulo Mw = 2^k - 1
      * (csrc/gecm_field.hpp); results are brought back modulo N by ff_settle() */
     gecm_dev *dev_f;
@@ -245,6 +246,7 @@ int gecm_create(gecm_ctx **out, int device, const char *n_str, int digitbits)
         return GECM_ERR_DEVICE;
     }
     gecm_dev_set_s2const(c->dev, c->mod.r3_28, c->mod.inv_iters);
+    gecm_dev_set_r2(c->dev, gecm_mod_r2(&c->mod));
     row_setup(c);
     ff_setup(c);
     *out = c;
@@ -578,9 +580,51 @@ static int upload_plain(gecm_ctx *c, const uint32_t *px, const uint32_t *pz)
     return rc ? GECM_ERR_DEVICE : GECM_OK;
 }
 
+/* The device build of the batch alloc_batch has just set up (gecm_set_curve_build): sigma[0 .. total) in device order,
+ * c->bad from the kernel's flags; live[p] == GECM_PAD marks a padding position of a multi-modulus batch, whose flag
+ * does not count.  Returns 1 if some curve is flagged, 0 if none, GECM_ERR_DEVICE with the error text set. */
+static int build_on_device(gecm_ctx *c, const uint64_t *sigma, size_t total, const uint32_t *live)
+{
+    uint32_t *flags = (uint32_t *)malloc(total * sizeof(uint32_t));
+    if (!flags) return GECM_ERR_NOMEM;
+    if (gecm_dev_build(c->dev, sigma, total, flags)) { free(flags); set_err("%s", gecm_dev_error()); return GECM_ERR_DEVICE; }
+    int any = 0;
+    for (size_t p = 0; p < total; p++)
+        if (flags[p] && !(live && live[p] == GECM_PAD)) c->bad[p] = (uint8_t)(any = 1);
+    free(flags);
+    c->last_ms = gecm_dev_last_build_ms(c->dev);
+    return any;
+}
+
+/* build_single with the construction on the device.  A special-form twin is filled from the main context on the
+ * device, after the caller's points (px, pz) are in: no big-integer work per curve on the host. */
+static int build_single_device(gecm_ctx *c, const uint64_t *sigma, size_t batch, const uint32_t *px, const uint32_t *pz)
+{
+    int rc = alloc_batch(c, batch);
+    if (rc) return rc;
+    memcpy(c->sigma, sigma, batch * sizeof(uint64_t));
+    const int built = build_on_device(c, sigma, batch, NULL);
+    if (built < 0) { free_batch(c); return built; }
+    rc = px ? gecm_dev_upload_plain(c->dev, px, pz, gecm_mod_r2(&c->mod)) : 0;
+    if (!rc && c->dev_f) {
+        uint32_t *r2 = (uint32_t *)calloc((size_t)c->ff_nl, 4);
+        if (!r2) { free_batch(c); return GECM_ERR_NOMEM; }
+        mpl_t v;
+        mpl_mulmod(&v, &c->ff_r_mod_m, &c->ff_r_mod_m, &c->ff_M);
+        mpl_to_limbs32(r2, 1, c->ff_nl, LIMB_BITS, &v);
+        rc = gecm_dev_fill_twin(c->dev_f, c->dev, r2);
+        free(r2);
+        c->ff_loaded = !rc;
+    }
+    if (rc) { set_err("%s", gecm_dev_error()); free_batch(c); return GECM_ERR_DEVICE; }
+    return built;
+}
+
 /* gecm_build_curves after its checks; px != NULL: gecm_resume_points, the points are px, pz (upload_plain) */
 static int build_single(gecm_ctx *c, const uint64_t *sigma, size_t batch, const uint32_t *px, const uint32_t *pz)
 {
+    c->build_used = c->build_where;
+    if (c->build_where == GECM_BUILD_DEVICE) return build_single_device(c, sigma, batch, px, pz);
     int rc = alloc_batch(c, batch);
     if (rc) return rc;
     memcpy(c->sigma, sigma, batch * sizeof(uint64_t));
@@ -620,6 +664,18 @@ int gecm_build_curves(gecm_ctx *c, const uint64_t *sigma, size_t batch)
         if (sigma[i] < 6) { set_err("gecm_build_curves: sigma[%zu] < 6", i); return GECM_ERR_ARG; }
     return build_single(c, sigma, batch, NULL, NULL);
 }
+
+int gecm_set_curve_build(gecm_ctx *c, int where)
+{
+    if (!c || (where != GECM_BUILD_HOST && where != GECM_BUILD_DEVICE)) {
+        set_err("gecm_set_curve_build: bad argument (GECM_BUILD_HOST or GECM_BUILD_DEVICE)");
+        return GECM_ERR_ARG;
+    }
+    c->build_where = where;
+    return GECM_OK;
+}
+
+int gecm_get_curve_build(const gecm_ctx *c) { return c ? c->build_used : GECM_ERR_ARG; }
 
 int gecm_upload_points(gecm_ctx *c, const void *X, const void *Z, const void *s, size_t batch)
 {
@@ -911,6 +967,24 @@ int gecm_download_points(gecm_ctx *c, void *X, void *Z)
             mpl_mulmod(&v, &v, &c->mod.int_to_ref, &c->mod.N);
             vec_put(&c->mod, dst[k], batch, i, &v);
         }
+    free(h);
+    return GECM_OK;
+}
+
+int gecm_download_s(gecm_ctx *c, void *s)
+{
+    if (c && c->multi) return multi_refuse("gecm_download_s");
+    if (!c || !s || c->batch == 0) return GECM_ERR_ARG;
+    const size_t batch = c->batch;
+    uint32_t *h = (uint32_t *)malloc((size_t)c->mod.nl * batch * 4);
+    if (!h) return GECM_ERR_NOMEM;
+    if (gecm_dev_download_s(c->dev, h)) { free(h); set_err("%s", gecm_dev_error()); return GECM_ERR_DEVICE; }
+    for (size_t i = 0; i < batch; i++) {
+        mpl_t v;
+        mpl_from_limbs32(&v, h + i, batch, c->mod.nl, LIMB_BITS);
+        mpl_mulmod(&v, &v, &c->mod.int_to_ref, &c->mod.N);
+        vec_put(&c->mod, s, batch, i, &v);
+    }
     free(h);
     return GECM_OK;
 }
@@ -1479,7 +1553,9 @@ static int build_multi(gecm_ctx *c, const char *who, const uint64_t *sigma, cons
     }
     /* the Suyama construction modulus by modulus: what gecm_build_curves does for its one */
     int anybad = 0;
-    for (size_t g = 0; g < ng && !rc; g++) {
+    c->build_used = c->build_where;
+    const int on_device = c->build_where == GECM_BUILD_DEVICE;
+    for (size_t g = 0; g < ng && !rc && !on_device; g++) {
         gecm_mod_build b = {&c->grp[g], c->sigma + goff[g], c->bad, total, goff[g], hX, hX + words, hX + 2 * words,
                             NULL, NULL, 0, NULL, NULL, NULL};
         const int built = run_slices(cnt[g], gecm_mod_build_slice, &b);
@@ -1488,12 +1564,21 @@ static int build_multi(gecm_ctx *c, const char *who, const uint64_t *sigma, cons
     }
     free(goff);
     free(cnt);
-    if (!rc && gecm_dev_upload(c->dev, hX, hX + words, hX + 2 * words)) rc = GECM_ERR_DEVICE;
+    if (!rc && !on_device && gecm_dev_upload(c->dev, hX, hX + words, hX + 2 * words)) rc = GECM_ERR_DEVICE;
     if (!rc) {
         const uint32_t *q = c->gconst;
         const size_t w = ng * (size_t)c->mod.nl;
         if (gecm_dev_set_groups(c->dev, (uint32_t)ng, q, q + w, q + 2 * w, q + 3 * w, q + 5 * w, q + 5 * w + ng, q + 4 * w, blocks))
             rc = GECM_ERR_DEVICE;
+    }
+    if (!rc && on_device) {              /* the kernel takes every block's modulus from the groups just set */
+        const int built = build_on_device(c, c->sigma, total, pos_user);
+        if (built < 0) {
+            free(hX); free(blocks);
+            free_batch(c);
+            return built;
+        }
+        anybad = built;
     }
     if (!rc && ux) {
         uint32_t *dx = hX, *dz = hX + words;                     /* the build's X, Z: dropped */

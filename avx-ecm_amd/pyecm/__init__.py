@@ -143,6 +143,11 @@ _sig("gecm_resume_points", c_int, c_void_p, ctypes.POINTER(c_u64), c_void_p, c_v
 _sig("gecm_resume_points_multi", c_int, c_void_p, ctypes.POINTER(c_u64), ctypes.POINTER(ctypes.c_uint32), c_void_p,
      c_void_p, c_size_t, c_u64)
 EXPORTS += ["gecm_parse_resume_line", "gecm_stage1_resume_range", "gecm_resume_points", "gecm_resume_points_multi"]
+_sig("gecm_set_curve_build", c_int, c_void_p, c_int)
+_sig("gecm_get_curve_build", c_int, c_void_p)
+_sig("gecm_download_s", c_int, c_void_p, c_void_p)
+EXPORTS += ["gecm_set_curve_build", "gecm_get_curve_build", "gecm_download_s"]
+CURVE_BUILDS = ("host", "device")      # GECM_BUILD_HOST, GECM_BUILD_DEVICE
 
 
 class GecmError(RuntimeError):
@@ -286,6 +291,23 @@ class Engine:
         arr = (c_u64 * len(sigmas))(*sigmas)
         self.batch = len(sigmas)
         return _chk(lib.gecm_build_curves(self._h, arr, len(sigmas)), "gecm_build_curves")
+
+    def set_curve_build(self, where):
+        """"host" (default) or "device": where the next build_curves / resume makes the curves; the batch holds the same
+        words either way"""
+        if where not in CURVE_BUILDS:
+            raise ValueError("set_curve_build: 'host' or 'device'")
+        _chk(lib.gecm_set_curve_build(self._h, CURVE_BUILDS.index(where)), "gecm_set_curve_build")
+
+    def curve_build(self):
+        """what the last build_curves / resume used"""
+        return CURVE_BUILDS[_chk(lib.gecm_get_curve_build(self._h), "gecm_get_curve_build")]
+
+    def download_s(self):
+        """s = (A+2)/4 of every curve, in the radix download_points uses"""
+        s = self.empty(self.batch)
+        _chk(lib.gecm_download_s(self._h, s), "gecm_download_s")
+        return self.unpack(s, self.batch)
 
     def upload_points(self, X, Z, s):
         self.batch = len(X)

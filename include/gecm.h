@@ -98,6 +98,21 @@ int gecm_build_curves(gecm_ctx *ctx, const uint64_t *sigma, size_t batch);
 /* Alternative phase 0: caller supplies P=(X,Z) and s as vec operands (reference layout and
  * Montgomery radix), e.g. the output of the reference's own build_one_curve.                 */
 int gecm_upload_points(gecm_ctx *ctx, const void *X, const void *Z, const void *s, size_t batch);
+/* Where the Suyama construction runs.  GECM_BUILD_HOST (the default): big-integer arithmetic on worker threads, then
+ * an upload.  GECM_BUILD_DEVICE: one kernel, a curve per lane, in the device's Montgomery arithmetic with its own
+ * inversion; the batch holds the same words either way, stale operands of a failed inversion and the
+ * return value 1 included, so every file and every result is the same.  Takes effect at the next gecm_build_curves,
+ * gecm_build_curves_multi, gecm_resume_points or gecm_resume_points_multi (there s comes from the device, X and Z from
+ * the caller); the argument checks of those calls stay on the host.  After a device build gecm_last_kernel_ms is the
+ * build kernel's time.  GECM_ERR_ARG for another value or a NULL context.
+ * gecm_get_curve_build: what the last build of the context used (GECM_BUILD_HOST before the first). */
+#define GECM_BUILD_HOST 0
+#define GECM_BUILD_DEVICE 1
+int gecm_set_curve_build(gecm_ctx *ctx, int where);
+int gecm_get_curve_build(const gecm_ctx *ctx);
+/* s = (A+2)/4 of the batch as a vec operand (reference layout and Montgomery radix, canonical): the counterpart of
+ * gecm_upload_points' third argument.  GECM_ERR_STATE on a multi-modulus context, like gecm_download_points. */
+int gecm_download_s(gecm_ctx *ctx, void *s);
 
 /* ---- input preparation (main.c:393-527) -----------------------------------------------------
  * What the reference's main() does to its first argument before any curve is built: evaluate the
