@@ -38,8 +38,8 @@ __device__ __forceinline__ void pt_dup(Pt<NL> &out, const Fe<NL> &s, const Fe<NL
     fe_mul(out.Z, t2, t3, m);  // Z = t*w
 }
 
-template <int NL>
-__device__ __forceinline__ void pt_sumdiff(Fe<NL> &s, Fe<NL> &d, const Pt<NL> &p, const ModK<NL> &m)
+template <int NL, class MOD>
+__device__ __forceinline__ void pt_sumdiff(Fe<NL> &s, Fe<NL> &d, const Pt<NL> &p, const MOD &m)
 {
     fe_add(s, p.X, p.Z);
     fe_sub(d, p.X, p.Z, m);
@@ -119,10 +119,10 @@ struct TapePolicy {
 // Register budget (<=256 VGPRs for 2 waves/SIMD): the difference point is only copied after
 // the first half of the addition, and s = (A+2)/4 is re-read from memory for each doubling
 // (doublings are ~10% of the steps) instead of occupying NL registers throughout.
-template <int NL, class MOD>
+template <int NL, class MOD, class CST>
 __device__ __forceinline__ void run_tape(const uint32_t *__restrict__ tape, uint32_t tape_len, Pt<NL> &A,
                                          const uint32_t *__restrict__ S, size_t stride, uint32_t idx,
-                                         const MOD &m, CStore<NL, TapePolicy<NL>::c_in_lds> &cst)
+                                         const MOD &m, CST &cst)
 {
     Pt<NL> B = A;
     cst.put(A);

@@ -106,6 +106,12 @@ void gecm_dev_set_multi(gecm_dev *d);
 int gecm_dev_set_groups(gecm_dev *d, uint32_t ngroups, const uint32_t *n, const uint32_t *kp, const uint32_t *one,
                         const uint32_t *r3, const uint32_t *rho, const uint32_t *inv_iters, const uint32_t *r2,
                         const uint32_t *block_group);
+/* Lane packing: after gecm_dev_set_groups, the modulus of every curve position (stride entries, the
+ * padding included; host memory).  From now on the launches of this batch run the per-lane kernels: a modulus per lane,
+ * one lane per curve (gecm_dev_stage1 refuses two), block_group unused.  NULL: back to one modulus per 64-curve block.
+ * A resize of the batch ends it.  gecm_dev_lane_packing_built: whether the per-lane kernels exist at this limb count. */
+int gecm_dev_set_curve_groups(gecm_dev *d, uint32_t ngroups, const uint32_t *curve_group);
+int gecm_dev_lane_packing_built(int nl);
 
 /* ---- stage 2 (csrc/gecm_stage2.hpp) ----
  * r3 = R^3 mod N (28-bit limbs); inv_iters = batches of 28 division steps of the device inversion (fe_invert). */

@@ -103,6 +103,10 @@ struct gecm_dev {
     uint32_t *dBlockGroup = nullptr;  // modulus of every 64-curve block of the batch
     size_t groups_cap = 0, blocks_cap = 0;
     bool have_groups = false;
+    // lane packing (gecm_dev_set_curve_groups): one modulus per curve position instead of one per block
+    uint32_t *dCurveGroup = nullptr;
+    size_t curve_group_cap = 0;
+    bool lane_packed = false;
     // curve construction on the device (gecm_dev_build)
     std::vector<uint32_t> r2;         // R^2 mod N of a single-modulus context (gecm_dev_set_r2)
     uint64_t *dSigma = nullptr;
@@ -154,6 +158,7 @@ static gecm_modconst modconst(const gecm_dev *d)
     mc.groups = d->multi ? d->dGroups : nullptr;
     mc.block_group = d->multi ? d->dBlockGroup : nullptr;
     mc.r2 = nullptr;
+    mc.curve_group = (d->multi && d->lane_packed) ? d->dCurveGroup : nullptr;
     return mc;
 }
 
@@ -245,6 +250,7 @@ extern "C" void gecm_dev_close(gecm_dev *d)
     (void)hipFree(d->dTape);
     (void)hipFree(d->dGroups);
     (void)hipFree(d->dBlockGroup);
+    (void)hipFree(d->dCurveGroup);
     (void)hipFree(d->dSigma);
     if (d->ev0) (void)hipEventDestroy(d->ev0);
     if (d->ev1) (void)hipEventDestroy(d->ev1);
@@ -290,6 +296,7 @@ extern "C" int gecm_dev_resize(gecm_dev *d, size_t ncurves)
     }
     d->ncurves = ncurves;
     d->have_groups = false;
+    d->lane_packed = false;
     return 0;
 }
 
@@ -564,9 +571,16 @@ extern "C" int gecm_dev_stage1(gecm_dev *d, int lanes_per_curve)
         g_err = "gecm_dev_stage1: the moduli of the batch are not set (gecm_dev_set_groups)";
         return -2;
     }
-    const int lanes = lanes_per_curve ? lanes_per_curve : gecm_dev_auto_lanes(d);
+    int lanes = lanes_per_curve ? lanes_per_curve : gecm_dev_auto_lanes(d);
     char nm[96];   // the kernel's name as rocprofv3 prints it
-    if (d->multi) {
+    if (d->multi && d->lane_packed) {
+        if (lanes_per_curve > 1) {
+            g_err = "gecm_dev_stage1: a lane-packed multi-modulus batch runs with one lane per curve";
+            return -2;
+        }
+        lanes = 1;
+        snprintf(nm, sizeof nm, "k_stage1_lane<%d>", d->nl);
+    } else if (d->multi) {
         if (lanes != 1 && lanes != 2) {
             g_err = "gecm_dev_stage1: a multi-modulus batch runs with 1 or 2 lanes per curve";
             return -2;
@@ -756,6 +770,43 @@ extern "C" int gecm_dev_set_groups(gecm_dev *d, uint32_t ngroups, const uint32_t
     HIPCHK(hipMemcpyAsync(d->dBlockGroup, block_group, blocks * sizeof(uint32_t), hipMemcpyHostToDevice, d->stream));
     HIPCHK(hipStreamSynchronize(d->stream));
     d->have_groups = true;
+    return 0;
+}
+
+extern "C" int gecm_dev_lane_packing_built(int nl)
+{
+    const auto *kt = kernels_for(nl);
+    return kt ? kt->p1()->has_lane : 0;
+}
+
+extern "C" int gecm_dev_set_curve_groups(gecm_dev *d, uint32_t ngroups, const uint32_t *curve_group)
+{
+    HIPCHK(hipSetDevice(d->device));
+    if (!curve_group) {
+        d->lane_packed = false;
+        return 0;
+    }
+    if (!d->multi || !d->have_groups || !d->stride || !d->k1->has_lane) {
+        g_err = "gecm_dev_set_curve_groups: needs a multi-modulus context with its moduli set (gecm_dev_set_groups) at a "
+                "limb count the per-lane kernels are built for";
+        return -2;
+    }
+    for (size_t p = 0; p < d->stride; p++)
+        if (curve_group[p] >= ngroups) {
+            g_err = "gecm_dev_set_curve_groups: position " + std::to_string(p) + " names modulus " + std::to_string(curve_group[p]);
+            return -2;
+        }
+    if (d->stride > d->curve_group_cap) {
+        (void)hipFree(d->dCurveGroup);
+        d->dCurveGroup = nullptr;
+        d->curve_group_cap = 0;
+        HIPCHK(hipMalloc(&d->dCurveGroup, d->stride * sizeof(uint32_t)));
+        d->curve_group_cap = d->stride;
+    }
+    // synchronous, as in gecm_dev_set_groups
+    HIPCHK(hipMemcpyAsync(d->dCurveGroup, curve_group, d->stride * sizeof(uint32_t), hipMemcpyHostToDevice, d->stream));
+    HIPCHK(hipStreamSynchronize(d->stream));
+    d->lane_packed = true;
     return 0;
 }
 

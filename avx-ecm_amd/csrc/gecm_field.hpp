@@ -539,6 +539,115 @@ __device__ __forceinline__ void fe_cond_sub_n(Fe<NL> &r, const ModK<NL> &m)
     if (!borrow) r = t;
 }
 
+// ---- a modulus per lane (lane-packed multi-modulus batches) --------------------
+// Every lane of a wavefront works modulo its own N.  N and rho sit in vector registers; K' is read only by fe_sub and
+// waits in LDS, [limb][lane] (conflict-free: lane l hits bank l).  Same REDC, same digits, same bounds as ModK: the q*N
+// half of a column takes its second factor from a register of the lane (mad_chain_v) instead of an SGPR.
+template <int NL>
+struct ModV {
+    uint32_t n[NL];       // this lane's N, 28-bit limbs
+    const uint32_t *kp;   // this lane's K' column in LDS: limb i at kp[i * 64]
+    uint32_t rho;         // -N^-1 mod 2^28 of this lane's N
+};
+
+// a residue among this lane's constants in global memory (R mod N, R^3 mod N, R^2 mod N): read where it is used, so
+// that it holds no registers across the ladders
+template <int NL>
+struct FeG {
+    const uint32_t *p;
+};
+
+template <int NL>
+__device__ __forceinline__ void fe_get(Fe<NL> &r, const FeG<NL> &g)
+{
+#pragma unroll
+    for (int i = 0; i < NL; i++) r.v[i] = g.p[i];
+}
+
+template <int NL>
+__device__ __forceinline__ void fe_mul(Fe<NL> &r, const Fe<NL> &a, const Fe<NL> &b, const ModV<NL> &m)
+{
+    uint32_t q[NL];
+    Fe<NL> o;
+    uint64_t acc = 0;
+    static_for<0, NL>([&](auto ic) {
+        constexpr int c = decltype(ic)::value;
+        col_vv<c, 0, c + 1>(acc, a.v, b.v);
+        col_vv<c, 0, c>(acc, q, m.n);
+        q[c] = ((uint32_t)acc * m.rho) & GECM_LIMB_MASK;
+        col_vv<c, c, c + 1>(acc, q, m.n);
+        acc >>= GECM_LIMB_BITS;
+    });
+    static_for<NL, 2 * NL>([&](auto ic) {
+        constexpr int c = decltype(ic)::value;
+        col_vv<c, c - NL + 1, NL>(acc, a.v, b.v);
+        col_vv<c, c - NL + 1, NL>(acc, q, m.n);
+        o.v[c - NL] = (c == 2 * NL - 1) ? (uint32_t)acc : ((uint32_t)acc & GECM_LIMB_MASK);
+        acc >>= GECM_LIMB_BITS;
+    });
+    r = o;
+}
+
+template <int NL>
+__device__ __forceinline__ void fe_sqr(Fe<NL> &r, const Fe<NL> &a, const ModV<NL> &m)
+{
+    uint32_t q[NL];
+    uint32_t a2[NL];
+    Fe<NL> o;
+#pragma unroll
+    for (int i = 0; i < NL; i++) a2[i] = a.v[i] << 1;
+    uint64_t acc = 0;
+    static_for<0, NL>([&](auto ic) {
+        constexpr int c = decltype(ic)::value;
+        col_vv<c, 0, (c + 1) / 2>(acc, a.v, a2);
+        if constexpr ((c & 1) == 0) col_vv<c, c / 2, c / 2 + 1>(acc, a.v, a.v);
+        col_vv<c, 0, c>(acc, q, m.n);
+        q[c] = ((uint32_t)acc * m.rho) & GECM_LIMB_MASK;
+        col_vv<c, c, c + 1>(acc, q, m.n);
+        acc >>= GECM_LIMB_BITS;
+    });
+    static_for<NL, 2 * NL>([&](auto ic) {
+        constexpr int c = decltype(ic)::value;
+        col_vv<c, c - NL + 1, (c + 1) / 2>(acc, a.v, a2);
+        if constexpr ((c & 1) == 0 && c / 2 < NL) col_vv<c, c / 2, c / 2 + 1>(acc, a.v, a.v);
+        col_vv<c, c - NL + 1, NL>(acc, q, m.n);
+        o.v[c - NL] = (c == 2 * NL - 1) ? (uint32_t)acc : ((uint32_t)acc & GECM_LIMB_MASK);
+        acc >>= GECM_LIMB_BITS;
+    });
+    r = o;
+}
+
+template <int NL>
+__device__ __forceinline__ void fe_mul(Fe<NL> &r, const Fe<NL> &a, const FeG<NL> &b, const ModV<NL> &m)
+{
+    Fe<NL> t;
+    fe_get(t, b);
+    fe_mul(r, a, t, m);
+}
+
+template <int NL>
+__device__ __forceinline__ void fe_sub(Fe<NL> &r, const Fe<NL> &a, const Fe<NL> &b, const ModV<NL> &m)
+{
+    static_assert(!LazyPolicy<NL>::norm_sub, "the per-lane kernels are built for limb counts without renormalisation");
+#pragma unroll
+    for (int i = 0; i < NL; i++) r.v[i] = a.v[i] + m.kp[i * 64] - b.v[i];
+}
+
+template <int NL>
+__device__ __forceinline__ void fe_cond_sub_n(Fe<NL> &r, const ModV<NL> &m)
+{
+    Fe<NL> t;
+    uint32_t borrow = 0;
+#pragma unroll
+    for (int i = 0; i < NL; i++) {
+        uint32_t d = r.v[i] - m.n[i] - borrow;
+        borrow = (d >> 31) & 1u;
+        t.v[i] = (i == NL - 1) ? d : (d & GECM_LIMB_MASK);
+    }
+#pragma unroll
+    for (int i = 0; i < NL; i++) r.v[i] = borrow ? r.v[i] : t.v[i];
+}
+
 // x*R -> x canonical: the reference's "vecmulmod(P->X, one)" de-Montgomeryisation
 // (ecm.c:1327-1331) followed by the reduction to [0,N) every reference op performs.
 template <int NL, class MOD>
@@ -584,4 +693,21 @@ __device__ __forceinline__ void fe_store(uint32_t *__restrict__ base, size_t str
         char *row = (char *)(base + (size_t)i * stride);
         *(uint32_t *)(row + boff) = r.v[i];
     }
+}
+
+// the same with the second operand / the stored value among the lane's constants in global memory (FeG)
+template <int NL, class MOD>
+__device__ __forceinline__ void fe_canonical_mont(Fe<NL> &r, const Fe<NL> &a, const FeG<NL> &rmodn, const MOD &m)
+{
+    Fe<NL> t;
+    fe_get(t, rmodn);
+    fe_canonical_mont(r, a, t, m);
+}
+
+template <int NL>
+__device__ __forceinline__ void fe_store(uint32_t *__restrict__ base, size_t stride, uint32_t idx, const FeG<NL> &g)
+{
+    Fe<NL> t;
+    fe_get(t, g);
+    fe_store(base, stride, idx, t);
 }

@@ -64,6 +64,47 @@ __device__ __forceinline__ const A &mod_consts(const ModGroups<NL> &g, uint32_t 
     const uint32_t grp = ((c_u32 *)g.block_group)[block];
     return *(const A *)(const GroupConst<NL> *)((c_grp *)g.groups + grp);
 }
+
+// Lane-packed multi-modulus launch (one modulus per lane): the same constants array, and the modulus of
+// every curve.  Built for the limb counts up to GECM_LANE_MAXNL; lane_consts() gives a lane the constants of its own
+// curve: N and rho into registers, K' into the lane's LDS column `kp_col` (word limb*64), the residues R, R^3 and R^2
+// mod N left in global memory behind a pointer (FeG).
+#define GECM_LANE_MAXNL 15
+#define GECM_HAS_LANE (GECM_NL <= GECM_LANE_MAXNL)
+template <int NL>
+struct LaneGroups {
+    const GroupConst<NL> *groups; // read-only for the whole launch
+    const uint32_t *curve_group;  // modulus of curve position p
+};
+
+template <int NL>
+struct LaneConst : S2ConstV<NL> {
+    FeG<NL> r2;
+};
+
+template <int NL>
+__device__ __forceinline__ void lane_consts(LaneConst<NL> &k, const LaneGroups<NL> &g, uint32_t idx, uint32_t *kp_col)
+{
+    const uint32_t *gp = (const uint32_t *)(g.groups + g.curve_group[idx]);
+    const uint32_t *mp = gp + offsetof(GroupConst<NL>, k.m) / 4;
+#pragma unroll
+    for (int i = 0; i < NL; i++) {
+        k.m.n[i] = mp[offsetof(ModK<NL>, n) / 4 + i];
+        kp_col[i * 64] = mp[offsetof(ModK<NL>, kp) / 4 + i];
+    }
+    k.m.kp = kp_col;
+    k.m.rho = mp[offsetof(ModK<NL>, rho) / 4];
+    k.one.p = gp + offsetof(GroupConst<NL>, k.one) / 4;
+    k.r3.p = gp + offsetof(GroupConst<NL>, k.r3) / 4;
+    k.inv_iters = gp[offsetof(GroupConst<NL>, k.inv_iters) / 4];
+    k.r2.p = gp + offsetof(GroupConst<NL>, r2) / 4;
+}
+// every lane kernel starts with this: `k` = the constants of curve position idx
+#define GECM_LANE_CONSTS                                                        \
+    __shared__ uint32_t lds_kp[NL * 64];                                        \
+    LaneConst<NL> k;                                                            \
+    lane_consts(k, g, idx, lds_kp + threadIdx.x);
+
 #if GECM_HAS_PART(1)
 // ---------------------------------------------------------------- stage 1
 // One curve per lane.  64-thread blocks (one wave): a CU holds 8 of them at 2 waves/SIMD, the
@@ -105,6 +146,31 @@ k_stage1_multi(const uint32_t *__restrict__ tape, uint32_t tape_len, uint32_t *_
     GECM_STAGE1_BODY
 }
 #undef GECM_STAGE1_BODY
+
+#if GECM_HAS_LANE
+// One curve per lane and a modulus per lane.  The third PRAC point waits in LDS at every limb count (the column the
+// C store of TapePolicy uses above its threshold): the registers it leaves hold the lane's N.
+template <int NL>
+__global__ void __launch_bounds__(64, 2)
+k_stage1_lane(const uint32_t *__restrict__ tape, uint32_t tape_len, uint32_t *__restrict__ X,
+              uint32_t *__restrict__ Z, const uint32_t *__restrict__ S, size_t stride, LaneGroups<NL> g)
+{
+    const uint32_t idx = blockIdx.x * 64u + threadIdx.x;
+    GECM_LANE_CONSTS
+    Pt<NL> P;
+    fe_load(P.X, X, stride, idx);
+    fe_load(P.Z, Z, stride, idx);
+    __shared__ uint32_t lds_c[2 * NL * 64];
+    CStore<NL, true> cst;
+    cst.lds = lds_c + threadIdx.x;
+    run_tape<NL>(tape, tape_len, P, S, stride, idx, k.m, cst);
+    Fe<NL> ox, oz;
+    fe_canonical_mont(ox, P.X, k.one, k.m);
+    fe_canonical_mont(oz, P.Z, k.one, k.m);
+    fe_store(X, stride, idx, ox);
+    fe_store(Z, stride, idx, oz);
+}
+#endif
 
 // Stage 1 modulo Mw = 2^k - 1 (gecm_field.hpp, "F-form"): the same interpreter, the REDC half of every
 // multiply replaced by the shift-and-subtract form.  Used by the host for N | 2^k - 1.
@@ -270,6 +336,24 @@ k_from_mont_multi(const uint32_t *__restrict__ X, const uint32_t *__restrict__ Z
 }
 #undef GECM_FROM_MONT_BODY
 
+#if GECM_HAS_LANE
+template <int NL>
+__global__ void __launch_bounds__(64)
+k_from_mont_lane(const uint32_t *__restrict__ X, const uint32_t *__restrict__ Z, uint32_t *__restrict__ ox,
+                 uint32_t *__restrict__ oz, size_t stride, LaneGroups<NL> g)
+{
+    const uint32_t idx = blockIdx.x * 64u + threadIdx.x;
+    GECM_LANE_CONSTS
+    Fe<NL> x, z, r;
+    fe_load(x, X, stride, idx);
+    fe_load(z, Z, stride, idx);
+    fe_from_mont_canonical(r, x, k.m);
+    fe_store(ox, stride, idx, r);
+    fe_from_mont_canonical(r, z, k.m);
+    fe_store(oz, stride, idx, r);
+}
+#endif
+
 // The inverse: canonical plain residues x, z in [0, N) -> X = x R mod N, Z = z R mod N, canonical, by one multiply with
 // R^2 mod N each (x R^2 / R < N^2/R + N < 2N, then one conditional subtract).  The constants are in `a`, a ModArgs<NL>,
 // and R^2 mod N in `r2`.
@@ -304,6 +388,26 @@ k_to_mont_multi(const uint32_t *__restrict__ ix, const uint32_t *__restrict__ iz
     GECM_TO_MONT_BODY
 }
 #undef GECM_TO_MONT_BODY
+
+#if GECM_HAS_LANE
+template <int NL>
+__global__ void __launch_bounds__(64)
+k_to_mont_lane(const uint32_t *__restrict__ ix, const uint32_t *__restrict__ iz, uint32_t *__restrict__ X,
+               uint32_t *__restrict__ Z, size_t stride, LaneGroups<NL> g)
+{
+    const uint32_t idx = blockIdx.x * 64u + threadIdx.x;
+    GECM_LANE_CONSTS
+    Fe<NL> x, z, r;
+    fe_load(x, ix, stride, idx);
+    fe_load(z, iz, stride, idx);
+    fe_mul(r, x, k.r2, k.m);
+    fe_cond_sub_n(r, k.m);
+    fe_store(X, stride, idx, r);
+    fe_mul(r, z, k.r2, k.m);
+    fe_cond_sub_n(r, k.m);
+    fe_store(Z, stride, idx, r);
+}
+#endif
 
 // ---------------------------------------------------------------- L0 test-level operators
 template <int NL>
@@ -394,6 +498,29 @@ k_gcd_scan_multi(const uint32_t *__restrict__ V, uint32_t *__restrict__ G, uint3
     const S2Const<NL> &k = mod_consts<S2Const<NL>>(groups, blockIdx.x);
     GECM_GCD_SCAN_BODY
 }
+
+#if GECM_HAS_LANE
+template <int NL>
+__global__ void __launch_bounds__(64, 2)
+k_gcd_scan_lane(const uint32_t *__restrict__ V, uint32_t *__restrict__ G, uint32_t *__restrict__ flags, size_t stride,
+                LaneGroups<NL> g)
+{
+    const uint32_t idx = blockIdx.x * 64u + threadIdx.x;
+    GECM_LANE_CONSTS
+    Fe<NL> v, c, t, gc;
+    fe_load(v, V, stride, idx);
+    fe_canonical_mont(c, v, k.one, k.m);
+    fe_invert(t, gc, c, k.m, k.inv_iters);
+    bool is_one = gc.v[0] == 1u, is_n = true;
+#pragma unroll
+    for (int i = 0; i < NL; i++) {
+        if (i > 0) is_one = is_one && gc.v[i] == 0;
+        is_n = is_n && gc.v[i] == k.m.n[i];
+    }
+    fe_store(G, stride, idx, gc);
+    flags[idx] = (!is_one && !is_n) ? 1u : 0u;
+}
+#endif
 #undef GECM_GCD_SCAN_BODY
 
 // ---------------------------------------------------------------- curve construction
@@ -608,6 +735,46 @@ __global__ void __launch_bounds__(64, 2) k_s2_merge_multi(uint32_t *acc, uint32_
     s2_merge<NL>(acc, slices, stride, init_only != 0, mod_consts<S2Const<NL>>(g, blockIdx.x), blockIdx.x * 64u + threadIdx.x);
 }
 
+#if GECM_HAS_LANE
+// lane-packed multi-modulus contexts: the same four kernels with a modulus per lane (K = 1)
+template <int NL>
+__global__ void __launch_bounds__(64, 2) k_s2_init_lane(S2InitArgs a, LaneGroups<NL> g)
+{
+    const uint32_t idx = blockIdx.x * 64u + threadIdx.x;
+    GECM_LANE_CONSTS
+    s2_init<NL>(a, k, idx);
+}
+
+template <int NL>
+__global__ void __launch_bounds__(64, 2) k_s2_gen_lane(S2PairArgs a, uint32_t first_abs, uint32_t n, LaneGroups<NL> g)
+{
+    const uint32_t idx = blockIdx.x * 64u + threadIdx.x;
+    GECM_LANE_CONSTS
+    giant_chunk<NL>(a, first_abs, n, first_abs == 0, k, idx);
+}
+
+template <int NL>
+__global__ void __launch_bounds__(64, 2) k_s2_pairs_lane(S2PairArgs a, uint32_t first, uint32_t count, LaneGroups<NL> g)
+{
+    const uint32_t per = (count + gridDim.y - 1) / gridDim.y;
+    const uint32_t off = blockIdx.y * per;
+    if (off >= count) return;
+    const uint32_t n = count - off < per ? count - off : per;
+    const uint32_t idx = blockIdx.x * 64u + threadIdx.x;
+    GECM_LANE_CONSTS
+    s2_pairs<NL>(a, first + off, n, k, idx, a.acc + (size_t)blockIdx.y * NL * a.stride);
+}
+
+template <int NL>
+__global__ void __launch_bounds__(64, 2) k_s2_merge_lane(uint32_t *acc, uint32_t slices, size_t stride, int init_only,
+                                                         LaneGroups<NL> g)
+{
+    const uint32_t idx = blockIdx.x * 64u + threadIdx.x;
+    GECM_LANE_CONSTS
+    s2_merge<NL>(acc, slices, stride, init_only != 0, k, idx);
+}
+#endif
+
 #endif
 // ---------------------------------------------------------------- launchers (gecm_launch.h)
 // ModArgs, ModArgsS or S2Const from the host's copy of the modulus constants
@@ -637,6 +804,13 @@ static ModGroups<GECM_NL> mod_groups(const gecm_modconst *mc)
     return ModGroups<GECM_NL>{(const GroupConst<GECM_NL> *)mc->groups, mc->block_group};
 }
 
+#if GECM_HAS_LANE
+static LaneGroups<GECM_NL> lane_groups(const gecm_modconst *mc)
+{
+    return LaneGroups<GECM_NL>{(const GroupConst<GECM_NL> *)mc->groups, mc->curve_group};
+}
+#endif
+
 #define CAT_(a, b) a##b
 #define CAT(a, b) CAT_(a, b)
 
@@ -653,6 +827,12 @@ static void launch_stage1_mod(hipStream_t stream, const gecm_modconst *mc, const
 {
     const dim3 grid((unsigned)(stride / (lanes == 2 ? 32 : 64))), block(64);
     if constexpr (std::is_same<MOD, ModK<GECM_NL>>::value) {
+#if GECM_HAS_LANE
+        if (mc->groups && mc->curve_group) {      // lane packing: one lane per curve (gecm_dev_stage1 refuses two)
+            hipLaunchKernelGGL(k_stage1_lane<GECM_NL>, grid, block, 0, stream, tape, tape_len, X, Z, S, stride, lane_groups(mc));
+            return;
+        }
+#endif
         if (mc->groups) {
             const auto g = mod_groups(mc);
             if (lanes == 2) hipLaunchKernelGGL(k_stage1_pair_multi<GECM_NL>, grid, block, 0, stream, tape, tape_len, X, Z, S, stride, g);
@@ -697,6 +877,13 @@ static void launch_from_mont(void *stream, const gecm_modconst *mc, const uint32
                              uint32_t *oz, size_t stride)
 {
     const dim3 grid((unsigned)(stride / 64)), block(64);
+#if GECM_HAS_LANE
+    if (mc->groups && mc->curve_group) {
+        hipLaunchKernelGGL(k_from_mont_lane<GECM_NL>, grid, block, 0, (hipStream_t)stream, X, Z, ox, oz, stride,
+                           lane_groups(mc));
+        return;
+    }
+#endif
     if (mc->groups)
         hipLaunchKernelGGL(k_from_mont_multi<GECM_NL>, grid, block, 0, (hipStream_t)stream, X, Z, ox, oz, stride,
                            mod_groups(mc));
@@ -709,6 +896,13 @@ static void launch_to_mont(void *stream, const gecm_modconst *mc, const uint32_t
                            uint32_t *Z, size_t stride)
 {
     const dim3 grid((unsigned)(stride / 64)), block(64);
+#if GECM_HAS_LANE
+    if (mc->groups && mc->curve_group) {
+        hipLaunchKernelGGL(k_to_mont_lane<GECM_NL>, grid, block, 0, (hipStream_t)stream, ix, iz, X, Z, stride,
+                           lane_groups(mc));
+        return;
+    }
+#endif
     if (mc->groups) {
         hipLaunchKernelGGL(k_to_mont_multi<GECM_NL>, grid, block, 0, (hipStream_t)stream, ix, iz, X, Z, stride,
                            mod_groups(mc));
@@ -742,6 +936,13 @@ static void launch_gcd_scan(void *stream, const gecm_modconst *mc, const uint32_
                             size_t stride)
 {
     const dim3 grid((unsigned)(stride / 64)), block(64);
+#if GECM_HAS_LANE
+    if (mc->groups && mc->curve_group) {
+        hipLaunchKernelGGL(k_gcd_scan_lane<GECM_NL>, grid, block, 0, (hipStream_t)stream, V, G, flags, stride,
+                           lane_groups(mc));
+        return;
+    }
+#endif
     if (mc->groups)
         hipLaunchKernelGGL(k_gcd_scan_multi<GECM_NL>, grid, block, 0, (hipStream_t)stream, V, G, flags, stride,
                            mod_groups(mc));
@@ -775,7 +976,7 @@ extern "C" const gecm_kernels_p1 *CAT(CAT(gecm_kernels_, GECM_NL), _p1)(void)
 {
     static const gecm_kernels_p1 t = {launch_stage1, launch_canon, launch_from_mont, launch_to_mont, launch_l0, launch_l0_inv,
                                       launch_gcd_scan, launch_build, FPolicy<GECM_NL>::G, pack_group, sizeof(GroupConst<GECM_NL>),
-                                      GECM_MANIFEST};
+                                      GECM_MANIFEST, GECM_HAS_LANE};
     return &t;
 }
 #endif
@@ -785,6 +986,15 @@ static void launch_s2_init(void *stream, const gecm_modconst *mc, const gecm_s2_
     const S2InitArgs &a = h->a;
     const S2Const<GECM_NL> k = s2_const(mc);
     const dim3 grid((unsigned)(a.stride / 64)), block(64);
+#if GECM_HAS_LANE
+    if (mc->groups && mc->curve_group) {
+        const auto g = lane_groups(mc);
+        hipLaunchKernelGGL(k_s2_init_lane<GECM_NL>, grid, block, 0, (hipStream_t)stream, a, g);
+        if (h->slices > 1)
+            hipLaunchKernelGGL(k_s2_merge_lane<GECM_NL>, grid, block, 0, (hipStream_t)stream, a.acc, h->slices, a.stride, 1, g);
+        return;
+    }
+#endif
     if (mc->groups) {                 // K = 1 (gecm_dev_s2_init)
         const auto g = mod_groups(mc);
         hipLaunchKernelGGL(k_s2_init_multi<GECM_NL>, grid, block, 0, (hipStream_t)stream, a, g);
@@ -814,11 +1024,22 @@ static void launch_s2_pair(void *stream, const gecm_modconst *mc, const gecm_s2_
     const dim3 kgrid((unsigned)(a.stride / 64 * (a.K ? a.K : 1)));
     const ModGroups<GECM_NL> g = mc->groups ? mod_groups(mc) : ModGroups<GECM_NL>{};   // multi-modulus: K = 1
     uint32_t generated = 0, i = 0, kprev = 1;
+    // lane packing: the same launch sequence over the per-lane kernels (built up to GECM_LANE_MAXNL limbs)
+#if GECM_HAS_LANE
+    const bool lane = mc->groups && mc->curve_group;
+    const LaneGroups<GECM_NL> lg = lane ? lane_groups(mc) : LaneGroups<GECM_NL>{};
+#define GECM_LANE_LAUNCH(...) hipLaunchKernelGGL(__VA_ARGS__)
+#else
+    const bool lane = false;
+#define GECM_LANE_LAUNCH(...) (void)0
+#endif
     while (i < a.nsteps) {
         if (h->host_steps[2 * i] == S2_STEP_GEN) {
             const uint32_t word = h->host_steps[2 * i + 1];
             const uint32_t n = word & 0x7fffffffu;
-            if (mc->groups)
+            if (lane)
+                GECM_LANE_LAUNCH(k_s2_gen_lane<GECM_NL>, grid, block, 0, (hipStream_t)stream, a, generated, n, lg);
+            else if (mc->groups)
                 hipLaunchKernelGGL(k_s2_gen_multi<GECM_NL>, grid, block, 0, (hipStream_t)stream, a, generated, n, g);
             else if (a.K > 1 && !(word & 0x80000000u)) {
                 hipLaunchKernelGGL(k_s2_gen_k<GECM_NL>, kgrid, block, 0, (hipStream_t)stream, a, generated, n, k);
@@ -832,7 +1053,9 @@ static void launch_s2_pair(void *stream, const gecm_modconst *mc, const gecm_s2_
         } else {
             uint32_t j = i;
             while (j < a.nsteps && h->host_steps[2 * j] != S2_STEP_GEN) j++;
-            if (mc->groups)
+            if (lane)
+                GECM_LANE_LAUNCH(k_s2_pairs_lane<GECM_NL>, pgrid, block, 0, (hipStream_t)stream, a, i, j - i, lg);
+            else if (mc->groups)
                 hipLaunchKernelGGL(k_s2_pairs_multi<GECM_NL>, pgrid, block, 0, (hipStream_t)stream, a, i, j - i, g);
             else
                 hipLaunchKernelGGL(k_s2_pairs<GECM_NL>, pgrid, block, 0, (hipStream_t)stream, a, i, j - i, k);
@@ -840,11 +1063,14 @@ static void launch_s2_pair(void *stream, const gecm_modconst *mc, const gecm_s2_
         }
     }
     if (h->slices > 1) {
-        if (mc->groups)
+        if (lane)
+            GECM_LANE_LAUNCH(k_s2_merge_lane<GECM_NL>, grid, block, 0, (hipStream_t)stream, a.acc, h->slices, a.stride, 0, lg);
+        else if (mc->groups)
             hipLaunchKernelGGL(k_s2_merge_multi<GECM_NL>, grid, block, 0, (hipStream_t)stream, a.acc, h->slices, a.stride, 0, g);
         else
             hipLaunchKernelGGL(k_s2_merge<GECM_NL>, grid, block, 0, (hipStream_t)stream, a.acc, h->slices, a.stride, 0, k);
     }
+#undef GECM_LANE_LAUNCH
 }
 
 extern "C" const gecm_kernels_p2 *CAT(CAT(gecm_kernels_, GECM_NL), _p2)(void)

@@ -20,6 +20,10 @@ typedef struct {
     const void *groups;
     const uint32_t *block_group;
     const uint32_t *r2;          /* R^2 mod N: to_mont of a single-modulus launch, and pack_group */
+    /* lane-packed multi-modulus launch, else NULL: the modulus of every curve position (device array);
+     * with `groups` it sends stage1 (one lane per curve), from_mont, to_mont, gcd_scan, s2_init and s2_pair to the
+     * kernels' _lane instantiations (limb counts with gecm_kernels_p1::has_lane) */
+    const uint32_t *curve_group;
 } gecm_modconst;
 
 /* Stage-2 kernel arguments (csrc/gecm_stage2.hpp), passed by value: the type names are part of the kernel symbols. */
@@ -107,6 +111,7 @@ struct gecm_kernels_p1 {
     void (*pack_group)(const gecm_modconst *mc, void *out);
     size_t group_bytes;
     const char *manifest;         /* the hash of the sources the object was compiled from (Makefile: K_SHA) */
+    int has_lane;                 /* the per-lane kernels are built for this limb count (8 .. 15 limbs) */
 };
 
 /* Part 2: stage 2 (a multi-modulus mc takes K = 1 only). */

@@ -35,6 +35,15 @@ struct S2Const {
     uint32_t inv_iters;   // batches of 28 division steps of the inversion (fe_invert)
 };
 
+// the same for a lane of a lane-packed batch (ModV, gecm_field.hpp): N and rho in registers, K' in LDS, and `one` and
+// `r3` left in the modulus's constants block in global memory until they are used
+template <int NL>
+struct S2ConstV {
+    ModV<NL> m;
+    FeG<NL> one, r3;
+    uint32_t inv_iters;
+};
+
 // Tables are tiled per wavefront: [wave][entry][limb][lane].  One entry of one wave is NL*256
 // contiguous bytes (3.84 KB at NL=15), so a pair step reads one contiguous chunk of the 60-GB
 // baby-step table instead of NL 256-byte pieces half a megabyte apart ([entry][limb][curve] order):
@@ -179,8 +188,10 @@ __device__ __forceinline__ void imad(int64_t &acc, int32_t x, int32_t y)
     asm("v_mad_i64_i32 %0, vcc, %1, %2, %0" : "+v"(acc) : "v"(x), "v"(y) : "vcc");
 }
 
-template <int NL>
-__device__ __noinline__ bool fe_invert(Fe<NL> &r, Fe<NL> &gout, const Fe<NL> &x, const ModK<NL> &m, uint32_t batches)
+// MOD = ModK<NL>, or ModV<NL> (a modulus per lane, §16): every lane then runs its own number of batches — the loop bound
+// is per lane, lanes drop out as they finish, and the wavefront takes as long as its largest modulus needs.
+template <int NL, class MOD>
+__device__ __noinline__ bool fe_invert(Fe<NL> &r, Fe<NL> &gout, const Fe<NL> &x, const MOD &m, uint32_t batches)
 {
     constexpr int32_t M28 = (int32_t)GECM_LIMB_MASK;
     int32_t f[NL], g[NL], d[NL], e[NL];     // low limbs in [0, 2^28), the top limb carries the sign
@@ -296,8 +307,8 @@ __device__ __noinline__ bool fe_invert(Fe<NL> &r, Fe<NL> &gout, const Fe<NL> &x,
 // On failure r = 0 and *fail receives gcd(x R mod N, N) = gcd(x, N).  The LAST failure wins, as in the reference,
 // which overwrites its accumulator with the gcd every time an inversion fails (ecm.c:1925-1939); the host makes the
 // last chunk of giant steps coincide with the reference's last batch (gecm_stage2_pair).
-template <int NL>
-__device__ __forceinline__ void fe_inv_mont(Fe<NL> &r, const Fe<NL> &a, const S2Const<NL> &k, uint32_t *__restrict__ fail,
+template <int NL, class KC>
+__device__ __forceinline__ void fe_inv_mont(Fe<NL> &r, const Fe<NL> &a, const KC &k, uint32_t *__restrict__ fail,
                                             size_t stride, uint32_t idx)
 {
     Fe<NL> c, t, g;
@@ -319,10 +330,10 @@ __device__ __forceinline__ void fe_inv_mont(Fe<NL> &r, const Fe<NL> &a, const S2
 // tgt == nullptr: entry i of the block goes to table entry e0 + i; else to tgt[e0 + i] (a sub-sequence's kept
 // entries are not consecutive in the table).  sidx = index used for the block scratch (a virtual curve per
 // sub-sequence), idx = the curve's own index (table, failure record).
-template <int NL>
+template <int NL, class KC>
 __device__ __forceinline__ void block_normalise(uint32_t *__restrict__ out, uint32_t out_nent, size_t e0,
                                                 const uint32_t *__restrict__ bx, const uint32_t *__restrict__ bz,
-                                                uint32_t *__restrict__ bp, uint32_t n, const S2Const<NL> &k,
+                                                uint32_t *__restrict__ bp, uint32_t n, const KC &k,
                                                 uint32_t *__restrict__ fail, size_t stride, uint32_t idx,
                                                 const uint32_t *__restrict__ tgt = nullptr, uint32_t sidx = 0xffffffffu)
 {
@@ -388,8 +399,8 @@ template <int NL>
 __device__ __forceinline__ void fe_sub(Fe<NL> &r, const Fe<NL> &a, const Fe<NL> &b, const ModKOut<NL> &o) { fe_sub(r, a, b, o.m); }
 
 // P <- [c]P, binary ladder (next_pt_vec, ecm.c:886-976); c is wave-uniform.  MM = ModK<NL> or ModKOut<NL>.
-template <int NL, class MM>
-__device__ __forceinline__ void pt_ladder_body(Pt<NL> &P, uint64_t c, const Fe<NL> &s4, const ModK<NL> &m, const MM &mm_)
+template <int NL, class MOD, class MM>
+__device__ __forceinline__ void pt_ladder_body(Pt<NL> &P, uint64_t c, const Fe<NL> &s4, const MOD &m, const MM &mm_)
 {
     if (c == 1) return;
     Fe<NL> s1, d1, s2, d2;
@@ -418,18 +429,18 @@ __device__ __forceinline__ void pt_ladder_body(Pt<NL> &P, uint64_t c, const Fe<N
     }
     P = p1;
 }
-template <int NL>
-__device__ __forceinline__ void pt_ladder(Pt<NL> &P, uint64_t c, const Fe<NL> &s4, const ModK<NL> &m)
+template <int NL, class MOD>
+__device__ __forceinline__ void pt_ladder(Pt<NL> &P, uint64_t c, const Fe<NL> &s4, const MOD &m)
 {
     if constexpr (NL >= GECM_LADDER_OL_NL) pt_ladder_body(P, c, s4, m, ModKOut<NL>{m});
     else pt_ladder_body(P, c, s4, m, m);
 }
 
 // ecm_stage2_init, ecm.c:2201-2340
-template <int NL>
-__device__ __forceinline__ void s2_init(const S2InitArgs &a, const S2Const<NL> &k, uint32_t idx)
+template <int NL, class KC>
+__device__ __forceinline__ void s2_init(const S2InitArgs &a, const KC &k, uint32_t idx)
 {
-    const ModK<NL> &m = k.m;
+    const auto &m = k.m;
     const size_t stride = a.stride;
     Pt<NL> Q, P1, P3;
     Fe<NL> s4, sQ, dQ;
@@ -553,13 +564,13 @@ __device__ __forceinline__ void s2_init_k(const S2InitArgs &a, const S2Const<NL>
 // step a pair can still ask for.  Same points, same (unique) inverses, same accumulator.
 // kprev > 1: the steps before first_abs were made by giant_chunk_k with kprev sub-sequences; the two previous steps are
 // then the latest members of sub-sequences (first_abs-1) % kprev and (first_abs-2) % kprev.
-template <int NL>
+template <int NL, class KC>
 __device__ __forceinline__ void giant_chunk(const S2PairArgs &a, uint32_t first_abs, uint32_t n, bool very_first,
-                                            const S2Const<NL> &k, uint32_t idx, uint32_t kprev = 1)
+                                            const KC &k, uint32_t idx, uint32_t kprev = 1)
 {
     // its own kernel launch (k_s2_gen, ~84 per curve batch at B2=1e8): everything it needs is read from
     // memory, so the pair-walk kernel keeps only the accumulator and two operand pairs live
-    const ModK<NL> &m = k.m;
+    const auto &m = k.m;
     const size_t stride = a.stride;
     Pt<NL> Q, Pd;
     Fe<NL> s4, sD, dD;
@@ -725,11 +736,11 @@ __device__ __forceinline__ void giant_chunk_k(const S2PairArgs &a, uint32_t firs
 #ifndef GECM_S2_DEPTH_MAXNL
 #define GECM_S2_DEPTH_MAXNL 23            // above: two rows in flight (registers)
 #endif
-template <int NL>
-__device__ __forceinline__ void s2_pairs(const S2PairArgs &a, uint32_t first, uint32_t count, const S2Const<NL> &k,
+template <int NL, class KC>
+__device__ __forceinline__ void s2_pairs(const S2PairArgs &a, uint32_t first, uint32_t count, const KC &k,
                                          uint32_t idx, uint32_t *__restrict__ accbuf)
 {
-    const ModK<NL> &m = k.m;
+    const auto &m = k.m;
     const size_t stride = a.stride;
     if (count == 0) return;
     Fe<NL> acc;
@@ -804,9 +815,9 @@ __device__ __forceinline__ void s2_pairs(const S2PairArgs &a, uint32_t first, ui
 }
 
 // acc[0] <- product of the `slices` accumulators (skipped when init_only); acc[1..] <- one.
-template <int NL>
+template <int NL, class KC>
 __device__ __forceinline__ void s2_merge(uint32_t *__restrict__ acc, uint32_t slices, size_t stride, bool init_only,
-                                         const S2Const<NL> &k, uint32_t idx)
+                                         const KC &k, uint32_t idx)
 {
     const size_t slice_words = (size_t)NL * stride;
     Fe<NL> r;

@@ -246,6 +246,34 @@ static int set_curve_build(gecm_ctx *ctx)
     return gecm_set_curve_build(ctx, where);
 }
 
+/* How the multi-modulus passes of -f and -r are packed (include/gecm.h gecm_set_multi_packing):
+ * GECM_PACKING=lane|wave, wave when unset.  The files are byte for byte the same either way.  Lane packing serves the
+ * passes whose inputs all fit it (gecm_multi_packing_max_bits); a pass is closed when the next input falls on the other
+ * side of that line, and the passes of larger numbers stay wave-packed.  A lane-packed context builds its curves on the
+ * host, so the combination with GECM_CURVE_BUILD=device is refused before anything runs.  Returns the packing, or -1
+ * after printing why not. */
+static int cli_packing(void)
+{
+    const char *s = getenv("GECM_PACKING"), *b = getenv("GECM_CURVE_BUILD");
+    const int packing = !s || !strcmp(s, "wave") ? GECM_PACK_WAVE : !strcmp(s, "lane") ? GECM_PACK_LANE : -1;
+    if (packing < 0) printf("GECM_PACKING must be lane or wave\n");
+    else if (packing == GECM_PACK_LANE && b && !strcmp(b, "device")) {
+        printf("GECM_PACKING=lane builds its curves on the host: it cannot be combined with GECM_CURVE_BUILD=device\n");
+        return -1;
+    }
+    return packing;
+}
+
+/* positions of a pass of n inputs with `each` curves each (gecm_multi_positions has the rule: lane packing rounds the
+ * sum, wave packing every input) */
+static size_t pass_positions(size_t n, size_t each, int packing)
+{
+    const size_t all = n * each;
+    return packing == GECM_PACK_LANE ? gecm_multi_positions(&all, 1, packing) : n * gecm_multi_positions(&each, 1, packing);
+}
+
+static int fits_lane_packing(int nbits) { return nbits <= gecm_multi_packing_max_bits(GECM_PACK_LANE); }
+
 /* ---- per-GPU jobs of a pass ----------------------------------------------------------------- */
 static int step_build(job_t *j)
 {
@@ -1034,12 +1062,13 @@ typedef struct {
  * (-r): the curves start from the lines' residues, stage 1 complete.  Every input is written as the one-input path
  * writes it: a pass of all its batches on one context.  Returns 0, or 2 after a device or library error. */
 static int multi_run(const char **ns, const char *const *logs, size_t n, run_t *R, const uint64_t *sigma, const uint32_t *which,
-                     const size_t *first, const size_t *count, size_t total, const rline_t *rl)
+                     const size_t *first, const size_t *count, size_t total, const rline_t *rl, int packing)
 {
     gecm_ctx *mc = NULL;
     void *rx = NULL, *rz = NULL;
     int rc = gecm_create_multi(&mc, 0, ns, n, GECM_CLI_DIGITBITS);
     if (rc == 0) rc = set_curve_build(mc);
+    if (rc == 0) rc = gecm_set_multi_packing(mc, packing);
     if (rc == 0 && rl) {
         gecm_config cfg;
         gecm_get_config(mc, &cfg);
@@ -1065,16 +1094,16 @@ static int multi_run(const char **ns, const char *const *logs, size_t n, run_t *
         output_release(&v, &o);
     }
     if (!rc)
-        printf("multi-modulus pass: %zu inputs, %zu curves%s, %s%s, %1.4f seconds of kernels after stage 1\n", n,
-               rl ? total : count[0], rl ? " in all" : " each", rl ? "resumed after stage 1" : "stage 1",
-               R->do_stage2 ? " and stage 2" : "", gecm_last_kernel_ms(mc) / 1000.0);
+        printf("multi-modulus pass: %zu inputs, %zu curves%s, %s-packed, %s%s, %1.4f seconds of kernels after stage 1\n", n,
+               rl ? total : count[0], rl ? " in all" : " each", gecm_get_multi_packing(mc) == GECM_PACK_LANE ? "lane" : "wave",
+               rl ? "resumed after stage 1" : "stage 1", R->do_stage2 ? " and stage 2" : "", gecm_last_kernel_ms(mc) / 1000.0);
     gecm_destroy(mc);
     free(rx); free(rz);
     return rc ? 2 : 0;
 }
 
 /* the inputs of one multi-modulus pass of -f, ucurves curves each */
-static int multi_pass(input_t **in, size_t n, run_t *R, size_t ucurves)
+static int multi_pass(input_t **in, size_t n, run_t *R, size_t ucurves, int packing)
 {
     const char **ns = (const char **)malloc(n * sizeof *ns), **logs = (const char **)malloc(n * sizeof *logs);
     uint64_t *sigma = (uint64_t *)malloc(n * ucurves * sizeof *sigma);
@@ -1093,7 +1122,7 @@ static int multi_pass(input_t **in, size_t n, run_t *R, size_t ucurves)
             which[i * ucurves + u] = (uint32_t)i;
         }
     }
-    const int rc = multi_run(ns, logs, n, R, sigma, which, first, count, n * ucurves, NULL);
+    const int rc = multi_run(ns, logs, n, R, sigma, which, first, count, n * ucurves, NULL, packing);
     free(ns); free(logs); free(sigma); free(which); free(first);
     return rc;
 }
@@ -1103,6 +1132,8 @@ static int run_file(int argc, char **argv)
     static const char *usage = "usage: avx-ecm -f $file $numcurves $B1 [$threads] [$B2] [$sigma]\n"
                                "       (one input expression per line; blank lines and lines starting with # are skipped)\n";
     if (argc < 5) { printf("%s", usage); return 1; }
+    const int packing = cli_packing();
+    if (packing < 0) return 1;
     FILE *f = fopen(argv[2], "r");
     if (!f) { printf("cannot read %s\n%s", argv[2], usage); return 1; }
     size_t ninputs = 0, cap_in = 0;
@@ -1133,6 +1164,7 @@ static int run_file(int argc, char **argv)
     printf("starting process %d: %zu inputs from %s\n", (int)getpid(), ninputs, argv[2]);
     const size_t cap = env_count("GECM_PASS_CURVES") ? (size_t)env_count("GECM_PASS_CURVES") : FULL_BATCH;
     const int multi_ok = R.B1 <= 99999989ULL && padded <= cap;    /* one prime range, no checkpoint; one input fits */
+    int pend_packing = GECM_PACK_WAVE;                                 /* of the pending pass */
 
     /* the one-input path's argument list for input i: argv with "-f FILE" replaced by the input */
     char *sargv[8];
@@ -1145,23 +1177,29 @@ static int run_file(int argc, char **argv)
     int rc = 0;
     for (size_t i = 0; i <= ninputs && rc != 2; i++) {
         input_t *in = NULL;
-        int alone = 1;
+        int alone = 1, in_packing = GECM_PACK_WAVE;
         if (i < ninputs && multi_ok) {
             in = (input_t *)calloc(1, sizeof *in);
             if (!in) { fprintf(stderr, "out of memory\n"); return 2; }
             gecm_input_info inf;
             alone = gecm_prepare_input(exprs[i], GECM_CLI_DIGITBITS, in->ndec, sizeof in->ndec, &inf, in->log, sizeof in->log) ||
                     inf.ref_special_reduction;
+            if (!alone && packing == GECM_PACK_LANE && fits_lane_packing(inf.nbits)) in_packing = GECM_PACK_LANE;
         }
         /* the pending pass goes first when this input cannot join it */
-        if (npend && (i == ninputs || alone || (npend + 1) * padded > cap)) {
-            rc = multi_pass(pend, npend, &R, ucurves);
+        if (npend && (i == ninputs || alone || in_packing != pend_packing ||
+                      pass_positions(npend + 1, ucurves, pend_packing) > cap)) {
+            rc = multi_pass(pend, npend, &R, ucurves, pend_packing);
             for (size_t k = 0; k < npend; k++) free(pend[k]);
             npend = 0;
             if (rc == 2) break;
         }
         if (i == ninputs) break;
-        if (!alone) { pend[npend++] = in; continue; }
+        if (!alone) {
+            if (!npend) pend_packing = in_packing;
+            pend[npend++] = in;
+            continue;
+        }
         free(in);
         sargv[1] = exprs[i];
         const int r1 = run_single(sargc, sargv);
@@ -1227,6 +1265,8 @@ static int resume_single(const rgroup_t *g, const rline_t *lines, char **rargv, 
 static int run_resume(int argc, char **argv)
 {
     if (argc < 4) { printf("%s", resume_usage); return 1; }
+    const int packing = cli_packing();
+    if (packing < 0) return 1;
     FILE *f = fopen(argv[2], "r");
     if (!f) { printf("cannot read %s\n%s", argv[2], resume_usage); return 1; }
     /* the run's arguments through the one parser: curves B1 threads [B2], one thread, the curve count per group */
@@ -1336,11 +1376,23 @@ static int run_resume(int argc, char **argv)
         R0.t_start = now();
         R0.s1_complete = 1;                        /* the multi passes: stage 2 only */
         R0.nbatches = 0;
-        size_t p0 = 0, padded = 0;                 /* the pending multi pass: groups p0 .. i, their padded size */
-        for (size_t i = 0; i <= ngroups && rc != 2; i++) {
+        size_t p0 = 0;                             /* the pending multi pass: groups p0 .. i */
+        size_t *pcount = (size_t *)calloc(ngroups + 1, sizeof *pcount);   /* curves of the groups */
+        if (!pcount) { fprintf(stderr, "out of memory\n"); rc = 2; }
+        int pend_packing = GECM_PACK_WAVE;
+        for (size_t i = 0; i <= ngroups && rc != 2 && pcount; i++) {
             const size_t pad_i = i < ngroups ? (groups[i].count + 63) / 64 * 64 : 0;
             const int alone = i < ngroups && (ngroups == 1 || pad_i > cap);
-            if (i > p0 && (i == ngroups || alone || padded + pad_i > cap)) {
+            int in_packing = GECM_PACK_WAVE;
+            if (i < ngroups && !alone && packing == GECM_PACK_LANE) {
+                static char nd[MPL_MAXL * 10 + 16], lg[65536];
+                gecm_input_info inf;
+                if (!gecm_prepare_input(groups[i].ndec, GECM_CLI_DIGITBITS, nd, sizeof nd, &inf, lg, sizeof lg) && fits_lane_packing(inf.nbits))
+                    in_packing = GECM_PACK_LANE;
+            }
+            if (i < ngroups) pcount[i] = groups[i].count;
+            if (i > p0 && (i == ngroups || alone || in_packing != pend_packing ||
+                           gecm_multi_positions(pcount + p0, i + 1 - p0, pend_packing) > cap)) {
                 const size_t n_in = i - p0, total = groups[i - 1].first + groups[i - 1].count - groups[p0].first;
                 const char **ns = (const char **)malloc(n_in * sizeof *ns);
                 uint64_t *sigma = (uint64_t *)malloc(total * sizeof *sigma);
@@ -1362,19 +1414,23 @@ static int run_resume(int argc, char **argv)
                         which[first[k] + u] = (uint32_t)k;
                     }
                 }
-                const int r1 = multi_run(ns, NULL, n_in, &R0, sigma, which, first, first + n_in, total, lines + groups[p0].first);
+                const int r1 = multi_run(ns, NULL, n_in, &R0, sigma, which, first, first + n_in, total, lines + groups[p0].first,
+                                         pend_packing);
                 if (r1 > rc) rc = r1;
                 free(ns); free(sigma); free(which); free(first);
                 p0 = i;
-                padded = 0;
             }
             if (i == ngroups || rc == 2) break;
-            if (!alone) { padded += pad_i; continue; }
+            if (!alone) {
+                if (i == p0) pend_packing = in_packing;
+                continue;
+            }
             snprintf(ncurves, sizeof ncurves, "%zu", groups[i].count);
             const int r1 = resume_single(&groups[i], lines, rargv, rargc);
             if (r1 > rc) rc = r1;
             p0 = i + 1;
         }
+        free(pcount);
         printf("Process took %1.4f seconds.\n", now() - R0.t_start);
     }
     for (size_t i = 0; i < nlines; i++) free(lines[i].text);

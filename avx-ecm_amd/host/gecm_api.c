@@ -127,6 +127,9 @@ struct gecm_ctx {
     uint32_t *slot;          /* caller's curve -> device position */
     uint32_t *pos_user;      /* device position -> caller's curve, GECM_PAD for padding */
     uint32_t *pos_grp;       /* device position -> modulus */
+    /* GECM_PACK_WAVE / GECM_PACK_LANE: asked for (gecm_set_multi_packing), used by the last build.  Lane
+     * packing lays the groups back to back and pads only the batch's tail; every lane then carries its own modulus. */
+    int packing, packing_used;
 };
 #define GECM_PAD 0xffffffffu
 
@@ -348,8 +351,10 @@ int gecm_device_memory(gecm_ctx *c, uint64_t *free_bytes, uint64_t *total_bytes)
 uint64_t gecm_batch_bytes(const gecm_ctx *c, size_t curves, int with_stage2, uint64_t B1, uint32_t D, uint32_t U)
 {
     if (!c || !curves) return 0;
-    /* multi-modulus: every modulus's curves padded to whole wavefronts, at most 63 more per modulus that has curves */
-    if (c->multi) curves += 63 * (curves < c->ngroups ? curves : c->ngroups);
+    /* multi-modulus: every modulus's curves padded to whole wavefronts, at most 63 more per modulus that has curves;
+     * lane-packed, the batch's tail only (gecm_multi_positions) */
+    if (c->multi && c->packing == GECM_PACK_LANE) curves = gecm_multi_positions(&curves, 1, GECM_PACK_LANE);
+    else if (c->multi) curves += 63 * (curves < c->ngroups ? curves : c->ngroups);
     uint32_t npb = 0;
     if (with_stage2) {
         if (!D) D = gecm_s2_default_D(B1 ? B1 : 1000000);
@@ -820,6 +825,11 @@ int gecm_stage1_range(gecm_ctx *c, uint64_t B1, uint32_t range)
     if (c && c->ff_pending) { int rcs = ff_settle(c); if (rcs) return rcs; }
     if (!c || c->batch == 0) { set_err("gecm_stage1: no curves uploaded"); return GECM_ERR_STATE; }
     if (B1 < 2 || B1 > GECM_B1_MAX) { set_err("gecm_stage1: B1 must be in [2, %llu]", (unsigned long long)GECM_B1_MAX); return GECM_ERR_ARG; }
+    if (c->multi && c->packing_used == GECM_PACK_LANE && c->lanes_per_curve == 2) {
+        set_err("gecm_stage1: a lane-packed multi-modulus batch runs one lane per curve, and this context is set to 2 "
+                "(gecm_set_lanes_per_curve)");
+        return GECM_ERR_STATE;
+    }
     const uint32_t nranges = gecm_stage1_ranges_u(B1);
     if (range >= nranges) { set_err("gecm_stage1_range: B1 = %llu has %u prime range(s)", (unsigned long long)B1, nranges); return GECM_ERR_ARG; }
     int rc = tape_for(c, B1, range);
@@ -1497,6 +1507,42 @@ int gecm_create_multi(gecm_ctx **out, int device, const char *const *n_strs, siz
 
 size_t gecm_moduli(const gecm_ctx *c) { return c ? (c->multi ? c->ngroups : 1) : 0; }
 
+/* ---- packing of a multi-modulus batch ---- */
+int gecm_multi_packing_max_bits(int packing)
+{
+    if (packing == GECM_PACK_WAVE) return 0;
+    if (packing != GECM_PACK_LANE) return GECM_ERR_ARG;
+    int nl = 0;                                    /* the largest limb count with per-lane kernels */
+    for (const int *p = gecm_dev_supported_nl(); *p; p++)
+        if (gecm_dev_lane_packing_built(*p) && *p > nl) nl = *p;
+    return nl ? nl * LIMB_BITS - 5 : GECM_ERR_STATE;   /* R = 2^(28 nl) >= 32 N, as pick_nl */
+}
+
+size_t gecm_multi_positions(const size_t *counts, size_t n, int packing)
+{
+    size_t total = 0;
+    for (size_t g = 0; counts && g < n; g++) total += packing == GECM_PACK_LANE ? counts[g] : (counts[g] + 63) / 64 * 64;
+    return (total + 63) / 64 * 64;
+}
+
+int gecm_set_multi_packing(gecm_ctx *c, int packing)
+{
+    if (!c || (packing != GECM_PACK_WAVE && packing != GECM_PACK_LANE)) {
+        set_err("gecm_set_multi_packing: bad argument (GECM_PACK_WAVE or GECM_PACK_LANE)");
+        return GECM_ERR_ARG;
+    }
+    if (!c->multi) { set_err("gecm_set_multi_packing: not a multi-modulus context (gecm_create_multi)"); return GECM_ERR_STATE; }
+    if (packing == GECM_PACK_LANE && !gecm_dev_lane_packing_built(c->mod.nl)) {
+        set_err("gecm_set_multi_packing: lane packing serves numbers up to %d bits, and this context's largest has %d",
+                gecm_multi_packing_max_bits(GECM_PACK_LANE), mpl_bits(&c->mod.N));
+        return GECM_ERR_STATE;
+    }
+    c->packing = packing;
+    return GECM_OK;
+}
+
+int gecm_get_multi_packing(const gecm_ctx *c) { return c ? c->packing_used : GECM_ERR_ARG; }
+
 /* the checks gecm_build_curves_multi and gecm_resume_points_multi make on their common arguments */
 static int multi_args(const gecm_ctx *c, const char *who, const uint64_t *sigma, const uint32_t *modulus_index, size_t batch)
 {
@@ -1518,13 +1564,22 @@ static int multi_args(const gecm_ctx *c, const char *who, const uint64_t *sigma,
 static int build_multi(gecm_ctx *c, const char *who, const uint64_t *sigma, const uint32_t *modulus_index, size_t batch,
                        const uint32_t *ux, const uint32_t *uz)
 {
-    /* positions: the moduli in order, each one's curves in the caller's order, padded to a multiple of 64 */
+    /* positions: the moduli in order, each one's curves in the caller's order, padded to a multiple of 64; lane-packed:
+     * back to back, and the batch's tail padded (modulus 0 there: computed, never read) */
     const size_t ng = c->ngroups;
+    const int lane = c->packing == GECM_PACK_LANE;
+    if (lane && c->build_where == GECM_BUILD_DEVICE) {        /* before the previous batch is given up */
+        set_err("%s: the device curve build has no per-lane kernel: a lane-packed context builds on the host "
+                "(gecm_set_curve_build, gecm_set_multi_packing)", who);
+        return GECM_ERR_STATE;
+    }
     size_t *cnt = (size_t *)calloc(ng, sizeof(size_t)), *goff = (size_t *)calloc(ng, sizeof(size_t));
     if (!cnt || !goff) { free(cnt); free(goff); return GECM_ERR_NOMEM; }
     for (size_t i = 0; i < batch; i++) cnt[modulus_index[i]]++;
-    size_t total = 0;
-    for (size_t g = 0; g < ng; g++) { goff[g] = total; total += (cnt[g] + 63) / 64 * 64; }
+    /* positions of one group: its curves, under wave packing with its own padding (gecm_multi_positions has the rule) */
+#define GROUP_SPAN(g) (lane ? cnt[g] : gecm_multi_positions(&cnt[g], 1, GECM_PACK_WAVE))
+    const size_t total = gecm_multi_positions(cnt, ng, c->packing);
+    for (size_t g = 0, off = 0; g < ng; g++) { goff[g] = off; off += GROUP_SPAN(g); }
     int rc = alloc_batch(c, total);
     uint32_t *slot = (uint32_t *)malloc(batch * sizeof(uint32_t)), *pos_user = (uint32_t *)malloc(total * sizeof(uint32_t));
     uint32_t *pos_grp = (uint32_t *)malloc(total * sizeof(uint32_t)), *blocks = (uint32_t *)malloc(total / 64 * sizeof(uint32_t));
@@ -1537,12 +1592,18 @@ static int build_multi(gecm_ctx *c, const char *who, const uint64_t *sigma, cons
         return rc;
     }
     c->slot = slot; c->pos_user = pos_user; c->pos_grp = pos_grp; c->nuser = batch;
+    for (size_t p = 0; lane && p < total; p++) {
+        pos_grp[p] = 0;
+        pos_user[p] = GECM_PAD;
+        blocks[p / 64] = 0;                                     /* unused: the kernels read pos_grp */
+    }
     for (size_t g = 0; g < ng; g++)
-        for (size_t p = goff[g]; p < goff[g] + (cnt[g] + 63) / 64 * 64; p++) {
+        for (size_t p = goff[g]; p < goff[g] + GROUP_SPAN(g); p++) {
             pos_grp[p] = (uint32_t)g;
             pos_user[p] = GECM_PAD;
-            blocks[p / 64] = (uint32_t)g;
+            if (!lane) blocks[p / 64] = (uint32_t)g;
         }
+#undef GROUP_SPAN
     memset(cnt, 0, ng * sizeof(size_t));
     for (size_t i = 0; i < batch; i++) {
         const uint32_t g = modulus_index[i];
@@ -1571,6 +1632,7 @@ static int build_multi(gecm_ctx *c, const char *who, const uint64_t *sigma, cons
         if (gecm_dev_set_groups(c->dev, (uint32_t)ng, q, q + w, q + 2 * w, q + 3 * w, q + 5 * w, q + 5 * w + ng, q + 4 * w, blocks))
             rc = GECM_ERR_DEVICE;
     }
+    if (!rc && gecm_dev_set_curve_groups(c->dev, (uint32_t)ng, lane ? pos_grp : NULL)) rc = GECM_ERR_DEVICE;
     if (!rc && on_device) {              /* the kernel takes every block's modulus from the groups just set */
         const int built = build_on_device(c, c->sigma, total, pos_user);
         if (built < 0) {
@@ -1600,6 +1662,7 @@ static int build_multi(gecm_ctx *c, const char *who, const uint64_t *sigma, cons
         free_batch(c);
         return rc;
     }
+    c->packing_used = c->packing;
     return anybad ? 1 : GECM_OK;
 }
 

@@ -127,6 +127,21 @@ _sig("gecm_moduli", c_size_t, c_void_p)
 _sig("gecm_curve_modulus", c_int, c_void_p, c_size_t)
 _sig("gecm_curve_acc", c_int, c_void_p, c_size_t, c_char_p, c_size_t)
 EXPORTS += ["gecm_create_multi", "gecm_build_curves_multi", "gecm_moduli", "gecm_curve_modulus", "gecm_curve_acc"]
+PACK_WAVE, PACK_LANE = 0, 1
+_sig("gecm_set_multi_packing", c_int, c_void_p, c_int)
+_sig("gecm_get_multi_packing", c_int, c_void_p)
+_sig("gecm_multi_positions", c_size_t, ctypes.POINTER(c_size_t), c_size_t, c_int)
+_sig("gecm_multi_packing_max_bits", c_int, c_int)
+EXPORTS += ["gecm_set_multi_packing", "gecm_get_multi_packing", "gecm_multi_positions", "gecm_multi_packing_max_bits"]
+
+
+def multi_positions(counts, packing):
+    """padded curve positions of a multi-modulus batch with counts[g] curves on number g; packing is "wave" or "lane" """
+    arr = (c_size_t * max(1, len(counts)))(*counts)
+    return lib.gecm_multi_positions(arr, len(counts), _PACKINGS[packing])
+
+
+_PACKINGS = {"wave": PACK_WAVE, "lane": PACK_LANE}
 
 
 class ResumeNum(ctypes.Structure):
@@ -535,6 +550,17 @@ class MultiEngine(Engine):
         self.batch = len(sigmas)
         return _chk(lib.gecm_resume_points_multi(self._h, arr, idx, self.pack(xs), self.pack(zs), len(sigmas), b1_done),
                     "gecm_resume_points_multi")
+
+    def set_packing(self, packing):
+        """"wave" (one modulus per wavefront, every number padded to 64 curves) or "lane" (one modulus per lane, only the
+        batch's tail padded; numbers up to 415 bits): from the next build_curves or resume on"""
+        if packing not in _PACKINGS:
+            raise ValueError("set_packing: 'wave' or 'lane'")
+        return _chk(lib.gecm_set_multi_packing(self._h, _PACKINGS[packing]), "gecm_set_multi_packing")
+
+    def packing(self):
+        """what the last build used"""
+        return ["wave", "lane"][_chk(lib.gecm_get_multi_packing(self._h), "gecm_get_multi_packing")]
 
     def _line_moduli(self):
         return self.ns

@@ -311,7 +311,8 @@ int gecm_stage2_factor(gecm_ctx *ctx, size_t k, char *dec, size_t declen, int *i
  * gecm_build_curves_multi: curve i has sigma[i] on number modulus_index[i] (< count), in any order.  The library
  *   groups the curves by number and pads each group to whole wavefronts of 64 curves: padding lanes are computed and
  *   dropped, so a list with 8 curves per number runs at 1/8 of the chip's throughput (gecm_batch_bytes counts the
- *   padding, at most 63 curves per number).  Returns 1 like gecm_build_curves when a denominator was not invertible.
+ *   padding, at most 63 curves per number) — unless the context is lane-packed: gecm_set_multi_packing below,
+ *   DESIGN.md §16.  Returns 1 like gecm_build_curves when a denominator was not invertible.
  * Curve indices k of every per-curve call are the caller's i.  These work per curve against that curve's number,
  * exactly as they do on a single-N context of it: gecm_stage1, gecm_stage1_range, gecm_sync, gecm_stage2*,
  * gecm_format_save_line, gecm_format_resume_line, gecm_stage1_factor, gecm_stage2_factor, gecm_scan_factors (*first:
@@ -329,6 +330,29 @@ int gecm_curve_modulus(const gecm_ctx *ctx, size_t k);
 /* the stage-2 accumulator of curve k as the integer gecm_download_acc returns for it on a single-N context of its
  * number (reference Montgomery radix, canonical), in lower-case hex without prefix; returns the digit count */
 int gecm_curve_acc(gecm_ctx *ctx, size_t k, char *hex, size_t hexlen);
+
+/* ---- packing of a multi-modulus batch -------------------------------------------
+ * GECM_PACK_LANE puts one modulus on every lane instead of one on every wavefront: the numbers' curves lie back to
+ * back and only the batch's tail is padded to 64, so a list with 8 curves per number no longer computes 56 padding
+ * lanes per number.  For contexts whose largest number has at most 415 bits (15 limbs).  Every per-curve result is the
+ * one the default packing and a single-N context of the curve's number give, and the caller's curve indices are
+ * unchanged.  Stage 1 runs one lane per curve: a context set to 2 lanes per curve answers gecm_stage1 with
+ * GECM_ERR_STATE.  Curves are built on the host: with GECM_BUILD_DEVICE gecm_build_curves_multi and
+ * gecm_resume_points_multi answer GECM_ERR_STATE, and the previous batch stays.
+ * gecm_set_multi_packing takes effect at the next gecm_build_curves_multi or gecm_resume_points_multi, as
+ *   gecm_set_curve_build does; GECM_ERR_ARG for a bad value or a NULL context, GECM_ERR_STATE on a single-N context and
+ *   on a multi-modulus context of more than 15 limbs.
+ * gecm_get_multi_packing: what the last build used; GECM_PACK_WAVE before the first.
+ * gecm_multi_positions: padded curve positions a batch with counts[0..n) curves per number occupies under `packing`
+ *   (a multiple of 64); pure host code, the one place the rounding rule lives.
+ * gecm_multi_packing_max_bits: the largest number, in bits, a context of that packing takes (415 for GECM_PACK_LANE);
+ *   0 = no limit of the packing's own (GECM_PACK_WAVE); GECM_ERR_ARG for a bad value. */
+#define GECM_PACK_WAVE 0   /* one modulus per wavefront, each number padded to 64 curves (the default) */
+#define GECM_PACK_LANE 1   /* one modulus per lane: numbers back to back, only the batch's tail padded to 64 */
+int gecm_set_multi_packing(gecm_ctx *ctx, int packing);
+int gecm_get_multi_packing(const gecm_ctx *ctx);
+size_t gecm_multi_positions(const size_t *counts, size_t n, int packing);
+int gecm_multi_packing_max_bits(int packing);
 
 /* ---- resume: save_b1.txt and checkpoint.txt lines back into a context ------------
  * gecm_parse_resume_line reads one line "METHOD=ECM; SIGMA=...; B1=...; N=...; X=...; Z=...; PROGRAM=...;" — ours

@@ -5,7 +5,13 @@ timed three ways on one device —
   (c) one multi-modulus context holding every curve,
   (d) for reference, one single-N context holding as many curves of one number as (c) holds.
 Curve building is outside the timed part; one untimed run of (a) and (c) first loads the code objects and tapes.
-usage: python tools/multi_bench.py [--bits 415 831] [--count 32] [--curves 4096] [--b1 100000] [--out profiles/multi]"""
+usage: python tools/multi_bench.py [--bits 415 831] [--count 32] [--curves 4096] [--b1 100000] [--out profiles/multi]
+
+With --curves-per-number C [C ...] it compares the two packings of a multi-modulus batch instead:
+`--real-curves` curves on random N of `--bits` bits, C curves per number, stage 1 to B1 (and, with --b2, stage 2 to B2)
+under every `--packing` named, in one process: one warm call, then the median of five.
+usage: python tools/multi_bench.py --curves-per-number 8 16 32 64 [--packing wave lane] [--real-curves 131072]
+       [--bits 415 200] [--b1 100000] [--b2 0] [--out profiles/dense]"""
 import argparse
 import json
 import os
@@ -84,15 +90,76 @@ def run(bits, count, curves, b1):
     return out
 
 
+def run_dense(bits, real, cpn, packings, b1, b2):
+    """wave against lane packing: `real` curves, cpn per number"""
+    import statistics
+    import pyecm
+    rnd = random.Random(bits * 1000 + cpn)
+    count = real // cpn
+    ns = [rnd.getrandbits(bits) | (1 << (bits - 1)) | 1 for _ in range(count)]
+    sig = [1000 + k for k in range(count * cpn)]
+    which = [i for i in range(count) for _ in range(cpn)]
+    out = {"bits": bits, "numbers": count, "curves_per_number": cpn, "real_curves": count * cpn, "B1": b1, "B2": b2}
+    lines = {}
+    for packing in packings:
+        eng = pyecm.MultiEngine(ns)
+        eng.set_packing(packing)
+        out["dev_limbs"] = eng.cfg.dev_limbs
+        t = time.perf_counter()
+        eng.build_curves(sig, which)
+        build_s = time.perf_counter() - t
+        s1, s2 = [], []
+        for call in range(6):                   # stage 1 goes on from the points the call before left: the same work
+            t = time.perf_counter()
+            eng.stage1(b1)
+            s1.append(time.perf_counter() - t)
+            if call == 0:
+                lines[packing] = [eng.save_line(k) for k in (0, cpn - 1, count * cpn - 1)]
+            if b2:
+                t = time.perf_counter()
+                eng.stage2(b2)
+                s2.append(time.perf_counter() - t)
+        r = {"positions": pyecm.multi_positions([cpn] * count, packing), "build_seconds": round(build_s, 3),
+             "kernel": eng.last_kernel_name(), "lanes_per_curve": eng.lanes_per_curve(),
+             "stage1_seconds": [round(x, 4) for x in s1], "stage1_median_of_5": round(statistics.median(s1[1:]), 4)}
+        r["stage1_real_curves_per_s"] = round(count * cpn / r["stage1_median_of_5"], 1)
+        if b2:
+            r["stage2_seconds"] = [round(x, 4) for x in s2]
+            r["stage2_median_of_5"] = round(statistics.median(s2[1:]), 4)
+        out[packing] = r
+        eng.close()
+    if len(packings) == 2:
+        a, b = out[packings[0]], out[packings[1]]
+        assert lines[packings[0]] == lines[packings[1]]
+        out["stage1_%s_over_%s" % tuple(packings)] = round(a["stage1_median_of_5"] / b["stage1_median_of_5"], 3)
+        if b2:
+            out["stage2_%s_over_%s" % tuple(packings)] = round(a["stage2_median_of_5"] / b["stage2_median_of_5"], 3)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--curves-per-number", type=int, nargs="+", default=None)
+    ap.add_argument("--packing", nargs="+", choices=["wave", "lane"], default=["wave", "lane"])
+    ap.add_argument("--real-curves", type=int, default=131072)
+    ap.add_argument("--b2", type=int, default=0)
     ap.add_argument("--bits", type=int, nargs="+", default=[415, 831])
     ap.add_argument("--count", type=int, default=32)
     ap.add_argument("--curves", type=int, default=4096)
     ap.add_argument("--b1", type=int, default=100000)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "multi"))
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "dense" if a.curves_per_number else "multi")
     os.makedirs(a.out, exist_ok=True)
+    if a.curves_per_number:
+        for bits in a.bits:
+            for cpn in a.curves_per_number:
+                r = run_dense(bits, a.real_curves, cpn, a.packing, a.b1, a.b2)
+                print(json.dumps(r), flush=True)
+                with open(os.path.join(a.out, "dense_%d_c%d%s.json" % (bits, cpn, "_s2" if a.b2 else "")), "w") as f:
+                    json.dump(r, f, indent=1)
+        return
     for bits in a.bits:
         r = run(bits, a.count, a.curves, a.b1)
         print(json.dumps(r), flush=True)
