@@ -58,6 +58,10 @@ int gecm_dev_set_r2(gecm_dev *d, const uint32_t *r2);
 int gecm_dev_build(gecm_dev *d, const uint64_t *sigma, size_t count, uint32_t *flags);
 float gecm_dev_last_build_ms(gecm_dev *d);
 int gecm_dev_fill_twin(gecm_dev *dst, gecm_dev *src, const uint32_t *r2);
+/* X <- X/Z, Z <- R mod N in the batch planes (canonical), for every curve whose Z has an inverse; the others keep both
+ * and get flags[i] = 1 (count = the batch's curves, padding included as for gecm_dev_build).  Needs gecm_dev_set_s2const.
+ * Synchronous; the kernel's own time is gecm_dev_last_build_ms. */
+int gecm_dev_normalize(gecm_dev *d, uint32_t *flags);
 int gecm_dev_set_tape(gecm_dev *d, const uint8_t *tape, size_t len);
 /* stage 1: asynchronous on the context's stream; HIP events bracket the kernel */
 /* lanes_per_curve: 1 = one curve per lane, 2 = X and Z of a curve on two adjacent lanes (for batches

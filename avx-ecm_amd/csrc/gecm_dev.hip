@@ -428,6 +428,36 @@ extern "C" int gecm_dev_build(gecm_dev *d, const uint64_t *sigma, size_t count, 
     return 0;
 }
 
+extern "C" int gecm_dev_normalize(gecm_dev *d, uint32_t *flags)
+{
+    HIPCHK(hipSetDevice(d->device));
+    if (!d->stride || !d->ncurves || !flags) {
+        g_err = "gecm_dev_normalize: no batch";
+        return -2;
+    }
+    if (d->r3.empty() || (d->multi && !d->have_groups)) {
+        g_err = d->multi ? "gecm_dev_normalize: the moduli of the batch are not set" : "gecm_dev_normalize: inversion constants missing";
+        return -2;
+    }
+    if (d->flags_cap < d->stride) {
+        (void)hipFree(d->dFlags);
+        d->dFlags = nullptr;
+        d->flags_cap = 0;
+        HIPCHK(hipMalloc(&d->dFlags, d->stride * 4));
+        d->flags_cap = d->stride;
+    }
+    gecm_modconst mc = modconst(d);
+    HIPCHK(hipEventRecord(d->ev0, d->stream));
+    d->k1->normalize(d->stream, &mc, d->dX, d->dZ, d->dFlags, d->stride);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(d->ev1, d->stream));
+    HIPCHK(hipMemcpyAsync(flags, d->dFlags, d->ncurves * 4, hipMemcpyDeviceToHost, d->stream));
+    HIPCHK(hipStreamSynchronize(d->stream));
+    HIPCHK(hipEventElapsedTime(&d->build_ms, d->ev0, d->ev1));
+    d->timed = false;
+    return 0;
+}
+
 extern "C" int gecm_dev_fill_twin(gecm_dev *dst, gecm_dev *src, const uint32_t *r2)
 {
     HIPCHK(hipSetDevice(src->device));

@@ -655,6 +655,75 @@ k_build_multi(const uint64_t *__restrict__ sigma, uint32_t *__restrict__ X, uint
 }
 #undef GECM_BUILD_BODY
 
+// ---------------------------------------------------------------- normalisation
+// X <- X/Z, Z <- 1 for one curve per lane: the canonical x = X/Z mod N a standard save line holds.  X, Z come in
+// canonical (every stage-1 kernel and every upload leaves them so).  z R goes through build_invert — the multiply by R
+// mod N that keeps it what it is, fe_invert, the R^3 step: z^-1 R, a product (< 0.675 K) — then x R * z^-1 R / R, a
+// product again, and out through the multiply by R mod N and one conditional subtraction, the tail of k_to_mont and
+// k_build.  A lane whose Z has no inverse stores nothing but its flag.  Three out-of-line multiplies (ModKOut) next
+// to one inversion, once per batch: small code before speed.
+// (a macro for the reason given at GECM_STAGE1_BODY; the constants are in `k`, an S2Const<NL>)
+#define GECM_NORMALIZE_BODY                                                     \
+    const uint32_t idx = blockIdx.x * 64u + threadIdx.x;                        \
+    const ModKOut<NL> mm{k.m};                                                  \
+    Fe<NL> x, z, zi;                                                            \
+    fe_load(z, Z, stride, idx);                                                 \
+    const bool ok = build_invert(zi, z, k, mm);                                 \
+    fe_load(x, X, stride, idx);                                                 \
+    fe_mul(x, x, zi, mm);                                                       \
+    fe_mul(x, x, k.one, mm);                                                    \
+    fe_cond_sub_n(x, k.m);                                                      \
+    if (ok) {                                                                   \
+        fe_store(X, stride, idx, x);                                            \
+        fe_store(Z, stride, idx, k.one);                                        \
+    }                                                                           \
+    flags[idx] = ok ? 0u : 1u;
+
+template <int NL>
+__global__ void __launch_bounds__(64, 2)
+k_normalize(uint32_t *__restrict__ X, uint32_t *__restrict__ Z, uint32_t *__restrict__ flags, size_t stride, S2Const<NL> k)
+{
+    GECM_NORMALIZE_BODY
+}
+
+template <int NL>
+__global__ void __launch_bounds__(64, 2)
+k_normalize_multi(uint32_t *__restrict__ X, uint32_t *__restrict__ Z, uint32_t *__restrict__ flags, size_t stride,
+                  ModGroups<NL> groups)
+{
+    const S2Const<NL> &k = mod_consts<S2Const<NL>>(groups, blockIdx.x);
+    GECM_NORMALIZE_BODY
+}
+#undef GECM_NORMALIZE_BODY
+
+#if GECM_HAS_LANE
+// a modulus per lane: the same steps with the lane's constants (ModV); its multiplies are inline, the per-lane kernels
+// being built for 8 to 15 limbs only
+template <int NL>
+__global__ void __launch_bounds__(64, 2)
+k_normalize_lane(uint32_t *__restrict__ X, uint32_t *__restrict__ Z, uint32_t *__restrict__ flags, size_t stride,
+                 LaneGroups<NL> g)
+{
+    const uint32_t idx = blockIdx.x * 64u + threadIdx.x;
+    GECM_LANE_CONSTS
+    Fe<NL> x, z, c, t, gc;
+    fe_load(z, Z, stride, idx);
+    fe_canonical_mont(c, z, k.one, k.m);          // canonical z R
+    const bool ok = fe_invert(t, gc, c, k.m, k.inv_iters);
+    fe_mul(z, t, k.r3, k.m);                      // (z R)^-1 R^3 / R = z^-1 R
+    fe_load(x, X, stride, idx);
+    fe_mul(x, x, z, k.m);
+    fe_mul(x, x, k.one, k.m);
+    fe_cond_sub_n(x, k.m);
+    if (ok) {
+        fe_get(t, k.one);
+        fe_store(X, stride, idx, x);
+        fe_store(Z, stride, idx, t);
+    }
+    flags[idx] = ok ? 0u : 1u;
+}
+#endif
+
 #endif
 #if GECM_HAS_PART(2)
 // ---------------------------------------------------------------- stage 2
@@ -964,6 +1033,23 @@ static void launch_build(void *stream, const gecm_modconst *mc, const uint64_t *
     hipLaunchKernelGGL(k_build<GECM_NL>, grid, block, 0, (hipStream_t)stream, sigma, X, Z, S, flags, stride, s2_const(mc), r2);
 }
 
+static void launch_normalize(void *stream, const gecm_modconst *mc, uint32_t *X, uint32_t *Z, uint32_t *flags, size_t stride)
+{
+    const dim3 grid((unsigned)(stride / 64)), block(64);
+#if GECM_HAS_LANE
+    if (mc->groups && mc->curve_group) {
+        hipLaunchKernelGGL(k_normalize_lane<GECM_NL>, grid, block, 0, (hipStream_t)stream, X, Z, flags, stride,
+                           lane_groups(mc));
+        return;
+    }
+#endif
+    if (mc->groups)
+        hipLaunchKernelGGL(k_normalize_multi<GECM_NL>, grid, block, 0, (hipStream_t)stream, X, Z, flags, stride,
+                           mod_groups(mc));
+    else
+        hipLaunchKernelGGL(k_normalize<GECM_NL>, grid, block, 0, (hipStream_t)stream, X, Z, flags, stride, s2_const(mc));
+}
+
 static void pack_group(const gecm_modconst *mc, void *out)
 {
     GroupConst<GECM_NL> c;
@@ -976,7 +1062,7 @@ extern "C" const gecm_kernels_p1 *CAT(CAT(gecm_kernels_, GECM_NL), _p1)(void)
 {
     static const gecm_kernels_p1 t = {launch_stage1, launch_canon, launch_from_mont, launch_to_mont, launch_l0, launch_l0_inv,
                                       launch_gcd_scan, launch_build, FPolicy<GECM_NL>::G, pack_group, sizeof(GroupConst<GECM_NL>),
-                                      GECM_MANIFEST, GECM_HAS_LANE};
+                                      GECM_MANIFEST, GECM_HAS_LANE, launch_normalize};
     return &t;
 }
 #endif

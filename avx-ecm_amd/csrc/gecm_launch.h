@@ -112,6 +112,10 @@ struct gecm_kernels_p1 {
     size_t group_bytes;
     const char *manifest;         /* the hash of the sources the object was compiled from (Makefile: K_SHA) */
     int has_lane;                 /* the per-lane kernels are built for this limb count (8 .. 15 limbs) */
+    /* X <- X/Z, Z <- R mod N for every curve whose Z has an inverse, canonical; flags[curve] = 1 and X, Z untouched
+     * where it has none (needs mc->r3 and inv_iters; multi-modulus and lane-packed mc as for gcd_scan).  Last member:
+     * the ones above keep their places. */
+    void (*normalize)(void *stream, const gecm_modconst *mc, uint32_t *X, uint32_t *Z, uint32_t *flags, size_t stride);
 };
 
 /* Part 2: stage 2 (a multi-modulus mc takes K = 1 only). */

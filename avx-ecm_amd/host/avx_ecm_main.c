@@ -3,6 +3,7 @@
  *     avx-ecm input curves B1 [threads] [B2] [sigma]
  *     avx-ecm -f FILE curves B1 [threads] [B2] [sigma]      (a list of inputs, run_file)
  *     avx-ecm -r FILE B1 [B2]                               (go on from resume lines, run_resume)
+ *     avx-ecm -x FILE B1 [B2]                               (take resume lines to a higher B1, run_resume)
  *
  * Same positional arguments as the reference (main.c:380-384, 459-460, 537-559) and the same FILES, byte for byte:
  * save_b1.txt (GMP-ECM resume lines, ecm.c:1372-1380), ecm_results.txt (factor lines, ecm.c:1356-1367, 1510-1522)
@@ -113,6 +114,10 @@ typedef struct {
      * it is complete, the lines are save lines: nothing is added to save_b1.txt and stage-1 factors are old news) */
     const struct resume_t *res;
     int first_range, s1_complete;
+    /* avx-ecm -x: the lines are complete to the standard bound ext_from and go on to B1 in nranges extension segments
+     * (gecm_stage1_extend_segment); every line written is a normalised standard line (gecm_format_save_line_std) */
+    int extend;
+    uint64_t ext_from;
 } run_t;
 
 typedef struct {
@@ -319,6 +324,18 @@ static int step_stage1(job_t *j)
     return rc;
 }
 
+/* -x: one extension segment, then the normalisation every standard line needs and the factor scan */
+static int step_extend(job_t *j)
+{
+    gecm_ctx *ctx = j->part->ctx;
+    int rc = gecm_stage1_extend_segment(ctx, j->b1_done, j->B1, j->range);
+    if (rc == 0) rc = gecm_sync(ctx);
+    if (rc == 0) j->kernel_ms += gecm_last_kernel_ms(ctx);
+    if (rc == 0 && gecm_normalize_points(ctx) < 0) rc = -1;
+    if (rc == 0 && gecm_scan_factors(ctx, 1, NULL) < 0) rc = -1;
+    return rc;
+}
+
 static int step_stage2_init(job_t *j)
 {
     const int rc = gecm_stage2_init(j->part->ctx, 0, 0);                  /* ecm.c:1401-1407 */
@@ -446,7 +463,8 @@ static void *fmt_run(void *arg)
     for (size_t u = f->lo; u < f->hi; u++) {
         size_t k;
         const part_t *p = locate(f->v, u, &k);
-        int n = gecm_format_resume_line(p->ctx, k, f->b1_field, line, sizeof line);
+        int n = f->v->run->extend ? gecm_format_save_line_std(p->ctx, k, line, sizeof line)    /* at the context's B1 */
+                                  : gecm_format_resume_line(p->ctx, k, f->b1_field, line, sizeof line);
         f->lines[u] = n > 0 ? strdup(line) : NULL;
     }
     return NULL;
@@ -664,6 +682,32 @@ static int pass_stage1(pass_t *ps)
     return 0;
 }
 
+/* -x: the extension segments of the pass's curves, one after the other; checkpoint.txt gets the standard lines of
+ * every segment's end but the last, whose lines are the save lines; 0, or -1 after an error */
+static int pass_extend(pass_t *ps)
+{
+    run_t *R = ps->run;
+    const double t = now();
+    gecm_stage1_stats st;
+    memset(&st, 0, sizeof st);
+    for (int sg = 0; sg < R->nranges; sg++) {
+        gecm_extend_desc d;
+        if (gecm_stage1_describe_extend(R->ext_from, R->B1, (uint32_t)sg, &d)) { fprintf(stderr, "%s\n", gecm_last_error()); return -1; }
+        plog(ps, "Extending Stage 1 over (%lu : %lu]: %lu primes and %lu further prime-power steps\n", (unsigned long)d.lo,
+             (unsigned long)d.hi, (unsigned long)d.nprimes, (unsigned long)d.power_steps);
+        for (int g = 0; g < R->gpus; g++) { ps->jobs[g].B1 = R->B1; ps->jobs[g].range = (uint32_t)sg; ps->jobs[g].b1_done = R->ext_from; }
+        if (run_all(ps->jobs, R->gpus, step_extend, NULL, 0)) return -1;
+        gecm_get_stage1_stats(ps->v.part[0].ctx, &st);
+        plog(ps, "Stage 1 complete to %lu at prime %lu with %lu point-adds and %lu point-doubles\n", (unsigned long)d.hi,
+             (unsigned long)st.last_prime, (unsigned long)st.ptadds, (unsigned long)st.ptdups);
+        if (sg + 1 < R->nranges && pass_checkpoint(ps, d.hi)) return -1;
+    }
+    const double t_stage1 = now() - t;
+    plog(ps, "Stage 1 took %1.4f seconds\n", t_stage1);
+    plog(ps, "(%.1f curves/sec; kernel %.1f ms on GPU 0)\n", (double)ps->v.ucurves / t_stage1, ps->jobs[0].kernel_ms);
+    return 0;
+}
+
 /* stage 2 (ecm.c:1394-1528); what it prints goes to s2log, which comes after save_b1.txt; 0, or -1 after an error */
 static int pass_stage2(pass_t *ps, text_t *s2log)
 {
@@ -733,7 +777,7 @@ static void *pass_run(void *arg)
     plog(ps, "\nCommencing curves %zu-%zu of %zu\n", lines_per_batch * v->b0, lines_per_batch * (v->b0 + v->nb) - 1,
          (size_t)R->threads * R->per_thread);                                                      /* ecm.c:1201 */
     plog(ps, "Building curves took %1.4f seconds.\n", t_build);                                    /* ecm.c:1204 */
-    if ((!R->s1_complete && pass_stage1(ps)) || (R->do_stage2 && pass_stage2(ps, &s2log))) goto out;
+    if ((!R->s1_complete && (R->extend ? pass_extend(ps) : pass_stage1(ps))) || (R->do_stage2 && pass_stage2(ps, &s2log))) goto out;
     output_settle(v, &o);
     turn_done(R, GPU, i, o.found ? FOUND : DONE);   /* the GPUs go to the next pass */
 
@@ -1077,7 +1121,11 @@ static int multi_run(const char **ns, const char *const *logs, size_t n, run_t *
         rz = malloc(bytes);
         if (!rx || !rz) { fprintf(stderr, "out of memory\n"); exit(2); }
         pack_residues(&cfg, rl, total, 0, total, rx, rz);
-        rc = gecm_resume_points_multi(mc, sigma, which, rx, rz, total, R->B1) < 0 || gecm_scan_factors(mc, 1, NULL) < 0;
+        if (R->extend)      /* -x: one segment from the lines' common bound to B1, then the standard lines' normalisation */
+            rc = gecm_resume_points_multi(mc, sigma, which, rx, rz, total, 0) < 0 || gecm_stage1_extend(mc, R->ext_from, R->B1) ||
+                 gecm_sync(mc) || gecm_normalize_points(mc) < 0 || gecm_scan_factors(mc, 1, NULL) < 0;
+        else
+            rc = gecm_resume_points_multi(mc, sigma, which, rx, rz, total, R->B1) < 0 || gecm_scan_factors(mc, 1, NULL) < 0;
     } else if (rc == 0) {
         rc = gecm_build_curves_multi(mc, sigma, which, total) < 0;
         if (rc == 0) rc = gecm_stage1(mc, R->B1) || gecm_sync(mc) || gecm_scan_factors(mc, 1, NULL) < 0;
@@ -1096,7 +1144,7 @@ static int multi_run(const char **ns, const char *const *logs, size_t n, run_t *
     if (!rc)
         printf("multi-modulus pass: %zu inputs, %zu curves%s, %s-packed, %s%s, %1.4f seconds of kernels after stage 1\n", n,
                rl ? total : count[0], rl ? " in all" : " each", gecm_get_multi_packing(mc) == GECM_PACK_LANE ? "lane" : "wave",
-               rl ? "resumed after stage 1" : "stage 1", R->do_stage2 ? " and stage 2" : "", gecm_last_kernel_ms(mc) / 1000.0);
+               !rl ? "stage 1" : R->extend ? "stage 1 extended" : "resumed after stage 1", R->do_stage2 ? " and stage 2" : "", gecm_last_kernel_ms(mc) / 1000.0);
     gecm_destroy(mc);
     free(rx); free(rz);
     return rc ? 2 : 0;
@@ -1221,18 +1269,30 @@ static int run_file(int argc, char **argv)
  * B1) go to stage 2 alone and save_b1.txt is left as it is.  One N: the one-input path, on the first GPU.  Several N:
  * multi-modulus passes packed as -f packs its inputs — stage 2 only, a multi pass stays within one prime range — and a
  * group too large for one takes the one-input path.  A number's lines stand together: the same N in two places, with
- * another between, is refused.  Everything is checked before anything runs or is written. */
+ * another between, is refused.  Everything is checked before anything runs or is written.
+ *
+ * avx-ecm -x FILE B1 [B2] reads the same files and takes their lines from the standard bound they are complete to
+ * (gecm_resume_line_std_bound: B1 - 1 for a reference line within one prime range, the field itself for a standard line)
+ * on to B1 with the standard multiplier, extension segment by segment.  After every segment the curves are
+ * normalised; checkpoint.txt gets the standard lines at every segment's end but the last, save_b1.txt those at B1; then
+ * stage 2 if B2 > B1.  Grouping, numbering and the stopping rule are -r's.  Refused on top of what -r refuses: lines of one
+ * N complete to different bounds, a bound above B1, a reference line above one prime range, and several N when the
+ * extension takes more than one segment. */
 static const char *resume_usage = "usage: avx-ecm -r $file $B1 [$B2]\n"
                                   "       (resume lines as in save_b1.txt / checkpoint.txt, or of a GMP-ECM -save file)\n";
+
+static const char *extend_usage = "usage: avx-ecm -x $file $B1 [$B2]\n"
+                                  "       (resume lines as for -r, complete to any bound up to $B1: stage 1 is extended to $B1)\n";
 
 typedef struct {
     size_t first, count;       /* lines of the file */
     uint32_t range;            /* the range stage 1 goes on with; the range count: complete */
+    uint64_t from;             /* -x: the standard bound the lines are complete to (gecm_resume_line_std_bound) */
     char ndec[MPL_MAXL * 10 + 16];
 } rgroup_t;
 
-/* one group on the one-input path */
-static int resume_single(const rgroup_t *g, const rline_t *lines, char **rargv, int rargc)
+/* one group on the one-input path; extend: -x */
+static int resume_single(const rgroup_t *g, const rline_t *lines, char **rargv, int rargc, int extend)
 {
     static run_t R;
     memset(&R, 0, sizeof R);
@@ -1241,19 +1301,22 @@ static int resume_single(const rgroup_t *g, const rline_t *lines, char **rargv, 
     const resume_t res = {lines + g->first, g->count};
     R.res = &res;
     R.gpus = 1;
-    R.nranges = gecm_stage1_ranges(R.B1);
-    R.first_range = (int)g->range;
+    R.nranges = extend ? gecm_stage1_extend_segments(g->from, R.B1) : gecm_stage1_ranges(R.B1);
+    R.first_range = extend ? 0 : (int)g->range;
     R.s1_complete = R.first_range >= R.nranges;
+    R.extend = extend;
+    R.ext_from = g->from;
     R.rd = (gecm_stage1_range_desc *)calloc((size_t)R.nranges, sizeof *R.rd);
     if (!R.rd) { fprintf(stderr, "out of memory\n"); return 2; }
-    for (int r = R.first_range; r < R.nranges && !R.rd_rc; r++)
+    for (int r = R.first_range; r < R.nranges && !R.rd_rc && !extend; r++)
         R.rd_rc = gecm_stage1_describe_range(R.B1, R.B2, (uint32_t)r, &R.rd[r]);
     if (R.rd_rc) { fprintf(stderr, "%s\n", gecm_last_error()); return 2; }
     static gecm_ctx *ctx[2][MAX_GPUS];
     if (make_contexts(ctx[0], 1, 1, g->ndec, NULL)) return 2;
     uint64_t mem_free, budget;
     const size_t batches_per_pass = pass_batches(&R, ctx[0][0], 1, 1, &mem_free, &budget);
-    printf("resuming %zu curves on N = %s %s\n", g->count, g->ndec, R.s1_complete ? "after stage 1" : "inside stage 1");
+    if (extend) printf("extending %zu curves on N = %s from B1 = %lu to %lu\n", g->count, g->ndec, (unsigned long)g->from, (unsigned long)R.B1);
+    else printf("resuming %zu curves on N = %s %s\n", g->count, g->ndec, R.s1_complete ? "after stage 1" : "inside stage 1");
     run_begin(&R);
     if (run_passes(&R, ctx, 1, 1, batches_per_pass)) return 2;
     if (R.fr.valid) gecm_pairmap_release(&R.fr.pm);
@@ -1262,13 +1325,14 @@ static int resume_single(const rgroup_t *g, const rline_t *lines, char **rargv, 
     return R.failed ? 2 : 0;
 }
 
-static int run_resume(int argc, char **argv)
+static int run_resume(int argc, char **argv, int extend)
 {
-    if (argc < 4) { printf("%s", resume_usage); return 1; }
+    const char *usage = extend ? extend_usage : resume_usage;
+    if (argc < 4) { printf("%s", usage); return 1; }
     const int packing = cli_packing();
     if (packing < 0) return 1;
     FILE *f = fopen(argv[2], "r");
-    if (!f) { printf("cannot read %s\n%s", argv[2], resume_usage); return 1; }
+    if (!f) { printf("cannot read %s\n%s", argv[2], usage); return 1; }
     /* the run's arguments through the one parser: curves B1 threads [B2], one thread, the curve count per group */
     char ncurves[32] = "1", one[] = "1";
     char *rargv[4] = {ncurves, argv[3], one, argc > 4 ? argv[4] : NULL};
@@ -1322,8 +1386,20 @@ static int run_resume(int argc, char **argv)
             if (bad) break;
             ngroups++;
             n_cur = n;
+            g->range = 0;
+            g->from = 0;
+            if (extend) {
+                /* the standard bound of the lines: a reference line above one prime range has none, and none may lie above B1 */
+                if (gecm_resume_line_std_bound(l->text, &g->from)) { printf("%s line %zu: %s\n", argv[2], lineno, gecm_last_error()); bad = 1; break; }
+                if (g->from < 1 || g->from > R0.B1) {
+                    printf("%s line %zu: the line is complete to B1 = %lu, which is not in [1, %lu]: stage 1 is extended upwards only\n",
+                           argv[2], lineno, (unsigned long)g->from, (unsigned long)R0.B1);
+                    bad = 1;
+                    break;
+                }
+            }
             /* what the B1 field says about a run to B1: the one refusal that names what is not offered */
-            if (gecm_stage1_resume_range(R0.B1, l->rec.b1, &g->range)) {
+            else if (gecm_stage1_resume_range(R0.B1, l->rec.b1, &g->range)) {
                 printf("%s line %zu: B1 field %lu is neither B1 = %lu nor a checkpoint of a run to it: stage 1 is extended from "
                        "no other B1 (the reference's stage 1 is not a product of prime powers cut at that prime)\n",
                        argv[2], lineno, (unsigned long)l->rec.b1, (unsigned long)R0.B1);
@@ -1332,7 +1408,14 @@ static int run_resume(int argc, char **argv)
             }
         }
         rgroup_t *g = &groups[ngroups - 1];
-        if (l->rec.b1 != lines[g->first].rec.b1) {
+        uint64_t from_l = 0;
+        if (extend && (gecm_resume_line_std_bound(l->text, &from_l) || from_l != g->from)) {
+            printf("%s line %zu: the line is not complete to the bound %lu of the lines on this N before it\n", argv[2], lineno,
+                   (unsigned long)g->from);
+            bad = 1;
+            break;
+        }
+        if (!extend && l->rec.b1 != lines[g->first].rec.b1) {
             printf("%s line %zu: B1 field %lu differs from the %lu of the lines on this N before it\n", argv[2], lineno,
                    (unsigned long)l->rec.b1, (unsigned long)lines[g->first].rec.b1);
             bad = 1;
@@ -1357,8 +1440,15 @@ static int run_resume(int argc, char **argv)
     free(pending);
     if (oom) { fprintf(stderr, "out of memory\n"); bad = 1; }
     const uint32_t nranges = (uint32_t)gecm_stage1_ranges(R0.B1);
-    if (!bad && !nlines) { printf("%s holds no resume line\n%s", argv[2], resume_usage); bad = 1; }
-    for (size_t i = 0; i < ngroups && !bad; i++) {
+    if (!bad && !nlines) { printf("%s holds no resume line\n%s", argv[2], usage); bad = 1; }
+    for (size_t i = 0; i < ngroups && !bad && extend; i++)
+        if (ngroups > 1 && gecm_stage1_extend_segments(groups[i].from, R0.B1) > 1) {
+            printf("%s holds lines on %zu numbers and the extension from %lu to %lu takes several segments: several numbers are "
+                   "extended within one segment only (a multi-modulus pass stays within one prime range); extend them one file "
+                   "per number\n", argv[2], ngroups, (unsigned long)groups[i].from, (unsigned long)R0.B1);
+            bad = 1;
+        }
+    for (size_t i = 0; i < ngroups && !bad && !extend; i++) {
         if (groups[i].range >= nranges && !R0.do_stage2) {
             printf("stage 1 of these lines is complete at B1 = %lu: nothing to do without B2 > B1\n%s", (unsigned long)R0.B1, resume_usage);
             bad = 1;
@@ -1374,7 +1464,8 @@ static int run_resume(int argc, char **argv)
         printf("starting process %d: %zu resume lines on %zu number(s) from %s\n", (int)getpid(), nlines, ngroups, argv[2]);
         const size_t cap = env_count("GECM_PASS_CURVES") ? (size_t)env_count("GECM_PASS_CURVES") : FULL_BATCH;
         R0.t_start = now();
-        R0.s1_complete = 1;                        /* the multi passes: stage 2 only */
+        R0.s1_complete = !extend;                  /* the multi passes: stage 2 only; -x: one extension segment first */
+        R0.extend = extend;
         R0.nbatches = 0;
         size_t p0 = 0;                             /* the pending multi pass: groups p0 .. i */
         size_t *pcount = (size_t *)calloc(ngroups + 1, sizeof *pcount);   /* curves of the groups */
@@ -1391,8 +1482,10 @@ static int run_resume(int argc, char **argv)
                     in_packing = GECM_PACK_LANE;
             }
             if (i < ngroups) pcount[i] = groups[i].count;
-            if (i > p0 && (i == ngroups || alone || in_packing != pend_packing ||
+            /* (-x: the curves of a pass run one tape, so its groups are complete to one bound) */
+            if (i > p0 && (i == ngroups || alone || in_packing != pend_packing || groups[i].from != groups[p0].from ||
                            gecm_multi_positions(pcount + p0, i + 1 - p0, pend_packing) > cap)) {
+                R0.ext_from = groups[p0].from;
                 const size_t n_in = i - p0, total = groups[i - 1].first + groups[i - 1].count - groups[p0].first;
                 const char **ns = (const char **)malloc(n_in * sizeof *ns);
                 uint64_t *sigma = (uint64_t *)malloc(total * sizeof *sigma);
@@ -1426,7 +1519,7 @@ static int run_resume(int argc, char **argv)
                 continue;
             }
             snprintf(ncurves, sizeof ncurves, "%zu", groups[i].count);
-            const int r1 = resume_single(&groups[i], lines, rargv, rargc);
+            const int r1 = resume_single(&groups[i], lines, rargv, rargc, extend);
             if (r1 > rc) rc = r1;
             p0 = i + 1;
         }
@@ -1442,6 +1535,7 @@ static int run_resume(int argc, char **argv)
 int main(int argc, char **argv)
 {
     if (argc > 1 && strcmp(argv[1], "-f") == 0) return run_file(argc, argv);
-    if (argc > 1 && strcmp(argv[1], "-r") == 0) return run_resume(argc, argv);
+    if (argc > 1 && strcmp(argv[1], "-r") == 0) return run_resume(argc, argv, 0);
+    if (argc > 1 && strcmp(argv[1], "-x") == 0) return run_resume(argc, argv, 1);
     return run_single(argc, argv);
 }

@@ -57,6 +57,18 @@ const char *gecm_version(void)
 }
 int gecm_device_count(void) { return gecm_dev_count(); }
 
+/* which tape: kind 0 = the ecm_stage1 call number b of a reference run to B1 = a (gecm_tape_build_stage1_range),
+ * kind 1 = the extension segment (a, b] of the standard multiplier (gecm_tape_build_extend) */
+typedef struct {
+    int kind;
+    uint64_t a, b;
+} tape_key;
+static int key_eq(const tape_key *x, const tape_key *y) { return x->kind == y->kind && x->a == y->a && x->b == y->b; }
+static int tape_build(gecm_tape_t *t, const tape_key *k, int threads)
+{
+    return k->kind ? gecm_tape_build_extend(t, k->a, k->b, threads) : gecm_tape_build_stage1_range(t, k->a, (uint32_t)k->b, threads);
+}
+
 struct gecm_ctx {
     int device;
     gecm_mod mod;        /* the context's number; of a multi-modulus context the largest (what gecm_get_config reports) */
@@ -67,11 +79,12 @@ struct gecm_ctx {
     uint8_t *bad;
     uint32_t *hx, *hz;   /* last downloaded plain x, z: [nl][batch] */
     int have_plain;
+    int normalized;      /* X = x/z, Z = 1 since the last gecm_normalize_points; norm_left[pos] = 1: that curve's Z has no inverse */
+    uint8_t *norm_left;
     uint64_t B1;
-    /* tape cache: the tape of (tape_B1, tape_range), one ecm_stage1 call of the reference */
+    /* tape cache: the tape of tape_k, one ecm_stage1 call of the reference or one extension segment */
     gecm_tape_t tape;
-    uint64_t tape_B1;
-    uint32_t tape_range;
+    tape_key tape_k;
     int tape_on_dev;
     double last_ms;
     /* counters of the stage 1 in progress: summed over the ranges run since range 0 (work->ptadds / ptdups are
@@ -81,8 +94,7 @@ struct gecm_ctx {
     pthread_t pf_thread;
     int pf_active, pf_rc;
     gecm_tape_t pf_tape;
-    uint64_t pf_B1;
-    uint32_t pf_range;
+    tape_key pf_k;
     /* stage 2 */
     gecm_s2_plan s2;
     int s2_ready;
@@ -112,8 +124,7 @@ struct gecm_ctx {
     gecm_dev *dev_f;
     int ff_k, ff_sign, ff_nl, ff_on, ff_pending, ff_loaded, last_on_f;
     uint64_t ff_c;           /* Mw = 2^ff_k - ff_c for ff_sign > 0 (1: Mersenne form), 2^ff_k + 1 for ff_sign < 0 */
-    uint64_t ff_tape_B1;
-    uint32_t ff_tape_range;
+    tape_key ff_tape_k;
     mpl_t ff_M, ff_r_mod_m;  /* Mw; 2^(28 ff_nl) mod Mw */
     uint32_t *ff_n28;        /* n, kp, one for dev_f */
     /* multi-modulus context (gecm_create_multi): grp[] holds every modulus's N and constants (at this
@@ -258,6 +269,9 @@ int gecm_create(gecm_ctx **out, int device, const char *n_str, int digitbits)
 
 static void free_batch(gecm_ctx *c)
 {
+    free(c->norm_left);
+    c->norm_left = NULL;
+    c->normalized = 0;
     free(c->sigma); free(c->bad); free(c->hx); free(c->hz); free(c->hacc); free(c->hfail);
     free(c->flags[0]); free(c->flags[1]); free(c->hg[0]); free(c->hg[1]);
     c->flags[0] = c->flags[1] = NULL;
@@ -778,32 +792,32 @@ static int ff_settle(gecm_ctx *c)
 static void *prefetch_run(void *arg)
 {
     gecm_ctx *c = (gecm_ctx *)arg;
-    c->pf_rc = gecm_tape_build_stage1_range(&c->pf_tape, c->pf_B1, c->pf_range, host_threads());
+    c->pf_rc = tape_build(&c->pf_tape, &c->pf_k, host_threads());
     return NULL;
 }
 
-/* the tape of ecm_stage1's call number `range` for bound B1 into c->tape: kept from the last call, taken from the
- * helper thread that compiled it while the device ran the range before, or compiled now */
-static int tape_for(gecm_ctx *c, uint64_t B1, uint32_t range)
+/* the tape of key k into c->tape: kept from the last call, taken from the helper thread that compiled it while the
+ * device ran the launch before, or compiled now */
+static int tape_for(gecm_ctx *c, const tape_key *k)
 {
-    if (c->tape.ops && c->tape_B1 == B1 && c->tape_range == range) return GECM_OK;
+    if (c->tape.ops && key_eq(&c->tape_k, k)) return GECM_OK;
     int rc;
     if (c->pf_active) {
         pthread_join(c->pf_thread, NULL);
         c->pf_active = 0;
-        if (!c->pf_rc && c->pf_B1 == B1 && c->pf_range == range) {
+        if (!c->pf_rc && key_eq(&c->pf_k, k)) {
             gecm_tape_free(&c->tape);
             c->tape = c->pf_tape;
             memset(&c->pf_tape, 0, sizeof c->pf_tape);
-            c->tape_B1 = B1; c->tape_range = range; c->tape_on_dev = 0;
+            c->tape_k = *k; c->tape_on_dev = 0;
             return GECM_OK;
         }
         gecm_tape_free(&c->pf_tape);
     }
     gecm_tape_free(&c->tape);
-    rc = gecm_tape_build_stage1_range(&c->tape, B1, range, host_threads());
+    rc = tape_build(&c->tape, k, host_threads());
     if (rc) { set_err("gecm_stage1: tape build failed (%d)", rc); return rc == -1 ? GECM_ERR_NOMEM : GECM_ERR_STATE; }
-    c->tape_B1 = B1; c->tape_range = range; c->tape_on_dev = 0;
+    c->tape_k = *k; c->tape_on_dev = 0;
     return GECM_OK;
 }
 
@@ -820,26 +834,31 @@ int gecm_stage1_describe_range(uint64_t B1, uint64_t B2, uint32_t range, gecm_st
     return GECM_OK;
 }
 
-int gecm_stage1_range(gecm_ctx *c, uint64_t B1, uint32_t range)
+/* lane packing's refusal of two lanes per curve, with the error text set */
+static int lane_packing_refuses(const gecm_ctx *c)
 {
-    if (c && c->ff_pending) { int rcs = ff_settle(c); if (rcs) return rcs; }
-    if (!c || c->batch == 0) { set_err("gecm_stage1: no curves uploaded"); return GECM_ERR_STATE; }
-    if (B1 < 2 || B1 > GECM_B1_MAX) { set_err("gecm_stage1: B1 must be in [2, %llu]", (unsigned long long)GECM_B1_MAX); return GECM_ERR_ARG; }
-    if (c->multi && c->packing_used == GECM_PACK_LANE && c->lanes_per_curve == 2) {
-        set_err("gecm_stage1: a lane-packed multi-modulus batch runs one lane per curve, and this context is set to 2 "
-                "(gecm_set_lanes_per_curve)");
-        return GECM_ERR_STATE;
-    }
-    const uint32_t nranges = gecm_stage1_ranges_u(B1);
-    if (range >= nranges) { set_err("gecm_stage1_range: B1 = %llu has %u prime range(s)", (unsigned long long)B1, nranges); return GECM_ERR_ARG; }
-    int rc = tape_for(c, B1, range);
+    if (!(c->multi && c->packing_used == GECM_PACK_LANE && c->lanes_per_curve == 2)) return 0;
+    set_err("gecm_stage1: a lane-packed multi-modulus batch runs one lane per curve, and this context is set to 2 "
+            "(gecm_set_lanes_per_curve)");
+    return 1;
+}
+
+/* One stage-1 launch, of a reference range or of an extension segment: the tape of `key` onto the device (and onto the
+ * special-form twin when it runs there), the counters (`first`: they start again), the context's B1 afterwards, every
+ * cached result of the points dropped, the kernel started, and — next != NULL — the tape of the launch to follow
+ * handed to the helper thread.  An extension segment in which no prime gains a power has an empty tape and launches
+ * nothing.  The caller has checked its arguments and settled a pending twin. */
+static int stage1_launch(gecm_ctx *c, const tape_key *key, uint64_t B1, int first, const tape_key *next)
+{
+    int rc = tape_for(c, key);
     if (rc) return rc;
-    if (!c->tape_on_dev) {
+    const int idle = key->kind == 1 && c->tape.len == 0;
+    if (!c->tape_on_dev && !idle) {
         /* stream-ordered after the kernel of the range before; returns when the copy is done */
         if (gecm_dev_set_tape(c->dev, c->tape.ops, c->tape.len)) { set_err("%s", gecm_dev_error()); return GECM_ERR_DEVICE; }
         c->tape_on_dev = 1;
     }
-    if (range == 0) c->s1_ptadds = c->s1_ptdups = 0;
+    if (first) c->s1_ptadds = c->s1_ptdups = 0;
     c->s1_ptadds += c->tape.ptadds;
     c->s1_ptdups += c->tape.ptdups;
     c->s1_last_prime = c->tape.last_prime;
@@ -848,17 +867,18 @@ int gecm_stage1_range(gecm_ctx *c, uint64_t B1, uint32_t range)
     c->have_plain = 0;
     c->have_acc = 0;
     c->s2_ready = 0;
+    c->normalized = 0;
     c->scan_valid[0] = c->scan_valid[1] = 0;
+    if (idle) return GECM_OK;
     /* For a batch small enough for the eight-lane layout (generic moduli only) that layout beats the special
      * multiply in its two-lane form: 1.5x against 1.4x at 15 limbs, 2.2-2.4x at 30-37 limbs. */
     const int want = c->lanes_per_curve ? c->lanes_per_curve : gecm_dev_auto_lanes(c->dev);
     const int small_batch = want == 8 || want == 32;
     if (c->dev_f && c->ff_on && c->ff_loaded && !small_batch) {
         /* N | 2^k - 1: run the chain modulo 2^k - 1 with the F-form multiply; ff_settle brings X, Z back */
-        if (c->ff_tape_B1 != B1 || c->ff_tape_range != range) {
+        if (!key_eq(&c->ff_tape_k, key)) {
             if (gecm_dev_set_tape(c->dev_f, c->tape.ops, c->tape.len)) { set_err("%s", gecm_dev_error()); return GECM_ERR_DEVICE; }
-            c->ff_tape_B1 = B1;
-            c->ff_tape_range = range;
+            c->ff_tape_k = *key;
         }
         if (gecm_dev_stage1(c->dev_f, c->lanes_per_curve)) { set_err("%s", gecm_dev_error()); return GECM_ERR_DEVICE; }
         c->ff_pending = 1;
@@ -868,13 +888,78 @@ int gecm_stage1_range(gecm_ctx *c, uint64_t B1, uint32_t range)
         c->ff_loaded = 0;       /* the F-form copy of the points no longer matches */
         if (gecm_dev_stage1(c->dev, c->lanes_per_curve)) { set_err("%s", gecm_dev_error()); return GECM_ERR_DEVICE; }
     }
-    if (range + 1 < nranges && !c->pf_active) {
+    if (next && !c->pf_active) {
         /* while the device runs this range: the next one's tape (2 s of host time per 1e8 primes on 8 threads) */
-        c->pf_B1 = B1;
-        c->pf_range = range + 1;
+        c->pf_k = *next;
         c->pf_rc = 0;
         c->pf_active = pthread_create(&c->pf_thread, NULL, prefetch_run, c) == 0;
     }
+    return GECM_OK;
+}
+
+int gecm_stage1_range(gecm_ctx *c, uint64_t B1, uint32_t range)
+{
+    if (c && c->ff_pending) { int rcs = ff_settle(c); if (rcs) return rcs; }
+    if (!c || c->batch == 0) { set_err("gecm_stage1: no curves uploaded"); return GECM_ERR_STATE; }
+    if (B1 < 2 || B1 > GECM_B1_MAX) { set_err("gecm_stage1: B1 must be in [2, %llu]", (unsigned long long)GECM_B1_MAX); return GECM_ERR_ARG; }
+    if (lane_packing_refuses(c)) return GECM_ERR_STATE;
+    const uint32_t nranges = gecm_stage1_ranges_u(B1);
+    if (range >= nranges) { set_err("gecm_stage1_range: B1 = %llu has %u prime range(s)", (unsigned long long)B1, nranges); return GECM_ERR_ARG; }
+    const tape_key key = {0, B1, range}, next = {0, B1, (uint64_t)range + 1};
+    return stage1_launch(c, &key, B1, range == 0, range + 1 < nranges ? &next : NULL);
+}
+
+/* ---- extension with the standard multiplier ---------------------------------- */
+static int extend_args(const char *fn, uint64_t from, uint64_t to)
+{
+    if (from < 1 || to < from || to > GECM_B1_MAX) {
+        set_err("%s: need 1 <= from <= to <= %llu", fn, (unsigned long long)GECM_B1_MAX);
+        return GECM_ERR_ARG;
+    }
+    return GECM_OK;
+}
+
+int gecm_stage1_extend_segments(uint64_t from, uint64_t to)
+{
+    int rc = extend_args("gecm_stage1_extend_segments", from, to);
+    return rc ? rc : (int)gecm_extend_segments_plan(from, to);
+}
+
+int gecm_stage1_describe_extend(uint64_t from, uint64_t to, uint32_t seg, gecm_extend_desc *out)
+{
+    gecm_extend_info ei;
+    int rc = extend_args("gecm_stage1_describe_extend", from, to);
+    if (rc) return rc;
+    if (!out) { set_err("gecm_stage1_describe_extend: bad argument"); return GECM_ERR_ARG; }
+    rc = gecm_extend_segment_info(&ei, from, to, seg);
+    if (rc) { set_err("gecm_stage1_describe_extend: %s", rc == -1 ? "out of memory" : "no such segment"); return rc == -1 ? GECM_ERR_NOMEM : GECM_ERR_ARG; }
+    out->lo = ei.lo; out->hi = ei.hi; out->nprimes = ei.nprimes; out->power_steps = ei.power_steps; out->last_prime = ei.last_prime;
+    return GECM_OK;
+}
+
+int gecm_stage1_extend_segment(gecm_ctx *c, uint64_t from, uint64_t to, uint32_t seg)
+{
+    if (c && c->ff_pending) { int rcs = ff_settle(c); if (rcs) return rcs; }
+    int rc = extend_args("gecm_stage1_extend", from, to);
+    if (rc) return rc;
+    if (!c || c->batch == 0) { set_err("gecm_stage1_extend: no curves uploaded"); return GECM_ERR_STATE; }
+    if (lane_packing_refuses(c)) return GECM_ERR_STATE;
+    const uint32_t nseg = gecm_extend_segments_plan(from, to);
+    if (seg >= nseg) { set_err("gecm_stage1_extend_segment: the extension from %llu to %llu has %u segment(s)", (unsigned long long)from, (unsigned long long)to, nseg); return GECM_ERR_ARG; }
+    tape_key key = {1, 0, 0}, next = {1, 0, 0};
+    gecm_extend_segment_bounds(from, to, seg, &key.a, &key.b);
+    if (seg + 1 < nseg) gecm_extend_segment_bounds(from, to, seg + 1, &next.a, &next.b);
+    /* the context's B1 is the segment's hi: the points are complete to it, whatever follows */
+    return stage1_launch(c, &key, key.b, seg == 0, seg + 1 < nseg ? &next : NULL);
+}
+
+int gecm_stage1_extend(gecm_ctx *c, uint64_t from, uint64_t to)
+{
+    int rc = extend_args("gecm_stage1_extend", from, to);
+    if (rc) return rc;
+    const uint32_t nseg = gecm_extend_segments_plan(from, to);
+    for (uint32_t s = 0; s < nseg; s++)
+        if ((rc = gecm_stage1_extend_segment(c, from, to, s)) != 0) return rc;
     return GECM_OK;
 }
 
@@ -1079,6 +1164,64 @@ int gecm_stage1_factor(gecm_ctx *c, size_t k, char *dec, size_t declen, int *is_
         mpl_gcd(&g, &z, &m->N);
     }
     return gecm_mod_factor(m, &g, "gecm_stage1_factor", dec, declen, is_prp);
+}
+
+/* ---- normalisation and standard lines ---------------------------------------- */
+int gecm_normalize_points(gecm_ctx *c)
+{
+    if (c && c->ff_pending) { int rcs = ff_settle(c); if (rcs) return rcs; }
+    if (!c || c->batch == 0) { set_err("gecm_normalize_points: no curves uploaded"); return GECM_ERR_STATE; }
+    if (!c->multi && c->mod.have_report) {
+        set_err("gecm_normalize_points: not with a report modulus (gecm_set_report_modulus): x modulo the context's "
+                "modulus is not x modulo the number the lines name");
+        return GECM_ERR_STATE;
+    }
+    const size_t batch = c->batch;
+    uint32_t *flags = (uint32_t *)malloc(batch * sizeof(uint32_t));
+    uint8_t *left = (uint8_t *)calloc(batch, 1);
+    if (!flags || !left) { free(flags); free(left); return GECM_ERR_NOMEM; }
+    if (gecm_dev_normalize(c->dev, flags)) { free(flags); free(left); set_err("%s", gecm_dev_error()); return GECM_ERR_DEVICE; }
+    int any = 0;
+    for (size_t p = 0; p < batch; p++)
+        if (flags[p] && !(c->multi && c->pos_user[p] == GECM_PAD)) left[p] = (uint8_t)(any = 1);
+    free(flags);
+    free(c->norm_left);
+    c->norm_left = left;
+    c->normalized = 1;
+    c->last_ms = gecm_dev_last_build_ms(c->dev);
+    c->have_plain = 0;
+    c->s2_ready = 0;
+    c->scan_valid[0] = 0;
+    c->ff_loaded = 0;            /* the twin's copy of the points no longer matches: the next launch runs modulo N */
+    return any;
+}
+
+int gecm_points_normalized(const gecm_ctx *c) { return c && c->batch && c->normalized; }
+
+int gecm_format_save_line_std(gecm_ctx *c, size_t k, char *buf, size_t buflen)
+{
+    size_t pos;
+    const gecm_mod *m = c && buf ? curve_at(c, k, &pos) : NULL;
+    if (!m) return GECM_ERR_ARG;
+    if (!c->normalized) { set_err("gecm_format_save_line_std: the batch is not normalised (gecm_normalize_points)"); return GECM_ERR_STATE; }
+    int rc = fetch_plain(c);
+    if (rc) return rc;
+    static __thread char hn[MPL_MAXL * 10 + 2], hxs[MPL_MAXL * 10 + 2], hzs[MPL_MAXL * 10 + 2];
+    mpl_t v;
+    mpl_get_hex(hn, report_n(m));
+    mpl_from_limbs32(&v, c->hx + pos, c->batch, m->nl, LIMB_BITS);
+    mpl_get_hex(hxs, &v);
+    int n;
+    if (c->norm_left[pos]) {
+        mpl_from_limbs32(&v, c->hz + pos, c->batch, m->nl, LIMB_BITS);
+        mpl_get_hex(hzs, &v);
+        n = snprintf(buf, buflen, "METHOD=ECM; PARAM=0; SIGMA=%llu; B1=%llu; N=0x%s; X=0x%s; Z=0x%s; PROGRAM=AVX-ECM-STD;\n",
+                     (unsigned long long)c->sigma[pos], (unsigned long long)c->B1, hn, hxs, hzs);
+    } else
+        n = snprintf(buf, buflen, "METHOD=ECM; PARAM=0; SIGMA=%llu; B1=%llu; N=0x%s; X=0x%s; PROGRAM=AVX-ECM-STD;\n",
+                     (unsigned long long)c->sigma[pos], (unsigned long long)c->B1, hn, hxs);
+    if (n < 0 || (size_t)n >= buflen) { set_err("gecm_format_save_line_std: buffer too small"); return GECM_ERR_ARG; }
+    return n;
 }
 
 /* ---- stage 2 -------------------------------------------------------------------------------- */

@@ -184,6 +184,7 @@ __attribute__((constructor)) static void prime_range_from_env(void)
 
 typedef struct {
     const uint64_t *primes;
+    const uint8_t *reps;    /* chains per prime (an extension segment, gecm_tape_build_extend); NULL: the reference's rule */
     size_t lo, hi;
     uint64_t B1;
     gecm_tape_t t;
@@ -197,6 +198,10 @@ static void *tape_slice_run(void *arg)
     s->rc = 0;
     for (size_t k = s->lo; k < s->hi && !s->rc; k++) {  /* ecm.c:1824-1832 */
         const uint64_t q = s->primes[k];
+        if (s->reps) {
+            for (unsigned r = 0; r < s->reps[k] && !s->rc; r++) s->rc = gecm_tape_append_prac(&s->t, q);
+            continue;
+        }
         uint64_t c = 1;
         do {
             s->rc = gecm_tape_append_prac(&s->t, q);
@@ -204,6 +209,50 @@ static void *tape_slice_run(void *arg)
         } while (!s->rc && (c * q) < s->B1);
     }
     return NULL;
+}
+
+/* The chains of primes[first .. np) appended to t: the list is cut into slices compiled by up to `threads` worker
+ * threads and the pieces joined in order.  On an error t is freed. */
+static int tape_compile_slices(gecm_tape_t *t, const uint64_t *primes, const uint8_t *reps, size_t first, size_t np,
+                               uint64_t B1, int threads)
+{
+    const size_t cnt = np - first;
+    int nt = threads < 1 ? 1 : threads > 64 ? 64 : threads;
+    if ((size_t)nt > cnt / 4096 + 1) nt = (int)(cnt / 4096 + 1);
+    tape_slice sl[64];
+    pthread_t th[64];
+    for (int i = 0; i < nt; i++) {
+        sl[i].primes = primes; sl[i].reps = reps; sl[i].B1 = B1;
+        sl[i].lo = first + cnt * (size_t)i / (size_t)nt;
+        sl[i].hi = first + cnt * (size_t)(i + 1) / (size_t)nt;
+    }
+    for (int i = 1; i < nt; i++)
+        if (pthread_create(&th[i], NULL, tape_slice_run, &sl[i])) { tape_slice_run(&sl[i]); th[i] = 0; }
+    tape_slice_run(&sl[0]);
+    int rc = 0;
+    size_t total = t->len;
+    for (int i = 0; i < nt; i++) {
+        if (i > 0 && th[i]) pthread_join(th[i], NULL);
+        if (sl[i].rc) rc = sl[i].rc;
+        total += sl[i].t.len;
+    }
+    uint8_t *all = rc ? NULL : (uint8_t *)realloc(t->ops, total + 8);
+    if (!all) {
+        for (int i = 0; i < nt; i++) free(sl[i].t.ops);
+        gecm_tape_free(t);
+        return rc ? rc : -1;
+    }
+    t->ops = all;
+    for (int i = 0; i < nt; i++) {
+        if (sl[i].t.len) memcpy(t->ops + t->len, sl[i].t.ops, sl[i].t.len);
+        t->len += sl[i].t.len;
+        t->ptadds += sl[i].t.ptadds; t->ptdups += sl[i].t.ptdups; t->prac_calls += sl[i].t.prac_calls;
+        t->swaps += sl[i].t.swaps;
+        for (int r = 0; r < 4; r++) t->rule_count[r] += sl[i].t.rule_count[r];
+        free(sl[i].t.ops);
+    }
+    memset(t->ops + t->len, 0, 8);
+    return 0;
 }
 
 uint32_t gecm_stage1_ranges_plan(uint64_t B1)
@@ -239,44 +288,129 @@ int gecm_tape_build_stage1_range(gecm_tape_t *t, uint64_t B1, uint32_t range, in
         free(nx);
     }
     if (np > 1) {
-        int nt = threads < 1 ? 1 : threads > 64 ? 64 : threads;
-        if ((size_t)nt > (np - 1) / 4096 + 1) nt = (int)((np - 1) / 4096 + 1);
-        tape_slice sl[64];
-        pthread_t th[64];
-        for (int i = 0; i < nt; i++) {
-            sl[i].primes = primes; sl[i].B1 = B1;
-            sl[i].lo = 1 + (np - 1) * (size_t)i / (size_t)nt;
-            sl[i].hi = 1 + (np - 1) * (size_t)(i + 1) / (size_t)nt;
-        }
-        for (int i = 1; i < nt; i++)
-            if (pthread_create(&th[i], NULL, tape_slice_run, &sl[i])) { tape_slice_run(&sl[i]); th[i] = 0; }
-        tape_slice_run(&sl[0]);
-        int rc = 0;
-        size_t total = t->len;
-        for (int i = 0; i < nt; i++) {
-            if (i > 0 && th[i]) pthread_join(th[i], NULL);
-            if (sl[i].rc) rc = sl[i].rc;
-            total += sl[i].t.len;
-        }
-        uint8_t *all = rc ? NULL : (uint8_t *)realloc(t->ops, total + 8);
-        if (!all) {
-            for (int i = 0; i < nt; i++) free(sl[i].t.ops);
-            free(primes);
-            gecm_tape_free(t);
-            return rc ? rc : -1;
-        }
-        t->ops = all;
-        for (int i = 0; i < nt; i++) {
-            if (sl[i].t.len) memcpy(t->ops + t->len, sl[i].t.ops, sl[i].t.len);
-            t->len += sl[i].t.len;
-            t->ptadds += sl[i].t.ptadds; t->ptdups += sl[i].t.ptdups; t->prac_calls += sl[i].t.prac_calls;
-            t->swaps += sl[i].t.swaps;
-            for (int r = 0; r < 4; r++) t->rule_count[r] += sl[i].t.rule_count[r];
-            free(sl[i].t.ops);
-        }
-        memset(t->ops + t->len, 0, 8);
+        const int rc = tape_compile_slices(t, primes, NULL, 1, np, B1, threads);
+        if (rc) { free(primes); return rc; }
     }
     free(primes);
+    if (!t->ops) { t->ops = (uint8_t *)calloc(8, 1); if (!t->ops) return -1; }
+    return 0;
+}
+
+/* ---- extension segments: the standard multiplier -----------------------------------
+ * k_std(B) = the product over the primes p <= B of p^e, e the largest with p^e <= B.  Taking points that are complete
+ * to `from` on to `to` means multiplying by k_std(to) / k_std(from) = the product of p^(e_p(to) - e_p(from)); the work
+ * is cut at the multiples of the prime range strictly between the two bounds, and the state after every segment
+ * (lo, hi] is complete to hi.  Within a segment only the primes <= sqrt(hi) can gain a power beyond the first, and
+ * only the primes of (lo, hi] gain their first: those two sets are all that is sieved. */
+static unsigned std_exponent(uint64_t p, uint64_t x)
+{
+    unsigned e = 0;
+    if (p > x) return 0;
+    for (uint64_t q = p; ; q *= p) {          /* q = p^(e+1) <= x; the next power is compared without overflow */
+        e++;
+        if (q > x / p) break;
+    }
+    return e;
+}
+
+static uint64_t isqrt_u64(uint64_t x)
+{
+    uint64_t r = 0;
+    for (uint64_t bit = 1ull << 31; bit; bit >>= 1)
+        if ((r | bit) <= x / (r | bit)) r |= bit;
+    return r;
+}
+
+uint32_t gecm_extend_segments_plan(uint64_t from, uint64_t to)
+{
+    if (from < 1 || to < from) return 0;
+    if (to == from) return 1;
+    return (uint32_t)((to - 1) / g_prime_range - from / g_prime_range) + 1u;
+}
+
+int gecm_extend_segment_bounds(uint64_t from, uint64_t to, uint32_t seg, uint64_t *lo, uint64_t *hi)
+{
+    const uint32_t n = gecm_extend_segments_plan(from, to);
+    if (seg >= n) return -2;
+    const uint64_t first_cut = from / g_prime_range;           /* cut i lies at (first_cut + i) ranges, i = 1 .. n - 1 */
+    *lo = seg == 0 ? from : (first_cut + seg) * g_prime_range;
+    *hi = seg + 1 == n ? to : (first_cut + seg + 1) * g_prime_range;
+    return 0;
+}
+
+/* the odd primes that gain a power in (lo, hi] with the number of powers each gains, ascending: those <= sqrt(hi) that
+ * do, then every prime of (max(lo, sqrt(hi)), hi].  *twos = the powers 2 gains.  reps may be NULL (a description
+ * counts only); primes are returned only with reps. */
+static int extend_gather(uint64_t lo, uint64_t hi, uint64_t **primes_out, uint8_t **reps_out, size_t *np_out,
+                         unsigned *twos, gecm_extend_info *ei)
+{
+    const uint64_t root = isqrt_u64(hi);
+    size_t ns = 0, nb = 0;
+    uint64_t *small = gecm_primes_range(3, root + 1, &ns);
+    if (!small) return -1;
+    uint64_t big_lo = lo > root ? lo : root;
+    if (big_lo < 2) big_lo = 2;                           /* 2 is the doublings' */
+    uint64_t *big = gecm_primes_range(big_lo + 1, hi + 1, &nb);
+    if (!big) { free(small); return -1; }
+    uint64_t *pr = NULL;
+    uint8_t *reps = NULL;
+    if (primes_out) {
+        pr = (uint64_t *)malloc((ns + nb + 1) * sizeof(uint64_t));
+        reps = (uint8_t *)malloc(ns + nb + 1);
+        if (!pr || !reps) { free(pr); free(reps); free(small); free(big); return -1; }
+    }
+    *twos = std_exponent(2, hi) - std_exponent(2, lo);
+    size_t n = 0;
+    uint64_t steps = *twos, own = (lo < 2 && hi >= 2) ? 1 : 0, last = *twos ? 2 : 0;
+    for (size_t i = 0; i < ns; i++) {
+        const unsigned d = std_exponent(small[i], hi) - std_exponent(small[i], lo);
+        if (!d) continue;
+        steps += d;
+        if (small[i] > lo) own++;
+        last = small[i];
+        if (pr) { pr[n] = small[i]; reps[n] = (uint8_t)d; n++; }
+    }
+    for (size_t i = 0; i < nb; i++)
+        if (pr) { pr[n] = big[i]; reps[n] = 1; n++; }
+    steps += nb;
+    own += nb;
+    if (nb) last = big[nb - 1];
+    free(small);
+    free(big);
+    if (ei) { ei->lo = lo; ei->hi = hi; ei->nprimes = own; ei->power_steps = steps - own; ei->last_prime = last; }
+    if (primes_out) { *primes_out = pr; *reps_out = reps; *np_out = n; }
+    return 0;
+}
+
+int gecm_extend_segment_info(gecm_extend_info *ei, uint64_t from, uint64_t to, uint32_t seg)
+{
+    uint64_t lo, hi;
+    unsigned twos;
+    memset(ei, 0, sizeof *ei);
+    if (gecm_extend_segment_bounds(from, to, seg, &lo, &hi)) return -2;
+    return extend_gather(lo, hi, NULL, NULL, NULL, &twos, ei);
+}
+
+int gecm_tape_build_extend(gecm_tape_t *t, uint64_t lo, uint64_t hi, int threads)
+{
+    memset(t, 0, sizeof *t);
+    if (lo < 1 || hi < lo) return -2;
+    uint64_t *primes = NULL;
+    uint8_t *reps = NULL;
+    size_t np = 0;
+    unsigned twos = 0;
+    gecm_extend_info ei;
+    int rc = extend_gather(lo, hi, &primes, &reps, &np, &twos, &ei);
+    if (rc) return rc;
+    for (unsigned i = 0; i < twos; i++) {                /* as the reference's 2-power loop emits them, ecm.c:1815-1822 */
+        if (tape_push(t, GECM_OP_PRAC_BEGIN)) { free(primes); free(reps); gecm_tape_free(t); return -1; }
+        t->ptdups++;
+    }
+    if (np) rc = tape_compile_slices(t, primes, reps, 0, np, hi, threads);
+    free(primes);
+    free(reps);
+    if (rc) return rc;
+    t->last_prime = ei.last_prime;
     if (!t->ops) { t->ops = (uint8_t *)calloc(8, 1); if (!t->ops) return -1; }
     return 0;
 }

@@ -55,6 +55,28 @@ int gecm_stage1_range_info(gecm_range_info *ri, uint64_t B1, uint64_t B2, uint32
 void gecm_plan_set_prime_range_for_tests(uint64_t range);
 uint64_t gecm_plan_prime_range(void);                        /* PRIME_RANGE in force: 1e8, or the test hook's */
 
+
+/* ---- extension to a higher B1 with the standard multiplier ----
+ * k_std(B) = the product over the primes p <= B of p^e, e the largest with p^e <= B (inclusive, GMP-ECM's rule).  An
+ * extension from `from` to `to` (1 <= from <= to) is cut at the multiples of gecm_plan_prime_range() strictly between
+ * the two: segment j is (lo_j, hi_j] with lo_0 = from and the last hi = to, and the points after it are complete to hi_j.
+ * gecm_extend_segments_plan: the number of segments (1 for from == to; 0 for bad bounds).
+ * gecm_tape_build_extend: the tape of one segment (lo, hi]: e_2(hi) - e_2(lo) doublings (GECM_OP_PRAC_BEGIN alone),
+ *   then prac(p) for every odd prime p <= hi ascending, e_p(hi) - e_p(lo) times, e_p(x) the largest e with p^e <= x.
+ *   The counters are those of this tape; last_prime = the largest prime that gained a power (2 if only doublings were
+ *   made, 0 for an empty tape).  Compiled in slices like gecm_tape_build_stage1_range.
+ * gecm_extend_segment_info: what a driver prints around segment `seg` without building its tape. */
+uint32_t gecm_extend_segments_plan(uint64_t from, uint64_t to);
+int gecm_extend_segment_bounds(uint64_t from, uint64_t to, uint32_t seg, uint64_t *lo, uint64_t *hi);
+int gecm_tape_build_extend(gecm_tape_t *t, uint64_t lo, uint64_t hi, int threads);
+typedef struct {
+    uint64_t lo, hi;        /* the segment (lo, hi] */
+    uint64_t nprimes;       /* primes of (lo, hi]: each gains its first power here */
+    uint64_t power_steps;   /* further steps: powers beyond the first, of the segment's primes and of smaller ones (2's doublings included) */
+    uint64_t last_prime;    /* as gecm_tape_build_extend sets it */
+} gecm_extend_info;
+int gecm_extend_segment_info(gecm_extend_info *ei, uint64_t from, uint64_t to, uint32_t seg);
+
 #ifdef __cplusplus
 }
 #endif

@@ -155,6 +155,43 @@ int gecm_stage1_resume_range(uint64_t B1, uint64_t b1_field, uint32_t *range)
     return GECM_ERR_ARG;
 }
 
+/* The standard bound a line's points are complete to.  PROGRAM exactly AVX-ECM: the reference's
+ * multiplier, every prime power BELOW the B1 field, which within one prime range is k_std(field - 1); above one range
+ * the reference's stage 1 is no prime-power product at all.  Anything else — AVX-ECM-STD, GMP-ECM, no PROGRAM — is a
+ * standard line and complete to its field. */
+int gecm_resume_line_std_bound(const char *line, uint64_t *from)
+{
+    gecm_resume_rec rec;
+    if (!from) { set_err("gecm_resume_line_std_bound: bad argument"); return GECM_ERR_ARG; }
+    int rc = gecm_parse_resume_line(line, &rec);
+    if (rc) return rc;
+    int reference = 0;
+    for (const char *p = line; *p; ) {
+        const char *fe = p, *ns = p, *eq = p;
+        while (*fe && *fe != ';') fe++;
+        while (ns < fe && is_space(*ns)) ns++;
+        while (eq < fe && *eq != '=') eq++;
+        if (eq < fe) {
+            const char *ne = eq, *vs = eq + 1, *ve = fe;
+            while (ne > ns && is_space(ne[-1])) ne--;
+            while (vs < ve && is_space(*vs)) vs++;
+            while (ve > vs && is_space(ve[-1])) ve--;
+            if (name_is(ns, ne, "PROGRAM")) reference = name_is(vs, ve, "AVX-ECM");
+        }
+        p = *fe ? fe + 1 : fe;
+    }
+    if (!reference) { *from = rec.b1; return GECM_OK; }
+    if (rec.b1 > gecm_plan_prime_range()) {
+        set_err("gecm_resume_line_std_bound: B1 field %llu of an AVX-ECM line lies above one prime range (%llu): a "
+                "reference run over several prime ranges has no standard multiplier (DESIGN.md §5b)",
+                (unsigned long long)rec.b1, (unsigned long long)gecm_plan_prime_range());
+        return GECM_ERR_ARG;
+    }
+    if (rec.b1 < 2) { set_err("gecm_resume_line_std_bound: B1 field %llu of an AVX-ECM line is below 2", (unsigned long long)rec.b1); return GECM_ERR_ARG; }
+    *from = rec.b1 - 1;
+    return GECM_OK;
+}
+
 /* the hash of the host sources this object was compiled from (Makefile: H_SHA); gecm_version() compares them */
 #ifdef GECM_MANIFEST_FN
 const char *GECM_MANIFEST_FN(void) { return GECM_MANIFEST; }

@@ -165,6 +165,22 @@ EXPORTS += ["gecm_set_curve_build", "gecm_get_curve_build", "gecm_download_s"]
 CURVE_BUILDS = ("host", "device")      # GECM_BUILD_HOST, GECM_BUILD_DEVICE
 
 
+class ExtendDesc(ctypes.Structure):
+    _fields_ = [("lo", c_u64), ("hi", c_u64), ("nprimes", c_u64), ("power_steps", c_u64), ("last_prime", c_u64)]
+
+
+_sig("gecm_stage1_extend_segments", c_int, c_u64, c_u64)
+_sig("gecm_stage1_describe_extend", c_int, c_u64, c_u64, ctypes.c_uint32, ctypes.POINTER(ExtendDesc))
+_sig("gecm_stage1_extend_segment", c_int, c_void_p, c_u64, c_u64, ctypes.c_uint32)
+_sig("gecm_stage1_extend", c_int, c_void_p, c_u64, c_u64)
+_sig("gecm_normalize_points", c_int, c_void_p)
+_sig("gecm_points_normalized", c_int, c_void_p)
+_sig("gecm_format_save_line_std", c_int, c_void_p, c_size_t, c_char_p, c_size_t)
+_sig("gecm_resume_line_std_bound", c_int, c_char_p, ctypes.POINTER(c_u64))
+EXPORTS += ["gecm_stage1_extend_segments", "gecm_stage1_describe_extend", "gecm_stage1_extend_segment", "gecm_stage1_extend",
+            "gecm_normalize_points", "gecm_points_normalized", "gecm_format_save_line_std", "gecm_resume_line_std_bound"]
+
+
 class GecmError(RuntimeError):
     pass
 
@@ -218,6 +234,27 @@ def stage1_resume_range(b1, field):
     r = ctypes.c_uint32(0)
     _chk(lib.gecm_stage1_resume_range(b1, field, ctypes.byref(r)), "gecm_stage1_resume_range")
     return r.value
+
+
+def extend_segments(b1_from, b1_to):
+    """segments an extension of the standard multiplier from b1_from to b1_to runs in"""
+    return _chk(lib.gecm_stage1_extend_segments(b1_from, b1_to), "gecm_stage1_extend_segments")
+
+
+def describe_extend(b1_from, b1_to, seg):
+    d = ExtendDesc()
+    _chk(lib.gecm_stage1_describe_extend(b1_from, b1_to, seg, ctypes.byref(d)), "gecm_stage1_describe_extend")
+    return d
+
+
+def resume_line_std_bound(line):
+    """the standard bound the points of a resume line are complete to (None for a line to skip): B1 - 1 for a line of the
+    reference semantic (PROGRAM=AVX-ECM) within one prime range, the B1 field for every other line"""
+    raw = line.encode() if isinstance(line, str) else bytes(line)
+    b = c_u64(0)
+    if _chk(lib.gecm_resume_line_std_bound(raw, ctypes.byref(b)), "gecm_resume_line_std_bound") == 1:
+        return None
+    return b.value
 
 
 class Engine:
@@ -372,6 +409,32 @@ class Engine:
         _chk(lib.gecm_stage1_range(self._h, b1, r), "gecm_stage1_range")
         if sync:
             self.sync()
+
+    def stage1_extend(self, b1_from, b1_to, sync=True):
+        """the points, complete to b1_from with the standard multiplier (1: fresh curves), on to b1_to"""
+        _chk(lib.gecm_stage1_extend(self._h, b1_from, b1_to), "gecm_stage1_extend")
+        if sync:
+            self.sync()
+
+    def stage1_extend_segment(self, b1_from, b1_to, seg, sync=True):
+        _chk(lib.gecm_stage1_extend_segment(self._h, b1_from, b1_to, seg), "gecm_stage1_extend_segment")
+        if sync:
+            self.sync()
+
+    def normalize(self):
+        """X <- X/Z, Z <- 1 on the device; 1 if some curve's Z had no inverse and the curve was left as it was, else 0"""
+        return _chk(lib.gecm_normalize_points(self._h), "gecm_normalize_points")
+
+    def normalized(self):
+        return bool(lib.gecm_points_normalized(self._h))
+
+    def save_line_std(self, k):
+        buf = ctypes.create_string_buffer(8192)
+        _chk(lib.gecm_format_save_line_std(self._h, k, buf, len(buf)), "gecm_format_save_line_std")
+        return buf.value.decode()
+
+    def save_lines_std(self):
+        return [self.save_line_std(k) for k in range(self.batch)]
 
     def resume_line(self, k, b1_field):
         buf = ctypes.create_string_buffer(8192)

@@ -397,6 +397,54 @@ int gecm_resume_points(gecm_ctx *ctx, const uint64_t *sigma, const void *x, cons
 int gecm_resume_points_multi(gecm_ctx *ctx, const uint64_t *sigma, const uint32_t *modulus_index, const void *x,
                              const void *z, size_t batch, uint64_t b1_done);
 
+/* ---- extension to a higher B1: the standard stage-1 multiplier ------------------
+ * k_std(B) = the product over the primes p <= B of p^e, e the largest with p^e <= B — the bound inclusive, GMP-ECM's
+ * rule; the reference's own multiplier (every prime power BELOW B1, ecm.c:1816, 1832) is k_std(B1 - 1) as long as B1
+ * lies within one prime range, so its save lines with B1 <= 10^8 are standard lines of the bound B1 - 1.
+ * gecm_stage1_extend takes points that are complete to `from` on to `to`: P <- [k_std(to) / k_std(from)] P.  `from` is
+ * the caller's statement about the points in the context, as b1_done is for gecm_resume_points; from = 1 means a fresh
+ * build, so gecm_stage1_extend(ctx, 1, B) IS standard stage 1 to B.  1 <= from <= to <= 10^12 (GECM_ERR_ARG), a batch
+ * in the context (GECM_ERR_STATE).  The work is cut at the multiples of the prime range (10^8) strictly between the two
+ * bounds: segment j is (lo_j, hi_j] with lo_0 = from and the last hi = to, and after every segment the points are
+ * complete to hi_j — the context's B1 is hi_j then, so a checkpoint after a segment is an ordinary standard line.
+ * gecm_stage1_extend_segment runs one segment (0 .. gecm_stage1_extend_segments - 1, in order), asynchronous like
+ * gecm_stage1_range, and compiles the next segment's tape on the helper thread meanwhile; gecm_stage1_extend runs them
+ * all and returns after the last launch.  Afterwards save lines, the factor scan and gecm_stage2* work as after
+ * gecm_stage1(to); gecm_get_stage1_stats sums over the segments since segment 0.  A segment in which no prime gains a
+ * power (from == to among them) launches nothing.  Every layout, the special-form multiply and both packings of a
+ * multi-modulus context run extensions as they run gecm_stage1: only the tape differs. */
+typedef struct {
+    uint64_t lo, hi;        /* the segment (lo, hi] */
+    uint64_t nprimes;       /* primes of (lo, hi]: each enters the multiplier here */
+    uint64_t power_steps;   /* further prime-power steps: powers beyond the first, of these primes and of smaller ones */
+    uint64_t last_prime;    /* the largest prime that gains a power (0: none does) */
+} gecm_extend_desc;
+int gecm_stage1_extend_segments(uint64_t from, uint64_t to);
+int gecm_stage1_describe_extend(uint64_t from, uint64_t to, uint32_t seg, gecm_extend_desc *out);
+int gecm_stage1_extend_segment(gecm_ctx *ctx, uint64_t from, uint64_t to, uint32_t seg);
+int gecm_stage1_extend(gecm_ctx *ctx, uint64_t from, uint64_t to);
+/* Projective (X : Z) depends on the order the primes were processed in; x = X/Z mod N does not, and is the residue any
+ * correct program writes for that sigma and bound (GMP-ECM stores it as X= with no Z=).  gecm_normalize_points gives
+ * every curve with gcd(Z, N) = 1 X <- X/Z and Z <- 1 on the device, synchronously; a curve whose Z has no inverse keeps
+ * its X and Z word for word — it is a stage-1 factor, which gecm_stage1_factor still reports.  Returns GECM_OK, or 1
+ * when some curve was left as it was (the convention of gecm_build_curves).  GECM_ERR_STATE without a batch and on a
+ * context with a report modulus (gecm_set_report_modulus).  A special-form multiply in use is settled first; the
+ * launches after a normalisation run modulo N.  After it gecm_last_kernel_ms is the normalisation kernel's time.
+ * gecm_points_normalized: 1 after a normalisation, until the next stage-1 launch, build, upload or resume.
+ * gecm_format_save_line_std writes curve k's standard line at the context's B1,
+ *   "METHOD=ECM; PARAM=0; SIGMA=%llu; B1=%llu; N=0x%s; X=0x%s; PROGRAM=AVX-ECM-STD;\n"
+ * (with "X=0x%s; Z=0x%s;" for a curve left as it was); GECM_ERR_STATE if the batch is not normalised.
+ * gecm_parse_resume_line reads both shapes.  Returns the line length, or < 0. */
+int gecm_normalize_points(gecm_ctx *ctx);
+int gecm_points_normalized(const gecm_ctx *ctx);
+int gecm_format_save_line_std(gecm_ctx *ctx, size_t k, char *buf, size_t buflen);
+/* The standard bound the points of a resume line are complete to: the `from` of gecm_stage1_extend.  PROGRAM exactly
+ * "AVX-ECM": the line holds the reference's multiplier, *from = B1 field - 1, provided the field lies within one prime
+ * range; above it GECM_ERR_ARG — a reference run over several prime ranges has no standard multiplier.
+ * Any other or no PROGRAM (ours with -STD, GMP-ECM's): *from = the B1 field.  Pure host code, no context; returns what
+ * gecm_parse_resume_line returns for a line it refuses or skips. */
+int gecm_resume_line_std_bound(const char *line, uint64_t *from);
+
 #ifdef __cplusplus
 }
 #endif
