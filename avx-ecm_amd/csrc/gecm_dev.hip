@@ -155,10 +155,11 @@ static gecm_modconst modconst(const gecm_dev *d)
     mc.r3 = d->r3.empty() ? d->one.data() : d->r3.data();
     mc.rho = d->rho;
     mc.inv_iters = d->inv_iters;
+    mc.source = !d->multi ? GECM_SRC_VALUE : d->lane_packed ? GECM_SRC_LANE : GECM_SRC_WAVE;
     mc.groups = d->multi ? d->dGroups : nullptr;
     mc.block_group = d->multi ? d->dBlockGroup : nullptr;
     mc.r2 = nullptr;
-    mc.curve_group = (d->multi && d->lane_packed) ? d->dCurveGroup : nullptr;
+    mc.curve_group = mc.source == GECM_SRC_LANE ? d->dCurveGroup : nullptr;
     return mc;
 }
 
@@ -780,7 +781,7 @@ extern "C" int gecm_dev_set_groups(gecm_dev *d, uint32_t ngroups, const uint32_t
     std::vector<unsigned char> packed(gb * ngroups);
     for (uint32_t g = 0; g < ngroups; g++) {
         gecm_modconst mc = {n + g * nl, kp + g * nl, one + g * nl, r3 + g * nl, rho[g], inv_iters[g], nullptr, nullptr,
-                            r2 + g * nl};
+                            r2 + g * nl, nullptr, GECM_SRC_VALUE};
         d->k1->pack_group(&mc, packed.data() + g * gb);
     }
     if (packed.size() > d->groups_cap) {

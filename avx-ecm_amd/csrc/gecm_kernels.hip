@@ -27,13 +27,27 @@ struct ModArgs {
     Fe<NL> one;   // R mod N, canonical
 };
 
-// Where a kernel finds the constants of its modulus.  A single-N launch passes ModArgs / S2Const by value; a
-// multi-modulus launch (one modulus per wavefront) passes ModGroups: one S2Const per modulus in device
-// memory and the modulus of every 64-curve block.  mod_consts() gives a kernel the constants of its curve block from
-// either source, as a reference the multiplies read as wave-uniform operands; each single-N kernel and its _multi twin
-// share one body (GECM_STAGE1_BODY and the like).
-// One modulus's constants block in device memory: S2Const, then what only the multi-modulus kernels without a by-value
-// twin of it need.  New fields go at the end: the kernels that read a prefix keep their offsets.
+// ---------------------------------------------------------------- constants sources, prologues, bodies
+// A kernel finds the constants of its modulus in one of three places (gecm_source in gecm_launch.h):
+//   by value      the kernel argument `k` is the constants: ModArgs / S2Const of a single-N launch;
+//   per wavefront ModGroups `g`: one GroupConst per modulus in device memory and the modulus of every
+//                 64-curve block; the multiplies read them as wave-uniform operands (the _multi kernels);
+//   per lane      LaneGroups `g`: the same array and the modulus of every curve (the _lane kernels,
+//                 built up to GECM_LANE_MAXNL limbs).
+// The rule: one prologue per source and one body text per operation; a kernel is signature, prologue, body.  The
+// prologues (GECM_ARG_CONSTS, GECM_WAVE_CONSTS, GECM_LANE_CONSTS) leave the constants in `k` and, for the two in device
+// memory, R^2 mod N in `r2`; the bodies (GECM_*_BODY) read `k`, `r2` and the kernel's own arguments and use no other
+// free name.  Where a variant really differs, the difference is a parameter of the body.  Prologues and bodies are
+// macros, not device functions or kernel templates over the source: through a function the kernels compiled to other
+// instructions (k_gcd_scan<15> 1089 -> 1064, k_stage1_multi<15> 12561 -> 12595, k_s2_pairs<26> 5906 -> 5909, k_stage1
+// at the same count in another order), and the single-N kernels must stay instruction for instruction
+// what they were.  Shared text costs nothing, but the order of the statements does: what a kernel computes before it
+// fetches its constants (the slice of the pair walk, the flag of the merge) stays before the prologue.  After any change
+// here, tools/kernel_isa_diff.py compares two builds symbol by symbol.
+#define GECM_ARG_CONSTS     // by value: the kernel argument `k` is the constants (and `r2`, where the body wants it)
+
+// One modulus's constants block in device memory: S2Const, then what only the kernels without a by-value copy of it
+// need.  New fields go at the end: the kernels that read a prefix keep their offsets.
 template <int NL>
 struct GroupConst {
     S2Const<NL> k;
@@ -50,9 +64,6 @@ static_assert(offsetof(S2Const<GECM_NL>, m) == offsetof(ModArgs<GECM_NL>, m) &&
               offsetof(S2Const<GECM_NL>, one) == offsetof(ModArgs<GECM_NL>, one),
               "ModArgs must be a prefix of S2Const: multi-modulus kernels read one through the other");
 
-template <class A>
-__device__ __forceinline__ const A &mod_consts(const A &a, uint32_t) { return a; }
-
 // The loads go through the constant address space: the constants are read-only while the kernel runs, so the
 // compiler fetches them with scalar loads at a wave-uniform address and may fetch them again where it needs them
 // instead of holding them in registers, as it does with kernel arguments.
@@ -64,6 +75,11 @@ __device__ __forceinline__ const A &mod_consts(const ModGroups<NL> &g, uint32_t 
     const uint32_t grp = ((c_u32 *)g.block_group)[block];
     return *(const A *)(const GroupConst<NL> *)((c_grp *)g.groups + grp);
 }
+// per wavefront: `k` = the constants of curve block `block`, read as a T (ModArgs or S2Const, prefixes of GroupConst)
+#define GECM_WAVE_CONSTS(T, block)                                              \
+    const GroupConst<NL> &gk = mod_consts<GroupConst<NL>>(g, block);            \
+    const T &k = *(const T *)&gk;                                               \
+    [[maybe_unused]] const Fe<NL> &r2 = gk.r2;
 
 // Lane-packed multi-modulus launch (one modulus per lane): the same constants array, and the modulus of
 // every curve.  Built for the limb counts up to GECM_LANE_MAXNL; lane_consts() gives a lane the constants of its own
@@ -99,42 +115,41 @@ __device__ __forceinline__ void lane_consts(LaneConst<NL> &k, const LaneGroups<N
     k.inv_iters = gp[offsetof(GroupConst<NL>, k.inv_iters) / 4];
     k.r2.p = gp + offsetof(GroupConst<NL>, r2) / 4;
 }
-// every lane kernel starts with this: `k` = the constants of curve position idx
+// per lane: `k` = the constants of the lane's curve (64 curves per block in every lane kernel)
 #define GECM_LANE_CONSTS                                                        \
     __shared__ uint32_t lds_kp[NL * 64];                                        \
     LaneConst<NL> k;                                                            \
-    lane_consts(k, g, idx, lds_kp + threadIdx.x);
+    lane_consts(k, g, blockIdx.x * 64u + threadIdx.x, lds_kp + threadIdx.x);    \
+    [[maybe_unused]] const FeG<NL> &r2 = k.r2;
 
 #if GECM_HAS_PART(1)
 // ---------------------------------------------------------------- stage 1
 // One curve per lane.  64-thread blocks (one wave): a CU holds 8 of them at 2 waves/SIMD, the
 // occupancy at which v_mad_u64_u32 issues back-to-back (profiles/r01_valu_ubench_gfx950.txt).
-// The body of k_stage1 and k_stage1_multi, with the constants in `a` (a ModArgs<NL>).  A macro, not a device function
-// over the constants source: through such a function the single-N kernels compiled to different code at some limb
-// counts (operand order, register choice, stack layout), and they must stay instruction for instruction what they
-// were.  The other single-N / multi pairs below share their bodies the same way.
-#define GECM_STAGE1_BODY                                                        \
+// C_IN_LDS: the third PRAC point waits in LDS (the C store of the tape interpreter) instead of in registers.
+#define GECM_STAGE1_BODY(C_IN_LDS)                                              \
     uint32_t idx = blockIdx.x * 64u + threadIdx.x;                              \
     Pt<NL> P;                                                                   \
     fe_load(P.X, X, stride, idx);                                               \
     fe_load(P.Z, Z, stride, idx);                                               \
-    constexpr bool CL = TapePolicy<NL>::c_in_lds;                               \
+    constexpr bool CL = C_IN_LDS;                                               \
     __shared__ uint32_t lds_c[CL ? 2 * NL * 64 : 1];                            \
     CStore<NL, CL> cst;                                                         \
     if constexpr (CL) cst.lds = lds_c + threadIdx.x;                            \
-    run_tape<NL>(tape, tape_len, P, S, stride, idx, a.m, cst);                  \
+    run_tape<NL>(tape, tape_len, P, S, stride, idx, k.m, cst);                  \
     Fe<NL> ox, oz;                                                              \
-    fe_canonical_mont(ox, P.X, a.one, a.m);                                     \
-    fe_canonical_mont(oz, P.Z, a.one, a.m);                                     \
+    fe_canonical_mont(ox, P.X, k.one, k.m);                                     \
+    fe_canonical_mont(oz, P.Z, k.one, k.m);                                     \
     fe_store(X, stride, idx, ox);                                               \
     fe_store(Z, stride, idx, oz);
 
 template <int NL>
 __global__ void __launch_bounds__(64, 2)
 k_stage1(const uint32_t *__restrict__ tape, uint32_t tape_len, uint32_t *__restrict__ X,
-         uint32_t *__restrict__ Z, const uint32_t *__restrict__ S, size_t stride, ModArgs<NL> a)
+         uint32_t *__restrict__ Z, const uint32_t *__restrict__ S, size_t stride, ModArgs<NL> k)
 {
-    GECM_STAGE1_BODY
+    GECM_ARG_CONSTS
+    GECM_STAGE1_BODY(TapePolicy<NL>::c_in_lds)
 }
 
 template <int NL>
@@ -142,33 +157,20 @@ __global__ void __launch_bounds__(64, 2)
 k_stage1_multi(const uint32_t *__restrict__ tape, uint32_t tape_len, uint32_t *__restrict__ X,
                uint32_t *__restrict__ Z, const uint32_t *__restrict__ S, size_t stride, ModGroups<NL> g)
 {
-    const ModArgs<NL> &a = mod_consts<ModArgs<NL>>(g, blockIdx.x);
-    GECM_STAGE1_BODY
+    GECM_WAVE_CONSTS(ModArgs<NL>, blockIdx.x)
+    GECM_STAGE1_BODY(TapePolicy<NL>::c_in_lds)
 }
-#undef GECM_STAGE1_BODY
 
 #if GECM_HAS_LANE
-// One curve per lane and a modulus per lane.  The third PRAC point waits in LDS at every limb count (the column the
-// C store of TapePolicy uses above its threshold): the registers it leaves hold the lane's N.
+// A modulus per lane: the third PRAC point waits in LDS at every limb count (the column the C store of TapePolicy uses
+// above its threshold): the registers it leaves hold the lane's N.
 template <int NL>
 __global__ void __launch_bounds__(64, 2)
 k_stage1_lane(const uint32_t *__restrict__ tape, uint32_t tape_len, uint32_t *__restrict__ X,
               uint32_t *__restrict__ Z, const uint32_t *__restrict__ S, size_t stride, LaneGroups<NL> g)
 {
-    const uint32_t idx = blockIdx.x * 64u + threadIdx.x;
     GECM_LANE_CONSTS
-    Pt<NL> P;
-    fe_load(P.X, X, stride, idx);
-    fe_load(P.Z, Z, stride, idx);
-    __shared__ uint32_t lds_c[2 * NL * 64];
-    CStore<NL, true> cst;
-    cst.lds = lds_c + threadIdx.x;
-    run_tape<NL>(tape, tape_len, P, S, stride, idx, k.m, cst);
-    Fe<NL> ox, oz;
-    fe_canonical_mont(ox, P.X, k.one, k.m);
-    fe_canonical_mont(oz, P.Z, k.one, k.m);
-    fe_store(X, stride, idx, ox);
-    fe_store(Z, stride, idx, oz);
+    GECM_STAGE1_BODY(true)
 }
 #endif
 
@@ -184,43 +186,32 @@ struct ModArgsS {
 template <int NL, class MOD>
 __global__ void __launch_bounds__(64, 2)
 k_stage1_f(const uint32_t *__restrict__ tape, uint32_t tape_len, uint32_t *__restrict__ X,
-           uint32_t *__restrict__ Z, const uint32_t *__restrict__ S, size_t stride, ModArgsS<NL, MOD> a)
+           uint32_t *__restrict__ Z, const uint32_t *__restrict__ S, size_t stride, ModArgsS<NL, MOD> k)
 {
-    uint32_t idx = blockIdx.x * 64u + threadIdx.x;
-    Pt<NL> P;
-    fe_load(P.X, X, stride, idx);
-    fe_load(P.Z, Z, stride, idx);
-    constexpr bool CL = TapePolicy<NL>::c_in_lds;
-    __shared__ uint32_t lds_c[CL ? 2 * NL * 64 : 1];
-    CStore<NL, CL> cst;
-    if constexpr (CL) cst.lds = lds_c + threadIdx.x;
-    run_tape<NL>(tape, tape_len, P, S, stride, idx, a.m, cst);
-    Fe<NL> ox, oz;
-    fe_canonical_mont(ox, P.X, a.one, a.m);
-    fe_canonical_mont(oz, P.Z, a.one, a.m);
-    fe_store(X, stride, idx, ox);
-    fe_store(Z, stride, idx, oz);
+    GECM_ARG_CONSTS
+    GECM_STAGE1_BODY(TapePolicy<NL>::c_in_lds)
 }
+#undef GECM_STAGE1_BODY
 
 // Two lanes per curve (gecm_curve.hpp, "split-coordinate"): lane 2j works on X, lane 2j+1 on Z of
 // curve blockIdx.x*32 + j.  Chosen by the device layer for batches that leave SIMDs under-occupied.
-// (a macro for the reason given at GECM_STAGE1_BODY; the constants are in `a`, a ModArgs<NL>)
 #define GECM_STAGE1_PAIR_BODY                                                   \
     const uint32_t cidx = blockIdx.x * 32u + (threadIdx.x >> 1);                \
     const bool isZ = (threadIdx.x & 1u) != 0;                                   \
     uint32_t *mine = isZ ? Z : X;                                               \
     Fe<NL> P;                                                                   \
     fe_load(P, mine, stride, cidx);                                             \
-    run_tape_pair<NL>(tape, tape_len, P, S, stride, cidx, isZ, a.m);            \
+    run_tape_pair<NL>(tape, tape_len, P, S, stride, cidx, isZ, k.m);            \
     Fe<NL> o;                                                                   \
-    fe_canonical_mont(o, P, a.one, a.m);                                        \
+    fe_canonical_mont(o, P, k.one, k.m);                                        \
     fe_store(mine, stride, cidx, o);
 
 template <int NL>
 __global__ void __launch_bounds__(64, 2)
 k_stage1_pair(const uint32_t *__restrict__ tape, uint32_t tape_len, uint32_t *__restrict__ X,
-              uint32_t *__restrict__ Z, const uint32_t *__restrict__ S, size_t stride, ModArgs<NL> a)
+              uint32_t *__restrict__ Z, const uint32_t *__restrict__ S, size_t stride, ModArgs<NL> k)
 {
+    GECM_ARG_CONSTS
     GECM_STAGE1_PAIR_BODY
 }
 
@@ -229,26 +220,19 @@ __global__ void __launch_bounds__(64, 2)
 k_stage1_pair_multi(const uint32_t *__restrict__ tape, uint32_t tape_len, uint32_t *__restrict__ X,
                     uint32_t *__restrict__ Z, const uint32_t *__restrict__ S, size_t stride, ModGroups<NL> g)
 {
-    const ModArgs<NL> &a = mod_consts<ModArgs<NL>>(g, blockIdx.x >> 1);   // 32 curves per block
+    GECM_WAVE_CONSTS(ModArgs<NL>, blockIdx.x >> 1)   // 32 curves per block
     GECM_STAGE1_PAIR_BODY
 }
-#undef GECM_STAGE1_PAIR_BODY
 
 template <int NL, class MOD>
 __global__ void __launch_bounds__(64, 2)
 k_stage1_pair_f(const uint32_t *__restrict__ tape, uint32_t tape_len, uint32_t *__restrict__ X,
-                uint32_t *__restrict__ Z, const uint32_t *__restrict__ S, size_t stride, ModArgsS<NL, MOD> a)
+                uint32_t *__restrict__ Z, const uint32_t *__restrict__ S, size_t stride, ModArgsS<NL, MOD> k)
 {
-    const uint32_t cidx = blockIdx.x * 32u + (threadIdx.x >> 1);
-    const bool isZ = (threadIdx.x & 1u) != 0;
-    uint32_t *mine = isZ ? Z : X;
-    Fe<NL> P;
-    fe_load(P, mine, stride, cidx);
-    run_tape_pair<NL>(tape, tape_len, P, S, stride, cidx, isZ, a.m);
-    Fe<NL> o;
-    fe_canonical_mont(o, P, a.one, a.m);
-    fe_store(mine, stride, cidx, o);
+    GECM_ARG_CONSTS
+    GECM_STAGE1_PAIR_BODY
 }
+#undef GECM_STAGE1_PAIR_BODY
 
 // Eight lanes per curve (gecm_quad.hpp).
 // 256-thread workgroups (four independent wavefronts): this kernel needs about 65 registers, and one-wavefront
@@ -281,21 +265,21 @@ k_stage1_quad(const uint32_t *__restrict__ tape, uint32_t tape_len, uint32_t *__
 }
 
 // canonical Montgomery form of X, Z in place (the tail of k_stage1, for kernels that leave lazy values)
-// (macros for the reason given at GECM_STAGE1_BODY; the constants are in `a`, a ModArgs<NL>)
 #define GECM_CANON_BODY                                                         \
     uint32_t idx = blockIdx.x * 64u + threadIdx.x;                              \
     Fe<NL> x, z, r;                                                             \
     fe_load(x, X, stride, idx);                                                 \
     fe_load(z, Z, stride, idx);                                                 \
-    fe_canonical_mont(r, x, a.one, a.m);                                        \
+    fe_canonical_mont(r, x, k.one, k.m);                                        \
     fe_store(X, stride, idx, r);                                                \
-    fe_canonical_mont(r, z, a.one, a.m);                                        \
+    fe_canonical_mont(r, z, k.one, k.m);                                        \
     fe_store(Z, stride, idx, r);
 
 template <int NL>
 __global__ void __launch_bounds__(64)
-k_canon(uint32_t *__restrict__ X, uint32_t *__restrict__ Z, size_t stride, ModArgs<NL> a)
+k_canon(uint32_t *__restrict__ X, uint32_t *__restrict__ Z, size_t stride, ModArgs<NL> k)
 {
+    GECM_ARG_CONSTS
     GECM_CANON_BODY
 }
 
@@ -303,7 +287,7 @@ template <int NL>
 __global__ void __launch_bounds__(64)
 k_canon_multi(uint32_t *__restrict__ X, uint32_t *__restrict__ Z, size_t stride, ModGroups<NL> g)
 {
-    const ModArgs<NL> &a = mod_consts<ModArgs<NL>>(g, blockIdx.x);
+    GECM_WAVE_CONSTS(ModArgs<NL>, blockIdx.x)
     GECM_CANON_BODY
 }
 #undef GECM_CANON_BODY
@@ -313,16 +297,17 @@ k_canon_multi(uint32_t *__restrict__ X, uint32_t *__restrict__ Z, size_t stride,
     Fe<NL> x, z, r;                                                             \
     fe_load(x, X, stride, idx);                                                 \
     fe_load(z, Z, stride, idx);                                                 \
-    fe_from_mont_canonical(r, x, a.m);                                          \
+    fe_from_mont_canonical(r, x, k.m);                                          \
     fe_store(ox, stride, idx, r);                                               \
-    fe_from_mont_canonical(r, z, a.m);                                          \
+    fe_from_mont_canonical(r, z, k.m);                                          \
     fe_store(oz, stride, idx, r);
 
 template <int NL>
 __global__ void __launch_bounds__(64)
 k_from_mont(const uint32_t *__restrict__ X, const uint32_t *__restrict__ Z, uint32_t *__restrict__ ox,
-            uint32_t *__restrict__ oz, size_t stride, ModArgs<NL> a)
+            uint32_t *__restrict__ oz, size_t stride, ModArgs<NL> k)
 {
+    GECM_ARG_CONSTS
     GECM_FROM_MONT_BODY
 }
 
@@ -331,10 +316,9 @@ __global__ void __launch_bounds__(64)
 k_from_mont_multi(const uint32_t *__restrict__ X, const uint32_t *__restrict__ Z, uint32_t *__restrict__ ox,
                   uint32_t *__restrict__ oz, size_t stride, ModGroups<NL> g)
 {
-    const ModArgs<NL> &a = mod_consts<ModArgs<NL>>(g, blockIdx.x);
+    GECM_WAVE_CONSTS(ModArgs<NL>, blockIdx.x)
     GECM_FROM_MONT_BODY
 }
-#undef GECM_FROM_MONT_BODY
 
 #if GECM_HAS_LANE
 template <int NL>
@@ -342,38 +326,32 @@ __global__ void __launch_bounds__(64)
 k_from_mont_lane(const uint32_t *__restrict__ X, const uint32_t *__restrict__ Z, uint32_t *__restrict__ ox,
                  uint32_t *__restrict__ oz, size_t stride, LaneGroups<NL> g)
 {
-    const uint32_t idx = blockIdx.x * 64u + threadIdx.x;
     GECM_LANE_CONSTS
-    Fe<NL> x, z, r;
-    fe_load(x, X, stride, idx);
-    fe_load(z, Z, stride, idx);
-    fe_from_mont_canonical(r, x, k.m);
-    fe_store(ox, stride, idx, r);
-    fe_from_mont_canonical(r, z, k.m);
-    fe_store(oz, stride, idx, r);
+    GECM_FROM_MONT_BODY
 }
 #endif
+#undef GECM_FROM_MONT_BODY
 
 // The inverse: canonical plain residues x, z in [0, N) -> X = x R mod N, Z = z R mod N, canonical, by one multiply with
-// R^2 mod N each (x R^2 / R < N^2/R + N < 2N, then one conditional subtract).  The constants are in `a`, a ModArgs<NL>,
-// and R^2 mod N in `r2`.
+// R^2 mod N each (x R^2 / R < N^2/R + N < 2N, then one conditional subtract).
 #define GECM_TO_MONT_BODY                                                       \
     uint32_t idx = blockIdx.x * 64u + threadIdx.x;                              \
     Fe<NL> x, z, r;                                                             \
     fe_load(x, ix, stride, idx);                                                \
     fe_load(z, iz, stride, idx);                                                \
-    fe_mul(r, x, r2, a.m);                                                      \
-    fe_cond_sub_n(r, a.m);                                                      \
+    fe_mul(r, x, r2, k.m);                                                      \
+    fe_cond_sub_n(r, k.m);                                                      \
     fe_store(X, stride, idx, r);                                                \
-    fe_mul(r, z, r2, a.m);                                                      \
-    fe_cond_sub_n(r, a.m);                                                      \
+    fe_mul(r, z, r2, k.m);                                                      \
+    fe_cond_sub_n(r, k.m);                                                      \
     fe_store(Z, stride, idx, r);
 
 template <int NL>
 __global__ void __launch_bounds__(64)
 k_to_mont(const uint32_t *__restrict__ ix, const uint32_t *__restrict__ iz, uint32_t *__restrict__ X,
-          uint32_t *__restrict__ Z, size_t stride, ModArgs<NL> a, Fe<NL> r2)
+          uint32_t *__restrict__ Z, size_t stride, ModArgs<NL> k, Fe<NL> r2)
 {
+    GECM_ARG_CONSTS
     GECM_TO_MONT_BODY
 }
 
@@ -382,12 +360,9 @@ __global__ void __launch_bounds__(64)
 k_to_mont_multi(const uint32_t *__restrict__ ix, const uint32_t *__restrict__ iz, uint32_t *__restrict__ X,
                 uint32_t *__restrict__ Z, size_t stride, ModGroups<NL> g)
 {
-    const GroupConst<NL> &c = mod_consts<GroupConst<NL>>(g, blockIdx.x);
-    const ModArgs<NL> &a = *(const ModArgs<NL> *)&c;
-    const Fe<NL> &r2 = c.r2;
+    GECM_WAVE_CONSTS(ModArgs<NL>, blockIdx.x)
     GECM_TO_MONT_BODY
 }
-#undef GECM_TO_MONT_BODY
 
 #if GECM_HAS_LANE
 template <int NL>
@@ -395,19 +370,11 @@ __global__ void __launch_bounds__(64)
 k_to_mont_lane(const uint32_t *__restrict__ ix, const uint32_t *__restrict__ iz, uint32_t *__restrict__ X,
                uint32_t *__restrict__ Z, size_t stride, LaneGroups<NL> g)
 {
-    const uint32_t idx = blockIdx.x * 64u + threadIdx.x;
     GECM_LANE_CONSTS
-    Fe<NL> x, z, r;
-    fe_load(x, ix, stride, idx);
-    fe_load(z, iz, stride, idx);
-    fe_mul(r, x, k.r2, k.m);
-    fe_cond_sub_n(r, k.m);
-    fe_store(X, stride, idx, r);
-    fe_mul(r, z, k.r2, k.m);
-    fe_cond_sub_n(r, k.m);
-    fe_store(Z, stride, idx, r);
+    GECM_TO_MONT_BODY
 }
 #endif
+#undef GECM_TO_MONT_BODY
 
 // ---------------------------------------------------------------- L0 test-level operators
 template <int NL>
@@ -466,20 +433,19 @@ k_l0_inv(const uint32_t *__restrict__ A, uint32_t *__restrict__ C, uint32_t *__r
 // check_factor (ecm.c:2542-2557) for every curve on the device: g = gcd(v, N) by the same
 // fixed-iteration binary algorithm the stage-2 inversion uses; flag = 1 iff 1 < g < N.
 // v is any representative (Montgomery form or not: R is a power of two, N is odd).
-// (a macro for the reason given at GECM_STAGE1_BODY; the constants are in `k`, an S2Const<NL>)
 #define GECM_GCD_SCAN_BODY                                                      \
     uint32_t idx = blockIdx.x * 64u + threadIdx.x;                              \
-    Fe<NL> v, c, t, g;                                                          \
+    Fe<NL> v, c, t, gcd;                                                        \
     fe_load(v, V, stride, idx);                                                 \
     fe_canonical_mont(c, v, k.one, k.m);                                        \
-    fe_invert(t, g, c, k.m, k.inv_iters);                                       \
-    bool is_one = g.v[0] == 1u, is_n = true;                                    \
+    fe_invert(t, gcd, c, k.m, k.inv_iters);                                     \
+    bool is_one = gcd.v[0] == 1u, is_n = true;                                  \
     _Pragma("unroll")                                                           \
     for (int i = 0; i < NL; i++) {                                              \
-        if (i > 0) is_one = is_one && g.v[i] == 0;                              \
-        is_n = is_n && g.v[i] == k.m.n[i];                                      \
+        if (i > 0) is_one = is_one && gcd.v[i] == 0;                            \
+        is_n = is_n && gcd.v[i] == k.m.n[i];                                    \
     }                                                                           \
-    fe_store(G, stride, idx, g);                                                \
+    fe_store(G, stride, idx, gcd);                                              \
     flags[idx] = (!is_one && !is_n) ? 1u : 0u;
 
 template <int NL>
@@ -487,15 +453,16 @@ __global__ void __launch_bounds__(64, 2)
 k_gcd_scan(const uint32_t *__restrict__ V, uint32_t *__restrict__ G, uint32_t *__restrict__ flags, size_t stride,
            S2Const<NL> k)
 {
+    GECM_ARG_CONSTS
     GECM_GCD_SCAN_BODY
 }
 
 template <int NL>
 __global__ void __launch_bounds__(64, 2)
 k_gcd_scan_multi(const uint32_t *__restrict__ V, uint32_t *__restrict__ G, uint32_t *__restrict__ flags, size_t stride,
-                 ModGroups<NL> groups)
+                 ModGroups<NL> g)
 {
-    const S2Const<NL> &k = mod_consts<S2Const<NL>>(groups, blockIdx.x);
+    GECM_WAVE_CONSTS(S2Const<NL>, blockIdx.x)
     GECM_GCD_SCAN_BODY
 }
 
@@ -505,20 +472,8 @@ __global__ void __launch_bounds__(64, 2)
 k_gcd_scan_lane(const uint32_t *__restrict__ V, uint32_t *__restrict__ G, uint32_t *__restrict__ flags, size_t stride,
                 LaneGroups<NL> g)
 {
-    const uint32_t idx = blockIdx.x * 64u + threadIdx.x;
     GECM_LANE_CONSTS
-    Fe<NL> v, c, t, gc;
-    fe_load(v, V, stride, idx);
-    fe_canonical_mont(c, v, k.one, k.m);
-    fe_invert(t, gc, c, k.m, k.inv_iters);
-    bool is_one = gc.v[0] == 1u, is_n = true;
-#pragma unroll
-    for (int i = 0; i < NL; i++) {
-        if (i > 0) is_one = is_one && gc.v[i] == 0;
-        is_n = is_n && gc.v[i] == k.m.n[i];
-    }
-    fe_store(G, stride, idx, gc);
-    flags[idx] = (!is_one && !is_n) ? 1u : 0u;
+    GECM_GCD_SCAN_BODY
 }
 #endif
 #undef GECM_GCD_SCAN_BODY
@@ -630,7 +585,6 @@ __device__ __forceinline__ void build_curve(uint64_t sg, uint32_t *__restrict__ 
     flags[idx] = flag;
 }
 
-// (a macro for the reason given at GECM_STAGE1_BODY; the constants are in `k`, an S2Const<NL>, and R^2 mod N in `r2`)
 #define GECM_BUILD_BODY                                                         \
     const uint32_t idx = blockIdx.x * 64u + threadIdx.x;                        \
     build_curve<NL>(sigma[idx], X, Z, S, flags, stride, idx, k, r2);
@@ -640,17 +594,16 @@ __global__ void __launch_bounds__(64, 2)
 k_build(const uint64_t *__restrict__ sigma, uint32_t *__restrict__ X, uint32_t *__restrict__ Z, uint32_t *__restrict__ S,
         uint32_t *__restrict__ flags, size_t stride, S2Const<NL> k, Fe<NL> r2)
 {
+    GECM_ARG_CONSTS
     GECM_BUILD_BODY
 }
 
 template <int NL>
 __global__ void __launch_bounds__(64, 2)
-k_build_multi(const uint64_t *__restrict__ sigma, uint32_t *__restrict__ X, uint32_t *__restrict__ Z,
-              uint32_t *__restrict__ S, uint32_t *__restrict__ flags, size_t stride, ModGroups<NL> groups)
+k_build_multi(const uint64_t *__restrict__ sigma, uint32_t *__restrict__ X, uint32_t *__restrict__ Z, uint32_t *__restrict__ S,
+              uint32_t *__restrict__ flags, size_t stride, ModGroups<NL> g)
 {
-    const GroupConst<NL> &c = mod_consts<GroupConst<NL>>(groups, blockIdx.x);
-    const S2Const<NL> &k = c.k;
-    const Fe<NL> &r2 = c.r2;
+    GECM_WAVE_CONSTS(S2Const<NL>, blockIdx.x)
     GECM_BUILD_BODY
 }
 #undef GECM_BUILD_BODY
@@ -662,7 +615,6 @@ k_build_multi(const uint64_t *__restrict__ sigma, uint32_t *__restrict__ X, uint
 // product again, and out through the multiply by R mod N and one conditional subtraction, the tail of k_to_mont and
 // k_build.  A lane whose Z has no inverse stores nothing but its flag.  Three out-of-line multiplies (ModKOut) next
 // to one inversion, once per batch: small code before speed.
-// (a macro for the reason given at GECM_STAGE1_BODY; the constants are in `k`, an S2Const<NL>)
 #define GECM_NORMALIZE_BODY                                                     \
     const uint32_t idx = blockIdx.x * 64u + threadIdx.x;                        \
     const ModKOut<NL> mm{k.m};                                                  \
@@ -683,15 +635,16 @@ template <int NL>
 __global__ void __launch_bounds__(64, 2)
 k_normalize(uint32_t *__restrict__ X, uint32_t *__restrict__ Z, uint32_t *__restrict__ flags, size_t stride, S2Const<NL> k)
 {
+    GECM_ARG_CONSTS
     GECM_NORMALIZE_BODY
 }
 
 template <int NL>
 __global__ void __launch_bounds__(64, 2)
 k_normalize_multi(uint32_t *__restrict__ X, uint32_t *__restrict__ Z, uint32_t *__restrict__ flags, size_t stride,
-                  ModGroups<NL> groups)
+                  ModGroups<NL> g)
 {
-    const S2Const<NL> &k = mod_consts<S2Const<NL>>(groups, blockIdx.x);
+    GECM_WAVE_CONSTS(S2Const<NL>, blockIdx.x)
     GECM_NORMALIZE_BODY
 }
 #undef GECM_NORMALIZE_BODY
@@ -727,18 +680,30 @@ k_normalize_lane(uint32_t *__restrict__ X, uint32_t *__restrict__ Z, uint32_t *_
 #endif
 #if GECM_HAS_PART(2)
 // ---------------------------------------------------------------- stage 2
+// Multi-modulus contexts run stage 2 with one sub-sequence per curve (K = 1): for them the _multi or _lane kernels of
+// init, gen, pairs and merge are the whole path.
 template <int NL>
 __global__ void __launch_bounds__(64, 2) k_s2_init(S2InitArgs a, S2Const<NL> k)
 {
+    GECM_ARG_CONSTS
     s2_init<NL>(a, k, blockIdx.x * 64u + threadIdx.x);
 }
 
-// multi-modulus contexts run stage 2 with one sub-sequence per curve (K = 1): these four kernels are the whole path
 template <int NL>
 __global__ void __launch_bounds__(64, 2) k_s2_init_multi(S2InitArgs a, ModGroups<NL> g)
 {
-    s2_init<NL>(a, mod_consts<S2Const<NL>>(g, blockIdx.x), blockIdx.x * 64u + threadIdx.x);
+    GECM_WAVE_CONSTS(S2Const<NL>, blockIdx.x)
+    s2_init<NL>(a, k, blockIdx.x * 64u + threadIdx.x);
 }
+
+#if GECM_HAS_LANE
+template <int NL>
+__global__ void __launch_bounds__(64, 2) k_s2_init_lane(S2InitArgs a, LaneGroups<NL> g)
+{
+    GECM_LANE_CONSTS
+    s2_init<NL>(a, k, blockIdx.x * 64u + threadIdx.x);
+}
+#endif
 
 // K sub-sequences per curve (small batches): block b works on curve block b / K, sub-sequence b % K
 template <int NL>
@@ -757,90 +722,90 @@ __global__ void __launch_bounds__(64, 2) k_s2_gen_k(S2PairArgs a, uint32_t first
 template <int NL>
 __global__ void __launch_bounds__(64, 2) k_s2_gen(S2PairArgs a, uint32_t first_abs, uint32_t n, uint32_t kprev, S2Const<NL> k)
 {
+    GECM_ARG_CONSTS
     giant_chunk<NL>(a, first_abs, n, first_abs == 0, k, blockIdx.x * 64u + threadIdx.x, kprev);
 }
 
 template <int NL>
 __global__ void __launch_bounds__(64, 2) k_s2_gen_multi(S2PairArgs a, uint32_t first_abs, uint32_t n, ModGroups<NL> g)
 {
-    giant_chunk<NL>(a, first_abs, n, first_abs == 0, mod_consts<S2Const<NL>>(g, blockIdx.x), blockIdx.x * 64u + threadIdx.x);
+    GECM_WAVE_CONSTS(S2Const<NL>, blockIdx.x)
+    giant_chunk<NL>(a, first_abs, n, first_abs == 0, k, blockIdx.x * 64u + threadIdx.x);
 }
 
-// pair walk over tape entries [first, first+count)
-// (a macro for the reason given at GECM_STAGE1_BODY; the constants are in `k`, an S2Const<NL>)
-#define GECM_S2_PAIRS_BODY                                                      \
-    /* gridDim.y slices of the segment, one accumulator each (see s2_pairs) */  \
+#if GECM_HAS_LANE
+template <int NL>
+__global__ void __launch_bounds__(64, 2) k_s2_gen_lane(S2PairArgs a, uint32_t first_abs, uint32_t n, LaneGroups<NL> g)
+{
+    GECM_LANE_CONSTS
+    giant_chunk<NL>(a, first_abs, n, first_abs == 0, k, blockIdx.x * 64u + threadIdx.x);
+}
+#endif
+
+// pair walk over tape entries [first, first+count): gridDim.y slices of the segment, one accumulator each (see s2_pairs)
+// (a lane fetches its constants after the slice's early return, a wavefront before it)
+#define GECM_S2_SLICE                                                           \
     const uint32_t per = (count + gridDim.y - 1) / gridDim.y;                   \
     const uint32_t off = blockIdx.y * per;                                      \
     if (off >= count) return;                                                   \
-    const uint32_t n = count - off < per ? count - off : per;                   \
+    const uint32_t n = count - off < per ? count - off : per;
+#define GECM_S2_PAIRS_BODY                                                      \
     s2_pairs<NL>(a, first + off, n, k, blockIdx.x * 64u + threadIdx.x, a.acc + (size_t)blockIdx.y * NL * a.stride);
 
 template <int NL>
 __global__ void __launch_bounds__(64, 2) k_s2_pairs(S2PairArgs a, uint32_t first, uint32_t count, S2Const<NL> k)
 {
+    GECM_ARG_CONSTS
+    GECM_S2_SLICE
     GECM_S2_PAIRS_BODY
 }
 
 template <int NL>
 __global__ void __launch_bounds__(64, 2) k_s2_pairs_multi(S2PairArgs a, uint32_t first, uint32_t count, ModGroups<NL> g)
 {
-    const S2Const<NL> &k = mod_consts<S2Const<NL>>(g, blockIdx.x);
+    GECM_WAVE_CONSTS(S2Const<NL>, blockIdx.x)
+    GECM_S2_SLICE
     GECM_S2_PAIRS_BODY
 }
+
+#if GECM_HAS_LANE
+template <int NL>
+__global__ void __launch_bounds__(64, 2) k_s2_pairs_lane(S2PairArgs a, uint32_t first, uint32_t count, LaneGroups<NL> g)
+{
+    GECM_S2_SLICE
+    GECM_LANE_CONSTS
+    GECM_S2_PAIRS_BODY
+}
+#endif
+#undef GECM_S2_SLICE
 #undef GECM_S2_PAIRS_BODY
 
 template <int NL>
 __global__ void __launch_bounds__(64, 2) k_s2_merge(uint32_t *acc, uint32_t slices, size_t stride, int init_only,
                                                     S2Const<NL> k)
 {
-    s2_merge<NL>(acc, slices, stride, init_only != 0, k, blockIdx.x * 64u + threadIdx.x);
+    const bool init = init_only != 0;
+    GECM_ARG_CONSTS
+    s2_merge<NL>(acc, slices, stride, init, k, blockIdx.x * 64u + threadIdx.x);
 }
 
 template <int NL>
 __global__ void __launch_bounds__(64, 2) k_s2_merge_multi(uint32_t *acc, uint32_t slices, size_t stride, int init_only,
                                                           ModGroups<NL> g)
 {
-    s2_merge<NL>(acc, slices, stride, init_only != 0, mod_consts<S2Const<NL>>(g, blockIdx.x), blockIdx.x * 64u + threadIdx.x);
+    const bool init = init_only != 0;
+    GECM_WAVE_CONSTS(S2Const<NL>, blockIdx.x)
+    s2_merge<NL>(acc, slices, stride, init, k, blockIdx.x * 64u + threadIdx.x);
 }
 
 #if GECM_HAS_LANE
-// lane-packed multi-modulus contexts: the same four kernels with a modulus per lane (K = 1)
-template <int NL>
-__global__ void __launch_bounds__(64, 2) k_s2_init_lane(S2InitArgs a, LaneGroups<NL> g)
-{
-    const uint32_t idx = blockIdx.x * 64u + threadIdx.x;
-    GECM_LANE_CONSTS
-    s2_init<NL>(a, k, idx);
-}
-
-template <int NL>
-__global__ void __launch_bounds__(64, 2) k_s2_gen_lane(S2PairArgs a, uint32_t first_abs, uint32_t n, LaneGroups<NL> g)
-{
-    const uint32_t idx = blockIdx.x * 64u + threadIdx.x;
-    GECM_LANE_CONSTS
-    giant_chunk<NL>(a, first_abs, n, first_abs == 0, k, idx);
-}
-
-template <int NL>
-__global__ void __launch_bounds__(64, 2) k_s2_pairs_lane(S2PairArgs a, uint32_t first, uint32_t count, LaneGroups<NL> g)
-{
-    const uint32_t per = (count + gridDim.y - 1) / gridDim.y;
-    const uint32_t off = blockIdx.y * per;
-    if (off >= count) return;
-    const uint32_t n = count - off < per ? count - off : per;
-    const uint32_t idx = blockIdx.x * 64u + threadIdx.x;
-    GECM_LANE_CONSTS
-    s2_pairs<NL>(a, first + off, n, k, idx, a.acc + (size_t)blockIdx.y * NL * a.stride);
-}
-
 template <int NL>
 __global__ void __launch_bounds__(64, 2) k_s2_merge_lane(uint32_t *acc, uint32_t slices, size_t stride, int init_only,
                                                          LaneGroups<NL> g)
 {
-    const uint32_t idx = blockIdx.x * 64u + threadIdx.x;
+    const bool init = init_only != 0;
     GECM_LANE_CONSTS
-    s2_merge<NL>(acc, slices, stride, init_only != 0, k, idx);
+    s2_merge<NL>(acc, slices, stride, init, k, blockIdx.x * 64u + threadIdx.x);
 }
 #endif
 
@@ -868,17 +833,58 @@ static S2Const<GECM_NL> s2_const(const gecm_modconst *mc)
     return k;
 }
 
-static ModGroups<GECM_NL> mod_groups(const gecm_modconst *mc)
+// the R^2 mod N of a single-modulus launch (to_mont, build)
+static Fe<GECM_NL> r2_const(const gecm_modconst *mc)
 {
-    return ModGroups<GECM_NL>{(const GroupConst<GECM_NL> *)mc->groups, mc->block_group};
+    Fe<GECM_NL> r2;
+    for (int i = 0; i < GECM_NL; i++) r2.v[i] = mc->r2[i];
+    return r2;
 }
 
-#if GECM_HAS_LANE
-static LaneGroups<GECM_NL> lane_groups(const gecm_modconst *mc)
+// a by-value kernel's constants argument of type V
+template <class V>
+static V by_value(const gecm_modconst *mc)
 {
-    return LaneGroups<GECM_NL>{(const GroupConst<GECM_NL> *)mc->groups, mc->curve_group};
+    if constexpr (std::is_same<V, Fe<GECM_NL>>::value) return r2_const(mc);
+    else if constexpr (std::is_same<V, S2Const<GECM_NL>>::value) return s2_const(mc);
+    else return mod_args<V>(mc);
 }
+
+// The one place that picks a kernel by the constants source of the launch (mc->source, set by the device layer): the
+// by-value kernel `kv`, whose last arguments are the V..., its per-wavefront twin `kw` or its per-lane twin `kl`, on
+// 64-thread blocks with the arguments `c...` they have in common.  nullptr stands for a twin that does not exist; a
+// launch whose source has none goes to the next in that order, as it always has (the device layer refuses such
+// launches before they get here).  GECM_LANE names a per-lane kernel where they are built, and nothing above
+// GECM_LANE_MAXNL limbs.
+#if GECM_HAS_LANE
+#define GECM_LANE(kernel) kernel<GECM_NL>
+#else
+#define GECM_LANE(kernel) nullptr
 #endif
+template <class KT>
+static constexpr bool has_kernel = !std::is_same<KT, std::nullptr_t>::value;
+
+template <class... V, class KV, class KW, class KL, class... C>
+static void launch_by_source(void *stream, const gecm_modconst *mc, dim3 grid, KV kv, KW kw, KL kl, const C &...c)
+{
+    const hipStream_t s = (hipStream_t)stream;
+    const dim3 block(64);
+    const auto *groups = (const GroupConst<GECM_NL> *)mc->groups;
+    if constexpr (has_kernel<KL>)
+        if (mc->source == GECM_SRC_LANE) {
+            hipLaunchKernelGGL(kl, grid, block, 0, s, c..., LaneGroups<GECM_NL>{groups, mc->curve_group});
+            return;
+        }
+    if constexpr (has_kernel<KW>)
+        if (mc->source != GECM_SRC_VALUE) {
+            hipLaunchKernelGGL(kw, grid, block, 0, s, c..., ModGroups<GECM_NL>{groups, mc->block_group});
+            return;
+        }
+    if constexpr (has_kernel<KV>) hipLaunchKernelGGL(kv, grid, block, 0, s, c..., by_value<V>(mc)...);
+}
+
+// one 64-thread block per 64 curves
+static dim3 blocks_of(size_t stride) { return dim3((unsigned)(stride / 64)); }
 
 #define CAT_(a, b) a##b
 #define CAT(a, b) CAT_(a, b)
@@ -889,98 +895,59 @@ static LaneGroups<GECM_NL> lane_groups(const gecm_modconst *mc)
 #endif
 
 #if GECM_HAS_PART(1)
-// one or two lanes per curve; MOD = ModK<GECM_NL> for a generic modulus
+// one or two lanes per curve; MOD = ModK<GECM_NL> for a generic modulus, which alone has multi-modulus kernels (and
+// per-lane ones with one lane per curve: gecm_dev_stage1 refuses two)
 template <class MOD>
-static void launch_stage1_mod(hipStream_t stream, const gecm_modconst *mc, const uint32_t *tape, uint32_t tape_len,
-                              uint32_t *X, uint32_t *Z, const uint32_t *S, size_t stride, int lanes)
+static void launch_stage1_mod(void *stream, const gecm_modconst *mc, const uint32_t *tape, uint32_t tape_len, uint32_t *X,
+                              uint32_t *Z, const uint32_t *S, size_t stride, int lanes)
 {
-    const dim3 grid((unsigned)(stride / (lanes == 2 ? 32 : 64))), block(64);
+    const dim3 grid((unsigned)(stride / (lanes == 2 ? 32 : 64)));
     if constexpr (std::is_same<MOD, ModK<GECM_NL>>::value) {
-#if GECM_HAS_LANE
-        if (mc->groups && mc->curve_group) {      // lane packing: one lane per curve (gecm_dev_stage1 refuses two)
-            hipLaunchKernelGGL(k_stage1_lane<GECM_NL>, grid, block, 0, stream, tape, tape_len, X, Z, S, stride, lane_groups(mc));
-            return;
-        }
-#endif
-        if (mc->groups) {
-            const auto g = mod_groups(mc);
-            if (lanes == 2) hipLaunchKernelGGL(k_stage1_pair_multi<GECM_NL>, grid, block, 0, stream, tape, tape_len, X, Z, S, stride, g);
-            else hipLaunchKernelGGL(k_stage1_multi<GECM_NL>, grid, block, 0, stream, tape, tape_len, X, Z, S, stride, g);
-            return;
-        }
-        const auto a = mod_args<ModArgs<GECM_NL>>(mc);
-        if (lanes == 2) hipLaunchKernelGGL(k_stage1_pair<GECM_NL>, grid, block, 0, stream, tape, tape_len, X, Z, S, stride, a);
-        else hipLaunchKernelGGL(k_stage1<GECM_NL>, grid, block, 0, stream, tape, tape_len, X, Z, S, stride, a);
-    } else {
-        const auto a = mod_args<ModArgsS<GECM_NL, MOD>>(mc);
-        if (lanes == 2) hipLaunchKernelGGL((k_stage1_pair_f<GECM_NL, MOD>), grid, block, 0, stream, tape, tape_len, X, Z, S, stride, a);
-        else hipLaunchKernelGGL((k_stage1_f<GECM_NL, MOD>), grid, block, 0, stream, tape, tape_len, X, Z, S, stride, a);
-    }
+        if (lanes == 2)
+            launch_by_source<ModArgs<GECM_NL>>(stream, mc, grid, k_stage1_pair<GECM_NL>, k_stage1_pair_multi<GECM_NL>, nullptr,
+                                               tape, tape_len, X, Z, S, stride);
+        else
+            launch_by_source<ModArgs<GECM_NL>>(stream, mc, grid, k_stage1<GECM_NL>, k_stage1_multi<GECM_NL>,
+                                               GECM_LANE(k_stage1_lane), tape, tape_len, X, Z, S, stride);
+    } else if (lanes == 2)
+        launch_by_source<ModArgsS<GECM_NL, MOD>>(stream, mc, grid, k_stage1_pair_f<GECM_NL, MOD>, nullptr, nullptr, tape,
+                                                 tape_len, X, Z, S, stride);
+    else
+        launch_by_source<ModArgsS<GECM_NL, MOD>>(stream, mc, grid, k_stage1_f<GECM_NL, MOD>, nullptr, nullptr, tape, tape_len,
+                                                 X, Z, S, stride);
 }
 
 static void launch_stage1(void *stream, const gecm_modconst *mc, const uint32_t *tape, uint32_t tape_len, uint32_t *X,
                           uint32_t *Z, const uint32_t *S, size_t stride, const uint32_t *modq, int lanes, int form)
 {
-    const hipStream_t s = (hipStream_t)stream;
     if (lanes == 8)
-        hipLaunchKernelGGL(k_stage1_quad<GECM_NL>, dim3((unsigned)(stride / 32)), dim3(256), 0, s, tape, tape_len, X, Z, S,   // stride: a multiple of 64
-                           stride, modq, mc->rho);
+        hipLaunchKernelGGL(k_stage1_quad<GECM_NL>, dim3((unsigned)(stride / 32)), dim3(256), 0, (hipStream_t)stream, tape,
+                           tape_len, X, Z, S, stride, modq, mc->rho);   // stride: a multiple of 64
     else if (form == 2) {
-        if constexpr (FPolicy<GECM_NL>::NF >= 3) launch_stage1_mod<ModC<GECM_NL>>(s, mc, tape, tape_len, X, Z, S, stride, lanes);
-    } else if (form > 0) launch_stage1_mod<ModF<GECM_NL>>(s, mc, tape, tape_len, X, Z, S, stride, lanes);
-    else if (form < 0) launch_stage1_mod<ModP<GECM_NL>>(s, mc, tape, tape_len, X, Z, S, stride, lanes);
-    else launch_stage1_mod<ModK<GECM_NL>>(s, mc, tape, tape_len, X, Z, S, stride, lanes);
+        if constexpr (FPolicy<GECM_NL>::NF >= 3) launch_stage1_mod<ModC<GECM_NL>>(stream, mc, tape, tape_len, X, Z, S, stride, lanes);
+    } else if (form > 0) launch_stage1_mod<ModF<GECM_NL>>(stream, mc, tape, tape_len, X, Z, S, stride, lanes);
+    else if (form < 0) launch_stage1_mod<ModP<GECM_NL>>(stream, mc, tape, tape_len, X, Z, S, stride, lanes);
+    else launch_stage1_mod<ModK<GECM_NL>>(stream, mc, tape, tape_len, X, Z, S, stride, lanes);
 }
 
 static void launch_canon(void *stream, const gecm_modconst *mc, uint32_t *X, uint32_t *Z, size_t stride)
 {
-    const dim3 grid((unsigned)(stride / 64)), block(64);
-    if (mc->groups)
-        hipLaunchKernelGGL(k_canon_multi<GECM_NL>, grid, block, 0, (hipStream_t)stream, X, Z, stride, mod_groups(mc));
-    else
-        hipLaunchKernelGGL(k_canon<GECM_NL>, grid, block, 0, (hipStream_t)stream, X, Z, stride,
-                           mod_args<ModArgs<GECM_NL>>(mc));
+    launch_by_source<ModArgs<GECM_NL>>(stream, mc, blocks_of(stride), k_canon<GECM_NL>, k_canon_multi<GECM_NL>, nullptr, X, Z,
+                                       stride);
 }
 
 static void launch_from_mont(void *stream, const gecm_modconst *mc, const uint32_t *X, const uint32_t *Z, uint32_t *ox,
                              uint32_t *oz, size_t stride)
 {
-    const dim3 grid((unsigned)(stride / 64)), block(64);
-#if GECM_HAS_LANE
-    if (mc->groups && mc->curve_group) {
-        hipLaunchKernelGGL(k_from_mont_lane<GECM_NL>, grid, block, 0, (hipStream_t)stream, X, Z, ox, oz, stride,
-                           lane_groups(mc));
-        return;
-    }
-#endif
-    if (mc->groups)
-        hipLaunchKernelGGL(k_from_mont_multi<GECM_NL>, grid, block, 0, (hipStream_t)stream, X, Z, ox, oz, stride,
-                           mod_groups(mc));
-    else
-        hipLaunchKernelGGL(k_from_mont<GECM_NL>, grid, block, 0, (hipStream_t)stream, X, Z, ox, oz, stride,
-                           mod_args<ModArgs<GECM_NL>>(mc));
+    launch_by_source<ModArgs<GECM_NL>>(stream, mc, blocks_of(stride), k_from_mont<GECM_NL>, k_from_mont_multi<GECM_NL>,
+                                       GECM_LANE(k_from_mont_lane), X, Z, ox, oz, stride);
 }
 
 static void launch_to_mont(void *stream, const gecm_modconst *mc, const uint32_t *ix, const uint32_t *iz, uint32_t *X,
                            uint32_t *Z, size_t stride)
 {
-    const dim3 grid((unsigned)(stride / 64)), block(64);
-#if GECM_HAS_LANE
-    if (mc->groups && mc->curve_group) {
-        hipLaunchKernelGGL(k_to_mont_lane<GECM_NL>, grid, block, 0, (hipStream_t)stream, ix, iz, X, Z, stride,
-                           lane_groups(mc));
-        return;
-    }
-#endif
-    if (mc->groups) {
-        hipLaunchKernelGGL(k_to_mont_multi<GECM_NL>, grid, block, 0, (hipStream_t)stream, ix, iz, X, Z, stride,
-                           mod_groups(mc));
-        return;
-    }
-    Fe<GECM_NL> r2;
-    for (int i = 0; i < GECM_NL; i++) r2.v[i] = mc->r2[i];
-    hipLaunchKernelGGL(k_to_mont<GECM_NL>, grid, block, 0, (hipStream_t)stream, ix, iz, X, Z, stride,
-                       mod_args<ModArgs<GECM_NL>>(mc), r2);
+    launch_by_source<ModArgs<GECM_NL>, Fe<GECM_NL>>(stream, mc, blocks_of(stride), k_to_mont<GECM_NL>, k_to_mont_multi<GECM_NL>,
+                                                    GECM_LANE(k_to_mont_lane), ix, iz, X, Z, stride);
 }
 
 static void launch_l0(void *stream, const gecm_modconst *mc, int op, const uint32_t *A, const uint32_t *B, uint32_t *C,
@@ -1004,57 +971,26 @@ static void launch_l0_inv(void *stream, const gecm_modconst *mc, const uint32_t 
 static void launch_gcd_scan(void *stream, const gecm_modconst *mc, const uint32_t *V, uint32_t *G, uint32_t *flags,
                             size_t stride)
 {
-    const dim3 grid((unsigned)(stride / 64)), block(64);
-#if GECM_HAS_LANE
-    if (mc->groups && mc->curve_group) {
-        hipLaunchKernelGGL(k_gcd_scan_lane<GECM_NL>, grid, block, 0, (hipStream_t)stream, V, G, flags, stride,
-                           lane_groups(mc));
-        return;
-    }
-#endif
-    if (mc->groups)
-        hipLaunchKernelGGL(k_gcd_scan_multi<GECM_NL>, grid, block, 0, (hipStream_t)stream, V, G, flags, stride,
-                           mod_groups(mc));
-    else
-        hipLaunchKernelGGL(k_gcd_scan<GECM_NL>, grid, block, 0, (hipStream_t)stream, V, G, flags, stride, s2_const(mc));
+    launch_by_source<S2Const<GECM_NL>>(stream, mc, blocks_of(stride), k_gcd_scan<GECM_NL>, k_gcd_scan_multi<GECM_NL>,
+                                       GECM_LANE(k_gcd_scan_lane), V, G, flags, stride);
 }
 
 static void launch_build(void *stream, const gecm_modconst *mc, const uint64_t *sigma, uint32_t *X, uint32_t *Z, uint32_t *S,
                          uint32_t *flags, size_t stride)
 {
-    const dim3 grid((unsigned)(stride / 64)), block(64);
-    if (mc->groups) {
-        hipLaunchKernelGGL(k_build_multi<GECM_NL>, grid, block, 0, (hipStream_t)stream, sigma, X, Z, S, flags, stride,
-                           mod_groups(mc));
-        return;
-    }
-    Fe<GECM_NL> r2;
-    for (int i = 0; i < GECM_NL; i++) r2.v[i] = mc->r2[i];
-    hipLaunchKernelGGL(k_build<GECM_NL>, grid, block, 0, (hipStream_t)stream, sigma, X, Z, S, flags, stride, s2_const(mc), r2);
+    launch_by_source<S2Const<GECM_NL>, Fe<GECM_NL>>(stream, mc, blocks_of(stride), k_build<GECM_NL>, k_build_multi<GECM_NL>,
+                                                    nullptr, sigma, X, Z, S, flags, stride);
 }
 
 static void launch_normalize(void *stream, const gecm_modconst *mc, uint32_t *X, uint32_t *Z, uint32_t *flags, size_t stride)
 {
-    const dim3 grid((unsigned)(stride / 64)), block(64);
-#if GECM_HAS_LANE
-    if (mc->groups && mc->curve_group) {
-        hipLaunchKernelGGL(k_normalize_lane<GECM_NL>, grid, block, 0, (hipStream_t)stream, X, Z, flags, stride,
-                           lane_groups(mc));
-        return;
-    }
-#endif
-    if (mc->groups)
-        hipLaunchKernelGGL(k_normalize_multi<GECM_NL>, grid, block, 0, (hipStream_t)stream, X, Z, flags, stride,
-                           mod_groups(mc));
-    else
-        hipLaunchKernelGGL(k_normalize<GECM_NL>, grid, block, 0, (hipStream_t)stream, X, Z, flags, stride, s2_const(mc));
+    launch_by_source<S2Const<GECM_NL>>(stream, mc, blocks_of(stride), k_normalize<GECM_NL>, k_normalize_multi<GECM_NL>,
+                                       GECM_LANE(k_normalize_lane), X, Z, flags, stride);
 }
 
 static void pack_group(const gecm_modconst *mc, void *out)
 {
-    GroupConst<GECM_NL> c;
-    c.k = s2_const(mc);
-    for (int i = 0; i < GECM_NL; i++) c.r2.v[i] = mc->r2[i];
+    const GroupConst<GECM_NL> c = {s2_const(mc), r2_const(mc)};
     memcpy(out, &c, sizeof c);
 }
 
@@ -1067,34 +1003,20 @@ extern "C" const gecm_kernels_p1 *CAT(CAT(gecm_kernels_, GECM_NL), _p1)(void)
 }
 #endif
 #if GECM_HAS_PART(2)
+// (a multi-modulus mc has K = 1: gecm_dev_s2_init)
 static void launch_s2_init(void *stream, const gecm_modconst *mc, const gecm_s2_init_launch *h)
 {
     const S2InitArgs &a = h->a;
-    const S2Const<GECM_NL> k = s2_const(mc);
-    const dim3 grid((unsigned)(a.stride / 64)), block(64);
-#if GECM_HAS_LANE
-    if (mc->groups && mc->curve_group) {
-        const auto g = lane_groups(mc);
-        hipLaunchKernelGGL(k_s2_init_lane<GECM_NL>, grid, block, 0, (hipStream_t)stream, a, g);
-        if (h->slices > 1)
-            hipLaunchKernelGGL(k_s2_merge_lane<GECM_NL>, grid, block, 0, (hipStream_t)stream, a.acc, h->slices, a.stride, 1, g);
-        return;
-    }
-#endif
-    if (mc->groups) {                 // K = 1 (gecm_dev_s2_init)
-        const auto g = mod_groups(mc);
-        hipLaunchKernelGGL(k_s2_init_multi<GECM_NL>, grid, block, 0, (hipStream_t)stream, a, g);
-        if (h->slices > 1)
-            hipLaunchKernelGGL(k_s2_merge_multi<GECM_NL>, grid, block, 0, (hipStream_t)stream, a.acc, h->slices, a.stride, 1, g);
-        return;
-    }
-    if (a.K > 1)
-        hipLaunchKernelGGL(k_s2_init_k<GECM_NL>, dim3((unsigned)(a.stride / 64 * a.K)), block, 0, (hipStream_t)stream, a, k);
+    const dim3 grid = blocks_of(a.stride);
+    if (mc->source == GECM_SRC_VALUE && a.K > 1)
+        launch_by_source<S2Const<GECM_NL>>(stream, mc, blocks_of(a.stride * a.K), k_s2_init_k<GECM_NL>, nullptr, nullptr, a);
     else
-        hipLaunchKernelGGL(k_s2_init<GECM_NL>, grid, block, 0, (hipStream_t)stream, a, k);
+        launch_by_source<S2Const<GECM_NL>>(stream, mc, grid, k_s2_init<GECM_NL>, k_s2_init_multi<GECM_NL>,
+                                           GECM_LANE(k_s2_init_lane), a);
     // the pair walk's other accumulators (slice 0 is acc itself, set by the table build)
     if (h->slices > 1)
-        hipLaunchKernelGGL(k_s2_merge<GECM_NL>, grid, block, 0, (hipStream_t)stream, a.acc, h->slices, a.stride, 1, k);
+        launch_by_source<S2Const<GECM_NL>>(stream, mc, grid, k_s2_merge<GECM_NL>, k_s2_merge_multi<GECM_NL>,
+                                           GECM_LANE(k_s2_merge_lane), a.acc, h->slices, a.stride, 1);
 }
 
 static void launch_s2_pair(void *stream, const gecm_modconst *mc, const gecm_s2_pair_launch *h)
@@ -1102,36 +1024,25 @@ static void launch_s2_pair(void *stream, const gecm_modconst *mc, const gecm_s2_
     const S2PairArgs &a = h->a;
     // the tape on the host decides the launch sequence: one k_s2_gen per "generate" mark, one
     // k_s2_pairs per run of pairs between marks (~84 + 84 launches per 1e8 range)
-    const dim3 grid((unsigned)(a.stride / 64)), block(64);
+    const dim3 grid = blocks_of(a.stride);
     const dim3 pgrid((unsigned)(a.stride / 64), h->slices ? h->slices : 1);
-    const S2Const<GECM_NL> k = s2_const(mc);
     // a "generate" mark with bit 31 set in its count is a single-chain chunk (the reference's last batch of the range,
-    // gecm_stage2_pair); the others use K sub-sequences per curve when the batch is small (a.K > 1)
-    const dim3 kgrid((unsigned)(a.stride / 64 * (a.K ? a.K : 1)));
-    const ModGroups<GECM_NL> g = mc->groups ? mod_groups(mc) : ModGroups<GECM_NL>{};   // multi-modulus: K = 1
+    // gecm_stage2_pair); the others use K sub-sequences per curve when the batch is small (a.K > 1; a multi-modulus mc
+    // has K = 1)
+    const dim3 kgrid = blocks_of(a.stride * (a.K ? a.K : 1));
     uint32_t generated = 0, i = 0, kprev = 1;
-    // lane packing: the same launch sequence over the per-lane kernels (built up to GECM_LANE_MAXNL limbs)
-#if GECM_HAS_LANE
-    const bool lane = mc->groups && mc->curve_group;
-    const LaneGroups<GECM_NL> lg = lane ? lane_groups(mc) : LaneGroups<GECM_NL>{};
-#define GECM_LANE_LAUNCH(...) hipLaunchKernelGGL(__VA_ARGS__)
-#else
-    const bool lane = false;
-#define GECM_LANE_LAUNCH(...) (void)0
-#endif
     while (i < a.nsteps) {
         if (h->host_steps[2 * i] == S2_STEP_GEN) {
             const uint32_t word = h->host_steps[2 * i + 1];
             const uint32_t n = word & 0x7fffffffu;
-            if (lane)
-                GECM_LANE_LAUNCH(k_s2_gen_lane<GECM_NL>, grid, block, 0, (hipStream_t)stream, a, generated, n, lg);
-            else if (mc->groups)
-                hipLaunchKernelGGL(k_s2_gen_multi<GECM_NL>, grid, block, 0, (hipStream_t)stream, a, generated, n, g);
+            if (mc->source != GECM_SRC_VALUE)
+                launch_by_source<>(stream, mc, grid, nullptr, k_s2_gen_multi<GECM_NL>, GECM_LANE(k_s2_gen_lane), a, generated, n);
             else if (a.K > 1 && !(word & 0x80000000u)) {
-                hipLaunchKernelGGL(k_s2_gen_k<GECM_NL>, kgrid, block, 0, (hipStream_t)stream, a, generated, n, k);
+                launch_by_source<S2Const<GECM_NL>>(stream, mc, kgrid, k_s2_gen_k<GECM_NL>, nullptr, nullptr, a, generated, n);
                 kprev = a.K;
             } else {
-                hipLaunchKernelGGL(k_s2_gen<GECM_NL>, grid, block, 0, (hipStream_t)stream, a, generated, n, generated ? kprev : 1u, k);
+                launch_by_source<S2Const<GECM_NL>>(stream, mc, grid, k_s2_gen<GECM_NL>, nullptr, nullptr, a, generated, n,
+                                                   generated ? kprev : 1u);
                 kprev = 1;
             }
             generated += n;
@@ -1139,24 +1050,14 @@ static void launch_s2_pair(void *stream, const gecm_modconst *mc, const gecm_s2_
         } else {
             uint32_t j = i;
             while (j < a.nsteps && h->host_steps[2 * j] != S2_STEP_GEN) j++;
-            if (lane)
-                GECM_LANE_LAUNCH(k_s2_pairs_lane<GECM_NL>, pgrid, block, 0, (hipStream_t)stream, a, i, j - i, lg);
-            else if (mc->groups)
-                hipLaunchKernelGGL(k_s2_pairs_multi<GECM_NL>, pgrid, block, 0, (hipStream_t)stream, a, i, j - i, g);
-            else
-                hipLaunchKernelGGL(k_s2_pairs<GECM_NL>, pgrid, block, 0, (hipStream_t)stream, a, i, j - i, k);
+            launch_by_source<S2Const<GECM_NL>>(stream, mc, pgrid, k_s2_pairs<GECM_NL>, k_s2_pairs_multi<GECM_NL>,
+                                               GECM_LANE(k_s2_pairs_lane), a, i, j - i);
             i = j;
         }
     }
-    if (h->slices > 1) {
-        if (lane)
-            GECM_LANE_LAUNCH(k_s2_merge_lane<GECM_NL>, grid, block, 0, (hipStream_t)stream, a.acc, h->slices, a.stride, 0, lg);
-        else if (mc->groups)
-            hipLaunchKernelGGL(k_s2_merge_multi<GECM_NL>, grid, block, 0, (hipStream_t)stream, a.acc, h->slices, a.stride, 0, g);
-        else
-            hipLaunchKernelGGL(k_s2_merge<GECM_NL>, grid, block, 0, (hipStream_t)stream, a.acc, h->slices, a.stride, 0, k);
-    }
-#undef GECM_LANE_LAUNCH
+    if (h->slices > 1)
+        launch_by_source<S2Const<GECM_NL>>(stream, mc, grid, k_s2_merge<GECM_NL>, k_s2_merge_multi<GECM_NL>,
+                                           GECM_LANE(k_s2_merge_lane), a.acc, h->slices, a.stride, 0);
 }
 
 extern "C" const gecm_kernels_p2 *CAT(CAT(gecm_kernels_, GECM_NL), _p2)(void)

@@ -12,18 +12,24 @@
 #define GECM_NL_LIST(X) X(8) X(10) X(12) X(14) X(15) X(17) X(19) X(21) X(23) X(26) X(28) X(30) X(32) X(34) X(37)
 #endif
 
+/* Where the kernels of a launch find the constants of their modulus.  The device layer says it (modconst() in
+ * gecm_dev.hip); the launchers pick the kernel by it in one place (launch_by_source in gecm_kernels.hip). */
+enum gecm_source {
+    GECM_SRC_VALUE = 0, /* single modulus: n, kp, one, r3, rho, inv_iters (and r2) below, passed as kernel arguments */
+    GECM_SRC_WAVE,      /* one modulus per 64-curve block: groups and block_group, the _multi kernels */
+    GECM_SRC_LANE       /* one modulus per curve position: groups and curve_group, the _lane kernels of
+                         * stage1 (one lane per curve), from_mont, to_mont, gcd_scan, normalize, s2_init and s2_pair
+                         * (limb counts with gecm_kernels_p1::has_lane) */
+};
+
 typedef struct {
     const uint32_t *n, *kp, *one, *r3;
     uint32_t rho, inv_iters;
-    /* multi-modulus launch, else NULL: device array of the moduli's constants (pack_group), and the
-     * modulus of every 64-curve block; the launchers then run the kernels' _multi instantiations */
-    const void *groups;
-    const uint32_t *block_group;
-    const uint32_t *r2;          /* R^2 mod N: to_mont of a single-modulus launch, and pack_group */
-    /* lane-packed multi-modulus launch, else NULL: the modulus of every curve position (device array);
-     * with `groups` it sends stage1 (one lane per curve), from_mont, to_mont, gcd_scan, s2_init and s2_pair to the
-     * kernels' _lane instantiations (limb counts with gecm_kernels_p1::has_lane) */
-    const uint32_t *curve_group;
+    const void *groups;          /* WAVE, LANE: device array of the moduli's constants (pack_group), else NULL */
+    const uint32_t *block_group; /* WAVE: the modulus of every 64-curve block (device array), else NULL */
+    const uint32_t *r2;          /* R^2 mod N: to_mont and build of a single-modulus launch, and pack_group */
+    const uint32_t *curve_group; /* LANE: the modulus of every curve position (device array), else NULL */
+    enum gecm_source source;
 } gecm_modconst;
 
 /* Stage-2 kernel arguments (csrc/gecm_stage2.hpp), passed by value: the type names are part of the kernel symbols. */
