@@ -85,7 +85,7 @@ struct gecm_ctx {
     /* tape cache: the tape of tape_k, one ecm_stage1 call of the reference or one extension segment */
     gecm_tape_t tape;
     tape_key tape_k;
-    int tape_on_dev;
+    tape_key dev_tape_k;     /* the tape dev holds (all zero: none, which is no tape's key) */
     double last_ms;
     /* counters of the stage 1 in progress: summed over the ranges run since range 0 (work->ptadds / ptdups are
      * cleared when the curves are built, ecm.c:1177-1178, and grow through every ecm_stage1 call) */
@@ -119,14 +119,20 @@ struct gecm_ctx {
     uint32_t s2_amin_last;
     int lanes_per_curve;     /* 0 = auto, 1, 2, 8, 32 (gecm_set_lanes_per_curve) */
     int build_where, build_used;   /* GECM_BUILD_HOST / _DEVICE: asked for (gecm_set_curve_build), used by the last build */
-    /* F-form stage 1 for N | 2^k - 1: a second device context working modulo Mw = 2^k - 1
-     * (csrc/gecm_field.hpp); results are brought back modulo N by ff_settle() */
-    gecm_dev *dev_f;
-    int ff_k, ff_sign, ff_nl, ff_on, ff_pending, ff_loaded, last_on_f;
-    uint64_t ff_c;           /* Mw = 2^ff_k - ff_c for ff_sign > 0 (1: Mersenne form), 2^ff_k + 1 for ff_sign < 0 */
-    tape_key ff_tape_k;
-    mpl_t ff_M, ff_r_mod_m;  /* Mw; 2^(28 ff_nl) mod Mw */
-    uint32_t *ff_n28;        /* n, kp, one for dev_f */
+    /* the special-form twin of a context whose N divides Mw = 2^k -/+ 1 or 2^k - c: a second device context working
+     * modulo Mw with the special stage-1 multiply (csrc/gecm_field.hpp); see "the special-form twin" below */
+    struct {
+        gecm_dev *dev;       /* NULL: this N has no twin */
+        int k, sign;         /* Mw = 2^k - c for sign > 0 (c = 1: Mersenne form), 2^k + 1 for sign < 0 */
+        uint64_t c;
+        int nl;              /* limbs of Mw */
+        uint32_t *n28;       /* constants block, nl limbs each: Mw, kp, one = R mod Mw, R^2 mod Mw (R = 2^(28 nl)) */
+        int on;              /* gecm_set_special_form */
+        int loaded;          /* the twin holds the main context's points (twin_fill) */
+        int pending;         /* a launch ran on the twin and its X, Z are not back in the main context (ff_settle) */
+        int ran_last;        /* the last stage-1 launch ran on the twin */
+        tape_key tape_k;     /* the tape twin.dev holds, as dev_tape_k */
+    } twin;
     /* multi-modulus context (gecm_create_multi): grp[] holds every modulus's N and constants (at this
      * context's limb count); the curves are grouped by modulus, each group padded to whole wavefronts of 64, and the
      * batch arrays are in that device order.  The caller numbers curves in its own order (curve_at). */
@@ -160,10 +166,61 @@ static int pick_nl(int nbits)
     return 0;
 }
 
-/* N | 2^k - 1, N | 2^k + 1 or N | 2^k - c with c below one reference limb (the reference's isMersenne == +1 / -1 / c,
- * main.c:410-441): open a second device context modulo Mw = 2^k -/+ 1 or 2^k - c for the special stage-1 multiply
- * (csrc/gecm_field.hpp, F-form / P-form / C-form) when that is the cheaper multiply.  Failure to set it up is not an error: stage 1 then runs modulo N
- * like everything else. */
+/* ---- host worker threads ---------------------------------------------------------------------- */
+static int host_threads(void)
+{
+    /* worker threads for host-side batch work: GECM_HOST_THREADS, else min(8, online CPUs) */
+    const char *e = getenv("GECM_HOST_THREADS");
+    long n = e ? atol(e) : sysconf(_SC_NPROCESSORS_ONLN);
+    if (n < 1) n = 1;
+    if (!e && n > 8) n = 8;
+    if (n > 64) n = 64;
+    return (int)n;
+}
+
+/* fn(arg, lo, hi) over the slices of [0, n), 256 or more items each, on up to host_threads() threads (a thread that
+ * cannot be started: its slice runs here).  Returns an error (< 0) of some slice, else the OR of the slices' results. */
+typedef struct {
+    int (*fn)(void *arg, size_t lo, size_t hi);
+    void *arg;
+    size_t lo, hi;
+    int ret;
+} slice_job;
+
+static void *slice_run(void *job)
+{
+    slice_job *j = (slice_job *)job;
+    j->ret = j->fn(j->arg, j->lo, j->hi);
+    return NULL;
+}
+
+static int run_slices(size_t n, int (*fn)(void *arg, size_t lo, size_t hi), void *arg)
+{
+    int nt = host_threads();
+    if ((size_t)nt > n / 256 + 1) nt = (int)(n / 256 + 1);
+    slice_job jobs[64];
+    pthread_t th[64];
+    for (int t = 0; t < nt; t++)
+        jobs[t] = (slice_job){fn, arg, n * (size_t)t / (size_t)nt, n * (size_t)(t + 1) / (size_t)nt, 0};
+    for (int t = 1; t < nt; t++)
+        if (pthread_create(&th[t], NULL, slice_run, &jobs[t])) { slice_run(&jobs[t]); th[t] = 0; }
+    slice_run(&jobs[0]);
+    int err = 0, any = 0;
+    for (int t = 0; t < nt; t++) {
+        if (t > 0 && th[t]) pthread_join(th[t], NULL);
+        if (jobs[t].ret < 0) err = jobs[t].ret;
+        any |= jobs[t].ret;
+    }
+    return err ? err : any;
+}
+
+/* ---- the special-form twin --------------------------------------------------------------------
+ * N | 2^k - 1, N | 2^k + 1 or N | 2^k - c with c below one reference limb (the reference's isMersenne == +1 / -1 / c,
+ * main.c:410-441): ff_setup opens a second device context modulo Mw = 2^k -/+ 1 or 2^k - c for the special stage-1
+ * multiply (csrc/gecm_field.hpp, F-form / P-form / C-form) when that is the cheaper multiply.  twin_fill loads it with
+ * the main context's batch, stage1_launch runs the chain there, and ff_settle brings X, Z back modulo N: everything
+ * after stage 1 (save lines, factor scan, stage 2) works on residues modulo N as always.  Failure to set the twin up
+ * is not an error: stage 1 then runs modulo N like everything else. */
 static void ff_setup(gecm_ctx *c)
 {
     cunningham_form f;
@@ -178,41 +235,101 @@ static void ff_setup(gecm_ctx *c)
     if (f.form == 2 && nlf - G < 3) return;                          /* limbs 0, 1 carry c - 1: one pure F limb above */
     /* multiply-adds per modular multiplication: about nl^2 + G*nl (+ 3 nl for 2^k - c) against 2 nl^2 + nl */
     if ((double)(nlf * nlf + (G + (f.form == 2 ? 3 : 0)) * nlf) * 1.15 > (double)(2 * c->mod.nl * c->mod.nl + c->mod.nl)) return;
-    mpl_t one, t;
+    mpl_t one, t, M, r;
     mpl_set_u64(&one, 1);
-    mpl_shl(&c->ff_M, &one, (unsigned)f.k);
-    if (f.form == 2) { mpl_set_u64(&t, f.c); mpl_sub(&c->ff_M, &c->ff_M, &t); }
-    else if (f.form > 0) mpl_sub(&c->ff_M, &c->ff_M, &one);
-    else mpl_add(&c->ff_M, &c->ff_M, &one);
-    { mpl_t r; mpl_mod(&r, &c->ff_M, &c->mod.N); if (!mpl_is_zero(&r)) return; }   /* N | Mw, or nothing below holds */
-    gecm_mod_pow2(&c->ff_r_mod_m, (unsigned)(LIMB_BITS * nlf), &c->ff_M);
-    c->ff_n28 = (uint32_t *)calloc((size_t)nlf * 3, sizeof(uint32_t));
-    if (!c->ff_n28) return;
-    mpl_to_limbs32(c->ff_n28, 1, nlf, LIMB_BITS, &c->ff_M);
-    mpl_to_limbs32(c->ff_n28 + 2 * nlf, 1, nlf, LIMB_BITS, &c->ff_r_mod_m);
+    mpl_shl(&M, &one, (unsigned)f.k);
+    if (f.form == 2) { mpl_set_u64(&t, f.c); mpl_sub(&M, &M, &t); }
+    else if (f.form > 0) mpl_sub(&M, &M, &one);
+    else mpl_add(&M, &M, &one);
+    mpl_mod(&r, &M, &c->mod.N);
+    if (!mpl_is_zero(&r)) return;                                    /* N | Mw, or nothing below holds */
+    uint32_t *q = (uint32_t *)calloc((size_t)nlf * 4, sizeof(uint32_t));
+    if (!q) return;
+    gecm_mod_pow2(&r, (unsigned)(LIMB_BITS * nlf), &M);
+    mpl_to_limbs32(q, 1, nlf, LIMB_BITS, &M);
+    mpl_to_limbs32(q + 2 * nlf, 1, nlf, LIMB_BITS, &r);
+    mpl_mulmod(&r, &r, &r, &M);
+    mpl_to_limbs32(q + 3 * nlf, 1, nlf, LIMB_BITS, &r);
     /* rho = -Mw^-1 mod 2^28: 1 for 2^k - 1, 2^28 - 1 for 2^k + 1, (c mod 2^28)^-1 for 2^k - c */
     uint32_t rho = f.form == 1 ? 1u : (1u << LIMB_BITS) - 1u;
     if (f.form == 2) {
         mpl_t two28, inv;
         mpl_set_u64(&two28, 1u << LIMB_BITS);
-        if (!mpl_invmod(&inv, &c->ff_M, &two28)) { free(c->ff_n28); c->ff_n28 = NULL; return; }
+        if (!mpl_invmod(&inv, &M, &two28)) { free(q); return; }
         mpl_sub(&inv, &two28, &inv);
         rho = (uint32_t)mpl_get_u64(&inv);
     }
-    if (gecm_mod_make_kp(c->ff_n28 + nlf, &c->ff_M, nlf) ||
-        gecm_dev_open(&c->dev_f, c->device, nlf, c->ff_n28, c->ff_n28 + nlf, c->ff_n28 + 2 * nlf, rho)) {
-        free(c->ff_n28);
-        c->ff_n28 = NULL;
-        c->dev_f = NULL;
+    if (gecm_mod_make_kp(q + nlf, &M, nlf) || gecm_dev_open(&c->twin.dev, c->device, nlf, q, q + nlf, q + 2 * nlf, rho)) {
+        free(q);
+        c->twin.dev = NULL;
         return;
     }
-    gecm_dev_set_fform(c->dev_f, f.form);
-    c->ff_k = f.k;
-    c->ff_sign = f.form < 0 ? -1 : 1;
-    c->ff_c = f.form == 2 ? f.c : 1;
-    c->ff_nl = nlf;
-    c->ff_on = 1;
+    gecm_dev_set_fform(c->twin.dev, f.form);
+    c->twin.n28 = q;
+    c->twin.k = f.k;
+    c->twin.sign = f.form < 0 ? -1 : 1;
+    c->twin.c = f.form == 2 ? f.c : 1;
+    c->twin.nl = nlf;
+    c->twin.on = 1;
 }
+
+/* The batch the main context holds into the twin, converted on the device (gecm_dev_fill_twin): out of Montgomery
+ * form modulo N, the limb planes copied, into Montgomery form modulo Mw (x < N <= Mw).  The only code that puts
+ * points into the twin, whether or not gecm_set_special_form has it switched on; for its callers a failure is a
+ * device error (gecm_dev_error has the text).  Nothing to do on a context without a twin. */
+static int twin_fill(gecm_ctx *c)
+{
+    if (!c->twin.dev) return 0;
+    const int rc = gecm_dev_fill_twin(c->twin.dev, c->dev, c->twin.n28 + 3 * c->twin.nl);
+    c->twin.loaded = !rc;
+    return rc;
+}
+
+/* ff_settle: wait for the stage-1 kernel that ran on the twin, fetch its X, Z (canonical, de-Montgomeryised), reduce
+ * them modulo N, put them back into Montgomery form modulo N and store them in the main context as if stage 1 had run
+ * there.  Nothing to do, and GECM_OK, when no launch on the twin is pending (or c is NULL: the callers check that
+ * after it). */
+typedef struct {
+    const gecm_ctx *c;
+    uint32_t *f;              /* fx, fz [twin.nl][batch], then hX, hZ [nl][batch] */
+} settle_job;
+
+static int settle_slice(void *arg, size_t lo, size_t hi)
+{
+    const settle_job *j = (const settle_job *)arg;
+    const gecm_ctx *c = j->c;
+    const size_t batch = c->batch, fwords = (size_t)c->twin.nl * batch, words = (size_t)c->mod.nl * batch;
+    for (size_t i = lo; i < hi; i++)
+        for (int q = 0; q < 2; q++) {                /* x, z */
+            mpl_t v;
+            mpl_from_limbs32(&v, j->f + q * fwords + i, batch, c->twin.nl, LIMB_BITS);
+            mpl_mod(&v, &v, &c->mod.N);
+            mpl_mulmod(&v, &v, &c->mod.rint_mod_n, &c->mod.N);
+            mpl_to_limbs32(j->f + 2 * fwords + q * words + i, batch, c->mod.nl, LIMB_BITS, &v);
+        }
+    return 0;
+}
+
+static int ff_settle(gecm_ctx *c)
+{
+    if (!c || !c->twin.pending) return GECM_OK;
+    c->twin.pending = 0;
+    if (gecm_dev_sync(c->twin.dev)) { set_err("%s", gecm_dev_error()); return GECM_ERR_DEVICE; }
+    c->last_ms = gecm_dev_last_kernel_ms(c->twin.dev);
+    const size_t batch = c->batch, fwords = (size_t)c->twin.nl * batch, words = (size_t)c->mod.nl * batch;
+    uint32_t *f = (uint32_t *)calloc(2 * fwords + 2 * words, 4);
+    if (!f) return GECM_ERR_NOMEM;
+    if (gecm_dev_download_plain(c->twin.dev, f, f + fwords)) { free(f); set_err("%s", gecm_dev_error()); return GECM_ERR_DEVICE; }
+    settle_job j = {c, f};
+    run_slices(batch, settle_slice, &j);
+    int rc = gecm_dev_upload_xz(c->dev, f + 2 * fwords, f + 2 * fwords + words);
+    free(f);
+    if (rc) { set_err("%s", gecm_dev_error()); return GECM_ERR_DEVICE; }
+    return GECM_OK;
+}
+
+/* the device the last stage-1 launch ran on */
+static inline gecm_dev *last_dev(const gecm_ctx *c) { return c->twin.ran_last ? c->twin.dev : c->dev; }
 
 /* Constants of the 32-lanes-per-curve stage-1 kernel (csrc/gecm_row.hpp): it works modulo N' = m*N, the multiple
  * of N that is -1 modulo 2^28 (the Montgomery digit is then the low limb itself), on L limbs (nl + 1 rounded up
@@ -306,8 +423,8 @@ void gecm_destroy(gecm_ctx *c)
     if (!c) return;
     gecm_dev_close(c->dev);
     gecm_dev_close(c->dev_l0);
-    gecm_dev_close(c->dev_f);
-    free(c->ff_n28);
+    gecm_dev_close(c->twin.dev);
+    free(c->twin.n28);
     if (c->pf_active) { pthread_join(c->pf_thread, NULL); c->pf_active = 0; gecm_tape_free(&c->pf_tape); }
     gecm_tape_free(&c->tape);
     free_batch(c);
@@ -381,7 +498,7 @@ uint64_t gecm_batch_bytes(const gecm_ctx *c, size_t curves, int with_stage2, uin
         }
     }
     uint64_t b = gecm_dev_batch_bytes(c->dev, curves, npb, S2_GIANT_CHUNK, S2_RING);
-    if (c->dev_f) b += gecm_dev_batch_bytes(c->dev_f, curves, 0, 0, 0);
+    if (c->twin.dev) b += gecm_dev_batch_bytes(c->twin.dev, curves, 0, 0, 0);
     return b;
 }
 
@@ -522,81 +639,10 @@ static int alloc_batch(gecm_ctx *c, size_t batch)
     if (!c->sigma || !c->bad || !c->hx || !c->hz || !c->hacc || !c->hfail) { free_batch(c); return GECM_ERR_NOMEM; }
     c->batch = batch;
     if (gecm_dev_resize(c->dev, batch)) { set_err("%s", gecm_dev_error()); return GECM_ERR_DEVICE; }
-    c->ff_pending = 0;
-    c->ff_loaded = 0;
-    if (c->dev_f && gecm_dev_resize(c->dev_f, batch)) { set_err("%s", gecm_dev_error()); return GECM_ERR_DEVICE; }
+    c->twin.pending = 0;
+    c->twin.loaded = 0;
+    if (c->twin.dev && gecm_dev_resize(c->twin.dev, batch)) { set_err("%s", gecm_dev_error()); return GECM_ERR_DEVICE; }
     return GECM_OK;
-}
-
-static int host_threads(void)
-{
-    /* worker threads for host-side batch work: GECM_HOST_THREADS, else min(8, online CPUs) */
-    const char *e = getenv("GECM_HOST_THREADS");
-    long n = e ? atol(e) : sysconf(_SC_NPROCESSORS_ONLN);
-    if (n < 1) n = 1;
-    if (!e && n > 8) n = 8;
-    if (n > 64) n = 64;
-    return (int)n;
-}
-
-/* fn(arg, lo, hi) over the slices of [0, n), 256 or more items each, on up to host_threads() threads (a thread that
- * cannot be started: its slice runs here).  Returns an error (< 0) of some slice, else the OR of the slices' results. */
-typedef struct {
-    int (*fn)(void *arg, size_t lo, size_t hi);
-    void *arg;
-    size_t lo, hi;
-    int ret;
-} slice_job;
-
-static void *slice_run(void *job)
-{
-    slice_job *j = (slice_job *)job;
-    j->ret = j->fn(j->arg, j->lo, j->hi);
-    return NULL;
-}
-
-static int run_slices(size_t n, int (*fn)(void *arg, size_t lo, size_t hi), void *arg)
-{
-    int nt = host_threads();
-    if ((size_t)nt > n / 256 + 1) nt = (int)(n / 256 + 1);
-    slice_job jobs[64];
-    pthread_t th[64];
-    for (int t = 0; t < nt; t++)
-        jobs[t] = (slice_job){fn, arg, n * (size_t)t / (size_t)nt, n * (size_t)(t + 1) / (size_t)nt, 0};
-    for (int t = 1; t < nt; t++)
-        if (pthread_create(&th[t], NULL, slice_run, &jobs[t])) { slice_run(&jobs[t]); th[t] = 0; }
-    slice_run(&jobs[0]);
-    int err = 0, any = 0;
-    for (int t = 0; t < nt; t++) {
-        if (t > 0 && th[t]) pthread_join(th[t], NULL);
-        if (jobs[t].ret < 0) err = jobs[t].ret;
-        any |= jobs[t].ret;
-    }
-    return err ? err : any;
-}
-
-/* plain residues for the batch just built (gecm_resume_points): px, pz canonical in [0, N), [nl][batch] in device
- * order; X, Z of the build are replaced by their Montgomery forms, made on the device.  A special-form twin takes the
- * same residues (x < N <= Mw) with its own R^2 mod Mw and stays loaded. */
-static int upload_plain(gecm_ctx *c, const uint32_t *px, const uint32_t *pz)
-{
-    if (gecm_dev_upload_plain(c->dev, px, pz, c->multi ? NULL : gecm_mod_r2(&c->mod))) return GECM_ERR_DEVICE;
-    if (!c->dev_f || !c->ff_loaded) return GECM_OK;
-    const size_t batch = c->batch, fwords = (size_t)c->ff_nl * batch;
-    uint32_t *f = (uint32_t *)calloc(2 * fwords + (size_t)c->ff_nl, 4);
-    if (!f) return GECM_ERR_NOMEM;
-    mpl_t v;
-    for (size_t i = 0; i < batch; i++) {
-        mpl_from_limbs32(&v, px + i, batch, c->mod.nl, LIMB_BITS);
-        mpl_to_limbs32(f + i, batch, c->ff_nl, LIMB_BITS, &v);
-        mpl_from_limbs32(&v, pz + i, batch, c->mod.nl, LIMB_BITS);
-        mpl_to_limbs32(f + fwords + i, batch, c->ff_nl, LIMB_BITS, &v);
-    }
-    mpl_mulmod(&v, &c->ff_r_mod_m, &c->ff_r_mod_m, &c->ff_M);
-    mpl_to_limbs32(f + 2 * fwords, 1, c->ff_nl, LIMB_BITS, &v);
-    const int rc = gecm_dev_upload_plain(c->dev_f, f, f + fwords, f + 2 * fwords);
-    free(f);
-    return rc ? GECM_ERR_DEVICE : GECM_OK;
 }
 
 /* The device build of the batch alloc_batch has just set up (gecm_set_curve_build): sigma[0 .. total) in device order,
@@ -615,60 +661,35 @@ static int build_on_device(gecm_ctx *c, const uint64_t *sigma, size_t total, con
     return any;
 }
 
-/* build_single with the construction on the device.  A special-form twin is filled from the main context on the
- * device, after the caller's points (px, pz) are in: no big-integer work per curve on the host. */
-static int build_single_device(gecm_ctx *c, const uint64_t *sigma, size_t batch, const uint32_t *px, const uint32_t *pz)
-{
-    int rc = alloc_batch(c, batch);
-    if (rc) return rc;
-    memcpy(c->sigma, sigma, batch * sizeof(uint64_t));
-    const int built = build_on_device(c, sigma, batch, NULL);
-    if (built < 0) { free_batch(c); return built; }
-    rc = px ? gecm_dev_upload_plain(c->dev, px, pz, gecm_mod_r2(&c->mod)) : 0;
-    if (!rc && c->dev_f) {
-        uint32_t *r2 = (uint32_t *)calloc((size_t)c->ff_nl, 4);
-        if (!r2) { free_batch(c); return GECM_ERR_NOMEM; }
-        mpl_t v;
-        mpl_mulmod(&v, &c->ff_r_mod_m, &c->ff_r_mod_m, &c->ff_M);
-        mpl_to_limbs32(r2, 1, c->ff_nl, LIMB_BITS, &v);
-        rc = gecm_dev_fill_twin(c->dev_f, c->dev, r2);
-        free(r2);
-        c->ff_loaded = !rc;
-    }
-    if (rc) { set_err("%s", gecm_dev_error()); free_batch(c); return GECM_ERR_DEVICE; }
-    return built;
-}
-
-/* gecm_build_curves after its checks; px != NULL: gecm_resume_points, the points are px, pz (upload_plain) */
+/* gecm_build_curves after its checks: the batch allocated, the curves constructed on the host and uploaded or on the
+ * device (gecm_set_curve_build), then px != NULL: gecm_resume_points, X and Z replaced by the Montgomery forms of
+ * the plain residues px, pz (canonical in [0, N), [nl][batch]), made on the device; last the twin, from what the main
+ * context now holds. */
 static int build_single(gecm_ctx *c, const uint64_t *sigma, size_t batch, const uint32_t *px, const uint32_t *pz)
 {
     c->build_used = c->build_where;
-    if (c->build_where == GECM_BUILD_DEVICE) return build_single_device(c, sigma, batch, px, pz);
     int rc = alloc_batch(c, batch);
     if (rc) return rc;
     memcpy(c->sigma, sigma, batch * sizeof(uint64_t));
-    size_t words = (size_t)c->mod.nl * batch;
-    uint32_t *hX = (uint32_t *)calloc(words * 3, 4);
-    if (!hX) { free_batch(c); return GECM_ERR_NOMEM; }
-    const size_t fwords = c->dev_f ? (size_t)c->ff_nl * batch : 0;
-    uint32_t *fX = fwords ? (uint32_t *)calloc(fwords * 3, 4) : NULL;
-    if (fwords && !fX) { free(hX); free_batch(c); return GECM_ERR_NOMEM; }
-    gecm_mod_build b = {&c->mod, sigma, c->bad, batch, 0, hX, hX + words, hX + 2 * words, &c->ff_M, &c->ff_r_mod_m, c->ff_nl,
-                        fX, fX ? fX + fwords : NULL, fX ? fX + 2 * fwords : NULL};
-    const int built = run_slices(batch, gecm_mod_build_slice, &b);
-    if (built < 0) { free(hX); free(fX); free_batch(c); return built; }
-    rc = gecm_dev_upload(c->dev, hX, hX + words, hX + 2 * words);
-    if (!rc && fX) {
-        rc = gecm_dev_upload(c->dev_f, fX, fX + fwords, fX + 2 * fwords);
-        c->ff_loaded = !rc;
+    int built;
+    if (c->build_where == GECM_BUILD_DEVICE) built = build_on_device(c, sigma, batch, NULL);
+    else {
+        const size_t words = (size_t)c->mod.nl * batch;
+        uint32_t *hX = (uint32_t *)calloc(words * 3, 4);
+        if (!hX) { free_batch(c); return GECM_ERR_NOMEM; }
+        gecm_mod_build b = {&c->mod, sigma, c->bad, batch, 0, hX, hX + words, hX + 2 * words};
+        built = run_slices(batch, gecm_mod_build_slice, &b);
+        if (built >= 0 && gecm_dev_upload(c->dev, hX, hX + words, hX + 2 * words)) {
+            set_err("%s", gecm_dev_error());
+            built = GECM_ERR_DEVICE;
+        }
+        free(hX);
     }
-    free(hX);
-    free(fX);
-    if (rc) { set_err("%s", gecm_dev_error()); free_batch(c); return GECM_ERR_DEVICE; }
-    if (px && (rc = upload_plain(c, px, pz)) != 0) {
-        if (rc == GECM_ERR_DEVICE) set_err("%s", gecm_dev_error());
+    if (built < 0) { free_batch(c); return built; }
+    if ((px && gecm_dev_upload_plain(c->dev, px, pz, gecm_mod_r2(&c->mod))) || twin_fill(c)) {
+        set_err("%s", gecm_dev_error());
         free_batch(c);
-        return rc;
+        return GECM_ERR_DEVICE;
     }
     return built;
 }
@@ -721,70 +742,8 @@ int gecm_upload_points(gecm_ctx *c, const void *X, const void *Z, const void *s,
             mpl_to_limbs32(h + (size_t)k * words + i, batch, nl, LIMB_BITS, &v);
         }
     rc = gecm_dev_upload(c->dev, h, h + words, h + 2 * words);
-    if (!rc && c->dev_f) {
-        /* x*Rint mod N -> x -> x*Rf mod Mw */
-        const size_t fwords = (size_t)c->ff_nl * batch;
-        uint32_t *f = (uint32_t *)calloc(fwords * 3, 4);
-        mpl_t rinv;
-        if (f && mpl_invmod(&rinv, &c->mod.rint_mod_n, &c->mod.N)) {
-            for (int k = 0; k < 3; k++)
-                for (size_t i = 0; i < batch; i++) {
-                    mpl_t v;
-                    mpl_from_limbs32(&v, h + (size_t)k * words + i, batch, nl, LIMB_BITS);
-                    mpl_mulmod(&v, &v, &rinv, &c->mod.N);
-                    mpl_mulmod(&v, &v, &c->ff_r_mod_m, &c->ff_M);
-                    mpl_to_limbs32(f + (size_t)k * fwords + i, batch, c->ff_nl, LIMB_BITS, &v);
-                }
-            c->ff_loaded = !gecm_dev_upload(c->dev_f, f, f + fwords, f + 2 * fwords);
-        }
-        free(f);
-    }
     free(h);
-    if (rc) { set_err("%s", gecm_dev_error()); free_batch(c); return GECM_ERR_DEVICE; }
-    return GECM_OK;
-}
-
-/* ---- the F-form detour of stage 1 ------------------------------------------------------------
- * ff_settle: wait for the stage-1 kernel that ran modulo Mw = 2^k - 1, fetch its X, Z (canonical,
- * de-Montgomeryised), reduce them modulo N, put them back into Montgomery form modulo N and store them
- * in the main context as if stage 1 had run there.  Everything after stage 1 (save lines, factor scan,
- * stage 2) then works on residues modulo N as always. */
-typedef struct {
-    const gecm_ctx *c;
-    uint32_t *f;              /* fx, fz [ff_nl][batch], then hX, hZ [nl][batch] */
-} settle_job;
-
-static int settle_slice(void *arg, size_t lo, size_t hi)
-{
-    const settle_job *j = (const settle_job *)arg;
-    const gecm_ctx *c = j->c;
-    const size_t batch = c->batch, fwords = (size_t)c->ff_nl * batch, words = (size_t)c->mod.nl * batch;
-    for (size_t i = lo; i < hi; i++)
-        for (int q = 0; q < 2; q++) {                /* x, z */
-            mpl_t v;
-            mpl_from_limbs32(&v, j->f + q * fwords + i, batch, c->ff_nl, LIMB_BITS);
-            mpl_mod(&v, &v, &c->mod.N);
-            mpl_mulmod(&v, &v, &c->mod.rint_mod_n, &c->mod.N);
-            mpl_to_limbs32(j->f + 2 * fwords + q * words + i, batch, c->mod.nl, LIMB_BITS, &v);
-        }
-    return 0;
-}
-
-static int ff_settle(gecm_ctx *c)
-{
-    if (!c->ff_pending) return GECM_OK;
-    c->ff_pending = 0;
-    if (gecm_dev_sync(c->dev_f)) { set_err("%s", gecm_dev_error()); return GECM_ERR_DEVICE; }
-    c->last_ms = gecm_dev_last_kernel_ms(c->dev_f);
-    const size_t batch = c->batch, fwords = (size_t)c->ff_nl * batch, words = (size_t)c->mod.nl * batch;
-    uint32_t *f = (uint32_t *)calloc(2 * fwords + 2 * words, 4);
-    if (!f) return GECM_ERR_NOMEM;
-    if (gecm_dev_download_plain(c->dev_f, f, f + fwords)) { free(f); set_err("%s", gecm_dev_error()); return GECM_ERR_DEVICE; }
-    settle_job j = {c, f};
-    run_slices(batch, settle_slice, &j);
-    int rc = gecm_dev_upload_xz(c->dev, f + 2 * fwords, f + 2 * fwords + words);
-    free(f);
-    if (rc) { set_err("%s", gecm_dev_error()); return GECM_ERR_DEVICE; }
+    if (rc || twin_fill(c)) { set_err("%s", gecm_dev_error()); free_batch(c); return GECM_ERR_DEVICE; }
     return GECM_OK;
 }
 
@@ -809,7 +768,7 @@ static int tape_for(gecm_ctx *c, const tape_key *k)
             gecm_tape_free(&c->tape);
             c->tape = c->pf_tape;
             memset(&c->pf_tape, 0, sizeof c->pf_tape);
-            c->tape_k = *k; c->tape_on_dev = 0;
+            c->tape_k = *k;
             return GECM_OK;
         }
         gecm_tape_free(&c->pf_tape);
@@ -817,7 +776,7 @@ static int tape_for(gecm_ctx *c, const tape_key *k)
     gecm_tape_free(&c->tape);
     rc = tape_build(&c->tape, k, host_threads());
     if (rc) { set_err("gecm_stage1: tape build failed (%d)", rc); return rc == -1 ? GECM_ERR_NOMEM : GECM_ERR_STATE; }
-    c->tape_k = *k; c->tape_on_dev = 0;
+    c->tape_k = *k;
     return GECM_OK;
 }
 
@@ -853,10 +812,10 @@ static int stage1_launch(gecm_ctx *c, const tape_key *key, uint64_t B1, int firs
     int rc = tape_for(c, key);
     if (rc) return rc;
     const int idle = key->kind == 1 && c->tape.len == 0;
-    if (!c->tape_on_dev && !idle) {
+    if (!idle && !key_eq(&c->dev_tape_k, key)) {
         /* stream-ordered after the kernel of the range before; returns when the copy is done */
         if (gecm_dev_set_tape(c->dev, c->tape.ops, c->tape.len)) { set_err("%s", gecm_dev_error()); return GECM_ERR_DEVICE; }
-        c->tape_on_dev = 1;
+        c->dev_tape_k = *key;
     }
     if (first) c->s1_ptadds = c->s1_ptdups = 0;
     c->s1_ptadds += c->tape.ptadds;
@@ -874,18 +833,18 @@ static int stage1_launch(gecm_ctx *c, const tape_key *key, uint64_t B1, int firs
      * multiply in its two-lane form: 1.5x against 1.4x at 15 limbs, 2.2-2.4x at 30-37 limbs. */
     const int want = c->lanes_per_curve ? c->lanes_per_curve : gecm_dev_auto_lanes(c->dev);
     const int small_batch = want == 8 || want == 32;
-    if (c->dev_f && c->ff_on && c->ff_loaded && !small_batch) {
+    if (c->twin.dev && c->twin.on && c->twin.loaded && !small_batch) {
         /* N | 2^k - 1: run the chain modulo 2^k - 1 with the F-form multiply; ff_settle brings X, Z back */
-        if (!key_eq(&c->ff_tape_k, key)) {
-            if (gecm_dev_set_tape(c->dev_f, c->tape.ops, c->tape.len)) { set_err("%s", gecm_dev_error()); return GECM_ERR_DEVICE; }
-            c->ff_tape_k = *key;
+        if (!key_eq(&c->twin.tape_k, key)) {
+            if (gecm_dev_set_tape(c->twin.dev, c->tape.ops, c->tape.len)) { set_err("%s", gecm_dev_error()); return GECM_ERR_DEVICE; }
+            c->twin.tape_k = *key;
         }
-        if (gecm_dev_stage1(c->dev_f, c->lanes_per_curve)) { set_err("%s", gecm_dev_error()); return GECM_ERR_DEVICE; }
-        c->ff_pending = 1;
-        c->last_on_f = 1;
+        if (gecm_dev_stage1(c->twin.dev, c->lanes_per_curve)) { set_err("%s", gecm_dev_error()); return GECM_ERR_DEVICE; }
+        c->twin.pending = 1;
+        c->twin.ran_last = 1;
     } else {
-        c->last_on_f = 0;
-        c->ff_loaded = 0;       /* the F-form copy of the points no longer matches */
+        c->twin.ran_last = 0;
+        c->twin.loaded = 0;       /* the F-form copy of the points no longer matches */
         if (gecm_dev_stage1(c->dev, c->lanes_per_curve)) { set_err("%s", gecm_dev_error()); return GECM_ERR_DEVICE; }
     }
     if (next && !c->pf_active) {
@@ -899,7 +858,8 @@ static int stage1_launch(gecm_ctx *c, const tape_key *key, uint64_t B1, int firs
 
 int gecm_stage1_range(gecm_ctx *c, uint64_t B1, uint32_t range)
 {
-    if (c && c->ff_pending) { int rcs = ff_settle(c); if (rcs) return rcs; }
+    const int settled = ff_settle(c);
+    if (settled) return settled;
     if (!c || c->batch == 0) { set_err("gecm_stage1: no curves uploaded"); return GECM_ERR_STATE; }
     if (B1 < 2 || B1 > GECM_B1_MAX) { set_err("gecm_stage1: B1 must be in [2, %llu]", (unsigned long long)GECM_B1_MAX); return GECM_ERR_ARG; }
     if (lane_packing_refuses(c)) return GECM_ERR_STATE;
@@ -939,7 +899,8 @@ int gecm_stage1_describe_extend(uint64_t from, uint64_t to, uint32_t seg, gecm_e
 
 int gecm_stage1_extend_segment(gecm_ctx *c, uint64_t from, uint64_t to, uint32_t seg)
 {
-    if (c && c->ff_pending) { int rcs = ff_settle(c); if (rcs) return rcs; }
+    const int settled = ff_settle(c);
+    if (settled) return settled;
     int rc = extend_args("gecm_stage1_extend", from, to);
     if (rc) return rc;
     if (!c || c->batch == 0) { set_err("gecm_stage1_extend: no curves uploaded"); return GECM_ERR_STATE; }
@@ -978,17 +939,17 @@ int gecm_set_special_form(gecm_ctx *c, int on)
 {
     if (!c) return GECM_ERR_ARG;
     if (c && c->multi) return multi_refuse("gecm_set_special_form");
-    c->ff_on = on != 0;
+    c->twin.on = on != 0;
     return GECM_OK;
 }
 
 int gecm_get_special_form(const gecm_ctx *c, int *k, int *limbs)
 {
     if (!c) return GECM_ERR_ARG;
-    if (k) *k = c->dev_f ? c->ff_k * c->ff_sign : 0;
-    if (limbs) *limbs = c->dev_f ? c->ff_nl : 0;
-    if (!c->dev_f || !c->ff_on) return 0;
-    return c->last_on_f ? 2 : 1;
+    if (k) *k = c->twin.dev ? c->twin.k * c->twin.sign : 0;
+    if (limbs) *limbs = c->twin.dev ? c->twin.nl : 0;
+    if (!c->twin.dev || !c->twin.on) return 0;
+    return c->twin.ran_last ? 2 : 1;
 }
 
 int gecm_set_lanes_per_curve(gecm_ctx *c, int lanes)
@@ -1008,26 +969,26 @@ int gecm_set_lanes_per_curve(gecm_ctx *c, int lanes)
 int gecm_get_lanes_per_curve(const gecm_ctx *c)
 {
     if (!c) return GECM_ERR_ARG;
-    return gecm_dev_last_lanes(c->last_on_f ? c->dev_f : c->dev);
+    return gecm_dev_last_lanes(last_dev(c));
 }
 
 int gecm_stage1_progress(const gecm_ctx *c, uint32_t *done, uint32_t *total)
 {
     if (!c) return GECM_ERR_ARG;
-    return gecm_dev_stage1_progress(c->last_on_f ? c->dev_f : c->dev, done, total) ? GECM_ERR_DEVICE : GECM_OK;
+    return gecm_dev_stage1_progress(last_dev(c), done, total) ? GECM_ERR_DEVICE : GECM_OK;
 }
 
 int gecm_last_kernel_name(const gecm_ctx *c, char *buf, size_t len)
 {
     if (!c || !buf || !len) return GECM_ERR_ARG;
-    snprintf(buf, len, "%s", gecm_dev_last_kernel(c->last_on_f ? c->dev_f : c->dev));
+    snprintf(buf, len, "%s", gecm_dev_last_kernel(last_dev(c)));
     return GECM_OK;
 }
 
 int gecm_sync(gecm_ctx *c)
 {
     if (!c) return GECM_ERR_ARG;
-    if (c->ff_pending) return ff_settle(c);
+    if (c->twin.pending) return ff_settle(c);
     if (gecm_dev_sync(c->dev)) { set_err("%s", gecm_dev_error()); return GECM_ERR_DEVICE; }
     c->last_ms = gecm_dev_last_kernel_ms(c->dev);
     return GECM_OK;
@@ -1048,7 +1009,8 @@ int gecm_get_stage1_stats(const gecm_ctx *c, gecm_stage1_stats *st)
 int gecm_download_points(gecm_ctx *c, void *X, void *Z)
 {
     if (c && c->multi) return multi_refuse("gecm_download_points");
-    if (c && c->ff_pending) { int rcs = ff_settle(c); if (rcs) return rcs; }
+    const int settled = ff_settle(c);
+    if (settled) return settled;
     if (!c || !X || !Z || c->batch == 0) return GECM_ERR_ARG;
     size_t batch = c->batch, words = (size_t)c->mod.nl * batch;
     uint32_t *h = (uint32_t *)malloc(words * 2 * 4);
@@ -1086,7 +1048,8 @@ int gecm_download_s(gecm_ctx *c, void *s)
 
 static int fetch_plain(gecm_ctx *c)
 {
-    if (c->ff_pending) { int rcs = ff_settle(c); if (rcs) return rcs; }
+    const int settled = ff_settle(c);
+    if (settled) return settled;
     if (c->have_plain) return GECM_OK;
     if (c->batch == 0) { set_err("no batch"); return GECM_ERR_STATE; }
     if (gecm_dev_download_plain(c->dev, c->hx, c->hz)) { set_err("%s", gecm_dev_error()); return GECM_ERR_DEVICE; }
@@ -1169,7 +1132,8 @@ int gecm_stage1_factor(gecm_ctx *c, size_t k, char *dec, size_t declen, int *is_
 /* ---- normalisation and standard lines ---------------------------------------- */
 int gecm_normalize_points(gecm_ctx *c)
 {
-    if (c && c->ff_pending) { int rcs = ff_settle(c); if (rcs) return rcs; }
+    const int settled = ff_settle(c);
+    if (settled) return settled;
     if (!c || c->batch == 0) { set_err("gecm_normalize_points: no curves uploaded"); return GECM_ERR_STATE; }
     if (!c->multi && c->mod.have_report) {
         set_err("gecm_normalize_points: not with a report modulus (gecm_set_report_modulus): x modulo the context's "
@@ -1192,7 +1156,7 @@ int gecm_normalize_points(gecm_ctx *c)
     c->have_plain = 0;
     c->s2_ready = 0;
     c->scan_valid[0] = 0;
-    c->ff_loaded = 0;            /* the twin's copy of the points no longer matches: the next launch runs modulo N */
+    c->twin.loaded = 0;            /* the twin's copy of the points no longer matches: the next launch runs modulo N */
     return any;
 }
 
@@ -1236,7 +1200,8 @@ static uint64_t ladder_adds(uint64_t c)
 
 int gecm_stage2_init(gecm_ctx *c, uint32_t D, uint32_t U)
 {
-    if (c && c->ff_pending) { int rcs = ff_settle(c); if (rcs) return rcs; }
+    const int settled = ff_settle(c);
+    if (settled) return settled;
     if (!c || c->batch == 0 || c->B1 == 0) { set_err("gecm_stage2_init: run stage 1 first"); return GECM_ERR_STATE; }
     if (!D) D = gecm_s2_default_D(c->B1);
     if (!U) U = GECM_S2_DEFAULT_U;
@@ -1535,7 +1500,8 @@ int gecm_stage2_factor(gecm_ctx *c, size_t k, char *dec, size_t declen, int *is_
  * is in the caller's numbering. */
 int gecm_scan_factors(gecm_ctx *c, int stage, size_t *first)
 {
-    if (c && c->ff_pending) { int rcs = ff_settle(c); if (rcs) return rcs; }
+    const int settled = ff_settle(c);
+    if (settled) return settled;
     if (!c || c->batch == 0 || (stage != 1 && stage != 2)) { set_err("gecm_scan_factors: bad argument"); return GECM_ERR_ARG; }
     if (stage == 2 && !c->s2_ready) { set_err("gecm_scan_factors: no stage-2 state"); return GECM_ERR_STATE; }
     uint32_t **f = &c->flags[stage - 1], **hg = &c->hg[stage - 1];
@@ -1760,8 +1726,7 @@ static int build_multi(gecm_ctx *c, const char *who, const uint64_t *sigma, cons
     c->build_used = c->build_where;
     const int on_device = c->build_where == GECM_BUILD_DEVICE;
     for (size_t g = 0; g < ng && !rc && !on_device; g++) {
-        gecm_mod_build b = {&c->grp[g], c->sigma + goff[g], c->bad, total, goff[g], hX, hX + words, hX + 2 * words,
-                            NULL, NULL, 0, NULL, NULL, NULL};
+        gecm_mod_build b = {&c->grp[g], c->sigma + goff[g], c->bad, total, goff[g], hX, hX + words, hX + 2 * words};
         const int built = run_slices(cnt[g], gecm_mod_build_slice, &b);
         if (built < 0) rc = built;
         else anybad |= built;
@@ -1796,7 +1761,7 @@ static int build_multi(gecm_ctx *c, const char *who, const uint64_t *sigma, cons
                 dz[l * total + p] = uz[l * batch + i];
             }
         }
-        rc = upload_plain(c, dx, dz);
+        if (gecm_dev_upload_plain(c->dev, dx, dz, NULL)) rc = GECM_ERR_DEVICE;   /* NULL: every curve's own R^2 */
     }
     free(hX);
     free(blocks);

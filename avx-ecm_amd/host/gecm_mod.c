@@ -211,13 +211,6 @@ int gecm_mod_build_slice(void *build, size_t lo, size_t hi)
         mpl_to_limbs32(j->hX + k, batch, nl, LIMB_BITS, &Xm);
         mpl_to_limbs32(j->hZ + k, batch, nl, LIMB_BITS, &c->rint_mod_n);
         mpl_to_limbs32(j->hS + k, batch, nl, LIMB_BITS, &Sm);
-        if (j->fX) {           /* plain residues mod N, lifted to Montgomery form modulo Mw = 2^k - 1 */
-            mpl_mulmod(&Xm, &X, j->ff_r_mod_m, j->ff_M);
-            mpl_mulmod(&Sm, &A, j->ff_r_mod_m, j->ff_M);
-            mpl_to_limbs32(j->fX + k, batch, j->ff_nl, LIMB_BITS, &Xm);
-            mpl_to_limbs32(j->fZ + k, batch, j->ff_nl, LIMB_BITS, j->ff_r_mod_m);
-            mpl_to_limbs32(j->fS + k, batch, j->ff_nl, LIMB_BITS, &Sm);
-        }
     }
     free(x3); free(dens); free(pref);
     return anybad;

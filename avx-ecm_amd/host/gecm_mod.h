@@ -48,16 +48,13 @@ static inline int to_report(const gecm_mod *m, mpl_t *g)
 }
 
 /* The Suyama construction for curves [lo, hi) of `sigma`, written to position off + k of arrays of stride `batch`
- * (gecm_mod_build_slice).  fX != NULL: the same three values once more in Montgomery form modulo ff_M. */
+ * (gecm_mod_build_slice). */
 typedef struct {
     const gecm_mod *m;
     const uint64_t *sigma;
     uint8_t *bad;             /* [batch], set where a denominator does not invert */
     size_t batch, off;
     uint32_t *hX, *hZ, *hS;   /* [nl][batch] */
-    const mpl_t *ff_M, *ff_r_mod_m;
-    int ff_nl;
-    uint32_t *fX, *fZ, *fS;   /* [ff_nl][batch] */
 } gecm_mod_build;
 /* GECM_ERR_NOMEM, 1 if some curve was marked bad, else 0 */
 int gecm_mod_build_slice(void *build, size_t lo, size_t hi);

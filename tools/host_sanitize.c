@@ -176,7 +176,7 @@ int main(void)
             if (nl == 15 || last) {
                 uint32_t *h = (uint32_t *)calloc((size_t)900 * nl, sizeof(uint32_t));
                 uint8_t bad[300] = {0};
-                gecm_mod_build b = {&m, sig, bad, 300, 0, h, h + 300 * nl, h + 600 * nl, NULL, NULL, 0, NULL, NULL, NULL};
+                gecm_mod_build b = {&m, sig, bad, 300, 0, h, h + 300 * nl, h + 600 * nl};
                 int rc = h ? gecm_mod_build_slice(&b, 0, 300) : -1, nbad = 0;
                 for (int i = 0; i < 300; i++) nbad += bad[i];
                 printf("build_slice at %d limbs: rc=%d bad=%d\n", nl, rc, nbad);
