@@ -101,8 +101,8 @@ int gecm_dev_l0_inv(gecm_dev *d, const uint32_t *a, uint32_t *inv, uint32_t *g, 
 
 /* ---- multi-modulus batches ----
  * gecm_dev_set_multi: from now on every launch of this context takes its modulus per 64-curve block from the group
- * tables, with 1 or 2 lanes per curve and one stage-2 sub-sequence per curve; the L0 operators are refused.  Call it
- * right after gecm_dev_open.
+ * tables, with 1 or 2 lanes per curve and one stage-2 sub-sequence per curve (until gecm_dev_set_s2_subseq says
+ * otherwise); the L0 operators are refused.  Call it right after gecm_dev_open.
  * gecm_dev_set_groups: after gecm_dev_resize, the constants of ngroups moduli (n, kp, one, r3, r2: nl limbs each,
  * modulus g at [g*nl]; rho, inv_iters: one word each) and the modulus of every 64-curve block of the batch
  * (stride / 64 entries, each < ngroups).  Copied before it returns. */
@@ -126,6 +126,11 @@ int gecm_dev_set_s2const(gecm_dev *d, const uint32_t *r3, uint32_t inv_iters);
  * the range of tgt[] holding the table indices of the kept members j = r, r+K, ... (r = 0: K, 2K, ...) of
  * sub-sequence r, in order; tgt_off has K + 1 entries. */
 uint32_t gecm_dev_s2_subseq(gecm_dev *d);
+/* k = 0: K by batch size on a single-modulus context, 1 on a multi-modulus one (the default); -1: by batch size on
+ * both; 1, 2, 4, .. 32: that K.  Takes effect at the next gecm_dev_s2_init; -2 for any other value.
+ * gecm_dev_s2_k_chunks: giant-step chunks launched with sub-sequences since the last gecm_dev_s2_init. */
+int gecm_dev_set_s2_subseq(gecm_dev *d, int k);
+uint32_t gecm_dev_s2_k_chunks(gecm_dev *d);
 int gecm_dev_s2_init(gecm_dev *d, const uint32_t *keep, size_t keep_words, uint32_t umax, uint32_t D,
                      uint32_t npb, uint32_t G, uint32_t ring_size, const uint32_t *tgt, const uint32_t *tgt_off,
                      uint32_t K);

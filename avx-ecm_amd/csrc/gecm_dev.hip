@@ -84,6 +84,8 @@ struct gecm_dev {
     uint32_t steps_n = 0;
     uint32_t s2_slices = 1;   // stage-2 accumulators per curve (pair-walk slices), see gecm_dev_s2_init
     uint32_t s2_K = 1;        // sub-sequences per curve for the table build and the giant steps (gecm_dev_s2_subseq)
+    int s2_subseq_set = 0;    // gecm_dev_set_s2_subseq: 0 = default, -1 = by batch size on every kind of context, or K itself
+    uint32_t s2_k_chunks = 0; // giant-step chunks launched with sub-sequences since the last gecm_dev_s2_init
     uint32_t *dKBlk = nullptr, *dKPa = nullptr, *dPdK = nullptr, *dTgt = nullptr;
     size_t tgt_cap = 0;
     hipStream_t stream = nullptr;
@@ -852,7 +854,8 @@ extern "C" int gecm_dev_set_s2const(gecm_dev *d, const uint32_t *r3, uint32_t in
 /* Sub-sequences per curve for the stage-2 table build and giant steps: those are one dependent chain per curve, so a
  * batch of a few thousand curves (a few dozen wavefronts) is split into K interleaved chains per curve until there
  * are 2 wavefronts per SIMD (csrc/gecm_stage2.hpp, s2_init_k / giant_chunk_k).  1 for batches that fill the chip.
- * GECM_S2_SUBSEQ=1..32 (a power of two) overrides, for measurements. */
+ * GECM_S2_SUBSEQ=1..32 (a power of two) overrides, for measurements.  A multi-modulus context keeps K = 1, whatever
+ * the batch and the environment say, until gecm_dev_set_s2_subseq opts it in; a K set there holds on every context. */
 static uint32_t s2_slices_for(const gecm_dev *d, size_t stride);
 static uint32_t s2_subseq_for(const gecm_dev *d, size_t stride);
 
@@ -877,12 +880,22 @@ extern "C" uint64_t gecm_dev_batch_bytes(gecm_dev *d, size_t curves, uint32_t np
 
 extern "C" uint32_t gecm_dev_s2_subseq(gecm_dev *d) { return s2_subseq_for(d, d->stride); }
 
+extern "C" int gecm_dev_set_s2_subseq(gecm_dev *d, int k)
+{
+    if (k != 0 && k != -1 && (k < 1 || k > 32 || (k & (k - 1)))) return -2;
+    d->s2_subseq_set = k;
+    return 0;
+}
+
+extern "C" uint32_t gecm_dev_s2_k_chunks(gecm_dev *d) { return d->s2_k_chunks; }
+
 static uint32_t s2_subseq_for(const gecm_dev *d, size_t stride)
 {
     // two wavefronts per SIMD is the target (4096 curves, B2 = 1e8: K = 1 1.14 s, 4 0.75 s, 16 and 32 0.64 s)
     const size_t waves = stride / 64, want = (size_t)d->cus * 4 * 2;
     uint32_t k = 1;
-    if (d->multi) return 1;    // multi-modulus contexts have no sub-sequence kernels
+    if (d->s2_subseq_set > 0) return (uint32_t)d->s2_subseq_set;
+    if (d->multi && d->s2_subseq_set == 0) return 1;    // multi-modulus contexts: sub-sequences only when asked for
     while (k < 32 && waves * (k * 2) <= want) k *= 2;
     if (const char *e = getenv("GECM_S2_SUBSEQ")) {
         const long v = strtol(e, nullptr, 10);
@@ -915,7 +928,7 @@ extern "C" int gecm_dev_s2_init(gecm_dev *d, const uint32_t *keep, size_t keep_w
         return -2;
     }
     const size_t coord = (size_t)d->nl * d->stride * sizeof(uint32_t);
-    if (K < 1 || K > 32 || (K & (K - 1)) || (K > 1 && (!tgt || !tgt_off)) || (d->multi && K != 1)) {
+    if (K < 1 || K > 32 || (K & (K - 1)) || (K > 1 && (!tgt || !tgt_off))) {
         g_err = "gecm_dev_s2_init: bad number of sub-sequences";
         return -2;
     }
@@ -983,6 +996,7 @@ extern "C" int gecm_dev_s2_init(gecm_dev *d, const uint32_t *keep, size_t keep_w
         a.PdKX = d->dPdK; a.PdKZ = d->dPdK + coord / 4;
     }
     L.slices = d->s2_slices;
+    d->s2_k_chunks = 0;
     gecm_modconst mc = modconst(d);
     HIPCHK(hipEventRecord(d->ev0, d->stream));
     d->k2->s2_init(d->stream, &mc, &L);
@@ -1023,6 +1037,7 @@ extern "C" int gecm_dev_s2_pair(gecm_dev *d, const uint32_t *steps, uint32_t nst
     a.acc = d->dAcc; a.fail = d->dFail; a.steps = d->dSteps; L.host_steps = steps;
     a.nsteps = nsteps; a.D = D; a.G = G; a.ring_size = ring_size; a.A0 = A0; a.stride = d->stride;
     L.slices = d->s2_slices;
+    L.k_chunks = &d->s2_k_chunks;
     a.K = d->s2_K; a.Gs = (uint32_t)(G / d->s2_K + 1);
     a.kgx = a.kgz = a.kgp = nullptr; a.PdKX = a.PdKZ = nullptr;
     if (d->s2_K > 1) {

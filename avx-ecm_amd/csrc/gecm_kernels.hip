@@ -98,6 +98,14 @@ struct LaneConst : S2ConstV<NL> {
     FeG<NL> r2;
 };
 
+// The same under a name of its own, for the sub-sequence kernels of stage 2 (k_s2_init_k_lane, k_s2_gen_k_lane).  With
+// LaneConst itself they shared block_normalise<NL, LaneConst<NL>> and the lambda in it with k_s2_init_lane, which until
+// then had that instance to itself, and k_s2_init_lane came out with other registers and two to nine instructions fewer
+// (9770 -> 9768 at 8 limbs, 26820 -> 26811 at 15).  A type of their own gives them instances of their own.
+template <int NL>
+struct LaneConstK : LaneConst<NL> {
+};
+
 template <int NL>
 __device__ __forceinline__ void lane_consts(LaneConst<NL> &k, const LaneGroups<NL> &g, uint32_t idx, uint32_t *kp_col)
 {
@@ -115,12 +123,14 @@ __device__ __forceinline__ void lane_consts(LaneConst<NL> &k, const LaneGroups<N
     k.inv_iters = gp[offsetof(GroupConst<NL>, k.inv_iters) / 4];
     k.r2.p = gp + offsetof(GroupConst<NL>, r2) / 4;
 }
-// per lane: `k` = the constants of the lane's curve (64 curves per block in every lane kernel)
-#define GECM_LANE_CONSTS                                                        \
+// per lane: `k` = the constants of the curve at position `pos` (64 curves per block in every lane kernel; the
+// sub-sequence kernels of stage 2 run several blocks per curve block and say which position is theirs)
+#define GECM_LANE_CONSTS_AT(T, pos)                                             \
     __shared__ uint32_t lds_kp[NL * 64];                                        \
-    LaneConst<NL> k;                                                            \
-    lane_consts(k, g, blockIdx.x * 64u + threadIdx.x, lds_kp + threadIdx.x);    \
+    T k;                                                                        \
+    lane_consts(k, g, pos, lds_kp + threadIdx.x);                               \
     [[maybe_unused]] const FeG<NL> &r2 = k.r2;
+#define GECM_LANE_CONSTS GECM_LANE_CONSTS_AT(LaneConst<NL>, blockIdx.x * 64u + threadIdx.x)
 
 #if GECM_HAS_PART(1)
 // ---------------------------------------------------------------- stage 1
@@ -680,8 +690,10 @@ k_normalize_lane(uint32_t *__restrict__ X, uint32_t *__restrict__ Z, uint32_t *_
 #endif
 #if GECM_HAS_PART(2)
 // ---------------------------------------------------------------- stage 2
-// Multi-modulus contexts run stage 2 with one sub-sequence per curve (K = 1): for them the _multi or _lane kernels of
-// init, gen, pairs and merge are the whole path.
+// Multi-modulus contexts run stage 2 with one sub-sequence per curve (K = 1) unless they ask for more
+// (gecm_set_stage2_subseq): at K = 1 the _multi or _lane kernels of init, gen, pairs and merge are the
+// whole path; at K > 1 init and gen go through the _k_multi / _k_lane kernels and the plain-chain chunks through
+// k_s2_gen_after_k_*.
 template <int NL>
 __global__ void __launch_bounds__(64, 2) k_s2_init(S2InitArgs a, S2Const<NL> k)
 {
@@ -705,18 +717,58 @@ __global__ void __launch_bounds__(64, 2) k_s2_init_lane(S2InitArgs a, LaneGroups
 }
 #endif
 
-// K sub-sequences per curve (small batches): block b works on curve block b / K, sub-sequence b % K
+// K sub-sequences per curve (small batches): block b works on curve block b / K, sub-sequence b % K; the constants of
+// a launch that keeps them in device memory are those of curve block b / K
+#define GECM_S2_INIT_K_BODY                                                     \
+    s2_init_k<NL>(a, k, (blockIdx.x / a.K) * 64u + threadIdx.x, blockIdx.x % a.K);
+#define GECM_S2_GEN_K_BODY                                                      \
+    giant_chunk_k<NL>(a, first_abs, n, k, (blockIdx.x / a.K) * 64u + threadIdx.x, blockIdx.x % a.K);
+
 template <int NL>
 __global__ void __launch_bounds__(64, 2) k_s2_init_k(S2InitArgs a, S2Const<NL> k)
 {
-    s2_init_k<NL>(a, k, (blockIdx.x / a.K) * 64u + threadIdx.x, blockIdx.x % a.K);
+    GECM_ARG_CONSTS
+    GECM_S2_INIT_K_BODY
+}
+
+template <int NL>
+__global__ void __launch_bounds__(64, 2) k_s2_init_k_multi(S2InitArgs a, ModGroups<NL> g)
+{
+    GECM_WAVE_CONSTS(S2Const<NL>, blockIdx.x / a.K)
+    GECM_S2_INIT_K_BODY
 }
 
 template <int NL>
 __global__ void __launch_bounds__(64, 2) k_s2_gen_k(S2PairArgs a, uint32_t first_abs, uint32_t n, S2Const<NL> k)
 {
-    giant_chunk_k<NL>(a, first_abs, n, k, (blockIdx.x / a.K) * 64u + threadIdx.x, blockIdx.x % a.K);
+    GECM_ARG_CONSTS
+    GECM_S2_GEN_K_BODY
 }
+
+template <int NL>
+__global__ void __launch_bounds__(64, 2) k_s2_gen_k_multi(S2PairArgs a, uint32_t first_abs, uint32_t n, ModGroups<NL> g)
+{
+    GECM_WAVE_CONSTS(S2Const<NL>, blockIdx.x / a.K)
+    GECM_S2_GEN_K_BODY
+}
+
+#if GECM_HAS_LANE
+template <int NL>
+__global__ void __launch_bounds__(64, 2) k_s2_init_k_lane(S2InitArgs a, LaneGroups<NL> g)
+{
+    GECM_LANE_CONSTS_AT(LaneConstK<NL>, (blockIdx.x / a.K) * 64u + threadIdx.x)
+    GECM_S2_INIT_K_BODY
+}
+
+template <int NL>
+__global__ void __launch_bounds__(64, 2) k_s2_gen_k_lane(S2PairArgs a, uint32_t first_abs, uint32_t n, LaneGroups<NL> g)
+{
+    GECM_LANE_CONSTS_AT(LaneConstK<NL>, (blockIdx.x / a.K) * 64u + threadIdx.x)
+    GECM_S2_GEN_K_BODY
+}
+#endif
+#undef GECM_S2_INIT_K_BODY
+#undef GECM_S2_GEN_K_BODY
 
 // giant steps [first_abs, first_abs+n): generate + normalise into the ring
 template <int NL>
@@ -739,6 +791,27 @@ __global__ void __launch_bounds__(64, 2) k_s2_gen_lane(S2PairArgs a, uint32_t fi
 {
     GECM_LANE_CONSTS
     giant_chunk<NL>(a, first_abs, n, first_abs == 0, k, blockIdx.x * 64u + threadIdx.x);
+}
+#endif
+
+// The plain-chain chunks of a multi-modulus launch with sub-sequences (the last chunk of a range, and every chunk when
+// amin = 0): they take the two steps before first_abs from the sub-sequences' scratch when kprev > 1, as k_s2_gen does.
+// Kernels of their own: k_s2_gen_multi and k_s2_gen_lane keep their signatures and their code.
+template <int NL>
+__global__ void __launch_bounds__(64, 2) k_s2_gen_after_k_multi(S2PairArgs a, uint32_t first_abs, uint32_t n, uint32_t kprev,
+                                                                ModGroups<NL> g)
+{
+    GECM_WAVE_CONSTS(S2Const<NL>, blockIdx.x)
+    giant_chunk<NL>(a, first_abs, n, first_abs == 0, k, blockIdx.x * 64u + threadIdx.x, kprev);
+}
+
+#if GECM_HAS_LANE
+template <int NL>
+__global__ void __launch_bounds__(64, 2) k_s2_gen_after_k_lane(S2PairArgs a, uint32_t first_abs, uint32_t n, uint32_t kprev,
+                                                               LaneGroups<NL> g)
+{
+    GECM_LANE_CONSTS
+    giant_chunk<NL>(a, first_abs, n, first_abs == 0, k, blockIdx.x * 64u + threadIdx.x, kprev);
 }
 #endif
 
@@ -1003,13 +1076,13 @@ extern "C" const gecm_kernels_p1 *CAT(CAT(gecm_kernels_, GECM_NL), _p1)(void)
 }
 #endif
 #if GECM_HAS_PART(2)
-// (a multi-modulus mc has K = 1: gecm_dev_s2_init)
 static void launch_s2_init(void *stream, const gecm_modconst *mc, const gecm_s2_init_launch *h)
 {
     const S2InitArgs &a = h->a;
     const dim3 grid = blocks_of(a.stride);
-    if (mc->source == GECM_SRC_VALUE && a.K > 1)
-        launch_by_source<S2Const<GECM_NL>>(stream, mc, blocks_of(a.stride * a.K), k_s2_init_k<GECM_NL>, nullptr, nullptr, a);
+    if (a.K > 1)
+        launch_by_source<S2Const<GECM_NL>>(stream, mc, blocks_of(a.stride * a.K), k_s2_init_k<GECM_NL>,
+                                           k_s2_init_k_multi<GECM_NL>, GECM_LANE(k_s2_init_k_lane), a);
     else
         launch_by_source<S2Const<GECM_NL>>(stream, mc, grid, k_s2_init<GECM_NL>, k_s2_init_multi<GECM_NL>,
                                            GECM_LANE(k_s2_init_lane), a);
@@ -1027,19 +1100,25 @@ static void launch_s2_pair(void *stream, const gecm_modconst *mc, const gecm_s2_
     const dim3 grid = blocks_of(a.stride);
     const dim3 pgrid((unsigned)(a.stride / 64), h->slices ? h->slices : 1);
     // a "generate" mark with bit 31 set in its count is a single-chain chunk (the reference's last batch of the range,
-    // gecm_stage2_pair); the others use K sub-sequences per curve when the batch is small (a.K > 1; a multi-modulus mc
-    // has K = 1)
+    // gecm_stage2_pair); the others use K sub-sequences per curve when the batch is small or the context asks (a.K > 1).
+    // A multi-modulus mc at K = 1 keeps the gen kernels it always had; at K > 1 its single-chain chunks need kprev.
     const dim3 kgrid = blocks_of(a.stride * (a.K ? a.K : 1));
     uint32_t generated = 0, i = 0, kprev = 1;
     while (i < a.nsteps) {
         if (h->host_steps[2 * i] == S2_STEP_GEN) {
             const uint32_t word = h->host_steps[2 * i + 1];
             const uint32_t n = word & 0x7fffffffu;
-            if (mc->source != GECM_SRC_VALUE)
+            if (mc->source != GECM_SRC_VALUE && a.K <= 1)
                 launch_by_source<>(stream, mc, grid, nullptr, k_s2_gen_multi<GECM_NL>, GECM_LANE(k_s2_gen_lane), a, generated, n);
             else if (a.K > 1 && !(word & 0x80000000u)) {
-                launch_by_source<S2Const<GECM_NL>>(stream, mc, kgrid, k_s2_gen_k<GECM_NL>, nullptr, nullptr, a, generated, n);
+                launch_by_source<S2Const<GECM_NL>>(stream, mc, kgrid, k_s2_gen_k<GECM_NL>, k_s2_gen_k_multi<GECM_NL>,
+                                                   GECM_LANE(k_s2_gen_k_lane), a, generated, n);
                 kprev = a.K;
+                if (h->k_chunks) ++*h->k_chunks;
+            } else if (mc->source != GECM_SRC_VALUE) {
+                launch_by_source<>(stream, mc, grid, nullptr, k_s2_gen_after_k_multi<GECM_NL>, GECM_LANE(k_s2_gen_after_k_lane), a,
+                                   generated, n, generated ? kprev : 1u);
+                kprev = 1;
             } else {
                 launch_by_source<S2Const<GECM_NL>>(stream, mc, grid, k_s2_gen<GECM_NL>, nullptr, nullptr, a, generated, n,
                                                    generated ? kprev : 1u);

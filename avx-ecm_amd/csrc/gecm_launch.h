@@ -83,6 +83,7 @@ struct gecm_s2_pair_launch {
     S2PairArgs a;
     const uint32_t *host_steps;   /* host copy of the tape: the launcher splits it at the "generate" marks */
     uint32_t slices;              /* accumulators per curve: each run of pairs is cut into this many slices */
+    uint32_t *k_chunks;           /* out (may be NULL): one more for every chunk launched with K sub-sequences per curve */
 };
 
 /* Part 1: stage 1, canonical form, de-Montgomeryisation, L0 operators, factor scan, curve construction. */
@@ -124,7 +125,7 @@ struct gecm_kernels_p1 {
     void (*normalize)(void *stream, const gecm_modconst *mc, uint32_t *X, uint32_t *Z, uint32_t *flags, size_t stride);
 };
 
-/* Part 2: stage 2 (a multi-modulus mc takes K = 1 only). */
+/* Part 2: stage 2 (any mc takes K = 1, 2, .. 32; a lane-packed one at limb counts with has_lane). */
 struct gecm_kernels_p2 {
     void (*s2_init)(void *stream, const gecm_modconst *mc, const gecm_s2_init_launch *h);
     void (*s2_pair)(void *stream, const gecm_modconst *mc, const gecm_s2_pair_launch *h);

@@ -489,11 +489,11 @@ __device__ __forceinline__ void s2_init(const S2InitArgs &a, const KC &k, uint32
 // r = 0 starts at K) and steps by [K]Q: P_(j+K) = P_j + [K]Q with difference P_(j-K) — the same points [j]Q as the
 // reference's chain j -> j+1 (ecm.c:2263-2313), as other projective representatives, and only X/Z of them is kept.
 // A batch of a few thousand curves is a few dozen wavefronts; with K = 32 chains per curve it fills the chip.
-// r is wave-uniform (blockIdx.x % K); idx is the curve.
-template <int NL>
-__device__ __forceinline__ void s2_init_k(const S2InitArgs &a, const S2Const<NL> &k, uint32_t idx, uint32_t r)
+// r is wave-uniform (blockIdx.x % K); idx is the curve.  KC = S2Const<NL>, or the constants of a lane (S2ConstV<NL>).
+template <int NL, class KC>
+__device__ __forceinline__ void s2_init_k(const S2InitArgs &a, const KC &k, uint32_t idx, uint32_t r)
 {
-    const ModK<NL> &m = k.m;
+    const auto &m = k.m;
     const size_t stride = a.stride;
     const uint32_t K = a.K;
     const uint32_t sidx = ((idx >> 6) * K + r) * 64u + (idx & 63u);      // virtual curve: scratch of (curve block, r)
@@ -656,11 +656,11 @@ __device__ __forceinline__ void giant_chunk(const S2PairArgs &a, uint32_t first_
 // its own inversion and writes them to the ring.  Same points, same X/Z.  State between chunks: the latest two members
 // in scratch entries 0, 1 of (curve block, r).  A failing inversion is recorded in plane 1 + r of `fail` (plane 0
 // belongs to the single-chain chunks, whose last one reproduces the reference's last batch).
-template <int NL>
-__device__ __forceinline__ void giant_chunk_k(const S2PairArgs &a, uint32_t first_abs, uint32_t n, const S2Const<NL> &k,
+template <int NL, class KC>
+__device__ __forceinline__ void giant_chunk_k(const S2PairArgs &a, uint32_t first_abs, uint32_t n, const KC &k,
                                               uint32_t idx, uint32_t r)
 {
-    const ModK<NL> &m = k.m;
+    const auto &m = k.m;
     const size_t stride = a.stride;
     const uint32_t K = a.K;
     const uint32_t s0 = first_abs + (r + K - first_abs % K) % K;            // first step of this sub-sequence in the chunk

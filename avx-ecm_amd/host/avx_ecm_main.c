@@ -277,6 +277,18 @@ static size_t pass_positions(size_t n, size_t each, int packing)
     return packing == GECM_PACK_LANE ? gecm_multi_positions(&all, 1, packing) : n * gecm_multi_positions(&each, 1, packing);
 }
 
+/* Sub-sequences per curve in stage 2 of the multi-modulus passes of -f, -r and -x (include/gecm.h
+ * gecm_set_stage2_subseq): GECM_MULTI_SUBSEQ=auto|default, default when unset.  The files are byte for
+ * byte the same either way.  Returns the setting, or 1 (no setting has that value) after printing why not. */
+static int cli_multi_subseq(void)
+{
+    const char *s = getenv("GECM_MULTI_SUBSEQ");
+    if (!s || !strcmp(s, "default")) return GECM_S2_SUBSEQ_DEFAULT;
+    if (!strcmp(s, "auto")) return GECM_S2_SUBSEQ_AUTO;
+    printf("GECM_MULTI_SUBSEQ must be auto or default\n");
+    return 1;
+}
+
 static int fits_lane_packing(int nbits) { return nbits <= gecm_multi_packing_max_bits(GECM_PACK_LANE); }
 
 /* ---- per-GPU jobs of a pass ----------------------------------------------------------------- */
@@ -1113,6 +1125,7 @@ static int multi_run(const char **ns, const char *const *logs, size_t n, run_t *
     int rc = gecm_create_multi(&mc, 0, ns, n, GECM_CLI_DIGITBITS);
     if (rc == 0) rc = set_curve_build(mc);
     if (rc == 0) rc = gecm_set_multi_packing(mc, packing);
+    if (rc == 0) rc = gecm_set_stage2_subseq(mc, cli_multi_subseq());
     if (rc == 0 && rl) {
         gecm_config cfg;
         gecm_get_config(mc, &cfg);
@@ -1141,10 +1154,13 @@ static int multi_run(const char **ns, const char *const *logs, size_t n, run_t *
         if (!rc) output_write(&v, &o, logs ? logs[i] : NULL, NULL);   /* log: "gen: ...", "commencing parallel ecm on ..." */
         output_release(&v, &o);
     }
-    if (!rc)
+    if (!rc) {
+        char s2[48] = "";
+        if (R->do_stage2) snprintf(s2, sizeof s2, " and stage 2 (K = %d)", gecm_get_stage2_subseq(mc, NULL));
         printf("multi-modulus pass: %zu inputs, %zu curves%s, %s-packed, %s%s, %1.4f seconds of kernels after stage 1\n", n,
                rl ? total : count[0], rl ? " in all" : " each", gecm_get_multi_packing(mc) == GECM_PACK_LANE ? "lane" : "wave",
-               !rl ? "stage 1" : R->extend ? "stage 1 extended" : "resumed after stage 1", R->do_stage2 ? " and stage 2" : "", gecm_last_kernel_ms(mc) / 1000.0);
+               !rl ? "stage 1" : R->extend ? "stage 1 extended" : "resumed after stage 1", s2, gecm_last_kernel_ms(mc) / 1000.0);
+    }
     gecm_destroy(mc);
     free(rx); free(rz);
     return rc ? 2 : 0;
@@ -1181,7 +1197,7 @@ static int run_file(int argc, char **argv)
                                "       (one input expression per line; blank lines and lines starting with # are skipped)\n";
     if (argc < 5) { printf("%s", usage); return 1; }
     const int packing = cli_packing();
-    if (packing < 0) return 1;
+    if (packing < 0 || cli_multi_subseq() == 1) return 1;
     FILE *f = fopen(argv[2], "r");
     if (!f) { printf("cannot read %s\n%s", argv[2], usage); return 1; }
     size_t ninputs = 0, cap_in = 0;
@@ -1330,7 +1346,7 @@ static int run_resume(int argc, char **argv, int extend)
     const char *usage = extend ? extend_usage : resume_usage;
     if (argc < 4) { printf("%s", usage); return 1; }
     const int packing = cli_packing();
-    if (packing < 0) return 1;
+    if (packing < 0 || cli_multi_subseq() == 1) return 1;
     FILE *f = fopen(argv[2], "r");
     if (!f) { printf("cannot read %s\n%s", argv[2], usage); return 1; }
     /* the run's arguments through the one parser: curves B1 threads [B2], one thread, the curve count per group */

@@ -100,6 +100,7 @@ struct gecm_ctx {
     int s2_ready;
     uint32_t *hacc, *hfail;
     uint32_t fail_planes;    /* planes of hfail: 1, or 1 + sub-sequences (gecm_dev_s2_fail_planes) */
+    uint32_t s2_K;           /* sub-sequences per curve of the last gecm_stage2_init; 0 before the first */
     gecm_pairs pm;           /* pair map of the last single-range gecm_stage2 call (pm_valid), reused while (range, D, U) match */
     int pm_valid;
     gecm_s2_tape tp;         /* the device tape made from pm (tp_valid): it depends on (pm, D, U) only, so it is kept with it */
@@ -1257,7 +1258,27 @@ int gecm_stage2_init(gecm_ctx *c, uint32_t D, uint32_t U)
     }
     if (gecm_dev_s2_fail_planes(c->dev) != planes) { set_err("gecm_stage2_init: failure planes out of step"); return GECM_ERR_STATE; }
     c->s2_ready = 1;
+    c->s2_K = K;
     return GECM_OK;
+}
+
+/* Sub-sequences per curve in stage 2 (include/gecm.h): the device layer keeps the setting and applies it where it
+ * chooses K for a batch (gecm_dev_s2_subseq, gecm_dev_batch_bytes), so memory accounting and init agree. */
+int gecm_set_stage2_subseq(gecm_ctx *c, int k)
+{
+    if (!c) { set_err("gecm_set_stage2_subseq: no context"); return GECM_ERR_ARG; }
+    if (gecm_dev_set_s2_subseq(c->dev, k)) {
+        set_err("gecm_set_stage2_subseq: %d is not GECM_S2_SUBSEQ_DEFAULT, GECM_S2_SUBSEQ_AUTO or 1, 2, 4, 8, 16, 32", k);
+        return GECM_ERR_ARG;
+    }
+    return GECM_OK;
+}
+
+int gecm_get_stage2_subseq(const gecm_ctx *c, uint32_t *k_chunks)
+{
+    if (!c) { set_err("gecm_get_stage2_subseq: no context"); return GECM_ERR_ARG; }
+    if (k_chunks) *k_chunks = c->s2_K ? gecm_dev_s2_k_chunks(c->dev) : 0;
+    return (int)c->s2_K;
 }
 
 int gecm_pair_primes(gecm_pairs *out, uint64_t B1, uint64_t B2, uint32_t D, uint32_t U)

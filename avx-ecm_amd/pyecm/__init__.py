@@ -117,6 +117,10 @@ EXPORTS += ["gecm_stage1_ranges", "gecm_stage1_range", "gecm_stage1_describe_ran
 _sig("gecm_scan_factors", c_int, c_void_p, c_int, ctypes.POINTER(c_size_t))
 _sig("gecm_curve_flag", c_int, c_void_p, c_int, c_size_t)
 EXPORTS += ["gecm_scan_factors", "gecm_curve_flag", "gecm_prepare_input", "gecm_sizeinbase10"]
+_sig("gecm_set_stage2_subseq", c_int, c_void_p, c_int)
+_sig("gecm_get_stage2_subseq", c_int, c_void_p, ctypes.POINTER(ctypes.c_uint32))
+EXPORTS += ["gecm_set_stage2_subseq", "gecm_get_stage2_subseq"]
+S2_SUBSEQ_DEFAULT, S2_SUBSEQ_AUTO = 0, -1
 EXPORTS += ["gecm_stage2_init", "gecm_pair_primes", "gecm_pairmap_release", "gecm_stage2_pair", "gecm_stage2", "gecm_stage2_prepare", "gecm_stage2_pair_prepare",
             "gecm_get_stage2_stats", "gecm_download_acc", "gecm_stage2_factor"]
 
@@ -555,6 +559,20 @@ class Engine:
         """host side of stage2_pair(pairs) ahead of time (the launch tape of that pair map); no device work"""
         _chk(lib.gecm_stage2_pair_prepare(self._h, D, U, pairs.steps, pairs.pairmap_v, pairs.pairmap_u, pairs.amin),
              "gecm_stage2_pair_prepare")
+
+    def set_stage2_subseq(self, k):
+        """sub-sequences per curve for the table build and the giant steps of stage 2, from the next stage 2 on:
+        "default" (single-N: by batch size; multi-modulus: 1), "auto" (by batch size on every context) or 1, 2, .. 32"""
+        k = {"default": S2_SUBSEQ_DEFAULT, "auto": S2_SUBSEQ_AUTO}.get(k, k)
+        if isinstance(k, bool) or not isinstance(k, int):
+            raise ValueError("set_stage2_subseq: 'auto', 'default' or an int")
+        _chk(lib.gecm_set_stage2_subseq(self._h, k), "gecm_set_stage2_subseq")
+
+    def stage2_subseq(self):
+        """(K of the last stage-2 init, 0 before the first; giant-step chunks made with sub-sequences since)"""
+        n = ctypes.c_uint32(0)
+        k = _chk(lib.gecm_get_stage2_subseq(self._h, ctypes.byref(n)), "gecm_get_stage2_subseq")
+        return k, n.value
 
     def stage2_stats(self):
         st = Stage2Stats()

@@ -296,6 +296,25 @@ typedef struct {
 } gecm_stage2_stats;
 int gecm_get_stage2_stats(const gecm_ctx *ctx, gecm_stage2_stats *st);
 
+/* ---- sub-sequences per curve in stage 2 ----------------------------------------
+ * The baby-step table and the giant steps are one dependent chain per curve.  A batch too small to fill the chip
+ * splits each chain into K interleaved sub-sequences (K times the wavefronts for those two phases; the pair walk is
+ * not touched).  The accumulators are bit for bit those of K = 1.  Where an inversion of stage 2 meets a factor, the
+ * factor reported for a curve may be a proper divisor of the one K = 1 reports (a modulus made of many small primes).
+ * gecm_set_stage2_subseq: GECM_S2_SUBSEQ_DEFAULT keeps what the library always did: K by batch size on a single-N
+ *   context (two wavefronts per SIMD; the GECM_S2_SUBSEQ environment knob overrides), K = 1 on a multi-modulus one.
+ *   GECM_S2_SUBSEQ_AUTO applies the batch-size rule on every kind of context, counted over the batch's padded
+ *   positions.  1, 2, 4, 8, 16 or 32 is that K on any context.  Takes effect at the next gecm_stage2_init, gecm_stage2
+ *   or gecm_stage2_prepare; gecm_batch_bytes counts the scratch of the K the setting gives.  GECM_ERR_ARG for any
+ *   other value or a NULL context.
+ * gecm_get_stage2_subseq: the K the last gecm_stage2_init used, 0 before the first; *k_chunks (may be NULL) = the
+ *   giant-step chunks generated with sub-sequences since that init (the last chunk of a range, and every chunk of a
+ *   range that starts at the origin, are plain chains at any K).  GECM_ERR_ARG for a NULL context. */
+#define GECM_S2_SUBSEQ_DEFAULT 0    /* single-N: by batch size; multi-modulus: 1 */
+#define GECM_S2_SUBSEQ_AUTO   (-1)  /* by batch size on every kind of context */
+int gecm_set_stage2_subseq(gecm_ctx *ctx, int k);
+int gecm_get_stage2_subseq(const gecm_ctx *ctx, uint32_t *k_chunks);
+
 /* stg2acc as a vec operand (reference layout, Montgomery radix, canonical), ecm.c:1489 */
 int gecm_download_acc(gecm_ctx *ctx, void *acc);
 /* Factor check after stage 2 (ecm.c:1485-1528): gcd(acc_k, N), or — when a batch inversion met a
@@ -317,7 +336,7 @@ int gecm_stage2_factor(gecm_ctx *ctx, size_t k, char *dec, size_t declen, int *i
  * exactly as they do on a single-N context of it: gecm_stage1, gecm_stage1_range, gecm_sync, gecm_stage2*,
  * gecm_format_save_line, gecm_format_resume_line, gecm_stage1_factor, gecm_stage2_factor, gecm_scan_factors (*first:
  * the lowest flagged caller index), gecm_curve_flag.  Stage 1 runs with 1 or 2 lanes per curve (0 = chosen by batch
- * size as for one number), stage 2 with one sub-sequence per curve.
+ * size as for one number), stage 2 with one sub-sequence per curve unless gecm_set_stage2_subseq asks for more.
  * GECM_ERR_STATE on a multi-modulus context: the L0 operators (gecm_vecinvmod among them), gecm_get_one,
  * gecm_upload_points (given points go in through gecm_resume_points_multi), gecm_download_points, gecm_download_points_plain, gecm_download_acc (the reference radix differs from number to number),
  * gecm_build_curves, gecm_set_special_form, gecm_set_report_modulus; gecm_build_curves_multi on a single-N context.

@@ -11,7 +11,14 @@ With --curves-per-number C [C ...] it compares the two packings of a multi-modul
 `--real-curves` curves on random N of `--bits` bits, C curves per number, stage 1 to B1 (and, with --b2, stage 2 to B2)
 under every `--packing` named, in one process: one warm call, then the median of five.
 usage: python tools/multi_bench.py --curves-per-number 8 16 32 64 [--packing wave lane] [--real-curves 131072]
-       [--bits 415 200] [--b1 100000] [--b2 0] [--out profiles/dense]"""
+       [--bits 415 200] [--b1 100000] [--b2 0] [--out profiles/dense]
+
+With --stage2 it times stage 2 of a multi-modulus batch with and without sub-sequences per curve:
+`--count` random N of `--bits` bits with `--curves` curves each, stage 1 to B1 once, then for every `--packing` and every
+`--subseq` (1 = the plain chain, auto = by batch size) in one process: one warm stage 2 to B2, then five timed ones
+(wall time of the synchronous call, median of five).  The accumulators of the first and last curve must not depend on K.
+usage: python tools/multi_bench.py --stage2 --count 32 --curves 128 [--subseq 1 auto] [--packing wave lane]
+       [--bits 415] [--b1 100000] [--b2 10000000] [--out profiles/subseq]"""
 import argparse
 import json
 import os
@@ -137,6 +144,45 @@ def run_dense(bits, real, cpn, packings, b1, b2):
     return out
 
 
+def run_stage2(bits, count, cpn, packings, subseqs, b1, b2):
+    """stage 2 with K = 1 against K by batch size, `count` numbers x `cpn` curves"""
+    import statistics
+    import pyecm
+    rnd = random.Random(bits * 1000 + cpn)
+    ns = [rnd.getrandbits(bits) | (1 << (bits - 1)) | 1 for _ in range(count)]
+    sig = [1000 + k for k in range(count * cpn)]
+    which = [i for i in range(count) for _ in range(cpn)]
+    out = {"bits": bits, "numbers": count, "curves_per_number": cpn, "real_curves": count * cpn, "B1": b1, "B2": b2}
+    for packing in packings:
+        eng = pyecm.MultiEngine(ns)
+        eng.set_packing(packing)
+        out["dev_limbs"] = eng.cfg.dev_limbs
+        eng.build_curves(sig, which)
+        eng.stage1(b1)
+        r = {"positions": pyecm.multi_positions([cpn] * count, packing)}
+        accs = {}
+        for k in subseqs:
+            eng.set_stage2_subseq(k if k == "auto" else int(k))
+            secs, kernel_ms = [], []
+            for call in range(6):               # stage 2 starts from the stage-1 points every time: the same work
+                t = time.perf_counter()
+                eng.stage2(b2)
+                secs.append(time.perf_counter() - t)
+                kernel_ms.append(eng.last_kernel_ms())
+            used, k_chunks = eng.stage2_subseq()
+            accs[k] = (eng.acc(0), eng.acc(count * cpn - 1))
+            r["subseq_%s" % k] = {"K": used, "k_chunks": k_chunks, "stage2_seconds": [round(x, 4) for x in secs],
+                                  "stage2_median_of_5": round(statistics.median(secs[1:]), 4),
+                                  "last_launch_kernel_ms": [round(x, 2) for x in kernel_ms]}
+        assert len(set(accs.values())) == 1, "the accumulators depend on K"
+        if len(subseqs) == 2:
+            a, b = (r["subseq_%s" % k]["stage2_median_of_5"] for k in subseqs)
+            r["stage2_%s_over_%s" % tuple(subseqs)] = round(a / b, 3)
+        out[packing] = r
+        eng.close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--curves-per-number", type=int, nargs="+", default=None)
@@ -148,10 +194,19 @@ def main():
     ap.add_argument("--curves", type=int, default=4096)
     ap.add_argument("--b1", type=int, default=100000)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--stage2", action="store_true")
+    ap.add_argument("--subseq", nargs="+", default=["1", "auto"])
     a = ap.parse_args()
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "dense" if a.curves_per_number else "multi")
+        a.out = os.path.join(ROOT, "profiles", "subseq" if a.stage2 else "dense" if a.curves_per_number else "multi")
     os.makedirs(a.out, exist_ok=True)
+    if a.stage2:
+        for bits in a.bits:
+            r = run_stage2(bits, a.count, a.curves, a.packing, a.subseq, a.b1, a.b2 or 10000000)
+            print(json.dumps(r), flush=True)
+            with open(os.path.join(a.out, "stage2_%d_n%d_c%d.json" % (bits, a.count, a.curves)), "w") as f:
+                json.dump(r, f, indent=1)
+        return
     if a.curves_per_number:
         for bits in a.bits:
             for cpn in a.curves_per_number:
