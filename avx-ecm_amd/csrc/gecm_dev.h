@@ -26,8 +26,9 @@ const char *gecm_dev_error(void);
 /* limb counts for which kernels are instantiated, ascending, 0-terminated */
 const int *gecm_dev_supported_nl(void);
 
-int gecm_dev_open(gecm_dev **out, int device, int nl, const uint32_t *n, const uint32_t *kp,
-                  const uint32_t *one, uint32_t rho);
+/* m: the constants of the context's modulus at nl limbs (gecm_ops.h), copied before it returns.  multi != 0: a
+ * multi-modulus context, m the modulus gecm_get_config reports; see gecm_dev_set_groups. */
+int gecm_dev_open(gecm_dev **out, int device, int nl, const gecm_devmod *m, int multi);
 void gecm_dev_close(gecm_dev *d);
 int gecm_dev_device_name(gecm_dev *d, char *buf, size_t len);
 int gecm_dev_memory(gecm_dev *d, uint64_t *free_bytes, uint64_t *total_bytes);   /* hipMemGetInfo */
@@ -40,26 +41,23 @@ size_t gecm_dev_stride(gecm_dev *d);
 int gecm_dev_upload(gecm_dev *d, const uint32_t *X, const uint32_t *Z, const uint32_t *S);
 int gecm_dev_upload_xz(gecm_dev *d, const uint32_t *X, const uint32_t *Z);   /* X, Z only; S untouched */
 /* X, Z from canonical PLAIN residues x, z in [0, N) ([limb][curve], not Montgomery form): the device multiplies each by
- * r2 = R^2 mod N (nl limbs; a multi-modulus context takes every block's from its group constants and ignores r2).
- * S untouched; the padding lanes get x = z = 1.  Synchronous. */
-int gecm_dev_upload_plain(gecm_dev *d, const uint32_t *x, const uint32_t *z, const uint32_t *r2);
+ * R^2 mod N (a multi-modulus context: by that of the curve's own modulus).  S untouched; the padding lanes get
+ * x = z = 1.  Synchronous. */
+int gecm_dev_upload_plain(gecm_dev *d, const uint32_t *x, const uint32_t *z);
 /* canonical Montgomery-form S = (A+2)/4 of the batch */
 int gecm_dev_download_s(gecm_dev *d, uint32_t *S);
 /* ---- curve construction on the device (csrc/gecm_kernels.hip: k_build) ----
- * gecm_dev_set_r2: R^2 mod N (nl limbs) of a single-modulus context, kept for gecm_dev_build.
  * gecm_dev_build: the Suyama curves of sigma[0 .. count) into X, Z, S of the batch; count is what gecm_dev_resize was
- * given (a multi-modulus context: after gecm_dev_set_groups, sigma in device order, any value in the padding).  Needs
- * gecm_dev_set_s2const.  flags[i] = 1 where a denominator of curve i had no inverse.  Synchronous; the kernel's own time
- * is gecm_dev_last_build_ms.
+ * given (a multi-modulus context: sigma in device order, any value in the padding).  Inverts.  flags[i] = 1 where a
+ * denominator of curve i had no inverse.  Synchronous; the kernel's own time is gecm_dev_last_build_ms.
  * gecm_dev_fill_twin: X, Z, S of dst (a context modulo Mw, N | Mw, on the same device with a batch of the same size)
  * from those of src, on the device: out of src's Montgomery form, the limb planes copied (zero-filled or cut to dst's
- * limb count), into dst's with r2 = dst's R^2 mod Mw.  Synchronous. */
-int gecm_dev_set_r2(gecm_dev *d, const uint32_t *r2);
+ * limb count), into dst's with dst's own R^2 mod Mw.  Synchronous. */
 int gecm_dev_build(gecm_dev *d, const uint64_t *sigma, size_t count, uint32_t *flags);
 float gecm_dev_last_build_ms(gecm_dev *d);
-int gecm_dev_fill_twin(gecm_dev *dst, gecm_dev *src, const uint32_t *r2);
+int gecm_dev_fill_twin(gecm_dev *dst, gecm_dev *src);
 /* X <- X/Z, Z <- R mod N in the batch planes (canonical), for every curve whose Z has an inverse; the others keep both
- * and get flags[i] = 1 (count = the batch's curves, padding included as for gecm_dev_build).  Needs gecm_dev_set_s2const.
+ * and get flags[i] = 1 (count = the batch's curves, padding included as for gecm_dev_build).  Inverts.
  * Synchronous; the kernel's own time is gecm_dev_last_build_ms. */
 int gecm_dev_normalize(gecm_dev *d, uint32_t *flags);
 int gecm_dev_set_tape(gecm_dev *d, const uint8_t *tape, size_t len);
@@ -94,33 +92,27 @@ int gecm_dev_download_plain(gecm_dev *d, uint32_t *x, uint32_t *z);
  * ABI returns results in the reference's own Montgomery radix. */
 int gecm_dev_l0(gecm_dev *d, int op, const uint32_t *a, const uint32_t *b, uint32_t *c, uint32_t *dd,
                 size_t count, const uint32_t *fix);
-/* test-level inversion of `count` independent residues with the stage-2 inversion (fe_inv_mont; needs
- * gecm_dev_set_s2const).  a canonical; inv = the inverse as fe_inv_mont returns it, multiplied by the constant `fix`
+/* test-level inversion of `count` independent residues with the stage-2 inversion (fe_inv_mont; needs the context's
+ * r3).  a canonical; inv = the inverse as fe_inv_mont returns it, multiplied by the constant `fix`
  * (internal Montgomery form) and canonical, or 0 where gcd(a, N) != 1; g = gcd(a, N), a plain integer. */
 int gecm_dev_l0_inv(gecm_dev *d, const uint32_t *a, uint32_t *inv, uint32_t *g, size_t count, const uint32_t *fix);
 
-/* ---- multi-modulus batches (DESIGN.md §13) ----
- * gecm_dev_set_multi: from now on every launch of this context takes its modulus per 64-curve block from the group
- * tables, with 1 or 2 lanes per curve and one stage-2 sub-sequence per curve (until gecm_dev_set_s2_subseq says
- * otherwise); the L0 operators are refused.  Call it right after gecm_dev_open.
- * gecm_dev_set_groups: after gecm_dev_resize, the constants of ngroups moduli (n, kp, one, r3, r2: nl limbs each,
- * modulus g at [g*nl]; rho, inv_iters: one word each) and the modulus of every 64-curve block of the batch
- * (stride / 64 entries, each < ngroups).  Copied before it returns. */
-void gecm_dev_set_multi(gecm_dev *d);
-int gecm_dev_set_groups(gecm_dev *d, uint32_t ngroups, const uint32_t *n, const uint32_t *kp, const uint32_t *one,
-                        const uint32_t *r3, const uint32_t *rho, const uint32_t *inv_iters, const uint32_t *r2,
-                        const uint32_t *block_group);
-/* Lane packing: after gecm_dev_set_groups, the modulus of every curve position (stride entries, the
- * padding included; host memory).  From now on the launches of this batch run the per-lane kernels: a modulus per lane,
- * one lane per curve (gecm_dev_stage1 refuses two), block_group unused.  NULL: back to one modulus per 64-curve block.
- * A resize of the batch ends it.  gecm_dev_lane_packing_built: whether the per-lane kernels exist at this limb count. */
-int gecm_dev_set_curve_groups(gecm_dev *d, uint32_t ngroups, const uint32_t *curve_group);
+/* ---- multi-modulus batches (DESIGN.md §13, §16) ----
+ * A context opened with multi != 0 takes the modulus of every launch from device tables, with 1 or 2 lanes per curve
+ * and one stage-2 sub-sequence per curve (until gecm_dev_set_s2_subseq says otherwise); the L0 operators are refused.
+ * gecm_dev_set_groups, once per batch (a gecm_dev_resize ends what it set): the constants of the batch's ngroups
+ * moduli, r3 included, and which modulus goes where.  curve_group == NULL, wave packing: block_group names the modulus
+ * of every 64-curve block (stride / 64 entries).  curve_group != NULL, lane packing: it names the modulus of every curve
+ * position (stride entries, the padding included), block_group is not read, and the launches of this batch run the
+ * per-lane kernels: a modulus per lane, one lane per curve (gecm_dev_stage1 refuses two).  Every entry < ngroups.
+ * Host memory, copied before it returns.  gecm_dev_lane_packing_built: whether the per-lane kernels exist at this
+ * limb count. */
+int gecm_dev_set_groups(gecm_dev *d, uint32_t ngroups, const gecm_devmod *mods, const uint32_t *block_group,
+                        const uint32_t *curve_group);
 int gecm_dev_lane_packing_built(int nl);
 
 /* ---- stage 2 (csrc/gecm_stage2.hpp) ----
- * r3 = R^3 mod N (28-bit limbs); inv_iters = batches of 28 division steps of the device inversion (fe_invert). */
-int gecm_dev_set_s2const(gecm_dev *d, const uint32_t *r3, uint32_t inv_iters);
-/* ecm_stage2_init: baby-step table (npb entries, X/Z normalised), Pd = [D]Q, acc = one.
+ * ecm_stage2_init: baby-step table (npb entries, X/Z normalised), Pd = [D]Q, acc = one.  Inverts.
  * keep: bitmap over j in [0, umax], bit set iff j is stored.  L = ring half-size (2L giant steps). */
 /* K = gecm_dev_s2_subseq(d) sub-sequences per curve (1: the plain chain).  For K > 1: tgt_off[r] .. tgt_off[r+1] is
  * the range of tgt[] holding the table indices of the kept members j = r, r+K, ... (r = 0: K, 2K, ...) of

@@ -64,8 +64,8 @@ struct gecm_dev {
     int nl = 0;
     const gecm_kernels_p1 *k1 = nullptr;   // the launchers of this limb count
     const gecm_kernels_p2 *k2 = nullptr;
-    std::vector<uint32_t> n, kp, one;
-    uint32_t rho = 0;
+    gecm_devmod mod = {};            // the context's modulus (gecm_dev_open), its pointers into mod_limbs
+    std::vector<uint32_t> mod_limbs;
     size_t ncurves = 0, stride = 0;
     uint32_t *dX = nullptr, *dZ = nullptr, *dS = nullptr, *dT0 = nullptr, *dT1 = nullptr;
     uint32_t *dTape = nullptr;
@@ -74,8 +74,6 @@ struct gecm_dev {
     size_t cut_launches = 0;
     std::vector<size_t> tape_cuts;   // byte offsets at which a stage-1 launch may start (gecm_dev_set_tape), first = 0, last = tape_len
     // stage 2
-    std::vector<uint32_t> r3;
-    uint32_t inv_iters = 0;
     uint32_t *dPbX = nullptr, *dBlk = nullptr, *dPd = nullptr, *dAcc = nullptr, *dFail = nullptr, *dKeep = nullptr;
     uint32_t *dPa = nullptr, *dSteps = nullptr, *dFlags = nullptr;
     size_t flags_cap = 0;
@@ -99,18 +97,17 @@ struct gecm_dev {
     int cus = 0;          // compute units of the device (4 SIMDs each)
     int last_lanes = 0;   // lanes per curve the last stage-1 launch used
     std::string last_kernel;   // and the kernel's name as rocprofv3 prints it
-    // multi-modulus context (gecm_dev_set_multi): one modulus per 64-curve block, constants in device memory
+    // multi-modulus context (gecm_dev_open): one modulus per 64-curve block, constants in device memory
     bool multi = false;
-    void *dGroups = nullptr;          // one packed constant set per modulus (gecm_kernels_p1::pack_group)
+    unsigned char *dGroups = nullptr; // one packed constant set per modulus (gecm_kernels_p1::pack_group)
     uint32_t *dBlockGroup = nullptr;  // modulus of every 64-curve block of the batch
     size_t groups_cap = 0, blocks_cap = 0;
     bool have_groups = false;
-    // lane packing (gecm_dev_set_curve_groups): one modulus per curve position instead of one per block
+    // lane packing (gecm_dev_set_groups with curve_group): one modulus per curve position instead of one per block
     uint32_t *dCurveGroup = nullptr;
     size_t curve_group_cap = 0;
     bool lane_packed = false;
     // curve construction on the device (gecm_dev_build)
-    std::vector<uint32_t> r2;         // R^2 mod N of a single-modulus context (gecm_dev_set_r2)
     uint64_t *dSigma = nullptr;
     size_t sigma_cap = 0;
     float build_ms = 0.f;
@@ -151,26 +148,50 @@ extern "C" int gecm_dev_count(void)
 static gecm_modconst modconst(const gecm_dev *d)
 {
     gecm_modconst mc;
-    mc.n = d->n.data();
-    mc.kp = d->kp.data();
-    mc.one = d->one.data();
-    mc.r3 = d->r3.empty() ? d->one.data() : d->r3.data();
-    mc.rho = d->rho;
-    mc.inv_iters = d->inv_iters;
+    mc.m = d->mod;
     mc.source = !d->multi ? GECM_SRC_VALUE : d->lane_packed ? GECM_SRC_LANE : GECM_SRC_WAVE;
     mc.groups = d->multi ? d->dGroups : nullptr;
     mc.block_group = d->multi ? d->dBlockGroup : nullptr;
-    mc.r2 = nullptr;
     mc.curve_group = mc.source == GECM_SRC_LANE ? d->dCurveGroup : nullptr;
     return mc;
 }
 
-extern "C" int gecm_dev_open(gecm_dev **out, int device, int nl, const uint32_t *n, const uint32_t *kp,
-                             const uint32_t *one, uint32_t rho)
+// Has the context what operation `fn` needs?  A batch, on a multi-modulus context the batch's moduli, and where the
+// operation inverts, r3.
+static int ready(const gecm_dev *d, const char *fn, bool inverts)
+{
+    const char *lacks = !d->stride                   ? "no batch (gecm_dev_resize)"
+                        : d->multi && !d->have_groups ? "the moduli of the batch are not set (gecm_dev_set_groups)"
+                        : inverts && !d->mod.r3       ? "the context was opened without inversion constants (r3)"
+                                                      : nullptr;
+    if (!lacks) return 0;
+    g_err = std::string(fn) + ": " + lacks;
+    return -2;
+}
+
+// A device array that only grows: room for `want` elements at *p, of which *cap says how many it has.  What it held is
+// not kept.
+template <class T>
+static int grow(T **p, size_t *cap, size_t want)
+{
+    if (want <= *cap) return 0;
+    (void)hipFree(*p);
+    *p = nullptr;
+    *cap = 0;
+    HIPCHK(hipMalloc(p, want * sizeof(T)));
+    *cap = want;
+    return 0;
+}
+
+extern "C" int gecm_dev_open(gecm_dev **out, int device, int nl, const gecm_devmod *m, int multi)
 {
     const auto *kt = kernels_for(nl);
     if (!kt) {
         g_err = "gecm_dev_open: unsupported limb count " + std::to_string(nl);
+        return -2;
+    }
+    if (!m || !m->n || !m->kp || !m->one || !m->r2) {
+        g_err = "gecm_dev_open: the modulus constants are incomplete";
         return -2;
     }
     int cnt = 0;
@@ -188,15 +209,20 @@ extern "C" int gecm_dev_open(gecm_dev **out, int device, int nl, const uint32_t 
     d->nl = nl;
     d->k1 = kt->p1();
     d->k2 = kt->p2();
-    d->n.assign(n, n + nl);
-    d->kp.assign(kp, kp + nl);
-    d->one.assign(one, one + nl);
-    d->rho = rho;
+    d->multi = multi != 0;
+    const uint32_t *rows[5] = {m->n, m->kp, m->one, m->r2, m->r3};
+    d->mod_limbs.assign((size_t)5 * nl, 0);
+    uint32_t *own[5];
+    for (int q = 0; q < 5; q++) {
+        own[q] = d->mod_limbs.data() + (size_t)q * nl;
+        if (rows[q]) memcpy(own[q], rows[q], (size_t)nl * sizeof(uint32_t));
+    }
+    d->mod = {own[0], own[1], own[2], own[3], m->r3 ? own[4] : nullptr, m->rho, m->inv_iters};
     if (nl <= 40) {
         uint32_t h[80] = {0};
         for (int i = 0; i < nl; i++) {
-            h[i] = n[i];
-            h[40 + i] = kp[i];
+            h[i] = m->n[i];
+            h[40 + i] = m->kp[i];
         }
         HIPCHK(hipMalloc(&d->dModQ, sizeof h));
         HIPCHK(hipMemcpy(d->dModQ, h, sizeof h, hipMemcpyHostToDevice));
@@ -342,17 +368,10 @@ extern "C" int gecm_dev_upload_xz(gecm_dev *d, const uint32_t *X, const uint32_t
 
 // Plain residues into the batch: x, z canonical in [0, N), host [limb][ncurves]; X = x R mod N, Z = z R mod N by the
 // to_mont kernel, through the scratch planes the downloads use.  The padding lanes get x = z = 1.
-extern "C" int gecm_dev_upload_plain(gecm_dev *d, const uint32_t *x, const uint32_t *z, const uint32_t *r2)
+extern "C" int gecm_dev_upload_plain(gecm_dev *d, const uint32_t *x, const uint32_t *z)
 {
     HIPCHK(hipSetDevice(d->device));
-    if (d->multi ? !d->have_groups : !r2) {
-        g_err = d->multi ? "gecm_dev_upload_plain: the moduli of the batch are not set" : "gecm_dev_upload_plain: R^2 mod N missing";
-        return -2;
-    }
-    if (!d->stride) {
-        g_err = "gecm_dev_upload_plain: no batch";
-        return -2;
-    }
+    if (ready(d, "gecm_dev_upload_plain", false)) return -2;
     if (upload_soa(d, d->dT0, x)) return -1;
     if (upload_soa(d, d->dT1, z)) return -1;
     const size_t pad = d->stride - d->ncurves;        // at most 63: limb 0 of the padding lanes, set to 1
@@ -362,7 +381,6 @@ extern "C" int gecm_dev_upload_plain(gecm_dev *d, const uint32_t *x, const uint3
         HIPCHK(hipMemcpyAsync(d->dT1 + d->ncurves, ones.data(), pad * sizeof(uint32_t), hipMemcpyHostToDevice, d->stream));
     }
     gecm_modconst mc = modconst(d);
-    mc.r2 = r2;
     d->k1->to_mont(d->stream, &mc, d->dT0, d->dT1, d->dX, d->dZ, d->stride);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(d->stream));
@@ -382,12 +400,6 @@ extern "C" int gecm_dev_download_s(gecm_dev *d, uint32_t *S)
 }
 
 // ---------------------------------------------------------------- curve construction
-extern "C" int gecm_dev_set_r2(gecm_dev *d, const uint32_t *r2)
-{
-    d->r2.assign(r2, r2 + d->nl);
-    return 0;
-}
-
 extern "C" float gecm_dev_last_build_ms(gecm_dev *d) { return d->build_ms; }
 
 extern "C" int gecm_dev_build(gecm_dev *d, const uint64_t *sigma, size_t count, uint32_t *flags)
@@ -397,29 +409,12 @@ extern "C" int gecm_dev_build(gecm_dev *d, const uint64_t *sigma, size_t count, 
         g_err = "gecm_dev_build: no batch of that many curves (gecm_dev_resize)";
         return -2;
     }
-    if (d->r3.empty() || (d->multi ? !d->have_groups : d->r2.empty())) {
-        g_err = d->multi ? "gecm_dev_build: the moduli of the batch are not set" : "gecm_dev_build: inversion constants or R^2 mod N missing";
-        return -2;
-    }
-    if (d->sigma_cap < d->stride) {
-        (void)hipFree(d->dSigma);
-        d->dSigma = nullptr;
-        d->sigma_cap = 0;
-        HIPCHK(hipMalloc(&d->dSigma, d->stride * sizeof(uint64_t)));
-        d->sigma_cap = d->stride;
-    }
-    if (d->flags_cap < d->stride) {
-        (void)hipFree(d->dFlags);
-        d->dFlags = nullptr;
-        d->flags_cap = 0;
-        HIPCHK(hipMalloc(&d->dFlags, d->stride * 4));
-        d->flags_cap = d->stride;
-    }
+    if (ready(d, "gecm_dev_build", true)) return -2;
+    if (grow(&d->dSigma, &d->sigma_cap, d->stride) || grow(&d->dFlags, &d->flags_cap, d->stride)) return -1;
     // the padding lanes build sigma = 0: computed, never flagged or read
     HIPCHK(hipMemsetAsync(d->dSigma, 0, d->stride * sizeof(uint64_t), d->stream));
     HIPCHK(hipMemcpyAsync(d->dSigma, sigma, count * sizeof(uint64_t), hipMemcpyHostToDevice, d->stream));
     gecm_modconst mc = modconst(d);
-    mc.r2 = d->r2.empty() ? nullptr : d->r2.data();
     HIPCHK(hipEventRecord(d->ev0, d->stream));
     d->k1->build(d->stream, &mc, d->dSigma, d->dX, d->dZ, d->dS, d->dFlags, d->stride);
     HIPCHK(hipGetLastError());
@@ -434,21 +429,12 @@ extern "C" int gecm_dev_build(gecm_dev *d, const uint64_t *sigma, size_t count, 
 extern "C" int gecm_dev_normalize(gecm_dev *d, uint32_t *flags)
 {
     HIPCHK(hipSetDevice(d->device));
-    if (!d->stride || !d->ncurves || !flags) {
-        g_err = "gecm_dev_normalize: no batch";
+    if (ready(d, "gecm_dev_normalize", true)) return -2;
+    if (!d->ncurves || !flags) {
+        g_err = "gecm_dev_normalize: no curves, or nowhere to put their flags";
         return -2;
     }
-    if (d->r3.empty() || (d->multi && !d->have_groups)) {
-        g_err = d->multi ? "gecm_dev_normalize: the moduli of the batch are not set" : "gecm_dev_normalize: inversion constants missing";
-        return -2;
-    }
-    if (d->flags_cap < d->stride) {
-        (void)hipFree(d->dFlags);
-        d->dFlags = nullptr;
-        d->flags_cap = 0;
-        HIPCHK(hipMalloc(&d->dFlags, d->stride * 4));
-        d->flags_cap = d->stride;
-    }
+    if (grow(&d->dFlags, &d->flags_cap, d->stride)) return -1;
     gecm_modconst mc = modconst(d);
     HIPCHK(hipEventRecord(d->ev0, d->stream));
     d->k1->normalize(d->stream, &mc, d->dX, d->dZ, d->dFlags, d->stride);
@@ -461,19 +447,18 @@ extern "C" int gecm_dev_normalize(gecm_dev *d, uint32_t *flags)
     return 0;
 }
 
-extern "C" int gecm_dev_fill_twin(gecm_dev *dst, gecm_dev *src, const uint32_t *r2)
+extern "C" int gecm_dev_fill_twin(gecm_dev *dst, gecm_dev *src)
 {
     HIPCHK(hipSetDevice(src->device));
     if (dst->device != src->device || !src->stride || dst->stride != src->stride || dst->ncurves != src->ncurves ||
-        src->multi || dst->multi || !r2) {
+        src->multi || dst->multi) {
         g_err = "gecm_dev_fill_twin: the two contexts do not hold batches of one size on one device";
         return -2;
     }
     HIPCHK(hipStreamSynchronize(dst->stream));    // the copies below run on src's stream
     const int common = src->nl < dst->nl ? src->nl : dst->nl;
     const size_t row = src->stride * sizeof(uint32_t);
-    gecm_modconst ms = modconst(src), md = modconst(dst);
-    md.r2 = r2;
+    const gecm_modconst ms = modconst(src), md = modconst(dst);
     // src's planes out of Montgomery form into its scratch planes, then limb plane by limb plane into dst's
     auto lift = [&](const uint32_t *a, const uint32_t *b) -> int {
         src->k1->from_mont(src->stream, &ms, a, b, src->dT0, src->dT1, src->stride);
@@ -501,12 +486,7 @@ extern "C" int gecm_dev_set_tape(gecm_dev *d, const uint8_t *tape, size_t len)
 {
     HIPCHK(hipSetDevice(d->device));
     size_t words = (len + 3) / 4 + 1;
-    if (words > d->tape_cap) {
-        (void)hipFree(d->dTape);
-        d->dTape = nullptr;
-        HIPCHK(hipMalloc(&d->dTape, words * 4));
-        d->tape_cap = words;
-    }
+    if (grow(&d->dTape, &d->tape_cap, words)) return -1;
     HIPCHK(hipMemsetAsync(d->dTape, 0, words * 4, d->stream));
     if (len) HIPCHK(hipMemcpyAsync(d->dTape, tape, len, hipMemcpyHostToDevice, d->stream));
     HIPCHK(hipStreamSynchronize(d->stream));
@@ -596,12 +576,9 @@ extern "C" void gecm_dev_set_fform(gecm_dev *d, int form) { d->fform = form == 2
 extern "C" int gecm_dev_stage1(gecm_dev *d, int lanes_per_curve)
 {
     HIPCHK(hipSetDevice(d->device));
-    if (!d->stride || !d->dTape) {
-        g_err = "gecm_dev_stage1: no curves or no tape";
-        return -2;
-    }
-    if (d->multi && !d->have_groups) {
-        g_err = "gecm_dev_stage1: the moduli of the batch are not set (gecm_dev_set_groups)";
+    if (ready(d, "gecm_dev_stage1", false)) return -2;
+    if (!d->dTape) {
+        g_err = "gecm_dev_stage1: no tape";
         return -2;
     }
     int lanes = lanes_per_curve ? lanes_per_curve : gecm_dev_auto_lanes(d);
@@ -654,7 +631,7 @@ extern "C" int gecm_dev_stage1(gecm_dev *d, int lanes_per_curve)
         const uint32_t tl = (uint32_t)(d->tape_cuts[cut + 1] - d->tape_cuts[cut]);
         if (lanes == 32) {
             if (gecm_launch_stage1_row(d->stream, d->row_nq, d->row_rows, tp, tl, d->dX, d->dZ, d->dS, d->stride,
-                                       (uint32_t)d->nl, d->dRowC, d->rho, row_a_lds(d))) {
+                                       (uint32_t)d->nl, d->dRowC, d->mod.rho, row_a_lds(d))) {
                 g_err = "gecm_dev_stage1: no 32-lane kernel for this limb count";
                 return -2;
             }
@@ -708,10 +685,7 @@ extern "C" int gecm_dev_download_mont(gecm_dev *d, uint32_t *X, uint32_t *Z)
 extern "C" int gecm_dev_download_plain(gecm_dev *d, uint32_t *x, uint32_t *z)
 {
     HIPCHK(hipSetDevice(d->device));
-    if (d->multi && !d->have_groups) {
-        g_err = "gecm_dev_download_plain: the moduli of the batch are not set";
-        return -2;
-    }
+    if (ready(d, "gecm_dev_download_plain", false)) return -2;
     gecm_modconst mc = modconst(d);
     d->k1->from_mont(d->stream, &mc, d->dX, d->dZ, d->dT0, d->dT1, d->stride);
     HIPCHK(hipGetLastError());
@@ -734,7 +708,7 @@ extern "C" int gecm_dev_l0(gecm_dev *d, int op, const uint32_t *a, const uint32_
     if (upload_soa(d, d->dX, a)) return -1;
     if (upload_soa(d, d->dZ, b ? b : a)) return -1;
     gecm_modconst mc = modconst(d);
-    d->k1->l0(d->stream, &mc, op, d->dX, d->dZ, d->dT0, d->dT1, d->stride, fix ? fix : d->one.data());
+    d->k1->l0(d->stream, &mc, op, d->dX, d->dZ, d->dT0, d->dT1, d->stride, fix ? fix : d->mod.one);
     HIPCHK(hipGetLastError());
     if (download_soa(d, c, d->dT0)) return -1;
     if (op == GECM_L0_ADDSUB && dd)
@@ -746,8 +720,8 @@ extern "C" int gecm_dev_l0(gecm_dev *d, int op, const uint32_t *a, const uint32_
 extern "C" int gecm_dev_l0_inv(gecm_dev *d, const uint32_t *a, uint32_t *inv, uint32_t *g, size_t count, const uint32_t *fix)
 {
     HIPCHK(hipSetDevice(d->device));
-    if (d->multi || d->r3.empty() || !fix) {
-        g_err = "gecm_dev_l0_inv: needs a single-modulus context with its inversion constants (gecm_dev_set_s2const)";
+    if (d->multi || !d->mod.r3 || !fix) {
+        g_err = "gecm_dev_l0_inv: needs a single-modulus context opened with its inversion constants (r3)";
         return -2;
     }
     if (gecm_dev_resize(d, count)) return -1;
@@ -763,94 +737,58 @@ extern "C" int gecm_dev_l0_inv(gecm_dev *d, const uint32_t *a, uint32_t *inv, ui
 }
 
 // ---------------------------------------------------------------- multi-modulus batches
-extern "C" void gecm_dev_set_multi(gecm_dev *d) { d->multi = true; }
-
-extern "C" int gecm_dev_set_groups(gecm_dev *d, uint32_t ngroups, const uint32_t *n, const uint32_t *kp,
-                                   const uint32_t *one, const uint32_t *r3, const uint32_t *rho,
-                                   const uint32_t *inv_iters, const uint32_t *r2, const uint32_t *block_group)
-{
-    HIPCHK(hipSetDevice(d->device));
-    const size_t blocks = d->stride / 64, gb = d->k1->group_bytes, nl = (size_t)d->nl;
-    if (!d->multi || !ngroups || !blocks) {
-        g_err = "gecm_dev_set_groups: not a multi-modulus context, or no moduli or curves";
-        return -2;
-    }
-    for (size_t b = 0; b < blocks; b++)
-        if (block_group[b] >= ngroups) {
-            g_err = "gecm_dev_set_groups: block " + std::to_string(b) + " names modulus " + std::to_string(block_group[b]);
-            return -2;
-        }
-    std::vector<unsigned char> packed(gb * ngroups);
-    for (uint32_t g = 0; g < ngroups; g++) {
-        gecm_modconst mc = {n + g * nl, kp + g * nl, one + g * nl, r3 + g * nl, rho[g], inv_iters[g], nullptr, nullptr,
-                            r2 + g * nl, nullptr, GECM_SRC_VALUE};
-        d->k1->pack_group(&mc, packed.data() + g * gb);
-    }
-    if (packed.size() > d->groups_cap) {
-        (void)hipFree(d->dGroups);
-        d->dGroups = nullptr;
-        HIPCHK(hipMalloc(&d->dGroups, packed.size()));
-        d->groups_cap = packed.size();
-    }
-    if (blocks > d->blocks_cap) {
-        (void)hipFree(d->dBlockGroup);
-        d->dBlockGroup = nullptr;
-        HIPCHK(hipMalloc(&d->dBlockGroup, blocks * sizeof(uint32_t)));
-        d->blocks_cap = blocks;
-    }
-    // synchronous: the host arrays may go away when this returns, and no launch may see half of them
-    HIPCHK(hipMemcpyAsync(d->dGroups, packed.data(), packed.size(), hipMemcpyHostToDevice, d->stream));
-    HIPCHK(hipMemcpyAsync(d->dBlockGroup, block_group, blocks * sizeof(uint32_t), hipMemcpyHostToDevice, d->stream));
-    HIPCHK(hipStreamSynchronize(d->stream));
-    d->have_groups = true;
-    return 0;
-}
-
 extern "C" int gecm_dev_lane_packing_built(int nl)
 {
     const auto *kt = kernels_for(nl);
     return kt ? kt->p1()->has_lane : 0;
 }
 
-extern "C" int gecm_dev_set_curve_groups(gecm_dev *d, uint32_t ngroups, const uint32_t *curve_group)
+extern "C" int gecm_dev_set_groups(gecm_dev *d, uint32_t ngroups, const gecm_devmod *mods, const uint32_t *block_group,
+                                   const uint32_t *curve_group)
 {
     HIPCHK(hipSetDevice(d->device));
-    if (!curve_group) {
-        d->lane_packed = false;
-        return 0;
-    }
-    if (!d->multi || !d->have_groups || !d->stride || !d->k1->has_lane) {
-        g_err = "gecm_dev_set_curve_groups: needs a multi-modulus context with its moduli set (gecm_dev_set_groups) at a "
-                "limb count the per-lane kernels are built for";
+    const size_t blocks = d->stride / 64, gb = d->k1->group_bytes;
+    if (!d->multi || !ngroups || !blocks || !mods || (!block_group && !curve_group)) {
+        g_err = "gecm_dev_set_groups: not a multi-modulus context, or no moduli or curves";
         return -2;
     }
-    for (size_t p = 0; p < d->stride; p++)
-        if (curve_group[p] >= ngroups) {
-            g_err = "gecm_dev_set_curve_groups: position " + std::to_string(p) + " names modulus " + std::to_string(curve_group[p]);
+    if (curve_group && !d->k1->has_lane) {
+        g_err = "gecm_dev_set_groups: the per-lane kernels are not built for this limb count";
+        return -2;
+    }
+    // the table the kernels of this batch read: a modulus per curve position, or one per 64-curve block
+    const uint32_t *table = curve_group ? curve_group : block_group;
+    for (size_t p = 0, entries = curve_group ? d->stride : blocks; p < entries; p++)
+        if (table[p] >= ngroups) {
+            g_err = std::string("gecm_dev_set_groups: ") + (curve_group ? "position " : "block ") + std::to_string(p) +
+                    " names modulus " + std::to_string(table[p]);
             return -2;
         }
-    if (d->stride > d->curve_group_cap) {
-        (void)hipFree(d->dCurveGroup);
-        d->dCurveGroup = nullptr;
-        d->curve_group_cap = 0;
-        HIPCHK(hipMalloc(&d->dCurveGroup, d->stride * sizeof(uint32_t)));
-        d->curve_group_cap = d->stride;
+    std::vector<unsigned char> packed(gb * ngroups);
+    for (uint32_t g = 0; g < ngroups; g++) {
+        if (!mods[g].r3) {
+            g_err = "gecm_dev_set_groups: modulus " + std::to_string(g) + " has no inversion constants (r3)";
+            return -2;
+        }
+        d->k1->pack_group(&mods[g], packed.data() + g * gb);
     }
-    // synchronous, as in gecm_dev_set_groups
-    HIPCHK(hipMemcpyAsync(d->dCurveGroup, curve_group, d->stride * sizeof(uint32_t), hipMemcpyHostToDevice, d->stream));
+    if (grow(&d->dGroups, &d->groups_cap, packed.size()) || grow(&d->dBlockGroup, &d->blocks_cap, blocks) ||
+        (curve_group && grow(&d->dCurveGroup, &d->curve_group_cap, d->stride)))
+        return -1;
+    // synchronous: the host arrays may go away when this returns, and no launch may see half of them
+    HIPCHK(hipMemcpyAsync(d->dGroups, packed.data(), packed.size(), hipMemcpyHostToDevice, d->stream));
+    if (curve_group) {       // the block table is not read, and defined
+        HIPCHK(hipMemsetAsync(d->dBlockGroup, 0, blocks * sizeof(uint32_t), d->stream));
+        HIPCHK(hipMemcpyAsync(d->dCurveGroup, curve_group, d->stride * sizeof(uint32_t), hipMemcpyHostToDevice, d->stream));
+    } else
+        HIPCHK(hipMemcpyAsync(d->dBlockGroup, block_group, blocks * sizeof(uint32_t), hipMemcpyHostToDevice, d->stream));
     HIPCHK(hipStreamSynchronize(d->stream));
-    d->lane_packed = true;
+    d->have_groups = true;
+    d->lane_packed = curve_group != nullptr;
     return 0;
 }
 
 // ---------------------------------------------------------------- stage 2
-extern "C" int gecm_dev_set_s2const(gecm_dev *d, const uint32_t *r3, uint32_t inv_iters)
-{
-    d->r3.assign(r3, r3 + d->nl);
-    d->inv_iters = inv_iters;
-    return 0;
-}
-
 /* Sub-sequences per curve for the stage-2 table build and giant steps: those are one dependent chain per curve, so a
  * batch of a few thousand curves (a few dozen wavefronts) is split into K interleaved chains per curve until there
  * are 2 wavefronts per SIMD (csrc/gecm_stage2.hpp, s2_init_k / giant_chunk_k).  1 for batches that fill the chip.
@@ -923,10 +861,7 @@ extern "C" int gecm_dev_s2_init(gecm_dev *d, const uint32_t *keep, size_t keep_w
                                 uint32_t K)
 {
     HIPCHK(hipSetDevice(d->device));
-    if (!d->stride || d->r3.empty() || (d->multi && !d->have_groups)) {
-        g_err = "gecm_dev_s2_init: no curves or stage-2 constants not set";
-        return -2;
-    }
+    if (ready(d, "gecm_dev_s2_init", true)) return -2;
     const size_t coord = (size_t)d->nl * d->stride * sizeof(uint32_t);
     if (K < 1 || K > 32 || (K & (K - 1)) || (K > 1 && (!tgt || !tgt_off))) {
         g_err = "gecm_dev_s2_init: bad number of sub-sequences";
@@ -958,21 +893,11 @@ extern "C" int gecm_dev_s2_init(gecm_dev *d, const uint32_t *keep, size_t keep_w
         HIPCHK(hipMalloc(&d->dPa, coord * (2 * ((size_t)G + 2) + (size_t)G + (size_t)ring_size)));
         d->s2_npb = npb; d->s2_G = G; d->s2_ring = ring_size; d->s2_stride = d->stride;
     }
-    if (keep_words > d->keep_cap) {
-        (void)hipFree(d->dKeep);
-        d->dKeep = nullptr;
-        HIPCHK(hipMalloc(&d->dKeep, keep_words * 4));
-        d->keep_cap = keep_words;
-    }
+    if (grow(&d->dKeep, &d->keep_cap, keep_words)) return -1;
     HIPCHK(hipMemcpyAsync(d->dKeep, keep, keep_words * 4, hipMemcpyHostToDevice, d->stream));
     if (K > 1) {
         const size_t tw = (size_t)tgt_off[K] + (K + 1);                 // target lists, then the K + 1 offsets
-        if (tw > d->tgt_cap) {
-            (void)hipFree(d->dTgt);
-            d->dTgt = nullptr;
-            HIPCHK(hipMalloc(&d->dTgt, tw * 4));
-            d->tgt_cap = tw;
-        }
+        if (grow(&d->dTgt, &d->tgt_cap, tw)) return -1;
         HIPCHK(hipMemcpyAsync(d->dTgt, tgt, (size_t)tgt_off[K] * 4, hipMemcpyHostToDevice, d->stream));
         HIPCHK(hipMemcpyAsync(d->dTgt + tgt_off[K], tgt_off, (K + 1) * 4, hipMemcpyHostToDevice, d->stream));
     }
@@ -1016,13 +941,8 @@ extern "C" int gecm_dev_s2_pair(gecm_dev *d, const uint32_t *steps, uint32_t nst
     }
     const size_t coord = (size_t)d->nl * d->stride * sizeof(uint32_t);
     size_t words = (size_t)nsteps * 2 + 2;
-    if (words > d->steps_cap) {
-        (void)hipFree(d->dSteps);
-        d->dSteps = nullptr;
-        d->steps_id = 0;
-        HIPCHK(hipMalloc(&d->dSteps, words * 4));
-        d->steps_cap = words;
-    }
+    if (words > d->steps_cap) d->steps_id = 0;      // the kept copy goes with the array
+    if (grow(&d->dSteps, &d->steps_cap, words)) return -1;
     // tape_id != 0 names a tape the host keeps from batch to batch: the device copy of the last one is kept too
     if (nsteps && !(tape_id && tape_id == d->steps_id && nsteps == d->steps_n))
         HIPCHK(hipMemcpyAsync(d->dSteps, steps, (size_t)nsteps * 8, hipMemcpyHostToDevice, d->stream));
@@ -1075,16 +995,12 @@ extern "C" int gecm_dev_gcd_scan(gecm_dev *d, int which, uint32_t *flags, uint32
 {
     HIPCHK(hipSetDevice(d->device));
     const uint32_t *src = which == 0 ? d->dZ : d->dAcc;
-    if (!src || !d->stride || d->r3.empty() || (d->multi && !d->have_groups)) {
+    if (!src) {
         g_err = "gecm_dev_gcd_scan: nothing to scan";
         return -2;
     }
-    if (d->flags_cap < d->stride) {
-        (void)hipFree(d->dFlags);
-        d->dFlags = nullptr;
-        HIPCHK(hipMalloc(&d->dFlags, d->stride * 4));
-        d->flags_cap = d->stride;
-    }
+    if (ready(d, "gecm_dev_gcd_scan", true)) return -2;
+    if (grow(&d->dFlags, &d->flags_cap, d->stride)) return -1;
     gecm_modconst mc = modconst(d);
     d->k1->gcd_scan(d->stream, &mc, src, d->dT0, d->dFlags, d->stride);
     HIPCHK(hipGetLastError());

@@ -884,43 +884,45 @@ __global__ void __launch_bounds__(64, 2) k_s2_merge_lane(uint32_t *acc, uint32_t
 
 #endif
 // ---------------------------------------------------------------- launchers (gecm_launch.h)
-// ModArgs, ModArgsS or S2Const from the host's copy of the modulus constants
+// ModArgs, ModArgsS or S2Const from the host's record of the modulus constants
 template <class A>
-static A mod_args(const gecm_modconst *mc)
+static A mod_args(const gecm_devmod *m)
 {
     A a;
     for (int i = 0; i < GECM_NL; i++) {
-        a.m.n[i] = mc->n[i];
-        a.m.kp[i] = mc->kp[i];
-        a.one.v[i] = mc->one[i];
+        a.m.n[i] = m->n[i];
+        a.m.kp[i] = m->kp[i];
+        a.one.v[i] = m->one[i];
     }
-    a.m.rho = mc->rho;
+    a.m.rho = m->rho;
     return a;
 }
 
-static S2Const<GECM_NL> s2_const(const gecm_modconst *mc)
+// m->r3 is not NULL here: the device layer lets no operation that inverts reach a launcher without it (ready() and
+// gecm_dev_l0_inv in gecm_dev.hip; gecm_dev_set_groups for pack_group)
+static S2Const<GECM_NL> s2_const(const gecm_devmod *m)
 {
-    S2Const<GECM_NL> k = mod_args<S2Const<GECM_NL>>(mc);
-    for (int i = 0; i < GECM_NL; i++) k.r3.v[i] = mc->r3[i];
-    k.inv_iters = mc->inv_iters;
+    S2Const<GECM_NL> k = mod_args<S2Const<GECM_NL>>(m);
+    for (int i = 0; i < GECM_NL; i++) k.r3.v[i] = m->r3[i];
+    k.inv_iters = m->inv_iters;
     return k;
 }
 
 // the R^2 mod N of a single-modulus launch (to_mont, build)
-static Fe<GECM_NL> r2_const(const gecm_modconst *mc)
+static Fe<GECM_NL> r2_const(const gecm_devmod *m)
 {
     Fe<GECM_NL> r2;
-    for (int i = 0; i < GECM_NL; i++) r2.v[i] = mc->r2[i];
+    for (int i = 0; i < GECM_NL; i++) r2.v[i] = m->r2[i];
     return r2;
 }
 
 // a by-value kernel's constants argument of type V
 template <class V>
-static V by_value(const gecm_modconst *mc)
+static V by_value(const gecm_devmod *m)
 {
-    if constexpr (std::is_same<V, Fe<GECM_NL>>::value) return r2_const(mc);
-    else if constexpr (std::is_same<V, S2Const<GECM_NL>>::value) return s2_const(mc);
-    else return mod_args<V>(mc);
+    if constexpr (std::is_same<V, Fe<GECM_NL>>::value) return r2_const(m);
+    else if constexpr (std::is_same<V, S2Const<GECM_NL>>::value) return s2_const(m);
+    else return mod_args<V>(m);
 }
 
 // The one place that picks a kernel by the constants source of the launch (mc->source, set by the device layer): the
@@ -953,7 +955,7 @@ static void launch_by_source(void *stream, const gecm_modconst *mc, dim3 grid, K
             hipLaunchKernelGGL(kw, grid, block, 0, s, c..., ModGroups<GECM_NL>{groups, mc->block_group});
             return;
         }
-    if constexpr (has_kernel<KV>) hipLaunchKernelGGL(kv, grid, block, 0, s, c..., by_value<V>(mc)...);
+    if constexpr (has_kernel<KV>) hipLaunchKernelGGL(kv, grid, block, 0, s, c..., by_value<V>(&mc->m)...);
 }
 
 // one 64-thread block per 64 curves
@@ -995,7 +997,7 @@ static void launch_stage1(void *stream, const gecm_modconst *mc, const uint32_t 
 {
     if (lanes == 8)
         hipLaunchKernelGGL(k_stage1_quad<GECM_NL>, dim3((unsigned)(stride / 32)), dim3(256), 0, (hipStream_t)stream, tape,
-                           tape_len, X, Z, S, stride, modq, mc->rho);   // stride: a multiple of 64
+                           tape_len, X, Z, S, stride, modq, mc->m.rho);   // stride: a multiple of 64
     else if (form == 2) {
         if constexpr (FPolicy<GECM_NL>::NF >= 3) launch_stage1_mod<ModC<GECM_NL>>(stream, mc, tape, tape_len, X, Z, S, stride, lanes);
     } else if (form > 0) launch_stage1_mod<ModF<GECM_NL>>(stream, mc, tape, tape_len, X, Z, S, stride, lanes);
@@ -1029,7 +1031,7 @@ static void launch_l0(void *stream, const gecm_modconst *mc, int op, const uint3
     Fe<GECM_NL> f;
     for (int i = 0; i < GECM_NL; i++) f.v[i] = fix[i];
     hipLaunchKernelGGL(k_l0<GECM_NL>, dim3((unsigned)(stride / 64)), dim3(64), 0, (hipStream_t)stream, op, A, B, C,
-                       D, stride, mod_args<ModArgs<GECM_NL>>(mc), f);
+                       D, stride, mod_args<ModArgs<GECM_NL>>(&mc->m), f);
 }
 
 static void launch_l0_inv(void *stream, const gecm_modconst *mc, const uint32_t *A, uint32_t *C, uint32_t *G, size_t stride,
@@ -1038,7 +1040,7 @@ static void launch_l0_inv(void *stream, const gecm_modconst *mc, const uint32_t 
     Fe<GECM_NL> f;
     for (int i = 0; i < GECM_NL; i++) f.v[i] = fix[i];
     hipLaunchKernelGGL(k_l0_inv<GECM_NL>, dim3((unsigned)(stride / 64)), dim3(64), 0, (hipStream_t)stream, A, C, G, stride,
-                       s2_const(mc), f);
+                       s2_const(&mc->m), f);
 }
 
 static void launch_gcd_scan(void *stream, const gecm_modconst *mc, const uint32_t *V, uint32_t *G, uint32_t *flags,
@@ -1061,9 +1063,9 @@ static void launch_normalize(void *stream, const gecm_modconst *mc, uint32_t *X,
                                        GECM_LANE(k_normalize_lane), X, Z, flags, stride);
 }
 
-static void pack_group(const gecm_modconst *mc, void *out)
+static void pack_group(const gecm_devmod *m, void *out)
 {
-    const GroupConst<GECM_NL> c = {s2_const(mc), r2_const(mc)};
+    const GroupConst<GECM_NL> c = {s2_const(m), r2_const(m)};
     memcpy(out, &c, sizeof c);
 }
 

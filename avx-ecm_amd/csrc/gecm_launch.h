@@ -4,6 +4,7 @@
 #define GECM_LAUNCH_H
 #include <stddef.h>
 #include <stdint.h>
+#include "gecm_ops.h"
 
 /* limb counts built into the library; keep in sync with the Makefile's NLS */
 #ifdef GECM_DEV_NL15
@@ -15,19 +16,18 @@
 /* Where the kernels of a launch find the constants of their modulus.  The device layer says it (modconst() in
  * gecm_dev.hip); the launchers pick the kernel by it in one place (launch_by_source in gecm_kernels.hip). */
 enum gecm_source {
-    GECM_SRC_VALUE = 0, /* single modulus: n, kp, one, r3, rho, inv_iters (and r2) below, passed as kernel arguments */
+    GECM_SRC_VALUE = 0, /* single modulus: the record m below, passed as kernel arguments */
     GECM_SRC_WAVE,      /* one modulus per 64-curve block: groups and block_group, the _multi kernels */
     GECM_SRC_LANE       /* one modulus per curve position: groups and curve_group, the _lane kernels of
                          * stage1 (one lane per curve), from_mont, to_mont, gcd_scan, normalize, s2_init and s2_pair
                          * (limb counts with gecm_kernels_p1::has_lane) */
 };
 
+/* the constants of a launch: the context's own modulus, and where the kernels are to take theirs from */
 typedef struct {
-    const uint32_t *n, *kp, *one, *r3;
-    uint32_t rho, inv_iters;
+    gecm_devmod m;               /* host memory; m.r3 NULL on a context that never inverts */
     const void *groups;          /* WAVE, LANE: device array of the moduli's constants (pack_group), else NULL */
     const uint32_t *block_group; /* WAVE: the modulus of every 64-curve block (device array), else NULL */
-    const uint32_t *r2;          /* R^2 mod N: to_mont and build of a single-modulus launch, and pack_group */
     const uint32_t *curve_group; /* LANE: the modulus of every curve position (device array), else NULL */
     enum gecm_source source;
 } gecm_modconst;
@@ -97,7 +97,7 @@ struct gecm_kernels_p1 {
     void (*canon)(void *stream, const gecm_modconst *mc, uint32_t *X, uint32_t *Z, size_t stride);
     void (*from_mont)(void *stream, const gecm_modconst *mc, const uint32_t *X, const uint32_t *Z, uint32_t *ox,
                       uint32_t *oz, size_t stride);
-    /* the inverse: canonical plain residues ix, iz in [0, N) -> canonical Montgomery form in X, Z (needs mc->r2) */
+    /* the inverse: canonical plain residues ix, iz in [0, N) -> canonical Montgomery form in X, Z (needs mc->m.r2) */
     void (*to_mont)(void *stream, const gecm_modconst *mc, const uint32_t *ix, const uint32_t *iz, uint32_t *X,
                     uint32_t *Z, size_t stride);
     void (*l0)(void *stream, const gecm_modconst *mc, int op, const uint32_t *A, const uint32_t *B, uint32_t *C,
@@ -108,19 +108,19 @@ struct gecm_kernels_p1 {
     void (*gcd_scan)(void *stream, const gecm_modconst *mc, const uint32_t *V, uint32_t *G, uint32_t *flags,
                      size_t stride);
     /* the Suyama construction on the device: sigma[stride] (64-bit, device memory) -> X, Z, S of the batch, canonical, and
-     * flags[curve] = 1 where a denominator had no inverse (needs mc->r3, inv_iters and r2; a multi-modulus mc takes every
+     * flags[curve] = 1 where a denominator had no inverse (needs mc->m.r3; a multi-modulus mc takes every
      * block's from its group constants) */
     void (*build)(void *stream, const gecm_modconst *mc, const uint64_t *sigma, uint32_t *X, uint32_t *Z, uint32_t *S,
                   uint32_t *flags, size_t stride);
     int fform_generic_limbs;      /* limbs of a 2^k -+ c modulus that are not 2^28 - 1 */
-    /* one modulus's constants (n, kp, one, r3, rho, inv_iters, r2 of mc) as the multi-modulus kernels read them from device
-     * memory: group_bytes bytes at out */
-    void (*pack_group)(const gecm_modconst *mc, void *out);
+    /* one modulus's constants (r3 included) as the multi-modulus kernels read them from device memory: group_bytes bytes
+     * at out */
+    void (*pack_group)(const gecm_devmod *m, void *out);
     size_t group_bytes;
     const char *manifest;         /* the hash of the sources the object was compiled from (Makefile: K_SHA) */
     int has_lane;                 /* the per-lane kernels are built for this limb count (8 .. 15 limbs) */
     /* X <- X/Z, Z <- R mod N for every curve whose Z has an inverse, canonical; flags[curve] = 1 and X, Z untouched
-     * where it has none (needs mc->r3 and inv_iters; multi-modulus and lane-packed mc as for gcd_scan).  Last member:
+     * where it has none (needs mc->m.r3; multi-modulus and lane-packed mc as for gcd_scan).  Last member:
      * the ones above keep their places. */
     void (*normalize)(void *stream, const gecm_modconst *mc, uint32_t *X, uint32_t *Z, uint32_t *flags, size_t stride);
 };

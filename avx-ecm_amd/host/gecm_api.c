@@ -127,7 +127,6 @@ struct gecm_ctx {
         int k, sign;         /* Mw = 2^k - c for sign > 0 (c = 1: Mersenne form), 2^k + 1 for sign < 0 */
         uint64_t c;
         int nl;              /* limbs of Mw */
-        uint32_t *n28;       /* constants block, nl limbs each: Mw, kp, one = R mod Mw, R^2 mod Mw (R = 2^(28 nl)) */
         int on;              /* gecm_set_special_form */
         int loaded;          /* the twin holds the main context's points (twin_fill) */
         int pending;         /* a launch ran on the twin and its X, Z are not back in the main context (ff_settle) */
@@ -140,7 +139,7 @@ struct gecm_ctx {
     int multi;
     size_t ngroups;
     gecm_mod *grp;
-    uint32_t *gconst;        /* the moduli's n, kp, one, r3, r2 ([5][ngroups][nl]), then rho and inv_iters [ngroups] each */
+    gecm_devmod *grp_dev;    /* grp[]'s constants as the device layer takes them (gecm_dev_set_groups) */
     size_t nuser;            /* curves the caller built */
     uint32_t *slot;          /* caller's curve -> device position */
     uint32_t *pos_user;      /* device position -> caller's curve, GECM_PAD for padding */
@@ -244,6 +243,7 @@ static void ff_setup(gecm_ctx *c)
     else mpl_add(&M, &M, &one);
     mpl_mod(&r, &M, &c->mod.N);
     if (!mpl_is_zero(&r)) return;                                    /* N | Mw, or nothing below holds */
+    /* the constants block, nlf limbs each: Mw, kp, one = R mod Mw, R^2 mod Mw (R = 2^(28 nlf)); the twin never inverts */
     uint32_t *q = (uint32_t *)calloc((size_t)nlf * 4, sizeof(uint32_t));
     if (!q) return;
     gecm_mod_pow2(&r, (unsigned)(LIMB_BITS * nlf), &M);
@@ -260,13 +260,14 @@ static void ff_setup(gecm_ctx *c)
         mpl_sub(&inv, &two28, &inv);
         rho = (uint32_t)mpl_get_u64(&inv);
     }
-    if (gecm_mod_make_kp(q + nlf, &M, nlf) || gecm_dev_open(&c->twin.dev, c->device, nlf, q, q + nlf, q + 2 * nlf, rho)) {
-        free(q);
+    const gecm_devmod dm = {q, q + nlf, q + 2 * nlf, q + 3 * nlf, NULL, rho, 0};
+    const int failed = gecm_mod_make_kp(q + nlf, &M, nlf) || gecm_dev_open(&c->twin.dev, c->device, nlf, &dm, 0);
+    free(q);                                                         /* the device layer has its copy */
+    if (failed) {
         c->twin.dev = NULL;
         return;
     }
     gecm_dev_set_fform(c->twin.dev, f.form);
-    c->twin.n28 = q;
     c->twin.k = f.k;
     c->twin.sign = f.form < 0 ? -1 : 1;
     c->twin.c = f.form == 2 ? f.c : 1;
@@ -281,7 +282,7 @@ static void ff_setup(gecm_ctx *c)
 static int twin_fill(gecm_ctx *c)
 {
     if (!c->twin.dev) return 0;
-    const int rc = gecm_dev_fill_twin(c->twin.dev, c->dev, c->twin.n28 + 3 * c->twin.nl);
+    const int rc = gecm_dev_fill_twin(c->twin.dev, c->dev);
     c->twin.loaded = !rc;
     return rc;
 }
@@ -371,14 +372,13 @@ int gecm_create(gecm_ctx **out, int device, const char *n_str, int digitbits)
     int rc = gecm_mod_setup(&c->mod, "gecm_create", n_str, digitbits, 0, pick_nl);
     if (rc) { free(c); return rc; }
     c->device = device;
-    if (gecm_dev_open(&c->dev, device, c->mod.nl, c->mod.n28, c->mod.kp28, c->mod.one28, c->mod.rho28)) {
+    const gecm_devmod dm = gecm_mod_devmod(&c->mod);
+    if (gecm_dev_open(&c->dev, device, c->mod.nl, &dm, 0)) {
         set_err("gecm_create: %s", gecm_dev_error());
         gecm_mod_free(&c->mod);
         free(c);
         return GECM_ERR_DEVICE;
     }
-    gecm_dev_set_s2const(c->dev, c->mod.r3_28, c->mod.inv_iters);
-    gecm_dev_set_r2(c->dev, gecm_mod_r2(&c->mod));
     row_setup(c);
     ff_setup(c);
     *out = c;
@@ -425,7 +425,6 @@ void gecm_destroy(gecm_ctx *c)
     gecm_dev_close(c->dev);
     gecm_dev_close(c->dev_l0);
     gecm_dev_close(c->twin.dev);
-    free(c->twin.n28);
     if (c->pf_active) { pthread_join(c->pf_thread, NULL); c->pf_active = 0; gecm_tape_free(&c->pf_tape); }
     gecm_tape_free(&c->tape);
     free_batch(c);
@@ -435,7 +434,7 @@ void gecm_destroy(gecm_ctx *c)
     gecm_mod_free(&c->mod);
     for (size_t g = 0; g < c->ngroups; g++) gecm_mod_free(&c->grp[g]);
     free(c->grp);
-    free(c->gconst);
+    free(c->grp_dev);
     free(c);
 }
 
@@ -531,15 +530,21 @@ int gecm_get_one(const gecm_ctx *c, void *one_limbs)
 }
 
 /* ---- L0 ------------------------------------------------------------------------------------ */
+/* the L0 operators' own device context, opened by the first of them */
+static int l0_open(gecm_ctx *c)
+{
+    if (c->dev_l0) return GECM_OK;
+    const gecm_devmod dm = gecm_mod_devmod(&c->mod);
+    if (!gecm_dev_open(&c->dev_l0, c->device, c->mod.nl, &dm, 0)) return GECM_OK;
+    set_err("L0: %s", gecm_dev_error());
+    return GECM_ERR_DEVICE;
+}
+
 static int l0_call(gecm_ctx *c, int op, const void *a, const void *b, void *r0, void *r1, size_t batch)
 {
     if (c && c->multi) return multi_refuse("the L0 operators");
     if (!c || !a || !r0 || batch == 0) { set_err("L0: bad argument"); return GECM_ERR_ARG; }
-    if (!c->dev_l0 &&
-        gecm_dev_open(&c->dev_l0, c->device, c->mod.nl, c->mod.n28, c->mod.kp28, c->mod.one28, c->mod.rho28)) {
-        set_err("L0: %s", gecm_dev_error());
-        return GECM_ERR_DEVICE;
-    }
+    if (l0_open(c)) return GECM_ERR_DEVICE;
     int nl = c->mod.nl;
     size_t words = (size_t)nl * batch;
     uint32_t *ha = (uint32_t *)malloc(words * 4 * 4);
@@ -597,12 +602,7 @@ int gecm_vecinvmod(gecm_ctx *c, const void *a, void *inv, void *gcd, size_t batc
 {
     if (c && c->multi) return multi_refuse("the L0 operators");
     if (!c || !a || !inv || !gcd || batch == 0) { set_err("L0: bad argument"); return GECM_ERR_ARG; }
-    if (!c->dev_l0 &&
-        gecm_dev_open(&c->dev_l0, c->device, c->mod.nl, c->mod.n28, c->mod.kp28, c->mod.one28, c->mod.rho28)) {
-        set_err("L0: %s", gecm_dev_error());
-        return GECM_ERR_DEVICE;
-    }
-    gecm_dev_set_s2const(c->dev_l0, c->mod.r3_28, c->mod.inv_iters);
+    if (l0_open(c)) return GECM_ERR_DEVICE;
     int nl = c->mod.nl;
     size_t words = (size_t)nl * batch;
     uint32_t *ha = (uint32_t *)malloc(words * 4 * 3);
@@ -687,7 +687,7 @@ static int build_single(gecm_ctx *c, const uint64_t *sigma, size_t batch, const 
         free(hX);
     }
     if (built < 0) { free_batch(c); return built; }
-    if ((px && gecm_dev_upload_plain(c->dev, px, pz, gecm_mod_r2(&c->mod))) || twin_fill(c)) {
+    if ((px && gecm_dev_upload_plain(c->dev, px, pz)) || twin_fill(c)) {
         set_err("%s", gecm_dev_error());
         free_batch(c);
         return GECM_ERR_DEVICE;
@@ -1611,26 +1611,18 @@ int gecm_create_multi(gecm_ctx **out, int device, const char *const *n_strs, siz
     /* the context itself: the largest N (what gecm_get_config reports) and the device */
     if (!rc) rc = gecm_mod_setup(&c->mod, "gecm_create_multi", n_strs[largest], digitbits, nl, pick_nl);
     if (!rc) {
-        c->gconst = (uint32_t *)calloc((size_t)5 * count * nl + 2 * count, sizeof(uint32_t));
-        if (!c->gconst) rc = GECM_ERR_NOMEM;
+        c->grp_dev = (gecm_devmod *)calloc(count, sizeof *c->grp_dev);
+        if (!c->grp_dev) rc = GECM_ERR_NOMEM;
     }
     if (!rc) {
-        uint32_t *rho = c->gconst + (size_t)5 * count * nl, *iters = rho + count;
-        for (size_t g = 0; g < count; g++) {
-            for (int q = 0; q < 5; q++)        /* n, kp, one, r3, r2 */
-                memcpy(c->gconst + ((size_t)q * count + g) * nl,
-                       q < 3 ? grp[g].n28 + (size_t)q * nl : q == 3 ? grp[g].r3_28 : gecm_mod_r2(&grp[g]), (size_t)nl * sizeof(uint32_t));
-            rho[g] = grp[g].rho28;
-            iters[g] = grp[g].inv_iters;
-        }
-        if (gecm_dev_open(&c->dev, device, nl, c->mod.n28, c->mod.kp28, c->mod.one28, c->mod.rho28)) {
+        for (size_t g = 0; g < count; g++) c->grp_dev[g] = gecm_mod_devmod(&grp[g]);
+        const gecm_devmod dm = gecm_mod_devmod(&c->mod);
+        if (gecm_dev_open(&c->dev, device, nl, &dm, 1)) {
             set_err("gecm_create_multi: %s", gecm_dev_error());
             rc = GECM_ERR_DEVICE;
         }
     }
     if (rc) { gecm_destroy(c); return rc; }
-    gecm_dev_set_multi(c->dev);
-    gecm_dev_set_s2const(c->dev, c->mod.r3_28, c->mod.inv_iters);
     *out = c;
     return GECM_OK;
 }
@@ -1712,10 +1704,12 @@ static int build_multi(gecm_ctx *c, const char *who, const uint64_t *sigma, cons
     for (size_t g = 0, off = 0; g < ng; g++) { goff[g] = off; off += GROUP_SPAN(g); }
     int rc = alloc_batch(c, total);
     uint32_t *slot = (uint32_t *)malloc(batch * sizeof(uint32_t)), *pos_user = (uint32_t *)malloc(total * sizeof(uint32_t));
-    uint32_t *pos_grp = (uint32_t *)malloc(total * sizeof(uint32_t)), *blocks = (uint32_t *)malloc(total / 64 * sizeof(uint32_t));
+    uint32_t *pos_grp = (uint32_t *)malloc(total * sizeof(uint32_t));
+    /* wave packing: the modulus of every 64-curve block, which the kernels read there (lane packing: pos_grp) */
+    uint32_t *blocks = lane ? NULL : (uint32_t *)malloc(total / 64 * sizeof(uint32_t));
     const size_t words = (size_t)c->mod.nl * total;
     uint32_t *hX = (uint32_t *)calloc(words * 3, 4);           /* padding stays zero: computed, never read */
-    if (!rc && (!slot || !pos_user || !pos_grp || !blocks || !hX)) rc = GECM_ERR_NOMEM;
+    if (!rc && (!slot || !pos_user || !pos_grp || (!lane && !blocks) || !hX)) rc = GECM_ERR_NOMEM;
     if (rc) {
         free(cnt); free(goff); free(slot); free(pos_user); free(pos_grp); free(blocks); free(hX);
         free_batch(c);
@@ -1725,7 +1719,6 @@ static int build_multi(gecm_ctx *c, const char *who, const uint64_t *sigma, cons
     for (size_t p = 0; lane && p < total; p++) {
         pos_grp[p] = 0;
         pos_user[p] = GECM_PAD;
-        blocks[p / 64] = 0;                                     /* unused: the kernels read pos_grp */
     }
     for (size_t g = 0; g < ng; g++)
         for (size_t p = goff[g]; p < goff[g] + GROUP_SPAN(g); p++) {
@@ -1755,13 +1748,7 @@ static int build_multi(gecm_ctx *c, const char *who, const uint64_t *sigma, cons
     free(goff);
     free(cnt);
     if (!rc && !on_device && gecm_dev_upload(c->dev, hX, hX + words, hX + 2 * words)) rc = GECM_ERR_DEVICE;
-    if (!rc) {
-        const uint32_t *q = c->gconst;
-        const size_t w = ng * (size_t)c->mod.nl;
-        if (gecm_dev_set_groups(c->dev, (uint32_t)ng, q, q + w, q + 2 * w, q + 3 * w, q + 5 * w, q + 5 * w + ng, q + 4 * w, blocks))
-            rc = GECM_ERR_DEVICE;
-    }
-    if (!rc && gecm_dev_set_curve_groups(c->dev, (uint32_t)ng, lane ? pos_grp : NULL)) rc = GECM_ERR_DEVICE;
+    if (!rc && gecm_dev_set_groups(c->dev, (uint32_t)ng, c->grp_dev, blocks, lane ? pos_grp : NULL)) rc = GECM_ERR_DEVICE;
     if (!rc && on_device) {              /* the kernel takes every block's modulus from the groups just set */
         const int built = build_on_device(c, c->sigma, total, pos_user);
         if (built < 0) {
@@ -1782,7 +1769,7 @@ static int build_multi(gecm_ctx *c, const char *who, const uint64_t *sigma, cons
                 dz[l * total + p] = uz[l * batch + i];
             }
         }
-        if (gecm_dev_upload_plain(c->dev, dx, dz, NULL)) rc = GECM_ERR_DEVICE;   /* NULL: every curve's own R^2 */
+        if (gecm_dev_upload_plain(c->dev, dx, dz)) rc = GECM_ERR_DEVICE;
     }
     free(hX);
     free(blocks);

@@ -106,7 +106,7 @@ int gecm_mod_setup(gecm_mod *m, const char *who, const char *n_str, int digitbit
     mpl_to_limbs32(m->finv28, 1, nl, LIMB_BITS, &t);
     /* R^2 mod N: one Montgomery multiply by it takes a plain residue x to x R (csrc/gecm_kernels.hip: k_to_mont) */
     mpl_mulmod(&t, &m->rint_mod_n, &m->rint_mod_n, &m->N);
-    mpl_to_limbs32(gecm_mod_r2(m), 1, nl, LIMB_BITS, &t);
+    mpl_to_limbs32(m->finv28 + nl, 1, nl, LIMB_BITS, &t);
     /* batches of 28 division steps after which the device inversion has converged for a modulus of nbits bits:
      * the bound of the "half-delta" variant, floor((45907 bits + 26313) / 19929), +1, rounded up to whole batches */
     m->inv_iters = (uint32_t)((((45907ull * (unsigned)m->nbits + 26313ull) / 19929ull + 1) + 27) / 28);
@@ -115,8 +115,14 @@ int gecm_mod_setup(gecm_mod *m, const char *who, const char *n_str, int digitbit
 
 void gecm_mod_free(gecm_mod *m)
 {
-    free(m->n28);                          /* kp28 .. finv28 and gecm_mod_r2 are parts of it */
+    free(m->n28);                          /* kp28 .. finv28 and R^2 mod N are parts of it */
     m->n28 = NULL;
+}
+
+gecm_devmod gecm_mod_devmod(const gecm_mod *m)
+{
+    const gecm_devmod d = {m->n28, m->kp28, m->one28, m->finv28 + m->nl, m->r3_28, m->rho28, m->inv_iters};
+    return d;
 }
 
 /* Suyama curve for one sigma up to (but not including) the two modular inversions

@@ -4,6 +4,7 @@
 #ifndef GECM_MOD_H
 #define GECM_MOD_H
 #include "mpl.h"
+#include "../csrc/gecm_ops.h"
 
 #define LIMB_BITS 28
 
@@ -23,9 +24,10 @@ typedef struct {
     uint32_t *finv28;    /* Rref^2/Rint mod N (see gecm_vecinvmod) */
     uint32_t inv_iters;  /* batches of 28 division steps after which the device inversion has converged for N */
 } gecm_mod;
-/* Rint^2 mod N, nl limbs: plain residue -> Montgomery form on the device (gecm_resume_points).  The last part of the
- * n28 block, after finv28, without a pointer of its own: tests/test_inverse_model_cpu.py mirrors the struct as it is. */
-static inline uint32_t *gecm_mod_r2(const gecm_mod *m) { return m->finv28 + m->nl; }
+/* The constants of N as the device layer takes them (csrc/gecm_ops.h), pointing into the n28 block: valid as long as m.
+ * Its r2 = Rint^2 mod N (plain residue -> Montgomery form on the device) is the block's last part, after finv28, and
+ * has no pointer of its own in the struct: tests/test_inverse_model_cpu.py mirrors the struct as it is. */
+gecm_devmod gecm_mod_devmod(const gecm_mod *m);
 
 /* the calling thread's error text (gecm_last_error) */
 extern __thread char gecm_mod_err[512];
