@@ -55,6 +55,12 @@ int gecm_dev_download_s(gecm_dev *d, uint32_t *S);
  * limb count), into dst's with dst's own R^2 mod Mw.  Synchronous. */
 int gecm_dev_build(gecm_dev *d, const uint64_t *sigma, size_t count, uint32_t *flags);
 float gecm_dev_last_build_ms(gecm_dev *d);
+/* gecm_dev_build for a batch with a parametrisation per curve (param[i] = 0, 1 or 3, the padding of a
+ * multi-modulus batch 0): k_build over the batch as gecm_dev_build launches it whenever some param[i] is 0 — the other
+ * lanes compute a Suyama curve nobody reads — then k_build_param, which overwrites X, Z, S and the flag (with 0) of the
+ * lanes whose parameter is not 0.  Without a 0 among param the first kernel is skipped (and does not need r3), the
+ * planes are cleared first.  gecm_dev_last_build_ms is the sum of the kernels launched. */
+int gecm_dev_build_param(gecm_dev *d, const uint64_t *sigma, const uint8_t *param, size_t count, uint32_t *flags);
 int gecm_dev_fill_twin(gecm_dev *dst, gecm_dev *src);
 /* X <- X/Z, Z <- R mod N in the batch planes (canonical), for every curve whose Z has an inverse; the others keep both
  * and get flags[i] = 1 (count = the batch's curves, padding included as for gecm_dev_build).  Inverts.

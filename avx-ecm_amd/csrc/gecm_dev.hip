@@ -110,6 +110,8 @@ struct gecm_dev {
     // curve construction on the device (gecm_dev_build)
     uint64_t *dSigma = nullptr;
     size_t sigma_cap = 0;
+    uint8_t *dParam = nullptr;        // the parametrisation of every curve position (gecm_dev_build_param)
+    size_t param_cap = 0;
     float build_ms = 0.f;
 };
 
@@ -281,6 +283,7 @@ extern "C" void gecm_dev_close(gecm_dev *d)
     (void)hipFree(d->dBlockGroup);
     (void)hipFree(d->dCurveGroup);
     (void)hipFree(d->dSigma);
+    (void)hipFree(d->dParam);
     if (d->ev0) (void)hipEventDestroy(d->ev0);
     if (d->ev1) (void)hipEventDestroy(d->ev1);
     if (d->stream) (void)hipStreamDestroy(d->stream);
@@ -417,6 +420,52 @@ extern "C" int gecm_dev_build(gecm_dev *d, const uint64_t *sigma, size_t count, 
     gecm_modconst mc = modconst(d);
     HIPCHK(hipEventRecord(d->ev0, d->stream));
     d->k1->build(d->stream, &mc, d->dSigma, d->dX, d->dZ, d->dS, d->dFlags, d->stride);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(d->ev1, d->stream));
+    HIPCHK(hipMemcpyAsync(flags, d->dFlags, count * 4, hipMemcpyDeviceToHost, d->stream));
+    HIPCHK(hipStreamSynchronize(d->stream));
+    HIPCHK(hipEventElapsedTime(&d->build_ms, d->ev0, d->ev1));
+    d->timed = false;
+    return 0;
+}
+
+extern "C" int gecm_dev_build_param(gecm_dev *d, const uint64_t *sigma, const uint8_t *param, size_t count, uint32_t *flags)
+{
+    HIPCHK(hipSetDevice(d->device));
+    if (!d->stride || count != d->ncurves || !sigma || !param || !flags) {
+        g_err = "gecm_dev_build_param: no batch of that many curves (gecm_dev_resize)";
+        return -2;
+    }
+    bool suyama = false, other = false;
+    for (size_t i = 0; i < count; i++) {
+        if (param[i] != 0 && param[i] != 1 && param[i] != 3) {
+            g_err = "gecm_dev_build_param: a parametrisation other than 0, 1 and 3";
+            return -2;
+        }
+        (param[i] ? other : suyama) = true;
+    }
+    if (ready(d, "gecm_dev_build_param", suyama)) return -2;
+    if (grow(&d->dSigma, &d->sigma_cap, d->stride) || grow(&d->dFlags, &d->flags_cap, d->stride) ||
+        grow(&d->dParam, &d->param_cap, d->stride))
+        return -1;
+    // the padding lanes: sigma = 0 with parameter 0, computed by k_build (if it runs), never flagged or read
+    HIPCHK(hipMemsetAsync(d->dSigma, 0, d->stride * sizeof(uint64_t), d->stream));
+    HIPCHK(hipMemcpyAsync(d->dSigma, sigma, count * sizeof(uint64_t), hipMemcpyHostToDevice, d->stream));
+    HIPCHK(hipMemsetAsync(d->dParam, 0, d->stride, d->stream));
+    HIPCHK(hipMemcpyAsync(d->dParam, param, count, hipMemcpyHostToDevice, d->stream));
+    if (!suyama) {
+        // no k_build: what it would have written in the lanes k_build_param leaves alone is cleared instead
+        const size_t plane = (size_t)d->nl * d->stride * sizeof(uint32_t);
+        HIPCHK(hipMemsetAsync(d->dX, 0, plane, d->stream));
+        HIPCHK(hipMemsetAsync(d->dZ, 0, plane, d->stream));
+        HIPCHK(hipMemsetAsync(d->dS, 0, plane, d->stream));
+        HIPCHK(hipMemsetAsync(d->dFlags, 0, d->stride * sizeof(uint32_t), d->stream));
+    }
+    gecm_modconst mc = modconst(d);
+    HIPCHK(hipEventRecord(d->ev0, d->stream));
+    if (suyama) d->k1->build(d->stream, &mc, d->dSigma, d->dX, d->dZ, d->dS, d->dFlags, d->stride);
+    HIPCHK(hipGetLastError());
+    if (other) d->k1->build_param(d->stream, &mc, d->dSigma, d->dParam, d->dX, d->dZ, d->dS, d->dFlags, d->stride);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(d->ev1, d->stream));
     HIPCHK(hipMemcpyAsync(flags, d->dFlags, count * 4, hipMemcpyDeviceToHost, d->stream));

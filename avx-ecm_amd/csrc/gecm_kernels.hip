@@ -618,6 +618,70 @@ k_build_multi(const uint64_t *__restrict__ sigma, uint32_t *__restrict__ X, uint
 }
 #undef GECM_BUILD_BODY
 
+// GMP-ECM's PARAM 1 and PARAM 3 curves: B y^2 = x^3 + A x^2 + x with (A+2)/4 = d and the start point
+// (2 : 1), d = sigma^2 / 2^64 (PARAM 1) or sigma / 2^32 (PARAM 3) modulo N.  One curve per lane; a lane whose parameter is
+// 0 (a Suyama curve of a mixed batch, which k_build has made, or padding) stores nothing.  No inversion: the division is
+// one Montgomery multiply a b / R with b = R / 2^w = 2^(28 NL - w), a single bit of a single limb — limb NL - 3, bit 20
+// for w = 64 and limb NL - 2, bit 24 for w = 32 — which lies below 2^(28 NL - 5) <= K and so is an operand as it stands,
+// like sigma's own three limbs and the small constants of build_curve.  sigma R and sigma^2 R are products (< 0.675 K);
+// S and X = 2 R leave through the multiply by R mod N and one conditional subtraction, the tail of k_build; Z = R mod N.
+// The out-of-line multiplies (ModKOut), as in k_build: five of them, once per batch.
+template <int NL>
+__device__ __forceinline__ void fe_param_shift(Fe<NL> &r, uint32_t prm)
+{
+#pragma unroll
+    for (int i = 0; i < NL; i++)
+        r.v[i] = (i == NL - 3 && prm == 1u) ? 1u << 20 : (i == NL - 2 && prm != 1u) ? 1u << 24 : 0u;
+}
+
+#define GECM_BUILD_PARAM_BODY                                                   \
+    const uint32_t idx = blockIdx.x * 64u + threadIdx.x;                        \
+    const uint32_t prm = param[idx];                                            \
+    if (prm != 0) {                                                             \
+        static_assert(NL >= 3, "sigma takes three limbs");                      \
+        const ModKOut<NL> mm{k.m};                                              \
+        const uint64_t sg = sigma[idx];                                         \
+        Fe<NL> t, w;                                                            \
+        fe_small(t, (uint32_t)sg & GECM_LIMB_MASK);                             \
+        t.v[1] = (uint32_t)(sg >> GECM_LIMB_BITS) & GECM_LIMB_MASK;             \
+        t.v[2] = (uint32_t)(sg >> (2 * GECM_LIMB_BITS));                        \
+        fe_mul(w, t, r2, mm);                         /* sigma R */             \
+        if (prm == 1) fe_sqr(w, w, mm);               /* sigma^2 R */           \
+        fe_param_shift(t, prm);                       /* R / 2^w */             \
+        fe_mul(w, w, t, mm);                          /* d R */                 \
+        fe_mul(w, w, k.one, mm);                                                \
+        fe_cond_sub_n(w, k.m);                                                  \
+        fe_store(S, stride, idx, w);                                            \
+        fe_small(t, 2u);                                                        \
+        fe_mul(t, t, r2, mm);                                                   \
+        fe_mul(t, t, k.one, mm);                                                \
+        fe_cond_sub_n(t, k.m);                                                  \
+        fe_store(X, stride, idx, t);                                            \
+        fe_store(Z, stride, idx, k.one);                                        \
+        flags[idx] = 0u;                                                        \
+    }
+
+template <int NL>
+__global__ void __launch_bounds__(64, 2)
+k_build_param(const uint64_t *__restrict__ sigma, const uint8_t *__restrict__ param, uint32_t *__restrict__ X,
+              uint32_t *__restrict__ Z, uint32_t *__restrict__ S, uint32_t *__restrict__ flags, size_t stride, ModArgs<NL> k,
+              Fe<NL> r2)
+{
+    GECM_ARG_CONSTS
+    GECM_BUILD_PARAM_BODY
+}
+
+template <int NL>
+__global__ void __launch_bounds__(64, 2)
+k_build_param_multi(const uint64_t *__restrict__ sigma, const uint8_t *__restrict__ param, uint32_t *__restrict__ X,
+                    uint32_t *__restrict__ Z, uint32_t *__restrict__ S, uint32_t *__restrict__ flags, size_t stride,
+                    ModGroups<NL> g)
+{
+    GECM_WAVE_CONSTS(ModArgs<NL>, blockIdx.x)
+    GECM_BUILD_PARAM_BODY
+}
+#undef GECM_BUILD_PARAM_BODY
+
 // ---------------------------------------------------------------- normalisation
 // X <- X/Z, Z <- 1 for one curve per lane: the canonical x = X/Z mod N a standard save line holds.  X, Z come in
 // canonical (every stage-1 kernel and every upload leaves them so).  z R goes through build_invert — the multiply by R
@@ -1063,6 +1127,13 @@ static void launch_normalize(void *stream, const gecm_modconst *mc, uint32_t *X,
                                        GECM_LANE(k_normalize_lane), X, Z, flags, stride);
 }
 
+static void launch_build_param(void *stream, const gecm_modconst *mc, const uint64_t *sigma, const uint8_t *param, uint32_t *X,
+                               uint32_t *Z, uint32_t *S, uint32_t *flags, size_t stride)
+{
+    launch_by_source<ModArgs<GECM_NL>, Fe<GECM_NL>>(stream, mc, blocks_of(stride), k_build_param<GECM_NL>,
+                                                    k_build_param_multi<GECM_NL>, nullptr, sigma, param, X, Z, S, flags, stride);
+}
+
 static void pack_group(const gecm_devmod *m, void *out)
 {
     const GroupConst<GECM_NL> c = {s2_const(m), r2_const(m)};
@@ -1073,7 +1144,7 @@ extern "C" const gecm_kernels_p1 *CAT(CAT(gecm_kernels_, GECM_NL), _p1)(void)
 {
     static const gecm_kernels_p1 t = {launch_stage1, launch_canon, launch_from_mont, launch_to_mont, launch_l0, launch_l0_inv,
                                       launch_gcd_scan, launch_build, FPolicy<GECM_NL>::G, pack_group, sizeof(GroupConst<GECM_NL>),
-                                      GECM_MANIFEST, GECM_HAS_LANE, launch_normalize};
+                                      GECM_MANIFEST, GECM_HAS_LANE, launch_normalize, launch_build_param};
     return &t;
 }
 #endif

@@ -120,9 +120,14 @@ struct gecm_kernels_p1 {
     const char *manifest;         /* the hash of the sources the object was compiled from (Makefile: K_SHA) */
     int has_lane;                 /* the per-lane kernels are built for this limb count (8 .. 15 limbs) */
     /* X <- X/Z, Z <- R mod N for every curve whose Z has an inverse, canonical; flags[curve] = 1 and X, Z untouched
-     * where it has none (needs mc->m.r3; multi-modulus and lane-packed mc as for gcd_scan).  Last member:
-     * the ones above keep their places. */
+     * where it has none (needs mc->m.r3; multi-modulus and lane-packed mc as for gcd_scan).  New members go at the
+     * end: the ones above keep their places. */
     void (*normalize)(void *stream, const gecm_modconst *mc, uint32_t *X, uint32_t *Z, uint32_t *flags, size_t stride);
+    /* GMP-ECM's PARAM 1 and 3 curves: for every curve with param[curve] = 1 or 3 (device array of
+     * stride bytes), X = 2, Z = 1, S = sigma^2 / 2^64 or sigma / 2^32 in canonical Montgomery form and flags[curve] = 0;
+     * the curves with param 0 keep what they hold.  Needs mc->m.r2, never inverts; a multi-modulus mc as for build. */
+    void (*build_param)(void *stream, const gecm_modconst *mc, const uint64_t *sigma, const uint8_t *param, uint32_t *X,
+                        uint32_t *Z, uint32_t *S, uint32_t *flags, size_t stride);
 };
 
 /* Part 2: stage 2 (any mc takes K = 1, 2, .. 32; a lane-packed one at limb counts with has_lane). */

@@ -4,6 +4,8 @@
  *     avx-ecm -f FILE curves B1 [threads] [B2] [sigma]      (a list of inputs, run_file)
  *     avx-ecm -r FILE B1 [B2]                               (go on from resume lines, run_resume)
  *     avx-ecm -x FILE B1 [B2]                               (take resume lines to a higher B1, run_resume)
+ *     avx-ecm -g -r FILE B1 [B2],  avx-ecm -g -x FILE B1 [B2]  (the same two, lines of GMP-ECM's PARAM 1 and 3 accepted)
+ *     avx-ecm -p PARAM input curves B1 [B2] [sigma]         (a fresh run in standard mode, PARAM 0, 1 or 3, run_param)
  *
  * Same positional arguments as the reference (main.c:380-384, 459-460, 537-559) and the same FILES, byte for byte:
  * save_b1.txt (GMP-ECM resume lines, ecm.c:1372-1380), ecm_results.txt (factor lines, ecm.c:1356-1367, 1510-1522)
@@ -118,6 +120,9 @@ typedef struct {
      * (gecm_stage1_extend_segment); every line written is a normalised standard line (gecm_format_save_line_std) */
     int extend;
     uint64_t ext_from;
+    /* avx-ecm -g -r / -g -x: the lines carry their parametrisation (PARAM 0, 1, 3) into the build;
+     * avx-ecm -p: fresh curves of the parametrisation fresh_param, run as an extension from the bound 1 */
+    int with_params, fresh, fresh_param;
 } run_t;
 
 typedef struct {
@@ -167,6 +172,7 @@ typedef struct job_t {
     int progress;              /* print the launches of a long stage 1 as they finish (GPU 0 of a pass that prints live) */
     const void *rx, *rz;       /* -r: the plain residues of the part's curves (vec layout), and what stage 1 has done */
     uint64_t b1_done;
+    const uint8_t *param;      /* -g, -p: the parametrisation of the part's curves (NULL: Suyama's throughout) */
 } job_t;
 
 typedef struct {
@@ -180,6 +186,7 @@ typedef struct {
     pthread_t th;
     int threaded;              /* th is a thread to join */
     void *rx, *rz;             /* -r: the residues its one job starts from */
+    uint8_t *param;            /* -g, -p: the parametrisation of its curves */
 } pass_t;
 
 static void text_add(text_t *t, const char *s, size_t n)
@@ -294,12 +301,14 @@ static int fits_lane_packing(int nbits) { return nbits <= gecm_multi_packing_max
 /* ---- per-GPU jobs of a pass ----------------------------------------------------------------- */
 static int step_build(job_t *j)
 {
+    if (j->param && gecm_set_next_params(j->part->ctx, j->param, j->part->ncurves)) return -1;
     return gecm_build_curves(j->part->ctx, j->part->sigma, j->part->ncurves);
 }
 
 /* -r: the curves of the lines; save lines (stage 1 complete) get the factor scan a stage 1 would have ended with */
 static int step_resume(job_t *j)
 {
+    if (j->param && gecm_set_next_params(j->part->ctx, j->param, j->part->ncurves)) return -1;
     int rc = gecm_resume_points(j->part->ctx, j->part->sigma, j->rx, j->rz, j->part->ncurves, j->b1_done);
     if (rc >= 0 && j->b1_done && gecm_scan_factors(j->part->ctx, 1, NULL) < 0) rc = -1;
     return rc;
@@ -818,6 +827,7 @@ static void pass_join(pass_t *ps)
     free(ps->sigma);
     free(ps->rx);
     free(ps->rz);
+    free(ps->param);
     free(ps->log.buf);
     memset(ps, 0, sizeof *ps);
 }
@@ -865,6 +875,7 @@ static int make_contexts(gecm_ctx **ctx, int n, int devices, const char *modulus
 typedef struct {
     char *text;
     gecm_resume_rec rec;
+    int param;                 /* -g: the line's PARAM (0, 1 or 3); else 0 */
 } rline_t;
 
 typedef struct resume_t {
@@ -911,6 +922,11 @@ static int resume_pass_input(pass_t *ps, const gecm_ctx *ctx)
     ps->rz = malloc(bytes);
     if (!ps->rx || !ps->rz) { fprintf(stderr, "out of memory\n"); return -1; }
     for (size_t u = 0; u < v->ucurves; u++) ps->sigma[u] = R->res->lines[first + u].rec.sigma;
+    if (R->with_params) {
+        ps->param = (uint8_t *)malloc(v->ucurves);
+        if (!ps->param) { fprintf(stderr, "out of memory\n"); return -1; }
+        for (size_t u = 0; u < v->ucurves; u++) ps->param[u] = (uint8_t)R->res->lines[first + u].param;
+    }
     return pack_residues(&cfg, R->res->lines + first, v->ucurves, 0, v->ucurves, ps->rx, ps->rz);
 }
 
@@ -943,7 +959,13 @@ static int run_passes(run_t *R, gecm_ctx *ctx[2][MAX_GPUS], int gpus, int slots,
         for (size_t u = 0; u < v->ucurves && !R->res; u++) {
             /* fixed sigma: lane i of every thread of batch b runs sigma + 8 b + i (main.c:761, ecm.c:1187) */
             if (R->fixed_sigma) ps->sigma[u] = R->sigma0 + VECLEN * v->b0 + u;
+            else if (R->fresh && R->fresh_param) ps->sigma[u] = 2 + lcg_rand(&R->lcg) % 0xfffffffeULL;   /* -p 1, -p 3: [2, 2^32) */
             else do { ps->sigma[u] = lcg_rand(&R->lcg); } while (ps->sigma[u] < 6);   /* ecm.c:1564-1570 */
+        }
+        if (R->fresh) {
+            ps->param = (uint8_t *)malloc(v->ucurves);
+            if (!ps->param) { fprintf(stderr, "out of memory\n"); return 2; }
+            memset(ps->param, R->fresh_param, v->ucurves);
         }
         /* host-side split: GPU g owns distinct curves [n*g/G, n*(g+1)/G) of this pass */
         v->nparts = gpus;
@@ -955,6 +977,7 @@ static int run_passes(run_t *R, gecm_ctx *ctx[2][MAX_GPUS], int gpus, int slots,
             ps->jobs[g].rx = ps->rx;                  /* -r runs on one context: its part is the pass */
             ps->jobs[g].rz = ps->rz;
             ps->jobs[g].b1_done = R->s1_complete ? R->B1 : 0;
+            ps->jobs[g].param = ps->param ? ps->param + lo : NULL;
         }
         ps->threaded = pthread_create(&ps->th, NULL, pass_run, ps) == 0;
         if (!ps->threaded) pass_run(ps);
@@ -1134,7 +1157,15 @@ static int multi_run(const char **ns, const char *const *logs, size_t n, run_t *
         rz = malloc(bytes);
         if (!rx || !rz) { fprintf(stderr, "out of memory\n"); exit(2); }
         pack_residues(&cfg, rl, total, 0, total, rx, rz);
-        if (R->extend)      /* -x: one segment from the lines' common bound to B1, then the standard lines' normalisation */
+        if (R->with_params) {                       /* -g: every curve by its line's parametrisation */
+            uint8_t *param = (uint8_t *)malloc(total);
+            if (!param) { fprintf(stderr, "out of memory\n"); exit(2); }
+            for (size_t u = 0; u < total; u++) param[u] = (uint8_t)rl[u].param;
+            rc = gecm_set_next_params(mc, param, total);
+            free(param);
+        }
+        if (rc) rc = 1;
+        else if (R->extend) /* -x: one segment from the lines' common bound to B1, then the standard lines' normalisation */
             rc = gecm_resume_points_multi(mc, sigma, which, rx, rz, total, 0) < 0 || gecm_stage1_extend(mc, R->ext_from, R->B1) ||
                  gecm_sync(mc) || gecm_normalize_points(mc) < 0 || gecm_scan_factors(mc, 1, NULL) < 0;
         else
@@ -1300,6 +1331,13 @@ static const char *resume_usage = "usage: avx-ecm -r $file $B1 [$B2]\n"
 static const char *extend_usage = "usage: avx-ecm -x $file $B1 [$B2]\n"
                                   "       (resume lines as for -r, complete to any bound up to $B1: stage 1 is extended to $B1)\n";
 
+/* -g before either: the file may hold lines of GMP-ECM's PARAM 1 and PARAM 3 next to PARAM 0, mixed or not
+ * (DESIGN.md §19); every line written carries its curve's PARAM=.  Nothing else differs. */
+static const char *gmp_resume_usage = "usage: avx-ecm -g -r $file $B1 [$B2]\n"
+                                      "       (-r with resume lines of PARAM 0, 1 and 3 accepted, as GMP-ECM 7 and ecm -gpu write them)\n";
+static const char *gmp_extend_usage = "usage: avx-ecm -g -x $file $B1 [$B2]\n"
+                                      "       (-x with resume lines of PARAM 0, 1 and 3 accepted, as GMP-ECM 7 and ecm -gpu write them)\n";
+
 typedef struct {
     size_t first, count;       /* lines of the file */
     uint32_t range;            /* the range stage 1 goes on with; the range count: complete */
@@ -1308,7 +1346,7 @@ typedef struct {
 } rgroup_t;
 
 /* one group on the one-input path; extend: -x */
-static int resume_single(const rgroup_t *g, const rline_t *lines, char **rargv, int rargc, int extend)
+static int resume_single(const rgroup_t *g, const rline_t *lines, char **rargv, int rargc, int extend, int gmp)
 {
     static run_t R;
     memset(&R, 0, sizeof R);
@@ -1322,6 +1360,7 @@ static int resume_single(const rgroup_t *g, const rline_t *lines, char **rargv, 
     R.s1_complete = R.first_range >= R.nranges;
     R.extend = extend;
     R.ext_from = g->from;
+    R.with_params = gmp;
     R.rd = (gecm_stage1_range_desc *)calloc((size_t)R.nranges, sizeof *R.rd);
     if (!R.rd) { fprintf(stderr, "out of memory\n"); return 2; }
     for (int r = R.first_range; r < R.nranges && !R.rd_rc && !extend; r++)
@@ -1341,9 +1380,10 @@ static int resume_single(const rgroup_t *g, const rline_t *lines, char **rargv, 
     return R.failed ? 2 : 0;
 }
 
-static int run_resume(int argc, char **argv, int extend)
+/* gmp: -g before -r or -x, lines of PARAM 0, 1 and 3 are read (gecm_parse_resume_line_param) */
+static int run_resume(int argc, char **argv, int extend, int gmp)
 {
-    const char *usage = extend ? extend_usage : resume_usage;
+    const char *usage = gmp ? (extend ? gmp_extend_usage : gmp_resume_usage) : extend ? extend_usage : resume_usage;
     if (argc < 4) { printf("%s", usage); return 1; }
     const int packing = cli_packing();
     if (packing < 0 || cli_multi_subseq() == 1) return 1;
@@ -1367,9 +1407,17 @@ static int run_resume(int argc, char **argv, int extend)
     while (!bad && !oom && getline(&text, &text_cap, f) > 0) {
         lineno++;
         gecm_resume_rec rec;
-        const int rc = gecm_parse_resume_line(text, &rec);
+        int param = 0;
+        const int rc = gmp ? gecm_parse_resume_line_param(text, &rec, &param) : gecm_parse_resume_line(text, &rec);
         if (rc == 1) continue;
-        if (rc) { printf("%s line %zu: %s\n", argv[2], lineno, gecm_last_error()); bad = 1; break; }
+        if (rc) {
+            const int other = !gmp && gecm_parse_resume_line_param(text, &rec, &param) == 0;   /* (the first text is gone then) */
+            if (other) printf("%s line %zu: field PARAM = %d: only PARAM 0 (Suyama's sigma) curves are resumed without -g "
+                              "(avx-ecm -g -%c reads PARAM 1 and 3)\n", argv[2], lineno, param, extend ? 'x' : 'r');
+            else printf("%s line %zu: %s\n", argv[2], lineno, gecm_last_error());
+            bad = 1;
+            break;
+        }
         if (nlines == cap_lines) {
             cap_lines = cap_lines ? 2 * cap_lines : 1024;
             rline_t *more = (rline_t *)realloc(lines, cap_lines * sizeof *lines);
@@ -1378,7 +1426,8 @@ static int run_resume(int argc, char **argv, int extend)
         }
         rline_t *l = &lines[nlines];
         l->text = pending = strdup(text);
-        if (!l->text || gecm_parse_resume_line(l->text, &l->rec)) { oom = 1; break; }   /* (it parsed a moment ago) */
+        l->param = 0;
+        if (!l->text || (gmp ? gecm_parse_resume_line_param(l->text, &l->rec, &l->param) : gecm_parse_resume_line(l->text, &l->rec))) { oom = 1; break; }   /* (it parsed a moment ago) */
         rnum(&n, &l->rec.n);
         if (!ngroups || mpl_cmp(&n, &n_cur) != 0) {
             if (ngroups == cap_groups) {
@@ -1406,7 +1455,7 @@ static int run_resume(int argc, char **argv, int extend)
             g->from = 0;
             if (extend) {
                 /* the standard bound of the lines: a reference line above one prime range has none, and none may lie above B1 */
-                if (gecm_resume_line_std_bound(l->text, &g->from)) { printf("%s line %zu: %s\n", argv[2], lineno, gecm_last_error()); bad = 1; break; }
+                if (gmp ? gecm_resume_line_std_bound_param(l->text, &g->from) : gecm_resume_line_std_bound(l->text, &g->from)) { printf("%s line %zu: %s\n", argv[2], lineno, gecm_last_error()); bad = 1; break; }
                 if (g->from < 1 || g->from > R0.B1) {
                     printf("%s line %zu: the line is complete to B1 = %lu, which is not in [1, %lu]: stage 1 is extended upwards only\n",
                            argv[2], lineno, (unsigned long)g->from, (unsigned long)R0.B1);
@@ -1425,7 +1474,7 @@ static int run_resume(int argc, char **argv, int extend)
         }
         rgroup_t *g = &groups[ngroups - 1];
         uint64_t from_l = 0;
-        if (extend && (gecm_resume_line_std_bound(l->text, &from_l) || from_l != g->from)) {
+        if (extend && ((gmp ? gecm_resume_line_std_bound_param(l->text, &from_l) : gecm_resume_line_std_bound(l->text, &from_l)) || from_l != g->from)) {
             printf("%s line %zu: the line is not complete to the bound %lu of the lines on this N before it\n", argv[2], lineno,
                    (unsigned long)g->from);
             bad = 1;
@@ -1482,6 +1531,7 @@ static int run_resume(int argc, char **argv, int extend)
         R0.t_start = now();
         R0.s1_complete = !extend;                  /* the multi passes: stage 2 only; -x: one extension segment first */
         R0.extend = extend;
+        R0.with_params = gmp;
         R0.nbatches = 0;
         size_t p0 = 0;                             /* the pending multi pass: groups p0 .. i */
         size_t *pcount = (size_t *)calloc(ngroups + 1, sizeof *pcount);   /* curves of the groups */
@@ -1535,7 +1585,7 @@ static int run_resume(int argc, char **argv, int extend)
                 continue;
             }
             snprintf(ncurves, sizeof ncurves, "%zu", groups[i].count);
-            const int r1 = resume_single(&groups[i], lines, rargv, rargc, extend);
+            const int r1 = resume_single(&groups[i], lines, rargv, rargc, extend, gmp);
             if (r1 > rc) rc = r1;
             p0 = i + 1;
         }
@@ -1548,10 +1598,83 @@ static int run_resume(int argc, char **argv, int extend)
     return rc;
 }
 
+/* ---- avx-ecm -p PARAM input curves B1 [B2] [sigma]: a fresh run in standard mode ------------------------------------
+ * Curves of GMP-ECM's parametrisation PARAM (0, 1 or 3) on the input as gecm_prepare_input leaves it —
+ * the context is on N itself, without the reference's special-form folding — built and then taken through -x's own
+ * path from the bound 1: extension segments, checkpoint.txt after every segment but the last, normalisation, standard
+ * lines in save_b1.txt, stage 2 when B2 > B1 (left out: 100 B1), factors to ecm_results.txt.  With a sigma the curves are
+ * sigma, sigma + 1, ... as ecm -gpu numbers them; without, sigmas come from the driver's generator, for PARAM 1 and 3
+ * reduced into [2, 2^32).  One thread, the first GPU. */
+static const char *param_usage = "usage: avx-ecm -p $param $input $numcurves $B1 [$B2] [$sigma]\n"
+                                 "       (a fresh run with the standard stage-1 multiplier; $param: 0 = Suyama's sigma, 1 and 3 = GMP-ECM's\n"
+                                 "        batch parametrisations d = sigma^2 / 2^64 and sigma / 2^32, start point (2 : 1))\n";
+
+static int run_param(int argc, char **argv)
+{
+    if (argc < 6) { printf("%s", param_usage); return 1; }
+    char *end = NULL;
+    const long param = strtol(argv[2], &end, 10);
+    if (!*argv[2] || *end || (param != GECM_PARAM_SUYAMA && param != GECM_PARAM_BATCH_SQUARE && param != GECM_PARAM_BATCH_32)) {
+        printf("-p %s: the parametrisations offered are 0, 1 and 3 (PARAM 2 takes a point multiplication on another curve)\n%s",
+               argv[2], param_usage);
+        return 1;
+    }
+    static run_t R;
+    memset(&R, 0, sizeof R);
+    R.t_start = now();
+    static char ndec[MPL_MAXL * 10 + 16], prep_log[65536];
+    gecm_input_info inf;
+    if (gecm_prepare_input(argv[3], GECM_CLI_DIGITBITS, ndec, sizeof ndec, &inf, prep_log, sizeof prep_log)) {
+        fputs(prep_log, stdout);
+        printf("input must evaluate to an odd integer >= 3 (operators + - * / %% ^ ! # fib() luc())\n");
+        return 1;
+    }
+    /* the run's arguments through the one parser: curves B1 threads [B2] [sigma], one thread */
+    char one[] = "1";
+    char *rargv[5] = {argv[4], argv[5], one, argc > 6 ? argv[6] : NULL, argc > 7 ? argv[7] : NULL};
+    if (parse_run(&R, argc > 7 ? 5 : argc > 6 ? 4 : 3, rargv)) return 1;
+    const uint64_t last = R.sigma0 + R.nbatches * R.ub - 1;                       /* of sigma, sigma + 1, ... */
+    if (R.fixed_sigma && (param == GECM_PARAM_SUYAMA ? R.sigma0 < 6 : last < R.sigma0 || (param == GECM_PARAM_BATCH_32 && last >> 32))) {
+        printf("-p %ld: sigma %lu and the curves after it leave the parametrisation's range\n%s", param, (unsigned long)R.sigma0, param_usage);
+        return 1;
+    }
+    if (gecm_device_count() < 1) { fprintf(stderr, "no HIP device visible\n"); return 2; }
+    printf("starting process %d\n", (int)getpid());
+    fputs(prep_log, stdout);
+    R.gpus = 1;
+    R.extend = 1;
+    R.ext_from = 1;
+    R.fresh = 1;
+    R.fresh_param = (int)param;
+    R.nranges = gecm_stage1_extend_segments(1, R.B1);
+    R.rd = (gecm_stage1_range_desc *)calloc((size_t)R.nranges, sizeof *R.rd);
+    if (!R.rd) { fprintf(stderr, "out of memory\n"); return 2; }
+    static gecm_ctx *ctx[2][MAX_GPUS];
+    if (make_contexts(ctx[0], 1, 1, ndec, NULL)) return 2;
+    uint64_t mem_free, budget;
+    const size_t batches_per_pass = pass_batches(&R, ctx[0][0], 1, 1, &mem_free, &budget);
+    printf("running %zu curves of PARAM %ld on N = %s in standard mode to B1 = %lu\n", R.nbatches * R.ub, param, ndec, (unsigned long)R.B1);
+    run_begin(&R);
+    if (run_passes(&R, ctx, 1, 1, batches_per_pass)) return 2;
+    if (R.fr.valid) gecm_pairmap_release(&R.fr.pm);
+    gecm_destroy(ctx[0][0]);
+    free(R.rd);
+    printf("Process took %1.4f seconds.\n", now() - R.t_start);
+    return R.failed ? 2 : 0;
+}
+
 int main(int argc, char **argv)
 {
     if (argc > 1 && strcmp(argv[1], "-f") == 0) return run_file(argc, argv);
-    if (argc > 1 && strcmp(argv[1], "-r") == 0) return run_resume(argc, argv, 0);
-    if (argc > 1 && strcmp(argv[1], "-x") == 0) return run_resume(argc, argv, 1);
+    if (argc > 1 && strcmp(argv[1], "-r") == 0) return run_resume(argc, argv, 0, 0);
+    if (argc > 1 && strcmp(argv[1], "-x") == 0) return run_resume(argc, argv, 1, 0);
+    if (argc > 1 && strcmp(argv[1], "-g") == 0) {
+        /* -g -r, -g -x: the same two with lines of PARAM 0, 1 and 3 accepted */
+        if (argc > 2 && strcmp(argv[2], "-r") == 0) return run_resume(argc - 1, argv + 1, 0, 1);
+        if (argc > 2 && strcmp(argv[2], "-x") == 0) return run_resume(argc - 1, argv + 1, 1, 1);
+        printf("%s%s", gmp_resume_usage, gmp_extend_usage);
+        return 1;
+    }
+    if (argc > 1 && strcmp(argv[1], "-p") == 0) return run_param(argc, argv);
     return run_single(argc, argv);
 }

@@ -77,6 +77,9 @@ struct gecm_ctx {
     size_t batch;
     uint64_t *sigma;
     uint8_t *bad;
+    uint8_t *param;      /* the parametrisation of every position; NULL: the batch was built without a setting, 0 throughout */
+    uint8_t *next_param; /* gecm_set_next_params: of the next build, the caller's order, next_batch curves; NULL: none pending */
+    size_t next_batch;
     uint32_t *hx, *hz;   /* last downloaded plain x, z: [nl][batch] */
     int have_plain;
     int normalized;      /* X = x/z, Z = 1 since the last gecm_normalize_points; norm_left[pos] = 1: that curve's Z has no inverse */
@@ -390,6 +393,8 @@ static void free_batch(gecm_ctx *c)
     free(c->norm_left);
     c->norm_left = NULL;
     c->normalized = 0;
+    free(c->param);
+    c->param = NULL;
     free(c->sigma); free(c->bad); free(c->hx); free(c->hz); free(c->hacc); free(c->hfail);
     free(c->flags[0]); free(c->flags[1]); free(c->hg[0]); free(c->hg[1]);
     c->flags[0] = c->flags[1] = NULL;
@@ -428,6 +433,7 @@ void gecm_destroy(gecm_ctx *c)
     if (c->pf_active) { pthread_join(c->pf_thread, NULL); c->pf_active = 0; gecm_tape_free(&c->pf_tape); }
     gecm_tape_free(&c->tape);
     free_batch(c);
+    free(c->next_param);
     gecm_s2_plan_free(&c->s2);
     drop_kept_pairmap(c);
     if (c->ptp_valid) free(c->ptp.words);
@@ -627,6 +633,69 @@ int gecm_vecinvmod(gecm_ctx *c, const void *a, void *inv, void *gcd, size_t batc
 }
 
 /* ---- phase 0 -------------------------------------------------------------------------------- */
+/* The one-shot setting of gecm_set_next_params, taken by the build call that follows it whether that call succeeds or
+ * not: the array (the caller of this frees it; NULL: none pending) and the batch it was given for. */
+static uint8_t *take_next_params(gecm_ctx *c, size_t *batch)
+{
+    if (!c) return NULL;
+    uint8_t *p = c->next_param;
+    *batch = c->next_batch;
+    c->next_param = NULL;
+    c->next_batch = 0;
+    return p;
+}
+
+/* the checks of a build call on its sigmas, before the context gives up its batch: the setting is for this batch size,
+ * sigma >= 6 for the PARAM 0 curves, the range of the parametrisation for the others (prm NULL: PARAM 0 throughout) */
+static int params_fit(const char *who, size_t batch, const uint8_t *prm, size_t prm_batch)
+{
+    if (!prm || prm_batch == batch) return GECM_OK;
+    set_err("%s: gecm_set_next_params gave the parametrisations of %zu curves, this batch has %zu", who, prm_batch, batch);
+    return GECM_ERR_ARG;
+}
+
+static int sigma_arg(const char *who, const uint64_t *sigma, size_t i, const uint8_t *prm)
+{
+    if (prm && prm[i]) {
+        if (gecm_mod_param_sigma_ok(prm[i], sigma[i])) return GECM_OK;
+        set_err("%s: SIGMA: sigma[%zu] = %llu is outside [1, 2^%d), the range of PARAM %d", who, i,
+                (unsigned long long)sigma[i], prm[i] == GECM_PARAM_BATCH_SQUARE ? 64 : 32, prm[i]);
+        return GECM_ERR_ARG;
+    }
+    if (sigma[i] < 6) { set_err("%s: sigma[%zu] < 6", who, i); return GECM_ERR_ARG; }
+    return GECM_OK;
+}
+
+static int sigma_args(const char *who, const uint64_t *sigma, size_t batch, const uint8_t *prm, size_t prm_batch)
+{
+    int rc = params_fit(who, batch, prm, prm_batch);
+    for (size_t i = 0; i < batch && !rc; i++) rc = sigma_arg(who, sigma, i, prm);
+    return rc;
+}
+
+int gecm_set_next_params(gecm_ctx *c, const uint8_t *param, size_t batch)
+{
+    if (param) {
+        if (batch == 0) { set_err("gecm_set_next_params: bad argument (an empty batch)"); return GECM_ERR_ARG; }
+        for (size_t i = 0; i < batch; i++)
+            if (param[i] != GECM_PARAM_SUYAMA && param[i] != GECM_PARAM_BATCH_SQUARE && param[i] != GECM_PARAM_BATCH_32) {
+                set_err("gecm_set_next_params: param[%zu] = %d: a parametrisation is 0 (Suyama), 1 (sigma^2 / 2^64) or 3 "
+                        "(sigma / 2^32)", i, param[i]);
+                return GECM_ERR_ARG;
+            }
+    }
+    if (!c) { set_err("gecm_set_next_params: bad argument (no context)"); return GECM_ERR_ARG; }
+    free(c->next_param);
+    c->next_param = NULL;
+    c->next_batch = 0;
+    if (!param) return GECM_OK;
+    c->next_param = (uint8_t *)malloc(batch);
+    if (!c->next_param) return GECM_ERR_NOMEM;
+    memcpy(c->next_param, param, batch);
+    c->next_batch = batch;
+    return GECM_OK;
+}
+
 static int alloc_batch(gecm_ctx *c, size_t batch)
 {
     free_batch(c);
@@ -653,7 +722,12 @@ static int build_on_device(gecm_ctx *c, const uint64_t *sigma, size_t total, con
 {
     uint32_t *flags = (uint32_t *)malloc(total * sizeof(uint32_t));
     if (!flags) return GECM_ERR_NOMEM;
-    if (gecm_dev_build(c->dev, sigma, total, flags)) { free(flags); set_err("%s", gecm_dev_error()); return GECM_ERR_DEVICE; }
+    /* with a parametrisation per curve: the Suyama kernel if some curve is PARAM 0, then k_build_param over the others */
+    if (c->param ? gecm_dev_build_param(c->dev, sigma, c->param, total, flags) : gecm_dev_build(c->dev, sigma, total, flags)) {
+        free(flags);
+        set_err("%s", gecm_dev_error());
+        return GECM_ERR_DEVICE;
+    }
     int any = 0;
     for (size_t p = 0; p < total; p++)
         if (flags[p] && !(live && live[p] == GECM_PAD)) c->bad[p] = (uint8_t)(any = 1);
@@ -666,19 +740,24 @@ static int build_on_device(gecm_ctx *c, const uint64_t *sigma, size_t total, con
  * device (gecm_set_curve_build), then px != NULL: gecm_resume_points, X and Z replaced by the Montgomery forms of
  * the plain residues px, pz (canonical in [0, N), [nl][batch]), made on the device; last the twin, from what the main
  * context now holds. */
-static int build_single(gecm_ctx *c, const uint64_t *sigma, size_t batch, const uint32_t *px, const uint32_t *pz)
+static int build_single(gecm_ctx *c, const uint64_t *sigma, size_t batch, const uint32_t *px, const uint32_t *pz, const uint8_t *prm)
 {
     c->build_used = c->build_where;
     int rc = alloc_batch(c, batch);
     if (rc) return rc;
     memcpy(c->sigma, sigma, batch * sizeof(uint64_t));
+    if (prm) {                                        /* gecm_set_next_params: a parametrisation per curve */
+        c->param = (uint8_t *)malloc(batch);
+        if (!c->param) { free_batch(c); return GECM_ERR_NOMEM; }
+        memcpy(c->param, prm, batch);
+    }
     int built;
     if (c->build_where == GECM_BUILD_DEVICE) built = build_on_device(c, sigma, batch, NULL);
     else {
         const size_t words = (size_t)c->mod.nl * batch;
         uint32_t *hX = (uint32_t *)calloc(words * 3, 4);
         if (!hX) { free_batch(c); return GECM_ERR_NOMEM; }
-        gecm_mod_build b = {&c->mod, sigma, c->bad, batch, 0, hX, hX + words, hX + 2 * words};
+        gecm_mod_build b = {&c->mod, sigma, c->bad, batch, 0, hX, hX + words, hX + 2 * words, c->param};
         built = run_slices(batch, gecm_mod_build_slice, &b);
         if (built >= 0 && gecm_dev_upload(c->dev, hX, hX + words, hX + 2 * words)) {
             set_err("%s", gecm_dev_error());
@@ -697,13 +776,16 @@ static int build_single(gecm_ctx *c, const uint64_t *sigma, size_t batch, const 
 
 int gecm_build_curves(gecm_ctx *c, const uint64_t *sigma, size_t batch)
 {
-    if (!c || !sigma || batch == 0) { set_err("gecm_build_curves: bad argument"); return GECM_ERR_ARG; }
-    if (c && c->multi) return multi_refuse("gecm_build_curves");
+    size_t prm_batch = 0;
+    uint8_t *prm = take_next_params(c, &prm_batch);
+    if (!c || !sigma || batch == 0) { free(prm); set_err("gecm_build_curves: bad argument"); return GECM_ERR_ARG; }
+    if (c && c->multi) { free(prm); return multi_refuse("gecm_build_curves"); }
     /* inputs are checked before the context takes the new batch: after an error it holds no batch at all (the
      * phase functions then return GECM_ERR_STATE instead of running on memory nothing was uploaded to) */
-    for (size_t i = 0; i < batch; i++)
-        if (sigma[i] < 6) { set_err("gecm_build_curves: sigma[%zu] < 6", i); return GECM_ERR_ARG; }
-    return build_single(c, sigma, batch, NULL, NULL);
+    int rc = sigma_args("gecm_build_curves", sigma, batch, prm, prm_batch);
+    if (!rc) rc = build_single(c, sigma, batch, NULL, NULL, prm);
+    free(prm);
+    return rc;
 }
 
 int gecm_set_curve_build(gecm_ctx *c, int where)
@@ -1084,6 +1166,16 @@ static const gecm_mod *curve_at(const gecm_ctx *c, size_t k, size_t *pos)
     return &c->grp[c->pos_grp[*pos]];
 }
 
+int gecm_curve_param(const gecm_ctx *c, size_t k)
+{
+    size_t pos;
+    if (!c || !curve_at(c, k, &pos)) {
+        if (!c || !c->multi) set_err("gecm_curve_param: curve %zu: no such curve in the batch", k);
+        return GECM_ERR_ARG;
+    }
+    return c->param ? c->param[pos] : GECM_PARAM_SUYAMA;
+}
+
 int gecm_format_save_line(gecm_ctx *c, size_t k, char *buf, size_t buflen)
 {
     return gecm_format_resume_line(c, k, c ? c->B1 : 0, buf, buflen);
@@ -1103,8 +1195,10 @@ int gecm_format_resume_line(gecm_ctx *c, size_t k, uint64_t b1_label, char *buf,
     mpl_get_hex(hxs, &v);
     mpl_from_limbs32(&v, c->hz + pos, c->batch, m->nl, LIMB_BITS);
     mpl_get_hex(hzs, &v);
-    /* ecm.c:1372-1380 */
-    int n = snprintf(buf, buflen, "METHOD=ECM; SIGMA=%llu; B1=%llu; N=0x%s; X=0x%s; Z=0x%s; PROGRAM=AVX-ECM;\n",
+    /* ecm.c:1372-1380; a curve of another parametrisation says so, or a reader would take its sigma for Suyama's */
+    char prm[16] = "";
+    if (c->param && c->param[pos]) snprintf(prm, sizeof prm, "PARAM=%d; ", c->param[pos]);
+    int n = snprintf(buf, buflen, "METHOD=ECM; %sSIGMA=%llu; B1=%llu; N=0x%s; X=0x%s; Z=0x%s; PROGRAM=AVX-ECM;\n", prm,
                      (unsigned long long)c->sigma[pos], (unsigned long long)b1_label, hn, hxs, hzs);
     if (n < 0 || (size_t)n >= buflen) { set_err("gecm_format_save_line: buffer too small"); return GECM_ERR_ARG; }
     return n;
@@ -1176,14 +1270,15 @@ int gecm_format_save_line_std(gecm_ctx *c, size_t k, char *buf, size_t buflen)
     mpl_get_hex(hn, report_n(m));
     mpl_from_limbs32(&v, c->hx + pos, c->batch, m->nl, LIMB_BITS);
     mpl_get_hex(hxs, &v);
+    const int prm = c->param ? c->param[pos] : GECM_PARAM_SUYAMA;
     int n;
     if (c->norm_left[pos]) {
         mpl_from_limbs32(&v, c->hz + pos, c->batch, m->nl, LIMB_BITS);
         mpl_get_hex(hzs, &v);
-        n = snprintf(buf, buflen, "METHOD=ECM; PARAM=0; SIGMA=%llu; B1=%llu; N=0x%s; X=0x%s; Z=0x%s; PROGRAM=AVX-ECM-STD;\n",
+        n = snprintf(buf, buflen, "METHOD=ECM; PARAM=%d; SIGMA=%llu; B1=%llu; N=0x%s; X=0x%s; Z=0x%s; PROGRAM=AVX-ECM-STD;\n", prm,
                      (unsigned long long)c->sigma[pos], (unsigned long long)c->B1, hn, hxs, hzs);
     } else
-        n = snprintf(buf, buflen, "METHOD=ECM; PARAM=0; SIGMA=%llu; B1=%llu; N=0x%s; X=0x%s; PROGRAM=AVX-ECM-STD;\n",
+        n = snprintf(buf, buflen, "METHOD=ECM; PARAM=%d; SIGMA=%llu; B1=%llu; N=0x%s; X=0x%s; PROGRAM=AVX-ECM-STD;\n", prm,
                      (unsigned long long)c->sigma[pos], (unsigned long long)c->B1, hn, hxs);
     if (n < 0 || (size_t)n >= buflen) { set_err("gecm_format_save_line_std: buffer too small"); return GECM_ERR_ARG; }
     return n;
@@ -1666,13 +1761,15 @@ int gecm_set_multi_packing(gecm_ctx *c, int packing)
 int gecm_get_multi_packing(const gecm_ctx *c) { return c ? c->packing_used : GECM_ERR_ARG; }
 
 /* the checks gecm_build_curves_multi and gecm_resume_points_multi make on their common arguments */
-static int multi_args(const gecm_ctx *c, const char *who, const uint64_t *sigma, const uint32_t *modulus_index, size_t batch)
+static int multi_args(const gecm_ctx *c, const char *who, const uint64_t *sigma, const uint32_t *modulus_index, size_t batch,
+                      const uint8_t *prm, size_t prm_batch)
 {
     if (!c || !sigma || !modulus_index || batch == 0) { set_err("%s: bad argument", who); return GECM_ERR_ARG; }
     if (!c->multi) { set_err("%s: not a multi-modulus context (gecm_create_multi)", who); return GECM_ERR_STATE; }
     if (batch >= GECM_PAD) { set_err("%s: batch too large", who); return GECM_ERR_ARG; }
+    if (params_fit(who, batch, prm, prm_batch)) return GECM_ERR_ARG;
     for (size_t i = 0; i < batch; i++) {
-        if (sigma[i] < 6) { set_err("%s: sigma[%zu] < 6", who, i); return GECM_ERR_ARG; }
+        if (sigma_arg(who, sigma, i, prm)) return GECM_ERR_ARG;
         if (modulus_index[i] >= c->ngroups) {
             set_err("%s: modulus_index[%zu] = %u, the context has %zu moduli", who, i, modulus_index[i], c->ngroups);
             return GECM_ERR_ARG;
@@ -1684,7 +1781,7 @@ static int multi_args(const gecm_ctx *c, const char *who, const uint64_t *sigma,
 /* gecm_build_curves_multi after its checks; ux != NULL: gecm_resume_points_multi, the points are the plain residues ux,
  * uz ([nl][batch], the caller's order), the padding gets x = z = 1 */
 static int build_multi(gecm_ctx *c, const char *who, const uint64_t *sigma, const uint32_t *modulus_index, size_t batch,
-                       const uint32_t *ux, const uint32_t *uz)
+                       const uint32_t *ux, const uint32_t *uz, const uint8_t *prm)
 {
     /* positions: the moduli in order, each one's curves in the caller's order, padded to a multiple of 64; lane-packed:
      * back to back, and the batch's tail padded (modulus 0 there: computed, never read) */
@@ -1709,13 +1806,17 @@ static int build_multi(gecm_ctx *c, const char *who, const uint64_t *sigma, cons
     uint32_t *blocks = lane ? NULL : (uint32_t *)malloc(total / 64 * sizeof(uint32_t));
     const size_t words = (size_t)c->mod.nl * total;
     uint32_t *hX = (uint32_t *)calloc(words * 3, 4);           /* padding stays zero: computed, never read */
-    if (!rc && (!slot || !pos_user || !pos_grp || (!lane && !blocks) || !hX)) rc = GECM_ERR_NOMEM;
+    /* gecm_set_next_params: the parametrisation of every position, the padding's 0 */
+    uint8_t *param = prm ? (uint8_t *)calloc(total, 1) : NULL;
+    if (!rc && (!slot || !pos_user || !pos_grp || (!lane && !blocks) || !hX || (prm && !param))) rc = GECM_ERR_NOMEM;
     if (rc) {
+        free(param);
         free(cnt); free(goff); free(slot); free(pos_user); free(pos_grp); free(blocks); free(hX);
         free_batch(c);
         return rc;
     }
     c->slot = slot; c->pos_user = pos_user; c->pos_grp = pos_grp; c->nuser = batch;
+    c->param = param;
     for (size_t p = 0; lane && p < total; p++) {
         pos_grp[p] = 0;
         pos_user[p] = GECM_PAD;
@@ -1734,13 +1835,15 @@ static int build_multi(gecm_ctx *c, const char *who, const uint64_t *sigma, cons
         slot[i] = (uint32_t)p;
         pos_user[p] = (uint32_t)i;
         c->sigma[p] = sigma[i];
+        if (param) param[p] = prm[i];
     }
     /* the Suyama construction modulus by modulus: what gecm_build_curves does for its one */
     int anybad = 0;
     c->build_used = c->build_where;
     const int on_device = c->build_where == GECM_BUILD_DEVICE;
     for (size_t g = 0; g < ng && !rc && !on_device; g++) {
-        gecm_mod_build b = {&c->grp[g], c->sigma + goff[g], c->bad, total, goff[g], hX, hX + words, hX + 2 * words};
+        gecm_mod_build b = {&c->grp[g], c->sigma + goff[g], c->bad, total, goff[g], hX, hX + words, hX + 2 * words,
+                            param ? param + goff[g] : NULL};
         const int built = run_slices(cnt[g], gecm_mod_build_slice, &b);
         if (built < 0) rc = built;
         else anybad |= built;
@@ -1784,8 +1887,12 @@ static int build_multi(gecm_ctx *c, const char *who, const uint64_t *sigma, cons
 
 int gecm_build_curves_multi(gecm_ctx *c, const uint64_t *sigma, const uint32_t *modulus_index, size_t batch)
 {
-    const int rc = multi_args(c, "gecm_build_curves_multi", sigma, modulus_index, batch);
-    return rc ? rc : build_multi(c, "gecm_build_curves_multi", sigma, modulus_index, batch, NULL, NULL);
+    size_t prm_batch = 0;
+    uint8_t *prm = take_next_params(c, &prm_batch);
+    int rc = multi_args(c, "gecm_build_curves_multi", sigma, modulus_index, batch, prm, prm_batch);
+    if (!rc) rc = build_multi(c, "gecm_build_curves_multi", sigma, modulus_index, batch, NULL, NULL, prm);
+    free(prm);
+    return rc;
 }
 
 /* ---- resume ------------------------------------------------------------------- */
@@ -1823,7 +1930,7 @@ static int plain_slice(void *arg, size_t lo, size_t hi)
 
 /* what both resume calls do once their context kind is settled; idx NULL on a single-N context */
 static int resume_points(gecm_ctx *c, const char *who, const uint64_t *sigma, const uint32_t *idx, const void *x,
-                         const void *z, size_t batch, uint64_t b1_done)
+                         const void *z, size_t batch, uint64_t b1_done, const uint8_t *prm)
 {
     if (!x || !z) { set_err("%s: bad argument", who); return GECM_ERR_ARG; }
     if (b1_done == 1 || b1_done > GECM_B1_MAX) { set_err("%s: b1_done must be 0 or a B1 in [2, %llu]", who, (unsigned long long)GECM_B1_MAX); return GECM_ERR_ARG; }
@@ -1838,8 +1945,8 @@ static int resume_points(gecm_ctx *c, const char *who, const uint64_t *sigma, co
         set_err("%s: x[%zu] or z[%zu] is not below the curve's N", who, j.first_bad, j.first_bad);
         return GECM_ERR_ARG;                      /* the previous batch is untouched */
     }
-    const int built = idx ? build_multi(c, who, sigma, idx, batch, planes, planes + words)
-                          : build_single(c, sigma, batch, planes, planes + words);
+    const int built = idx ? build_multi(c, who, sigma, idx, batch, planes, planes + words, prm)
+                          : build_single(c, sigma, batch, planes, planes + words, prm);
     free(planes);
     if (built < 0) return built;
     /* mid stage 1 (the caller goes on with gecm_stage1_range), or stage 1 taken as finished at b1_done; the counters
@@ -1851,18 +1958,25 @@ static int resume_points(gecm_ctx *c, const char *who, const uint64_t *sigma, co
 
 int gecm_resume_points(gecm_ctx *c, const uint64_t *sigma, const void *x, const void *z, size_t batch, uint64_t b1_done)
 {
-    if (!c || !sigma || batch == 0) { set_err("gecm_resume_points: bad argument"); return GECM_ERR_ARG; }
-    if (c->multi) return multi_refuse("gecm_resume_points");
-    for (size_t i = 0; i < batch; i++)
-        if (sigma[i] < 6) { set_err("gecm_resume_points: sigma[%zu] < 6", i); return GECM_ERR_ARG; }
-    return resume_points(c, "gecm_resume_points", sigma, NULL, x, z, batch, b1_done);
+    size_t prm_batch = 0;
+    uint8_t *prm = take_next_params(c, &prm_batch);
+    if (!c || !sigma || batch == 0) { free(prm); set_err("gecm_resume_points: bad argument"); return GECM_ERR_ARG; }
+    if (c->multi) { free(prm); return multi_refuse("gecm_resume_points"); }
+    int rc = sigma_args("gecm_resume_points", sigma, batch, prm, prm_batch);
+    if (!rc) rc = resume_points(c, "gecm_resume_points", sigma, NULL, x, z, batch, b1_done, prm);
+    free(prm);
+    return rc;
 }
 
 int gecm_resume_points_multi(gecm_ctx *c, const uint64_t *sigma, const uint32_t *modulus_index, const void *x,
                              const void *z, size_t batch, uint64_t b1_done)
 {
-    const int rc = multi_args(c, "gecm_resume_points_multi", sigma, modulus_index, batch);
-    return rc ? rc : resume_points(c, "gecm_resume_points_multi", sigma, modulus_index, x, z, batch, b1_done);
+    size_t prm_batch = 0;
+    uint8_t *prm = take_next_params(c, &prm_batch);
+    int rc = multi_args(c, "gecm_resume_points_multi", sigma, modulus_index, batch, prm, prm_batch);
+    if (!rc) rc = resume_points(c, "gecm_resume_points_multi", sigma, modulus_index, x, z, batch, b1_done, prm);
+    free(prm);
+    return rc;
 }
 
 int gecm_curve_modulus(const gecm_ctx *c, size_t k)

@@ -159,6 +159,54 @@ static void suyama_pre(const mpl_t *n, uint64_t sigma, mpl_t *x3, mpl_t *z3, mpl
     mpl_mod(den, &t2, n);               /* 16 u^3 v               ecm.c:1718-1720 */
 }
 
+/* ---- GMP-ECM's PARAM 1 and PARAM 3 ---- */
+int gecm_mod_param_sigma_ok(int param, uint64_t sigma)
+{
+    return sigma >= 1 && (param == GECM_PARAM_BATCH_SQUARE || (param == GECM_PARAM_BATCH_32 && sigma >> 32 == 0));
+}
+
+void gecm_mod_param_unit(mpl_t *unit, int param, const mpl_t *N)
+{
+    mpl_t t;
+    gecm_mod_pow2(&t, param == GECM_PARAM_BATCH_SQUARE ? 64 : 32, N);
+    mpl_invmod(unit, &t, N);                            /* N is odd: a power of two has an inverse */
+}
+
+void gecm_mod_param_d(mpl_t *d, int param, uint64_t sigma, const mpl_t *unit, const mpl_t *N)
+{
+    mpl_t s;
+    mpl_set_u64(&s, sigma);
+    if (param == GECM_PARAM_BATCH_SQUARE) mpl_mul(&s, &s, &s);
+    mpl_mod(&s, &s, N);
+    mpl_mulmod(d, &s, unit, N);
+}
+
+int gecm_param_s(int param, uint64_t sigma, const char *n_str, char *hex, size_t hexlen)
+{
+    mpl_t N, unit, d;
+    if (param != GECM_PARAM_BATCH_SQUARE && param != GECM_PARAM_BATCH_32) {
+        gecm_mod_set_err("gecm_param_s: PARAM %d: s comes from sigma alone for PARAM 1 and 3 only (PARAM 0 needs the "
+                         "inversion rule of a build, PARAM 2 a point multiplication on another curve)", param);
+        return GECM_ERR_ARG;
+    }
+    if (!gecm_mod_param_sigma_ok(param, sigma)) {
+        gecm_mod_set_err("gecm_param_s: SIGMA = %llu is outside [1, 2^%d), the range of PARAM %d", (unsigned long long)sigma,
+                         param == GECM_PARAM_BATCH_SQUARE ? 64 : 32, param);
+        return GECM_ERR_ARG;
+    }
+    if (!n_str || !hex || mpl_set_str(&N, n_str) || !mpl_is_odd(&N) || mpl_cmp_u64(&N, 3) < 0) {
+        gecm_mod_set_err("gecm_param_s: N must be an odd integer >= 3 (decimal or 0x-hex), and hex a buffer");
+        return GECM_ERR_ARG;
+    }
+    gecm_mod_param_unit(&unit, param, &N);
+    gecm_mod_param_d(&d, param, sigma, &unit, &N);
+    static __thread char tmp[MPL_MAXL * 10 + 2];
+    const int n = mpl_get_hex(tmp, &d);
+    if (n < 0 || (size_t)n >= hexlen) { gecm_mod_set_err("gecm_param_s: buffer too small"); return GECM_ERR_ARG; }
+    memcpy(hex, tmp, (size_t)n + 1);
+    return n;
+}
+
 /* One worker's slice [lo, hi): the whole Suyama construction for those curves.
  * The two inversions per curve, mpz_invert(16u^3v) ecm.c:1745 and mpz_invert(v^3) ecm.c:1759, share the
  * modulus, so each slice does Montgomery's simultaneous inversion: one extended Euclid per slice
@@ -176,8 +224,21 @@ int gecm_mod_build_slice(void *build, size_t lo, size_t hi)
     mpl_t *pref = (mpl_t *)malloc(m * sizeof(mpl_t));
     if (!x3 || !dens || !pref) { free(x3); free(dens); free(pref); return GECM_ERR_NOMEM; }
     mpl_t *num = x3 + cnt;
-    for (size_t i = 0; i < cnt; i++)
-        suyama_pre(&c->N, j->sigma[lo + i], &x3[i], &dens[2 * i + 1], &num[i], &dens[2 * i]);
+    /* a PARAM 1 or 3 curve of a mixed batch (j->param) has no inversion: it stands in the shared one with the
+     * denominators 1, 1 — the Suyama curves of the slice get the inverses they get without it, inverses being unique,
+     * and the same failure records — and is written by its own formula below */
+    const uint8_t *prm = j->param ? j->param + lo : NULL;
+    mpl_t unit[2];
+    int have_unit[2] = {0, 0};
+    for (size_t i = 0; i < cnt; i++) {
+        if (prm && prm[i]) {
+            mpl_set_u64(&x3[i], 0);
+            mpl_set_u64(&num[i], 0);
+            mpl_set_u64(&dens[2 * i], 1);
+            mpl_set_u64(&dens[2 * i + 1], 1);
+        } else
+            suyama_pre(&c->N, j->sigma[lo + i], &x3[i], &dens[2 * i + 1], &num[i], &dens[2 * i]);
+    }
     int batch_ok = 1;
     pref[0] = dens[0];
     for (size_t i = 1; i < m; i++) mpl_mulmod(&pref[i], &pref[i - 1], &dens[i], &c->N);
@@ -209,8 +270,17 @@ int gecm_mod_build_slice(void *build, size_t lo, size_t hi)
     for (size_t i = 0; i < cnt; i++) {
         mpl_t A, X, Xm, Sm;
         const size_t k = j->off + lo + i;
-        mpl_mulmod(&A, &num[i], &invs[2 * i], &c->N);          /* b = a / 16u^3v   ecm.c:1752-1753 */
-        mpl_mulmod(&X, &x3[i], &invs[2 * i + 1], &c->N);       /* X = u^3 / v^3, Z = 1  ecm.c:1759-1761 */
+        if (prm && prm[i]) {                                   /* s = d, P = (2 : 1) */
+            const int w = prm[i] == GECM_PARAM_BATCH_SQUARE ? 0 : 1;
+            if (!have_unit[w]) gecm_mod_param_unit(&unit[w], prm[i], &c->N);
+            have_unit[w] = 1;
+            gecm_mod_param_d(&A, prm[i], j->sigma[lo + i], &unit[w], &c->N);
+            mpl_set_u64(&X, 2);
+            mpl_mod(&X, &X, &c->N);
+        } else {
+            mpl_mulmod(&A, &num[i], &invs[2 * i], &c->N);      /* b = a / 16u^3v   ecm.c:1752-1753 */
+            mpl_mulmod(&X, &x3[i], &invs[2 * i + 1], &c->N);   /* X = u^3 / v^3, Z = 1  ecm.c:1759-1761 */
+        }
         /* into Montgomery form (ecm.c:1763-1772), internal radix */
         mpl_mulmod(&Xm, &X, &c->rint_mod_n, &c->N);
         mpl_mulmod(&Sm, &A, &c->rint_mod_n, &c->N);

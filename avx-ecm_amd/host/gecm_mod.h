@@ -57,9 +57,19 @@ typedef struct {
     uint8_t *bad;             /* [batch], set where a denominator does not invert */
     size_t batch, off;
     uint32_t *hX, *hZ, *hS;   /* [nl][batch] */
+    const uint8_t *param;     /* next to sigma: the parametrisation of every curve (below); NULL: Suyama's throughout */
 } gecm_mod_build;
 /* GECM_ERR_NOMEM, 1 if some curve was marked bad, else 0 */
 int gecm_mod_build_slice(void *build, size_t lo, size_t hi);
+
+/* GMP-ECM's PARAM 1 and PARAM 3 curves: B y^2 = x^3 + A x^2 + x with (A+2)/4 = d, start point (2 : 1),
+ * d = sigma^2 / 2^64 mod N with 1 <= sigma < 2^64 (PARAM 1) or sigma / 2^32 mod N with 1 <= sigma < 2^32 (PARAM 3).  The
+ * one place the two formulae live on the host: gecm_param_s and the host build both come here.
+ * gecm_mod_param_sigma_ok: is sigma in the range of param (1 or 3)?   gecm_mod_param_unit: 2^-64 or 2^-32 mod N (N odd).
+ * gecm_mod_param_d: d from sigma and that unit. */
+int gecm_mod_param_sigma_ok(int param, uint64_t sigma);
+void gecm_mod_param_unit(mpl_t *unit, int param, const mpl_t *N);
+void gecm_mod_param_d(mpl_t *d, int param, uint64_t sigma, const mpl_t *unit, const mpl_t *N);
 
 /* the failed-inversion record of the curve at position k of hfail ([planes][nl][batch]): 0 or a divisor of N */
 void gecm_mod_fail_record(const gecm_mod *m, const uint32_t *hfail, uint32_t planes, size_t batch, size_t k, mpl_t *g);

@@ -75,9 +75,11 @@ static int name_is(const char *p, const char *e, const char *name)
     return (size_t)(e - p) == n && memcmp(p, name, n) == 0;
 }
 
-int gecm_parse_resume_line(const char *line, gecm_resume_rec *rec)
+/* the body of gecm_parse_resume_line (param == NULL: PARAM 0 only) and of gecm_parse_resume_line_param */
+static int parse_line(const char *line, gecm_resume_rec *rec, int *param)
 {
-    if (!line || !rec) { set_err("gecm_parse_resume_line: bad argument"); return GECM_ERR_ARG; }
+    uint64_t prm = 0;
+    int have_param = 0;
     memset(rec, 0, sizeof *rec);
     const char *p = line;
     while (is_space(*p)) p++;
@@ -99,7 +101,7 @@ int gecm_parse_resume_line(const char *line, gecm_resume_rec *rec)
             int rc = GECM_OK;
             const int again = (name_is(ns, ne, "SIGMA") && have_sigma) || (name_is(ns, ne, "B1") && have_b1) ||
                               (name_is(ns, ne, "N") && rec->n.digits) || (name_is(ns, ne, "X") && rec->x.digits) ||
-                              (name_is(ns, ne, "Z") && rec->z.digits);
+                              (name_is(ns, ne, "Z") && rec->z.digits) || (param && name_is(ns, ne, "PARAM") && have_param);
             if (again) {                              /* two lines run together, most likely */
                 set_err("gecm_parse_resume_line: field %.*s appears twice", (int)(ne - ns), ns);
                 return GECM_ERR_ARG;
@@ -108,11 +110,16 @@ int gecm_parse_resume_line(const char *line, gecm_resume_rec *rec)
                 if (!name_is(vs, ve, "ECM")) { set_err("gecm_parse_resume_line: field METHOD is not ECM"); return GECM_ERR_ARG; }
             }
             else if (name_is(ns, ne, "PARAM")) {
-                uint64_t prm = 0;
                 rc = take_u64("PARAM", vs, ve, &prm);
-                if (!rc && prm != 0) {
+                have_param = 1;
+                if (!rc && !param && prm != 0) {
                     set_err("gecm_parse_resume_line: field PARAM = %llu: only PARAM 0 (Suyama's sigma) curves can be resumed",
                             (unsigned long long)prm);
+                    return GECM_ERR_ARG;
+                }
+                if (!rc && prm != GECM_PARAM_SUYAMA && prm != GECM_PARAM_BATCH_SQUARE && prm != GECM_PARAM_BATCH_32) {
+                    set_err("gecm_parse_resume_line_param: field PARAM = %llu: curves of PARAM 0, 1 and 3 can be resumed (PARAM 2 "
+                            "takes a point multiplication on another curve to get its curve)", (unsigned long long)prm);
                     return GECM_ERR_ARG;
                 }
             } else if (name_is(ns, ne, "SIGMA")) {
@@ -132,8 +139,26 @@ int gecm_parse_resume_line(const char *line, gecm_resume_rec *rec)
     const char *missing = !have_sigma ? "SIGMA" : !have_b1 ? "B1" : !rec->n.digits ? "N"
                           : !rec->x.digits ? "X" : NULL;
     if (missing) { set_err("gecm_parse_resume_line: field %s is missing", missing); return GECM_ERR_ARG; }
-    if (rec->sigma < 6) { set_err("gecm_parse_resume_line: field SIGMA = %llu is below 6", (unsigned long long)rec->sigma); return GECM_ERR_ARG; }
+    if (prm == GECM_PARAM_SUYAMA && rec->sigma < 6) { set_err("gecm_parse_resume_line: field SIGMA = %llu is below 6", (unsigned long long)rec->sigma); return GECM_ERR_ARG; }
+    if (prm != GECM_PARAM_SUYAMA && !gecm_mod_param_sigma_ok((int)prm, rec->sigma)) {
+        set_err("gecm_parse_resume_line_param: field SIGMA = %llu is outside [1, 2^%d), the range of PARAM %d",
+                (unsigned long long)rec->sigma, prm == GECM_PARAM_BATCH_SQUARE ? 64 : 32, (int)prm);
+        return GECM_ERR_ARG;
+    }
+    if (param) *param = (int)prm;
     return GECM_OK;
+}
+
+int gecm_parse_resume_line(const char *line, gecm_resume_rec *rec)
+{
+    if (!line || !rec) { set_err("gecm_parse_resume_line: bad argument"); return GECM_ERR_ARG; }
+    return parse_line(line, rec, NULL);
+}
+
+int gecm_parse_resume_line_param(const char *line, gecm_resume_rec *rec, int *param)
+{
+    if (!line || !rec || !param) { set_err("gecm_parse_resume_line_param: bad argument"); return GECM_ERR_ARG; }
+    return parse_line(line, rec, param);
 }
 
 int gecm_stage1_resume_range(uint64_t B1, uint64_t b1_field, uint32_t *range)
@@ -159,11 +184,12 @@ int gecm_stage1_resume_range(uint64_t B1, uint64_t b1_field, uint32_t *range)
  * multiplier, every prime power BELOW the B1 field, which within one prime range is k_std(field - 1); above one range
  * the reference's stage 1 is no prime-power product at all.  Anything else — AVX-ECM-STD, GMP-ECM, no PROGRAM — is a
  * standard line and complete to its field. */
-int gecm_resume_line_std_bound(const char *line, uint64_t *from)
+static int std_bound(const char *line, uint64_t *from, int with_param)
 {
     gecm_resume_rec rec;
+    int prm;
     if (!from) { set_err("gecm_resume_line_std_bound: bad argument"); return GECM_ERR_ARG; }
-    int rc = gecm_parse_resume_line(line, &rec);
+    int rc = with_param ? gecm_parse_resume_line_param(line, &rec, &prm) : gecm_parse_resume_line(line, &rec);
     if (rc) return rc;
     int reference = 0;
     for (const char *p = line; *p; ) {
@@ -191,6 +217,9 @@ int gecm_resume_line_std_bound(const char *line, uint64_t *from)
     *from = rec.b1 - 1;
     return GECM_OK;
 }
+
+int gecm_resume_line_std_bound(const char *line, uint64_t *from) { return std_bound(line, from, 0); }
+int gecm_resume_line_std_bound_param(const char *line, uint64_t *from) { return std_bound(line, from, 1); }
 
 /* the hash of the host sources this object was compiled from (Makefile: H_SHA); gecm_version() compares them */
 #ifdef GECM_MANIFEST_FN

@@ -185,6 +185,17 @@ EXPORTS += ["gecm_stage1_extend_segments", "gecm_stage1_describe_extend", "gecm_
             "gecm_normalize_points", "gecm_points_normalized", "gecm_format_save_line_std", "gecm_resume_line_std_bound"]
 
 
+# the parametrisations of a curve: Suyama's sigma, GMP-ECM's batch modes d = sigma^2 / 2^64 and sigma / 2^32
+PARAM_SUYAMA, PARAM_BATCH_SQUARE, PARAM_BATCH_32 = 0, 1, 3
+_sig("gecm_param_s", c_int, c_int, c_u64, c_char_p, c_char_p, c_size_t)
+_sig("gecm_set_next_params", c_int, c_void_p, ctypes.POINTER(ctypes.c_uint8), c_size_t)
+_sig("gecm_curve_param", c_int, c_void_p, c_size_t)
+_sig("gecm_parse_resume_line_param", c_int, c_char_p, ctypes.POINTER(ResumeRec), ctypes.POINTER(c_int))
+_sig("gecm_resume_line_std_bound_param", c_int, c_char_p, ctypes.POINTER(c_u64))
+EXPORTS += ["gecm_param_s", "gecm_set_next_params", "gecm_curve_param", "gecm_parse_resume_line_param",
+            "gecm_resume_line_std_bound_param"]
+
+
 class GecmError(RuntimeError):
     pass
 
@@ -219,18 +230,44 @@ def describe_range(b1, b2, r):
 ResumeLine = collections.namedtuple("ResumeLine", "sigma b1 n x z")
 
 
-def parse_resume_line(line):
-    """ResumeLine of one resume line, None for a line to skip (blank or '#'); GecmError names the field that is wrong"""
+# the same with the line's parametrisation (PARAM absent: 0)
+ResumeLineParam = collections.namedtuple("ResumeLineParam", "sigma b1 n x z param")
+
+
+def _parse_line(line, with_param):
     raw = line.encode() if isinstance(line, str) else bytes(line)
     buf = ctypes.create_string_buffer(raw)
     rec = ResumeRec()
-    if _chk(lib.gecm_parse_resume_line(buf, ctypes.byref(rec)), "gecm_parse_resume_line") == 1:
+    param = c_int(0)
+    if with_param:
+        rc = _chk(lib.gecm_parse_resume_line_param(buf, ctypes.byref(rec), ctypes.byref(param)), "gecm_parse_resume_line_param")
+    else:
+        rc = _chk(lib.gecm_parse_resume_line(buf, ctypes.byref(rec)), "gecm_parse_resume_line")
+    if rc == 1:
         return None
 
     def num(f):
         off = f.digits - ctypes.addressof(buf)
         return int(raw[off:off + f.len], f.base)
-    return ResumeLine(rec.sigma, rec.b1, num(rec.n), num(rec.x), num(rec.z) if rec.z.digits else 1)
+    fields = (rec.sigma, rec.b1, num(rec.n), num(rec.x), num(rec.z) if rec.z.digits else 1)
+    return ResumeLineParam(*fields, param.value) if with_param else ResumeLine(*fields)
+
+
+def parse_resume_line(line):
+    """ResumeLine of one resume line, None for a line to skip (blank or '#'); GecmError names the field that is wrong"""
+    return _parse_line(line, False)
+
+
+def parse_resume_line_param(line):
+    """parse_resume_line with PARAM 0, 1 and 3 accepted: ResumeLineParam, the same fields and the parametrisation"""
+    return _parse_line(line, True)
+
+
+def param_s(param, sigma, n):
+    """s = (A+2)/4 = d of the PARAM 1 (sigma^2 / 2^64) or PARAM 3 (sigma / 2^32) curve of sigma modulo n"""
+    buf = ctypes.create_string_buffer(2048)
+    _chk(lib.gecm_param_s(param, sigma, str(n).encode(), buf, len(buf)), "gecm_param_s")
+    return int(buf.value.decode(), 16)
 
 
 def stage1_resume_range(b1, field):
@@ -251,12 +288,14 @@ def describe_extend(b1_from, b1_to, seg):
     return d
 
 
-def resume_line_std_bound(line):
+def resume_line_std_bound(line, params=False):
     """the standard bound the points of a resume line are complete to (None for a line to skip): B1 - 1 for a line of the
-    reference semantic (PROGRAM=AVX-ECM) within one prime range, the B1 field for every other line"""
+    reference semantic (PROGRAM=AVX-ECM) within one prime range, the B1 field for every other line; params=True reads
+    the line as parse_resume_line_param does"""
     raw = line.encode() if isinstance(line, str) else bytes(line)
     b = c_u64(0)
-    if _chk(lib.gecm_resume_line_std_bound(raw, ctypes.byref(b)), "gecm_resume_line_std_bound") == 1:
+    fn = "gecm_resume_line_std_bound_param" if params else "gecm_resume_line_std_bound"
+    if _chk(getattr(lib, fn)(raw, ctypes.byref(b)), fn) == 1:
         return None
     return b.value
 
@@ -343,10 +382,26 @@ class Engine:
         return self.unpack(inv, n), self.unpack(g, n)
 
     # ---- L1 ----
-    def build_curves(self, sigmas):
+    def _next_params(self, params, batch):
+        # the parametrisation of every curve of the build that follows (one-shot); None: a build as always
+        if params is None:
+            return
+        if len(params) != batch:
+            raise ValueError("params: one parametrisation (0, 1 or 3) per sigma")
+        arr = (ctypes.c_uint8 * max(1, batch))(*[p if 0 <= p < 256 else 255 for p in params])
+        _chk(lib.gecm_set_next_params(self._h, arr, batch), "gecm_set_next_params")
+
+    def build_curves(self, sigmas, params=None):
+        """params: per curve 0 (Suyama, sigma >= 6), 1 (d = sigma^2 / 2^64, 1 <= sigma < 2^64) or 3 (d = sigma / 2^32,
+        1 <= sigma < 2^32); None: every curve 0"""
         arr = (c_u64 * len(sigmas))(*sigmas)
+        self._next_params(params, len(sigmas))
         self.batch = len(sigmas)
         return _chk(lib.gecm_build_curves(self._h, arr, len(sigmas)), "gecm_build_curves")
+
+    def curve_param(self, k):
+        """the parametrisation curve k was built with"""
+        return _chk(lib.gecm_curve_param(self._h, k), "gecm_curve_param")
 
     def set_curve_build(self, where):
         """"host" (default) or "device": where the next build_curves / resume makes the curves; the batch holds the same
@@ -369,13 +424,14 @@ class Engine:
         self.batch = len(X)
         _chk(lib.gecm_upload_points(self._h, self.pack(X), self.pack(Z), self.pack(s), len(X)), "gecm_upload_points")
 
-    def resume(self, sigmas, xs, zs, b1_done=0):
+    def resume(self, sigmas, xs, zs, b1_done=0, params=None):
         """start from the plain residues of save or checkpoint lines: mid stage 1 (go on with stage1_range), or with
-        b1_done = B1 as after stage1(B1)"""
+        b1_done = B1 as after stage1(B1); params as for build_curves"""
         if not len(sigmas) == len(xs) == len(zs):
             raise ValueError("resume: one x and one z per sigma")
         self._fits(xs, zs)
         arr = (c_u64 * len(sigmas))(*sigmas)
+        self._next_params(params, len(sigmas))
         self.batch = len(sigmas)
         return _chk(lib.gecm_resume_points(self._h, arr, self.pack(xs), self.pack(zs), len(sigmas), b1_done),
                     "gecm_resume_points")
@@ -390,17 +446,20 @@ class Engine:
         rep = getattr(self, "_report_modulus", None)
         return [self.n if rep is None else int(rep, 0) if isinstance(rep, str) else int(rep)]
 
-    def _resume_recs(self, recs, ns, b1_done):
-        return self.resume([r.sigma for r in recs], [r.x for r in recs], [r.z for r in recs], b1_done=b1_done)
+    def _resume_recs(self, recs, ns, b1_done, params=None):
+        return self.resume([r.sigma for r in recs], [r.x for r in recs], [r.z for r in recs], b1_done=b1_done, params=params)
 
-    def resume_lines(self, lines, b1_done=0):
+    def resume_lines(self, lines, b1_done=0, params=False):
         """resume() from the text of resume lines (skipped lines dropped); every N must be the context's (on a
-        MultiEngine: one of its numbers, which decides the curve's modulus)"""
-        recs = [r for r in map(parse_resume_line, lines) if r is not None]
+        MultiEngine: one of its numbers, which decides the curve's modulus).  params=True: lines of PARAM 0, 1 and 3
+        are read (parse_resume_line_param) and every curve is built by its line's parametrisation"""
+        recs = [r for r in map(parse_resume_line_param if params else parse_resume_line, lines) if r is not None]
         ns = self._line_moduli()
         for k, r in enumerate(recs):
             if r.n not in ns:
                 raise ValueError("resume_lines: line %d is on N = %d, not a number of this context" % (k, r.n))
+        if params:
+            return self._resume_recs(recs, ns, b1_done, [r.param for r in recs])
         return self._resume_recs(recs, ns, b1_done)
 
     def stage1(self, b1, sync=True):
@@ -612,22 +671,24 @@ class MultiEngine(Engine):
         self.n = max(self.ns)
         self.batch = 0
 
-    def build_curves(self, sigmas, which):
-        """curve k: sigma sigmas[k] on number ns[which[k]]"""
+    def build_curves(self, sigmas, which, params=None):
+        """curve k: sigma sigmas[k] on number ns[which[k]]; params as for Engine.build_curves"""
         if len(which) != len(sigmas):
             raise ValueError("build_curves: one modulus index per sigma")
         arr = (c_u64 * len(sigmas))(*sigmas)
         idx = (ctypes.c_uint32 * len(which))(*which)
+        self._next_params(params, len(sigmas))
         self.batch = len(sigmas)
         return _chk(lib.gecm_build_curves_multi(self._h, arr, idx, len(sigmas)), "gecm_build_curves_multi")
 
-    def resume(self, sigmas, which, xs, zs, b1_done=0):
+    def resume(self, sigmas, which, xs, zs, b1_done=0, params=None):
         """Engine.resume with curve k on number ns[which[k]]; xs, zs below that number"""
         if not len(sigmas) == len(which) == len(xs) == len(zs):
             raise ValueError("resume: one modulus index, one x and one z per sigma")
         self._fits(xs, zs)
         arr = (c_u64 * len(sigmas))(*sigmas)
         idx = (ctypes.c_uint32 * len(which))(*which)
+        self._next_params(params, len(sigmas))
         self.batch = len(sigmas)
         return _chk(lib.gecm_resume_points_multi(self._h, arr, idx, self.pack(xs), self.pack(zs), len(sigmas), b1_done),
                     "gecm_resume_points_multi")
@@ -646,9 +707,9 @@ class MultiEngine(Engine):
     def _line_moduli(self):
         return self.ns
 
-    def _resume_recs(self, recs, ns, b1_done):
+    def _resume_recs(self, recs, ns, b1_done, params=None):
         return self.resume([r.sigma for r in recs], [ns.index(r.n) for r in recs], [r.x for r in recs],
-                           [r.z for r in recs], b1_done=b1_done)
+                           [r.z for r in recs], b1_done=b1_done, params=params)
 
     def modulus_of(self, k):
         return _chk(lib.gecm_curve_modulus(self._h, k), "gecm_curve_modulus")

@@ -114,6 +114,37 @@ int gecm_get_curve_build(const gecm_ctx *ctx);
  * gecm_upload_points' third argument.  GECM_ERR_STATE on a multi-modulus context, like gecm_download_points. */
 int gecm_download_s(gecm_ctx *ctx, void *s);
 
+/* ---- GMP-ECM's other parametrisations ----------------------------------------------
+ * GMP-ECM 7 writes PARAM 1 on 64-bit CPUs at ordinary B1 and PARAM 3 from its GPU stage 1; both are curves
+ * B y^2 = x^3 + A x^2 + x with A = 4d - 2, so s = (A+2)/4 = d, and the start point (X : Z) = (2 : 1):
+ *   GECM_PARAM_BATCH_SQUARE (1): d = sigma^2 / 2^64 mod N, 1 <= sigma < 2^64;
+ *   GECM_PARAM_BATCH_32     (3): d = sigma / 2^32 mod N,   1 <= sigma < 2^32.
+ * No inversion is involved: such a curve never sets a build flag and never makes a build call return 1.  sigma = 0
+ * (d = 0, a singular curve) is refused; d = 1 (A = 2) is singular too, is not looked for and finds nothing.  PARAM 2 and
+ * every value above 3 stay refused.  Their stage-1 multiplier is the standard one: a fresh PARAM 1 or 3 curve is run with
+ * gecm_stage1_extend(ctx, 1, B1); gecm_stage1 stays allowed and writes PROGRAM=AVX-ECM lines, as on any batch.
+ * gecm_param_s: s = d for param 1 or 3 in lower-case hex without prefix; returns the digit count.  Pure host code, no
+ *   context.  GECM_ERR_ARG for param 0 (its s needs the inversion rule of a build), 2 and above, a SIGMA out of range, a
+ *   bad N (odd, >= 3, decimal or 0x-hex) or a buffer too small.
+ * gecm_set_next_params: the parametrisation of each curve of the NEXT gecm_build_curves, gecm_build_curves_multi,
+ *   gecm_resume_points or gecm_resume_points_multi (the caller's order), as gecm_set_curve_build says where it runs.
+ *   One-shot: that call takes the setting and clears it, whether it succeeds or not; param == NULL clears a pending one.
+ *   Values other than 0, 1, 3 and batch == 0 are GECM_ERR_ARG.  A build whose batch differs from `batch`, or whose sigma
+ *   is outside its parametrisation's range (sigma >= 6 for the PARAM 0 curves of the call), answers GECM_ERR_ARG and keeps
+ *   the previous batch.  Mixed batches are allowed.  The PARAM 0 curves get exactly the words, flags, failure records and
+ *   return value they get without a setting; the others X = 2, Z = 1, s = d (a resume: the caller's X and Z, s = d).
+ *   With GECM_BUILD_DEVICE the Suyama kernel runs over the batch if it holds a PARAM 0 curve, then k_build_param
+ *   overwrites the other curves; gecm_last_kernel_ms is the sum.  Without a pending setting every call is what it was.
+ * gecm_curve_param: the parametrisation of the caller's curve k; 0 for every batch built without a setting.
+ * Save lines carry it: gecm_format_save_line_std writes the curve's PARAM=, gecm_format_save_line and
+ * gecm_format_resume_line insert "PARAM=%d; " after "METHOD=ECM; " for a curve whose parametrisation is not 0. */
+#define GECM_PARAM_SUYAMA 0
+#define GECM_PARAM_BATCH_SQUARE 1
+#define GECM_PARAM_BATCH_32 3
+int gecm_param_s(int param, uint64_t sigma, const char *n_str, char *hex, size_t hexlen);
+int gecm_set_next_params(gecm_ctx *ctx, const uint8_t *param, size_t batch);
+int gecm_curve_param(const gecm_ctx *ctx, size_t k);
+
 /* ---- input preparation (main.c:393-527) -----------------------------------------------------
  * What the reference's main() does to its first argument before any curve is built: evaluate the
  * expression (calc.c), recognise N | 2^k - 1, N | 2^k + 1 or 2^k = c (mod N) with c below one limb
@@ -392,6 +423,11 @@ typedef struct {
     gecm_resume_num n, x, z;
 } gecm_resume_rec;
 int gecm_parse_resume_line(const char *line, gecm_resume_rec *rec);
+/* The same with GMP-ECM's PARAM 1 and 3 accepted and returned in *param (PARAM absent: 0).  The SIGMA range follows the
+ * parametrisation: >= 6 for PARAM 0, [1, 2^64) for PARAM 1, [1, 2^32) for PARAM 3.  PARAM 2, PARAM >= 4 and a PARAM
+ * field given twice are refused with a text naming the field.  gecm_parse_resume_line itself keeps refusing PARAM 1 and 3:
+ * a caller that takes such lines says so by calling this one, and hands *param on to gecm_set_next_params. */
+int gecm_parse_resume_line_param(const char *line, gecm_resume_rec *rec, int *param);
 /* The range a run to B1 goes on with from lines whose B1 field is b1_field.  b1_field == B1: *range =
  * gecm_stage1_ranges(B1), stage 1 is complete (save lines).  Else the r + 1 for which range r of a run to B1 ends at
  * prime b1_field and writes a checkpoint (gecm_stage1_describe_range(B1, B1, r): last_prime, checkpoint); that can be
@@ -451,7 +487,7 @@ int gecm_stage1_extend(gecm_ctx *ctx, uint64_t from, uint64_t to);
  * launches after a normalisation run modulo N.  After it gecm_last_kernel_ms is the normalisation kernel's time.
  * gecm_points_normalized: 1 after a normalisation, until the next stage-1 launch, build, upload or resume.
  * gecm_format_save_line_std writes curve k's standard line at the context's B1,
- *   "METHOD=ECM; PARAM=0; SIGMA=%llu; B1=%llu; N=0x%s; X=0x%s; PROGRAM=AVX-ECM-STD;\n"
+ *   "METHOD=ECM; PARAM=%d; SIGMA=%llu; B1=%llu; N=0x%s; X=0x%s; PROGRAM=AVX-ECM-STD;\n"   (PARAM: gecm_curve_param)
  * (with "X=0x%s; Z=0x%s;" for a curve left as it was); GECM_ERR_STATE if the batch is not normalised.
  * gecm_parse_resume_line reads both shapes.  Returns the line length, or < 0. */
 int gecm_normalize_points(gecm_ctx *ctx);
@@ -463,6 +499,8 @@ int gecm_format_save_line_std(gecm_ctx *ctx, size_t k, char *buf, size_t buflen)
  * Any other or no PROGRAM (ours with -STD, GMP-ECM's): *from = the B1 field.  Pure host code, no context; returns what
  * gecm_parse_resume_line returns for a line it refuses or skips. */
 int gecm_resume_line_std_bound(const char *line, uint64_t *from);
+/* the same for a caller that reads its lines with gecm_parse_resume_line_param: PARAM 1 and 3 lines have a bound too */
+int gecm_resume_line_std_bound_param(const char *line, uint64_t *from);
 
 #ifdef __cplusplus
 }
