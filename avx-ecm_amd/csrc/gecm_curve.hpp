@@ -421,3 +421,154 @@ __device__ __forceinline__ void run_tape_pair(const uint32_t *__restrict__ tape,
         }
     }
 }
+
+// ======================================================================================
+// One residue per lane: Pollard's P-1 and Williams' P+1 on the same tape.
+//
+// PRAC generates a Lucas chain, and its tape drives x^k and V_k(x) unchanged when a "point" is one residue:
+//   add T = X + Y, difference W:  P-1: X*Y       P+1: X*Y - W       (V_{m+n} = V_m V_n - V_{m-n})
+//   dup D = 2X:                   P-1: X^2       P+1: X^2 - 2
+// `pp1` is wave-uniform (a kernel argument) and turns the two subtractions on.  P-1 needs nothing but the multiply:
+// every value is a product (< 0.675 K, normalised limbs).
+//
+// P+1: fe_sub wants a subtrahend with normalised limbs below K, and here the subtrahend W is an earlier
+// T = X*Y - W' (lazy: below 1.675 K, limbs up to 3*2^28).  So the subtraction itself leaves a normalised value
+// below K: with a = X*Y (a product) and b = W (normalised, < K), two carry chains run side by side,
+//   p = a + K' - b  (unsigned; K' >= b limb by limb)      q = a - b  (signed, borrow chain)
+// and the result is q where a >= b (then q < 0.675 K) and p where a < b (then 0 <= p < K).  Either way it is
+// a - b modulo K, fully normalised, below K: a legal subtrahend and a legal multiply operand (< 1.675 K), so A, B and C
+// of the chain always hold such values and no bias is widened.  The 2 of the doubling is 2R mod N, canonical, made from
+// R mod N where a doubling needs it (doublings are a tenth of the events).
+template <int NL>
+__device__ __forceinline__ uint32_t kp_limb(const ModK<NL> &m, int i) { return m.kp[i]; }
+template <int NL>
+__device__ __forceinline__ uint32_t kp_limb(const ModV<NL> &m, int i) { return m.kp[i * 64]; }
+
+template <int NL>
+__device__ __forceinline__ void fe_get(Fe<NL> &r, const Fe<NL> &a) { r = a; }
+
+// r = a - b or a - b + K, whichever is in [0, K): normalised limbs.  a, b: normalised limbs, b < K, a < K.
+template <int NL, class MOD>
+__device__ __forceinline__ void fe_sub_full(Fe<NL> &r, const Fe<NL> &a, const Fe<NL> &b, const MOD &m)
+{
+    Fe<NL> p, q;
+    uint32_t cp = 0;
+    int32_t cq = 0;
+#pragma unroll
+    for (int i = 0; i < NL; i++) {
+        const uint32_t u = a.v[i] + kp_limb(m, i) - b.v[i] + cp;
+        const int32_t s = (int32_t)a.v[i] - (int32_t)b.v[i] + cq;
+        p.v[i] = (i == NL - 1) ? u : (u & GECM_LIMB_MASK);
+        q.v[i] = (i == NL - 1) ? (uint32_t)s : ((uint32_t)s & GECM_LIMB_MASK);
+        cp = u >> GECM_LIMB_BITS;
+        cq = s >> GECM_LIMB_BITS;           // arithmetic: 0 or -1
+    }
+    const bool neg = (int32_t)q.v[NL - 1] < 0;
+#pragma unroll
+    for (int i = 0; i < NL; i++) r.v[i] = neg ? p.v[i] : q.v[i];
+}
+
+// c R mod N for c = 1 or 2, canonical, from `one` = R mod N (an Fe, or an FeG among a lane's constants)
+template <int NL, class ONE, class MOD>
+__device__ __forceinline__ void unit_const(Fe<NL> &r, const ONE &one, bool twice, const MOD &m)
+{
+    fe_get(r, one);
+    if (twice) {
+        uint32_t c = 0;
+#pragma unroll
+        for (int i = 0; i < NL; i++) {
+            const uint32_t u = 2u * r.v[i] + c;
+            r.v[i] = (i == NL - 1) ? u : (u & GECM_LIMB_MASK);
+            c = u >> GECM_LIMB_BITS;
+        }
+        fe_cond_sub_n(r, m);                // 2 (R mod N) < 2N
+    }
+}
+
+// Run a tape on the residue in A.  Returns with the result in A: a product or a value of fe_sub_full.
+// Same tape, same renamings as run_tape; A, B, C are one Fe each and stay in registers at every limb count.
+template <int NL, class ONE, class MOD>
+__device__ __forceinline__ void run_tape_unit(const uint32_t *__restrict__ tape, uint32_t tape_len, Fe<NL> &A, bool pp1,
+                                              const ONE &one, const MOD &m)
+{
+    Fe<NL> B = A, C = A;
+    auto fetch = [&](uint32_t pc) -> uint32_t {
+        uint32_t w = tape[pc >> 2];
+        return __builtin_amdgcn_readfirstlane((w >> ((pc & 3u) * 8u)) & 0xffu);
+    };
+    uint32_t nxt = tape_len ? fetch(0) : GECM_OP_NOP;
+    for (uint32_t pc = 0; pc < tape_len; pc++) {
+        uint32_t op = nxt;
+        nxt = (pc + 1 < tape_len) ? fetch(pc + 1) : GECM_OP_NOP;
+        // rule 3: T = B + A (C); (B,T,C) <- (T,C,B)
+        while ((op & ~GECM_OP_SWAP) == (GECM_OP_STEP | GECM_OP_RULE3)) {
+            if (op & GECM_OP_SWAP) {
+                Fe<NL> t = A;
+                A = B;
+                B = t;
+            }
+            Fe<NL> T;
+            fe_mul(T, B, A, m);
+            if (pp1) fe_sub_full(T, T, C, m);
+            C = B;
+            B = T;
+            pc++;
+            op = nxt;
+            nxt = (pc + 1 < tape_len) ? fetch(pc + 1) : GECM_OP_NOP;
+        }
+        if (op == GECM_OP_NOP) continue;
+        const uint32_t rule = op & GECM_OP_RULE_MASK;
+        const bool is_step = op >= GECM_OP_STEP;
+        const bool do_add = op != GECM_OP_PRAC_BEGIN;
+        const bool do_dup = op != GECM_OP_PRAC_END;
+        if (is_step && (op & GECM_OP_SWAP)) {
+            Fe<NL> t = A;
+            A = B;
+            B = t;
+        }
+        if (is_step && rule == GECM_OP_RULE5) {
+            Fe<NL> t = B;
+            B = C;
+            C = t;
+        } else if (is_step && rule == GECM_OP_RULE9) {
+            Fe<NL> t = A;
+            A = B;
+            B = C;
+            C = t;
+        } else if (op == GECM_OP_PRAC_BEGIN) {
+            B = A;
+            C = A;
+        }
+        Fe<NL> T, D;
+        if (do_add) {                               // T = B + A, difference C
+            fe_mul(T, B, A, m);
+            if (pp1) fe_sub_full(T, T, C, m);
+        }
+        if (do_dup) {                               // D = 2A
+            fe_sqr(D, A, m);
+            if (pp1) {
+                Fe<NL> two;
+                unit_const(two, one, true, m);
+                fe_sub_full(D, D, two, m);
+            }
+        }
+        if (op == GECM_OP_PRAC_END) {
+            A = T;
+        } else if (op == GECM_OP_PRAC_BEGIN) {
+            A = D;
+        } else if (rule == GECM_OP_RULE4) {
+            B = T;
+            A = D;
+        } else if (rule == GECM_OP_RULE5) {
+            Fe<NL> t = C;
+            C = T;
+            B = t;
+            A = D;
+        } else {
+            Fe<NL> oldA = C;
+            C = T;
+            B = D;
+            A = oldA;
+        }
+    }
+}

@@ -146,6 +146,15 @@ int gecm_dev_s2_download(gecm_dev *d, uint32_t *acc, uint32_t *fail);
  * 1 < gcd(value, N) < N; g = the gcds ([limb][curve]); either output may be NULL. */
 int gecm_dev_gcd_scan(gecm_dev *d, int which, uint32_t *flags, uint32_t *g);
 
+/* ---- P-1 and P+1 stage 1: one residue per lane, in X of the batch (gecm_dev_upload_plain with z = 1) ----
+ * gecm_dev_stage1_unit: the tape of gecm_dev_set_tape on every residue, x <- x^E (P-1) or V_E(x) (P+1), canonical;
+ * asynchronous like gecm_dev_stage1, one lane per residue, any kind of context (lane-packed where the per-lane kernels
+ * are built).  gecm_dev_gcd_scan_off: gecm_dev_gcd_scan of x - off, off = 1 (P-1) or 2 (P+1). */
+#define GECM_UNIT_PM1 1
+#define GECM_UNIT_PP1 2
+int gecm_dev_stage1_unit(gecm_dev *d, int method);
+int gecm_dev_gcd_scan_off(gecm_dev *d, uint32_t off, uint32_t *flags, uint32_t *g);
+
 #ifdef __cplusplus
 }
 #endif

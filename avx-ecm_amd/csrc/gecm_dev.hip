@@ -695,6 +695,48 @@ extern "C" int gecm_dev_stage1(gecm_dev *d, int lanes_per_curve)
     return 0;
 }
 
+/* P-1 / P+1 stage 1: the tape on one residue per lane, cut into launches as gecm_dev_stage1 cuts it
+ * (between two prac() calls only A is live here too).  method: GECM_UNIT_PM1 or GECM_UNIT_PP1. */
+extern "C" int gecm_dev_stage1_unit(gecm_dev *d, int method)
+{
+    HIPCHK(hipSetDevice(d->device));
+    if (ready(d, "gecm_dev_stage1_unit", false)) return -2;
+    if (!d->dTape) {
+        g_err = "gecm_dev_stage1_unit: no tape";
+        return -2;
+    }
+    if (method != GECM_UNIT_PM1 && method != GECM_UNIT_PP1) {
+        g_err = "gecm_dev_stage1_unit: the method must be P-1 or P+1";
+        return -2;
+    }
+    if (d->multi && d->lane_packed && !d->k1->has_lane) {
+        g_err = "gecm_dev_stage1_unit: no per-lane kernels at this limb count";
+        return -2;
+    }
+    char nm[96];
+    snprintf(nm, sizeof nm, "%s<%d>", !d->multi ? "k_unit" : d->lane_packed ? "k_unit_lane" : "k_unit_multi", d->nl);
+    d->last_lanes = 1;
+    d->last_kernel = nm;
+    gecm_modconst mc = modconst(d);
+    HIPCHK(hipEventRecord(d->ev0, d->stream));
+    d->cut_launches = d->tape_cuts.size() - 1;
+    while (d->cut_events.size() < d->cut_launches) {
+        hipEvent_t e;
+        HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        d->cut_events.push_back(e);
+    }
+    for (size_t cut = 0; cut + 1 < d->tape_cuts.size(); cut++) {
+        const uint32_t *tp = d->dTape + d->tape_cuts[cut] / 4;
+        const uint32_t tl = (uint32_t)(d->tape_cuts[cut + 1] - d->tape_cuts[cut]);
+        d->k1->stage1_unit(d->stream, &mc, tp, tl, d->dX, d->dZ, d->stride, method == GECM_UNIT_PP1);
+        HIPCHK(hipEventRecord(d->cut_events[cut], d->stream));
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(d->ev1, d->stream));
+    d->timed = true;
+    return 0;
+}
+
 /* launches of the last gecm_dev_stage1 that have finished / that it made (a long tape runs as several) */
 extern "C" int gecm_dev_stage1_progress(gecm_dev *d, uint32_t *done, uint32_t *total)
 {
@@ -1052,6 +1094,26 @@ extern "C" int gecm_dev_gcd_scan(gecm_dev *d, int which, uint32_t *flags, uint32
     if (grow(&d->dFlags, &d->flags_cap, d->stride)) return -1;
     gecm_modconst mc = modconst(d);
     d->k1->gcd_scan(d->stream, &mc, src, d->dT0, d->dFlags, d->stride);
+    HIPCHK(hipGetLastError());
+    if (flags && d->ncurves)
+        HIPCHK(hipMemcpyAsync(flags, d->dFlags, d->ncurves * 4, hipMemcpyDeviceToHost, d->stream));
+    if (g && download_soa(d, g, d->dT0)) return -1;
+    HIPCHK(hipStreamSynchronize(d->stream));
+    return 0;
+}
+
+/* the factor scan of a P-1 / P+1 batch: gcd(x - off, N) for the residues in X, off = 1 or 2 */
+extern "C" int gecm_dev_gcd_scan_off(gecm_dev *d, uint32_t off, uint32_t *flags, uint32_t *g)
+{
+    HIPCHK(hipSetDevice(d->device));
+    if (off != 1 && off != 2) {
+        g_err = "gecm_dev_gcd_scan_off: the offset is 1 or 2";
+        return -2;
+    }
+    if (ready(d, "gecm_dev_gcd_scan_off", true)) return -2;
+    if (grow(&d->dFlags, &d->flags_cap, d->stride)) return -1;
+    gecm_modconst mc = modconst(d);
+    d->k1->gcd_scan_off(d->stream, &mc, d->dX, d->dT0, d->dFlags, d->stride, off);
     HIPCHK(hipGetLastError());
     if (flags && d->ncurves)
         HIPCHK(hipMemcpyAsync(flags, d->dFlags, d->ncurves * 4, hipMemcpyDeviceToHost, d->stream));

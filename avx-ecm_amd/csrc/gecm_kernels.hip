@@ -244,6 +244,48 @@ k_stage1_pair_f(const uint32_t *__restrict__ tape, uint32_t tape_len, uint32_t *
 }
 #undef GECM_STAGE1_PAIR_BODY
 
+// One residue per lane: P-1 and P+1 stage 1 (gecm_curve.hpp, run_tape_unit).  X of position idx is the
+// residue; out come its canonical Montgomery form and Z = R mod N.  pp1 != 0: P+1, else P-1 (wave-uniform).
+#define GECM_UNIT_BODY                                                          \
+    uint32_t idx = blockIdx.x * 64u + threadIdx.x;                              \
+    Fe<NL> P;                                                                   \
+    fe_load(P, X, stride, idx);                                                 \
+    run_tape_unit<NL>(tape, tape_len, P, pp1 != 0, k.one, k.m);                 \
+    Fe<NL> o;                                                                   \
+    fe_canonical_mont(o, P, k.one, k.m);                                        \
+    fe_store(X, stride, idx, o);                                                \
+    fe_store(Z, stride, idx, k.one);
+
+template <int NL>
+__global__ void __launch_bounds__(64, 2)
+k_unit(const uint32_t *__restrict__ tape, uint32_t tape_len, uint32_t *__restrict__ X, uint32_t *__restrict__ Z,
+       size_t stride, uint32_t pp1, ModArgs<NL> k)
+{
+    GECM_ARG_CONSTS
+    GECM_UNIT_BODY
+}
+
+template <int NL>
+__global__ void __launch_bounds__(64, 2)
+k_unit_multi(const uint32_t *__restrict__ tape, uint32_t tape_len, uint32_t *__restrict__ X, uint32_t *__restrict__ Z,
+             size_t stride, uint32_t pp1, ModGroups<NL> g)
+{
+    GECM_WAVE_CONSTS(ModArgs<NL>, blockIdx.x)
+    GECM_UNIT_BODY
+}
+
+#if GECM_HAS_LANE
+template <int NL>
+__global__ void __launch_bounds__(64, 2)
+k_unit_lane(const uint32_t *__restrict__ tape, uint32_t tape_len, uint32_t *__restrict__ X, uint32_t *__restrict__ Z,
+            size_t stride, uint32_t pp1, LaneGroups<NL> g)
+{
+    GECM_LANE_CONSTS
+    GECM_UNIT_BODY
+}
+#endif
+#undef GECM_UNIT_BODY
+
 // Eight lanes per curve (gecm_quad.hpp).
 // 256-thread workgroups (four independent wavefronts): this kernel needs about 65 registers, and one-wavefront
 // workgroups of such a kernel are not spread evenly by a cold dispatcher — see gecm_rowk.hip; its first launch of a
@@ -447,6 +489,9 @@ k_l0_inv(const uint32_t *__restrict__ A, uint32_t *__restrict__ C, uint32_t *__r
     uint32_t idx = blockIdx.x * 64u + threadIdx.x;                              \
     Fe<NL> v, c, t, gcd;                                                        \
     fe_load(v, V, stride, idx);                                                 \
+    GECM_GCD_SCAN_TAIL
+// the scan of the value in v
+#define GECM_GCD_SCAN_TAIL                                                      \
     fe_canonical_mont(c, v, k.one, k.m);                                        \
     fe_invert(t, gcd, c, k.m, k.inv_iters);                                     \
     bool is_one = gcd.v[0] == 1u, is_n = true;                                  \
@@ -487,6 +532,48 @@ k_gcd_scan_lane(const uint32_t *__restrict__ V, uint32_t *__restrict__ G, uint32
 }
 #endif
 #undef GECM_GCD_SCAN_BODY
+
+// The scan of a P-1 / P+1 batch: v = X - c R mod N for c = off = 1 or 2 (X canonical, Montgomery form:
+// the residue x of the method, so v stands for x - 1 or x - 2), then the same scan.  Kernels of their own: k_gcd_scan*
+// keep their code.
+#define GECM_GCD_SCAN_OFF_BODY                                                  \
+    uint32_t idx = blockIdx.x * 64u + threadIdx.x;                              \
+    Fe<NL> v, c, t, gcd;                                                        \
+    fe_load(c, V, stride, idx);                                                 \
+    unit_const(t, k.one, off == 2u, k.m);                                       \
+    fe_sub(v, c, t, k.m);                                                       \
+    GECM_GCD_SCAN_TAIL
+
+template <int NL>
+__global__ void __launch_bounds__(64, 2)
+k_gcd_scan_off(const uint32_t *__restrict__ V, uint32_t *__restrict__ G, uint32_t *__restrict__ flags, size_t stride,
+               uint32_t off, S2Const<NL> k)
+{
+    GECM_ARG_CONSTS
+    GECM_GCD_SCAN_OFF_BODY
+}
+
+template <int NL>
+__global__ void __launch_bounds__(64, 2)
+k_gcd_scan_off_multi(const uint32_t *__restrict__ V, uint32_t *__restrict__ G, uint32_t *__restrict__ flags, size_t stride,
+                     uint32_t off, ModGroups<NL> g)
+{
+    GECM_WAVE_CONSTS(S2Const<NL>, blockIdx.x)
+    GECM_GCD_SCAN_OFF_BODY
+}
+
+#if GECM_HAS_LANE
+template <int NL>
+__global__ void __launch_bounds__(64, 2)
+k_gcd_scan_off_lane(const uint32_t *__restrict__ V, uint32_t *__restrict__ G, uint32_t *__restrict__ flags, size_t stride,
+                    uint32_t off, LaneGroups<NL> g)
+{
+    GECM_LANE_CONSTS
+    GECM_GCD_SCAN_OFF_BODY
+}
+#endif
+#undef GECM_GCD_SCAN_OFF_BODY
+#undef GECM_GCD_SCAN_TAIL
 
 // ---------------------------------------------------------------- curve construction
 // The Suyama construction of one curve per lane (build_one_curve, ecm.c:1548-1803; on the host: suyama_pre and the tail
@@ -1134,6 +1221,20 @@ static void launch_build_param(void *stream, const gecm_modconst *mc, const uint
                                                     k_build_param_multi<GECM_NL>, nullptr, sigma, param, X, Z, S, flags, stride);
 }
 
+static void launch_stage1_unit(void *stream, const gecm_modconst *mc, const uint32_t *tape, uint32_t tape_len, uint32_t *X,
+                               uint32_t *Z, size_t stride, int pp1)
+{
+    launch_by_source<ModArgs<GECM_NL>>(stream, mc, blocks_of(stride), k_unit<GECM_NL>, k_unit_multi<GECM_NL>,
+                                       GECM_LANE(k_unit_lane), tape, tape_len, X, Z, stride, (uint32_t)(pp1 != 0));
+}
+
+static void launch_gcd_scan_off(void *stream, const gecm_modconst *mc, const uint32_t *V, uint32_t *G, uint32_t *flags,
+                                size_t stride, uint32_t off)
+{
+    launch_by_source<S2Const<GECM_NL>>(stream, mc, blocks_of(stride), k_gcd_scan_off<GECM_NL>, k_gcd_scan_off_multi<GECM_NL>,
+                                       GECM_LANE(k_gcd_scan_off_lane), V, G, flags, stride, off);
+}
+
 static void pack_group(const gecm_devmod *m, void *out)
 {
     const GroupConst<GECM_NL> c = {s2_const(m), r2_const(m)};
@@ -1144,7 +1245,8 @@ extern "C" const gecm_kernels_p1 *CAT(CAT(gecm_kernels_, GECM_NL), _p1)(void)
 {
     static const gecm_kernels_p1 t = {launch_stage1, launch_canon, launch_from_mont, launch_to_mont, launch_l0, launch_l0_inv,
                                       launch_gcd_scan, launch_build, FPolicy<GECM_NL>::G, pack_group, sizeof(GroupConst<GECM_NL>),
-                                      GECM_MANIFEST, GECM_HAS_LANE, launch_normalize, launch_build_param};
+                                      GECM_MANIFEST, GECM_HAS_LANE, launch_normalize, launch_build_param,
+                                      launch_stage1_unit, launch_gcd_scan_off};
     return &t;
 }
 #endif

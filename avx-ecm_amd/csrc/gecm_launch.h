@@ -128,6 +128,13 @@ struct gecm_kernels_p1 {
      * the curves with param 0 keep what they hold.  Needs mc->m.r2, never inverts; a multi-modulus mc as for build. */
     void (*build_param)(void *stream, const gecm_modconst *mc, const uint64_t *sigma, const uint8_t *param, uint32_t *X,
                         uint32_t *Z, uint32_t *S, uint32_t *flags, size_t stride);
+    /* P-1 (pp1 = 0) and P+1 (pp1 != 0) stage 1 on the tape: one residue per lane, X <- x^E or V_E(x)
+     * in canonical Montgomery form, Z <- R mod N.  Generic REDC; any mc, a lane-packed one where has_lane. */
+    void (*stage1_unit)(void *stream, const gecm_modconst *mc, const uint32_t *tape, uint32_t tape_len, uint32_t *X,
+                        uint32_t *Z, size_t stride, int pp1);
+    /* gcd_scan of V - off R mod N, off = 1 or 2: the factor test of a P-1 / P+1 residue in Montgomery form */
+    void (*gcd_scan_off)(void *stream, const gecm_modconst *mc, const uint32_t *V, uint32_t *G, uint32_t *flags,
+                         size_t stride, uint32_t off);
 };
 
 /* Part 2: stage 2 (any mc takes K = 1, 2, .. 32; a lane-packed one at limb counts with has_lane). */

@@ -6,6 +6,8 @@
  *     avx-ecm -x FILE B1 [B2]                               (take resume lines to a higher B1, run_resume)
  *     avx-ecm -g -r FILE B1 [B2],  avx-ecm -g -x FILE B1 [B2]  (the same two, lines of GMP-ECM's PARAM 1 and 3 accepted)
  *     avx-ecm -p PARAM input curves B1 [B2] [sigma]         (a fresh run in standard mode, PARAM 0, 1 or 3, run_param)
+ *     avx-ecm -m pm1|pp1 input B1 [x0]                      (P-1 or P+1 stage 1 on one number, run_method)
+ *     avx-ecm -m pm1|pp1 -f FILE B1,  avx-ecm -m pm1|pp1 -x FILE B1   (on a list of inputs; P-1 / P+1 lines on to B1)
  *
  * Same positional arguments as the reference (main.c:380-384, 459-460, 537-559) and the same FILES, byte for byte:
  * save_b1.txt (GMP-ECM resume lines, ecm.c:1372-1380), ecm_results.txt (factor lines, ecm.c:1356-1367, 1510-1522)
@@ -1663,6 +1665,337 @@ static int run_param(int argc, char **argv)
     return R.failed ? 2 : 0;
 }
 
+
+/* ---- avx-ecm -m pm1|pp1 ...: P-1 and P+1 stage 1 -------------------------------------------------------
+ *     avx-ecm -m pm1|pp1 input B1 [x0]     one number; x0 decimal or 0x-hex, below the number
+ *     avx-ecm -m pm1|pp1 -f FILE B1        every input of FILE (one expression per line, as -f reads it)
+ *     avx-ecm -m pm1|pp1 -x FILE B1        the P-1 / P+1 lines of FILE (of the method named) on to B1
+ * Seeds when none is given: P-1 x0 = 3; P+1 two residues per number, x0 = 2/7 mod N and 6/5 mod N, the customary pair; a
+ * number for which 7 or 5 has no inverse reports that gcd as its factor and gets no residue for it.  A pass is one
+ * context: a single-N one for one number, else a multi-modulus one, closed when it is full (FULL_BATCH positions, or
+ * GECM_PASS_CURVES), when the next number falls on the other side of lane packing's 415-bit line under GECM_PACKING=lane,
+ * and (-x) when the next number's lines are complete to another bound or differ in whether they name their seed.  A pass
+ * goes through the extension segments from its bound to B1 one by one: checkpoint.txt gets the standard lines after every
+ * segment but the last, save_b1.txt those at B1, then the factor scan, and every factor one line in ecm_results.txt and on
+ * stdout.  There is no stage 2: a B2 argument is refused.  -x groups and refuses as avx-ecm -x does: consecutive lines on
+ * one N are a group, the same N in two places is refused, so are lines of one N complete to different bounds, a bound
+ * above B1, ECM lines and lines of the other method.  Everything is checked before anything runs or is written. */
+static const char *method_usage = "usage: avx-ecm -m pm1|pp1 $input $B1 [$x0]\n"
+                                  "       avx-ecm -m pm1|pp1 -f $file $B1     (one input expression per line)\n"
+                                  "       avx-ecm -m pm1|pp1 -x $file $B1     (P-1 / P+1 resume lines, taken on to $B1)\n"
+                                  "       (stage 1 only: there is no $B2)\n";
+
+typedef struct {
+    char ndec[MPL_MAXL * 10 + 16];
+    mpl_t n;
+    int nbits;
+    size_t index;              /* of the input: its place in FILE, 0 for the one of the command line */
+    uint64_t from;             /* the bound its residues are complete to (1: fresh) */
+    int known;                 /* its residues name their seed */
+} mnum_t;
+
+typedef struct {
+    size_t num;                /* its number */
+    mpl_t x0, x;
+} mres_t;
+
+static void vec_set(const gecm_config *cfg, void *vec, size_t lane, size_t batch, const mpl_t *v)
+{
+    if (cfg->digitbits == 52) mpl_to_limbs64((uint64_t *)vec + lane, batch, cfg->nwords, 52, v);
+    else mpl_to_limbs32((uint32_t *)vec + lane, batch, cfg->nwords, 32, v);
+}
+
+static void append_lines(const char *file, gecm_ctx *c, size_t count)
+{
+    FILE *f = fopen(file, "a");
+    static char line[MPL_MAXL * 40];
+    if (!f) { fprintf(stderr, "cannot write %s\n", file); exit(2); }
+    for (size_t k = 0; k < count; k++)
+        if (gecm_format_save_line_std(c, k, line, sizeof line) > 0) fputs(line, f);
+    fclose(f);
+}
+
+/* one pass: the numbers nums[0 .. nn) and their residues res[0 .. nr) (res[r].num counts from nums[0]) */
+static int method_pass(int method, const mnum_t *nums, size_t nn, const mres_t *res, size_t nr, uint64_t B1, int packing)
+{
+    const char *mname = method == GECM_METHOD_PM1 ? "P-1" : "P+1";
+    const uint64_t from = nums[0].from;
+    const int known = nums[0].known, fresh = from == 1 && known;
+    gecm_ctx *c = NULL;
+    int rc;
+    if (nn == 1) rc = gecm_create(&c, 0, nums[0].ndec, GECM_CLI_DIGITBITS);
+    else {
+        const char **ns = (const char **)malloc(nn * sizeof *ns);
+        if (!ns) { fprintf(stderr, "out of memory\n"); exit(2); }
+        for (size_t i = 0; i < nn; i++) ns[i] = nums[i].ndec;
+        rc = gecm_create_multi(&c, 0, ns, nn, GECM_CLI_DIGITBITS);
+        free(ns);
+        if (!rc) rc = gecm_set_multi_packing(c, packing);
+    }
+    gecm_config cfg;
+    if (!rc) rc = gecm_get_config(c, &cfg);
+    void *x0 = NULL, *x = NULL;
+    uint32_t *which = NULL;
+    if (!rc) {
+        const size_t bytes = nr * (size_t)cfg.nwords * (cfg.digitbits == 52 ? 8 : 4);
+        x0 = calloc(1, bytes);
+        x = calloc(1, bytes);
+        which = (uint32_t *)malloc(nr * sizeof *which);
+        if (!x0 || !x || !which) { fprintf(stderr, "out of memory\n"); exit(2); }
+        for (size_t r = 0; r < nr; r++) {
+            which[r] = (uint32_t)res[r].num;
+            if (known) vec_set(&cfg, x0, r, nr, &res[r].x0);
+            vec_set(&cfg, x, r, nr, &res[r].x);
+        }
+        rc = nn == 1 ? gecm_build_seeds(c, method, known ? x0 : NULL, fresh ? NULL : x, nr, from)
+                     : gecm_build_seeds_multi(c, method, which, known ? x0 : NULL, fresh ? NULL : x, nr, from);
+    }
+    const int nseg = rc ? 0 : gecm_stage1_extend_segments(from, B1);
+    double ms = 0;
+    for (int seg = 0; seg < nseg && !rc; seg++) {
+        rc = gecm_stage1_extend_segment(c, from, B1, (uint32_t)seg) || gecm_sync(c);
+        ms += gecm_last_kernel_ms(c);
+        if (!rc && seg + 1 < nseg) append_lines("checkpoint.txt", c, nr);
+    }
+    int found = 0;
+    if (!rc) {
+        append_lines("save_b1.txt", c, nr);
+        found = gecm_scan_factors(c, 1, NULL);
+        if (found < 0) rc = found;
+    }
+    if (rc) fprintf(stderr, "%s\n", gecm_last_error());
+    for (size_t r = 0; r < nr && !rc && found > 0; r++) {
+        static char fac[4096], seed[MPL_MAXL * 10 + 16], line[4096 + MPL_MAXL * 10 + 512];
+        int prp = 0;
+        if (!gecm_curve_flag(c, 1, r) || gecm_stage1_factor(c, r, fac, sizeof fac, &prp) != 1) continue;
+        if (gecm_curve_seed(c, r, seed, sizeof seed) > 0)
+            snprintf(line, sizeof line, "\nfound %s%d factor %s by %s (B1 = %lu): input %zu, x0 0x%s\n", prp ? "PRP" : "C",
+                     gecm_sizeinbase10(fac), fac, mname, (unsigned long)B1, nums[res[r].num].index, seed);
+        else
+            snprintf(line, sizeof line, "\nfound %s%d factor %s by %s (B1 = %lu): input %zu, x0 unknown\n", prp ? "PRP" : "C",
+                     gecm_sizeinbase10(fac), fac, mname, (unsigned long)B1, nums[res[r].num].index);
+        fputs(line, stdout);
+        FILE *f = fopen("ecm_results.txt", "a");
+        if (!f) { fprintf(stderr, "cannot write ecm_results.txt\n"); exit(2); }
+        fputs(line, f);
+        fclose(f);
+    }
+    if (!rc) {
+        char kn[128] = "";
+        gecm_last_kernel_name(c, kn, sizeof kn);
+        printf("%s pass: %zu number%s, %zu residue%s, B1 %lu -> %lu in %d segment%s, %s%s, %1.4f seconds of kernels\n", mname, nn,
+               nn == 1 ? "" : "s", nr, nr == 1 ? "" : "s", (unsigned long)from, (unsigned long)B1, nseg, nseg == 1 ? "" : "s", kn,
+               nn == 1 ? "" : gecm_get_multi_packing(c) == GECM_PACK_LANE ? ", lane-packed" : ", wave-packed", ms / 1000.0);
+    }
+    if (c) gecm_destroy(c);
+    free(x0); free(x); free(which);
+    return rc ? 2 : 0;
+}
+
+/* a small-factor line for a number whose P+1 seed a/b does not exist: gcd(b, N) */
+static void seed_factor_line(text_t *t, const mpl_t *g, uint64_t B1, size_t index, const char *seed)
+{
+    static char fac[MPL_MAXL * 10 + 16];
+    mpl_get_dec(fac, g);
+    text_printf(t, "\nfound %s%d factor %s by P+1 (B1 = %lu): input %zu, x0 %s has no inverse\n", mpl_probab_prime(g, 3) ? "PRP" : "C",
+                gecm_sizeinbase10(fac), fac, (unsigned long)B1, index, seed);
+}
+
+static int run_method(int argc, char **argv)
+{
+    if (argc < 5) { printf("%s", method_usage); return 1; }
+    const int method = !strcmp(argv[2], "pm1") ? GECM_METHOD_PM1 : !strcmp(argv[2], "pp1") ? GECM_METHOD_PP1 : 0;
+    if (!method) { printf("-m %s: the methods offered are pm1 (P-1) and pp1 (P+1)\n%s", argv[2], method_usage); return 1; }
+    const int from_file = !strcmp(argv[3], "-f"), from_lines = !strcmp(argv[3], "-x");
+    const int listed = from_file || from_lines;
+    if (listed ? argc != 6 : argc > 6) { printf("-m: stage 1 only: there is no stage 2, and no $B2 argument\n%s", method_usage); return 1; }
+    const char *b1s = listed ? argv[5] : argv[4];
+    char *end = NULL;
+    const double b1d = strtod(b1s, &end);
+    if (!*b1s || *end || !(b1d >= 2) || b1d > 1e12) { printf("-m: B1 must be in [2, 10^12]\n%s", method_usage); return 1; }
+    const uint64_t B1 = (uint64_t)b1d;
+    const int packing = cli_packing();
+    if (packing < 0) return 1;
+    const double t_start = now();
+    const size_t per = method == GECM_METHOD_PP1 ? 2 : 1;       /* fresh residues per number */
+
+    mnum_t *nums = NULL;
+    mres_t *res = NULL;
+    size_t nn = 0, nr = 0, cap_n = 0, cap_r = 0;
+    text_t early = {0};                                          /* the factor lines of seeds that do not exist */
+    FILE *f = listed ? fopen(argv[4], "r") : NULL;
+    if (listed && !f) { printf("cannot read %s\n%s", argv[4], method_usage); return 1; }
+    char *text = NULL;
+    size_t text_cap = 0, lineno = 0, input = 0;
+    int bad = 0;
+    for (;;) {
+        static char prep_log[65536];
+        const char *expr = NULL;
+        gecm_resume_rec rec;
+        gecm_resume_num seed = {NULL, 0, 0};
+        int prm = 0, meth = 0;
+        if (!listed) {
+            if (input) break;
+            expr = argv[3];
+        } else {
+            if (getline(&text, &text_cap, f) <= 0) break;
+            lineno++;
+            if (from_file) {
+                char *q = text, *e;
+                while (*q == ' ' || *q == '\t') q++;
+                e = q + strlen(q);
+                while (e > q && (e[-1] == '\n' || e[-1] == '\r' || e[-1] == ' ' || e[-1] == '\t')) *--e = 0;
+                if (!*q || *q == '#') continue;
+                expr = q;
+            } else {
+                const int rc = gecm_parse_resume_line_method(text, &rec, &prm, &meth, &seed);
+                if (rc == 1) continue;
+                if (rc) { printf("%s line %zu: %s\n", argv[4], lineno, gecm_last_error()); bad = 1; break; }
+                if (meth != method) {
+                    printf("%s line %zu: a METHOD=%s line: avx-ecm -m %s -x takes %s lines\n", argv[4], lineno,
+                           meth == GECM_METHOD_ECM ? "ECM" : meth == GECM_METHOD_PM1 ? "P-1" : "P+1", argv[2],
+                           method == GECM_METHOD_PM1 ? "P-1" : "P+1");
+                    bad = 1;
+                    break;
+                }
+            }
+        }
+        if (nn + 1 > cap_n) { cap_n = cap_n ? 2 * cap_n : 64; nums = (mnum_t *)realloc(nums, cap_n * sizeof *nums); }
+        if (nr + 2 > cap_r) { cap_r = cap_r ? 2 * cap_r : 128; res = (mres_t *)realloc(res, cap_r * sizeof *res); }
+        if (!nums || !res) { fprintf(stderr, "out of memory\n"); return 2; }
+        if (!from_lines) {
+            mnum_t *m = &nums[nn];
+            gecm_input_info inf;
+            if (gecm_prepare_input(expr, GECM_CLI_DIGITBITS, m->ndec, sizeof m->ndec, &inf, prep_log, sizeof prep_log)) {
+                fputs(prep_log, stdout);
+                printf("input must evaluate to an odd integer >= 3 (operators + - * / %% ^ ! # fib() luc())\n");
+                bad = 1;
+                break;
+            }
+            mpl_set_str(&m->n, m->ndec);
+            m->nbits = inf.nbits;
+            m->index = input++;
+            m->from = 1;
+            m->known = 1;
+            size_t made = 0;
+            if (!listed && argc == 6) {                          /* the seed of the command line */
+                mres_t *r = &res[nr];
+                if (mpl_set_str(&r->x0, argv[5]) || mpl_cmp(&r->x0, &m->n) >= 0) { printf("-m: x0 must be a number below the input\n%s", method_usage); bad = 1; break; }
+                r->x = r->x0;
+                r->num = nn;
+                made = 1;
+            } else
+                for (size_t k = 0; k < per; k++) {
+                    static const uint64_t num[3] = {3, 2, 6}, den[3] = {1, 7, 5};
+                    static const char *name[3] = {"3", "2/7", "6/5"};
+                    const size_t w = method == GECM_METHOD_PM1 ? 0 : 1 + k;
+                    mpl_t a, b, inv;
+                    mres_t *r = &res[nr + made];
+                    mpl_set_u64(&a, num[w]);
+                    mpl_set_u64(&b, den[w]);
+                    mpl_mod(&a, &a, &m->n);
+                    mpl_mod(&b, &b, &m->n);
+                    if (!mpl_invmod(&inv, &b, &m->n)) {
+                        mpl_t g;
+                        mpl_gcd(&g, &b, &m->n);
+                        if (mpl_is_zero(&b)) g = m->n;
+                        if (mpl_cmp(&g, &m->n) < 0) seed_factor_line(&early, &g, B1, m->index, name[w]);
+                        continue;
+                    }
+                    mpl_mulmod(&r->x0, &a, &inv, &m->n);
+                    r->x = r->x0;
+                    r->num = nn;
+                    made++;
+                }
+            if (made) { nr += made; nn++; }
+            continue;
+        }
+        /* -x: one line */
+        mpl_t n, v;
+        rnum(&n, &rec.n);
+        if (!mpl_is_odd(&n) || mpl_cmp_u64(&n, 3) < 0) { printf("%s line %zu: field N must be an odd number >= 3\n", argv[4], lineno); bad = 1; break; }
+        uint64_t from = 0;
+        if (gecm_resume_line_std_bound_method(text, &from)) { printf("%s line %zu: %s\n", argv[4], lineno, gecm_last_error()); bad = 1; break; }
+        if (from < 1 || from > B1) {
+            printf("%s line %zu: the line is complete to B1 = %lu, which is not in [1, %lu]: stage 1 is extended upwards only\n", argv[4],
+                   lineno, (unsigned long)from, (unsigned long)B1);
+            bad = 1;
+            break;
+        }
+        if (!nn || mpl_cmp(&n, &nums[nn - 1].n) != 0) {
+            mnum_t *m = &nums[nn];
+            m->n = n;
+            mpl_get_dec(m->ndec, &n);
+            m->nbits = mpl_bits(&n);
+            m->index = nn;
+            m->from = from;
+            m->known = seed.digits != NULL;
+            for (size_t k = 0; k < nn && !bad; k++)
+                if (mpl_cmp(&nums[k].n, &n) == 0) {
+                    printf("%s line %zu: lines on this N stand further up as well, with another N between: put the lines on one "
+                           "number together\n", argv[4], lineno);
+                    bad = 1;
+                }
+            if (bad) break;
+            nn++;
+        }
+        mnum_t *m = &nums[nn - 1];
+        if (from != m->from) {
+            printf("%s line %zu: the line is not complete to the bound %lu of the lines on this N before it\n", argv[4], lineno, (unsigned long)m->from);
+            bad = 1;
+            break;
+        }
+        if (m->known && !seed.digits) m->known = 0;             /* one line without its seed: the number's lines omit it */
+        mres_t *r = &res[nr];
+        rnum(&r->x, &rec.x);
+        if (seed.digits) rnum(&r->x0, &seed);
+        else mpl_set_u64(&r->x0, 0);
+        rnum(&v, &rec.x);
+        if (mpl_cmp(&v, &n) >= 0 || mpl_cmp(&r->x0, &n) >= 0) { printf("%s line %zu: X or X0 is not below N\n", argv[4], lineno); bad = 1; break; }
+        r->num = nn - 1;
+        nr++;
+    }
+    if (f) fclose(f);
+    free(text);
+    if (!bad && !nr && !early.len) { printf("%s holds no %s\n%s", listed ? argv[4] : argv[3], from_lines ? "resume line" : "input", method_usage); bad = 1; }
+    if (bad) { free(nums); free(res); free(early.buf); return 1; }
+    if (gecm_device_count() < 1) { fprintf(stderr, "no HIP device visible\n"); return 2; }
+    printf("starting process %d: %s stage 1 to B1 = %lu on %zu number%s, %zu residue%s\n", (int)getpid(),
+           method == GECM_METHOD_PM1 ? "P-1" : "P+1", (unsigned long)B1, nn, nn == 1 ? "" : "s", nr, nr == 1 ? "" : "s");
+    if (early.len) {
+        fputs(early.buf, stdout);
+        FILE *rf = fopen("ecm_results.txt", "a");
+        if (!rf) { fprintf(stderr, "cannot write ecm_results.txt\n"); return 2; }
+        fputs(early.buf, rf);
+        fclose(rf);
+    }
+    /* the passes: numbers in order, closed by size, by the packing's line, by the bound and by whether seeds are known */
+    const size_t cap = env_count("GECM_PASS_CURVES") ? (size_t)env_count("GECM_PASS_CURVES") : FULL_BATCH;
+    int rc = 0;
+    size_t r0 = 0;
+    for (size_t n0 = 0; n0 < nn && rc != 2; ) {
+        const int pk = packing == GECM_PACK_LANE && fits_lane_packing(nums[n0].nbits) ? GECM_PACK_LANE : GECM_PACK_WAVE;
+        size_t n1 = n0, r1 = r0, positions = 0;
+        while (n1 < nn) {
+            size_t cnt = 0;
+            while (r1 + cnt < nr && res[r1 + cnt].num == n1) cnt++;
+            const int pk1 = packing == GECM_PACK_LANE && fits_lane_packing(nums[n1].nbits) ? GECM_PACK_LANE : GECM_PACK_WAVE;
+            const size_t add = pk == GECM_PACK_LANE ? cnt : gecm_multi_positions(&cnt, 1, GECM_PACK_WAVE);
+            if (n1 > n0 && (pk1 != pk || nums[n1].from != nums[n0].from || nums[n1].known != nums[n0].known || positions + add > cap)) break;
+            positions += add;
+            r1 += cnt;
+            n1++;
+        }
+        for (size_t r = r0; r < r1; r++) res[r].num -= n0;
+        rc = method_pass(method, nums + n0, n1 - n0, res + r0, r1 - r0, B1, pk);
+        n0 = n1;
+        r0 = r1;
+    }
+    free(nums); free(res); free(early.buf);
+    printf("Process took %1.4f seconds.\n", now() - t_start);
+    return rc;
+}
+
 int main(int argc, char **argv)
 {
     if (argc > 1 && strcmp(argv[1], "-f") == 0) return run_file(argc, argv);
@@ -1676,5 +2009,6 @@ int main(int argc, char **argv)
         return 1;
     }
     if (argc > 1 && strcmp(argv[1], "-p") == 0) return run_param(argc, argv);
+    if (argc > 1 && strcmp(argv[1], "-m") == 0) return run_method(argc, argv);
     return run_single(argc, argv);
 }

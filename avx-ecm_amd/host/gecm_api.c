@@ -150,6 +150,10 @@ struct gecm_ctx {
     /* GECM_PACK_WAVE / GECM_PACK_LANE: asked for (gecm_set_multi_packing), used by the last build.  Lane
      * packing lays the groups back to back and pads only the batch's tail; every lane then carries its own modulus. */
     int packing, packing_used;
+    /* P-1 / P+1 batch (gecm_build_seeds): GECM_METHOD_PM1 / _PP1, one residue per position in X, Z = 1;
+     * seed = the plain x0 of every position, [nl][batch] in device order, NULL when the caller did not know it */
+    int method;
+    uint32_t *seed;
 };
 #define GECM_PAD 0xffffffffu
 
@@ -158,6 +162,16 @@ struct gecm_ctx {
 static int multi_refuse(const char *fn)
 {
     set_err("%s: not available on a multi-modulus context (gecm_create_multi)", fn);
+    return GECM_ERR_STATE;
+}
+
+static const char *method_name(int method) { return method == GECM_METHOD_PM1 ? "P-1" : method == GECM_METHOD_PP1 ? "P+1" : "ECM"; }
+
+/* what a P-1 / P+1 batch cannot do (include/gecm.h): 0 for a batch of curves */
+static int method_refuse(const gecm_ctx *c, const char *fn)
+{
+    if (!c || !c->method || c->batch == 0) return 0;
+    set_err("%s: not available on a %s batch (gecm_build_seeds): it holds residues, not curves", fn, method_name(c->method));
     return GECM_ERR_STATE;
 }
 
@@ -395,6 +409,9 @@ static void free_batch(gecm_ctx *c)
     c->normalized = 0;
     free(c->param);
     c->param = NULL;
+    free(c->seed);
+    c->seed = NULL;
+    c->method = GECM_METHOD_ECM;
     free(c->sigma); free(c->bad); free(c->hx); free(c->hz); free(c->hacc); free(c->hfail);
     free(c->flags[0]); free(c->flags[1]); free(c->hg[0]); free(c->hg[1]);
     c->flags[0] = c->flags[1] = NULL;
@@ -912,6 +929,13 @@ static int stage1_launch(gecm_ctx *c, const tape_key *key, uint64_t B1, int firs
     c->normalized = 0;
     c->scan_valid[0] = c->scan_valid[1] = 0;
     if (idle) return GECM_OK;
+    if (c->method) {                 /* one residue per lane, generic multiply: no layouts, no twin */
+        c->twin.ran_last = 0;
+        if (gecm_dev_stage1_unit(c->dev, c->method == GECM_METHOD_PP1 ? GECM_UNIT_PP1 : GECM_UNIT_PM1)) {
+            set_err("%s", gecm_dev_error());
+            return GECM_ERR_DEVICE;
+        }
+    } else {
     /* For a batch small enough for the eight-lane layout (generic moduli only) that layout beats the special
      * multiply in its two-lane form: 1.5x against 1.4x at 15 limbs, 2.2-2.4x at 30-37 limbs. */
     const int want = c->lanes_per_curve ? c->lanes_per_curve : gecm_dev_auto_lanes(c->dev);
@@ -930,6 +954,7 @@ static int stage1_launch(gecm_ctx *c, const tape_key *key, uint64_t B1, int firs
         c->twin.loaded = 0;       /* the F-form copy of the points no longer matches */
         if (gecm_dev_stage1(c->dev, c->lanes_per_curve)) { set_err("%s", gecm_dev_error()); return GECM_ERR_DEVICE; }
     }
+    }
     if (next && !c->pf_active) {
         /* while the device runs this range: the next one's tape (2 s of host time per 1e8 primes on 8 threads) */
         c->pf_k = *next;
@@ -944,6 +969,7 @@ int gecm_stage1_range(gecm_ctx *c, uint64_t B1, uint32_t range)
     const int settled = ff_settle(c);
     if (settled) return settled;
     if (!c || c->batch == 0) { set_err("gecm_stage1: no curves uploaded"); return GECM_ERR_STATE; }
+    if (method_refuse(c, "gecm_stage1")) return GECM_ERR_STATE;
     if (B1 < 2 || B1 > GECM_B1_MAX) { set_err("gecm_stage1: B1 must be in [2, %llu]", (unsigned long long)GECM_B1_MAX); return GECM_ERR_ARG; }
     if (lane_packing_refuses(c)) return GECM_ERR_STATE;
     const uint32_t nranges = gecm_stage1_ranges_u(B1);
@@ -987,7 +1013,7 @@ int gecm_stage1_extend_segment(gecm_ctx *c, uint64_t from, uint64_t to, uint32_t
     int rc = extend_args("gecm_stage1_extend", from, to);
     if (rc) return rc;
     if (!c || c->batch == 0) { set_err("gecm_stage1_extend: no curves uploaded"); return GECM_ERR_STATE; }
-    if (lane_packing_refuses(c)) return GECM_ERR_STATE;
+    if (!c->method && lane_packing_refuses(c)) return GECM_ERR_STATE;
     const uint32_t nseg = gecm_extend_segments_plan(from, to);
     if (seg >= nseg) { set_err("gecm_stage1_extend_segment: the extension from %llu to %llu has %u segment(s)", (unsigned long long)from, (unsigned long long)to, nseg); return GECM_ERR_ARG; }
     tape_key key = {1, 0, 0}, next = {1, 0, 0};
@@ -1114,6 +1140,7 @@ int gecm_download_points(gecm_ctx *c, void *X, void *Z)
 int gecm_download_s(gecm_ctx *c, void *s)
 {
     if (c && c->multi) return multi_refuse("gecm_download_s");
+    if (method_refuse(c, "gecm_download_s")) return GECM_ERR_STATE;
     if (!c || !s || c->batch == 0) return GECM_ERR_ARG;
     const size_t batch = c->batch;
     uint32_t *h = (uint32_t *)malloc((size_t)c->mod.nl * batch * 4);
@@ -1186,6 +1213,7 @@ int gecm_format_resume_line(gecm_ctx *c, size_t k, uint64_t b1_label, char *buf,
     size_t pos;
     const gecm_mod *m = c && buf ? curve_at(c, k, &pos) : NULL;
     if (!m) return GECM_ERR_ARG;
+    if (method_refuse(c, "gecm_format_save_line")) return GECM_ERR_STATE;
     int rc = fetch_plain(c);
     if (rc) return rc;
     static __thread char hn[MPL_MAXL * 10 + 2], hxs[MPL_MAXL * 10 + 2], hzs[MPL_MAXL * 10 + 2];
@@ -1217,6 +1245,13 @@ int gecm_stage1_factor(gecm_ctx *c, size_t k, char *dec, size_t declen, int *is_
      * of this batch has run, its gcd is used; otherwise it is computed here. */
     if (c->scan_valid[0] && c->hg[0]) {
         mpl_from_limbs32(&g, c->hg[0] + pos, c->batch, m->nl, LIMB_BITS);
+    } else if (c->method) {                          /* gcd(x - 1, N) or gcd(x - 2, N); x - c = 0 gives g = N: no factor */
+        mpl_t off;
+        mpl_set_u64(&off, c->method == GECM_METHOD_PP1 ? 2 : 1);
+        mpl_mod(&off, &off, &m->N);
+        mpl_from_limbs32(&z, c->hx + pos, c->batch, m->nl, LIMB_BITS);
+        mpl_submod(&z, &z, &off, &m->N);
+        mpl_gcd(&g, &z, &m->N);
     } else {
         mpl_from_limbs32(&z, c->hz + pos, c->batch, m->nl, LIMB_BITS);
         mpl_gcd(&g, &z, &m->N);
@@ -1230,6 +1265,7 @@ int gecm_normalize_points(gecm_ctx *c)
     const int settled = ff_settle(c);
     if (settled) return settled;
     if (!c || c->batch == 0) { set_err("gecm_normalize_points: no curves uploaded"); return GECM_ERR_STATE; }
+    if (method_refuse(c, "gecm_normalize_points")) return GECM_ERR_STATE;
     if (!c->multi && c->mod.have_report) {
         set_err("gecm_normalize_points: not with a report modulus (gecm_set_report_modulus): x modulo the context's "
                 "modulus is not x modulo the number the lines name");
@@ -1257,11 +1293,35 @@ int gecm_normalize_points(gecm_ctx *c)
 
 int gecm_points_normalized(const gecm_ctx *c) { return c && c->batch && c->normalized; }
 
+/* the standard line of a P-1 / P+1 residue (include/gecm.h): no SIGMA, no Z, X0 when the seed is known */
+static int format_method_line(gecm_ctx *c, const gecm_mod *m, size_t pos, char *buf, size_t buflen)
+{
+    int rc = fetch_plain(c);
+    if (rc) return rc;
+    static __thread char hn[MPL_MAXL * 10 + 2], hxs[MPL_MAXL * 10 + 2], h0[MPL_MAXL * 10 + 16];
+    mpl_t v;
+    mpl_get_hex(hn, &m->N);
+    mpl_from_limbs32(&v, c->hx + pos, c->batch, m->nl, LIMB_BITS);
+    mpl_get_hex(hxs, &v);
+    h0[0] = 0;
+    if (c->seed) {
+        mpl_from_limbs32(&v, c->seed + pos, c->batch, m->nl, LIMB_BITS);
+        memcpy(h0, "X0=0x", 5);
+        int n0 = mpl_get_hex(h0 + 5, &v);
+        memcpy(h0 + 5 + n0, "; ", 3);
+    }
+    int n = snprintf(buf, buflen, "METHOD=%s; B1=%llu; N=0x%s; X=0x%s; %sPROGRAM=AVX-ECM-STD;\n", method_name(c->method),
+                     (unsigned long long)c->B1, hn, hxs, h0);
+    if (n < 0 || (size_t)n >= buflen) { set_err("gecm_format_save_line_std: buffer too small"); return GECM_ERR_ARG; }
+    return n;
+}
+
 int gecm_format_save_line_std(gecm_ctx *c, size_t k, char *buf, size_t buflen)
 {
     size_t pos;
     const gecm_mod *m = c && buf ? curve_at(c, k, &pos) : NULL;
     if (!m) return GECM_ERR_ARG;
+    if (c->method) return format_method_line(c, m, pos, buf, buflen);
     if (!c->normalized) { set_err("gecm_format_save_line_std: the batch is not normalised (gecm_normalize_points)"); return GECM_ERR_STATE; }
     int rc = fetch_plain(c);
     if (rc) return rc;
@@ -1298,6 +1358,7 @@ int gecm_stage2_init(gecm_ctx *c, uint32_t D, uint32_t U)
 {
     const int settled = ff_settle(c);
     if (settled) return settled;
+    if (method_refuse(c, "gecm_stage2_init")) return GECM_ERR_STATE;
     if (!c || c->batch == 0 || c->B1 == 0) { set_err("gecm_stage2_init: run stage 1 first"); return GECM_ERR_STATE; }
     if (!D) D = gecm_s2_default_D(c->B1);
     if (!U) U = GECM_S2_DEFAULT_U;
@@ -1460,6 +1521,7 @@ static int s2_tape_for(gecm_ctx *c, uint32_t steps, const uint32_t *pm_v, const 
 
 int gecm_stage2_pair(gecm_ctx *c, uint32_t steps, const uint32_t *pm_v, const uint32_t *pm_u, uint32_t amin)
 {
+    if (method_refuse(c, "gecm_stage2_pair")) return GECM_ERR_STATE;
     if (!c || !c->s2_ready) { set_err("gecm_stage2_pair: gecm_stage2_init has not run"); return GECM_ERR_STATE; }
     if (steps && (!pm_v || !pm_u)) return GECM_ERR_ARG;
     int rc = s2_tape_for(c, steps, pm_v, pm_u, amin);
@@ -1472,6 +1534,7 @@ int gecm_stage2_pair(gecm_ctx *c, uint32_t steps, const uint32_t *pm_v, const ui
 int gecm_stage2_pair_prepare(gecm_ctx *c, uint32_t D, uint32_t U, uint32_t steps, const uint32_t *pm_v, const uint32_t *pm_u,
                              uint32_t amin)
 {
+    if (method_refuse(c, "gecm_stage2_pair_prepare")) return GECM_ERR_STATE;
     if (!c || (steps && (!pm_v || !pm_u))) return GECM_ERR_ARG;
     if (!D || !U || U > (S2_RING - S2_GIANT_CHUNK) / 4) { set_err("gecm_stage2_pair_prepare: bad D/U"); return GECM_ERR_ARG; }
     if (c->s2.D != D || c->s2.U != U) {                                  /* the plan gecm_stage2_init(D, U) would make */
@@ -1501,6 +1564,7 @@ static int keep_pairmap(gecm_ctx *c, gecm_pairs *pm, uint64_t lo, uint64_t hi)
 int gecm_stage2_prepare(gecm_ctx *c, uint64_t B2, uint32_t D, uint32_t U)
 {
     const uint64_t PRIME_RANGE = 100000000ull;
+    if (method_refuse(c, "gecm_stage2_prepare")) return GECM_ERR_STATE;
     if (!c || c->B1 == 0 || B2 <= c->B1) { set_err("gecm_stage2_prepare: call gecm_stage1 first; B2 > B1"); return GECM_ERR_ARG; }
     if (!D) D = gecm_s2_default_D(c->B1);
     if (!U) U = GECM_S2_DEFAULT_U;
@@ -1521,6 +1585,7 @@ int gecm_stage2_prepare(gecm_ctx *c, uint64_t B2, uint32_t D, uint32_t U)
 int gecm_stage2(gecm_ctx *c, uint64_t B2, uint32_t D, uint32_t U)
 {
     const uint64_t PRIME_RANGE = 100000000ull;                           /* main.c:581 */
+    if (method_refuse(c, "gecm_stage2")) return GECM_ERR_STATE;
     if (!c || c->B1 == 0 || B2 <= c->B1) { set_err("gecm_stage2: need B2 > B1 and a finished stage 1"); return GECM_ERR_ARG; }
     int rc = gecm_stage2_init(c, D, U);
     if (rc) return rc;
@@ -1596,6 +1661,7 @@ int gecm_stage2_factor(gecm_ctx *c, size_t k, char *dec, size_t declen, int *is_
     size_t pos;
     const gecm_mod *m = c ? curve_at(c, k, &pos) : NULL;
     if (!m) return GECM_ERR_ARG;
+    if (method_refuse(c, "gecm_stage2_factor")) return GECM_ERR_STATE;
     int rc = fetch_acc(c);
     if (rc) return rc;
     mpl_t a, g;
@@ -1619,12 +1685,14 @@ int gecm_scan_factors(gecm_ctx *c, int stage, size_t *first)
     const int settled = ff_settle(c);
     if (settled) return settled;
     if (!c || c->batch == 0 || (stage != 1 && stage != 2)) { set_err("gecm_scan_factors: bad argument"); return GECM_ERR_ARG; }
+    if (stage == 2 && method_refuse(c, "gecm_scan_factors(stage 2)")) return GECM_ERR_STATE;
     if (stage == 2 && !c->s2_ready) { set_err("gecm_scan_factors: no stage-2 state"); return GECM_ERR_STATE; }
     uint32_t **f = &c->flags[stage - 1], **hg = &c->hg[stage - 1];
     if (!*f) *f = (uint32_t *)calloc(c->batch, sizeof(uint32_t));
     if (!*hg) *hg = (uint32_t *)calloc(c->batch * (size_t)c->mod.nl, sizeof(uint32_t));
     if (!*f || !*hg) return GECM_ERR_NOMEM;
-    if (gecm_dev_gcd_scan(c->dev, stage - 1, *f, *hg)) { set_err("gecm_scan_factors: %s", gecm_dev_error()); return GECM_ERR_DEVICE; }
+    if (c->method ? gecm_dev_gcd_scan_off(c->dev, c->method == GECM_METHOD_PP1 ? 2 : 1, *f, *hg)
+                  : gecm_dev_gcd_scan(c->dev, stage - 1, *f, *hg)) { set_err("gecm_scan_factors: %s", gecm_dev_error()); return GECM_ERR_DEVICE; }
     /* stage 1: x, z come to the host with the scan: everything a caller does next (save lines, factors of the flagged
      * curves) is then host work, off the device's queue */
     int rc = stage == 1 ? fetch_plain(c) : fetch_acc(c);
@@ -1780,14 +1848,15 @@ static int multi_args(const gecm_ctx *c, const char *who, const uint64_t *sigma,
 
 /* gecm_build_curves_multi after its checks; ux != NULL: gecm_resume_points_multi, the points are the plain residues ux,
  * uz ([nl][batch], the caller's order), the padding gets x = z = 1 */
+/* seeds != 0: gecm_build_seeds_multi, no curves are built at all (sigma NULL: 0 throughout); S stays what it is */
 static int build_multi(gecm_ctx *c, const char *who, const uint64_t *sigma, const uint32_t *modulus_index, size_t batch,
-                       const uint32_t *ux, const uint32_t *uz, const uint8_t *prm)
+                       const uint32_t *ux, const uint32_t *uz, const uint8_t *prm, int seeds)
 {
     /* positions: the moduli in order, each one's curves in the caller's order, padded to a multiple of 64; lane-packed:
      * back to back, and the batch's tail padded (modulus 0 there: computed, never read) */
     const size_t ng = c->ngroups;
     const int lane = c->packing == GECM_PACK_LANE;
-    if (lane && c->build_where == GECM_BUILD_DEVICE) {        /* before the previous batch is given up */
+    if (lane && c->build_where == GECM_BUILD_DEVICE && !seeds) {        /* before the previous batch is given up */
         set_err("%s: the device curve build has no per-lane kernel: a lane-packed context builds on the host "
                 "(gecm_set_curve_build, gecm_set_multi_packing)", who);
         return GECM_ERR_STATE;
@@ -1834,14 +1903,14 @@ static int build_multi(gecm_ctx *c, const char *who, const uint64_t *sigma, cons
         const size_t p = goff[g] + cnt[g]++;
         slot[i] = (uint32_t)p;
         pos_user[p] = (uint32_t)i;
-        c->sigma[p] = sigma[i];
+        c->sigma[p] = sigma ? sigma[i] : 0;
         if (param) param[p] = prm[i];
     }
     /* the Suyama construction modulus by modulus: what gecm_build_curves does for its one */
     int anybad = 0;
     c->build_used = c->build_where;
-    const int on_device = c->build_where == GECM_BUILD_DEVICE;
-    for (size_t g = 0; g < ng && !rc && !on_device; g++) {
+    const int on_device = c->build_where == GECM_BUILD_DEVICE && !seeds;
+    for (size_t g = 0; g < ng && !rc && !on_device && !seeds; g++) {
         gecm_mod_build b = {&c->grp[g], c->sigma + goff[g], c->bad, total, goff[g], hX, hX + words, hX + 2 * words,
                             param ? param + goff[g] : NULL};
         const int built = run_slices(cnt[g], gecm_mod_build_slice, &b);
@@ -1850,7 +1919,7 @@ static int build_multi(gecm_ctx *c, const char *who, const uint64_t *sigma, cons
     }
     free(goff);
     free(cnt);
-    if (!rc && !on_device && gecm_dev_upload(c->dev, hX, hX + words, hX + 2 * words)) rc = GECM_ERR_DEVICE;
+    if (!rc && !on_device && !seeds && gecm_dev_upload(c->dev, hX, hX + words, hX + 2 * words)) rc = GECM_ERR_DEVICE;
     if (!rc && gecm_dev_set_groups(c->dev, (uint32_t)ng, c->grp_dev, blocks, lane ? pos_grp : NULL)) rc = GECM_ERR_DEVICE;
     if (!rc && on_device) {              /* the kernel takes every block's modulus from the groups just set */
         const int built = build_on_device(c, c->sigma, total, pos_user);
@@ -1890,7 +1959,7 @@ int gecm_build_curves_multi(gecm_ctx *c, const uint64_t *sigma, const uint32_t *
     size_t prm_batch = 0;
     uint8_t *prm = take_next_params(c, &prm_batch);
     int rc = multi_args(c, "gecm_build_curves_multi", sigma, modulus_index, batch, prm, prm_batch);
-    if (!rc) rc = build_multi(c, "gecm_build_curves_multi", sigma, modulus_index, batch, NULL, NULL, prm);
+    if (!rc) rc = build_multi(c, "gecm_build_curves_multi", sigma, modulus_index, batch, NULL, NULL, prm, 0);
     free(prm);
     return rc;
 }
@@ -1945,7 +2014,7 @@ static int resume_points(gecm_ctx *c, const char *who, const uint64_t *sigma, co
         set_err("%s: x[%zu] or z[%zu] is not below the curve's N", who, j.first_bad, j.first_bad);
         return GECM_ERR_ARG;                      /* the previous batch is untouched */
     }
-    const int built = idx ? build_multi(c, who, sigma, idx, batch, planes, planes + words, prm)
+    const int built = idx ? build_multi(c, who, sigma, idx, batch, planes, planes + words, prm, 0)
                           : build_single(c, sigma, batch, planes, planes + words, prm);
     free(planes);
     if (built < 0) return built;
@@ -1977,6 +2046,107 @@ int gecm_resume_points_multi(gecm_ctx *c, const uint64_t *sigma, const uint32_t 
     if (!rc) rc = resume_points(c, "gecm_resume_points_multi", sigma, modulus_index, x, z, batch, b1_done, prm);
     free(prm);
     return rc;
+}
+
+/* ---- P-1 and P+1 batches -------------------------------------------------------- */
+static int build_seeds(gecm_ctx *c, const char *who, int method, const uint32_t *idx, const void *x0, const void *x,
+                       size_t batch, uint64_t b1_done)
+{
+    if (method != GECM_METHOD_PM1 && method != GECM_METHOD_PP1) {
+        set_err("%s: the method must be GECM_METHOD_PM1 (P-1) or GECM_METHOD_PP1 (P+1)", who);
+        return GECM_ERR_ARG;
+    }
+    if (batch == 0 || batch >= GECM_PAD || (!x0 && !x)) { set_err("%s: bad argument", who); return GECM_ERR_ARG; }
+    if (!x && b1_done != 1) { set_err("%s: a fresh batch (x == NULL) has b1_done = 1", who); return GECM_ERR_ARG; }
+    if (b1_done < 1 || b1_done > GECM_B1_MAX) { set_err("%s: b1_done must be in [1, %llu]", who, (unsigned long long)GECM_B1_MAX); return GECM_ERR_ARG; }
+    if (!c->multi && c->mod.have_report) {
+        set_err("%s: not with a report modulus (gecm_set_report_modulus): %s runs modulo the number the lines name", who,
+                method_name(method));
+        return GECM_ERR_STATE;
+    }
+    for (size_t i = 0; idx && i < batch; i++)
+        if (idx[i] >= c->ngroups) {
+            set_err("%s: modulus_index[%zu] = %u, the context has %zu moduli", who, i, idx[i], c->ngroups);
+            return GECM_ERR_ARG;
+        }
+    const int nl = c->mod.nl;
+    const size_t words = (size_t)nl * batch;
+    uint32_t *planes = (uint32_t *)calloc(words * 3, 4);        /* x0 (or x), x (or x0), z = 1: the caller's order */
+    if (!planes) return GECM_ERR_NOMEM;
+    plain_job j = {c, {x0 ? x0 : x, x ? x : x0}, idx, batch, planes, batch};
+    const int bad = run_slices(batch, plain_slice, &j);
+    if (bad) {
+        free(planes);
+        if (bad < 0) return bad;
+        set_err("%s: x0[%zu] or x[%zu] is not below its N", who, j.first_bad, j.first_bad);
+        return GECM_ERR_ARG;                      /* the previous batch is untouched */
+    }
+    for (size_t i = 0; i < batch; i++) planes[2 * words + i] = 1;
+    int rc;
+    if (idx) rc = build_multi(c, who, NULL, idx, batch, planes + words, planes + 2 * words, NULL, 1);
+    else {
+        rc = alloc_batch(c, batch);
+        if (!rc && gecm_dev_upload_plain(c->dev, planes + words, planes + 2 * words)) {
+            set_err("%s: %s", who, gecm_dev_error());
+            free_batch(c);
+            rc = GECM_ERR_DEVICE;
+        }
+    }
+    if (!rc && x0) {                              /* the seeds, in device order */
+        c->seed = (uint32_t *)calloc((size_t)nl * c->batch, 4);
+        if (!c->seed) { free_batch(c); rc = GECM_ERR_NOMEM; }
+        for (size_t i = 0; !rc && i < batch; i++) {
+            const size_t p = idx ? c->slot[i] : i;
+            for (int l = 0; l < nl; l++) c->seed[(size_t)l * c->batch + p] = planes[(size_t)l * batch + i];
+        }
+    }
+    free(planes);
+    if (rc) return rc;
+    c->method = method;
+    c->B1 = b1_done;
+    c->s1_ptadds = c->s1_ptdups = c->s1_last_prime = c->s1_tape_len = 0;
+    return GECM_OK;
+}
+
+int gecm_build_seeds(gecm_ctx *c, int method, const void *x0, const void *x, size_t batch, uint64_t b1_done)
+{
+    size_t prm_batch = 0;
+    free(take_next_params(c, &prm_batch));        /* a pending setting does not apply to seeds */
+    if (!c) { set_err("gecm_build_seeds: bad argument"); return GECM_ERR_ARG; }
+    if (c->multi) return multi_refuse("gecm_build_seeds");
+    return build_seeds(c, "gecm_build_seeds", method, NULL, x0, x, batch, b1_done);
+}
+
+int gecm_build_seeds_multi(gecm_ctx *c, int method, const uint32_t *modulus_index, const void *x0, const void *x,
+                           size_t batch, uint64_t b1_done)
+{
+    size_t prm_batch = 0;
+    free(take_next_params(c, &prm_batch));
+    if (!c || !modulus_index) { set_err("gecm_build_seeds_multi: bad argument"); return GECM_ERR_ARG; }
+    if (!c->multi) { set_err("gecm_build_seeds_multi: not a multi-modulus context (gecm_create_multi)"); return GECM_ERR_STATE; }
+    return build_seeds(c, "gecm_build_seeds_multi", method, modulus_index, x0, x, batch, b1_done);
+}
+
+int gecm_batch_method(const gecm_ctx *c) { return c && c->batch ? c->method : GECM_METHOD_ECM; }
+
+int gecm_curve_seed(gecm_ctx *c, size_t k, char *hex, size_t hexlen)
+{
+    size_t pos;
+    const gecm_mod *m = c && hex && hexlen ? curve_at(c, k, &pos) : NULL;
+    if (!m) {
+        if (!c || !c->multi) set_err("gecm_curve_seed: position %zu: no such residue in the batch", k);
+        return GECM_ERR_ARG;
+    }
+    if (!c->method) { set_err("gecm_curve_seed: the batch holds curves, not P-1 / P+1 residues"); return GECM_ERR_STATE; }
+    hex[0] = 0;
+    if (!c->seed) return 0;
+    mpl_t v;
+    mpl_from_limbs32(&v, c->seed + pos, c->batch, m->nl, LIMB_BITS);
+    static __thread char tmp[MPL_MAXL * 10 + 2];
+    int n = mpl_get_hex(tmp, &v);
+    if (n < 0 || (size_t)n >= hexlen) { set_err("gecm_curve_seed: buffer too small"); return GECM_ERR_ARG; }
+    memcpy(hex, tmp, (size_t)n + 1);
+    return n;
 }
 
 int gecm_curve_modulus(const gecm_ctx *c, size_t k)

@@ -75,8 +75,33 @@ static int name_is(const char *p, const char *e, const char *name)
     return (size_t)(e - p) == n && memcmp(p, name, n) == 0;
 }
 
-/* the body of gecm_parse_resume_line (param == NULL: PARAM 0 only) and of gecm_parse_resume_line_param */
-static int parse_line(const char *line, gecm_resume_rec *rec, int *param)
+/* The METHOD of a line for gecm_parse_resume_line_method: 0 for ECM or no METHOD field, 1 for P-1, 2 for P+1, -1 for
+ * anything else.  Looked up before the fields are read: a P-1 / P+1 line's SIGMA and PARAM are not looked at, wherever
+ * they stand. */
+static int method_of(const char *line)
+{
+    int meth = 0;
+    for (const char *p = line; *p; ) {
+        const char *fe = p, *ns = p, *eq = p;
+        while (*fe && *fe != ';') fe++;
+        while (ns < fe && is_space(*ns)) ns++;
+        while (eq < fe && *eq != '=') eq++;
+        if (eq < fe) {
+            const char *ne = eq, *vs = eq + 1, *ve = fe;
+            while (ne > ns && is_space(ne[-1])) ne--;
+            while (vs < ve && is_space(*vs)) vs++;
+            while (ve > vs && is_space(ve[-1])) ve--;
+            if (name_is(ns, ne, "METHOD"))
+                meth = name_is(vs, ve, "ECM") ? 0 : name_is(vs, ve, "P-1") ? GECM_METHOD_PM1 : name_is(vs, ve, "P+1") ? GECM_METHOD_PP1 : -1;
+        }
+        p = *fe ? fe + 1 : fe;
+    }
+    return meth;
+}
+
+/* the body of gecm_parse_resume_line (param == NULL: PARAM 0 only), of gecm_parse_resume_line_param and (x0 != NULL, meth
+ * = method_of(line) >= 0) of gecm_parse_resume_line_method */
+static int parse_line(const char *line, gecm_resume_rec *rec, int *param, int meth, gecm_resume_num *x0)
 {
     uint64_t prm = 0;
     int have_param = 0;
@@ -101,12 +126,16 @@ static int parse_line(const char *line, gecm_resume_rec *rec, int *param)
             int rc = GECM_OK;
             const int again = (name_is(ns, ne, "SIGMA") && have_sigma) || (name_is(ns, ne, "B1") && have_b1) ||
                               (name_is(ns, ne, "N") && rec->n.digits) || (name_is(ns, ne, "X") && rec->x.digits) ||
-                              (name_is(ns, ne, "Z") && rec->z.digits) || (param && name_is(ns, ne, "PARAM") && have_param);
+                              (name_is(ns, ne, "Z") && rec->z.digits) || (param && name_is(ns, ne, "PARAM") && have_param) ||
+                              (x0 && name_is(ns, ne, "X0") && x0->digits);
             if (again) {                              /* two lines run together, most likely */
                 set_err("gecm_parse_resume_line: field %.*s appears twice", (int)(ne - ns), ns);
                 return GECM_ERR_ARG;
             }
-            if (name_is(ns, ne, "METHOD")) {
+            if (meth && (name_is(ns, ne, "METHOD") || name_is(ns, ne, "SIGMA") || name_is(ns, ne, "PARAM"))) {
+                /* a P-1 / P+1 line: METHOD is known, SIGMA and PARAM are ignored */
+            } else if (x0 && name_is(ns, ne, "X0")) rc = take_number("X0", vs, ve, x0);
+            else if (name_is(ns, ne, "METHOD")) {
                 if (!name_is(vs, ve, "ECM")) { set_err("gecm_parse_resume_line: field METHOD is not ECM"); return GECM_ERR_ARG; }
             }
             else if (name_is(ns, ne, "PARAM")) {
@@ -136,9 +165,17 @@ static int parse_line(const char *line, gecm_resume_rec *rec, int *param)
         }
         p = *fe ? fe + 1 : fe;
     }
-    const char *missing = !have_sigma ? "SIGMA" : !have_b1 ? "B1" : !rec->n.digits ? "N"
+    const char *missing = !have_sigma && !meth ? "SIGMA" : !have_b1 ? "B1" : !rec->n.digits ? "N"
                           : !rec->x.digits ? "X" : NULL;
     if (missing) { set_err("gecm_parse_resume_line: field %s is missing", missing); return GECM_ERR_ARG; }
+    if (meth) {
+        if (rec->z.digits && !(rec->z.len == 1 && rec->z.digits[0] == '1')) {
+            set_err("gecm_parse_resume_line_method: field Z of a %s line is not 1", meth == GECM_METHOD_PM1 ? "P-1" : "P+1");
+            return GECM_ERR_ARG;
+        }
+        if (param) *param = 0;
+        return GECM_OK;
+    }
     if (prm == GECM_PARAM_SUYAMA && rec->sigma < 6) { set_err("gecm_parse_resume_line: field SIGMA = %llu is below 6", (unsigned long long)rec->sigma); return GECM_ERR_ARG; }
     if (prm != GECM_PARAM_SUYAMA && !gecm_mod_param_sigma_ok((int)prm, rec->sigma)) {
         set_err("gecm_parse_resume_line_param: field SIGMA = %llu is outside [1, 2^%d), the range of PARAM %d",
@@ -152,13 +189,29 @@ static int parse_line(const char *line, gecm_resume_rec *rec, int *param)
 int gecm_parse_resume_line(const char *line, gecm_resume_rec *rec)
 {
     if (!line || !rec) { set_err("gecm_parse_resume_line: bad argument"); return GECM_ERR_ARG; }
-    return parse_line(line, rec, NULL);
+    return parse_line(line, rec, NULL, 0, NULL);
 }
 
 int gecm_parse_resume_line_param(const char *line, gecm_resume_rec *rec, int *param)
 {
     if (!line || !rec || !param) { set_err("gecm_parse_resume_line_param: bad argument"); return GECM_ERR_ARG; }
-    return parse_line(line, rec, param);
+    return parse_line(line, rec, param, 0, NULL);
+}
+
+int gecm_parse_resume_line_method(const char *line, gecm_resume_rec *rec, int *param, int *method, gecm_resume_num *x0)
+{
+    if (!line || !rec || !param || !method || !x0) { set_err("gecm_parse_resume_line_method: bad argument"); return GECM_ERR_ARG; }
+    memset(x0, 0, sizeof *x0);
+    *method = GECM_METHOD_ECM;
+    const int meth = method_of(line);
+    if (meth < 0) { set_err("gecm_parse_resume_line_method: field METHOD is not ECM, P-1 or P+1"); return GECM_ERR_ARG; }
+    if (!meth) return parse_line(line, rec, param, 0, NULL);
+    gecm_resume_num seed = {NULL, 0, 0};
+    const int rc = parse_line(line, rec, param, meth, &seed);
+    if (rc) return rc;
+    *x0 = seed;
+    *method = meth;
+    return GECM_OK;
 }
 
 int gecm_stage1_resume_range(uint64_t B1, uint64_t b1_field, uint32_t *range)
@@ -220,6 +273,19 @@ static int std_bound(const char *line, uint64_t *from, int with_param)
 
 int gecm_resume_line_std_bound(const char *line, uint64_t *from) { return std_bound(line, from, 0); }
 int gecm_resume_line_std_bound_param(const char *line, uint64_t *from) { return std_bound(line, from, 1); }
+
+int gecm_resume_line_std_bound_method(const char *line, uint64_t *from)
+{
+    gecm_resume_rec rec;
+    gecm_resume_num x0;
+    int prm, meth;
+    if (!line || !from) { set_err("gecm_resume_line_std_bound_method: bad argument"); return GECM_ERR_ARG; }
+    if (method_of(line) <= 0) return std_bound(line, from, 1);
+    const int rc = gecm_parse_resume_line_method(line, &rec, &prm, &meth, &x0);
+    if (rc) return rc;
+    *from = rec.b1;
+    return GECM_OK;
+}
 
 /* the hash of the host sources this object was compiled from (Makefile: H_SHA); gecm_version() compares them */
 #ifdef GECM_MANIFEST_FN

@@ -195,6 +195,18 @@ _sig("gecm_resume_line_std_bound_param", c_int, c_char_p, ctypes.POINTER(c_u64))
 EXPORTS += ["gecm_param_s", "gecm_set_next_params", "gecm_curve_param", "gecm_parse_resume_line_param",
             "gecm_resume_line_std_bound_param"]
 
+# P-1 and P+1 batches: one residue per lane on the stage-1 tape
+METHOD_ECM, METHOD_PM1, METHOD_PP1 = 0, 1, 2
+_sig("gecm_build_seeds", c_int, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_u64)
+_sig("gecm_build_seeds_multi", c_int, c_void_p, c_int, ctypes.POINTER(ctypes.c_uint32), c_void_p, c_void_p, c_size_t, c_u64)
+_sig("gecm_batch_method", c_int, c_void_p)
+_sig("gecm_curve_seed", c_int, c_void_p, c_size_t, c_char_p, c_size_t)
+_sig("gecm_parse_resume_line_method", c_int, c_char_p, ctypes.POINTER(ResumeRec), ctypes.POINTER(c_int), ctypes.POINTER(c_int),
+     ctypes.POINTER(ResumeNum))
+_sig("gecm_resume_line_std_bound_method", c_int, c_char_p, ctypes.POINTER(c_u64))
+EXPORTS += ["gecm_build_seeds", "gecm_build_seeds_multi", "gecm_batch_method", "gecm_curve_seed",
+            "gecm_parse_resume_line_method", "gecm_resume_line_std_bound_method"]
+
 
 class GecmError(RuntimeError):
     pass
@@ -261,6 +273,39 @@ def parse_resume_line(line):
 def parse_resume_line_param(line):
     """parse_resume_line with PARAM 0, 1 and 3 accepted: ResumeLineParam, the same fields and the parametrisation"""
     return _parse_line(line, True)
+
+
+# a line of any method: method is METHOD_ECM / _PM1 / _PP1; x0 is the seed of a P-1 / P+1 line, None where it names none
+ResumeLineMethod = collections.namedtuple("ResumeLineMethod", "sigma b1 n x z param method x0")
+
+
+def parse_resume_line_method(line):
+    """parse_resume_line_param with METHOD=P-1 and METHOD=P+1 lines accepted: ResumeLineMethod (sigma = 0, param = 0 and
+    z = 1 on such a line), None for a line to skip"""
+    raw = line.encode() if isinstance(line, str) else bytes(line)
+    buf = ctypes.create_string_buffer(raw)
+    rec, x0 = ResumeRec(), ResumeNum()
+    param, method = c_int(0), c_int(0)
+    rc = _chk(lib.gecm_parse_resume_line_method(buf, ctypes.byref(rec), ctypes.byref(param), ctypes.byref(method),
+                                                ctypes.byref(x0)), "gecm_parse_resume_line_method")
+    if rc == 1:
+        return None
+
+    def num(f):
+        off = f.digits - ctypes.addressof(buf)
+        return int(raw[off:off + f.len], f.base)
+    return ResumeLineMethod(rec.sigma, rec.b1, num(rec.n), num(rec.x), num(rec.z) if rec.z.digits else 1, param.value,
+                            method.value, num(x0) if x0.digits else None)
+
+
+def resume_line_std_bound_method(line):
+    """resume_line_std_bound for a reader of parse_resume_line_method: the B1 field of a P-1 / P+1 line, and what
+    resume_line_std_bound(line, params=True) gives for an ECM line"""
+    raw = line.encode() if isinstance(line, str) else bytes(line)
+    b = c_u64(0)
+    if _chk(lib.gecm_resume_line_std_bound_method(raw, ctypes.byref(b)), "gecm_resume_line_std_bound_method") == 1:
+        return None
+    return b.value
 
 
 def param_s(param, sigma, n):
@@ -435,6 +480,28 @@ class Engine:
         self.batch = len(sigmas)
         return _chk(lib.gecm_resume_points(self._h, arr, self.pack(xs), self.pack(zs), len(sigmas), b1_done),
                     "gecm_resume_points")
+
+    def build_seeds(self, method, x0s, xs=None, b1_done=1):
+        """a P-1 (METHOD_PM1) or P+1 (METHOD_PP1) batch: one residue per position, seeds x0s; xs = the residues of lines
+        complete to b1_done (x0s may then be None: seeds unknown), None = a fresh batch.  Go on with stage1_extend."""
+        given = xs if xs is not None else x0s
+        if given is None or (x0s is not None and xs is not None and len(x0s) != len(xs)):
+            raise ValueError("build_seeds: seeds, residues or one of each per position")
+        self._fits(*[v for v in (x0s, xs) if v is not None])
+        rc = _chk(lib.gecm_build_seeds(self._h, method, None if x0s is None else self.pack(x0s),
+                                       None if xs is None else self.pack(xs), len(given), b1_done), "gecm_build_seeds")
+        self.batch = len(given)                   # a refused call leaves the previous batch, and its size
+        return rc
+
+    def batch_method(self):
+        """METHOD_ECM, METHOD_PM1 or METHOD_PP1: what the batch in the context holds"""
+        return lib.gecm_batch_method(self._h)
+
+    def curve_seed(self, k):
+        """x0 of position k of a P-1 / P+1 batch; None where the batch was built without seeds"""
+        buf = ctypes.create_string_buffer(2048)
+        n = _chk(lib.gecm_curve_seed(self._h, k, buf, len(buf)), "gecm_curve_seed")
+        return int(buf.value.decode(), 16) if n else None
 
     def _fits(self, *vecs):
         # pack() keeps the low MAXBITS bits: what does not fit them is no residue of this context
@@ -692,6 +759,19 @@ class MultiEngine(Engine):
         self.batch = len(sigmas)
         return _chk(lib.gecm_resume_points_multi(self._h, arr, idx, self.pack(xs), self.pack(zs), len(sigmas), b1_done),
                     "gecm_resume_points_multi")
+
+    def build_seeds(self, method, x0s, which, xs=None, b1_done=1):
+        """Engine.build_seeds with position k on number ns[which[k]]"""
+        given = xs if xs is not None else x0s
+        if given is None or len(which) != len(given) or (x0s is not None and xs is not None and len(x0s) != len(xs)):
+            raise ValueError("build_seeds: one modulus index per position, and seeds, residues or one of each")
+        self._fits(*[v for v in (x0s, xs) if v is not None])
+        idx = (ctypes.c_uint32 * len(which))(*which)
+        rc = _chk(lib.gecm_build_seeds_multi(self._h, method, idx, None if x0s is None else self.pack(x0s),
+                                             None if xs is None else self.pack(xs), len(given), b1_done),
+                  "gecm_build_seeds_multi")
+        self.batch = len(given)
+        return rc
 
     def set_packing(self, packing):
         """"wave" (one modulus per wavefront, every number padded to 64 curves) or "lane" (one modulus per lane, only the

@@ -502,6 +502,56 @@ int gecm_resume_line_std_bound(const char *line, uint64_t *from);
 /* the same for a caller that reads its lines with gecm_parse_resume_line_param: PARAM 1 and 3 lines have a bound too */
 int gecm_resume_line_std_bound_param(const char *line, uint64_t *from);
 
+/* ---- P-1 and P+1 stage 1: one residue per lane on the stage-1 tape --------------
+ * Pretesting a list of composites is P-1, then P+1, then ECM; a method batch holds one residue x per position instead
+ * of a curve and runs the standard multiplier on it:
+ *   P-1: x <- x0^E mod N, factor test gcd(x - 1, N);
+ *   P+1: x <- V_E(x0) mod N (V_0 = 2, V_1 = x0, V_{m+n} = V_m V_n - V_{m-n}), factor test gcd(x - 2, N);
+ * E = k_std(to) / k_std(from), exactly what gecm_stage1_extend(ctx, from, to) means for curves; a fresh run is from = 1.
+ * The residue does not depend on the chain that computed it, so there is no normalisation step, and going on needs only
+ * x: V_a(V_b(P)) = V_ab(P), (x^a)^b = x^ab.  The reference's own multiplier (gecm_stage1, gecm_stage1_range) is not
+ * offered.  The special-form twin is not filled: these batches run the generic multiply modulo N.
+ * gecm_build_seeds / gecm_build_seeds_multi: x0 and x are plain canonical residues in the context's vec layout, as for
+ *   gecm_resume_points.  x == NULL: a fresh batch, x = x0, and b1_done must be 1.  Otherwise x is the residue of a line
+ *   complete to b1_done (1 .. 10^12), and x0 may be NULL: the seed is not known, and the lines omit it.  Checked before
+ *   the previous batch is given up: method is GECM_METHOD_PM1 or GECM_METHOD_PP1, batch >= 1, every value below its N
+ *   (GECM_ERR_ARG); the _multi form on a single-N context and the reverse, and a context with a report modulus, answer
+ *   GECM_ERR_STATE.  x0 = 0, and for P+1 also x0 = 2 and x0 = N - 2, are degenerate but legal: they are computed like
+ *   any other seed and find nothing (as is P-1 with x0 = 1).  Both packings of a multi-modulus context work; lane packing
+ *   keeps its 415-bit limit.  A pending gecm_set_next_params setting is taken and dropped: it does not apply to seeds.
+ * On a method batch work: gecm_stage1_extend, gecm_stage1_extend_segment, gecm_sync, gecm_stage1_progress,
+ *   gecm_last_kernel_ms, gecm_last_kernel_name (k_unit, k_unit_multi, k_unit_lane), gecm_get_stage1_stats (ptadds and
+ *   ptdups count tape events as they do for curves), gecm_scan_factors(ctx, 1, ..) and gecm_curve_flag(ctx, 1, k) (of
+ *   x - 1 or x - 2), gecm_stage1_factor (g = N is "no factor"), gecm_download_points_plain on a single-N context (x, and
+ *   z = 1), gecm_curve_modulus, and gecm_format_save_line_std, which writes
+ *     "METHOD=P-1; B1=%llu; N=0x%s; X=0x%s; X0=0x%s; PROGRAM=AVX-ECM-STD;\n"   (METHOD=P+1 likewise)
+ *   with "X0=0x%s; " left out when the seed is unknown.  One lane per residue whatever gecm_set_lanes_per_curve says;
+ *   gecm_get_lanes_per_curve answers 1 after such a launch.
+ * GECM_ERR_STATE with a text naming the method: gecm_stage1, gecm_stage1_range, every gecm_stage2* call,
+ *   gecm_normalize_points, gecm_download_s, gecm_format_save_line, gecm_format_resume_line, gecm_scan_factors(ctx, 2, ..).
+ * Any of the build, upload or resume calls for curves makes the context an ECM context again.
+ * gecm_batch_method: the method of the batch in the context; GECM_METHOD_ECM for every batch built for curves, and
+ *   without a batch.
+ * gecm_curve_seed: x0 of the caller's position k, lower-case hex without prefix; returns the digit count, 0 (and an empty
+ *   string) if the seed is unknown, GECM_ERR_ARG for no such position, GECM_ERR_STATE on an ECM batch.
+ * gecm_parse_resume_line_method: gecm_parse_resume_line_param with METHOD=P-1 and METHOD=P+1 accepted (*method = 1, 2).
+ *   On such a line SIGMA and PARAM need not be present and are ignored when they are (rec->sigma = 0, *param = 0), X0 is
+ *   returned in *x0 when present (digits NULL otherwise), Z must be absent or 1.  For METHOD=ECM and for lines without
+ *   METHOD it returns exactly what gecm_parse_resume_line_param returns, *method = 0, and no x0.  The two older parsers
+ *   and bound functions keep refusing other methods.
+ * gecm_resume_line_std_bound_method: the B1 field of a P-1 / P+1 line (such lines are always standard); for ECM lines
+ *   what gecm_resume_line_std_bound_param returns. */
+#define GECM_METHOD_ECM 0
+#define GECM_METHOD_PM1 1
+#define GECM_METHOD_PP1 2
+int gecm_build_seeds(gecm_ctx *ctx, int method, const void *x0, const void *x, size_t batch, uint64_t b1_done);
+int gecm_build_seeds_multi(gecm_ctx *ctx, int method, const uint32_t *modulus_index, const void *x0, const void *x,
+                           size_t batch, uint64_t b1_done);
+int gecm_batch_method(const gecm_ctx *ctx);
+int gecm_curve_seed(gecm_ctx *ctx, size_t k, char *hex, size_t hexlen);
+int gecm_parse_resume_line_method(const char *line, gecm_resume_rec *rec, int *param, int *method, gecm_resume_num *x0);
+int gecm_resume_line_std_bound_method(const char *line, uint64_t *from);
+
 #ifdef __cplusplus
 }
 #endif
