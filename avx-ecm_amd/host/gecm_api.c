@@ -1,8 +1,10 @@
 /* gecm_api.c — public C ABI of libgecm (include/gecm.h): the contexts, their batch state and the phase functions, in
  * C above the HIP device layer (csrc/gecm_dev.h).  What depends on one number N alone — its constants, the curve
  * construction, failure records, the factor report — is gecm_mod.c, which knows neither device nor context; a context
- * holds the gecm_mod of its number, a multi-modulus context one more per modulus, and curve_at() leads from a caller's
- * curve to its modulus and its place in the batch arrays.  Mirrors the reference's phase functions:
+ * holds the gecm_mod of its number, a multi-modulus context one more per modulus and the gecm_layout of its batch (the
+ * position arithmetic is gecm_mod.c's too), and curve_at() leads from a caller's curve to its modulus and its place in
+ * the batch arrays.  Every call that puts a batch into a context describes it (batch_desc) and ends in batch_build().
+ * Mirrors the reference's phase functions:
  *   ecm_stage1                  ecm.c:1806-1854 (tape built by gecm_plan.c, run by the device)
  *   save line                   ecm.c:1372-1380
  */
@@ -143,10 +145,7 @@ struct gecm_ctx {
     size_t ngroups;
     gecm_mod *grp;
     gecm_devmod *grp_dev;    /* grp[]'s constants as the device layer takes them (gecm_dev_set_groups) */
-    size_t nuser;            /* curves the caller built */
-    uint32_t *slot;          /* caller's curve -> device position */
-    uint32_t *pos_user;      /* device position -> caller's curve, GECM_PAD for padding */
-    uint32_t *pos_grp;       /* device position -> modulus */
+    gecm_layout lay;         /* the batch's positions (gecm_mod.h); all zero on a single-N context and without a batch */
     /* GECM_PACK_WAVE / GECM_PACK_LANE: asked for (gecm_set_multi_packing), used by the last build.  Lane
      * packing lays the groups back to back and pads only the batch's tail; every lane then carries its own modulus. */
     int packing, packing_used;
@@ -155,7 +154,6 @@ struct gecm_ctx {
     int method;
     uint32_t *seed;
 };
-#define GECM_PAD 0xffffffffu
 
 /* what a multi-modulus context cannot do: the reference radix (NWORDS) differs from modulus to modulus, and the L0
  * operators, uploaded points and the special forms work modulo one N */
@@ -418,9 +416,7 @@ static void free_batch(gecm_ctx *c)
     c->hg[0] = c->hg[1] = NULL;
     c->scan_valid[0] = c->scan_valid[1] = 0;
     c->sigma = NULL; c->bad = NULL; c->hx = c->hz = NULL; c->hacc = c->hfail = NULL;
-    free(c->slot); free(c->pos_user); free(c->pos_grp);
-    c->slot = c->pos_user = c->pos_grp = NULL;
-    c->nuser = 0;
+    gecm_layout_free(&c->lay);
     c->have_acc = 0; c->s2_ready = 0;
     c->batch = 0;
     c->have_plain = 0;
@@ -650,24 +646,26 @@ int gecm_vecinvmod(gecm_ctx *c, const void *a, void *inv, void *gcd, size_t batc
 }
 
 /* ---- phase 0 -------------------------------------------------------------------------------- */
-/* The one-shot setting of gecm_set_next_params, taken by the build call that follows it whether that call succeeds or
- * not: the array (the caller of this frees it; NULL: none pending) and the batch it was given for. */
-static uint8_t *take_next_params(gecm_ctx *c, size_t *batch)
+/* The one-shot setting of gecm_set_next_params belongs to the build call that follows it, whether that call succeeds
+ * or not: the call reads c->next_param where it needs it (seeds do not) and returns through here, which drops the
+ * setting.  gecm_upload_points alone leaves it pending. */
+static int build_call_end(gecm_ctx *c, int rc)
 {
-    if (!c) return NULL;
-    uint8_t *p = c->next_param;
-    *batch = c->next_batch;
-    c->next_param = NULL;
-    c->next_batch = 0;
-    return p;
+    if (c) {
+        free(c->next_param);
+        c->next_param = NULL;
+        c->next_batch = 0;
+    }
+    return rc;
 }
 
-/* the checks of a build call on its sigmas, before the context gives up its batch: the setting is for this batch size,
- * sigma >= 6 for the PARAM 0 curves, the range of the parametrisation for the others (prm NULL: PARAM 0 throughout) */
-static int params_fit(const char *who, size_t batch, const uint8_t *prm, size_t prm_batch)
+/* the checks of a build call on its sigmas, before the context gives up its batch: the pending setting is for this
+ * batch size, sigma >= 6 for the PARAM 0 curves, the range of the parametrisation for the others (no setting pending:
+ * PARAM 0 throughout) */
+static int params_fit(const gecm_ctx *c, const char *who, size_t batch)
 {
-    if (!prm || prm_batch == batch) return GECM_OK;
-    set_err("%s: gecm_set_next_params gave the parametrisations of %zu curves, this batch has %zu", who, prm_batch, batch);
+    if (!c->next_param || c->next_batch == batch) return GECM_OK;
+    set_err("%s: gecm_set_next_params gave the parametrisations of %zu curves, this batch has %zu", who, c->next_batch, batch);
     return GECM_ERR_ARG;
 }
 
@@ -683,10 +681,13 @@ static int sigma_arg(const char *who, const uint64_t *sigma, size_t i, const uin
     return GECM_OK;
 }
 
-static int sigma_args(const char *who, const uint64_t *sigma, size_t batch, const uint8_t *prm, size_t prm_batch)
+/* the checks gecm_build_curves and gecm_resume_points make on their common arguments */
+static int sigma_args(const gecm_ctx *c, const char *who, const uint64_t *sigma, size_t batch)
 {
-    int rc = params_fit(who, batch, prm, prm_batch);
-    for (size_t i = 0; i < batch && !rc; i++) rc = sigma_arg(who, sigma, i, prm);
+    if (!c || !sigma || batch == 0) { set_err("%s: bad argument", who); return GECM_ERR_ARG; }
+    if (c->multi) return multi_refuse(who);
+    int rc = params_fit(c, who, batch);
+    for (size_t i = 0; i < batch && !rc; i++) rc = sigma_arg(who, sigma, i, c->next_param);
     return rc;
 }
 
@@ -702,15 +703,45 @@ int gecm_set_next_params(gecm_ctx *c, const uint8_t *param, size_t batch)
             }
     }
     if (!c) { set_err("gecm_set_next_params: bad argument (no context)"); return GECM_ERR_ARG; }
-    free(c->next_param);
-    c->next_param = NULL;
-    c->next_batch = 0;
+    build_call_end(c, 0);
     if (!param) return GECM_OK;
     c->next_param = (uint8_t *)malloc(batch);
     if (!c->next_param) return GECM_ERR_NOMEM;
     memcpy(c->next_param, param, batch);
     c->next_batch = batch;
     return GECM_OK;
+}
+
+/* ---- how a batch is constructed -----------------------------------------------
+ * Every call that puts a batch into a context checks its arguments, describes the batch and hands the description to
+ * batch_build, which is five steps: lay the batch out, begin it, fill it, overlay plain residues, finish it. */
+typedef enum {
+    BATCH_CURVES,       /* X, Z, S are the curves constructed from sigma */
+    BATCH_MONT,         /* planes = X, Z, S in Montgomery form: gecm_upload_points */
+    BATCH_PLAIN         /* planes = plain x, z in [0, N): resumed points over the curves of sigma, or seeds without any */
+} batch_content;
+
+typedef struct {
+    const char *who;                 /* the entry point, for the error texts */
+    size_t batch;                    /* the caller's curves; every array below is [batch] or [nl][batch] in its order */
+    const uint64_t *sigma;           /* a curve is constructed from each; NULL: the batch has no sigmas (and S stays unset) */
+    const uint32_t *modulus_index;   /* the modulus of every curve of a multi-modulus context; NULL on a single-N one */
+    const uint8_t *param;            /* the parametrisation of every sigma; NULL: PARAM 0 throughout */
+    batch_content content;
+    const uint32_t *planes;          /* what `content` says, [nl][batch] each; NULL for BATCH_CURVES */
+    int method;                      /* GECM_METHOD_ECM, or what the residues of a seed batch are for */
+    const uint32_t *seed;            /* the plain x0 plane a seed batch keeps; NULL: unknown */
+} batch_desc;
+
+static inline size_t batch_pos(const gecm_ctx *c, size_t i) { return c->multi ? c->lay.slot[i] : i; }
+
+/* one [nl][nuser] plane in the caller's order into position order, stride c->batch; the padding is left as it is */
+static void scatter_plane(const gecm_ctx *c, uint32_t *dst, const uint32_t *src, size_t nuser)
+{
+    for (size_t i = 0; i < nuser; i++) {
+        const size_t p = batch_pos(c, i);
+        for (size_t l = 0; l < (size_t)c->mod.nl; l++) dst[l * c->batch + p] = src[l * nuser + i];
+    }
 }
 
 static int alloc_batch(gecm_ctx *c, size_t batch)
@@ -723,86 +754,166 @@ static int alloc_batch(gecm_ctx *c, size_t batch)
     c->hacc = (uint32_t *)calloc(batch * (size_t)c->mod.nl, 4);
     c->hfail = (uint32_t *)calloc(batch * (size_t)c->mod.nl, 4);
     c->fail_planes = 1;
-    if (!c->sigma || !c->bad || !c->hx || !c->hz || !c->hacc || !c->hfail) { free_batch(c); return GECM_ERR_NOMEM; }
+    if (!c->sigma || !c->bad || !c->hx || !c->hz || !c->hacc || !c->hfail) return GECM_ERR_NOMEM;
     c->batch = batch;
-    if (gecm_dev_resize(c->dev, batch)) { set_err("%s", gecm_dev_error()); return GECM_ERR_DEVICE; }
     c->twin.pending = 0;
     c->twin.loaded = 0;
-    if (c->twin.dev && gecm_dev_resize(c->twin.dev, batch)) { set_err("%s", gecm_dev_error()); return GECM_ERR_DEVICE; }
+    if (gecm_dev_resize(c->dev, batch) || (c->twin.dev && gecm_dev_resize(c->twin.dev, batch))) return GECM_ERR_DEVICE;
     return GECM_OK;
 }
 
-/* The device build of the batch alloc_batch has just set up (gecm_set_curve_build): sigma[0 .. total) in device order,
- * c->bad from the kernel's flags; live[p] == GECM_PAD marks a padding position of a multi-modulus batch, whose flag
- * does not count.  Returns 1 if some curve is flagged, 0 if none, GECM_ERR_DEVICE with the error text set. */
-static int build_on_device(gecm_ctx *c, const uint64_t *sigma, size_t total, const uint32_t *live)
+/* Step 2: the previous batch goes, the context takes the layout (`lay` is empty afterwards; all zero for a single-N
+ * batch) and arrays for its positions, on the host and on the device; sigma and param go into position order, the
+ * padding's stay 0. */
+static int batch_begin(gecm_ctx *c, const batch_desc *d, gecm_layout *lay)
 {
-    uint32_t *flags = (uint32_t *)malloc(total * sizeof(uint32_t));
+    const int rc = alloc_batch(c, c->multi ? lay->total : d->batch);
+    c->lay = *lay;
+    memset(lay, 0, sizeof *lay);
+    if (rc) return rc;
+    if (d->param && !(c->param = (uint8_t *)calloc(c->batch, 1))) return GECM_ERR_NOMEM;
+    for (size_t i = 0; i < d->batch; i++) {
+        const size_t p = batch_pos(c, i);
+        if (d->sigma) c->sigma[p] = d->sigma[i];
+        if (d->param) c->param[p] = d->param[i];
+    }
+    return GECM_OK;
+}
+
+/* The batch's moduli and which goes where, to the device (a multi-modulus context; once per batch, after its resize):
+ * the block table under wave packing, the per-position table under lane packing. */
+static int groups_to_device(gecm_ctx *c)
+{
+    const gecm_layout *l = &c->lay;
+    if (!c->multi) return GECM_OK;
+    return gecm_dev_set_groups(c->dev, (uint32_t)c->ngroups, c->grp_dev, l->blocks, l->blocks ? NULL : l->pos_grp) ? GECM_ERR_DEVICE : GECM_OK;
+}
+
+/* Step 3, curves on the host: the construction modulus by modulus on the worker threads (a single-N batch: its one
+ * modulus at position 0), uploaded; the padding stays zero: computed, never read.  1 if some curve is marked bad. */
+static int fill_on_host(gecm_ctx *c)
+{
+    const size_t words = (size_t)c->mod.nl * c->batch;
+    uint32_t *h = (uint32_t *)calloc(words * 3, 4);
+    if (!h) return GECM_ERR_NOMEM;
+    int rc = 0, anybad = 0;
+    for (size_t g = 0; g < (c->multi ? c->ngroups : 1) && rc >= 0; g++) {
+        const size_t off = c->multi ? c->lay.goff[g] : 0;
+        gecm_mod_build b = {c->multi ? &c->grp[g] : &c->mod, c->sigma + off, c->bad, c->batch, off, h, h + words, h + 2 * words,
+                            c->param ? c->param + off : NULL};
+        rc = run_slices(c->multi ? c->lay.cnt[g] : c->batch, gecm_mod_build_slice, &b);
+        anybad |= rc > 0;
+    }
+    if (rc >= 0) rc = gecm_dev_upload(c->dev, h, h + words, h + 2 * words) ? GECM_ERR_DEVICE : groups_to_device(c);
+    free(h);
+    return rc < 0 ? rc : anybad;
+}
+
+/* Step 3, curves on the device (gecm_set_curve_build): the kernels read the moduli just set and c->sigma, c->param in
+ * position order; c->bad from their flags, the padding's does not count.  1 if some curve is flagged. */
+static int fill_on_device(gecm_ctx *c)
+{
+    if (groups_to_device(c)) return GECM_ERR_DEVICE;
+    uint32_t *flags = (uint32_t *)malloc(c->batch * sizeof(uint32_t));
     if (!flags) return GECM_ERR_NOMEM;
     /* with a parametrisation per curve: the Suyama kernel if some curve is PARAM 0, then k_build_param over the others */
-    if (c->param ? gecm_dev_build_param(c->dev, sigma, c->param, total, flags) : gecm_dev_build(c->dev, sigma, total, flags)) {
+    if (c->param ? gecm_dev_build_param(c->dev, c->sigma, c->param, c->batch, flags) : gecm_dev_build(c->dev, c->sigma, c->batch, flags)) {
         free(flags);
-        set_err("%s", gecm_dev_error());
         return GECM_ERR_DEVICE;
     }
     int any = 0;
-    for (size_t p = 0; p < total; p++)
-        if (flags[p] && !(live && live[p] == GECM_PAD)) c->bad[p] = (uint8_t)(any = 1);
+    for (size_t p = 0; p < c->batch; p++)
+        if (flags[p] && !(c->multi && c->lay.pos_user[p] == GECM_PAD)) c->bad[p] = (uint8_t)(any = 1);
     free(flags);
     c->last_ms = gecm_dev_last_build_ms(c->dev);
     return any;
 }
 
-/* gecm_build_curves after its checks: the batch allocated, the curves constructed on the host and uploaded or on the
- * device (gecm_set_curve_build), then px != NULL: gecm_resume_points, X and Z replaced by the Montgomery forms of
- * the plain residues px, pz (canonical in [0, N), [nl][batch]), made on the device; last the twin, from what the main
- * context now holds. */
-static int build_single(gecm_ctx *c, const uint64_t *sigma, size_t batch, const uint32_t *px, const uint32_t *pz, const uint8_t *prm)
+/* Step 3: what X, Z, S hold first.  Curves where the batch has sigmas, built where gecm_set_curve_build says; else
+ * the planes given in Montgomery form, or nothing before step 4. */
+static int batch_fill(gecm_ctx *c, const batch_desc *d)
 {
-    c->build_used = c->build_where;
-    int rc = alloc_batch(c, batch);
-    if (rc) return rc;
-    memcpy(c->sigma, sigma, batch * sizeof(uint64_t));
-    if (prm) {                                        /* gecm_set_next_params: a parametrisation per curve */
-        c->param = (uint8_t *)malloc(batch);
-        if (!c->param) { free_batch(c); return GECM_ERR_NOMEM; }
-        memcpy(c->param, prm, batch);
+    if (d->sigma) return c->build_where == GECM_BUILD_DEVICE ? fill_on_device(c) : fill_on_host(c);
+    if (d->content == BATCH_MONT) {
+        const size_t words = (size_t)c->mod.nl * c->batch;
+        if (gecm_dev_upload(c->dev, d->planes, d->planes + words, d->planes + 2 * words)) return GECM_ERR_DEVICE;
     }
-    int built;
-    if (c->build_where == GECM_BUILD_DEVICE) built = build_on_device(c, sigma, batch, NULL);
-    else {
-        const size_t words = (size_t)c->mod.nl * batch;
-        uint32_t *hX = (uint32_t *)calloc(words * 3, 4);
-        if (!hX) { free_batch(c); return GECM_ERR_NOMEM; }
-        gecm_mod_build b = {&c->mod, sigma, c->bad, batch, 0, hX, hX + words, hX + 2 * words, c->param};
-        built = run_slices(batch, gecm_mod_build_slice, &b);
-        if (built >= 0 && gecm_dev_upload(c->dev, hX, hX + words, hX + 2 * words)) {
-            set_err("%s", gecm_dev_error());
-            built = GECM_ERR_DEVICE;
+    return groups_to_device(c);
+}
+
+/* Step 4: X, Z replaced by the Montgomery forms of the plain residues given, made on the device; a multi-modulus
+ * batch through its layout, the padding with x = z = 1. */
+static int batch_overlay(gecm_ctx *c, const batch_desc *d)
+{
+    if (d->content != BATCH_PLAIN) return GECM_OK;
+    const size_t words = (size_t)c->mod.nl * c->batch;
+    const uint32_t *x = d->planes, *z = d->planes + (size_t)c->mod.nl * d->batch;
+    uint32_t *h = NULL;
+    if (c->multi) {
+        if (!(h = (uint32_t *)calloc(words * 2, 4))) return GECM_ERR_NOMEM;
+        scatter_plane(c, h, x, d->batch);
+        scatter_plane(c, h + words, z, d->batch);
+        for (size_t p = 0; p < c->batch; p++)
+            if (c->lay.pos_user[p] == GECM_PAD) h[p] = h[words + p] = 1;
+        x = h;
+        z = h + words;
+    }
+    const int rc = gecm_dev_upload_plain(c->dev, x, z) ? GECM_ERR_DEVICE : GECM_OK;
+    free(h);
+    return rc;
+}
+
+/* Step 5: the twin from what the main context now holds (curves on a single-N context; a multi-modulus context has
+ * none), the seeds in position order, and what the batch was made with.  A wart kept as it was: build_used follows
+ * build_where after every batch with sigmas and every multi-modulus batch, so gecm_get_curve_build answers the
+ * asked-for place after gecm_build_seeds_multi and the previous batch's after gecm_build_seeds (and
+ * gecm_upload_points). */
+static int batch_finish(gecm_ctx *c, const batch_desc *d)
+{
+    if (!d->method && twin_fill(c)) return GECM_ERR_DEVICE;
+    if (d->seed) {
+        if (!(c->seed = (uint32_t *)calloc((size_t)c->mod.nl * c->batch, 4))) return GECM_ERR_NOMEM;
+        scatter_plane(c, c->seed, d->seed, d->batch);
+    }
+    c->method = d->method;
+    if (c->multi) c->packing_used = c->packing;
+    if (d->sigma || c->multi) c->build_used = c->build_where;
+    return GECM_OK;
+}
+
+/* The batch `d` describes into the context; the caller has checked d's arrays.  1 if some constructed curve is marked
+ * bad, GECM_OK, or an error: before the previous batch is given up while the batch is laid out, afterwards with no
+ * batch left and, for a device error, "<who>: <the device layer's text>". */
+static int batch_build(gecm_ctx *c, const batch_desc *d)
+{
+    gecm_layout lay;
+    memset(&lay, 0, sizeof lay);
+    if (c->multi) {                                   /* step 1 */
+        if (d->sigma && c->packing == GECM_PACK_LANE && c->build_where == GECM_BUILD_DEVICE) {
+            set_err("%s: the device curve build has no per-lane kernel: a lane-packed context builds on the host "
+                    "(gecm_set_curve_build, gecm_set_multi_packing)", d->who);
+            return GECM_ERR_STATE;
         }
-        free(hX);
+        const int rc = gecm_layout_make(&lay, d->modulus_index, d->batch, c->ngroups, c->packing);
+        if (rc) return rc;
     }
-    if (built < 0) { free_batch(c); return built; }
-    if ((px && gecm_dev_upload_plain(c->dev, px, pz)) || twin_fill(c)) {
-        set_err("%s", gecm_dev_error());
-        free_batch(c);
-        return GECM_ERR_DEVICE;
-    }
-    return built;
+    int rc = batch_begin(c, d, &lay), anybad = 0;
+    if (!rc && (rc = batch_fill(c, d)) > 0) { anybad = 1; rc = GECM_OK; }
+    if (!rc) rc = batch_overlay(c, d);
+    if (!rc) rc = batch_finish(c, d);
+    if (!rc) return anybad;
+    if (rc == GECM_ERR_DEVICE) set_err("%s: %s", d->who, gecm_dev_error());
+    free_batch(c);
+    return rc;
 }
 
 int gecm_build_curves(gecm_ctx *c, const uint64_t *sigma, size_t batch)
 {
-    size_t prm_batch = 0;
-    uint8_t *prm = take_next_params(c, &prm_batch);
-    if (!c || !sigma || batch == 0) { free(prm); set_err("gecm_build_curves: bad argument"); return GECM_ERR_ARG; }
-    if (c && c->multi) { free(prm); return multi_refuse("gecm_build_curves"); }
     /* inputs are checked before the context takes the new batch: after an error it holds no batch at all (the
      * phase functions then return GECM_ERR_STATE instead of running on memory nothing was uploaded to) */
-    int rc = sigma_args("gecm_build_curves", sigma, batch, prm, prm_batch);
-    if (!rc) rc = build_single(c, sigma, batch, NULL, NULL, prm);
-    free(prm);
-    return rc;
+    int rc = sigma_args(c, "gecm_build_curves", sigma, batch);
+    if (!rc) rc = batch_build(c, &(batch_desc){.who = "gecm_build_curves", .batch = batch, .sigma = sigma, .param = c->next_param});
+    return build_call_end(c, rc);
 }
 
 int gecm_set_curve_build(gecm_ctx *c, int where)
@@ -817,34 +928,41 @@ int gecm_set_curve_build(gecm_ctx *c, int where)
 
 int gecm_get_curve_build(const gecm_ctx *c) { return c ? c->build_used : GECM_ERR_ARG; }
 
-int gecm_upload_points(gecm_ctx *c, const void *X, const void *Z, const void *s, size_t batch)
+/* X, Z, s in the reference's Montgomery radix as planes of the internal one, [3][nl][batch]; NULL: *rc and the text say why */
+static uint32_t *upload_planes(const gecm_ctx *c, const void *X, const void *Z, const void *s, size_t batch, int *rc)
 {
-    if (!c || !X || !Z || !s || batch == 0) { set_err("gecm_upload_points: bad argument"); return GECM_ERR_ARG; }
-    if (c && c->multi) return multi_refuse("gecm_upload_points");
-    int rc = alloc_batch(c, batch);
-    if (rc) return rc;
-    int nl = c->mod.nl;
-    size_t words = (size_t)nl * batch;
+    const size_t words = (size_t)c->mod.nl * batch;
     uint32_t *h = (uint32_t *)calloc(words * 3, 4);
-    if (!h) { free_batch(c); return GECM_ERR_NOMEM; }
     const void *src[3] = {X, Z, s};
+    *rc = GECM_ERR_NOMEM;
+    if (!h) return NULL;
     for (int k = 0; k < 3; k++)
         for (size_t i = 0; i < batch; i++) {
             mpl_t v;
             vec_get(&c->mod, &v, src[k], batch, i);
             if (mpl_cmp(&v, &c->mod.N) >= 0) {
                 free(h);
-                free_batch(c);                 /* the context holds no batch after a rejected upload */
                 set_err("gecm_upload_points: operand not < N");
-                return GECM_ERR_ARG;
+                *rc = GECM_ERR_ARG;
+                return NULL;
             }
             mpl_mulmod(&v, &v, &c->mod.ref_to_int, &c->mod.N);
-            mpl_to_limbs32(h + (size_t)k * words + i, batch, nl, LIMB_BITS, &v);
+            mpl_to_limbs32(h + (size_t)k * words + i, batch, c->mod.nl, LIMB_BITS, &v);
         }
-    rc = gecm_dev_upload(c->dev, h, h + words, h + 2 * words);
+    return h;
+}
+
+/* the one build call a pending gecm_set_next_params setting passes by: it waits for the next of the others */
+int gecm_upload_points(gecm_ctx *c, const void *X, const void *Z, const void *s, size_t batch)
+{
+    if (!c || !X || !Z || !s || batch == 0) { set_err("gecm_upload_points: bad argument"); return GECM_ERR_ARG; }
+    if (c->multi) return multi_refuse("gecm_upload_points");
+    int rc;
+    uint32_t *h = upload_planes(c, X, Z, s, batch, &rc);
+    if (!h) free_batch(c);                     /* the context holds no batch after a rejected upload */
+    else rc = batch_build(c, &(batch_desc){.who = "gecm_upload_points", .batch = batch, .content = BATCH_MONT, .planes = h});
     free(h);
-    if (rc || twin_fill(c)) { set_err("%s", gecm_dev_error()); free_batch(c); return GECM_ERR_DEVICE; }
-    return GECM_OK;
+    return rc;
 }
 
 /* ---- phase 1 -------------------------------------------------------------------------------- */
@@ -1188,9 +1306,9 @@ int gecm_download_points_plain(gecm_ctx *c, void *x, void *z)
 static const gecm_mod *curve_at(const gecm_ctx *c, size_t k, size_t *pos)
 {
     if (!c->multi) { *pos = k; return k < c->batch ? &c->mod : NULL; }
-    if (c->batch == 0 || k >= c->nuser) { set_err("curve %zu: no such curve in the batch", k); return NULL; }
-    *pos = c->slot[k];
-    return &c->grp[c->pos_grp[*pos]];
+    if (c->batch == 0 || k >= c->lay.nuser) { set_err("curve %zu: no such curve in the batch", k); return NULL; }
+    *pos = c->lay.slot[k];
+    return &c->grp[c->lay.pos_grp[*pos]];
 }
 
 int gecm_curve_param(const gecm_ctx *c, size_t k)
@@ -1278,7 +1396,7 @@ int gecm_normalize_points(gecm_ctx *c)
     if (gecm_dev_normalize(c->dev, flags)) { free(flags); free(left); set_err("%s", gecm_dev_error()); return GECM_ERR_DEVICE; }
     int any = 0;
     for (size_t p = 0; p < batch; p++)
-        if (flags[p] && !(c->multi && c->pos_user[p] == GECM_PAD)) left[p] = (uint8_t)(any = 1);
+        if (flags[p] && !(c->multi && c->lay.pos_user[p] == GECM_PAD)) left[p] = (uint8_t)(any = 1);
     free(flags);
     free(c->norm_left);
     c->norm_left = left;
@@ -1697,14 +1815,14 @@ int gecm_scan_factors(gecm_ctx *c, int stage, size_t *first)
      * curves) is then host work, off the device's queue */
     int rc = stage == 1 ? fetch_plain(c) : fetch_acc(c);
     if (rc) return rc;
-    size_t n = 0, lo = c->multi ? c->nuser : c->batch;
+    size_t n = 0, lo = c->multi ? c->lay.nuser : c->batch;
     for (size_t p = 0; p < c->batch; p++) {
         const gecm_mod *m = &c->mod;
         size_t user = p;
         if (c->multi) {
-            if (c->pos_user[p] == GECM_PAD) { (*f)[p] = 0; continue; }
-            m = &c->grp[c->pos_grp[p]];
-            user = c->pos_user[p];
+            if (c->lay.pos_user[p] == GECM_PAD) { (*f)[p] = 0; continue; }
+            m = &c->grp[c->lay.pos_grp[p]];
+            user = c->lay.pos_user[p];
         }
         mpl_t fr, g;
         mpl_set_u64(&fr, 0);
@@ -1803,13 +1921,6 @@ int gecm_multi_packing_max_bits(int packing)
     return nl ? nl * LIMB_BITS - 5 : GECM_ERR_STATE;   /* R = 2^(28 nl) >= 32 N, as pick_nl */
 }
 
-size_t gecm_multi_positions(const size_t *counts, size_t n, int packing)
-{
-    size_t total = 0;
-    for (size_t g = 0; counts && g < n; g++) total += packing == GECM_PACK_LANE ? counts[g] : (counts[g] + 63) / 64 * 64;
-    return (total + 63) / 64 * 64;
-}
-
 int gecm_set_multi_packing(gecm_ctx *c, int packing)
 {
     if (!c || (packing != GECM_PACK_WAVE && packing != GECM_PACK_LANE)) {
@@ -1829,15 +1940,14 @@ int gecm_set_multi_packing(gecm_ctx *c, int packing)
 int gecm_get_multi_packing(const gecm_ctx *c) { return c ? c->packing_used : GECM_ERR_ARG; }
 
 /* the checks gecm_build_curves_multi and gecm_resume_points_multi make on their common arguments */
-static int multi_args(const gecm_ctx *c, const char *who, const uint64_t *sigma, const uint32_t *modulus_index, size_t batch,
-                      const uint8_t *prm, size_t prm_batch)
+static int multi_args(const gecm_ctx *c, const char *who, const uint64_t *sigma, const uint32_t *modulus_index, size_t batch)
 {
     if (!c || !sigma || !modulus_index || batch == 0) { set_err("%s: bad argument", who); return GECM_ERR_ARG; }
     if (!c->multi) { set_err("%s: not a multi-modulus context (gecm_create_multi)", who); return GECM_ERR_STATE; }
     if (batch >= GECM_PAD) { set_err("%s: batch too large", who); return GECM_ERR_ARG; }
-    if (params_fit(who, batch, prm, prm_batch)) return GECM_ERR_ARG;
+    if (params_fit(c, who, batch)) return GECM_ERR_ARG;
     for (size_t i = 0; i < batch; i++) {
-        if (sigma_arg(who, sigma, i, prm)) return GECM_ERR_ARG;
+        if (sigma_arg(who, sigma, i, c->next_param)) return GECM_ERR_ARG;
         if (modulus_index[i] >= c->ngroups) {
             set_err("%s: modulus_index[%zu] = %u, the context has %zu moduli", who, i, modulus_index[i], c->ngroups);
             return GECM_ERR_ARG;
@@ -1846,122 +1956,12 @@ static int multi_args(const gecm_ctx *c, const char *who, const uint64_t *sigma,
     return GECM_OK;
 }
 
-/* gecm_build_curves_multi after its checks; ux != NULL: gecm_resume_points_multi, the points are the plain residues ux,
- * uz ([nl][batch], the caller's order), the padding gets x = z = 1 */
-/* seeds != 0: gecm_build_seeds_multi, no curves are built at all (sigma NULL: 0 throughout); S stays what it is */
-static int build_multi(gecm_ctx *c, const char *who, const uint64_t *sigma, const uint32_t *modulus_index, size_t batch,
-                       const uint32_t *ux, const uint32_t *uz, const uint8_t *prm, int seeds)
-{
-    /* positions: the moduli in order, each one's curves in the caller's order, padded to a multiple of 64; lane-packed:
-     * back to back, and the batch's tail padded (modulus 0 there: computed, never read) */
-    const size_t ng = c->ngroups;
-    const int lane = c->packing == GECM_PACK_LANE;
-    if (lane && c->build_where == GECM_BUILD_DEVICE && !seeds) {        /* before the previous batch is given up */
-        set_err("%s: the device curve build has no per-lane kernel: a lane-packed context builds on the host "
-                "(gecm_set_curve_build, gecm_set_multi_packing)", who);
-        return GECM_ERR_STATE;
-    }
-    size_t *cnt = (size_t *)calloc(ng, sizeof(size_t)), *goff = (size_t *)calloc(ng, sizeof(size_t));
-    if (!cnt || !goff) { free(cnt); free(goff); return GECM_ERR_NOMEM; }
-    for (size_t i = 0; i < batch; i++) cnt[modulus_index[i]]++;
-    /* positions of one group: its curves, under wave packing with its own padding (gecm_multi_positions has the rule) */
-#define GROUP_SPAN(g) (lane ? cnt[g] : gecm_multi_positions(&cnt[g], 1, GECM_PACK_WAVE))
-    const size_t total = gecm_multi_positions(cnt, ng, c->packing);
-    for (size_t g = 0, off = 0; g < ng; g++) { goff[g] = off; off += GROUP_SPAN(g); }
-    int rc = alloc_batch(c, total);
-    uint32_t *slot = (uint32_t *)malloc(batch * sizeof(uint32_t)), *pos_user = (uint32_t *)malloc(total * sizeof(uint32_t));
-    uint32_t *pos_grp = (uint32_t *)malloc(total * sizeof(uint32_t));
-    /* wave packing: the modulus of every 64-curve block, which the kernels read there (lane packing: pos_grp) */
-    uint32_t *blocks = lane ? NULL : (uint32_t *)malloc(total / 64 * sizeof(uint32_t));
-    const size_t words = (size_t)c->mod.nl * total;
-    uint32_t *hX = (uint32_t *)calloc(words * 3, 4);           /* padding stays zero: computed, never read */
-    /* gecm_set_next_params: the parametrisation of every position, the padding's 0 */
-    uint8_t *param = prm ? (uint8_t *)calloc(total, 1) : NULL;
-    if (!rc && (!slot || !pos_user || !pos_grp || (!lane && !blocks) || !hX || (prm && !param))) rc = GECM_ERR_NOMEM;
-    if (rc) {
-        free(param);
-        free(cnt); free(goff); free(slot); free(pos_user); free(pos_grp); free(blocks); free(hX);
-        free_batch(c);
-        return rc;
-    }
-    c->slot = slot; c->pos_user = pos_user; c->pos_grp = pos_grp; c->nuser = batch;
-    c->param = param;
-    for (size_t p = 0; lane && p < total; p++) {
-        pos_grp[p] = 0;
-        pos_user[p] = GECM_PAD;
-    }
-    for (size_t g = 0; g < ng; g++)
-        for (size_t p = goff[g]; p < goff[g] + GROUP_SPAN(g); p++) {
-            pos_grp[p] = (uint32_t)g;
-            pos_user[p] = GECM_PAD;
-            if (!lane) blocks[p / 64] = (uint32_t)g;
-        }
-#undef GROUP_SPAN
-    memset(cnt, 0, ng * sizeof(size_t));
-    for (size_t i = 0; i < batch; i++) {
-        const uint32_t g = modulus_index[i];
-        const size_t p = goff[g] + cnt[g]++;
-        slot[i] = (uint32_t)p;
-        pos_user[p] = (uint32_t)i;
-        c->sigma[p] = sigma ? sigma[i] : 0;
-        if (param) param[p] = prm[i];
-    }
-    /* the Suyama construction modulus by modulus: what gecm_build_curves does for its one */
-    int anybad = 0;
-    c->build_used = c->build_where;
-    const int on_device = c->build_where == GECM_BUILD_DEVICE && !seeds;
-    for (size_t g = 0; g < ng && !rc && !on_device && !seeds; g++) {
-        gecm_mod_build b = {&c->grp[g], c->sigma + goff[g], c->bad, total, goff[g], hX, hX + words, hX + 2 * words,
-                            param ? param + goff[g] : NULL};
-        const int built = run_slices(cnt[g], gecm_mod_build_slice, &b);
-        if (built < 0) rc = built;
-        else anybad |= built;
-    }
-    free(goff);
-    free(cnt);
-    if (!rc && !on_device && !seeds && gecm_dev_upload(c->dev, hX, hX + words, hX + 2 * words)) rc = GECM_ERR_DEVICE;
-    if (!rc && gecm_dev_set_groups(c->dev, (uint32_t)ng, c->grp_dev, blocks, lane ? pos_grp : NULL)) rc = GECM_ERR_DEVICE;
-    if (!rc && on_device) {              /* the kernel takes every block's modulus from the groups just set */
-        const int built = build_on_device(c, c->sigma, total, pos_user);
-        if (built < 0) {
-            free(hX); free(blocks);
-            free_batch(c);
-            return built;
-        }
-        anybad = built;
-    }
-    if (!rc && ux) {
-        uint32_t *dx = hX, *dz = hX + words;                     /* the build's X, Z: dropped */
-        memset(hX, 0, words * 2 * sizeof(uint32_t));
-        for (size_t p = 0; p < total; p++) {
-            const uint32_t i = pos_user[p];
-            if (i == GECM_PAD) { dx[p] = dz[p] = 1; continue; }
-            for (size_t l = 0; l < (size_t)c->mod.nl; l++) {
-                dx[l * total + p] = ux[l * batch + i];
-                dz[l * total + p] = uz[l * batch + i];
-            }
-        }
-        if (gecm_dev_upload_plain(c->dev, dx, dz)) rc = GECM_ERR_DEVICE;
-    }
-    free(hX);
-    free(blocks);
-    if (rc) {
-        if (rc == GECM_ERR_DEVICE) set_err("%s: %s", who, gecm_dev_error());
-        free_batch(c);
-        return rc;
-    }
-    c->packing_used = c->packing;
-    return anybad ? 1 : GECM_OK;
-}
-
 int gecm_build_curves_multi(gecm_ctx *c, const uint64_t *sigma, const uint32_t *modulus_index, size_t batch)
 {
-    size_t prm_batch = 0;
-    uint8_t *prm = take_next_params(c, &prm_batch);
-    int rc = multi_args(c, "gecm_build_curves_multi", sigma, modulus_index, batch, prm, prm_batch);
-    if (!rc) rc = build_multi(c, "gecm_build_curves_multi", sigma, modulus_index, batch, NULL, NULL, prm, 0);
-    free(prm);
-    return rc;
+    int rc = multi_args(c, "gecm_build_curves_multi", sigma, modulus_index, batch);
+    if (!rc) rc = batch_build(c, &(batch_desc){.who = "gecm_build_curves_multi", .batch = batch, .sigma = sigma,
+                                               .modulus_index = modulus_index, .param = c->next_param});
+    return build_call_end(c, rc);
 }
 
 /* ---- resume ------------------------------------------------------------------- */
@@ -1997,58 +1997,55 @@ static int plain_slice(void *arg, size_t lo, size_t hi)
     return 0;
 }
 
-/* what both resume calls do once their context kind is settled; idx NULL on a single-N context */
+/* a batch that goes on from points given: stage 1 stands at b1_done and the counters start over, they count what runs
+ * from here */
+static void stage1_restart(gecm_ctx *c, uint64_t b1_done)
+{
+    c->B1 = b1_done;
+    c->s1_ptadds = c->s1_ptdups = c->s1_last_prime = c->s1_tape_len = 0;
+}
+
+/* what both resume calls do once their context kind and sigmas are settled; idx NULL on a single-N context */
 static int resume_points(gecm_ctx *c, const char *who, const uint64_t *sigma, const uint32_t *idx, const void *x,
-                         const void *z, size_t batch, uint64_t b1_done, const uint8_t *prm)
+                         const void *z, size_t batch, uint64_t b1_done)
 {
     if (!x || !z) { set_err("%s: bad argument", who); return GECM_ERR_ARG; }
     if (b1_done == 1 || b1_done > GECM_B1_MAX) { set_err("%s: b1_done must be 0 or a B1 in [2, %llu]", who, (unsigned long long)GECM_B1_MAX); return GECM_ERR_ARG; }
-    const size_t words = (size_t)c->mod.nl * batch;
-    uint32_t *planes = (uint32_t *)calloc(words * 2, 4);
+    uint32_t *planes = (uint32_t *)calloc((size_t)c->mod.nl * batch * 2, 4);
     if (!planes) return GECM_ERR_NOMEM;
     plain_job j = {c, {x, z}, idx, batch, planes, batch};
-    const int bad = run_slices(batch, plain_slice, &j);
-    if (bad) {
-        free(planes);
-        if (bad < 0) return bad;
+    int rc = run_slices(batch, plain_slice, &j);
+    if (rc > 0) {                                 /* the previous batch is untouched */
         set_err("%s: x[%zu] or z[%zu] is not below the curve's N", who, j.first_bad, j.first_bad);
-        return GECM_ERR_ARG;                      /* the previous batch is untouched */
+        rc = GECM_ERR_ARG;
+    } else if (!rc) {
+        /* the curves of the sigmas (S), then X and Z from the planes: mid stage 1 (the caller goes on with
+         * gecm_stage1_range), or stage 1 taken as finished at b1_done */
+        rc = batch_build(c, &(batch_desc){.who = who, .batch = batch, .sigma = sigma, .modulus_index = idx, .param = c->next_param,
+                                          .content = BATCH_PLAIN, .planes = planes});
+        if (rc >= 0) stage1_restart(c, b1_done);
     }
-    const int built = idx ? build_multi(c, who, sigma, idx, batch, planes, planes + words, prm, 0)
-                          : build_single(c, sigma, batch, planes, planes + words, prm);
     free(planes);
-    if (built < 0) return built;
-    /* mid stage 1 (the caller goes on with gecm_stage1_range), or stage 1 taken as finished at b1_done; the counters
-     * start over: they count the ranges run from here */
-    c->B1 = b1_done;
-    c->s1_ptadds = c->s1_ptdups = c->s1_last_prime = c->s1_tape_len = 0;
-    return built;
+    return rc;
 }
 
 int gecm_resume_points(gecm_ctx *c, const uint64_t *sigma, const void *x, const void *z, size_t batch, uint64_t b1_done)
 {
-    size_t prm_batch = 0;
-    uint8_t *prm = take_next_params(c, &prm_batch);
-    if (!c || !sigma || batch == 0) { free(prm); set_err("gecm_resume_points: bad argument"); return GECM_ERR_ARG; }
-    if (c->multi) { free(prm); return multi_refuse("gecm_resume_points"); }
-    int rc = sigma_args("gecm_resume_points", sigma, batch, prm, prm_batch);
-    if (!rc) rc = resume_points(c, "gecm_resume_points", sigma, NULL, x, z, batch, b1_done, prm);
-    free(prm);
-    return rc;
+    int rc = sigma_args(c, "gecm_resume_points", sigma, batch);
+    if (!rc) rc = resume_points(c, "gecm_resume_points", sigma, NULL, x, z, batch, b1_done);
+    return build_call_end(c, rc);
 }
 
 int gecm_resume_points_multi(gecm_ctx *c, const uint64_t *sigma, const uint32_t *modulus_index, const void *x,
                              const void *z, size_t batch, uint64_t b1_done)
 {
-    size_t prm_batch = 0;
-    uint8_t *prm = take_next_params(c, &prm_batch);
-    int rc = multi_args(c, "gecm_resume_points_multi", sigma, modulus_index, batch, prm, prm_batch);
-    if (!rc) rc = resume_points(c, "gecm_resume_points_multi", sigma, modulus_index, x, z, batch, b1_done, prm);
-    free(prm);
-    return rc;
+    int rc = multi_args(c, "gecm_resume_points_multi", sigma, modulus_index, batch);
+    if (!rc) rc = resume_points(c, "gecm_resume_points_multi", sigma, modulus_index, x, z, batch, b1_done);
+    return build_call_end(c, rc);
 }
 
 /* ---- P-1 and P+1 batches -------------------------------------------------------- */
+/* what both seed calls do once their context kind is settled; idx NULL on a single-N context */
 static int build_seeds(gecm_ctx *c, const char *who, int method, const uint32_t *idx, const void *x0, const void *x,
                        size_t batch, uint64_t b1_done)
 {
@@ -2069,62 +2066,42 @@ static int build_seeds(gecm_ctx *c, const char *who, int method, const uint32_t 
             set_err("%s: modulus_index[%zu] = %u, the context has %zu moduli", who, i, idx[i], c->ngroups);
             return GECM_ERR_ARG;
         }
-    const int nl = c->mod.nl;
-    const size_t words = (size_t)nl * batch;
+    const size_t words = (size_t)c->mod.nl * batch;
     uint32_t *planes = (uint32_t *)calloc(words * 3, 4);        /* x0 (or x), x (or x0), z = 1: the caller's order */
     if (!planes) return GECM_ERR_NOMEM;
     plain_job j = {c, {x0 ? x0 : x, x ? x : x0}, idx, batch, planes, batch};
-    const int bad = run_slices(batch, plain_slice, &j);
-    if (bad) {
-        free(planes);
-        if (bad < 0) return bad;
+    int rc = run_slices(batch, plain_slice, &j);
+    if (rc > 0) {                                 /* the previous batch is untouched */
         set_err("%s: x0[%zu] or x[%zu] is not below its N", who, j.first_bad, j.first_bad);
-        return GECM_ERR_ARG;                      /* the previous batch is untouched */
-    }
-    for (size_t i = 0; i < batch; i++) planes[2 * words + i] = 1;
-    int rc;
-    if (idx) rc = build_multi(c, who, NULL, idx, batch, planes + words, planes + 2 * words, NULL, 1);
-    else {
-        rc = alloc_batch(c, batch);
-        if (!rc && gecm_dev_upload_plain(c->dev, planes + words, planes + 2 * words)) {
-            set_err("%s: %s", who, gecm_dev_error());
-            free_batch(c);
-            rc = GECM_ERR_DEVICE;
-        }
-    }
-    if (!rc && x0) {                              /* the seeds, in device order */
-        c->seed = (uint32_t *)calloc((size_t)nl * c->batch, 4);
-        if (!c->seed) { free_batch(c); rc = GECM_ERR_NOMEM; }
-        for (size_t i = 0; !rc && i < batch; i++) {
-            const size_t p = idx ? c->slot[i] : i;
-            for (int l = 0; l < nl; l++) c->seed[(size_t)l * c->batch + p] = planes[(size_t)l * batch + i];
-        }
+        rc = GECM_ERR_ARG;
+    } else if (!rc) {
+        for (size_t i = 0; i < batch; i++) planes[2 * words + i] = 1;
+        /* no sigmas, so no curves: the residues are all the batch holds, and S stays what it is */
+        rc = batch_build(c, &(batch_desc){.who = who, .batch = batch, .modulus_index = idx, .content = BATCH_PLAIN,
+                                          .planes = planes + words, .method = method, .seed = x0 ? planes : NULL});
+        if (!rc) stage1_restart(c, b1_done);
     }
     free(planes);
-    if (rc) return rc;
-    c->method = method;
-    c->B1 = b1_done;
-    c->s1_ptadds = c->s1_ptdups = c->s1_last_prime = c->s1_tape_len = 0;
-    return GECM_OK;
+    return rc;
 }
 
 int gecm_build_seeds(gecm_ctx *c, int method, const void *x0, const void *x, size_t batch, uint64_t b1_done)
 {
-    size_t prm_batch = 0;
-    free(take_next_params(c, &prm_batch));        /* a pending setting does not apply to seeds */
-    if (!c) { set_err("gecm_build_seeds: bad argument"); return GECM_ERR_ARG; }
-    if (c->multi) return multi_refuse("gecm_build_seeds");
-    return build_seeds(c, "gecm_build_seeds", method, NULL, x0, x, batch, b1_done);
+    int rc;
+    if (!c) { set_err("gecm_build_seeds: bad argument"); rc = GECM_ERR_ARG; }
+    else if (c->multi) rc = multi_refuse("gecm_build_seeds");
+    else rc = build_seeds(c, "gecm_build_seeds", method, NULL, x0, x, batch, b1_done);
+    return build_call_end(c, rc);                 /* a pending setting does not apply to seeds: dropped unused */
 }
 
 int gecm_build_seeds_multi(gecm_ctx *c, int method, const uint32_t *modulus_index, const void *x0, const void *x,
                            size_t batch, uint64_t b1_done)
 {
-    size_t prm_batch = 0;
-    free(take_next_params(c, &prm_batch));
-    if (!c || !modulus_index) { set_err("gecm_build_seeds_multi: bad argument"); return GECM_ERR_ARG; }
-    if (!c->multi) { set_err("gecm_build_seeds_multi: not a multi-modulus context (gecm_create_multi)"); return GECM_ERR_STATE; }
-    return build_seeds(c, "gecm_build_seeds_multi", method, modulus_index, x0, x, batch, b1_done);
+    int rc;
+    if (!c || !modulus_index) { set_err("gecm_build_seeds_multi: bad argument"); rc = GECM_ERR_ARG; }
+    else if (!c->multi) { set_err("gecm_build_seeds_multi: not a multi-modulus context (gecm_create_multi)"); rc = GECM_ERR_STATE; }
+    else rc = build_seeds(c, "gecm_build_seeds_multi", method, modulus_index, x0, x, batch, b1_done);
+    return build_call_end(c, rc);
 }
 
 int gecm_batch_method(const gecm_ctx *c) { return c && c->batch ? c->method : GECM_METHOD_ECM; }
@@ -2151,8 +2128,8 @@ int gecm_curve_seed(gecm_ctx *c, size_t k, char *hex, size_t hexlen)
 
 int gecm_curve_modulus(const gecm_ctx *c, size_t k)
 {
-    if (!c || !c->multi || k >= c->nuser) { set_err("gecm_curve_modulus: no such curve in a multi-modulus batch"); return GECM_ERR_ARG; }
-    return (int)c->pos_grp[c->slot[k]];
+    if (!c || !c->multi || k >= c->lay.nuser) { set_err("gecm_curve_modulus: no such curve in a multi-modulus batch"); return GECM_ERR_ARG; }
+    return (int)c->lay.pos_grp[c->lay.slot[k]];
 }
 
 int gecm_curve_acc(gecm_ctx *c, size_t k, char *hex, size_t hexlen)

@@ -1,5 +1,6 @@
 /* gecm_mod.c — the device-free part of the host library (gecm_mod.h): the constants of one number, the curve
- * construction, failure records and the factor report.  Mirrors the reference's
+ * construction, failure records, the factor report and the position layout of a multi-modulus batch.  Mirrors the
+ * reference's
  *   Montgomery constants        main.c:597-640
  *   NWORDS/MAXBITS rule         main.c:465-483
  *   build_one_curve             ecm.c:1548-1803
@@ -330,6 +331,69 @@ int gecm_mod_factor(const gecm_mod *m, mpl_t *g, const char *who, char *dec, siz
     }
     if (is_prp) *is_prp = mpl_probab_prime(g, 3);   /* ecm.c:1346 */
     return 1;
+}
+
+/* ---- the position layout of a multi-modulus batch ---- */
+size_t gecm_multi_positions(const size_t *counts, size_t n, int packing)
+{
+    size_t total = 0;
+    for (size_t g = 0; counts && g < n; g++) total += packing == GECM_PACK_LANE ? counts[g] : (counts[g] + 63) / 64 * 64;
+    return (total + 63) / 64 * 64;
+}
+
+int gecm_layout_make(gecm_layout *l, const uint32_t *modulus_index, size_t batch, size_t ngroups, int packing)
+{
+    const int lane = packing == GECM_PACK_LANE;
+    memset(l, 0, sizeof *l);
+    if (!modulus_index || batch == 0 || batch >= GECM_PAD || ngroups == 0) return GECM_ERR_ARG;
+    int rc = GECM_ERR_NOMEM;
+    l->slot = (uint32_t *)malloc(batch * sizeof(uint32_t));
+    l->goff = (size_t *)calloc(ngroups, sizeof(size_t));
+    l->cnt = (size_t *)calloc(ngroups, sizeof(size_t));
+    if (!l->slot || !l->goff || !l->cnt) goto fail;
+    rc = GECM_ERR_ARG;
+    for (size_t i = 0; i < batch; i++) {
+        if (modulus_index[i] >= ngroups) goto fail;
+        l->cnt[modulus_index[i]]++;
+    }
+    l->nuser = batch;
+    l->ngroups = ngroups;
+    l->total = gecm_multi_positions(l->cnt, ngroups, packing);
+    if (l->total >= GECM_PAD) goto fail;
+    rc = GECM_ERR_NOMEM;
+    l->pos_user = (uint32_t *)malloc(l->total * sizeof(uint32_t));
+    l->pos_grp = (uint32_t *)calloc(l->total, sizeof(uint32_t));      /* lane packing: the tail stays on modulus 0 */
+    /* wave packing: the modulus of every 64-curve block, which the kernels read there (lane packing: pos_grp) */
+    if (!lane) l->blocks = (uint32_t *)malloc(l->total / 64 * sizeof(uint32_t));
+    if (!l->pos_user || !l->pos_grp || (!lane && !l->blocks)) goto fail;
+    memset(l->pos_user, 0xff, l->total * sizeof(uint32_t));          /* GECM_PAD until a curve takes the position */
+    for (size_t g = 0, off = 0; g < ngroups; g++) {
+        /* positions of one modulus: its curves, under wave packing with its own padding */
+        const size_t span = lane ? l->cnt[g] : gecm_multi_positions(&l->cnt[g], 1, GECM_PACK_WAVE);
+        l->goff[g] = off;
+        for (size_t p = off; p < off + span; p++) {
+            l->pos_grp[p] = (uint32_t)g;
+            if (!lane) l->blocks[p / 64] = (uint32_t)g;
+        }
+        off += span;
+    }
+    memset(l->cnt, 0, ngroups * sizeof(size_t));
+    for (size_t i = 0; i < batch; i++) {
+        const uint32_t g = modulus_index[i];
+        const size_t p = l->goff[g] + l->cnt[g]++;
+        l->slot[i] = (uint32_t)p;
+        l->pos_user[p] = (uint32_t)i;
+    }
+    return GECM_OK;
+fail:
+    gecm_layout_free(l);
+    return rc;
+}
+
+void gecm_layout_free(gecm_layout *l)
+{
+    free(l->slot); free(l->pos_user); free(l->pos_grp); free(l->blocks); free(l->goff); free(l->cnt);
+    memset(l, 0, sizeof *l);
 }
 
 /* the hash of the host sources this object was compiled from (Makefile: H_SHA); gecm_version() compares them */

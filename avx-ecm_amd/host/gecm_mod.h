@@ -1,6 +1,7 @@
 /* gecm_mod.h — one number N and everything derived from it, and the host work that needs nothing else: the Suyama
- * curve construction, the failed-inversion records of stage 2, the factor report.  No device, no batch state: a
- * context (gecm_api.c) holds one gecm_mod, a multi-modulus context one more per modulus. */
+ * curve construction, the failed-inversion records of stage 2, the factor report, and the position layout of a
+ * multi-modulus batch (gecm_layout, with gecm_multi_positions).  No device, no batch state: a context (gecm_api.c)
+ * holds one gecm_mod, a multi-modulus context one more per modulus and the gecm_layout of its batch. */
 #ifndef GECM_MOD_H
 #define GECM_MOD_H
 #include "mpl.h"
@@ -77,4 +78,22 @@ void gecm_mod_fail_record(const gecm_mod *m, const uint32_t *hfail, uint32_t pla
 /* g = gcd(value, N): 1 with the decimal string and PRP test if it holds a proper factor of the report modulus,
  * else 0; GECM_ERR_ARG "<who>: buffer too small" */
 int gecm_mod_factor(const gecm_mod *m, mpl_t *g, const char *who, char *dec, size_t declen, int *is_prp);
+
+/* The positions of a multi-modulus batch: the moduli in order, each one's curves in the caller's
+ * order.  Wave packing pads every modulus that has curves to whole blocks of 64 positions; lane packing lays them back
+ * to back and pads the batch's tail, on modulus 0.  gecm_multi_positions (include/gecm.h) is the padding rule.  A
+ * single-N batch has no layout: position = curve, and the struct stays zero. */
+#define GECM_PAD 0xffffffffu
+typedef struct {
+    size_t nuser, total, ngroups;
+    uint32_t *slot;          /* [nuser]      caller's curve -> position */
+    uint32_t *pos_user;      /* [total]      position -> caller's curve, GECM_PAD for padding */
+    uint32_t *pos_grp;       /* [total]      position -> modulus */
+    uint32_t *blocks;        /* [total / 64] wave packing: the modulus of every block; NULL under lane packing */
+    size_t *goff, *cnt;      /* [ngroups]    first position and curve count of every modulus */
+} gecm_layout;
+/* GECM_ERR_NOMEM; GECM_ERR_ARG: no curve or GECM_PAD or more positions, no modulus, some modulus_index[i] >= ngroups.
+ * On error l holds nothing to free; gecm_layout_free leaves l zero and may be called again. */
+int gecm_layout_make(gecm_layout *l, const uint32_t *modulus_index, size_t batch, size_t ngroups, int packing);
+void gecm_layout_free(gecm_layout *l);
 #endif
