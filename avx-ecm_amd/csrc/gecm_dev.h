@@ -154,6 +154,16 @@ int gecm_dev_gcd_scan(gecm_dev *d, int which, uint32_t *flags, uint32_t *g);
 #define GECM_UNIT_PP1 2
 int gecm_dev_stage1_unit(gecm_dev *d, int method);
 int gecm_dev_gcd_scan_off(gecm_dev *d, uint32_t off, uint32_t *flags, uint32_t *g);
+/* ---- stage 2 of such a batch: gecm_dev_s2_init / gecm_dev_s2_pair with the method as first argument ----
+ * The same allocations, slices and K; the table and the giant steps are values V_n(P) of the Lucas sequence of
+ * P = x (P+1) or x + 1/x (P-1), written to S of the batch (X and Z stay as they are); the pair walk, the merge,
+ * gecm_dev_s2_download and gecm_dev_gcd_scan(which = 1) are shared.  Only P-1 inverts, once per position: where x has
+ * no inverse, plane 0 of the failure record takes gcd(x, N).  Bit 31 of a "generate" mark is ignored. */
+int gecm_dev_s2_init_unit(gecm_dev *d, int method, const uint32_t *keep, size_t keep_words, uint32_t umax, uint32_t D,
+                          uint32_t npb, uint32_t G, uint32_t ring_size, const uint32_t *tgt, const uint32_t *tgt_off,
+                          uint32_t K);
+int gecm_dev_s2_pair_unit(gecm_dev *d, int method, const uint32_t *steps, uint32_t nsteps, uint32_t D, uint32_t G,
+                          uint32_t ring_size, uint64_t A0, uint64_t tape_id);
 
 #ifdef __cplusplus
 }

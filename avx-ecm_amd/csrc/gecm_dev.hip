@@ -947,9 +947,23 @@ static uint32_t s2_slices_for(const gecm_dev *d, size_t stride)
 
 extern "C" uint32_t gecm_dev_s2_fail_planes(gecm_dev *d) { return d->s2_K > 1 ? d->s2_K + 1 : 1; }
 
-extern "C" int gecm_dev_s2_init(gecm_dev *d, const uint32_t *keep, size_t keep_words, uint32_t umax, uint32_t D,
-                                uint32_t npb, uint32_t G, uint32_t ring_size, const uint32_t *tgt, const uint32_t *tgt_off,
-                                uint32_t K)
+/* method: 0 for a batch of curves, else GECM_UNIT_PM1 / GECM_UNIT_PP1.  Allocation, slices and the K
+ * choice are the same for both; a method batch leaves the block scratch and the Z halves of Pd untouched. */
+static int unit_method_ok(const gecm_dev *d, const char *fn, int method)
+{
+    if (method != GECM_UNIT_PM1 && method != GECM_UNIT_PP1) {
+        g_err = std::string(fn) + ": the method must be P-1 or P+1";
+        return -2;
+    }
+    if (d->multi && d->lane_packed && !d->k1->has_lane) {
+        g_err = std::string(fn) + ": no per-lane kernels at this limb count";
+        return -2;
+    }
+    return 0;
+}
+
+static int s2_init_any(gecm_dev *d, int method, const uint32_t *keep, size_t keep_words, uint32_t umax, uint32_t D,
+                       uint32_t npb, uint32_t G, uint32_t ring_size, const uint32_t *tgt, const uint32_t *tgt_off, uint32_t K)
 {
     HIPCHK(hipSetDevice(d->device));
     if (ready(d, "gecm_dev_s2_init", true)) return -2;
@@ -1015,15 +1029,31 @@ extern "C" int gecm_dev_s2_init(gecm_dev *d, const uint32_t *keep, size_t keep_w
     d->s2_k_chunks = 0;
     gecm_modconst mc = modconst(d);
     HIPCHK(hipEventRecord(d->ev0, d->stream));
-    d->k2->s2_init(d->stream, &mc, &L);
+    if (method) d->k2->s2_init_unit(d->stream, &mc, &L, method == GECM_UNIT_PM1);
+    else d->k2->s2_init(d->stream, &mc, &L);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(d->ev1, d->stream));
     d->timed = true;
     return 0;
 }
 
-extern "C" int gecm_dev_s2_pair(gecm_dev *d, const uint32_t *steps, uint32_t nsteps, uint32_t D, uint32_t G,
-                                uint32_t ring_size, uint64_t A0, uint64_t tape_id)
+extern "C" int gecm_dev_s2_init(gecm_dev *d, const uint32_t *keep, size_t keep_words, uint32_t umax, uint32_t D,
+                                uint32_t npb, uint32_t G, uint32_t ring_size, const uint32_t *tgt, const uint32_t *tgt_off,
+                                uint32_t K)
+{
+    return s2_init_any(d, 0, keep, keep_words, umax, D, npb, G, ring_size, tgt, tgt_off, K);
+}
+
+extern "C" int gecm_dev_s2_init_unit(gecm_dev *d, int method, const uint32_t *keep, size_t keep_words, uint32_t umax,
+                                     uint32_t D, uint32_t npb, uint32_t G, uint32_t ring_size, const uint32_t *tgt,
+                                     const uint32_t *tgt_off, uint32_t K)
+{
+    if (unit_method_ok(d, "gecm_dev_s2_init_unit", method)) return -2;
+    return s2_init_any(d, method, keep, keep_words, umax, D, npb, G, ring_size, tgt, tgt_off, K);
+}
+
+static int s2_pair_any(gecm_dev *d, int method, const uint32_t *steps, uint32_t nsteps, uint32_t D, uint32_t G,
+                       uint32_t ring_size, uint64_t A0, uint64_t tape_id)
 {
     HIPCHK(hipSetDevice(d->device));
     if (!d->dPbX || d->s2_G != G || d->s2_ring != ring_size || (ring_size & (ring_size - 1))) {
@@ -1058,11 +1088,25 @@ extern "C" int gecm_dev_s2_pair(gecm_dev *d, const uint32_t *steps, uint32_t nst
     }
     gecm_modconst mc = modconst(d);
     HIPCHK(hipEventRecord(d->ev0, d->stream));
-    d->k2->s2_pair(d->stream, &mc, &L);
+    if (method) d->k2->s2_pair_unit(d->stream, &mc, &L);
+    else d->k2->s2_pair(d->stream, &mc, &L);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(d->ev1, d->stream));
     d->timed = true;
     return 0;
+}
+
+extern "C" int gecm_dev_s2_pair(gecm_dev *d, const uint32_t *steps, uint32_t nsteps, uint32_t D, uint32_t G,
+                                uint32_t ring_size, uint64_t A0, uint64_t tape_id)
+{
+    return s2_pair_any(d, 0, steps, nsteps, D, G, ring_size, A0, tape_id);
+}
+
+extern "C" int gecm_dev_s2_pair_unit(gecm_dev *d, int method, const uint32_t *steps, uint32_t nsteps, uint32_t D, uint32_t G,
+                                     uint32_t ring_size, uint64_t A0, uint64_t tape_id)
+{
+    if (unit_method_ok(d, "gecm_dev_s2_pair_unit", method)) return -2;
+    return s2_pair_any(d, method, steps, nsteps, D, G, ring_size, A0, tape_id);
 }
 
 extern "C" int gecm_dev_s2_download(gecm_dev *d, uint32_t *acc, uint32_t *fail)

@@ -106,6 +106,11 @@ template <int NL>
 struct LaneConstK : LaneConst<NL> {
 };
 
+// And once more for the P-1 / P+1 stage-2 kernels (k_s2u_*_lane), for the same reason.
+template <int NL>
+struct LaneConstU : LaneConst<NL> {
+};
+
 template <int NL>
 __device__ __forceinline__ void lane_consts(LaneConst<NL> &k, const LaneGroups<NL> &g, uint32_t idx, uint32_t *kp_col)
 {
@@ -1033,6 +1038,94 @@ __global__ void __launch_bounds__(64, 2) k_s2_merge_lane(uint32_t *acc, uint32_t
 }
 #endif
 
+// ---------------------------------------------------------------- stage 2 of P-1 and P+1
+// The table and the giant steps of a method batch (gecm_stage2.hpp, s2u_*); the pair walk and the merge are the kernels
+// above.  The by-value kernels read their S2Const argument under the name S2ConstU.
+#define GECM_ARG_CONSTS_U const S2ConstU<NL> &k = *(const S2ConstU<NL> *)&kv;
+// P of every position into S (pm1 != 0: P-1, else P+1; wave-uniform), acc = one: one thread per position
+#define GECM_S2U_SEED_BODY                                                      \
+    s2u_seed<NL>(X, S, acc, fail, stride, pm1 != 0, k, blockIdx.x * 64u + threadIdx.x);
+// K sub-sequences per position, K >= 1: block b works on position block b / K, sub-sequence b % K
+#define GECM_S2U_INIT_BODY                                                      \
+    s2u_init<NL>(a, k, (blockIdx.x / a.K) * 64u + threadIdx.x, blockIdx.x % a.K);
+#define GECM_S2U_GEN_BODY                                                       \
+    s2u_gen<NL>(a, first_abs, n, k, (blockIdx.x / a.K) * 64u + threadIdx.x, blockIdx.x % a.K);
+
+template <int NL>
+__global__ void __launch_bounds__(64, 2) k_s2u_seed(const uint32_t *__restrict__ X, uint32_t *__restrict__ S,
+                                                    uint32_t *__restrict__ acc, uint32_t *__restrict__ fail, size_t stride,
+                                                    uint32_t pm1, S2Const<NL> kv)
+{
+    GECM_ARG_CONSTS_U
+    GECM_S2U_SEED_BODY
+}
+
+template <int NL>
+__global__ void __launch_bounds__(64, 2) k_s2u_seed_multi(const uint32_t *__restrict__ X, uint32_t *__restrict__ S,
+                                                          uint32_t *__restrict__ acc, uint32_t *__restrict__ fail,
+                                                          size_t stride, uint32_t pm1, ModGroups<NL> g)
+{
+    GECM_WAVE_CONSTS(S2ConstU<NL>, blockIdx.x)
+    GECM_S2U_SEED_BODY
+}
+
+template <int NL>
+__global__ void __launch_bounds__(64, 2) k_s2u_init(S2InitArgs a, S2Const<NL> kv)
+{
+    GECM_ARG_CONSTS_U
+    GECM_S2U_INIT_BODY
+}
+
+template <int NL>
+__global__ void __launch_bounds__(64, 2) k_s2u_init_multi(S2InitArgs a, ModGroups<NL> g)
+{
+    GECM_WAVE_CONSTS(S2ConstU<NL>, blockIdx.x / a.K)
+    GECM_S2U_INIT_BODY
+}
+
+template <int NL>
+__global__ void __launch_bounds__(64, 2) k_s2u_gen(S2PairArgs a, uint32_t first_abs, uint32_t n, S2Const<NL> kv)
+{
+    GECM_ARG_CONSTS_U
+    GECM_S2U_GEN_BODY
+}
+
+template <int NL>
+__global__ void __launch_bounds__(64, 2) k_s2u_gen_multi(S2PairArgs a, uint32_t first_abs, uint32_t n, ModGroups<NL> g)
+{
+    GECM_WAVE_CONSTS(S2ConstU<NL>, blockIdx.x / a.K)
+    GECM_S2U_GEN_BODY
+}
+
+#if GECM_HAS_LANE
+template <int NL>
+__global__ void __launch_bounds__(64, 2) k_s2u_seed_lane(const uint32_t *__restrict__ X, uint32_t *__restrict__ S,
+                                                         uint32_t *__restrict__ acc, uint32_t *__restrict__ fail,
+                                                         size_t stride, uint32_t pm1, LaneGroups<NL> g)
+{
+    GECM_LANE_CONSTS_AT(LaneConstU<NL>, blockIdx.x * 64u + threadIdx.x)
+    GECM_S2U_SEED_BODY
+}
+
+template <int NL>
+__global__ void __launch_bounds__(64, 2) k_s2u_init_lane(S2InitArgs a, LaneGroups<NL> g)
+{
+    GECM_LANE_CONSTS_AT(LaneConstU<NL>, (blockIdx.x / a.K) * 64u + threadIdx.x)
+    GECM_S2U_INIT_BODY
+}
+
+template <int NL>
+__global__ void __launch_bounds__(64, 2) k_s2u_gen_lane(S2PairArgs a, uint32_t first_abs, uint32_t n, LaneGroups<NL> g)
+{
+    GECM_LANE_CONSTS_AT(LaneConstU<NL>, (blockIdx.x / a.K) * 64u + threadIdx.x)
+    GECM_S2U_GEN_BODY
+}
+#endif
+#undef GECM_ARG_CONSTS_U
+#undef GECM_S2U_SEED_BODY
+#undef GECM_S2U_INIT_BODY
+#undef GECM_S2U_GEN_BODY
+
 #endif
 // ---------------------------------------------------------------- launchers (gecm_launch.h)
 // ModArgs, ModArgsS or S2Const from the host's record of the modulus constants
@@ -1314,9 +1407,53 @@ static void launch_s2_pair(void *stream, const gecm_modconst *mc, const gecm_s2_
                                            GECM_LANE(k_s2_merge_lane), a.acc, h->slices, a.stride, 0);
 }
 
+// stage 2 of a P-1 / P+1 batch: P into S, then the table with K >= 1 sub-sequences per position
+static void launch_s2_init_unit(void *stream, const gecm_modconst *mc, const gecm_s2_init_launch *h, int pm1)
+{
+    const S2InitArgs &a = h->a;
+    const dim3 grid = blocks_of(a.stride);
+    launch_by_source<S2Const<GECM_NL>>(stream, mc, grid, k_s2u_seed<GECM_NL>, k_s2u_seed_multi<GECM_NL>, GECM_LANE(k_s2u_seed_lane),
+                                       a.X, const_cast<uint32_t *>(a.S), a.acc, a.fail, a.stride, (uint32_t)(pm1 != 0));
+    launch_by_source<S2Const<GECM_NL>>(stream, mc, blocks_of(a.stride * a.K), k_s2u_init<GECM_NL>, k_s2u_init_multi<GECM_NL>,
+                                       GECM_LANE(k_s2u_init_lane), a);
+    if (h->slices > 1)
+        launch_by_source<S2Const<GECM_NL>>(stream, mc, grid, k_s2_merge<GECM_NL>, k_s2_merge_multi<GECM_NL>,
+                                           GECM_LANE(k_s2_merge_lane), a.acc, h->slices, a.stride, 1);
+}
+
+// The tape as launch_s2_pair walks it: k_s2u_gen at the marks, with the K of the batch at every one of them (bit 31 of
+// a mark's count, "one chain, one inversion", means nothing where nothing is inverted), the shared walk between them.
+static void launch_s2_pair_unit(void *stream, const gecm_modconst *mc, const gecm_s2_pair_launch *h)
+{
+    const S2PairArgs &a = h->a;
+    const dim3 grid = blocks_of(a.stride);
+    const dim3 pgrid((unsigned)(a.stride / 64), h->slices ? h->slices : 1);
+    const dim3 kgrid = blocks_of(a.stride * a.K);
+    uint32_t generated = 0, i = 0;
+    while (i < a.nsteps) {
+        if (h->host_steps[2 * i] == S2_STEP_GEN) {
+            const uint32_t n = h->host_steps[2 * i + 1] & 0x7fffffffu;
+            launch_by_source<S2Const<GECM_NL>>(stream, mc, kgrid, k_s2u_gen<GECM_NL>, k_s2u_gen_multi<GECM_NL>,
+                                               GECM_LANE(k_s2u_gen_lane), a, generated, n);
+            if (a.K > 1 && h->k_chunks) ++*h->k_chunks;
+            generated += n;
+            i++;
+        } else {
+            uint32_t j = i;
+            while (j < a.nsteps && h->host_steps[2 * j] != S2_STEP_GEN) j++;
+            launch_by_source<S2Const<GECM_NL>>(stream, mc, pgrid, k_s2_pairs<GECM_NL>, k_s2_pairs_multi<GECM_NL>,
+                                               GECM_LANE(k_s2_pairs_lane), a, i, j - i);
+            i = j;
+        }
+    }
+    if (h->slices > 1)
+        launch_by_source<S2Const<GECM_NL>>(stream, mc, grid, k_s2_merge<GECM_NL>, k_s2_merge_multi<GECM_NL>,
+                                           GECM_LANE(k_s2_merge_lane), a.acc, h->slices, a.stride, 0);
+}
+
 extern "C" const gecm_kernels_p2 *CAT(CAT(gecm_kernels_, GECM_NL), _p2)(void)
 {
-    static const gecm_kernels_p2 t = {launch_s2_init, launch_s2_pair, GECM_MANIFEST};
+    static const gecm_kernels_p2 t = {launch_s2_init, launch_s2_pair, GECM_MANIFEST, launch_s2_init_unit, launch_s2_pair_unit};
     return &t;
 }
 #endif

@@ -142,6 +142,14 @@ struct gecm_kernels_p2 {
     void (*s2_init)(void *stream, const gecm_modconst *mc, const gecm_s2_init_launch *h);
     void (*s2_pair)(void *stream, const gecm_modconst *mc, const gecm_s2_pair_launch *h);
     const char *manifest;
+    /* Stage 2 of a P-1 / P+1 batch, on the same arguments.  s2_init_unit: P = X (pm1 = 0) or X + 1/X
+     * (pm1 != 0; plane 0 of a.fail takes gcd(X, N) where there is no inverse) into a.S, acc = one, the table
+     * PbX[map[j]] = V_j(P), PdX = V_D(P) and for a.K > 1 PdKX = V_{K D}(P); bx/bz/bp, PdZ and PdKZ are not touched.
+     * s2_pair_unit: the tape as s2_pair walks it, the giant steps ring[s] = V_{(A0 / D + s) D}(P) at its marks (bit 31 of
+     * a mark ignored, a.K sub-sequences at every one), the pair walk and the merge of s2_pair between them.  New members
+     * go at the end. */
+    void (*s2_init_unit)(void *stream, const gecm_modconst *mc, const gecm_s2_init_launch *h, int pm1);
+    void (*s2_pair_unit)(void *stream, const gecm_modconst *mc, const gecm_s2_pair_launch *h);
 };
 
 /* the accessors: gecm_kernels_<nl>_p1 and _p2, one in each object */

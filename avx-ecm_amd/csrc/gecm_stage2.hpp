@@ -24,6 +24,7 @@
 #pragma once
 #include "gecm_curve.hpp"
 #include "gecm_launch.h"      // S2InitArgs, S2PairArgs
+#include <type_traits>
 
 #define S2_BLK 256
 
@@ -836,4 +837,178 @@ __device__ __forceinline__ void s2_merge(uint32_t *__restrict__ acc, uint32_t sl
         fe_canonical_mont(c, r, k.one, k.m);
         fe_store(acc, stride, idx, c);
     }
+}
+
+// ======================================================================================
+// Stage 2 of P-1 and P+1: the pair walk above on values of a Lucas sequence.
+//
+// x = the stage-1 residue of a position, P = x (P+1) or x + 1/x (P-1); then V_n(P) = x^n + x^-n, and V_a - V_u vanishes
+// modulo a prime p whenever a = +-u modulo the order stage 1 left, exactly as X_a/Z_a - X_u/Z_u does for a curve.  So the
+// table holds PbX[map[j]] = V_j(P), the ring holds V_{(2 amin + s) D}(P), and s2_pairs / s2_merge walk them unchanged.
+// There is nothing to normalise: V_{m+n} = V_m V_n - V_{m-n} is one multiply and one subtraction, no inversion.
+//
+// Operand bounds.  Every chain value is P (canonical), 2R mod N (canonical) or fe_sub_full(product, earlier value):
+// normalised limbs, below K.  That is a legal operand of the next multiply (< 1.675 K) and a legal subtrahend of the next
+// fe_sub_full, whose carry chains take any b < K.  It is NOT a legal subtrahend of the walk's fe_sub, which has no carry:
+// K' has K's top limb less one, so t = x + K' - y needs y's top limb below K's unless x's makes up for it, and a value
+// K - (something small) — every second one when N is short for its limb class, where K = N 2^k is mostly zero limbs —
+// has K's top limb itself: with a small x the top word of t is -1.  (A curve's table entry is a product, < 0.675 K.)  So
+// the TABLE entries are stored canonical (< N <= K / 2; one more multiply per kept j); the ring entries, the minuends,
+// stay as the chain leaves them: t = x + K' - y < 2 K with limbs in [0, 3 * 2^28), and acc * t / R + N
+// < 0.675 K * 2 K / R + N < 0.59 K.  tests/unit_s2_model.py restates this file's three bodies and one pair step with
+// these bounds asserted, at both ends of five limb classes.
+//
+// The types of the constants are the stage-2 ones under names of their own (as LaneConstK): the forceinline templates
+// these bodies share with the curve kernels (fe_inv_mont) then have instances of their own.
+template <int NL>
+struct S2ConstU : S2Const<NL> {
+};
+
+// (a, b) <- (V_n(Q), V_{n+1}(Q)) by the binary ladder on (V_k, V_{k+1}): V_{2k} = V_k^2 - 2, V_{2k+1} = V_k V_{k+1} - Q.
+// n is wave-uniform; Q and two = 2R mod N: normalised, below K.  MM = the modulus, or ModKOut (out-of-line multiplies).
+template <int NL, class MOD, class MM>
+__device__ __forceinline__ void lucas_ladder_body(Fe<NL> &a, Fe<NL> &b, const Fe<NL> &Q, const Fe<NL> &two, uint64_t n,
+                                                  const MOD &m, const MM &mm_)
+{
+    a = two;
+    b = Q;
+    if (n == 0) return;
+    for (int bit = 63 - __builtin_clzll(n); bit >= 0; bit--) {
+        uint32_t hi = (uint32_t)((n >> bit) & 1);
+        hi = __builtin_amdgcn_readfirstlane(hi);
+        Fe<NL> t, s;
+        fe_mul(t, a, b, mm_);
+        fe_sub_full(t, t, Q, m);                    // V_{2k+1}
+        s = hi ? b : a;
+        fe_sqr(s, s, mm_);
+        fe_sub_full(s, s, two, m);                  // V_{2k+2} or V_{2k}
+        if (hi) { a = t; b = s; }
+        else { a = s; b = t; }
+    }
+}
+template <int NL, class MOD>
+__device__ __forceinline__ void lucas_ladder(Fe<NL> &a, Fe<NL> &b, const Fe<NL> &Q, const Fe<NL> &two, uint64_t n, const MOD &m)
+{
+    if constexpr (NL >= GECM_LADDER_OL_NL && std::is_same<MOD, ModK<NL>>::value) lucas_ladder_body(a, b, Q, two, n, m, ModKOut<NL>{m});
+    else lucas_ladder_body(a, b, Q, two, n, m, m);
+}
+
+// k_s2u_seed: P of position idx into S, canonical Montgomery form, and acc = one.  P+1: P = X.  P-1: P = X + 1/X; where X
+// has no inverse the gcd goes to plane 0 of `fail`, as a failed batch inversion of a curve does, and P = X.
+template <int NL, class KC>
+__device__ __forceinline__ void s2u_seed(const uint32_t *__restrict__ X, uint32_t *__restrict__ S, uint32_t *__restrict__ acc,
+                                         uint32_t *__restrict__ fail, size_t stride, bool pm1, const KC &k, uint32_t idx)
+{
+    Fe<NL> x, p;
+    fe_load(x, X, stride, idx);
+    if (pm1) {
+        Fe<NL> inv;
+        fe_inv_mont(inv, x, k, fail, stride, idx);  // a product (or 0): normalised limbs, < 0.675 K
+        fe_add(x, x, inv);                          // < N + 0.675 K, limbs below 2^29
+    }
+    fe_canonical_mont(p, x, k.one, k.m);
+    fe_store(S, stride, idx, p);
+    fe_store(acc, stride, idx, k.one);
+}
+
+// k_s2u_init: the table.  Sub-sequence r of K (wave-uniform; K = 1: the plain chain) makes V_j for j = r, r + K, ...
+// (r = 0 starts at K) by V_{j+K} = V_j V_K - V_{j-K} and stores the kept ones: at table index 1, 2, 3, ... in the order
+// of j for K = 1 (the plan numbers the kept j that way), else at tgt[tgt_off[r] + i].  Its start values V_r, V_{K-r}
+// (= V_{r-K}) and V_K come from one plain chain of K - 1 steps.  Sub-sequence 0 also leaves V_D and, for K > 1, V_{K D}.
+template <int NL, class KC>
+__device__ __forceinline__ void s2u_init(const S2InitArgs &a, const KC &k, uint32_t idx, uint32_t r)
+{
+    const auto &m = k.m;
+    const size_t stride = a.stride;
+    const uint32_t K = a.K;
+    Fe<NL> P, two, VK, p1, p2, t;
+    fe_load(P, a.S, stride, idx);
+    unit_const(two, k.one, true, m);
+    {
+        Fe<NL> c0 = two, c1 = P;                    // V_{i-1}, V_i
+        p1 = P;
+        p2 = two;
+        for (uint32_t i = 1;; i++) {
+            if (i == r) p1 = c1;
+            if (i == K - r) p2 = c1;
+            if (i == K) break;
+            fe_mul(t, c1, P, m);
+            fe_sub_full(t, t, c0, m);
+            c0 = c1;
+            c1 = t;
+        }
+        VK = c1;
+        if (r == 0) { p1 = VK; p2 = two; }          // V_K and V_0
+    }
+    const uint32_t toff = K > 1 ? (uint32_t)__builtin_amdgcn_readfirstlane(a.tgt_off[r]) : 0u;
+    uint32_t cnt = 0;
+    for (uint32_t j = r ? r : K; j <= a.umax; j += K) {
+        uint32_t kb = (a.keep[j >> 5] >> (j & 31)) & 1u;
+        kb = __builtin_amdgcn_readfirstlane(kb);
+        if (kb) {
+            const uint32_t e = K > 1 ? (uint32_t)__builtin_amdgcn_readfirstlane(a.tgt[toff + cnt]) : cnt + 1;
+            Fe<NL> c;
+            fe_canonical_mont(c, p1, k.one, m);     // the walk's subtrahend: its top limb must stay below K's (see above)
+            tb_store(a.PbX, a.npb, idx, e, c);
+            cnt++;
+        }
+        fe_mul(t, p1, VK, m);
+        fe_sub_full(t, t, p2, m);
+        p2 = p1;
+        p1 = t;
+    }
+    if (r == 0) {
+        Fe<NL> vd, u;
+        lucas_ladder(vd, u, P, two, (uint64_t)a.D, m);
+        fe_store(a.PdX, stride, idx, vd);
+        if (K > 1) {
+            lucas_ladder(t, u, vd, two, (uint64_t)K, m);    // V_K(V_D(P)) = V_{K D}(P)
+            fe_store(a.PdKX, stride, idx, t);
+        }
+    }
+}
+
+// k_s2u_gen: giant steps [first_abs, first_abs + n): ring[s & mask] = W_s = V_{base + s}(V_D), base = 2 amin = A0 / D.
+// Sub-sequence r of K makes the steps s = r (mod K) by W_{s+K} = W_s V_{K D} - W_{s-K}.  Its first member and the one
+// before (W of a negative index is W of its absolute value) come from two ladders over V_D; afterwards the next member
+// and the latest one wait in entries 1 and 0 of the chunk scratch (gx for K = 1, else kgx of (block, r)).
+template <int NL, class KC>
+__device__ __forceinline__ void s2u_gen(const S2PairArgs &a, uint32_t first_abs, uint32_t n, const KC &k, uint32_t idx, uint32_t r)
+{
+    const auto &m = k.m;
+    const size_t stride = a.stride;
+    const uint32_t K = a.K;
+    const uint32_t s0 = first_abs + (r + K - first_abs % K) % K;            // first step of this sub-sequence in the chunk
+    if (s0 >= first_abs + n) return;                                        // wave-uniform
+    const uint32_t cnt = (first_abs + n - 1 - s0) / K + 1;
+    uint32_t *const cb = K > 1 ? a.kgx : a.gx;
+    const uint32_t nent = K > 1 ? a.Gs + 2 : a.G + 2;
+    const uint32_t v = K > 1 ? ((idx >> 6) * K + r) * 64u + (idx & 63u) : idx;
+    Fe<NL> step, p1, p2, t;
+    fe_load(step, K > 1 ? a.PdKX : a.PdX, stride, idx);
+    if (s0 < K) {                                                           // member 0 of the sub-sequence
+        Fe<NL> vd, two, u;
+        fe_load(vd, a.PdX, stride, idx);
+        unit_const(two, k.one, true, m);
+        const int64_t e1 = (int64_t)(a.A0 / a.D) + (int64_t)s0;
+        for (int w = 0; w < 2; w++) {
+            const int64_t e = e1 - (int64_t)w * (int64_t)K;
+            lucas_ladder(t, u, vd, two, (uint64_t)(e < 0 ? -e : e), m);
+            if (w == 0) p1 = t;
+            else p2 = t;
+        }
+    } else {
+        tb_load(p1, cb, nent, v, 1);
+        tb_load(p2, cb, nent, v, 0);
+    }
+    const uint32_t rmask = a.ring_size - 1;
+    for (uint32_t j = 0; j < cnt; j++) {
+        tb_store(a.ring, a.ring_size, idx, (s0 + j * K) & rmask, p1);
+        fe_mul(t, p1, step, m);
+        fe_sub_full(t, t, p2, m);
+        p2 = p1;
+        p1 = t;
+    }
+    tb_store(cb, nent, v, 1, p1);
+    tb_store(cb, nent, v, 0, p2);
 }

@@ -8,6 +8,7 @@
  *     avx-ecm -p PARAM input curves B1 [B2] [sigma]         (a fresh run in standard mode, PARAM 0, 1 or 3, run_param)
  *     avx-ecm -m pm1|pp1 input B1 [x0]                      (P-1 or P+1 stage 1 on one number, run_method)
  *     avx-ecm -m pm1|pp1 -f FILE B1,  avx-ecm -m pm1|pp1 -x FILE B1   (on a list of inputs; P-1 / P+1 lines on to B1)
+ *     avx-ecm -m pm1|pp1 -b B2 ...                          (any of the three, followed by stage 2 to B2)
  *
  * Same positional arguments as the reference (main.c:380-384, 459-460, 537-559) and the same FILES, byte for byte:
  * save_b1.txt (GMP-ECM resume lines, ecm.c:1372-1380), ecm_results.txt (factor lines, ecm.c:1356-1367, 1510-1522)
@@ -1677,13 +1678,17 @@ static int run_param(int argc, char **argv)
  * and (-x) when the next number's lines are complete to another bound or differ in whether they name their seed.  A pass
  * goes through the extension segments from its bound to B1 one by one: checkpoint.txt gets the standard lines after every
  * segment but the last, save_b1.txt those at B1, then the factor scan, and every factor one line in ecm_results.txt and on
- * stdout.  There is no stage 2: a B2 argument is refused.  -x groups and refuses as avx-ecm -x does: consecutive lines on
+ * stdout.  A trailing B2 argument is refused; `-b B2` right after the method (B2 > B1, else status 1 and nothing written)
+ * adds stage 2 to every pass: gecm_stage2(ctx, B2, 0, 0) on the pass's residues, GECM_MULTI_SUBSEQ honoured
+ * on multi-modulus passes as under -f, then the stage-2 scan, whose factor lines name both bounds; a position whose
+ * factor stage 1 reported is not reported again.  -x groups and refuses as avx-ecm -x does: consecutive lines on
  * one N are a group, the same N in two places is refused, so are lines of one N complete to different bounds, a bound
  * above B1, ECM lines and lines of the other method.  Everything is checked before anything runs or is written. */
 static const char *method_usage = "usage: avx-ecm -m pm1|pp1 $input $B1 [$x0]\n"
                                   "       avx-ecm -m pm1|pp1 -f $file $B1     (one input expression per line)\n"
                                   "       avx-ecm -m pm1|pp1 -x $file $B1     (P-1 / P+1 resume lines, taken on to $B1)\n"
-                                  "       (stage 1 only: there is no $B2)\n";
+                                  "       (stage 1 only: there is no $B2)\n"
+                                  "       avx-ecm -m pm1|pp1 -b $B2 ...       (any of the three, then stage 2 to $B2 > $B1)\n";
 
 typedef struct {
     char ndec[MPL_MAXL * 10 + 16];
@@ -1716,7 +1721,9 @@ static void append_lines(const char *file, gecm_ctx *c, size_t count)
 }
 
 /* one pass: the numbers nums[0 .. nn) and their residues res[0 .. nr) (res[r].num counts from nums[0]) */
-static int method_pass(int method, const mnum_t *nums, size_t nn, const mres_t *res, size_t nr, uint64_t B1, int packing)
+/* B2 != 0 (-b): after the stage-1 scan, gecm_stage2(c, B2, 0, 0) on the same residues and the stage-2 scan;
+ * a position whose factor stage 1 reported already is not reported again */
+static int method_pass(int method, const mnum_t *nums, size_t nn, const mres_t *res, size_t nr, uint64_t B1, uint64_t B2, int packing)
 {
     const char *mname = method == GECM_METHOD_PM1 ? "P-1" : "P+1";
     const uint64_t from = nums[0].from;
@@ -1780,6 +1787,44 @@ static int method_pass(int method, const mnum_t *nums, size_t nn, const mres_t *
         fputs(line, f);
         fclose(f);
     }
+    double ms2 = 0;
+    int found2 = 0;
+    if (!rc && B2) {
+        rc = gecm_set_method_stage2(c, GECM_METHOD_S2_ON);
+        if (!rc && nn > 1) rc = gecm_set_stage2_subseq(c, cli_multi_subseq());
+        const double t2 = now();
+        if (!rc) rc = gecm_stage2(c, B2, 0, 0);
+        ms2 = (now() - t2) * 1000.0;
+        if (!rc) {
+            found2 = gecm_scan_factors(c, 2, NULL);
+            if (found2 < 0) rc = found2;
+        }
+        if (rc) fprintf(stderr, "%s\n", gecm_last_error());
+    }
+    for (size_t r = 0; r < nr && !rc && found2 > 0; r++) {
+        static char fac[4096], seed[MPL_MAXL * 10 + 16], line[4096 + MPL_MAXL * 10 + 512];
+        int prp = 0;
+        if (!gecm_curve_flag(c, 2, r) || gecm_curve_flag(c, 1, r) || gecm_stage2_factor(c, r, fac, sizeof fac, &prp) != 1) continue;
+        if (gecm_curve_seed(c, r, seed, sizeof seed) > 0)
+            snprintf(line, sizeof line, "\nfound %s%d factor %s by %s (B1 = %lu, B2 = %lu): input %zu, x0 0x%s\n", prp ? "PRP" : "C",
+                     gecm_sizeinbase10(fac), fac, mname, (unsigned long)B1, (unsigned long)B2, nums[res[r].num].index, seed);
+        else
+            snprintf(line, sizeof line, "\nfound %s%d factor %s by %s (B1 = %lu, B2 = %lu): input %zu, x0 unknown\n", prp ? "PRP" : "C",
+                     gecm_sizeinbase10(fac), fac, mname, (unsigned long)B1, (unsigned long)B2, nums[res[r].num].index);
+        fputs(line, stdout);
+        FILE *f = fopen("ecm_results.txt", "a");
+        if (!f) { fprintf(stderr, "cannot write ecm_results.txt\n"); exit(2); }
+        fputs(line, f);
+        fclose(f);
+    }
+    if (!rc && B2) {
+        gecm_stage2_stats st;
+        uint32_t kch = 0;
+        const int K = gecm_get_stage2_subseq(c, &kch);
+        if (gecm_get_stage2_stats(c, &st) == GECM_OK)
+            printf("%s stage 2: B2 %lu, D %u, U %u, %lu pairs, %d sub-sequence%s, %1.4f seconds\n", mname, (unsigned long)B2, st.D, st.U,
+                   (unsigned long)st.paired, K, K == 1 ? "" : "s", ms2 / 1000.0);
+    }
     if (!rc) {
         char kn[128] = "";
         gecm_last_kernel_name(c, kn, sizeof kn);
@@ -1806,6 +1851,18 @@ static int run_method(int argc, char **argv)
     if (argc < 5) { printf("%s", method_usage); return 1; }
     const int method = !strcmp(argv[2], "pm1") ? GECM_METHOD_PM1 : !strcmp(argv[2], "pp1") ? GECM_METHOD_PP1 : 0;
     if (!method) { printf("-m %s: the methods offered are pm1 (P-1) and pp1 (P+1)\n%s", argv[2], method_usage); return 1; }
+    /* -b B2 after the method: taken out of the arguments, the rest is read as without it */
+    const char *b2s = NULL;
+    char *av[8];
+    if (!strcmp(argv[3], "-b")) {
+        if (argc < 7 || argc > 9) { printf("%s", method_usage); return 1; }
+        b2s = argv[4];
+        for (int i = 0; i < 3; i++) av[i] = argv[i];
+        for (int i = 5; i < argc; i++) av[i - 2] = argv[i];
+        argc -= 2;
+        av[argc] = NULL;
+        argv = av;
+    }
     const int from_file = !strcmp(argv[3], "-f"), from_lines = !strcmp(argv[3], "-x");
     const int listed = from_file || from_lines;
     if (listed ? argc != 6 : argc > 6) { printf("-m: stage 1 only: there is no stage 2, and no $B2 argument\n%s", method_usage); return 1; }
@@ -1814,8 +1871,15 @@ static int run_method(int argc, char **argv)
     const double b1d = strtod(b1s, &end);
     if (!*b1s || *end || !(b1d >= 2) || b1d > 1e12) { printf("-m: B1 must be in [2, 10^12]\n%s", method_usage); return 1; }
     const uint64_t B1 = (uint64_t)b1d;
+    uint64_t B2 = 0;
+    if (b2s) {
+        const double b2d = strtod(b2s, &end);
+        if (!*b2s || *end || !(b2d > b1d) || b2d > 1e15) { printf("-m -b: B2 must be above B1 (and at most 10^15)\n%s", method_usage); return 1; }
+        B2 = (uint64_t)b2d;
+        if (B2 <= B1) { printf("-m -b: B2 must be above B1 (and at most 10^15)\n%s", method_usage); return 1; }
+    }
     const int packing = cli_packing();
-    if (packing < 0) return 1;
+    if (packing < 0 || (B2 && cli_multi_subseq() == 1)) return 1;
     const double t_start = now();
     const size_t per = method == GECM_METHOD_PP1 ? 2 : 1;       /* fresh residues per number */
 
@@ -1987,7 +2051,7 @@ static int run_method(int argc, char **argv)
             n1++;
         }
         for (size_t r = r0; r < r1; r++) res[r].num -= n0;
-        rc = method_pass(method, nums + n0, n1 - n0, res + r0, r1 - r0, B1, pk);
+        rc = method_pass(method, nums + n0, n1 - n0, res + r0, r1 - r0, B1, B2, pk);
         n0 = n1;
         r0 = r1;
     }

@@ -153,6 +153,7 @@ struct gecm_ctx {
      * seed = the plain x0 of every position, [nl][batch] in device order, NULL when the caller did not know it */
     int method;
     uint32_t *seed;
+    int method_s2;           /* gecm_set_method_stage2: the stage-2 calls work on a method batch; kept across builds */
 };
 
 /* what a multi-modulus context cannot do: the reference radix (NWORDS) differs from modulus to modulus, and the L0
@@ -165,13 +166,30 @@ static int multi_refuse(const char *fn)
 
 static const char *method_name(int method) { return method == GECM_METHOD_PM1 ? "P-1" : method == GECM_METHOD_PP1 ? "P+1" : "ECM"; }
 
-/* what a P-1 / P+1 batch cannot do (include/gecm.h): 0 for a batch of curves */
-static int method_refuse(const gecm_ctx *c, const char *fn)
+/* what a P-1 / P+1 batch cannot do (include/gecm.h): 0 for a batch of curves.  stage2_call: fn is one of the stage-2
+ * calls, which gecm_set_method_stage2 lets through. */
+static int method_refuse(const gecm_ctx *c, const char *fn, int stage2_call)
 {
     if (!c || !c->method || c->batch == 0) return 0;
+    if (stage2_call && c->method_s2) return 0;
     set_err("%s: not available on a %s batch (gecm_build_seeds): it holds residues, not curves", fn, method_name(c->method));
     return GECM_ERR_STATE;
 }
+
+/* the device layer's name for the method of the batch */
+static int unit_method(const gecm_ctx *c) { return c->method == GECM_METHOD_PP1 ? GECM_UNIT_PP1 : GECM_UNIT_PM1; }
+
+int gecm_set_method_stage2(gecm_ctx *c, int on)
+{
+    if (!c || (on != GECM_METHOD_S2_OFF && on != GECM_METHOD_S2_ON)) {
+        set_err("gecm_set_method_stage2: needs a context and GECM_METHOD_S2_OFF or GECM_METHOD_S2_ON");
+        return GECM_ERR_ARG;
+    }
+    c->method_s2 = on;
+    return GECM_OK;
+}
+
+int gecm_get_method_stage2(const gecm_ctx *c) { return c ? c->method_s2 : GECM_METHOD_S2_OFF; }
 
 static int pick_nl(int nbits)
 {
@@ -1087,7 +1105,7 @@ int gecm_stage1_range(gecm_ctx *c, uint64_t B1, uint32_t range)
     const int settled = ff_settle(c);
     if (settled) return settled;
     if (!c || c->batch == 0) { set_err("gecm_stage1: no curves uploaded"); return GECM_ERR_STATE; }
-    if (method_refuse(c, "gecm_stage1")) return GECM_ERR_STATE;
+    if (method_refuse(c, "gecm_stage1", 0)) return GECM_ERR_STATE;
     if (B1 < 2 || B1 > GECM_B1_MAX) { set_err("gecm_stage1: B1 must be in [2, %llu]", (unsigned long long)GECM_B1_MAX); return GECM_ERR_ARG; }
     if (lane_packing_refuses(c)) return GECM_ERR_STATE;
     const uint32_t nranges = gecm_stage1_ranges_u(B1);
@@ -1258,7 +1276,7 @@ int gecm_download_points(gecm_ctx *c, void *X, void *Z)
 int gecm_download_s(gecm_ctx *c, void *s)
 {
     if (c && c->multi) return multi_refuse("gecm_download_s");
-    if (method_refuse(c, "gecm_download_s")) return GECM_ERR_STATE;
+    if (method_refuse(c, "gecm_download_s", 0)) return GECM_ERR_STATE;
     if (!c || !s || c->batch == 0) return GECM_ERR_ARG;
     const size_t batch = c->batch;
     uint32_t *h = (uint32_t *)malloc((size_t)c->mod.nl * batch * 4);
@@ -1331,7 +1349,7 @@ int gecm_format_resume_line(gecm_ctx *c, size_t k, uint64_t b1_label, char *buf,
     size_t pos;
     const gecm_mod *m = c && buf ? curve_at(c, k, &pos) : NULL;
     if (!m) return GECM_ERR_ARG;
-    if (method_refuse(c, "gecm_format_save_line")) return GECM_ERR_STATE;
+    if (method_refuse(c, "gecm_format_save_line", 0)) return GECM_ERR_STATE;
     int rc = fetch_plain(c);
     if (rc) return rc;
     static __thread char hn[MPL_MAXL * 10 + 2], hxs[MPL_MAXL * 10 + 2], hzs[MPL_MAXL * 10 + 2];
@@ -1383,7 +1401,7 @@ int gecm_normalize_points(gecm_ctx *c)
     const int settled = ff_settle(c);
     if (settled) return settled;
     if (!c || c->batch == 0) { set_err("gecm_normalize_points: no curves uploaded"); return GECM_ERR_STATE; }
-    if (method_refuse(c, "gecm_normalize_points")) return GECM_ERR_STATE;
+    if (method_refuse(c, "gecm_normalize_points", 0)) return GECM_ERR_STATE;
     if (!c->multi && c->mod.have_report) {
         set_err("gecm_normalize_points: not with a report modulus (gecm_set_report_modulus): x modulo the context's "
                 "modulus is not x modulo the number the lines name");
@@ -1476,7 +1494,7 @@ int gecm_stage2_init(gecm_ctx *c, uint32_t D, uint32_t U)
 {
     const int settled = ff_settle(c);
     if (settled) return settled;
-    if (method_refuse(c, "gecm_stage2_init")) return GECM_ERR_STATE;
+    if (method_refuse(c, "gecm_stage2_init", 1)) return GECM_ERR_STATE;
     if (!c || c->batch == 0 || c->B1 == 0) { set_err("gecm_stage2_init: run stage 1 first"); return GECM_ERR_STATE; }
     if (!D) D = gecm_s2_default_D(c->B1);
     if (!U) U = GECM_S2_DEFAULT_U;
@@ -1493,7 +1511,8 @@ int gecm_stage2_init(gecm_ctx *c, uint32_t D, uint32_t U)
     c->have_acc = 0;
     c->s2_ptadds = (uint64_t)c->s2.umax - 2 + ladder_adds(D);   /* ecm.c:2263: j = 3..U*w; Pd ladder :2334 */
     c->s2_numinv = 1;                                        /* ecm.c:2322 */
-    c->s2_devinv = (c->s2.npb - 1 + GECM_S2_BLK - 1) / GECM_S2_BLK;
+    /* a method batch normalises nothing: its only inversion is the seed's x^-1 of P-1 */
+    c->s2_devinv = c->method ? (c->method == GECM_METHOD_PM1) : (c->s2.npb - 1 + GECM_S2_BLK - 1) / GECM_S2_BLK;
     c->s2_paired = 0;
     /* small batches: K interleaved sub-sequences per curve (csrc/gecm_stage2.hpp, s2_init_k): the table indices of
      * the kept members of sub-sequence r, j = r, r+K, ... (r = 0: K, 2K, ...), in order */
@@ -1523,8 +1542,10 @@ int gecm_stage2_init(gecm_ctx *c, uint32_t D, uint32_t U)
         c->have_acc = 0;
     }
     c->s2_ready = 0;
-    int drc = gecm_dev_s2_init(c->dev, c->s2.keep, c->s2.keep_words, c->s2.umax, D, c->s2.npb, S2_GIANT_CHUNK, S2_RING, tgt,
-                               toff, K);
+    int drc = c->method ? gecm_dev_s2_init_unit(c->dev, unit_method(c), c->s2.keep, c->s2.keep_words, c->s2.umax, D, c->s2.npb,
+                                                S2_GIANT_CHUNK, S2_RING, tgt, toff, K)
+                        : gecm_dev_s2_init(c->dev, c->s2.keep, c->s2.keep_words, c->s2.umax, D, c->s2.npb, S2_GIANT_CHUNK,
+                                           S2_RING, tgt, toff, K);
     free(tgt);
     if (drc) {
         set_err("gecm_stage2_init: %s", gecm_dev_error());
@@ -1578,10 +1599,13 @@ static int s2_run_tape(gecm_ctx *c, const gecm_s2_tape *t, uint32_t amin, uint64
 {
     const gecm_s2_plan *p = &c->s2;
     const uint64_t A0 = (uint64_t)amin * p->D * 2;                       /* ecm.c:2378 */
-    int rc = gecm_dev_s2_pair(c->dev, t->words, (uint32_t)(t->nwords / 2), p->D, S2_GIANT_CHUNK, S2_RING, A0, tape_id);
+    int rc = c->method ? gecm_dev_s2_pair_unit(c->dev, unit_method(c), t->words, (uint32_t)(t->nwords / 2), p->D, S2_GIANT_CHUNK,
+                                               S2_RING, A0, tape_id)
+                       : gecm_dev_s2_pair(c->dev, t->words, (uint32_t)(t->nwords / 2), p->D, S2_GIANT_CHUNK, S2_RING, A0, tape_id);
     if (rc) { set_err("gecm_stage2_pair: %s", gecm_dev_error()); return GECM_ERR_DEVICE; }
     c->s2_ptadds += t->adds + ladder_adds(A0) + ladder_adds(A0 - p->D);  /* ecm.c:2383, 2390 */
-    c->s2_numinv += t->inv; c->s2_paired += t->paired; c->s2_devinv += t->devinv;
+    c->s2_numinv += t->inv; c->s2_paired += t->paired;
+    if (!c->method) c->s2_devinv += t->devinv;                           /* the giant steps of a method batch invert nothing */
     c->s2_amin_last = t->amin_last;
     c->have_acc = 0;
     c->scan_valid[1] = 0;
@@ -1639,7 +1663,7 @@ static int s2_tape_for(gecm_ctx *c, uint32_t steps, const uint32_t *pm_v, const 
 
 int gecm_stage2_pair(gecm_ctx *c, uint32_t steps, const uint32_t *pm_v, const uint32_t *pm_u, uint32_t amin)
 {
-    if (method_refuse(c, "gecm_stage2_pair")) return GECM_ERR_STATE;
+    if (method_refuse(c, "gecm_stage2_pair", 1)) return GECM_ERR_STATE;
     if (!c || !c->s2_ready) { set_err("gecm_stage2_pair: gecm_stage2_init has not run"); return GECM_ERR_STATE; }
     if (steps && (!pm_v || !pm_u)) return GECM_ERR_ARG;
     int rc = s2_tape_for(c, steps, pm_v, pm_u, amin);
@@ -1652,7 +1676,7 @@ int gecm_stage2_pair(gecm_ctx *c, uint32_t steps, const uint32_t *pm_v, const ui
 int gecm_stage2_pair_prepare(gecm_ctx *c, uint32_t D, uint32_t U, uint32_t steps, const uint32_t *pm_v, const uint32_t *pm_u,
                              uint32_t amin)
 {
-    if (method_refuse(c, "gecm_stage2_pair_prepare")) return GECM_ERR_STATE;
+    if (method_refuse(c, "gecm_stage2_pair_prepare", 1)) return GECM_ERR_STATE;
     if (!c || (steps && (!pm_v || !pm_u))) return GECM_ERR_ARG;
     if (!D || !U || U > (S2_RING - S2_GIANT_CHUNK) / 4) { set_err("gecm_stage2_pair_prepare: bad D/U"); return GECM_ERR_ARG; }
     if (c->s2.D != D || c->s2.U != U) {                                  /* the plan gecm_stage2_init(D, U) would make */
@@ -1682,7 +1706,7 @@ static int keep_pairmap(gecm_ctx *c, gecm_pairs *pm, uint64_t lo, uint64_t hi)
 int gecm_stage2_prepare(gecm_ctx *c, uint64_t B2, uint32_t D, uint32_t U)
 {
     const uint64_t PRIME_RANGE = 100000000ull;
-    if (method_refuse(c, "gecm_stage2_prepare")) return GECM_ERR_STATE;
+    if (method_refuse(c, "gecm_stage2_prepare", 1)) return GECM_ERR_STATE;
     if (!c || c->B1 == 0 || B2 <= c->B1) { set_err("gecm_stage2_prepare: call gecm_stage1 first; B2 > B1"); return GECM_ERR_ARG; }
     if (!D) D = gecm_s2_default_D(c->B1);
     if (!U) U = GECM_S2_DEFAULT_U;
@@ -1703,7 +1727,7 @@ int gecm_stage2_prepare(gecm_ctx *c, uint64_t B2, uint32_t D, uint32_t U)
 int gecm_stage2(gecm_ctx *c, uint64_t B2, uint32_t D, uint32_t U)
 {
     const uint64_t PRIME_RANGE = 100000000ull;                           /* main.c:581 */
-    if (method_refuse(c, "gecm_stage2")) return GECM_ERR_STATE;
+    if (method_refuse(c, "gecm_stage2", 1)) return GECM_ERR_STATE;
     if (!c || c->B1 == 0 || B2 <= c->B1) { set_err("gecm_stage2: need B2 > B1 and a finished stage 1"); return GECM_ERR_ARG; }
     int rc = gecm_stage2_init(c, D, U);
     if (rc) return rc;
@@ -1779,7 +1803,7 @@ int gecm_stage2_factor(gecm_ctx *c, size_t k, char *dec, size_t declen, int *is_
     size_t pos;
     const gecm_mod *m = c ? curve_at(c, k, &pos) : NULL;
     if (!m) return GECM_ERR_ARG;
-    if (method_refuse(c, "gecm_stage2_factor")) return GECM_ERR_STATE;
+    if (method_refuse(c, "gecm_stage2_factor", 1)) return GECM_ERR_STATE;
     int rc = fetch_acc(c);
     if (rc) return rc;
     mpl_t a, g;
@@ -1803,14 +1827,15 @@ int gecm_scan_factors(gecm_ctx *c, int stage, size_t *first)
     const int settled = ff_settle(c);
     if (settled) return settled;
     if (!c || c->batch == 0 || (stage != 1 && stage != 2)) { set_err("gecm_scan_factors: bad argument"); return GECM_ERR_ARG; }
-    if (stage == 2 && method_refuse(c, "gecm_scan_factors(stage 2)")) return GECM_ERR_STATE;
+    if (stage == 2 && method_refuse(c, "gecm_scan_factors(stage 2)", 1)) return GECM_ERR_STATE;
     if (stage == 2 && !c->s2_ready) { set_err("gecm_scan_factors: no stage-2 state"); return GECM_ERR_STATE; }
     uint32_t **f = &c->flags[stage - 1], **hg = &c->hg[stage - 1];
     if (!*f) *f = (uint32_t *)calloc(c->batch, sizeof(uint32_t));
     if (!*hg) *hg = (uint32_t *)calloc(c->batch * (size_t)c->mod.nl, sizeof(uint32_t));
     if (!*f || !*hg) return GECM_ERR_NOMEM;
-    if (c->method ? gecm_dev_gcd_scan_off(c->dev, c->method == GECM_METHOD_PP1 ? 2 : 1, *f, *hg)
-                  : gecm_dev_gcd_scan(c->dev, stage - 1, *f, *hg)) { set_err("gecm_scan_factors: %s", gecm_dev_error()); return GECM_ERR_DEVICE; }
+    /* stage 1 of a method batch tests x - 1 or x - 2; its stage-2 accumulator is scanned as any other */
+    if (c->method && stage == 1 ? gecm_dev_gcd_scan_off(c->dev, c->method == GECM_METHOD_PP1 ? 2 : 1, *f, *hg)
+                                : gecm_dev_gcd_scan(c->dev, stage - 1, *f, *hg)) { set_err("gecm_scan_factors: %s", gecm_dev_error()); return GECM_ERR_DEVICE; }
     /* stage 1: x, z come to the host with the scan: everything a caller does next (save lines, factors of the flagged
      * curves) is then host work, off the device's queue */
     int rc = stage == 1 ? fetch_plain(c) : fetch_acc(c);

@@ -207,6 +207,12 @@ _sig("gecm_resume_line_std_bound_method", c_int, c_char_p, ctypes.POINTER(c_u64)
 EXPORTS += ["gecm_build_seeds", "gecm_build_seeds_multi", "gecm_batch_method", "gecm_curve_seed",
             "gecm_parse_resume_line_method", "gecm_resume_line_std_bound_method"]
 
+# stage 2 of such batches: opt-in per context
+METHOD_S2_OFF, METHOD_S2_ON = 0, 1
+_sig("gecm_set_method_stage2", c_int, c_void_p, c_int)
+_sig("gecm_get_method_stage2", c_int, c_void_p)
+EXPORTS += ["gecm_set_method_stage2", "gecm_get_method_stage2"]
+
 
 class GecmError(RuntimeError):
     pass
@@ -496,6 +502,13 @@ class Engine:
     def batch_method(self):
         """METHOD_ECM, METHOD_PM1 or METHOD_PP1: what the batch in the context holds"""
         return lib.gecm_batch_method(self._h)
+
+    def set_method_stage2(self, on):
+        """let the stage-2 calls work on P-1 / P+1 batches of this context; holds across builds"""
+        return _chk(lib.gecm_set_method_stage2(self._h, METHOD_S2_ON if on else METHOD_S2_OFF), "gecm_set_method_stage2")
+
+    def method_stage2(self):
+        return bool(lib.gecm_get_method_stage2(self._h))
 
     def curve_seed(self, k):
         """x0 of position k of a P-1 / P+1 batch; None where the batch was built without seeds"""

@@ -528,7 +528,8 @@ int gecm_resume_line_std_bound_param(const char *line, uint64_t *from);
  *   with "X0=0x%s; " left out when the seed is unknown.  One lane per residue whatever gecm_set_lanes_per_curve says;
  *   gecm_get_lanes_per_curve answers 1 after such a launch.
  * GECM_ERR_STATE with a text naming the method: gecm_stage1, gecm_stage1_range, every gecm_stage2* call,
- *   gecm_normalize_points, gecm_download_s, gecm_format_save_line, gecm_format_resume_line, gecm_scan_factors(ctx, 2, ..).
+ *   gecm_normalize_points, gecm_download_s, gecm_format_save_line, gecm_format_resume_line, gecm_scan_factors(ctx, 2, ..)
+ *   (the stage-2 ones unless gecm_set_method_stage2 opted the context in, below).
  * Any of the build, upload or resume calls for curves makes the context an ECM context again.
  * gecm_batch_method: the method of the batch in the context; GECM_METHOD_ECM for every batch built for curves, and
  *   without a batch.
@@ -551,6 +552,36 @@ int gecm_batch_method(const gecm_ctx *ctx);
 int gecm_curve_seed(gecm_ctx *ctx, size_t k, char *hex, size_t hexlen);
 int gecm_parse_resume_line_method(const char *line, gecm_resume_rec *rec, int *param, int *method, gecm_resume_num *x0);
 int gecm_resume_line_std_bound_method(const char *line, uint64_t *from);
+
+/* ---- P-1 and P+1 stage 2: the pair walk on values of a Lucas sequence ----------
+ * With x the stage-1 residue of a position, let P = x for P+1 and P = x + 1/x mod N for P-1.  Then V_n(P) = x^n + x^-n
+ * (V_0 = 2, V_1 = P, V_{m+n} = V_m V_n - V_{m-n}, V_{-n} = V_n), and V_a - V_u = 0 modulo a prime p whenever a = +-u
+ * modulo the order stage 1 left: one stage 2 serves both methods and finds every p with p -+ 1 = (B1-smooth) * (one
+ * prime below B2).  For a pair map of wheel D and height U, walked in order with run_amin starting at amin and growing
+ * by U at every (0,0) entry, every other entry (v, u) contributes the factor
+ *     V_{(run_amin + v) D}(P) - V_u(P)  mod N,
+ * and the accumulator of a position is the product of those factors over every map given since gecm_stage2_init, as a
+ * plain residue; gecm_download_acc and gecm_curve_acc return it in the reference's Montgomery radix, as for curves.
+ * gecm_set_method_stage2(ctx, GECM_METHOD_S2_ON) opts a context in (GECM_ERR_ARG: another value, NULL ctx);
+ *   gecm_get_method_stage2 reads the setting (GECM_METHOD_S2_OFF for NULL).  It holds across builds and changes nothing
+ *   on a batch of curves.  Off, the default, every call answers what it answered before the setting existed.
+ * On, with a method batch whose stage 1 is complete to some B1, these work as on a batch of curves: gecm_stage2_init,
+ *   gecm_stage2_pair, gecm_stage2_pair_prepare, gecm_stage2_prepare, gecm_stage2, gecm_get_stage2_stats,
+ *   gecm_set_stage2_subseq / gecm_get_stage2_subseq, gecm_download_acc (single-N), gecm_curve_acc, gecm_stage2_factor,
+ *   gecm_scan_factors(ctx, 2, ..) (the plain scan of the accumulator) and gecm_curve_flag(ctx, 2, k).  The other
+ *   refusals of a method batch stay.
+ * Stage 2 leaves the residues alone (P goes to the batch's S array, which a method batch does not use): afterwards
+ *   gecm_format_save_line_std writes the same lines, gecm_stage1_extend goes on from the same residues, and another
+ *   stage 2 with other (D, U) starts clean.
+ * gecm_get_stage2_stats: D, U, L, amin_last, paired, ptadds, numinv are the plan's host-side counters, as for curves
+ *   (what the reference would count for a curve on the same maps); device_inversions is 1 for P-1 (x^-1) and 0 for P+1.
+ * P-1 where gcd(x, N) > 1: the position's failure record receives that gcd, as a failed batch inversion does for a curve:
+ *   gecm_stage2_factor reports it, gecm_scan_factors(ctx, 2, ..) flags the position, its accumulator is unspecified.
+ * gecm_batch_bytes counts a method batch as it counts curves: an upper bound (no block scratch is used). */
+#define GECM_METHOD_S2_OFF 0
+#define GECM_METHOD_S2_ON  1
+int gecm_set_method_stage2(gecm_ctx *ctx, int on);
+int gecm_get_method_stage2(const gecm_ctx *ctx);
 
 #ifdef __cplusplus
 }
