@@ -153,6 +153,17 @@ int gecm_dev_gcd_scan(gecm_dev *d, int which, uint32_t *flags, uint32_t *g);
 #define GECM_UNIT_PM1 1
 #define GECM_UNIT_PP1 2
 int gecm_dev_stage1_unit(gecm_dev *d, int method);
+/* ---- the same with a residue per 16-lane DPP row (csrc/gecm_row.hpp: k_unit_row) ----
+ * gecm_dev_set_unit_rowconst: the constant sets of the kernel, one per modulus (gecm_rowk.h: GECM_UROW_SET words each; a
+ * single-N context has one, a multi-modulus context one for every modulus gecm_dev_set_groups names, in that order), with
+ * nq limbs per lane and rows per multiply of the context's limb count (gecm_row_shape).  Host memory, copied before it
+ * returns.  gecm_dev_unit_rows_ready: are there sets for the moduli of the batch?
+ * gecm_dev_stage1_unit_lanes: lanes = 1 is gecm_dev_stage1_unit; lanes = 16 runs k_unit_row and canon per launch on any
+ * kind of context (-2 without constants), cut as the one-lane path cuts the tape; gecm_dev_last_lanes is then 16. */
+int gecm_dev_set_unit_rowconst(gecm_dev *d, int nq, int rows, uint32_t ngroups, const uint32_t *words);
+int gecm_dev_unit_rows_ready(gecm_dev *d);
+int gecm_dev_stage1_unit_lanes(gecm_dev *d, int method, int lanes);
+int gecm_dev_cus(gecm_dev *d);                 /* compute units of the device */
 int gecm_dev_gcd_scan_off(gecm_dev *d, uint32_t off, uint32_t *flags, uint32_t *g);
 /* ---- stage 2 of such a batch: gecm_dev_s2_init / gecm_dev_s2_pair with the method as first argument ----
  * The same allocations, slices and K; the table and the giant steps are values V_n(P) of the Lucas sequence of

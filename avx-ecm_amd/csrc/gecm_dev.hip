@@ -93,6 +93,10 @@ struct gecm_dev {
     uint32_t *dModQ = nullptr;   // N and K' limbs padded to 40 each, for the eight-lane kernel
     uint32_t *dRowC = nullptr;   // constants of the 32-lane kernel (gecm_dev_set_rowconst), GECM_ROW_KINDS x GECM_ROW_WORDS
     int row_nq = 0, row_rows = 0; // limbs per lane and rows of a multiply there; 0 = not available
+    uint32_t *dURowC = nullptr;  // constant sets of the 16-lane method kernel (gecm_dev_set_unit_rowconst), one per modulus
+    size_t urow_cap = 0;
+    uint32_t urow_groups = 0;     // sets dURowC holds; 0 = not available
+    int urow_nq = 0, urow_rows = 0;
     int fform = 0;        // +1 / -1 / 2: modulus is 2^k - 1 / 2^k + 1 / 2^k - c and stage 1 uses the special multiply (gecm_dev_set_fform)
     int cus = 0;          // compute units of the device (4 SIMDs each)
     int last_lanes = 0;   // lanes per curve the last stage-1 launch used
@@ -103,6 +107,7 @@ struct gecm_dev {
     uint32_t *dBlockGroup = nullptr;  // modulus of every 64-curve block of the batch
     size_t groups_cap = 0, blocks_cap = 0;
     bool have_groups = false;
+    uint32_t ngroups = 0;             // moduli of the batch (gecm_dev_set_groups)
     // lane packing (gecm_dev_set_groups with curve_group): one modulus per curve position instead of one per block
     uint32_t *dCurveGroup = nullptr;
     size_t curve_group_cap = 0;
@@ -250,6 +255,33 @@ extern "C" int gecm_dev_set_rowconst(gecm_dev *d, int nq, int rows, const uint32
     return 0;
 }
 
+extern "C" int gecm_dev_set_unit_rowconst(gecm_dev *d, int nq, int rows, uint32_t ngroups, const uint32_t *words)
+{
+    HIPCHK(hipSetDevice(d->device));
+    if (nq < 1 || nq > GECM_ROW_MAXNQ || 16 * nq > GECM_ROW_WORDS || rows <= 16 * (nq - 1) || rows > 16 * nq || !ngroups ||
+        !words) {
+        g_err = "gecm_dev_set_unit_rowconst: limbs per lane out of range, or no constants";
+        return -2;
+    }
+    d->urow_groups = 0;
+    if (grow(&d->dURowC, &d->urow_cap, (size_t)ngroups * GECM_UROW_SET)) return -1;
+    // synchronous: the host array may go away when this returns
+    HIPCHK(hipMemcpyAsync(d->dURowC, words, (size_t)ngroups * GECM_UROW_SET * sizeof(uint32_t), hipMemcpyHostToDevice,
+                          d->stream));
+    HIPCHK(hipStreamSynchronize(d->stream));
+    d->urow_nq = nq;
+    d->urow_rows = rows;
+    d->urow_groups = ngroups;
+    return 0;
+}
+
+extern "C" int gecm_dev_cus(gecm_dev *d) { return d->cus; }
+
+extern "C" int gecm_dev_unit_rows_ready(gecm_dev *d)
+{
+    return d->urow_groups != 0 && d->urow_groups == (d->multi ? d->ngroups : 1u);
+}
+
 static void free_state(gecm_dev *d)
 {
     (void)hipFree(d->dX); (void)hipFree(d->dZ); (void)hipFree(d->dS); (void)hipFree(d->dT0); (void)hipFree(d->dT1);
@@ -275,6 +307,7 @@ extern "C" void gecm_dev_close(gecm_dev *d)
     free_s2(d);
     (void)hipFree(d->dModQ);
     (void)hipFree(d->dRowC);
+    (void)hipFree(d->dURowC);
     (void)hipFree(d->dKeep);
     (void)hipFree(d->dSteps);
     (void)hipFree(d->dFlags);
@@ -697,7 +730,11 @@ extern "C" int gecm_dev_stage1(gecm_dev *d, int lanes_per_curve)
 
 /* P-1 / P+1 stage 1: the tape on one residue per lane, cut into launches as gecm_dev_stage1 cuts it
  * (between two prac() calls only A is live here too).  method: GECM_UNIT_PM1 or GECM_UNIT_PP1. */
-extern "C" int gecm_dev_stage1_unit(gecm_dev *d, int method)
+extern "C" int gecm_dev_stage1_unit(gecm_dev *d, int method) { return gecm_dev_stage1_unit_lanes(d, method, 1); }
+
+/* lanes = 1: one residue per lane (k_unit and its _multi / _lane forms).  lanes = 16: one residue per DPP row
+ * (k_unit_row), on every kind of context; it leaves lazy values, so canon follows every launch. */
+extern "C" int gecm_dev_stage1_unit_lanes(gecm_dev *d, int method, int lanes)
 {
     HIPCHK(hipSetDevice(d->device));
     if (ready(d, "gecm_dev_stage1_unit", false)) return -2;
@@ -709,13 +746,22 @@ extern "C" int gecm_dev_stage1_unit(gecm_dev *d, int method)
         g_err = "gecm_dev_stage1_unit: the method must be P-1 or P+1";
         return -2;
     }
+    if (lanes != 1 && lanes != 16) {
+        g_err = "gecm_dev_stage1_unit: lanes per residue must be 1 or 16";
+        return -2;
+    }
+    if (lanes == 16 && !gecm_dev_unit_rows_ready(d)) {
+        g_err = "gecm_dev_stage1_unit: the 16-lane kernel has no constants for this batch's moduli (gecm_dev_set_unit_rowconst)";
+        return -2;
+    }
     if (d->multi && d->lane_packed && !d->k1->has_lane) {
         g_err = "gecm_dev_stage1_unit: no per-lane kernels at this limb count";
         return -2;
     }
     char nm[96];
-    snprintf(nm, sizeof nm, "%s<%d>", !d->multi ? "k_unit" : d->lane_packed ? "k_unit_lane" : "k_unit_multi", d->nl);
-    d->last_lanes = 1;
+    if (lanes == 16) snprintf(nm, sizeof nm, "k_unit_row<%d, %d>", d->urow_nq, d->urow_rows);
+    else snprintf(nm, sizeof nm, "%s<%d>", !d->multi ? "k_unit" : d->lane_packed ? "k_unit_lane" : "k_unit_multi", d->nl);
+    d->last_lanes = lanes;
     d->last_kernel = nm;
     gecm_modconst mc = modconst(d);
     HIPCHK(hipEventRecord(d->ev0, d->stream));
@@ -728,7 +774,15 @@ extern "C" int gecm_dev_stage1_unit(gecm_dev *d, int method)
     for (size_t cut = 0; cut + 1 < d->tape_cuts.size(); cut++) {
         const uint32_t *tp = d->dTape + d->tape_cuts[cut] / 4;
         const uint32_t tl = (uint32_t)(d->tape_cuts[cut + 1] - d->tape_cuts[cut]);
-        d->k1->stage1_unit(d->stream, &mc, tp, tl, d->dX, d->dZ, d->stride, method == GECM_UNIT_PP1);
+        if (lanes == 16) {
+            if (gecm_launch_unit_row(d->stream, d->urow_nq, d->urow_rows, tp, tl, d->dX, d->stride, (uint32_t)d->nl,
+                                     method == GECM_UNIT_PP1, d->dURowC, mc.curve_group, mc.block_group)) {
+                g_err = "gecm_dev_stage1_unit: no 16-lane kernel for this limb count";
+                return -2;
+            }
+            d->k1->canon(d->stream, &mc, d->dX, d->dZ, d->stride);
+        } else
+            d->k1->stage1_unit(d->stream, &mc, tp, tl, d->dX, d->dZ, d->stride, method == GECM_UNIT_PP1);
         HIPCHK(hipEventRecord(d->cut_events[cut], d->stream));
     }
     HIPCHK(hipGetLastError());
@@ -875,6 +929,7 @@ extern "C" int gecm_dev_set_groups(gecm_dev *d, uint32_t ngroups, const gecm_dev
         HIPCHK(hipMemcpyAsync(d->dBlockGroup, block_group, blocks * sizeof(uint32_t), hipMemcpyHostToDevice, d->stream));
     HIPCHK(hipStreamSynchronize(d->stream));
     d->have_groups = true;
+    d->ngroups = ngroups;
     d->lane_packed = curve_group != nullptr;
     return 0;
 }

@@ -347,6 +347,17 @@ k_canon_multi(uint32_t *__restrict__ X, uint32_t *__restrict__ Z, size_t stride,
     GECM_WAVE_CONSTS(ModArgs<NL>, blockIdx.x)
     GECM_CANON_BODY
 }
+
+#if GECM_HAS_LANE
+// lane packing: after the 16-lane method kernel (gecm_rowk.hip, k_unit_row), the one lazy kernel that runs on it
+template <int NL>
+__global__ void __launch_bounds__(64)
+k_canon_lane(uint32_t *__restrict__ X, uint32_t *__restrict__ Z, size_t stride, LaneGroups<NL> g)
+{
+    GECM_LANE_CONSTS
+    GECM_CANON_BODY
+}
+#endif
 #undef GECM_CANON_BODY
 
 #define GECM_FROM_MONT_BODY                                                     \
@@ -1251,8 +1262,8 @@ static void launch_stage1(void *stream, const gecm_modconst *mc, const uint32_t 
 
 static void launch_canon(void *stream, const gecm_modconst *mc, uint32_t *X, uint32_t *Z, size_t stride)
 {
-    launch_by_source<ModArgs<GECM_NL>>(stream, mc, blocks_of(stride), k_canon<GECM_NL>, k_canon_multi<GECM_NL>, nullptr, X, Z,
-                                       stride);
+    launch_by_source<ModArgs<GECM_NL>>(stream, mc, blocks_of(stride), k_canon<GECM_NL>, k_canon_multi<GECM_NL>,
+                                       GECM_LANE(k_canon_lane), X, Z, stride);
 }
 
 static void launch_from_mont(void *stream, const gecm_modconst *mc, const uint32_t *X, const uint32_t *Z, uint32_t *ox,

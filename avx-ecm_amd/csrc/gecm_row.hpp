@@ -493,3 +493,181 @@ __device__ __forceinline__ void stage1_row(const uint32_t *__restrict__ tape, ui
         if (limb < nl) mine[(size_t)limb * stride + cidx] = (limb == nl - 1) ? v + (u[i] & ~GECM_LIMB_MASK) : v;
     }
 }
+
+// ======================================================================================
+// One residue per row: P-1 and P+1 stage 1 for small method batches.  Four residues per wavefront, the
+// limbs of each over the 16 lanes of its DPP row as above; the multiply is fer_mul as it stands (DPP form), the
+// interpreter is run_tape_unit of gecm_curve.hpp on FeR values: no X/Z exchange, no PtR forms.
+//   add T = X + Y, difference W:  P-1: X*Y       P+1: X*Y - W
+//   dup D = 2X:                   P-1: X^2       P+1: X^2 - 2
+// Limbs are signed and balanced, so the subtraction is limb-wise.  Its VALUE is not a product, though: with W an earlier
+// difference the bound would grow by a modulus per step, so every subtraction ends in a reduction (fer_reduce).  The
+// kernel works modulo M = N'' (gecm_rowk.h), whose limb ROWS - 1 is at least 2^20: the top limb of a value then gives
+// its quotient by M.
+
+// v <- v - q M with q = rint(top limb of v / (M / 2^(28 (ROWS - 1)))), then one balanced carry pass over the limbs below
+// the top one.  In: limbs |.| <= 2^28 + 8 below the top, |v| <= 2.1 M.  Out: limbs in [-2^27 - 3, 2^27 + 2] below the
+// top, |v| <= (1/2 + 2^-19) M: with B = 2^(28 (ROWS - 1)), v / B = top + d with |d| < 1.0001, so q differs from v / M by
+// at most 1/2 + 1.0001 B / M + the float roundings (three of 2^-24 relative on a quotient below 2.2), and B / M <= 2^-20.
+template <int NQ, int ROWS>
+__device__ __forceinline__ void fer_reduce(FeR<NQ> &v, const RowMod<NQ> &m, float minv, uint32_t l)
+{
+    constexpr int TL = (ROWS - 1) / NQ, TS = (ROWS - 1) % NQ;       // lane and slot of the top limb
+    const int32_t top = (int32_t)row_bcast<TL>((uint32_t)v.v[TS]);
+    const int32_t q = (int32_t)__builtin_rintf((float)top * minv);  // |q| <= 2
+    int32_t lo[NQ], c[NQ];
+#pragma unroll
+    for (int t = 0; t < NQ; t++) {
+        const int32_t x = v.v[t] - q * (int32_t)m.n[t];
+        const bool split = (uint32_t)NQ * l + (uint32_t)t < (uint32_t)(ROWS - 1);
+        c[t] = split ? (x + (1 << 27)) >> GECM_LIMB_BITS : 0;       // arithmetic shift: the balanced carry
+        lo[t] = x - (int32_t)((uint32_t)c[t] << GECM_LIMB_BITS);
+    }
+    v.v[0] = lo[0] + (int32_t)row_dpp<GECM_DPP_ROW_SHR1>((uint32_t)c[NQ - 1]);
+#pragma unroll
+    for (int t = 1; t < NQ; t++) v.v[t] = lo[t] + c[t - 1];
+}
+
+template <int NQ>
+struct UnitRow {
+    RowMod<NQ> m;      // M = N'', rho = 1
+    FeR<NQ> two;       // 2 R' mod M, balanced
+    float minv;        // 1 / (M / 2^(28 (ROWS - 1)))
+    uint32_t l;        // lane of the row
+    bool pp1;          // wave-uniform
+};
+
+// T = X*Y (- W)
+template <int NQ, int ROWS>
+__device__ __forceinline__ void unit_row_add(FeR<NQ> &T, const FeR<NQ> &X, const FeR<NQ> &Y, const FeR<NQ> &W,
+                                             const UnitRow<NQ> &u)
+{
+    fer_mul<NQ, ROWS, true, false>(T, X, Y, u.m);
+    if (u.pp1) {
+#pragma unroll
+        for (int t = 0; t < NQ; t++) T.v[t] -= W.v[t];
+        fer_reduce<NQ, ROWS>(T, u.m, u.minv, u.l);
+    }
+}
+
+// run_tape_unit (gecm_curve.hpp) on rows: the same control flow, the same renamings; A, B, C one FeR each.
+template <int NQ, int ROWS>
+__device__ __forceinline__ void run_tape_unit_row(const uint32_t *__restrict__ tape, uint32_t tape_len, FeR<NQ> &A,
+                                                  const UnitRow<NQ> &u)
+{
+    FeR<NQ> B = A, C = A;
+    auto fetch = [&](uint32_t pc) -> uint32_t {
+        uint32_t w = tape[pc >> 2];
+        return __builtin_amdgcn_readfirstlane((w >> ((pc & 3u) * 8u)) & 0xffu);
+    };
+    uint32_t nxt = tape_len ? fetch(0) : GECM_OP_NOP;
+    for (uint32_t pc = 0; pc < tape_len; pc++) {
+        uint32_t op = nxt;
+        nxt = (pc + 1 < tape_len) ? fetch(pc + 1) : GECM_OP_NOP;
+        // rule 3: T = B + A (C); (B,T,C) <- (T,C,B)
+        while ((op & ~GECM_OP_SWAP) == (GECM_OP_STEP | GECM_OP_RULE3)) {
+            if (op & GECM_OP_SWAP) {
+                FeR<NQ> t = A;
+                A = B;
+                B = t;
+            }
+            FeR<NQ> T;
+            unit_row_add<NQ, ROWS>(T, B, A, C, u);
+            C = B;
+            B = T;
+            pc++;
+            op = nxt;
+            nxt = (pc + 1 < tape_len) ? fetch(pc + 1) : GECM_OP_NOP;
+        }
+        if (op == GECM_OP_NOP) continue;
+        const uint32_t rule = op & GECM_OP_RULE_MASK;
+        const bool is_step = op >= GECM_OP_STEP;
+        const bool do_add = op != GECM_OP_PRAC_BEGIN;
+        const bool do_dup = op != GECM_OP_PRAC_END;
+        if (is_step && (op & GECM_OP_SWAP)) {
+            FeR<NQ> t = A;
+            A = B;
+            B = t;
+        }
+        if (is_step && rule == GECM_OP_RULE5) {
+            FeR<NQ> t = B;
+            B = C;
+            C = t;
+        } else if (is_step && rule == GECM_OP_RULE9) {
+            FeR<NQ> t = A;
+            A = B;
+            B = C;
+            C = t;
+        } else if (op == GECM_OP_PRAC_BEGIN) {
+            B = A;
+            C = A;
+        }
+        FeR<NQ> T, D;
+        if (do_add) unit_row_add<NQ, ROWS>(T, B, A, C, u);       // T = B + A, difference C
+        if (do_dup) unit_row_add<NQ, ROWS>(D, A, A, u.two, u);   // D = 2A
+        if (op == GECM_OP_PRAC_END) {
+            A = T;
+        } else if (op == GECM_OP_PRAC_BEGIN) {
+            A = D;
+        } else if (rule == GECM_OP_RULE4) {
+            B = T;
+            A = D;
+        } else if (rule == GECM_OP_RULE5) {
+            FeR<NQ> t = C;
+            C = T;
+            B = t;
+            A = D;
+        } else {
+            FeR<NQ> oldA = C;
+            C = T;
+            B = D;
+            A = oldA;
+        }
+    }
+}
+
+// The whole kernel body for one lane: position = global thread index >> 4, rc = the constant set of the position's
+// modulus (gecm_rowk.h).  nl = limbs per residue in the device buffers (R = 2^(28*nl)).
+template <int NQ, int ROWS>
+__device__ __forceinline__ void unit_row(const uint32_t *__restrict__ tape, uint32_t tape_len, uint32_t *__restrict__ X,
+                                         size_t stride, uint32_t nl, bool pp1, const uint32_t *__restrict__ rc)
+{
+    const uint32_t pos = (blockIdx.x * blockDim.x + threadIdx.x) >> 4;       // the rows of a wavefront are independent
+    const uint32_t l = threadIdx.x & 15u;
+    UnitRow<NQ> u;
+    RowMod<NQ> mn;
+    FeR<NQ> cin, one, kp;
+#pragma unroll
+    for (int t = 0; t < NQ; t++) {
+        const uint32_t j = (uint32_t)NQ * l + (uint32_t)t;
+        u.m.n[t] = rc[0 * GECM_ROW_WORDS + j];
+        mn.n[t] = rc[1 * GECM_ROW_WORDS + j];
+        cin.v[t] = (int32_t)rc[2 * GECM_ROW_WORDS + j];
+        one.v[t] = (int32_t)rc[3 * GECM_ROW_WORDS + j];
+        kp.v[t] = (int32_t)rc[4 * GECM_ROW_WORDS + j];
+        u.two.v[t] = (int32_t)rc[5 * GECM_ROW_WORDS + j];
+    }
+    u.minv = __uint_as_float(rc[6 * GECM_ROW_WORDS + 0]);
+    u.m.rho = 1u;
+    mn.rho = rc[6 * GECM_ROW_WORDS + 1];
+    u.m.c16 = mn.c16 = row_c16();
+    u.l = l;
+    u.pp1 = pp1;
+    FeR<NQ> A, t;
+    fer_load<NQ>(t, X, stride, pos, l, nl);
+    fer_mul<NQ, ROWS, true, false>(A, t, cin, u.m);              // x*R -> x*R' (mod M), |.| < 1.001 M
+    fer_reduce<NQ, ROWS>(A, u.m, u.minv, l);                     // |.| <= (1/2 + 2^-19) M
+    run_tape_unit_row<NQ, ROWS>(tape, tape_len, A, u);
+    fer_mul<NQ, ROWS, false, false>(t, A, one, mn);              // x*R' -> x*R (mod N), in (-N/16, 17N/16)
+    // + K', one carry-save pass: as stage1_row ends
+    uint32_t w[NQ];
+#pragma unroll
+    for (int i = 0; i < NQ; i++) w[i] = (uint32_t)(t.v[i] + kp.v[i]);
+    const uint32_t below = row_dpp<GECM_DPP_ROW_SHR1>(w[NQ - 1] >> GECM_LIMB_BITS);
+#pragma unroll
+    for (int i = 0; i < NQ; i++) {
+        const uint32_t limb = (uint32_t)NQ * l + (uint32_t)i;
+        const uint32_t v = (w[i] & GECM_LIMB_MASK) + (i == 0 ? below : (w[i - 1] >> GECM_LIMB_BITS));
+        if (limb < nl) X[(size_t)limb * stride + pos] = (limb == nl - 1) ? v + (w[i] & ~GECM_LIMB_MASK) : v;
+    }
+}

@@ -30,6 +30,22 @@ int gecm_launch_stage1_row(void *stream, int nq, int rows, const uint32_t *tape,
                            const uint32_t *S, size_t stride, uint32_t nl, const uint32_t *rc, uint32_t rho_n,
                            bool a_lds);
 
+/* 16 lanes per residue: P-1 and P+1 stage 1 with one residue per DPP row (k_unit_row).  The kernel works
+ * modulo N'' = (m + t 2^28) N, the multiple of N that is -1 modulo 2^28 AND fills the row: N'' >= 2^(28 (rows - 1) + 20),
+ * so that the top limb of a value tells its quotient by N'' (the reduction after a P+1 subtraction), and
+ * N'' < 2^(28 rows - 5) (1 + 2^-3) (t is the smallest that reaches the first bound): R' = 2^(28 rows) > 28 N''.
+ * rc = device table of one constant set per modulus, GECM_UROW_KINDS x GECM_ROW_WORDS words each, limb j at word j:
+ *   [0] N''   [1] N   [2] entry factor R'^2 / R mod N   [3] R mod N   [4] K' of N
+ *   [5] 2 R' mod N'', the residue nearest zero, in balanced limbs (|limb| <= 2^27 below the top one; two's complement)
+ *   [6] word 0: the float 1 / (N'' / 2^(28 (rows - 1))) as its bits; word 1: -N^-1 mod 2^28 (the exit multiply's rho)
+ * A position takes set curve_group[pos] (lane packing), block_group[pos / 64] (wave packing) or, with both NULL, set 0.
+ * Leaves a lazy value in X (run canon afterwards); Z is not touched.  Returns -1 if (nq, rows) is not built. */
+#define GECM_UROW_KINDS 7
+#define GECM_UROW_SET (GECM_UROW_KINDS * GECM_ROW_WORDS)
+#define GECM_UROW_TOP_MIN_BITS 20   /* limb rows - 1 of N'' is at least 2^20 */
+int gecm_launch_unit_row(void *stream, int nq, int rows, const uint32_t *tape, uint32_t tape_len, uint32_t *X, size_t stride,
+                         uint32_t nl, int pp1, const uint32_t *rc, const uint32_t *curve_group, const uint32_t *block_group);
+
 #ifdef __cplusplus
 }
 #endif

@@ -49,6 +49,36 @@ extern "C" int gecm_launch_stage1_row(void *stream, int nq, int rows, const uint
     return -1;
 }
 
+// One residue per row, four per wavefront: P-1 and P+1 stage 1 for small method batches (gecm_row.hpp, unit_row).
+// Workgroups of four wavefronts for the reason above.  The method is wave-uniform; the constants come from the table of
+// the batch's moduli through the position's group, which is uniform over a row (group 0 on a single-N context).
+template <int NQ, int ROWS>
+__global__ void __launch_bounds__(64 * GECM_ROW_WG_WAVES, 2)
+k_unit_row(const uint32_t *__restrict__ tape, uint32_t tape_len, uint32_t *__restrict__ X, size_t stride, uint32_t nl,
+           uint32_t pp1, const uint32_t *__restrict__ rc, const uint32_t *__restrict__ curve_group,
+           const uint32_t *__restrict__ block_group)
+{
+    const uint32_t pos = (blockIdx.x * blockDim.x + threadIdx.x) >> 4;       // < stride: the grid is stride / 16 blocks
+    const uint32_t g = curve_group ? curve_group[pos] : block_group ? block_group[pos >> 6] : 0u;
+    unit_row<NQ, ROWS>(tape, tape_len, X, stride, nl, pp1 != 0, rc + (size_t)g * GECM_UROW_SET);
+}
+
+extern "C" int gecm_launch_unit_row(void *stream, int nq, int rows, const uint32_t *tape, uint32_t tape_len, uint32_t *X,
+                                    size_t stride, uint32_t nl, int pp1, const uint32_t *rc, const uint32_t *curve_group,
+                                    const uint32_t *block_group)
+{
+    const dim3 grid((unsigned)(stride / (4 * GECM_ROW_WG_WAVES))), block(64 * GECM_ROW_WG_WAVES);   // stride: a multiple of 64
+#define GECM_UROW_LAUNCH(q, r)                                                                                              \
+    if (nq == q && rows == r) {                                                                                             \
+        hipLaunchKernelGGL((k_unit_row<q, r>), grid, block, 0, (hipStream_t)stream, tape, tape_len, X, stride, nl,          \
+                           (uint32_t)(pp1 != 0), rc, curve_group, block_group);                                             \
+        return 0;                                                                                                           \
+    }
+    GECM_ROW_SHAPES(GECM_UROW_LAUNCH)
+#undef GECM_UROW_LAUNCH
+    return -1;
+}
+
 // the hash of the sources this object was compiled from (Makefile: R_SHA)
 #ifndef GECM_MANIFEST
 #define GECM_MANIFEST "unset"

@@ -299,6 +299,19 @@ static int cli_multi_subseq(void)
     return 1;
 }
 
+/* Lanes per residue in stage 1 of the -m pm1|pp1 passes (include/gecm.h gecm_set_method_lanes):
+ * GECM_METHOD_LANES=1|16|auto, 1 when unset.  The files are byte for byte the same whatever the value.  Returns the
+ * setting, or 0 (no setting has that value) after printing why not. */
+static int cli_method_lanes(void)
+{
+    const char *s = getenv("GECM_METHOD_LANES");
+    if (!s || !strcmp(s, "1")) return 1;
+    if (!strcmp(s, "16")) return 16;
+    if (!strcmp(s, "auto")) return GECM_METHOD_LANES_AUTO;
+    printf("GECM_METHOD_LANES must be 1, 16 or auto\n");
+    return 0;
+}
+
 static int fits_lane_packing(int nbits) { return nbits <= gecm_multi_packing_max_bits(GECM_PACK_LANE); }
 
 /* ---- per-GPU jobs of a pass ----------------------------------------------------------------- */
@@ -1739,6 +1752,7 @@ static int method_pass(int method, const mnum_t *nums, size_t nn, const mres_t *
         free(ns);
         if (!rc) rc = gecm_set_multi_packing(c, packing);
     }
+    if (!rc) rc = gecm_set_method_lanes(c, cli_method_lanes());
     gecm_config cfg;
     if (!rc) rc = gecm_get_config(c, &cfg);
     void *x0 = NULL, *x = NULL;
@@ -1879,7 +1893,7 @@ static int run_method(int argc, char **argv)
         if (B2 <= B1) { printf("-m -b: B2 must be above B1 (and at most 10^15)\n%s", method_usage); return 1; }
     }
     const int packing = cli_packing();
-    if (packing < 0 || (B2 && cli_multi_subseq() == 1)) return 1;
+    if (packing < 0 || (B2 && cli_multi_subseq() == 1) || !cli_method_lanes()) return 1;
     const double t_start = now();
     const size_t per = method == GECM_METHOD_PP1 ? 2 : 1;       /* fresh residues per number */
 

@@ -154,6 +154,8 @@ struct gecm_ctx {
     int method;
     uint32_t *seed;
     int method_s2;           /* gecm_set_method_stage2: the stage-2 calls work on a method batch; kept across builds */
+    int method_lanes;        /* gecm_set_method_lanes: 0 (as 1), 1, 16 or GECM_METHOD_LANES_AUTO; kept across builds */
+    int urow_state;          /* the 16-lane method kernel's constants: 0 not made yet, 1 on the device, -1 none (unit_rows_setup) */
 };
 
 /* what a multi-modulus context cannot do: the reference radix (NWORDS) differs from modulus to modulus, and the L0
@@ -366,32 +368,157 @@ static int ff_settle(gecm_ctx *c)
 /* the device the last stage-1 launch ran on */
 static inline gecm_dev *last_dev(const gecm_ctx *c) { return c->twin.ran_last ? c->twin.dev : c->dev; }
 
-/* Constants of the 32-lanes-per-curve stage-1 kernel (csrc/gecm_row.hpp): it works modulo N' = m*N, the multiple
- * of N that is -1 modulo 2^28 (the Montgomery digit is then the low limb itself), on L limbs (nl + 1 rounded up
- * to whole lanes of nq limbs) with R' = 2^(28 L) >= 32 N'.  Entry factor R'^2/R mod N turns the buffers' x*R into x*R'; the exit multiply by R mod N
- * (modulo N itself) turns it back.  Not an error if it cannot be set up: the other layouts cover every N. */
+/* Constants of the row kernels (csrc/gecm_row.hpp) for one number, at the shape of a context of nl limbs: L limbs in
+ * use (nl + 1), R' = 2^(28 L).  Both kernels share the entry factor R'^2/R mod N, which turns the buffers' x*R into
+ * x*R', and the exit multiply by R mod N (modulo N itself), which turns it back, with K' of N.
+ *   w (GECM_ROW_KINDS x GECM_ROW_WORDS, or NULL): the 32-lanes-per-curve stage-1 kernel, which works modulo N' = m*N, the
+ *     multiple of N that is -1 modulo 2^28 (the Montgomery digit is then the low limb itself), with R' >= 32 N'.
+ *   u (GECM_UROW_SET words, or NULL): the 16-lanes-per-residue method kernel, which works modulo
+ *     N'' = (m + t 2^28) N with the smallest t >= 0 that makes N'' >= 2^(28 (L - 1) + GECM_UROW_TOP_MIN_BITS): still -1
+ *     modulo 2^28, below 2^(28 L - 5) (1 + 2^-3), and with a top limb that tells a value's quotient by N''; with it the
+ *     float reciprocal of N'' / 2^(28 (L - 1)), 2 R' mod N'' nearest zero in balanced limbs, and N's own rho.
+ * 1 if the constants asked for are made, 0 if this N has none (m->nl is not nl, or a bound does not hold). */
+static int row_consts(const gecm_mod *mod, int nl, int L, uint32_t *w, uint32_t *u)
+{
+    if (mod->nl != nl || L != nl + 1 || L < 3 || L > GECM_ROW_WORDS) return 0;
+    mpl_t two28, inv, m, np, cin;
+    mpl_set_u64(&two28, 1u << LIMB_BITS);
+    if (!mpl_invmod(&inv, &mod->N, &two28)) return 0;
+    mpl_sub(&m, &two28, &inv);                        /* m = -N^-1 mod 2^28, in [1, 2^28) */
+    mpl_mul(&np, &m, &mod->N);
+    gecm_mod_pow2(&cin, (unsigned)(2 * LIMB_BITS * L - LIMB_BITS * nl), &mod->N);
+    if (w) {
+        memset(w, 0, GECM_ROW_KINDS * GECM_ROW_WORDS * sizeof(uint32_t));
+        if (mpl_bits(&np) + 5 > LIMB_BITS * L) return 0;
+        mpl_to_limbs32(w + 0 * GECM_ROW_WORDS, 1, L, LIMB_BITS, &np);
+        if (w[0] != (1u << LIMB_BITS) - 1u) return 0;
+        memcpy(w + 1 * GECM_ROW_WORDS, mod->n28, (size_t)nl * sizeof(uint32_t));
+        mpl_to_limbs32(w + 2 * GECM_ROW_WORDS, 1, nl, LIMB_BITS, &cin);
+        memcpy(w + 3 * GECM_ROW_WORDS, mod->one28, (size_t)nl * sizeof(uint32_t));
+        memcpy(w + 4 * GECM_ROW_WORDS, mod->kp28, (size_t)nl * sizeof(uint32_t));
+    }
+    if (u) {
+        memset(u, 0, GECM_UROW_SET * sizeof(uint32_t));
+        mpl_t one, low, step, t, M, lim, v;
+        mpl_set_u64(&one, 1);
+        mpl_shl(&low, &one, (unsigned)(LIMB_BITS * (L - 1) + GECM_UROW_TOP_MIN_BITS));
+        M = np;
+        if (mpl_cmp(&M, &low) < 0) {                  /* t = ceil((low - m N) / (2^28 N)) */
+            mpl_shl(&step, &mod->N, LIMB_BITS);
+            mpl_sub(&t, &low, &M);
+            mpl_add(&t, &t, &step);
+            mpl_sub(&t, &t, &one);
+            mpl_divrem(&v, NULL, &t, &step);
+            mpl_mul(&t, &v, &step);
+            mpl_add(&M, &M, &t);
+        }
+        mpl_shl(&lim, &one, (unsigned)(LIMB_BITS * L - 5));
+        mpl_shr(&v, &lim, 3);
+        mpl_add(&lim, &lim, &v);
+        if (mpl_cmp(&M, &low) < 0 || mpl_cmp(&M, &lim) >= 0) return 0;
+        uint32_t *um = u + 0 * GECM_ROW_WORDS;
+        mpl_to_limbs32(um, 1, L, LIMB_BITS, &M);
+        if (um[0] != (1u << LIMB_BITS) - 1u) return 0;
+        memcpy(u + 1 * GECM_ROW_WORDS, mod->n28, (size_t)nl * sizeof(uint32_t));
+        mpl_to_limbs32(u + 2 * GECM_ROW_WORDS, 1, nl, LIMB_BITS, &cin);
+        memcpy(u + 3 * GECM_ROW_WORDS, mod->one28, (size_t)nl * sizeof(uint32_t));
+        memcpy(u + 4 * GECM_ROW_WORDS, mod->kp28, (size_t)nl * sizeof(uint32_t));
+        /* 2 R' mod N'', or that minus N'' if it is nearer zero, in balanced limbs: (-2^27, 2^27] below the top one */
+        gecm_mod_pow2(&v, (unsigned)(LIMB_BITS * L + 1), &M);
+        mpl_shl(&t, &v, 1);
+        const int neg = mpl_cmp(&t, &M) > 0;
+        if (neg) { mpl_sub(&t, &M, &v); v = t; }
+        uint32_t *two = u + 5 * GECM_ROW_WORDS;
+        mpl_to_limbs32(two, 1, L, LIMB_BITS, &v);
+        int32_t carry = 0;
+        for (int i = 0; i < L; i++) {
+            int32_t x = (int32_t)two[i] + carry;
+            carry = 0;
+            if (i < L - 1 && x > (1 << (LIMB_BITS - 1))) { x -= 1 << LIMB_BITS; carry = 1; }
+            two[i] = (uint32_t)(neg ? -x : x);
+        }
+        /* the reciprocal the reduction multiplies a top limb by: of N'' / 2^(28 (L - 1)) from its three top limbs */
+        const double scaled = (double)um[L - 1] + (double)um[L - 2] / 268435456.0 + (double)um[L - 3] / 72057594037927936.0;
+        const float rec = (float)(1.0 / scaled);
+        memcpy(u + 6 * GECM_ROW_WORDS, &rec, sizeof rec);
+        u[6 * GECM_ROW_WORDS + 1] = mod->rho28;
+    }
+    return 1;
+}
+
+/* The 32-lane stage-1 kernel's constants for the context's modulus.  Not an error if they cannot be set up: the other
+ * layouts cover every N. */
 static void row_setup(gecm_ctx *c)
 {
-    const int nl = c->mod.nl;
     int nq, L;                                        /* L = rows of a multiply = limbs in use: 28 (nl + 1) >= bits(N') + 5 */
-    gecm_row_shape(nl, &nq, &L);
+    gecm_row_shape(c->mod.nl, &nq, &L);
     if (nq > GECM_ROW_MAXNQ) return;
     uint32_t w[GECM_ROW_KINDS * GECM_ROW_WORDS];
-    memset(w, 0, sizeof w);
-    mpl_t two28, inv, m, np, t;
-    mpl_set_u64(&two28, 1u << LIMB_BITS);
-    if (!mpl_invmod(&inv, &c->mod.N, &two28)) return;
-    mpl_sub(&m, &two28, &inv);                        /* m = -N^-1 mod 2^28, in [1, 2^28) */
-    mpl_mul(&np, &m, &c->mod.N);
-    if (mpl_bits(&np) + 5 > LIMB_BITS * L) return;
-    mpl_to_limbs32(w + 0 * GECM_ROW_WORDS, 1, L, LIMB_BITS, &np);
-    if (w[0] != (1u << LIMB_BITS) - 1u) return;
-    memcpy(w + 1 * GECM_ROW_WORDS, c->mod.n28, (size_t)nl * sizeof(uint32_t));
-    gecm_mod_pow2(&t, (unsigned)(2 * LIMB_BITS * L - LIMB_BITS * nl), &c->mod.N);
-    mpl_to_limbs32(w + 2 * GECM_ROW_WORDS, 1, nl, LIMB_BITS, &t);
-    memcpy(w + 3 * GECM_ROW_WORDS, c->mod.one28, (size_t)nl * sizeof(uint32_t));
-    memcpy(w + 4 * GECM_ROW_WORDS, c->mod.kp28, (size_t)nl * sizeof(uint32_t));
-    (void)gecm_dev_set_rowconst(c->dev, nq, L, w);
+    if (row_consts(&c->mod, c->mod.nl, L, w, NULL)) (void)gecm_dev_set_rowconst(c->dev, nq, L, w);
+}
+
+/* The 16-lane method kernel's constant sets on the device: one for the context's modulus, or one for every modulus of
+ * a multi-modulus context, in the order gecm_dev_set_groups names them.  They depend on the context's numbers alone, so
+ * they are made once, when a launch first wants them.  1 if the device has them, 0 if they could not be set up. */
+static int unit_rows_setup(gecm_ctx *c)
+{
+    if (c->urow_state) return c->urow_state > 0;
+    c->urow_state = -1;
+    int nq, L;
+    gecm_row_shape(c->mod.nl, &nq, &L);
+    if (nq > GECM_ROW_MAXNQ) return 0;
+    const size_t ng = c->multi ? c->ngroups : 1;
+    uint32_t *u = (uint32_t *)calloc(ng * GECM_UROW_SET, sizeof(uint32_t));
+    if (!u) return 0;
+    int ok = 1;
+    for (size_t g = 0; g < ng && ok; g++)
+        ok = row_consts(c->multi ? &c->grp[g] : &c->mod, c->mod.nl, L, NULL, u + g * GECM_UROW_SET);
+    if (ok && !gecm_dev_set_unit_rowconst(c->dev, nq, L, (uint32_t)ng, u)) c->urow_state = 1;
+    free(u);
+    return c->urow_state > 0;
+}
+
+/* ---- lanes per residue of a method batch ---------------------------------------- */
+/* 16 up to 64 positions per compute unit (four wavefronts of four residues on every SIMD), 1 beyond: read off the table of
+ * DESIGN.md §22 (profiles/unit_row/time_rows.txt against time_parent_one_lane.txt, one MI355X of 256 compute units, tape
+ * (1, 1e5]).  Up to 16 positions per compute unit the row launch is at most one wavefront per SIMD and its time does not
+ * move with the batch: 83 ms against the one-lane kernel's 280 ms at 15 limbs, 205 ms against 1354 ms at 37.  At 64 per
+ * compute unit (16,384 positions) it still wins, 162 against 282 ms and 643 against 1364 ms; at 256 per compute unit
+ * (65,536) it has lost, 541 against 298 ms and 2445 against 1409 ms.  The crossover lies between the two at both limb
+ * counts and was not measured more finely, so the rule stops at the last size measured to win, for every limb count. */
+int gecm_method_lanes_auto(size_t positions, int dev_limbs, int cus)
+{
+    (void)dev_limbs;
+    if (positions == 0 || cus <= 0) return 1;
+    return positions <= (size_t)64 * (size_t)cus ? 16 : 1;
+}
+
+int gecm_set_method_lanes(gecm_ctx *c, int lanes)
+{
+    if (!c || (lanes != 1 && lanes != 16 && lanes != GECM_METHOD_LANES_AUTO)) {
+        set_err("gecm_set_method_lanes: needs a context and 1, 16 or GECM_METHOD_LANES_AUTO");
+        return GECM_ERR_ARG;
+    }
+    c->method_lanes = lanes;
+    return GECM_OK;
+}
+
+int gecm_get_method_lanes(const gecm_ctx *c) { return c && c->method_lanes ? c->method_lanes : 1; }
+
+/* the lanes the next launch on the method batch takes: 1 or 16, or 0 with the error text set (an explicit 16 without
+ * constants) */
+static int method_lanes_for_launch(gecm_ctx *c)
+{
+    const int set = gecm_get_method_lanes(c);
+    if (set == 1) return 1;
+    if (set == GECM_METHOD_LANES_AUTO &&
+        gecm_method_lanes_auto(gecm_dev_stride(c->dev), c->mod.nl, gecm_dev_cus(c->dev)) != 16)
+        return 1;
+    if (unit_rows_setup(c)) return 16;
+    if (set == GECM_METHOD_LANES_AUTO) return 1;
+    set_err("gecm_stage1_extend: the 16-lane method kernel has no constants for this context's numbers "
+            "(gecm_set_method_lanes)");
+    return 0;
 }
 
 int gecm_create(gecm_ctx **out, int device, const char *n_str, int digitbits)
@@ -1045,6 +1172,8 @@ static int lane_packing_refuses(const gecm_ctx *c)
  * nothing.  The caller has checked its arguments and settled a pending twin. */
 static int stage1_launch(gecm_ctx *c, const tape_key *key, uint64_t B1, int first, const tape_key *next)
 {
+    const int unit_lanes = c->method ? method_lanes_for_launch(c) : 1;
+    if (!unit_lanes) return GECM_ERR_STATE;          /* before anything of the batch has changed */
     int rc = tape_for(c, key);
     if (rc) return rc;
     const int idle = key->kind == 1 && c->tape.len == 0;
@@ -1065,9 +1194,9 @@ static int stage1_launch(gecm_ctx *c, const tape_key *key, uint64_t B1, int firs
     c->normalized = 0;
     c->scan_valid[0] = c->scan_valid[1] = 0;
     if (idle) return GECM_OK;
-    if (c->method) {                 /* one residue per lane, generic multiply: no layouts, no twin */
+    if (c->method) {                 /* one residue per lane or per row, generic multiply: no curve layouts, no twin */
         c->twin.ran_last = 0;
-        if (gecm_dev_stage1_unit(c->dev, c->method == GECM_METHOD_PP1 ? GECM_UNIT_PP1 : GECM_UNIT_PM1)) {
+        if (unit_lanes == 1 ? gecm_dev_stage1_unit(c->dev, unit_method(c)) : gecm_dev_stage1_unit_lanes(c->dev, unit_method(c), unit_lanes)) {
             set_err("%s", gecm_dev_error());
             return GECM_ERR_DEVICE;
         }

@@ -213,6 +213,18 @@ _sig("gecm_set_method_stage2", c_int, c_void_p, c_int)
 _sig("gecm_get_method_stage2", c_int, c_void_p)
 EXPORTS += ["gecm_set_method_stage2", "gecm_get_method_stage2"]
 
+# stage 1 of such batches with a residue per 16-lane DPP row: opt-in per context
+METHOD_LANES_AUTO = -1
+_sig("gecm_set_method_lanes", c_int, c_void_p, c_int)
+_sig("gecm_get_method_lanes", c_int, c_void_p)
+_sig("gecm_method_lanes_auto", c_int, c_size_t, c_int, c_int)
+EXPORTS += ["gecm_set_method_lanes", "gecm_get_method_lanes", "gecm_method_lanes_auto"]
+
+
+def method_lanes_auto(positions, limbs, cus):
+    """1 or 16: the lanes per residue "auto" gives a method batch of that many (padded) positions"""
+    return lib.gecm_method_lanes_auto(positions, limbs, cus)
+
 
 class GecmError(RuntimeError):
     pass
@@ -509,6 +521,15 @@ class Engine:
 
     def method_stage2(self):
         return bool(lib.gecm_get_method_stage2(self._h))
+
+    def set_method_lanes(self, lanes):
+        """lanes per residue of the P-1 / P+1 batches of this context in stage 1: 1 (the default), 16 or "auto"
+        (DESIGN.md §22); holds across builds, takes effect at the next stage1_extend"""
+        return _chk(lib.gecm_set_method_lanes(self._h, METHOD_LANES_AUTO if lanes == "auto" else lanes), "gecm_set_method_lanes")
+
+    def method_lanes(self):
+        v = lib.gecm_get_method_lanes(self._h)
+        return "auto" if v == METHOD_LANES_AUTO else v
 
     def curve_seed(self, k):
         """x0 of position k of a P-1 / P+1 batch; None where the batch was built without seeds"""

@@ -583,6 +583,30 @@ int gecm_resume_line_std_bound_method(const char *line, uint64_t *from);
 int gecm_set_method_stage2(gecm_ctx *ctx, int on);
 int gecm_get_method_stage2(const gecm_ctx *ctx);
 
+/* ---- P-1 and P+1 stage 1 with a residue per 16-lane DPP row, for small batches ----
+ * A method batch holds one residue per number, so its one-lane launch is a wavefront or two on a chip of a thousand
+ * SIMDs.  With 16 lanes per residue the limbs of a residue lie over the 16 lanes of a DPP row, four residues per
+ * wavefront, and a multiply is the row-wise one of the 32-lane curve layout (kernel k_unit_row<NQ, ROWS>).
+ * gecm_set_method_lanes(ctx, lanes): 1 (the default), 16 or GECM_METHOD_LANES_AUTO; GECM_ERR_ARG for another value or a
+ *   NULL context.  gecm_get_method_lanes reads the setting (1 for NULL).  It holds across builds, changes nothing on a
+ *   batch of curves (gecm_set_lanes_per_curve keeps having no say over method batches) and takes effect at the next
+ *   gecm_stage1_extend or gecm_stage1_extend_segment of a method batch.  With 1 every call answers what it answered
+ *   before the setting existed, kernel names and gecm_get_lanes_per_curve() == 1 included.
+ * With 16 those calls run k_unit_row, on single-N contexts and on multi-modulus contexts of both packings (lane packing
+ *   keeps its 415-bit limit on the context; the row kernel has none of its own): gecm_get_lanes_per_curve answers 16,
+ *   gecm_last_kernel_name "k_unit_row<..>".  Every residue is the integer the one-lane kernel gives; progress,
+ *   gecm_last_kernel_ms, stats, scan, factors, save lines, gecm_download_points_plain and stage 2 after it
+ *   (gecm_set_method_stage2) are unchanged in meaning.  If the kernel's constants cannot be set up for the context's
+ *   numbers the launch answers GECM_ERR_STATE with a text, and the batch is as it was.
+ * With GECM_METHOD_LANES_AUTO a launch takes gecm_method_lanes_auto(padded positions, device limbs, compute units), and
+ *   1 where 16 cannot be set up.
+ * gecm_method_lanes_auto: 1 or 16 for a batch of that many positions (padding included: gecm_multi_positions) on a
+ *   context of dev_limbs limbs and a device of cus compute units; pure host code, the one place the rule lives. */
+#define GECM_METHOD_LANES_AUTO (-1)
+int gecm_set_method_lanes(gecm_ctx *ctx, int lanes);   /* 1 (default), 16, GECM_METHOD_LANES_AUTO */
+int gecm_get_method_lanes(const gecm_ctx *ctx);
+int gecm_method_lanes_auto(size_t positions, int dev_limbs, int cus);   /* 1 or 16; pure host code */
+
 #ifdef __cplusplus
 }
 #endif
