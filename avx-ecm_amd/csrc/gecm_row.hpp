@@ -21,7 +21,10 @@
 //   * a multiply ends in the accumulators' own scale: T + 2^31 holds the balanced limb (+ 2^27) in bits 4..31 of its
 //     low register and the carry for the lane above AS its high register;
 //   * limbs are SIGNED and balanced ([-2^27, 2^27] after a multiply): subtraction is limb-wise without a bias,
-//     and the pre-multiplied operands stay inside 32 bits.
+//     and the pre-multiplied operands stay inside 32 bits;
+//   * between the entry and the exit conversion the tape interpreter keeps every value pre-multiplied (times 4): a
+//     multiply delivers its result in that scale in the instructions it spent on the plain one, sums and differences
+//     keep it, and no multiply of a point operation shifts an operand.
 // The residues are the same elements of Z/N as in every other layout (N | N'), so results are identical; the
 // kernel converts from and to the R = 2^(28*NL) Montgomery form of the device buffers at entry and exit
 // (R' = 2^(448*NQ) inside), and k_canon makes the exit values canonical.
@@ -121,7 +124,10 @@ __device__ __forceinline__ int64_t smad16_smad(int32_t x, int64_t add, int32_t y
 // Three forms: one limb per lane with the limbs of a broadcast by DPP row_newbcast (best up to 2 wavefronts per SIMD),
 // one limb per lane with ALDS: through the LDS crossbar (ds_swizzle: no VALU issue slot; best from 3 wavefronts per SIMD
 // up), and two or three limbs per lane, by DPP (best at every batch size: profiles/r03/mid_batch_rows.txt).
-template <int NQ, int ROWS, bool RHO1, bool ALDS>
+// A4, B4: the limbs of a, of b come multiplied by 4 already (the scale the rows read); R4: r is delivered times 4.  The
+// tape interpreter keeps every value in that scale, so that no multiply of a point operation shifts its operands: the
+// bounds above are those of the values, and 4 x (2^29 - 1) still fits the signed 32-bit operand of v_mad_i64_i32.
+template <int NQ, int ROWS, bool RHO1, bool ALDS, bool A4 = false, bool B4 = false, bool R4 = false>
 __device__ __forceinline__ void fer_mul(FeR<NQ> &r, const FeR<NQ> &a, const FeR<NQ> &b, const RowMod<NQ> &m)
 {
     static_assert(ROWS > 16 * (NQ - 1) && ROWS <= 16 * NQ, "the limbs in use fill the lanes but for the last one");
@@ -129,8 +135,8 @@ __device__ __forceinline__ void fer_mul(FeR<NQ> &r, const FeR<NQ> &a, const FeR<
     int32_t a4[NQ], b4[NQ];
 #pragma unroll
     for (int t = 0; t < NQ; t++) {
-        a4[t] = (int32_t)((uint32_t)a.v[t] << 2);
-        b4[t] = (int32_t)((uint32_t)b.v[t] << 2);
+        a4[t] = A4 ? a.v[t] : (int32_t)((uint32_t)a.v[t] << 2);
+        b4[t] = B4 ? b.v[t] : (int32_t)((uint32_t)b.v[t] << 2);
     }
     // The limbs of 4a reach the lanes of the row one per row of the multiply.  A DPP read of a register that a
     // VALU instruction has just written needs two independent instructions in between; a row has two such places
@@ -213,9 +219,9 @@ __device__ __forceinline__ void fer_mul(FeR<NQ> &r, const FeR<NQ> &a, const FeR<
         const int32_t ut = (int32_t)(T[(NQ - 1 + ROWS) % NQ] >> 4) + carry + (1 << 27);
         lo[NQ - 1] = (int32_t)((uint32_t)ut & GECM_LIMB_MASK) - (1 << 27);
         const int32_t below = (int32_t)row_dpp<GECM_DPP_ROW_SHR1>((uint32_t)(ut >> GECM_LIMB_BITS));
-        r.v[0] = lo[0] + below;
+        lo[0] += below;
 #pragma unroll
-        for (int t = 1; t < NQ; t++) r.v[t] = lo[t];
+        for (int t = 0; t < NQ; t++) r.v[t] = R4 ? (int32_t)((uint32_t)lo[t] << 2) : lo[t];
     } else {
         // One limb per lane.  DPP: the limbs travel TWO per move.  Every lane first takes the limb of the lane above
         // next to its own (one row_shl:1 per multiply); a 64-bit move (v_mov_b64_dpp, row_newbcast — the one control it
@@ -266,22 +272,31 @@ __device__ __forceinline__ void fer_mul(FeR<NQ> &r, const FeR<NQ> &a, const FeR<
         // bits 4..31 of its low register and what leaves the lane AS its high register; the neighbour's carry comes in
         // on the add itself (DPP)
         const int64_t u16 = T[0] + (int64_t)(1u << 31);
-        const int32_t lim = (int32_t)(((uint32_t)u16 >> 4) & GECM_LIMB_MASK) - (1 << 27);
-        r.v[0] = lim + (int32_t)row_dpp<GECM_DPP_ROW_SHR1>((uint32_t)(u16 >> 32));
+        if constexpr (R4) {
+            // times 4 in the same instructions: every accumulator is a multiple of 16 (4a x 4b, 16 x digit, 16 x high
+            // part), so its low register READ AS SIGNED is 16 x the balanced limb and an arithmetic shift by 2 leaves
+            // 4 x limb; the neighbour's carry enters shifted on the add (v_lshl_add_u32)
+            const int32_t lim4 = (int32_t)(uint32_t)T[0] >> 2;
+            r.v[0] = lim4 + (int32_t)(row_dpp<GECM_DPP_ROW_SHR1>((uint32_t)(u16 >> 32)) << 2);
+        } else {
+            const int32_t lim = (int32_t)(((uint32_t)u16 >> 4) & GECM_LIMB_MASK) - (1 << 27);
+            r.v[0] = lim + (int32_t)row_dpp<GECM_DPP_ROW_SHR1>((uint32_t)(u16 >> 32));
+        }
     }
 }
 
-// A point coordinate as the tape interpreter keeps it: its own limbs and the three combinations with the other
-// coordinate that the point formulas read (ecm.c:407-457 split into X and Z halves as in gecm_quad.hpp), all made
-// ONCE when the point is created, from one exchange between the X row and the Z row.  The exchange goes through
-// the LDS crossbar (ds_swizzle, lane ^ 16): no VALU issue slot, which is what a batch at 2 wavefronts per SIMD is
-// short of (v_permlane16_swap, measured: 7% slower at 4096 curves).
+// A point coordinate as the tape interpreter keeps it: its own limbs and those of the other coordinate, both TIMES 4 (the
+// scale the rows of a multiply read: fer_mul, A4 / B4 / R4), from one exchange between the X row and the Z row when the
+// point is made.  The exchange goes through the LDS crossbar (ds_swizzle, lane ^ 16): no VALU issue slot, which is what
+// a batch at 2 wavefronts per SIMD is short of (v_permlane16_swap, measured: 7% slower at 4096 curves).
+// The sum and the difference that the point formulas read (ecm.c:407-457 split into X and Z halves as in gecm_quad.hpp)
+// are made where a formula reads them (row_sd, row_ds), not kept: a point addition reads ONE of them of each of two
+// points, which costs the four instructions that making both of the new point would, and the renaming of a PRAC step
+// moves two registers per point instead of four.
 template <int NQ>
 struct PtR {
-    FeR<NQ> own;   // X rows: X        Z rows: Z
-    FeR<NQ> sd;    // X rows: Z + X    Z rows: X - Z      (the operand this point gives as "A")
-    FeR<NQ> ds;    // X rows: X - Z    Z rows: Z + X      (as "B")
-    FeR<NQ> oth;   // X rows: Z        Z rows: X          (as the difference point "C")
+    FeR<NQ> own;   // X rows: 4X       Z rows: 4Z
+    FeR<NQ> oth;   // X rows: 4Z       Z rows: 4X         (the operand this point gives as the difference point "C")
 };
 
 struct RowSign {
@@ -304,51 +319,71 @@ __device__ __forceinline__ void fer_sum_diff(FeR<NQ> &r, const FeR<NQ> &oth, con
     for (int t = 0; t < NQ; t++) r.v[t] = (int32_t)((uint32_t)oth.v[t] + ((uint32_t)own.v[t] ^ g.mz) + g.bz);
 }
 
+// the operand a point gives as "A": 4(Z + X) on X rows, 4(X - Z) on Z rows
 template <int NQ>
-__device__ __forceinline__ void row_forms(PtR<NQ> &p, const RowSign &g)
+__device__ __forceinline__ void row_sd(FeR<NQ> &r, const PtR<NQ> &p, const RowSign &g)
 {
-    fer_other<NQ>(p.oth, p.own);
-    fer_sum_diff<NQ>(p.sd, p.oth, p.own, g);
-#pragma unroll
-    for (int t = 0; t < NQ; t++)                  // own - oth on X rows, own + oth on Z rows
-        p.ds.v[t] = (int32_t)((uint32_t)p.own.v[t] + ((uint32_t)p.oth.v[t] ^ g.mx) + g.bx);
+    fer_sum_diff<NQ>(r, p.oth, p.own, g);
 }
 
-// T = A + B with difference C (vec_add, ecm.c:407-443): fB = B.ds, fA = A.sd, c = C.oth
+// the operand a point gives as "B": 4(X - Z) on X rows, 4(Z + X) on Z rows
+template <int NQ>
+__device__ __forceinline__ void row_ds(FeR<NQ> &r, const PtR<NQ> &p, const RowSign &g)
+{
+#pragma unroll
+    for (int t = 0; t < NQ; t++) r.v[t] = (int32_t)((uint32_t)p.own.v[t] + ((uint32_t)p.oth.v[t] ^ g.mx) + g.bx);
+}
+
+// r <- pick ? b : a (pick: all ones or zero, wave-uniform, in a scalar register pair) as an instruction of its own, where
+// it is written: the renaming of a rule-3 step (run_tape_row) frees a register BEFORE the new point is made, so that the
+// new point is made in it, and does so without a branch.  Left to the compiler, the renaming is a branch with copies on
+// both sides at the end of the step, and the new point is copied once more.
+template <int NQ>
+__device__ __forceinline__ void row_pick(FeR<NQ> &r, const FeR<NQ> &a, const FeR<NQ> &b, uint64_t pick)
+{
+#pragma unroll
+    for (int t = 0; t < NQ; t++) {
+        int32_t x;
+        asm volatile("v_cndmask_b32 %0, %1, %2, %3" : "=v"(x) : "v"(a.v[t]), "v"(b.v[t]), "s"(pick));
+        r.v[t] = x;
+    }
+}
+
+// own coordinate of T = A + B with difference C (vec_add, ecm.c:407-443): fB = row_ds(B), fA = row_sd(A), c = C.oth;
+// every value times 4.  With A and B exchanged the result is the same residue: the X rows then make V and the Z rows U,
+// U - V changes sign and the square removes it.  The swap of a rule-3 step is therefore only a renaming (run_tape_row).
 template <int NQ, int ROWS, bool ALDS>
-__device__ __forceinline__ void row_add(PtR<NQ> &T, const FeR<NQ> &fB, const FeR<NQ> &fA, const FeR<NQ> &c, bool isZ,
+__device__ __forceinline__ void row_add(FeR<NQ> &own, const FeR<NQ> &fB, const FeR<NQ> &fA, const FeR<NQ> &c, bool isZ,
                                         const RowSign &g, const RowMod<NQ> &m)
 {
     FeR<NQ> w, t, e;
-    fer_mul<NQ, ROWS, true, ALDS>(w, fB, fA, m);            // X: U      Z: V
+    fer_mul<NQ, ROWS, true, ALDS, true, true, true>(w, fB, fA, m);      // X: U      Z: V
     fer_other<NQ>(t, w);
-    fer_sum_diff<NQ>(e, t, w, g);                     // X: V + U  Z: U - V
-    fer_mul<NQ, ROWS, true, ALDS>(e, e, e, m);
-    fer_mul<NQ, ROWS, true, ALDS>(T.own, e, c, m);
-    row_forms<NQ>(T, g);
+    fer_sum_diff<NQ>(e, t, w, g);                                       // X: V + U  Z: U - V
+    fer_mul<NQ, ROWS, true, ALDS, true, true, true>(e, e, e, m);
+    fer_mul<NQ, ROWS, true, ALDS, true, true, true>(own, e, c, m);
 }
 
-// D = 2A (vec_duplicate, ecm.c:445-457): fA = A.sd, s4 = (A+2)/4 of the curve
+// own coordinate of D = 2A (vec_duplicate, ecm.c:445-457): fA = row_sd(A), s4 = (A+2)/4 of the curve; every value times 4
 template <int NQ, int ROWS, bool ALDS>
-__device__ __forceinline__ void row_dup(PtR<NQ> &D, const FeR<NQ> &fA, const FeR<NQ> &s4, bool isZ, const RowSign &g,
+__device__ __forceinline__ void row_dup(FeR<NQ> &own, const FeR<NQ> &fA, const FeR<NQ> &s4, bool isZ, const RowSign &g,
                                         const RowMod<NQ> &m)
 {
     FeR<NQ> q, t, w, p1, p2, r1;
-    fer_mul<NQ, ROWS, true, ALDS>(q, fA, fA, m);            // X: U = (x+z)^2    Z: V = (x-z)^2
-    fer_other<NQ>(t, q);                              // X: V              Z: U
+    fer_mul<NQ, ROWS, true, ALDS, true, true, true>(q, fA, fA, m);      // X: U = (x+z)^2    Z: V = (x-z)^2
+    fer_other<NQ>(t, q);                                                // X: V              Z: U
 #pragma unroll
     for (int i = 0; i < NQ; i++) {
         w.v[i] = t.v[i] - q.v[i];                     // Z: w = U - V
         p1.v[i] = isZ ? s4.v[i] : q.v[i];
         p2.v[i] = isZ ? w.v[i] : t.v[i];
     }
-    fer_mul<NQ, ROWS, true, ALDS>(r1, p1, p2, m);           // X: U*V            Z: s*w
+    fer_mul<NQ, ROWS, true, ALDS, true, true, true>(r1, p1, p2, m);     // X: U*V            Z: s*w
 #pragma unroll
     for (int i = 0; i < NQ; i++) t.v[i] = r1.v[i] + q.v[i];     // Z: s*w + V
-    fer_mul<NQ, ROWS, true, ALDS>(t, t, w, m);              // Z: (s*w + V)*w
+    fer_mul<NQ, ROWS, true, ALDS, true, true, true>(t, t, w, m);        // Z: (s*w + V)*w
 #pragma unroll
-    for (int i = 0; i < NQ; i++) D.own.v[i] = isZ ? t.v[i] : r1.v[i];
-    row_forms<NQ>(D, g);
+    for (int i = 0; i < NQ; i++) own.v[i] = isZ ? t.v[i] : r1.v[i];
 }
 
 template <int NQ>
@@ -367,7 +402,10 @@ template <int NQ, int ROWS, bool ALDS>
 __device__ __forceinline__ void run_tape_row(const uint32_t *__restrict__ tape, uint32_t tape_len, PtR<NQ> &A,
                                              const FeR<NQ> &s4, bool isZ, const RowSign &g, const RowMod<NQ> &m)
 {
-    PtR<NQ> B = A, C = A;
+    // Of C only the other coordinate is kept between steps: that is what C gives to an addition, and its own one is the
+    // other row's (one more exchange, made in the steps that turn C into A or B: rules 5 and 9).
+    PtR<NQ> B = A;
+    FeR<NQ> Coth = A.oth;
     auto fetch = [&](uint32_t pc) -> uint32_t {
         uint32_t w = tape[pc >> 2];
         return __builtin_amdgcn_readfirstlane((w >> ((pc & 3u) * 8u)) & 0xffu);
@@ -376,16 +414,20 @@ __device__ __forceinline__ void run_tape_row(const uint32_t *__restrict__ tape, 
     for (uint32_t pc = 0; pc < tape_len; pc++) {
         uint32_t op = nxt;
         nxt = (pc + 1 < tape_len) ? fetch(pc + 1) : GECM_OP_NOP;
+        // rule 3: T = A + B (C); (A, B, C) <- (A, T, B), after a swap (B, T, A): the sum does not depend on the order of A
+        // and B (row_add), so the swap only says which of the two stays A and which becomes C.  Three conditional moves:
+        // what stays A is chosen before the addition (B's own register is then free), what becomes C behind the last
+        // multiply, which reads the old C, and the new point is made in B's registers.
         while ((op & ~GECM_OP_SWAP) == (GECM_OP_STEP | GECM_OP_RULE3)) {
-            if (op & GECM_OP_SWAP) {
-                PtR<NQ> t = A;
-                A = B;
-                B = t;
-            }
-            PtR<NQ> T;
-            row_add<NQ, ROWS, ALDS>(T, B.ds, A.sd, C.oth, isZ, g, m);
-            C = B;
-            B = T;
+            const uint64_t swap = (op & GECM_OP_SWAP) ? ~(uint64_t)0 : 0;
+            FeR<NQ> fA, fB;
+            row_sd<NQ>(fA, A, g);
+            row_ds<NQ>(fB, B, g);
+            row_pick<NQ>(A.own, A.own, B.own, swap);
+            row_add<NQ, ROWS, ALDS>(B.own, fB, fA, Coth, isZ, g, m);
+            row_pick<NQ>(Coth, B.oth, A.oth, swap);
+            row_pick<NQ>(A.oth, A.oth, B.oth, swap);
+            fer_other<NQ>(B.oth, B.own);
             pc++;
             op = nxt;
             nxt = (pc + 1 < tape_len) ? fetch(pc + 1) : GECM_OP_NOP;
@@ -395,6 +437,9 @@ __device__ __forceinline__ void run_tape_row(const uint32_t *__restrict__ tape, 
         const bool is_step = op >= GECM_OP_STEP;
         const bool do_add = op != GECM_OP_PRAC_BEGIN;
         const bool do_dup = op != GECM_OP_PRAC_END;
+        PtR<NQ> C;
+        C.oth = Coth;
+        fer_other<NQ>(C.own, Coth);
         if (is_step && (op & GECM_OP_SWAP)) {
             PtR<NQ> t = A;
             A = B;
@@ -414,8 +459,17 @@ __device__ __forceinline__ void run_tape_row(const uint32_t *__restrict__ tape, 
             C = A;
         }
         PtR<NQ> T, D;
-        if (do_add) row_add<NQ, ROWS, ALDS>(T, B.ds, A.sd, C.oth, isZ, g, m);
-        if (do_dup) row_dup<NQ, ROWS, ALDS>(D, A.sd, s4, isZ, g, m);
+        FeR<NQ> fA, fB;
+        row_sd<NQ>(fA, A, g);
+        row_ds<NQ>(fB, B, g);
+        if (do_add) {
+            row_add<NQ, ROWS, ALDS>(T.own, fB, fA, C.oth, isZ, g, m);
+            fer_other<NQ>(T.oth, T.own);
+        }
+        if (do_dup) {
+            row_dup<NQ, ROWS, ALDS>(D.own, fA, s4, isZ, g, m);
+            fer_other<NQ>(D.oth, D.own);
+        }
         if (op == GECM_OP_PRAC_END) {
             A = T;
         } else if (op == GECM_OP_PRAC_BEGIN) {
@@ -434,6 +488,7 @@ __device__ __forceinline__ void run_tape_row(const uint32_t *__restrict__ tape, 
             B = D;
             A = oldA;
         }
+        Coth = C.oth;
     }
 }
 
@@ -470,17 +525,17 @@ __device__ __forceinline__ void stage1_row(const uint32_t *__restrict__ tape, ui
     PtR<NQ> P;
     FeR<NQ> s4, t;
     fer_load<NQ>(t, mine, stride, cidx, l, nl);
-    fer_mul<NQ, ROWS, true, ALDS>(P.own, t, cin, mp);             // x*R -> x*R' (mod N')
+    fer_mul<NQ, ROWS, true, ALDS, false, false, true>(P.own, t, cin, mp);     // x*R -> 4 x*R' (mod N')
     RowSign g;
     g.mz = isZ ? 0xffffffffu : 0u;
     g.bz = isZ ? 1u : 0u;
     g.mx = ~g.mz;
     g.bx = 1u - g.bz;
-    row_forms<NQ>(P, g);
+    fer_other<NQ>(P.oth, P.own);
     fer_load<NQ>(t, S, stride, cidx, l, nl);
-    fer_mul<NQ, ROWS, true, ALDS>(s4, t, cin, mp);
+    fer_mul<NQ, ROWS, true, ALDS, false, false, true>(s4, t, cin, mp);
     run_tape_row<NQ, ROWS, ALDS>(tape, tape_len, P, s4, isZ, g, mp);
-    fer_mul<NQ, ROWS, false, ALDS>(t, P.own, one, mn);                    // x*R' -> x*R (mod N), in (-N/16, 17N/16)
+    fer_mul<NQ, ROWS, false, ALDS, true>(t, P.own, one, mn);              // 4 x*R' -> x*R (mod N), in (-N/16, 17N/16)
     // + K' (a multiple of N with every limb >= 2^28 - 1): all limbs positive; then one carry-save pass
     uint32_t u[NQ];
 #pragma unroll
