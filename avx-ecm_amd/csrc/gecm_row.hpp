@@ -42,6 +42,8 @@ struct RowMod {
     uint32_t n[NQ];   // this lane's limbs of the modulus
     uint32_t rho;     // -modulus^-1 mod 2^28 (unused when RHO1)
     int32_t c16;      // 16, in a scalar register, opaque to the compiler (row_c16)
+    int32_t kb, zb;   // 2^27 and -2^27 in vector registers (row_bias): the rounding bias of a multiply that delivers its
+                      // result times 4 rides on its last two hand-overs (fer_mul, R4); set where R4 is used
 };
 
 // An empty asm statement that READS x: a second use of the value stops the compiler from re-associating the sum it
@@ -56,9 +58,18 @@ __device__ __forceinline__ int32_t row_c16()
     asm volatile("s_mov_b32 %0, 16" : "=s"(c));
     return c;
 }
+// v in a vector register of its own for the whole kernel, opaque to the compiler: the high half of an addend pair
+template <int32_t V>
+__device__ __forceinline__ int32_t row_bias()
+{
+    int32_t c;
+    asm volatile("v_mov_b32 %0, %1" : "=v"(c) : "n"(V));
+    return c;
+}
 
 #define GECM_DPP_ROW_SHL1 0x101        /* lane l <- lane l+1 of the row (lane 15: 0) */
 #define GECM_DPP_ROW_SHR1 0x111        /* lane l <- lane l-1 of the row (lane 0: 0) */
+#define GECM_DPP_ROW_ROR1 0x121        /* lane l <- lane l-1 of the row (lane 0 <- lane 15) */
 #define GECM_DPP_ROW_NEWBCAST 0x150    /* + i: every lane <- lane i of its row (gfx90a+) */
 
 template <int CTRL>
@@ -265,20 +276,28 @@ __device__ __forceinline__ void fer_mul(FeR<NQ> &r, const FeR<NQ> &a, const FeR<
             // above, in the same statement as the next row's first product
             const int32_t hi = (int32_t)(T[0] >> 32);
             const uint32_t lo = row_dpp<GECM_DPP_ROW_SHL1>((uint32_t)T[0]);
-            if constexpr (i + 1 < ROWS) T[0] = smad16_smad(hi, (int64_t)(uint64_t)lo, Ab[i + 1], b4[0]);
-            else T[0] = smad16(hi, (int64_t)(uint64_t)lo);
+            // R4: the rounding bias of the end rides on the last two hand-overs, as the high word of their addend pair
+            // (zero everywhere else): + 2^27 into the last row's high part, which its hand-over multiplies by 16, and
+            // - 2^27 on that hand-over itself (below)
+            int64_t add = (int64_t)(uint64_t)lo;
+            if constexpr (R4 && i + 2 == ROWS) add = (int64_t)(((uint64_t)(uint32_t)m.kb << 32) | lo);
+            if constexpr (R4 && i + 1 == ROWS) add = (int64_t)(((uint64_t)(uint32_t)m.zb << 32) | lo);
+            if constexpr (i + 1 < ROWS) T[0] = smad16_smad(hi, add, Ab[i + 1], b4[0]);
+            else T[0] = smad16(hi, add);
         });
         // balanced normalisation in the accumulator's own scale: u16 = 16 x (value + 2^27) has the limb (+ 2^27) in
         // bits 4..31 of its low register and what leaves the lane AS its high register; the neighbour's carry comes in
         // on the add itself (DPP)
-        const int64_t u16 = T[0] + (int64_t)(1u << 31);
         if constexpr (R4) {
-            // times 4 in the same instructions: every accumulator is a multiple of 16 (4a x 4b, 16 x digit, 16 x high
-            // part), so its low register READ AS SIGNED is 16 x the balanced limb and an arithmetic shift by 2 leaves
-            // 4 x limb; the neighbour's carry enters shifted on the add (v_lshl_add_u32)
-            const int32_t lim4 = (int32_t)(uint32_t)T[0] >> 2;
-            r.v[0] = lim4 + (int32_t)(row_dpp<GECM_DPP_ROW_SHR1>((uint32_t)(u16 >> 32)) << 2);
+            // times 4, and without the add: the hand-overs have put the bias in (m.kb, m.zb above), T[0] is already
+            // u16 - 2^59.  Its low register, read unsigned and shifted right by 2, is 4 x limb + 2^29; its high register is
+            // the carry - 2^27, which enters shifted on the add (v_lshl_add_u32) and takes the 2^29 away.  Lane 0 has no
+            // lane below and needs the bare - 2^27: row_ror:1 brings it lane 15's high register, which is that, because
+            // the top lane's carry is 0 (|value| < 1.2 N' < 2^(28 ROWS - 4): the top lane's accumulator is below 2^29
+            // in absolute value; lanes from ROWS up hold 0 throughout).  DESIGN.md §5e.
+            r.v[0] = (int32_t)(((uint32_t)T[0] >> 2) + (row_dpp<GECM_DPP_ROW_ROR1>((uint32_t)(T[0] >> 32)) << 2));
         } else {
+            const int64_t u16 = T[0] + (int64_t)(1u << 31);
             const int32_t lim = (int32_t)(((uint32_t)u16 >> 4) & GECM_LIMB_MASK) - (1 << 27);
             r.v[0] = lim + (int32_t)row_dpp<GECM_DPP_ROW_SHR1>((uint32_t)(u16 >> 32));
         }
@@ -522,6 +541,11 @@ __device__ __forceinline__ void stage1_row(const uint32_t *__restrict__ tape, ui
     mp.rho = 1u;
     mn.rho = rho_n;
     mp.c16 = mn.c16 = row_c16();
+    mp.kb = mn.kb = mp.zb = mn.zb = 0;
+    if constexpr (NQ == 1) {       // (two and three limbs per lane: the same fold saves no instruction)
+        mp.kb = mn.kb = row_bias<(1 << 27)>();
+        mp.zb = mn.zb = row_bias<-(1 << 27)>();
+    }
     PtR<NQ> P;
     FeR<NQ> s4, t;
     fer_load<NQ>(t, mine, stride, cidx, l, nl);
