@@ -102,6 +102,15 @@ int gecm_dev_l0(gecm_dev *d, int op, const uint32_t *a, const uint32_t *b, uint3
  * r3).  a canonical; inv = the inverse as fe_inv_mont returns it, multiplied by the constant `fix`
  * (internal Montgomery form) and canonical, or 0 where gcd(a, N) != 1; g = gcd(a, N), a plain integer. */
 int gecm_dev_l0_inv(gecm_dev *d, const uint32_t *a, uint32_t *inv, uint32_t *g, size_t count, const uint32_t *fix);
+/* The raw test-level operator (k_l0_raw): r = op(a, b) for `count` residues, op = GECM_L0_MUL, _SQR, _ADD, _SUB or
+ * _CONDSUB (fe_cond_sub_n of a; b may be NULL for the one-operand operators), by the field function itself on the limbs
+ * exactly as given — any 32-bit words: no canonical check, no Montgomery form assumed — and the limbs exactly as the
+ * function left them.  special != 0: the multiply gecm_dev_set_fform chose for this context (its fe_add, fe_sub and
+ * fe_cond_sub_n are the generic ones), else the generic REDC.  A single-modulus context takes any count; a
+ * multi-modulus context must hold a lane-packed batch and takes count = its positions, padding included: residue p is
+ * worked on modulo the N of position p.  Works in device memory of its own: the batch stays as it is.  Values outside
+ * the bounds of csrc/gecm_field.hpp give unspecified limbs, nothing else. */
+int gecm_dev_l0_raw(gecm_dev *d, int op, int special, const uint32_t *a, const uint32_t *b, uint32_t *r, size_t count);
 
 /* ---- multi-modulus batches ----
  * A context opened with multi != 0 takes the modulus of every launch from device tables, with 1 or 2 lanes per curve

@@ -881,6 +881,48 @@ extern "C" int gecm_dev_l0_inv(gecm_dev *d, const uint32_t *a, uint32_t *inv, ui
     return 0;
 }
 
+// The raw operator works in planes of its own, freed when it returns: the batch of the context, which on a lane-packed
+// context names the modulus of every position, stays as it is.
+struct raw_planes {
+    uint32_t *p = nullptr;
+    ~raw_planes() { (void)hipFree(p); }
+};
+
+extern "C" int gecm_dev_l0_raw(gecm_dev *d, int op, int special, const uint32_t *a, const uint32_t *b, uint32_t *r, size_t count)
+{
+    HIPCHK(hipSetDevice(d->device));
+    const bool known = op == GECM_L0_MUL || op == GECM_L0_SQR || op == GECM_L0_ADD || op == GECM_L0_SUB || op == GECM_L0_CONDSUB;
+    if (!known || !a || !r || !count) {
+        g_err = "gecm_dev_l0_raw: needs an operator (MUL, SQR, ADD, SUB, CONDSUB), operands and a result";
+        return -2;
+    }
+    if (d->multi && (!d->have_groups || !d->lane_packed || special || count != d->ncurves)) {
+        g_err = "gecm_dev_l0_raw: a multi-modulus context takes one residue per position of its lane-packed batch, generic "
+                "multiply";
+        return -2;
+    }
+    const int form = special ? d->fform : 0;
+    if (form == 2 && d->nl - d->k1->fform_generic_limbs < 3) {
+        g_err = "gecm_dev_l0_raw: no 2^k - c multiply at this limb count";
+        return -2;
+    }
+    const size_t stride = d->multi ? d->stride : (count + 63) / 64 * 64, plane = stride * d->nl;
+    raw_planes m;
+    HIPCHK(hipMalloc(&m.p, 3 * plane * sizeof(uint32_t)));
+    // A, B with zero padding lanes; B = A where the operator has one operand
+    HIPCHK(hipMemsetAsync(m.p, 0, 2 * plane * sizeof(uint32_t), d->stream));
+    const uint32_t *src[2] = {a, b ? b : a};
+    for (int q = 0; q < 2; q++)
+        HIPCHK(hipMemcpy2DAsync(m.p + q * plane, stride * 4, src[q], count * 4, count * 4, d->nl, hipMemcpyHostToDevice,
+                                d->stream));
+    gecm_modconst mc = modconst(d);
+    d->k1->l0_raw(d->stream, &mc, op, form, m.p, m.p + plane, m.p + 2 * plane, stride);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy2DAsync(r, count * 4, m.p + 2 * plane, stride * 4, count * 4, d->nl, hipMemcpyDeviceToHost, d->stream));
+    HIPCHK(hipStreamSynchronize(d->stream));
+    return 0;
+}
+
 // ---------------------------------------------------------------- multi-modulus batches
 extern "C" int gecm_dev_lane_packing_built(int nl)
 {

@@ -25,6 +25,18 @@
 // reference returns after every operation — are produced once, when results leave the device.
 // Because every intermediate is the same element of Z/N as in the reference, outputs are
 // bit-identical (SURVEY.md §8a semantics note).
+//
+// The contract, exactly.  With m the bound of a product as a fraction of K: a product has limbs < 2^28 (the top limb
+// takes the rest) and a value < m K; a sum of two products has limbs < 2^29 and a value < 2m K; a difference
+// a + K' - b of two products has limbs < 3*2^28 (renormalised from 26 limbs on: LazyPolicy) and a value < (1+m) K; every
+// operand of a multiply is below (1+m) K, and the result is a product again: (1+m)^2 K^2/R + N <= ((1+m)^2/16 + 1/2) K
+// must not exceed m K, which holds from m = 7 - sqrt(40) = 0.675445 on.  The bound is m = 0.6755.  "0.675 K" and
+// "1.675 K", here and in the other sources, are that number cut short: taken literally they are not closed (operands
+// just below 1.675 K give products up to 0.67535 K on a modulus close to R/32).  Under the contract the 64-bit column
+// accumulator stays below 0.80 * 2^64 (23 limbs), the class sums of the F-form, a2 = a << 1 of fe_sqr, the signed
+// multiply-add of the C-form and the bit-31 borrow test of fe_cond_sub_n stay inside their registers:
+// tests/field_model.py is this file limb for limb on integers with every register width checked, and k_l0_raw
+// (gecm_kernels.hip) runs these functions on the model's operands at the edge of the contract.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -497,6 +497,48 @@ k_l0_inv(const uint32_t *__restrict__ A, uint32_t *__restrict__ C, uint32_t *__r
     fe_store(C, stride, idx, r);
 }
 
+// The raw test-level operator: one field function of gecm_field.hpp on the limbs as they were uploaded — lazy operands
+// at the edge of the contract, not canonical ones — and the limbs it left, with no fe_canonical_mont behind it.  MOD is
+// the flavour of the multiply: ModK (generic REDC), ModF, ModP, ModC (the special forms; their fe_sub and fe_cond_sub_n
+// are ModK's) by value, and ModV through the lane constants, every lane modulo its own N with K' read from LDS.  Register
+// arithmetic on what was loaded: inputs outside the contract give unspecified limbs, never a fault.  Kernels of their
+// own so that k_l0 and k_l0_inv stay what they were.
+#define GECM_L0_RAW_BODY                                                        \
+    uint32_t idx = blockIdx.x * 64u + threadIdx.x;                              \
+    Fe<NL> x, y, r;                                                             \
+    fe_load(x, A, stride, idx);                                                 \
+    fe_load(y, B, stride, idx);                                                 \
+    if (op == GECM_L0_MUL) fe_mul(r, x, y, k.m);                                \
+    else if (op == GECM_L0_SQR) fe_sqr(r, x, k.m);                              \
+    else if (op == GECM_L0_ADD) fe_add(r, x, y);                                \
+    else if (op == GECM_L0_SUB) fe_sub(r, x, y, k.m);                           \
+    else {                                                                      \
+        r = x;                                                                  \
+        fe_cond_sub_n(r, k.m);                                                  \
+    }                                                                           \
+    fe_store(C, stride, idx, r);
+
+template <int NL, class MOD>
+__global__ void __launch_bounds__(64)
+k_l0_raw(int op, const uint32_t *__restrict__ A, const uint32_t *__restrict__ B, uint32_t *__restrict__ C, size_t stride,
+         ModArgsS<NL, MOD> k)
+{
+    GECM_ARG_CONSTS
+    GECM_L0_RAW_BODY
+}
+
+#if GECM_HAS_LANE
+template <int NL>
+__global__ void __launch_bounds__(64)
+k_l0_raw_lane(int op, const uint32_t *__restrict__ A, const uint32_t *__restrict__ B, uint32_t *__restrict__ C, size_t stride,
+              LaneGroups<NL> g)
+{
+    GECM_LANE_CONSTS
+    GECM_L0_RAW_BODY
+}
+#endif
+#undef GECM_L0_RAW_BODY
+
 // ---------------------------------------------------------------- factor scan
 // check_factor (ecm.c:2542-2557) for every curve on the device: g = gcd(v, N) by the same
 // fixed-iteration binary algorithm the stage-2 inversion uses; flag = 1 iff 1 < g < N.
@@ -1298,6 +1340,29 @@ static void launch_l0_inv(void *stream, const gecm_modconst *mc, const uint32_t 
                        s2_const(&mc->m), f);
 }
 
+// form as for stage1 (0: generic REDC, which alone has a per-lane twin; +1, -1, 2: the special multiplies, by value)
+template <class MOD>
+static void launch_l0_raw_mod(void *stream, const gecm_modconst *mc, int op, const uint32_t *A, const uint32_t *B, uint32_t *C,
+                              size_t stride)
+{
+    if constexpr (std::is_same<MOD, ModK<GECM_NL>>::value)
+        launch_by_source<ModArgsS<GECM_NL, MOD>>(stream, mc, blocks_of(stride), k_l0_raw<GECM_NL, MOD>, nullptr,
+                                                 GECM_LANE(k_l0_raw_lane), op, A, B, C, stride);
+    else
+        launch_by_source<ModArgsS<GECM_NL, MOD>>(stream, mc, blocks_of(stride), k_l0_raw<GECM_NL, MOD>, nullptr, nullptr, op, A,
+                                                 B, C, stride);
+}
+
+static void launch_l0_raw(void *stream, const gecm_modconst *mc, int op, int form, const uint32_t *A, const uint32_t *B,
+                          uint32_t *C, size_t stride)
+{
+    if (form == 2) {
+        if constexpr (FPolicy<GECM_NL>::NF >= 3) launch_l0_raw_mod<ModC<GECM_NL>>(stream, mc, op, A, B, C, stride);
+    } else if (form > 0) launch_l0_raw_mod<ModF<GECM_NL>>(stream, mc, op, A, B, C, stride);
+    else if (form < 0) launch_l0_raw_mod<ModP<GECM_NL>>(stream, mc, op, A, B, C, stride);
+    else launch_l0_raw_mod<ModK<GECM_NL>>(stream, mc, op, A, B, C, stride);
+}
+
 static void launch_gcd_scan(void *stream, const gecm_modconst *mc, const uint32_t *V, uint32_t *G, uint32_t *flags,
                             size_t stride)
 {
@@ -1350,7 +1415,7 @@ extern "C" const gecm_kernels_p1 *CAT(CAT(gecm_kernels_, GECM_NL), _p1)(void)
     static const gecm_kernels_p1 t = {launch_stage1, launch_canon, launch_from_mont, launch_to_mont, launch_l0, launch_l0_inv,
                                       launch_gcd_scan, launch_build, FPolicy<GECM_NL>::G, pack_group, sizeof(GroupConst<GECM_NL>),
                                       GECM_MANIFEST, GECM_HAS_LANE, launch_normalize, launch_build_param,
-                                      launch_stage1_unit, launch_gcd_scan_off};
+                                      launch_stage1_unit, launch_gcd_scan_off, launch_l0_raw};
     return &t;
 }
 #endif

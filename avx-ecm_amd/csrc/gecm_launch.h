@@ -135,6 +135,11 @@ struct gecm_kernels_p1 {
     /* gcd_scan of V - off R mod N, off = 1 or 2: the factor test of a P-1 / P+1 residue in Montgomery form */
     void (*gcd_scan_off)(void *stream, const gecm_modconst *mc, const uint32_t *V, uint32_t *G, uint32_t *flags,
                          size_t stride, uint32_t off);
+    /* the raw test-level operator: C = op(A, B), op = GECM_L0_MUL, _SQR, _ADD, _SUB or _CONDSUB (gecm_ops.h), by the field
+     * function itself on the limbs as they are, and the limbs it leaves.  form as for stage1 picks the multiply; a
+     * lane-packed mc takes form 0 (limb counts with has_lane), a wave-packed one is not served. */
+    void (*l0_raw)(void *stream, const gecm_modconst *mc, int op, int form, const uint32_t *A, const uint32_t *B, uint32_t *C,
+                   size_t stride);
 };
 
 /* Part 2: stage 2 (any mc takes K = 1, 2, .. 32; a lane-packed one at limb counts with has_lane). */

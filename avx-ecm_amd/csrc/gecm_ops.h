@@ -16,4 +16,6 @@ typedef struct {
 } gecm_devmod;
 
 enum { GECM_L0_MUL = 0, GECM_L0_SQR = 1, GECM_L0_ADD = 2, GECM_L0_SUB = 3, GECM_L0_ADDSUB = 4 };
+/* the raw test-level operator (k_l0_raw): MUL, SQR, ADD, SUB as above, and fe_cond_sub_n of the first operand */
+enum { GECM_L0_CONDSUB = 5 };
 #endif

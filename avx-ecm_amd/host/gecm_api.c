@@ -790,6 +790,44 @@ int gecm_vecinvmod(gecm_ctx *c, const void *a, void *inv, void *gcd, size_t batc
     return GECM_OK;
 }
 
+/* The field functions themselves on the caller's limbs (include/gecm.h): sizes and state are checked, the values are
+ * not, and nothing is converted on the way in or out. */
+int gecm_vecrawop(gecm_ctx *c, int target, int op, const uint32_t *a, const uint32_t *b, uint32_t *r, size_t count)
+{
+    const int one_operand = op == GECM_RAW_SQR || op == GECM_RAW_CONDSUB;
+    if (!c || !a || !r || count == 0 || op < GECM_RAW_MUL || op > GECM_RAW_CONDSUB || (!b && !one_operand)) {
+        set_err("gecm_vecrawop: bad argument");
+        return GECM_ERR_ARG;
+    }
+    /* GECM_RAW_MUL .. _SUB are the device layer's codes; CONDSUB has one of its own */
+    const int dev_op = op == GECM_RAW_CONDSUB ? GECM_L0_CONDSUB : op;
+    gecm_dev *dev = NULL;
+    if (target == GECM_RAW_BATCH) {
+        if (!c->multi || c->batch == 0 || c->packing_used != GECM_PACK_LANE || count != c->batch) {
+            set_err("gecm_vecrawop: GECM_RAW_BATCH needs the lane-packed batch of a multi-modulus context and one residue per "
+                    "position of it (%zu)", c->multi ? c->batch : (size_t)0);
+            return c->multi && c->batch && c->packing_used == GECM_PACK_LANE ? GECM_ERR_ARG : GECM_ERR_STATE;
+        }
+        dev = c->dev;
+    } else if (c->multi) {
+        return multi_refuse("gecm_vecrawop on one modulus");
+    } else if (target == GECM_RAW_TWIN) {
+        if (!c->twin.dev) { set_err("gecm_vecrawop: this N has no special-form twin (gecm_get_special_form)"); return GECM_ERR_STATE; }
+        dev = c->twin.dev;
+    } else if (target == GECM_RAW_OWN) {
+        if (l0_open(c)) return GECM_ERR_DEVICE;
+        dev = c->dev_l0;
+    } else {
+        set_err("gecm_vecrawop: bad target");
+        return GECM_ERR_ARG;
+    }
+    if (gecm_dev_l0_raw(dev, dev_op, target == GECM_RAW_TWIN, a, one_operand ? NULL : b, r, count)) {
+        set_err("gecm_vecrawop: %s", gecm_dev_error());
+        return GECM_ERR_DEVICE;
+    }
+    return GECM_OK;
+}
+
 /* ---- phase 0 -------------------------------------------------------------------------------- */
 /* The one-shot setting of gecm_set_next_params belongs to the build call that follows it, whether that call succeeds
  * or not: the call reads c->next_param where it needs it (seeds do not) and returns through here, which drops the

@@ -58,6 +58,11 @@ _sig("gecm_vecsubmod", c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t)
 _sig("gecm_vecaddsubmod", c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t)
 _sig("gecm_vecinvmod", c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t)
 EXPORTS += ["gecm_vecinvmod"]
+# the field functions themselves on raw device limbs (gecm_vecrawop)
+RAW_MUL, RAW_SQR, RAW_ADD, RAW_SUB, RAW_CONDSUB = range(5)
+RAW_OWN, RAW_TWIN, RAW_BATCH = range(3)
+_sig("gecm_vecrawop", c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t)
+EXPORTS += ["gecm_vecrawop"]
 _sig("gecm_build_curves", c_int, c_void_p, ctypes.POINTER(c_u64), c_size_t)
 _sig("gecm_upload_points", c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t)
 _sig("gecm_stage1", c_int, c_void_p, c_u64)
@@ -443,6 +448,25 @@ class Engine:
         inv, g = self.empty(n), self.empty(n)
         _chk(lib.gecm_vecinvmod(self._h, self.pack(a), inv, g, n), "gecm_vecinvmod")
         return self.unpack(inv, n), self.unpack(g, n)
+
+    def vecrawop(self, op, a, b=None, target=RAW_OWN, limbs=None):
+        """one field function of the device on raw limbs: a, b lists of residues, each a list of `limbs` 32-bit words
+        (default: the context's dev_limbs; the twin's for RAW_TWIN); the result in the same shape, limbs as the function
+        left them.  Nothing is checked against N or converted."""
+        if limbs is None:
+            limbs = self.special_form()[2] if target == RAW_TWIN else self.cfg.dev_limbs
+        n = len(a)
+        if any(len(v) != limbs for v in a) or (b is not None and (len(b) != n or any(len(v) != limbs for v in b))):
+            raise ValueError("vecrawop: every residue has %d limbs, and b as many residues as a" % limbs)
+
+        def planes(vals):
+            arr = (ctypes.c_uint32 * max(1, n * limbs))()
+            for j in range(limbs):
+                arr[j * n:(j + 1) * n] = [v[j] for v in vals]
+            return arr
+        out = (ctypes.c_uint32 * max(1, n * limbs))()
+        _chk(lib.gecm_vecrawop(self._h, target, op, planes(a), None if b is None else planes(b), out, n), "gecm_vecrawop")
+        return [[out[i + j * n] for j in range(limbs)] for i in range(n)]
 
     # ---- L1 ----
     def _next_params(self, params, batch):

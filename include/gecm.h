@@ -87,6 +87,24 @@ int gecm_vecaddsubmod(gecm_ctx *ctx, const void *a, const void *b, void *sum, vo
  * inv[i] = x^-1 * 2^(DIGITBITS*NWORDS) mod N, canonical, or 0 when gcd(a_i, N) != 1; gcd[i] = gcd(a_i, N) as a plain
  * integer in the same vec layout (N for a_i = 0).  inv and gcd must not alias each other.                      */
 int gecm_vecinvmod(gecm_ctx *ctx, const void *a, void *inv, void *gcd, size_t batch);
+/* A seventh, below the other six: one function of the device's one-lane field arithmetic (csrc/gecm_field.hpp: fe_mul,
+ * fe_sqr, fe_add, fe_sub, fe_cond_sub_n) on limbs of the caller's choice, and the limbs it leaves.  A residue is
+ * `limbs` 32-bit words, limb j of residue i at [i + j * count] — raw device limbs of 28 bits and whatever the caller
+ * puts above them: nothing is checked against N, nothing is converted to or from a Montgomery radix, no canonical form
+ * is made of the result.  This is how the lazy operands of the ladders (products, sums, differences at the bounds the
+ * header of gecm_field.hpp states) reach the multiply directly.  Inputs outside those bounds give unspecified limbs
+ * and nothing worse: the kernel does register arithmetic on what it loaded.  b may be NULL for GECM_RAW_SQR and
+ * GECM_RAW_CONDSUB.  target says modulo what, and with which multiply:
+ *   GECM_RAW_OWN    the context's N, generic REDC; limbs = gecm_config.dev_limbs, any count.
+ *   GECM_RAW_TWIN   the modulus Mw of the special-form twin with its special multiply (2^k - 1, 2^k + 1, 2^k - c);
+ *                   limbs = what gecm_get_special_form reports; GECM_ERR_STATE for an N without a twin.
+ *   GECM_RAW_BATCH  a multi-modulus context holding a lane-packed batch: count = the positions of the batch
+ *                   (gecm_multi_positions), residue p is worked on modulo the number of position p, every lane with its
+ *                   own constants; limbs = gecm_config.dev_limbs.  The batch itself is not touched.
+ * Sizes and state are checked, values never.                                                                        */
+enum { GECM_RAW_MUL = 0, GECM_RAW_SQR = 1, GECM_RAW_ADD = 2, GECM_RAW_SUB = 3, GECM_RAW_CONDSUB = 4 };
+enum { GECM_RAW_OWN = 0, GECM_RAW_TWIN = 1, GECM_RAW_BATCH = 2 };
+int gecm_vecrawop(gecm_ctx *ctx, int target, int op, const uint32_t *a, const uint32_t *b, uint32_t *r, size_t count);
 
 /* ---- L1 phase 0: curve construction (build_one_curve, ecm.c:1548-1803) ---------------------
  * Suyama parametrisation from sigma[0..batch): the context computes X, Z (=1), s = (A+2)/4 on the

@@ -81,11 +81,13 @@ class KernelModel:
         self.multiplies = 0
 
     def mul(self, a, b):
-        assert 0 <= a and 1000 * a < 1675 * self.K, "operand above 1.675 K"
-        assert 0 <= b and 1000 * b < 1675 * self.K, "operand above 1.675 K"
+        # 0.6755, not 0.675: operands below 1.675 K reach products of 0.67535 K; the closed bound is 7 - sqrt(40) = 0.675445
+        # (tests/field_model.py: PRODUCT_BOUND, fixed_point_case)
+        assert 0 <= a and 10000 * a < 16755 * self.K, "operand above 1.6755 K"
+        assert 0 <= b and 10000 * b < 16755 * self.K, "operand above 1.6755 K"
         t = a * b
         r = (t + (t * self.nprime % self.R) * self.n) // self.R
-        assert 1000 * r < 675 * self.K
+        assert 10000 * r < 6755 * self.K
         self.multiplies += 1
         return r
 
