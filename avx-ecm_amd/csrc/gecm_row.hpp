@@ -129,6 +129,12 @@ __device__ __forceinline__ int64_t smad16_smad(int32_t x, int64_t add, int32_t y
     return r;
 }
 
+// The scanned operand of a one-limb-per-lane multiply, broadcast: 4 x limb j of it in every lane of the row (fer_scan).
+template <int ROWS>
+struct RowScan {
+    int32_t Ab[ROWS];
+};
+
 // r = a*b/R' mod (modulus of m), R' = 2^(28*ROWS): ROWS = the limbs in use (at most 16*NQ; limbs from ROWS up are
 // zero in every operand and in the modulus, so their rows would add nothing).  Operand limbs |.| < 2^29; result limbs in
 // [-2^27-4, 2^27+4] (top limb: whatever the value needs), |result| < |a||b|/R' + modulus.
@@ -138,11 +144,15 @@ __device__ __forceinline__ int64_t smad16_smad(int32_t x, int64_t add, int32_t y
 // A4, B4: the limbs of a, of b come multiplied by 4 already (the scale the rows read); R4: r is delivered times 4.  The
 // tape interpreter keeps every value in that scale, so that no multiply of a point operation shifts its operands: the
 // bounds above are those of the values, and 4 x (2^29 - 1) still fits the signed 32-bit operand of v_mad_i64_i32.
-template <int NQ, int ROWS, bool RHO1, bool ALDS, bool A4 = false, bool B4 = false, bool R4 = false>
-__device__ __forceinline__ void fer_mul(FeR<NQ> &r, const FeR<NQ> &a, const FeR<NQ> &b, const RowMod<NQ> &m)
+// SCANNED (one limb per lane, DPP form): the limbs of 4a are in every lane already, in *scan (fer_scan); a is not read and
+// the rows make no requests (fer_mul_scanned).
+template <int NQ, int ROWS, bool RHO1, bool ALDS, bool A4 = false, bool B4 = false, bool R4 = false, bool SCANNED = false>
+__device__ __forceinline__ void fer_mul(FeR<NQ> &r, const FeR<NQ> &a, const FeR<NQ> &b, const RowMod<NQ> &m,
+                                        const RowScan<ROWS> *scan = nullptr)
 {
     static_assert(ROWS > 16 * (NQ - 1) && ROWS <= 16 * NQ, "the limbs in use fill the lanes but for the last one");
     static_assert(!ALDS || NQ == 1, "the crossbar form is for one limb per lane");
+    static_assert(!SCANNED || (NQ == 1 && !ALDS), "a ready-made scan is for the one-limb DPP form");
     int32_t a4[NQ], b4[NQ];
 #pragma unroll
     for (int t = 0; t < NQ; t++) {
@@ -239,10 +249,15 @@ __device__ __forceinline__ void fer_mul(FeR<NQ> &r, const FeR<NQ> &a, const FeR<
         // knows) from lane 2k then brings limbs 2k and 2k + 1: 8 moves + 1 instead of 16 for the 416-bit class.
         int32_t Ab[ROWS];
         int64_t a01 = 0;
-        if constexpr (!ALDS) a01 = (int64_t)(((uint64_t)row_dpp<GECM_DPP_ROW_SHL1>((uint32_t)a4[0]) << 32) | (uint32_t)a4[0]);
+        if constexpr (SCANNED) {
+#pragma unroll
+            for (int j = 0; j < ROWS; j++) Ab[j] = scan->Ab[j];
+        }
+        if constexpr (!ALDS && !SCANNED) a01 = (int64_t)(((uint64_t)row_dpp<GECM_DPP_ROW_SHL1>((uint32_t)a4[0]) << 32) | (uint32_t)a4[0]);
         auto request = [&](auto jc) {
             constexpr int j = decltype(jc)::value;
-            if constexpr (ALDS) {
+            if constexpr (SCANNED) {
+            } else if constexpr (ALDS) {
                 Ab[j] = (int32_t)row_bcast_lds<j>((uint32_t)a4[0]);
             } else if constexpr (j % 2 == 0) {
                 const int64_t P = row_bcast64<j>(a01);
@@ -302,6 +317,31 @@ __device__ __forceinline__ void fer_mul(FeR<NQ> &r, const FeR<NQ> &a, const FeR<
             r.v[0] = lim + (int32_t)row_dpp<GECM_DPP_ROW_SHR1>((uint32_t)(u16 >> 32));
         }
     }
+}
+
+// The one-limb DPP multiply in two halves, for a scanned operand that is known BEFORE the multiply can start (row_add_scanned:
+// each of its two scanned multiplies waits for an X <-> Z exchange that its scanned operand does not need).  fer_scan makes
+// all the requests for the limbs of a (times 4) at once: one row_shl:1 and ROWS / 2 v_mov_b64_dpp, VALU work that stays where
+// it is written, between a ds_swizzle and the wait that covers it.  fer_mul_scanned is the rows of fer_mul on the finished scan:
+// r = a*b/R' times 4, b times 4, the flags A4, B4, R4 and the bounds of fer_mul.  The rows ask for nothing; the wait-state
+// slots that a request filled in every other row are padded.  The product is the same integer whichever operand is scanned;
+// how its carries are spread over the limbs is not.
+template <int ROWS>
+__device__ __forceinline__ void fer_scan(RowScan<ROWS> &s, const FeR<1> &a)
+{
+    const int64_t a01 = (int64_t)(((uint64_t)row_dpp<GECM_DPP_ROW_SHL1>((uint32_t)a.v[0]) << 32) | (uint32_t)a.v[0]);
+    static_for<0, (ROWS + 1) / 2>([&](auto kc) {
+        constexpr int j = 2 * decltype(kc)::value;
+        const int64_t P = row_bcast64<j>(a01);
+        s.Ab[j] = (int32_t)(uint32_t)P;
+        if constexpr (j + 1 < ROWS) s.Ab[j + 1] = (int32_t)(P >> 32);
+    });
+    __builtin_amdgcn_sched_barrier(0);
+}
+template <int ROWS>
+__device__ __forceinline__ void fer_mul_scanned(FeR<1> &r, const RowScan<ROWS> &s, const FeR<1> &b, const RowMod<1> &m)
+{
+    fer_mul<1, ROWS, true, false, true, true, true, true>(r, b, b, m, &s);
 }
 
 // A point coordinate as the tape interpreter keeps it: its own limbs and those of the other coordinate, both TIMES 4 (the
@@ -383,6 +423,29 @@ __device__ __forceinline__ void row_add(FeR<NQ> &own, const FeR<NQ> &fB, const F
     fer_mul<NQ, ROWS, true, ALDS, true, true, true>(own, e, c, m);
 }
 
+// row_add for one limb per lane in the DPP form, with VALU work in the shadow of both X <-> Z exchanges.  sA = the scan of
+// fA, made by the caller while the exchange that fB waits for is in flight: the first multiply scans the kept point's form
+// (old) instead of the new point's.  The exchange of the first product is followed by the scan of c, which has been known
+// since the step began, and by shadow(), whatever the caller can do once c has been read (the renaming of a rule-3 step);
+// the third multiply then scans c instead of the fresh square.  Bounds: fA and fB are a sum or a difference of two product
+// limbs, times 4 (at most 2^30 + 32 in absolute value), c and the square are product limbs times 4: each inside fer_mul's
+// 4 x 2^29 whether it is the scanned operand or the lane's own.
+template <int ROWS, class Shadow>
+__device__ __forceinline__ void row_add_scanned(FeR<1> &own, const RowScan<ROWS> &sA, const FeR<1> &fB, const FeR<1> &c,
+                                                const RowSign &g, const RowMod<1> &m, Shadow &&shadow)
+{
+    FeR<1> w, t, e;
+    RowScan<ROWS> sC;
+    fer_mul_scanned<ROWS>(w, sA, fB, m);                                // X: U      Z: V
+    fer_other<1>(t, w);
+    fer_scan<ROWS>(sC, c);
+    shadow();
+    __builtin_amdgcn_sched_barrier(0);
+    fer_sum_diff<1>(e, t, w, g);                                        // X: V + U  Z: U - V
+    fer_mul<1, ROWS, true, false, true, true, true>(e, e, e, m);
+    fer_mul_scanned<ROWS>(own, sC, e, m);
+}
+
 // own coordinate of D = 2A (vec_duplicate, ecm.c:445-457): fA = row_sd(A), s4 = (A+2)/4 of the curve; every value times 4
 template <int NQ, int ROWS, bool ALDS>
 __device__ __forceinline__ void row_dup(FeR<NQ> &own, const FeR<NQ> &fA, const FeR<NQ> &s4, bool isZ, const RowSign &g,
@@ -440,16 +503,38 @@ __device__ __forceinline__ void run_tape_row(const uint32_t *__restrict__ tape, 
         while ((op & ~GECM_OP_SWAP) == (GECM_OP_STEP | GECM_OP_RULE3)) {
             const uint64_t swap = (op & GECM_OP_SWAP) ? ~(uint64_t)0 : 0;
             FeR<NQ> fA, fB;
-            row_sd<NQ>(fA, A, g);
-            row_ds<NQ>(fB, B, g);
-            row_pick<NQ>(A.own, A.own, B.own, swap);
-            row_add<NQ, ROWS, ALDS>(B.own, fB, fA, Coth, isZ, g, m);
-            row_pick<NQ>(Coth, B.oth, A.oth, swap);
-            row_pick<NQ>(A.oth, A.oth, B.oth, swap);
-            fer_other<NQ>(B.oth, B.own);
-            pc++;
-            op = nxt;
-            nxt = (pc + 1 < tape_len) ? fetch(pc + 1) : GECM_OP_NOP;
+            if constexpr (NQ == 1 && !ALDS) {
+                // One limb per lane, DPP form: the exchange that brings B.oth was issued at the end of the step before (below),
+                // and what does not read it comes first: the form of the kept point, the pick that frees B's register and
+                // the scan of that form.  Only then fB, the wait, and the rows.  The picks that read the old C follow its
+                // scan, in the shadow of the addition's own exchange (row_add_scanned).
+                RowScan<ROWS> sA;
+                row_sd<NQ>(fA, A, g);
+                row_pick<NQ>(A.own, A.own, B.own, swap);
+                fer_scan<ROWS>(sA, fA);
+                row_ds<NQ>(fB, B, g);
+                row_add_scanned<ROWS>(B.own, sA, fB, Coth, g, m, [&]() {
+                    row_pick<NQ>(Coth, B.oth, A.oth, swap);
+                    row_pick<NQ>(A.oth, A.oth, B.oth, swap);
+                });
+                // the tape byte first: its scalar load and the wait for it would drain the exchange as well
+                pc++;
+                op = nxt;
+                nxt = (pc + 1 < tape_len) ? fetch(pc + 1) : GECM_OP_NOP;
+                __builtin_amdgcn_sched_barrier(0);
+                fer_other<NQ>(B.oth, B.own);
+            } else {
+                row_sd<NQ>(fA, A, g);
+                row_ds<NQ>(fB, B, g);
+                row_pick<NQ>(A.own, A.own, B.own, swap);
+                row_add<NQ, ROWS, ALDS>(B.own, fB, fA, Coth, isZ, g, m);
+                row_pick<NQ>(Coth, B.oth, A.oth, swap);
+                row_pick<NQ>(A.oth, A.oth, B.oth, swap);
+                fer_other<NQ>(B.oth, B.own);
+                pc++;
+                op = nxt;
+                nxt = (pc + 1 < tape_len) ? fetch(pc + 1) : GECM_OP_NOP;
+            }
         }
         if (op == GECM_OP_NOP) continue;
         const uint32_t rule = op & GECM_OP_RULE_MASK;
@@ -482,7 +567,14 @@ __device__ __forceinline__ void run_tape_row(const uint32_t *__restrict__ tape, 
         row_sd<NQ>(fA, A, g);
         row_ds<NQ>(fB, B, g);
         if (do_add) {
-            row_add<NQ, ROWS, ALDS>(T.own, fB, fA, C.oth, isZ, g, m);
+            if constexpr (NQ == 1 && !ALDS) {
+                // (the scan of fA is not shared with the double's first multiply: it would stay live across the addition)
+                RowScan<ROWS> sA;
+                fer_scan<ROWS>(sA, fA);
+                row_add_scanned<ROWS>(T.own, sA, fB, C.oth, g, m, []() {});
+            } else {
+                row_add<NQ, ROWS, ALDS>(T.own, fB, fA, C.oth, isZ, g, m);
+            }
             fer_other<NQ>(T.oth, T.own);
         }
         if (do_dup) {
