@@ -125,6 +125,16 @@ int gecm_dev_l0_raw(gecm_dev *d, int op, int special, const uint32_t *a, const u
 int gecm_dev_set_groups(gecm_dev *d, uint32_t ngroups, const gecm_devmod *mods, const uint32_t *block_group,
                         const uint32_t *curve_group);
 int gecm_dev_lane_packing_built(int nl);
+/* ---- stage 1 of such a batch with 32 lanes per curve (csrc/gecm_rowk.hip: k_stage1_row_multi) ----
+ * gecm_dev_set_multi_rowconst: the constant sets of the kernel, one for every modulus gecm_dev_set_groups names, in that
+ * order (gecm_rowk.h: GECM_MROW_SET words each), with nq limbs per lane and rows per multiply of the context's limb count
+ * (gecm_row_shape).  Host memory, copied before it returns; -2 on a single-modulus context.
+ * gecm_dev_multi_rows_ready: are there sets for the moduli of the batch?
+ * gecm_dev_stage1_multi_rows: gecm_dev_stage1 with that kernel on either packing, then canon, per launch of a cut tape
+ * (-2 without constants); gecm_dev_last_lanes is then 32.  gecm_dev_stage1 itself answers as it always has. */
+int gecm_dev_set_multi_rowconst(gecm_dev *d, int nq, int rows, uint32_t ngroups, const uint32_t *words);
+int gecm_dev_multi_rows_ready(gecm_dev *d);
+int gecm_dev_stage1_multi_rows(gecm_dev *d);
 
 /* ---- stage 2 (csrc/gecm_stage2.hpp) ----
  * ecm_stage2_init: baby-step table (npb entries, X/Z normalised), Pd = [D]Q, acc = one.  Inverts.

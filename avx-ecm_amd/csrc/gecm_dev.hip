@@ -97,6 +97,10 @@ struct gecm_dev {
     size_t urow_cap = 0;
     uint32_t urow_groups = 0;     // sets dURowC holds; 0 = not available
     int urow_nq = 0, urow_rows = 0;
+    uint32_t *dMRowC = nullptr;  // constant sets of the 32-lane kernel on a multi-modulus batch (gecm_dev_set_multi_rowconst)
+    size_t mrow_cap = 0;
+    uint32_t mrow_groups = 0;     // sets dMRowC holds; 0 = not available
+    int mrow_nq = 0, mrow_rows = 0;
     int fform = 0;        // +1 / -1 / 2: modulus is 2^k - 1 / 2^k + 1 / 2^k - c and stage 1 uses the special multiply (gecm_dev_set_fform)
     int cus = 0;          // compute units of the device (4 SIMDs each)
     int last_lanes = 0;   // lanes per curve the last stage-1 launch used
@@ -275,7 +279,29 @@ extern "C" int gecm_dev_set_unit_rowconst(gecm_dev *d, int nq, int rows, uint32_
     return 0;
 }
 
+extern "C" int gecm_dev_set_multi_rowconst(gecm_dev *d, int nq, int rows, uint32_t ngroups, const uint32_t *words)
+{
+    HIPCHK(hipSetDevice(d->device));
+    if (!d->multi || nq < 1 || nq > GECM_ROW_MAXNQ || 16 * nq > GECM_ROW_WORDS || rows <= 16 * (nq - 1) || rows > 16 * nq ||
+        !ngroups || !words) {
+        g_err = "gecm_dev_set_multi_rowconst: not a multi-modulus context, limbs per lane out of range, or no constants";
+        return -2;
+    }
+    d->mrow_groups = 0;
+    if (grow(&d->dMRowC, &d->mrow_cap, (size_t)ngroups * GECM_MROW_SET)) return -1;
+    // synchronous: the host array may go away when this returns
+    HIPCHK(hipMemcpyAsync(d->dMRowC, words, (size_t)ngroups * GECM_MROW_SET * sizeof(uint32_t), hipMemcpyHostToDevice,
+                          d->stream));
+    HIPCHK(hipStreamSynchronize(d->stream));
+    d->mrow_nq = nq;
+    d->mrow_rows = rows;
+    d->mrow_groups = ngroups;
+    return 0;
+}
+
 extern "C" int gecm_dev_cus(gecm_dev *d) { return d->cus; }
+
+extern "C" int gecm_dev_multi_rows_ready(gecm_dev *d) { return d->multi && d->mrow_groups != 0 && d->mrow_groups == d->ngroups; }
 
 extern "C" int gecm_dev_unit_rows_ready(gecm_dev *d)
 {
@@ -308,6 +334,7 @@ extern "C" void gecm_dev_close(gecm_dev *d)
     (void)hipFree(d->dModQ);
     (void)hipFree(d->dRowC);
     (void)hipFree(d->dURowC);
+    (void)hipFree(d->dMRowC);
     (void)hipFree(d->dKeep);
     (void)hipFree(d->dSteps);
     (void)hipFree(d->dFlags);
@@ -655,7 +682,9 @@ extern "C" int gecm_dev_fform_generic_limbs(int nl)
 
 extern "C" void gecm_dev_set_fform(gecm_dev *d, int form) { d->fform = form == 2 ? 2 : form > 0 ? 1 : form < 0 ? -1 : 0; }
 
-extern "C" int gecm_dev_stage1(gecm_dev *d, int lanes_per_curve)
+/* multi_rows: the 32-lane layout on a multi-modulus batch of either packing (gecm_dev_stage1_multi_rows);
+ * lanes_per_curve is then not looked at. */
+static int stage1_run(gecm_dev *d, int lanes_per_curve, bool multi_rows)
 {
     HIPCHK(hipSetDevice(d->device));
     if (ready(d, "gecm_dev_stage1", false)) return -2;
@@ -663,9 +692,16 @@ extern "C" int gecm_dev_stage1(gecm_dev *d, int lanes_per_curve)
         g_err = "gecm_dev_stage1: no tape";
         return -2;
     }
-    int lanes = lanes_per_curve ? lanes_per_curve : gecm_dev_auto_lanes(d);
+    int lanes = multi_rows ? 32 : lanes_per_curve ? lanes_per_curve : gecm_dev_auto_lanes(d);
     char nm[96];   // the kernel's name as rocprofv3 prints it
-    if (d->multi && d->lane_packed) {
+    if (multi_rows) {
+        if (!gecm_dev_multi_rows_ready(d)) {
+            g_err = "gecm_dev_stage1_multi_rows: the 32-lane kernel has no constants for this batch's moduli "
+                    "(gecm_dev_set_multi_rowconst)";
+            return -2;
+        }
+        snprintf(nm, sizeof nm, "k_stage1_row_multi<%d, %d>", d->mrow_nq, d->mrow_rows);
+    } else if (d->multi && d->lane_packed) {
         if (lanes_per_curve > 1) {
             g_err = "gecm_dev_stage1: a lane-packed multi-modulus batch runs with one lane per curve";
             return -2;
@@ -711,7 +747,13 @@ extern "C" int gecm_dev_stage1(gecm_dev *d, int lanes_per_curve)
     for (size_t cut = 0; cut + 1 < d->tape_cuts.size(); cut++) {
         const uint32_t *tp = d->dTape + d->tape_cuts[cut] / 4;
         const uint32_t tl = (uint32_t)(d->tape_cuts[cut + 1] - d->tape_cuts[cut]);
-        if (lanes == 32) {
+        if (multi_rows) {
+            if (gecm_launch_stage1_row_multi(d->stream, d->mrow_nq, d->mrow_rows, tp, tl, d->dX, d->dZ, d->dS, d->stride,
+                                             (uint32_t)d->nl, d->dMRowC, mc.curve_group, mc.block_group)) {
+                g_err = "gecm_dev_stage1_multi_rows: no 32-lane kernel for this limb count";
+                return -2;
+            }
+        } else if (lanes == 32) {
             if (gecm_launch_stage1_row(d->stream, d->row_nq, d->row_rows, tp, tl, d->dX, d->dZ, d->dS, d->stride,
                                        (uint32_t)d->nl, d->dRowC, d->mod.rho, row_a_lds(d))) {
                 g_err = "gecm_dev_stage1: no 32-lane kernel for this limb count";
@@ -727,6 +769,10 @@ extern "C" int gecm_dev_stage1(gecm_dev *d, int lanes_per_curve)
     d->timed = true;
     return 0;
 }
+
+extern "C" int gecm_dev_stage1(gecm_dev *d, int lanes_per_curve) { return stage1_run(d, lanes_per_curve, false); }
+
+extern "C" int gecm_dev_stage1_multi_rows(gecm_dev *d) { return stage1_run(d, 0, true); }
 
 /* P-1 / P+1 stage 1: the tape on one residue per lane, cut into launches as gecm_dev_stage1 cuts it
  * (between two prac() calls only A is live here too).  method: GECM_UNIT_PM1 or GECM_UNIT_PP1. */

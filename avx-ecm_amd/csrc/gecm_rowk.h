@@ -30,6 +30,20 @@ int gecm_launch_stage1_row(void *stream, int nq, int rows, const uint32_t *tape,
                            const uint32_t *S, size_t stride, uint32_t nl, const uint32_t *rc, uint32_t rho_n,
                            bool a_lds);
 
+/* 32 lanes per curve on a multi-modulus batch (k_stage1_row_multi): the same kernel body, DPP form, with
+ * the constants of every curve taken from a table.  rc = device table of one set per modulus, GECM_MROW_KINDS x
+ * GECM_ROW_WORDS words each: the GECM_ROW_KINDS arrays above for that modulus ([0] N' = m*N with R' >= 32 N', [1] N,
+ * [2] entry factor, [3] R mod N, [4] K'), then [5] word 0: -N^-1 mod 2^28 (the exit multiply's rho).  Not the method
+ * kernel's set below: its N'' only has R' > 28 N''.
+ * A curve takes set curve_group[curve] (lane packing) or block_group[curve / 64] (wave packing); one of the two is
+ * given, with an entry below the table's size for every position of the stride, padding included.
+ * Leaves lazy values in X, Z (run canon afterwards).  Returns -1 if (nq, rows) is not built or both tables are NULL. */
+#define GECM_MROW_KINDS (GECM_ROW_KINDS + 1)
+#define GECM_MROW_SET (GECM_MROW_KINDS * GECM_ROW_WORDS)
+int gecm_launch_stage1_row_multi(void *stream, int nq, int rows, const uint32_t *tape, uint32_t tape_len, uint32_t *X,
+                                 uint32_t *Z, const uint32_t *S, size_t stride, uint32_t nl, const uint32_t *rc,
+                                 const uint32_t *curve_group, const uint32_t *block_group);
+
 /* 16 lanes per residue: P-1 and P+1 stage 1 with one residue per DPP row (k_unit_row).  The kernel works
  * modulo N'' = (m + t 2^28) N, the multiple of N that is -1 modulo 2^28 AND fills the row: N'' >= 2^(28 (rows - 1) + 20),
  * so that the top limb of a value tells its quotient by N'' (the reduction after a P+1 subtraction), and

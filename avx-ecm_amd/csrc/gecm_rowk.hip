@@ -49,6 +49,39 @@ extern "C" int gecm_launch_stage1_row(void *stream, int nq, int rows, const uint
     return -1;
 }
 
+// The same body on a multi-modulus batch, DPP form: the constants come from the table of the batch's
+// moduli through the curve's group, which is uniform over the two rows of a curve (with lane packing the two curves of
+// a wavefront may be on different numbers), and rho of N from the set instead of the argument list.  The workgroups and
+// the grid of k_stage1_row.
+template <int NQ, int ROWS>
+__global__ void __launch_bounds__(64 * GECM_ROW_WG_WAVES, 2)
+k_stage1_row_multi(const uint32_t *__restrict__ tape, uint32_t tape_len, uint32_t *__restrict__ X, uint32_t *__restrict__ Z,
+                   const uint32_t *__restrict__ S, size_t stride, uint32_t nl, const uint32_t *__restrict__ rc,
+                   const uint32_t *__restrict__ curve_group, const uint32_t *__restrict__ block_group)
+{
+    const uint32_t cidx = (blockIdx.x * blockDim.x + threadIdx.x) >> 5;      // < stride: the grid is stride / 8 blocks
+    const uint32_t g = curve_group ? curve_group[cidx] : block_group[cidx >> 6];
+    const uint32_t *set = rc + (size_t)g * GECM_MROW_SET;
+    stage1_row<NQ, ROWS, false>(tape, tape_len, X, Z, S, stride, nl, set, set[GECM_ROW_KINDS * GECM_ROW_WORDS]);
+}
+
+extern "C" int gecm_launch_stage1_row_multi(void *stream, int nq, int rows, const uint32_t *tape, uint32_t tape_len,
+                                            uint32_t *X, uint32_t *Z, const uint32_t *S, size_t stride, uint32_t nl,
+                                            const uint32_t *rc, const uint32_t *curve_group, const uint32_t *block_group)
+{
+    if (!curve_group && !block_group) return -1;
+    const dim3 grid((unsigned)(stride / (2 * GECM_ROW_WG_WAVES))), block(64 * GECM_ROW_WG_WAVES);   // stride: a multiple of 64
+#define GECM_MROW_LAUNCH(q, r)                                                                                              \
+    if (nq == q && rows == r) {                                                                                             \
+        hipLaunchKernelGGL((k_stage1_row_multi<q, r>), grid, block, 0, (hipStream_t)stream, tape, tape_len, X, Z, S,        \
+                           stride, nl, rc, curve_group, block_group);                                                       \
+        return 0;                                                                                                           \
+    }
+    GECM_ROW_SHAPES(GECM_MROW_LAUNCH)
+#undef GECM_MROW_LAUNCH
+    return -1;
+}
+
 // One residue per row, four per wavefront: P-1 and P+1 stage 1 for small method batches (gecm_row.hpp, unit_row).
 // Workgroups of four wavefronts for the reason above.  The method is wave-uniform; the constants come from the table of
 // the batch's moduli through the position's group, which is uniform over a row (group 0 on a single-N context).

@@ -299,6 +299,19 @@ static int cli_multi_subseq(void)
     return 1;
 }
 
+/* Stage 1 of the curves of the multi-modulus passes of -f, -r and -x with 32 lanes per curve (include/gecm.h
+ * gecm_set_multi_rows): GECM_MULTI_ROWS=on|auto|off, off when unset.  The files are byte for byte the
+ * same whatever the value.  Returns the setting, or 2 (no setting has that value) after printing why not. */
+static int cli_multi_rows(void)
+{
+    const char *s = getenv("GECM_MULTI_ROWS");
+    if (!s || !strcmp(s, "off")) return GECM_MULTI_ROWS_OFF;
+    if (!strcmp(s, "on")) return GECM_MULTI_ROWS_ON;
+    if (!strcmp(s, "auto")) return GECM_MULTI_ROWS_AUTO;
+    printf("GECM_MULTI_ROWS must be on, auto or off\n");
+    return 2;
+}
+
 /* Lanes per residue in stage 1 of the -m pm1|pp1 passes (include/gecm.h gecm_set_method_lanes):
  * GECM_METHOD_LANES=1|16|auto, 1 when unset.  The files are byte for byte the same whatever the value.  Returns the
  * setting, or 0 (no setting has that value) after printing why not. */
@@ -1165,6 +1178,7 @@ static int multi_run(const char **ns, const char *const *logs, size_t n, run_t *
     if (rc == 0) rc = set_curve_build(mc);
     if (rc == 0) rc = gecm_set_multi_packing(mc, packing);
     if (rc == 0) rc = gecm_set_stage2_subseq(mc, cli_multi_subseq());
+    if (rc == 0) rc = gecm_set_multi_rows(mc, cli_multi_rows());
     if (rc == 0 && rl) {
         gecm_config cfg;
         gecm_get_config(mc, &cfg);
@@ -1204,9 +1218,11 @@ static int multi_run(const char **ns, const char *const *logs, size_t n, run_t *
     if (!rc) {
         char s2[48] = "";
         if (R->do_stage2) snprintf(s2, sizeof s2, " and stage 2 (K = %d)", gecm_get_stage2_subseq(mc, NULL));
-        printf("multi-modulus pass: %zu inputs, %zu curves%s, %s-packed, %s%s, %1.4f seconds of kernels after stage 1\n", n,
+        /* (stage 1 in the row layout is named; without GECM_MULTI_ROWS the line is what it was) */
+        printf("multi-modulus pass: %zu inputs, %zu curves%s, %s-packed, %s%s%s, %1.4f seconds of kernels after stage 1\n", n,
                rl ? total : count[0], rl ? " in all" : " each", gecm_get_multi_packing(mc) == GECM_PACK_LANE ? "lane" : "wave",
-               !rl ? "stage 1" : R->extend ? "stage 1 extended" : "resumed after stage 1", s2, gecm_last_kernel_ms(mc) / 1000.0);
+               !rl ? "stage 1" : R->extend ? "stage 1 extended" : "resumed after stage 1",
+               gecm_get_lanes_per_curve(mc) == 32 ? " with 32 lanes per curve" : "", s2, gecm_last_kernel_ms(mc) / 1000.0);
     }
     gecm_destroy(mc);
     free(rx); free(rz);
@@ -1244,7 +1260,7 @@ static int run_file(int argc, char **argv)
                                "       (one input expression per line; blank lines and lines starting with # are skipped)\n";
     if (argc < 5) { printf("%s", usage); return 1; }
     const int packing = cli_packing();
-    if (packing < 0 || cli_multi_subseq() == 1) return 1;
+    if (packing < 0 || cli_multi_subseq() == 1 || cli_multi_rows() == 2) return 1;
     FILE *f = fopen(argv[2], "r");
     if (!f) { printf("cannot read %s\n%s", argv[2], usage); return 1; }
     size_t ninputs = 0, cap_in = 0;
@@ -1402,7 +1418,7 @@ static int run_resume(int argc, char **argv, int extend, int gmp)
     const char *usage = gmp ? (extend ? gmp_extend_usage : gmp_resume_usage) : extend ? extend_usage : resume_usage;
     if (argc < 4) { printf("%s", usage); return 1; }
     const int packing = cli_packing();
-    if (packing < 0 || cli_multi_subseq() == 1) return 1;
+    if (packing < 0 || cli_multi_subseq() == 1 || cli_multi_rows() == 2) return 1;
     FILE *f = fopen(argv[2], "r");
     if (!f) { printf("cannot read %s\n%s", argv[2], usage); return 1; }
     /* the run's arguments through the one parser: curves B1 threads [B2], one thread, the curve count per group */

@@ -156,6 +156,8 @@ struct gecm_ctx {
     int method_s2;           /* gecm_set_method_stage2: the stage-2 calls work on a method batch; kept across builds */
     int method_lanes;        /* gecm_set_method_lanes: 0 (as 1), 1, 16 or GECM_METHOD_LANES_AUTO; kept across builds */
     int urow_state;          /* the 16-lane method kernel's constants: 0 not made yet, 1 on the device, -1 none (unit_rows_setup) */
+    int multi_rows;          /* gecm_set_multi_rows: GECM_MULTI_ROWS_OFF, _ON or _AUTO; kept across builds */
+    int mrow_state;          /* the 32-lane kernel's constants for every modulus of a multi-modulus context, as urow_state (multi_rows_setup) */
 };
 
 /* what a multi-modulus context cannot do: the reference radix (NWORDS) differs from modulus to modulus, and the L0
@@ -519,6 +521,76 @@ static int method_lanes_for_launch(gecm_ctx *c)
     set_err("gecm_stage1_extend: the 16-lane method kernel has no constants for this context's numbers "
             "(gecm_set_method_lanes)");
     return 0;
+}
+
+/* ---- curve batches of a multi-modulus context in the 32-lane row layout ---------- */
+/* The 32-lane stage-1 kernel's constant sets on the device, one for every modulus of a multi-modulus context in the
+ * order gecm_dev_set_groups names them: what row_setup makes for a single N, and that modulus's rho.  Made once, when a
+ * launch first wants them.  1 if the device has them; 0 if some number of the context has none (remembered: mrow_state
+ * -1); -2 if host memory, -1 if the upload failed this time (not remembered: the next launch tries again). */
+static int multi_rows_setup(gecm_ctx *c)
+{
+    if (c->mrow_state) return c->mrow_state > 0;
+    int nq, L;
+    gecm_row_shape(c->mod.nl, &nq, &L);
+    if (!c->multi || nq > GECM_ROW_MAXNQ) { c->mrow_state = -1; return 0; }
+    uint32_t *w = (uint32_t *)calloc(c->ngroups * GECM_MROW_SET, sizeof(uint32_t));
+    if (!w) return -2;
+    for (size_t g = 0; g < c->ngroups; g++) {
+        if (!row_consts(&c->grp[g], c->mod.nl, L, w + g * GECM_MROW_SET, NULL)) { free(w); c->mrow_state = -1; return 0; }
+        w[g * GECM_MROW_SET + GECM_ROW_KINDS * GECM_ROW_WORDS] = c->grp[g].rho28;
+    }
+    const int failed = gecm_dev_set_multi_rowconst(c->dev, nq, L, (uint32_t)c->ngroups, w);
+    free(w);
+    if (failed) return -1;
+    c->mrow_state = 1;
+    return 1;
+}
+
+/* Rows up to 32 positions per compute unit, up to 64 at 37 limbs, the default layout beyond: read off the table of
+ * DESIGN.md §23 (profiles/multi_rows/time_rows_on.txt against time_parent_default.txt, one MI355X of 256 compute units,
+ * gecm_stage1(1e5), kernel time with the canon pass, 32 numbers).  The default launch (k_stage1_pair_multi, k_stage1_lane)
+ * takes the same time up to 32,768 positions; the row launch is flat up to 1,024 and grows with the batch from 4,096 on.
+ * 15 limbs, wave packing: 240 against 771 ms at 4,096 positions, 439 against 773 at 8,192, and lost at 16,384 (806 against
+ * 779).  15 limbs, lane packing: 240 against 1,405 ms at 4,096, still 806 against 1,412 at 16,384, lost at 32,768.  37
+ * limbs: 932 against 4,182 ms at 4,096, 3,453 against 4,253 at 16,384, lost at 32,768 (6,804 against 4,406).  Every
+ * difference named is far above the min - max spread of both series (under 25 ms).  The rule does not know the packing,
+ * so at 15 limbs it stops where wave packing stops winning.  Only 15 and 37 limbs were measured: the limb counts below
+ * 15 (8 to 14) and between 15 and 37 take the smaller bound unmeasured. */
+int gecm_multi_rows_auto(size_t positions, int dev_limbs, int cus)
+{
+    if (positions == 0 || cus <= 0) return 0;
+    return positions <= (size_t)(dev_limbs >= 37 ? 64 : 32) * (size_t)cus;
+}
+
+int gecm_set_multi_rows(gecm_ctx *c, int rows)
+{
+    if (!c || (rows != GECM_MULTI_ROWS_OFF && rows != GECM_MULTI_ROWS_ON && rows != GECM_MULTI_ROWS_AUTO)) {
+        set_err("gecm_set_multi_rows: needs a context and GECM_MULTI_ROWS_OFF, GECM_MULTI_ROWS_ON or GECM_MULTI_ROWS_AUTO");
+        return GECM_ERR_ARG;
+    }
+    if (!c->multi) { set_err("gecm_set_multi_rows: not a multi-modulus context (gecm_create_multi)"); return GECM_ERR_STATE; }
+    c->multi_rows = rows;
+    return GECM_OK;
+}
+
+int gecm_get_multi_rows(const gecm_ctx *c) { return c ? c->multi_rows : GECM_MULTI_ROWS_OFF; }
+
+/* does the next stage-1 launch of the curve batch run the row layout?  1 or 0, or -1 with the error text set (ON
+ * without constants); fn names the call in that text.  The setting has a say only while gecm_set_lanes_per_curve is 0. */
+static int multi_rows_for_launch(gecm_ctx *c, const char *fn)
+{
+    if (!c->multi || c->method || c->multi_rows == GECM_MULTI_ROWS_OFF || c->lanes_per_curve) return 0;
+    if (c->multi_rows == GECM_MULTI_ROWS_AUTO &&
+        !gecm_multi_rows_auto(gecm_dev_stride(c->dev), c->mod.nl, gecm_dev_cus(c->dev)))
+        return 0;
+    const int have = multi_rows_setup(c);
+    if (have > 0) return 1;
+    if (c->multi_rows == GECM_MULTI_ROWS_AUTO) return 0;
+    if (have == -2) set_err("%s: out of memory for the 32-lane kernel's constants", fn);
+    else if (have < 0) set_err("%s: the 32-lane kernel's constants could not be put on the device: %s", fn, gecm_dev_error());
+    else set_err("%s: the 32-lane kernel has no constants for this context's numbers (gecm_set_multi_rows)", fn);
+    return -1;
 }
 
 int gecm_create(gecm_ctx **out, int device, const char *n_str, int digitbits)
@@ -1212,6 +1284,8 @@ static int stage1_launch(gecm_ctx *c, const tape_key *key, uint64_t B1, int firs
 {
     const int unit_lanes = c->method ? method_lanes_for_launch(c) : 1;
     if (!unit_lanes) return GECM_ERR_STATE;          /* before anything of the batch has changed */
+    const int multi_rows = multi_rows_for_launch(c, key->kind == 1 ? "gecm_stage1_extend" : "gecm_stage1");
+    if (multi_rows < 0) return GECM_ERR_STATE;
     int rc = tape_for(c, key);
     if (rc) return rc;
     const int idle = key->kind == 1 && c->tape.len == 0;
@@ -1238,6 +1312,9 @@ static int stage1_launch(gecm_ctx *c, const tape_key *key, uint64_t B1, int firs
             set_err("%s", gecm_dev_error());
             return GECM_ERR_DEVICE;
         }
+    } else if (multi_rows) {         /* a multi-modulus context has no twin */
+        c->twin.ran_last = 0;
+        if (gecm_dev_stage1_multi_rows(c->dev)) { set_err("%s", gecm_dev_error()); return GECM_ERR_DEVICE; }
     } else {
     /* For a batch small enough for the eight-lane layout (generic moduli only) that layout beats the special
      * multiply in its two-lane form: 1.5x against 1.4x at 15 limbs, 2.2-2.4x at 30-37 limbs. */

@@ -231,6 +231,20 @@ def method_lanes_auto(positions, limbs, cus):
     return lib.gecm_method_lanes_auto(positions, limbs, cus)
 
 
+# stage 1 of the curve batches of a multi-modulus context with 32 lanes per curve: opt-in per context
+MULTI_ROWS_OFF, MULTI_ROWS_ON, MULTI_ROWS_AUTO = 0, 1, -1
+_MULTI_ROWS = {"off": MULTI_ROWS_OFF, "on": MULTI_ROWS_ON, "auto": MULTI_ROWS_AUTO}
+_sig("gecm_set_multi_rows", c_int, c_void_p, c_int)
+_sig("gecm_get_multi_rows", c_int, c_void_p)
+_sig("gecm_multi_rows_auto", c_int, c_size_t, c_int, c_int)
+EXPORTS += ["gecm_set_multi_rows", "gecm_get_multi_rows", "gecm_multi_rows_auto"]
+
+
+def multi_rows_auto(positions, limbs, cus):
+    """0 or 1: whether "auto" runs a multi-modulus curve batch of that many (padded) positions in the row layout"""
+    return lib.gecm_multi_rows_auto(positions, limbs, cus)
+
+
 class GecmError(RuntimeError):
     pass
 
@@ -841,6 +855,16 @@ class MultiEngine(Engine):
     def packing(self):
         """what the last build used"""
         return ["wave", "lane"][_chk(lib.gecm_get_multi_packing(self._h), "gecm_get_multi_packing")]
+
+    def set_rows(self, rows):
+        """stage 1 of this context's curve batches with 32 lanes per curve: "off" (the default), "on" or "auto"
+        (DESIGN.md §23); holds across builds, takes effect at the next stage-1 launch, and only while
+        set_lanes_per_curve is 0"""
+        return _chk(lib.gecm_set_multi_rows(self._h, _MULTI_ROWS.get(rows, 2) if isinstance(rows, str) else rows),
+                    "gecm_set_multi_rows")
+
+    def rows(self):
+        return {v: k for k, v in _MULTI_ROWS.items()}[lib.gecm_get_multi_rows(self._h)]
 
     def _line_moduli(self):
         return self.ns

@@ -625,6 +625,33 @@ int gecm_set_method_lanes(gecm_ctx *ctx, int lanes);   /* 1 (default), 16, GECM_
 int gecm_get_method_lanes(const gecm_ctx *ctx);
 int gecm_method_lanes_auto(size_t positions, int dev_limbs, int cus);   /* 1 or 16; pure host code */
 
+/* ---- curve batches of a multi-modulus context with 32 lanes per curve, for small batches ----
+ * A multi-modulus batch is small by construction, and gecm_set_lanes_per_curve gives it 1 or 2 lanes per curve.  With
+ * rows on, stage 1 of its curves runs in the layout small single-N batches run in: X and Z of a curve on two DPP rows,
+ * the limbs of a residue over the 16 lanes of a row (kernel k_stage1_row_multi<NQ, ROWS>), every curve with the
+ * constants of its own number.
+ * gecm_set_multi_rows(ctx, rows): GECM_MULTI_ROWS_OFF (the default), _ON or _AUTO; GECM_ERR_ARG for another value or a
+ *   NULL context, GECM_ERR_STATE on a single-N context.  gecm_get_multi_rows reads the setting (OFF for NULL).  It holds
+ *   across builds and takes effect at the next gecm_stage1, gecm_stage1_range, gecm_stage1_extend or
+ *   gecm_stage1_extend_segment of a batch of curves; method batches are not touched (gecm_set_method_lanes).  It applies
+ *   only while gecm_set_lanes_per_curve is 0: an explicit 1 or 2 runs what it runs without the setting, lane packing's
+ *   refusal of 2 included.  With OFF every call answers what it answered before the setting existed.
+ * With ON those launches run k_stage1_row_multi on both packings (lane packing keeps its 415-bit limit on the context):
+ *   gecm_get_lanes_per_curve answers 32, gecm_last_kernel_name "k_stage1_row_multi<..>".  Every residue, save and resume
+ *   line, flag, factor, failure record, statistic and stage-2 result is the one OFF gives.  If the kernel's constants
+ *   cannot be set up for one of the context's numbers the launch answers GECM_ERR_STATE with a text, and the batch is as
+ *   it was.
+ * With AUTO a launch runs rows where gecm_multi_rows_auto(padded positions, device limbs, compute units) says 1 and the
+ *   constants exist, and what OFF runs otherwise.
+ * gecm_multi_rows_auto: 0 or 1 for a batch of that many positions (padding included: gecm_multi_positions) on a context
+ *   of dev_limbs limbs and a device of cus compute units; pure host code, the one place the rule lives. */
+#define GECM_MULTI_ROWS_OFF 0
+#define GECM_MULTI_ROWS_ON 1
+#define GECM_MULTI_ROWS_AUTO (-1)
+int gecm_set_multi_rows(gecm_ctx *ctx, int rows);
+int gecm_get_multi_rows(const gecm_ctx *ctx);
+int gecm_multi_rows_auto(size_t positions, int dev_limbs, int cus);   /* 0 or 1; pure host code */
+
 #ifdef __cplusplus
 }
 #endif

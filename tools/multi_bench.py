@@ -97,8 +97,8 @@ def run(bits, count, curves, b1):
     return out
 
 
-def run_dense(bits, real, cpn, packings, b1, b2):
-    """wave against lane packing: `real` curves, cpn per number"""
+def run_dense(bits, real, cpn, packings, b1, b2, rows="off"):
+    """wave against lane packing: `real` curves, cpn per number; rows: MultiEngine.set_rows"""
     import statistics
     import pyecm
     rnd = random.Random(bits * 1000 + cpn)
@@ -111,7 +111,9 @@ def run_dense(bits, real, cpn, packings, b1, b2):
     for packing in packings:
         eng = pyecm.MultiEngine(ns)
         eng.set_packing(packing)
-        out["dev_limbs"] = eng.cfg.dev_limbs
+        if rows != "off":
+            eng.set_rows(rows)
+        out["dev_limbs"], out["rows"] = eng.cfg.dev_limbs, rows
         t = time.perf_counter()
         eng.build_curves(sig, which)
         build_s = time.perf_counter() - t
@@ -196,6 +198,7 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--stage2", action="store_true")
     ap.add_argument("--subseq", nargs="+", default=["1", "auto"])
+    ap.add_argument("--rows", choices=["off", "on", "auto"], default="off", help="with --curves-per-number: stage 1 in the row layout")
     a = ap.parse_args()
     if a.out is None:
         a.out = os.path.join(ROOT, "profiles", "subseq" if a.stage2 else "dense" if a.curves_per_number else "multi")
@@ -210,9 +213,10 @@ def main():
     if a.curves_per_number:
         for bits in a.bits:
             for cpn in a.curves_per_number:
-                r = run_dense(bits, a.real_curves, cpn, a.packing, a.b1, a.b2)
+                r = run_dense(bits, a.real_curves, cpn, a.packing, a.b1, a.b2, a.rows)
                 print(json.dumps(r), flush=True)
-                with open(os.path.join(a.out, "dense_%d_c%d%s.json" % (bits, cpn, "_s2" if a.b2 else "")), "w") as f:
+                name = "dense_%d_c%d%s%s.json" % (bits, cpn, "_s2" if a.b2 else "", "" if a.rows == "off" else "_rows_" + a.rows)
+                with open(os.path.join(a.out, name), "w") as f:
                     json.dump(r, f, indent=1)
         return
     for bits in a.bits:
