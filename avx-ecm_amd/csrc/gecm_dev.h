@@ -29,6 +29,18 @@ const int *gecm_dev_supported_nl(void);
 /* m: the constants of the context's modulus at nl limbs (gecm_ops.h), copied before it returns.  multi != 0: a
  * multi-modulus context, m the modulus gecm_get_config reports; see gecm_dev_set_groups. */
 int gecm_dev_open(gecm_dev **out, int device, int nl, const gecm_devmod *m, int multi);
+/* ---- a wide context: nl = 40, 43 or 47, limb counts that have the 32-lane stage-1 kernel of
+ * gecm_launch_stage1_row_wide and no other.  It holds no modulus constants but those of gecm_dev_set_rowconst (rho is the
+ * exit multiply's -N^-1 mod 2^28), and serves gecm_dev_close, _device_name, _memory, _batch_bytes (stage-1 arrays; 0
+ * with npb != 0), _resize, _stride, _upload (limbs the host has put into Montgomery form), _set_tape, _set_rowconst,
+ * _stage1 (lanes 0 or 32: the row kernel per cut of the tape and NOTHING between or after the launches, the exit values
+ * stay lazy), _stage1_progress, _sync, _last_kernel_ms, _last_kernel, _last_lanes, _cus and gecm_dev_download_raw.
+ * Every other call answers -2 with a text and touches nothing. */
+int gecm_dev_open_wide(gecm_dev **out, int device, int nl, uint32_t rho);
+int gecm_dev_is_wide(const gecm_dev *d);
+/* X, Z limb for limb as the last kernel left them ([limb][curve]): of a wide context lazy values, limbs below
+ * 2^28 + 16 and the top limb whatever the value t + K' < R/16 + 2N needs.  Any context. */
+int gecm_dev_download_raw(gecm_dev *d, uint32_t *X, uint32_t *Z);
 void gecm_dev_close(gecm_dev *d);
 int gecm_dev_device_name(gecm_dev *d, char *buf, size_t len);
 int gecm_dev_memory(gecm_dev *d, uint64_t *free_bytes, uint64_t *total_bytes);   /* hipMemGetInfo */

@@ -106,6 +106,7 @@ struct gecm_dev {
     int last_lanes = 0;   // lanes per curve the last stage-1 launch used
     std::string last_kernel;   // and the kernel's name as rocprofv3 prints it
     // multi-modulus context (gecm_dev_open): one modulus per 64-curve block, constants in device memory
+    bool wide = false;    // gecm_dev_open_wide: no kernel tables (k1, k2 stay null), the 32-lane kernel of the wide shapes only
     bool multi = false;
     unsigned char *dGroups = nullptr; // one packed constant set per modulus (gecm_kernels_p1::pack_group)
     uint32_t *dBlockGroup = nullptr;  // modulus of every 64-curve block of the batch
@@ -129,6 +130,7 @@ struct gecm_dev {
 #define GECM_MANIFEST "unset"
 #endif
 extern "C" const char *gecm_manifest_rowk(void);
+extern "C" const char *gecm_manifest_rowk_wide(void);
 extern "C" const char *gecm_dev_manifest(void)
 {
     static std::string m;
@@ -140,7 +142,8 @@ extern "C" const char *gecm_dev_manifest(void)
                 if (k.empty()) k = h;
                 else if (k != h) mixed = true;
             }
-        std::string t = std::string("K:") + (mixed ? "MIXED" : k) + " R:" + gecm_manifest_rowk() + " D:" + GECM_MANIFEST;
+        std::string t = std::string("K:") + (mixed ? "MIXED" : k) + " R:" +
+                        (strcmp(gecm_manifest_rowk(), gecm_manifest_rowk_wide()) ? "MIXED" : gecm_manifest_rowk()) + " D:" + GECM_MANIFEST;
 #ifdef GECM_DEV_NL15
         t += " DEV-BUILD(416-bit class only)";
 #endif
@@ -179,6 +182,15 @@ static int ready(const gecm_dev *d, const char *fn, bool inverts)
     g_err = std::string(fn) + ": " + lacks;
     return -2;
 }
+
+// What a wide context (gecm_dev_open_wide) does not serve: everything that needs a kernel table of the limb count.
+#define REFUSE_WIDE(d, fn)                                                                    \
+    do {                                                                                      \
+        if ((d)->wide) {                                                                      \
+            g_err = fn ": not available on a wide context (gecm_dev_open_wide)";              \
+            return -2;                                                                        \
+        }                                                                                     \
+    } while (0)
 
 // A device array that only grows: room for `want` elements at *p, of which *cap says how many it has.  What it held is
 // not kept.
@@ -245,11 +257,51 @@ extern "C" int gecm_dev_open(gecm_dev **out, int device, int nl, const gecm_devm
     return 0;
 }
 
+// A wide context (gecm_dev.h): a limb count of the wide shapes, which kernels_for() does not know.  The stream, the
+// events and rho; the row kernel's constants come with gecm_dev_set_rowconst.
+extern "C" int gecm_dev_open_wide(gecm_dev **out, int device, int nl, uint32_t rho)
+{
+    bool shape = false;
+#define X(q, r) shape |= nl + 1 == r;
+    GECM_ROW_WIDE_SHAPES(X)
+#undef X
+    if (!shape || kernels_for(nl)) {
+        g_err = "gecm_dev_open_wide: " + std::to_string(nl) + " limbs is not a limb count of the wide shapes";
+        return -2;
+    }
+    int cnt = 0;
+    HIPCHK(hipGetDeviceCount(&cnt));
+    if (device < 0 || device >= cnt) {
+        g_err = "gecm_dev_open_wide: no such device";
+        return -2;
+    }
+    HIPCHK(hipSetDevice(device));
+    int cus = 0;
+    HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
+    gecm_dev *d = new gecm_dev;
+    d->device = device;
+    d->cus = cus;
+    d->nl = nl;
+    d->wide = true;
+    d->mod.rho = rho;
+    HIPCHK(hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking));
+    HIPCHK(hipEventCreate(&d->ev0));
+    HIPCHK(hipEventCreate(&d->ev1));
+    *out = d;
+    return 0;
+}
+
+extern "C" int gecm_dev_is_wide(const gecm_dev *d) { return d && d->wide; }
+
 extern "C" int gecm_dev_set_rowconst(gecm_dev *d, int nq, int rows, const uint32_t *words)
 {
     HIPCHK(hipSetDevice(d->device));
     if (nq < 1 || nq > GECM_ROW_MAXNQ || 16 * nq > GECM_ROW_WORDS || rows <= 16 * (nq - 1) || rows > 16 * nq) {
         g_err = "gecm_dev_set_rowconst: limbs per lane out of range";
+        return -2;
+    }
+    if (d->wide && (nq != 3 || rows != d->nl + 1)) {
+        g_err = "gecm_dev_set_rowconst: a wide context takes three limbs per lane and its own limb count + 1 rows";
         return -2;
     }
     if (!d->dRowC) HIPCHK(hipMalloc(&d->dRowC, GECM_ROW_KINDS * GECM_ROW_WORDS * sizeof(uint32_t)));
@@ -261,6 +313,7 @@ extern "C" int gecm_dev_set_rowconst(gecm_dev *d, int nq, int rows, const uint32
 
 extern "C" int gecm_dev_set_unit_rowconst(gecm_dev *d, int nq, int rows, uint32_t ngroups, const uint32_t *words)
 {
+    REFUSE_WIDE(d, "gecm_dev_set_unit_rowconst");
     HIPCHK(hipSetDevice(d->device));
     if (nq < 1 || nq > GECM_ROW_MAXNQ || 16 * nq > GECM_ROW_WORDS || rows <= 16 * (nq - 1) || rows > 16 * nq || !ngroups ||
         !words) {
@@ -281,6 +334,7 @@ extern "C" int gecm_dev_set_unit_rowconst(gecm_dev *d, int nq, int rows, uint32_
 
 extern "C" int gecm_dev_set_multi_rowconst(gecm_dev *d, int nq, int rows, uint32_t ngroups, const uint32_t *words)
 {
+    REFUSE_WIDE(d, "gecm_dev_set_multi_rowconst");
     HIPCHK(hipSetDevice(d->device));
     if (!d->multi || nq < 1 || nq > GECM_ROW_MAXNQ || 16 * nq > GECM_ROW_WORDS || rows <= 16 * (nq - 1) || rows > 16 * nq ||
         !ngroups || !words) {
@@ -382,8 +436,10 @@ extern "C" int gecm_dev_resize(gecm_dev *d, size_t ncurves)
         HIPCHK(hipMalloc(&d->dX, bytes));
         HIPCHK(hipMalloc(&d->dZ, bytes));
         HIPCHK(hipMalloc(&d->dS, bytes));
-        HIPCHK(hipMalloc(&d->dT0, bytes));
-        HIPCHK(hipMalloc(&d->dT1, bytes));
+        if (!d->wide) {                        // the scratch planes of the downloads: a wide context has none
+            HIPCHK(hipMalloc(&d->dT0, bytes));
+            HIPCHK(hipMalloc(&d->dT1, bytes));
+        }
         d->stride = stride;
     }
     d->ncurves = ncurves;
@@ -422,6 +478,7 @@ extern "C" int gecm_dev_upload(gecm_dev *d, const uint32_t *X, const uint32_t *Z
 
 extern "C" int gecm_dev_upload_xz(gecm_dev *d, const uint32_t *X, const uint32_t *Z)
 {
+    REFUSE_WIDE(d, "gecm_dev_upload_xz");
     HIPCHK(hipSetDevice(d->device));
     if (upload_soa(d, d->dX, X)) return -1;
     if (upload_soa(d, d->dZ, Z)) return -1;
@@ -433,6 +490,7 @@ extern "C" int gecm_dev_upload_xz(gecm_dev *d, const uint32_t *X, const uint32_t
 // to_mont kernel, through the scratch planes the downloads use.  The padding lanes get x = z = 1.
 extern "C" int gecm_dev_upload_plain(gecm_dev *d, const uint32_t *x, const uint32_t *z)
 {
+    REFUSE_WIDE(d, "gecm_dev_upload_plain");
     HIPCHK(hipSetDevice(d->device));
     if (ready(d, "gecm_dev_upload_plain", false)) return -2;
     if (upload_soa(d, d->dT0, x)) return -1;
@@ -452,6 +510,7 @@ extern "C" int gecm_dev_upload_plain(gecm_dev *d, const uint32_t *x, const uint3
 
 extern "C" int gecm_dev_download_s(gecm_dev *d, uint32_t *S)
 {
+    REFUSE_WIDE(d, "gecm_dev_download_s");
     HIPCHK(hipSetDevice(d->device));
     if (!d->stride) {
         g_err = "gecm_dev_download_s: no batch";
@@ -467,6 +526,7 @@ extern "C" float gecm_dev_last_build_ms(gecm_dev *d) { return d->build_ms; }
 
 extern "C" int gecm_dev_build(gecm_dev *d, const uint64_t *sigma, size_t count, uint32_t *flags)
 {
+    REFUSE_WIDE(d, "gecm_dev_build");
     HIPCHK(hipSetDevice(d->device));
     if (!d->stride || count != d->ncurves || !sigma || !flags) {
         g_err = "gecm_dev_build: no batch of that many curves (gecm_dev_resize)";
@@ -491,6 +551,7 @@ extern "C" int gecm_dev_build(gecm_dev *d, const uint64_t *sigma, size_t count, 
 
 extern "C" int gecm_dev_build_param(gecm_dev *d, const uint64_t *sigma, const uint8_t *param, size_t count, uint32_t *flags)
 {
+    REFUSE_WIDE(d, "gecm_dev_build_param");
     HIPCHK(hipSetDevice(d->device));
     if (!d->stride || count != d->ncurves || !sigma || !param || !flags) {
         g_err = "gecm_dev_build_param: no batch of that many curves (gecm_dev_resize)";
@@ -537,6 +598,7 @@ extern "C" int gecm_dev_build_param(gecm_dev *d, const uint64_t *sigma, const ui
 
 extern "C" int gecm_dev_normalize(gecm_dev *d, uint32_t *flags)
 {
+    REFUSE_WIDE(d, "gecm_dev_normalize");
     HIPCHK(hipSetDevice(d->device));
     if (ready(d, "gecm_dev_normalize", true)) return -2;
     if (!d->ncurves || !flags) {
@@ -558,6 +620,8 @@ extern "C" int gecm_dev_normalize(gecm_dev *d, uint32_t *flags)
 
 extern "C" int gecm_dev_fill_twin(gecm_dev *dst, gecm_dev *src)
 {
+    REFUSE_WIDE(dst, "gecm_dev_fill_twin");
+    REFUSE_WIDE(src, "gecm_dev_fill_twin");
     HIPCHK(hipSetDevice(src->device));
     if (dst->device != src->device || !src->stride || dst->stride != src->stride || dst->ncurves != src->ncurves ||
         src->multi || dst->multi) {
@@ -646,6 +710,7 @@ extern "C" int gecm_dev_auto_lanes(gecm_dev *d)
      * 14.4k); more limbs per lane up to 30 curves per CU and from 32 to 50 (831 bits: 31.9k against 29.7k curves/s at
      * 12,288), the eight-lane layout at exactly one or two wavefronts per SIMD in between (8192 curves: 32.7k against
      * 30.6k). */
+    if (d->wide) return 32;                           // the one layout it has
     if (!d->multi && !d->fform && d->row_nq && d->nl >= 10 && d->stride) {
         const size_t s = d->stride, cu = (size_t)d->cus;
         if (d->row_nq == 1 ? s <= cu * 56 : (s <= cu * 30 || (s > cu * 32 && s <= cu * 50))) return 32;
@@ -680,7 +745,7 @@ extern "C" int gecm_dev_fform_generic_limbs(int nl)
     return kt ? kt->p1()->fform_generic_limbs : -1;
 }
 
-extern "C" void gecm_dev_set_fform(gecm_dev *d, int form) { d->fform = form == 2 ? 2 : form > 0 ? 1 : form < 0 ? -1 : 0; }
+extern "C" void gecm_dev_set_fform(gecm_dev *d, int form) { if (d->wide) return; d->fform = form == 2 ? 2 : form > 0 ? 1 : form < 0 ? -1 : 0; }
 
 /* multi_rows: the 32-lane layout on a multi-modulus batch of either packing (gecm_dev_stage1_multi_rows);
  * lanes_per_curve is then not looked at. */
@@ -694,7 +759,14 @@ static int stage1_run(gecm_dev *d, int lanes_per_curve, bool multi_rows)
     }
     int lanes = multi_rows ? 32 : lanes_per_curve ? lanes_per_curve : gecm_dev_auto_lanes(d);
     char nm[96];   // the kernel's name as rocprofv3 prints it
-    if (multi_rows) {
+    if (d->wide) {
+        if (lanes != 32 || !d->row_nq) {
+            g_err = !d->row_nq ? "gecm_dev_stage1: the wide context has no constants (gecm_dev_set_rowconst)"
+                               : "gecm_dev_stage1: a wide context runs with 32 lanes per curve (0 or 32)";
+            return -2;
+        }
+        snprintf(nm, sizeof nm, "k_stage1_row<%d, %d, false>", d->row_nq, d->row_rows);
+    } else if (multi_rows) {
         if (!gecm_dev_multi_rows_ready(d)) {
             g_err = "gecm_dev_stage1_multi_rows: the 32-lane kernel has no constants for this batch's moduli "
                     "(gecm_dev_set_multi_rowconst)";
@@ -747,7 +819,15 @@ static int stage1_run(gecm_dev *d, int lanes_per_curve, bool multi_rows)
     for (size_t cut = 0; cut + 1 < d->tape_cuts.size(); cut++) {
         const uint32_t *tp = d->dTape + d->tape_cuts[cut] / 4;
         const uint32_t tl = (uint32_t)(d->tape_cuts[cut + 1] - d->tape_cuts[cut]);
-        if (multi_rows) {
+        if (d->wide) {
+            // nothing canonicalises between the launches or after them: the exit value of a launch is inside the contract
+            // of the next one's entry multiply, and the host reduces what it downloads
+            if (gecm_launch_stage1_row_wide(d->stream, d->row_rows, tp, tl, d->dX, d->dZ, d->dS, d->stride, (uint32_t)d->nl,
+                                            d->dRowC, d->mod.rho)) {
+                g_err = "gecm_dev_stage1: no 32-lane kernel for this limb count";
+                return -2;
+            }
+        } else if (multi_rows) {
             if (gecm_launch_stage1_row_multi(d->stream, d->mrow_nq, d->mrow_rows, tp, tl, d->dX, d->dZ, d->dS, d->stride,
                                              (uint32_t)d->nl, d->dMRowC, mc.curve_group, mc.block_group)) {
                 g_err = "gecm_dev_stage1_multi_rows: no 32-lane kernel for this limb count";
@@ -761,7 +841,7 @@ static int stage1_run(gecm_dev *d, int lanes_per_curve, bool multi_rows)
             }
         } else
             d->k1->stage1(d->stream, &mc, tp, tl, d->dX, d->dZ, d->dS, d->stride, d->dModQ, lanes, d->fform);
-        if (lanes >= 8) d->k1->canon(d->stream, &mc, d->dX, d->dZ, d->stride);   // the 8- and 32-lane kernels leave lazy values
+        if (lanes >= 8 && !d->wide) d->k1->canon(d->stream, &mc, d->dX, d->dZ, d->stride);   // the 8- and 32-lane kernels leave lazy values
         HIPCHK(hipEventRecord(d->cut_events[cut], d->stream));
     }
     HIPCHK(hipGetLastError());
@@ -772,7 +852,11 @@ static int stage1_run(gecm_dev *d, int lanes_per_curve, bool multi_rows)
 
 extern "C" int gecm_dev_stage1(gecm_dev *d, int lanes_per_curve) { return stage1_run(d, lanes_per_curve, false); }
 
-extern "C" int gecm_dev_stage1_multi_rows(gecm_dev *d) { return stage1_run(d, 0, true); }
+extern "C" int gecm_dev_stage1_multi_rows(gecm_dev *d)
+{
+    REFUSE_WIDE(d, "gecm_dev_stage1_multi_rows");
+    return stage1_run(d, 0, true);
+}
 
 /* P-1 / P+1 stage 1: the tape on one residue per lane, cut into launches as gecm_dev_stage1 cuts it
  * (between two prac() calls only A is live here too).  method: GECM_UNIT_PM1 or GECM_UNIT_PP1. */
@@ -782,6 +866,7 @@ extern "C" int gecm_dev_stage1_unit(gecm_dev *d, int method) { return gecm_dev_s
  * (k_unit_row), on every kind of context; it leaves lazy values, so canon follows every launch. */
 extern "C" int gecm_dev_stage1_unit_lanes(gecm_dev *d, int method, int lanes)
 {
+    REFUSE_WIDE(d, "gecm_dev_stage1_unit_lanes");
     HIPCHK(hipSetDevice(d->device));
     if (ready(d, "gecm_dev_stage1_unit", false)) return -2;
     if (!d->dTape) {
@@ -866,7 +951,21 @@ extern "C" float gecm_dev_last_kernel_ms(gecm_dev *d) { return d->last_ms; }
 
 extern "C" int gecm_dev_download_mont(gecm_dev *d, uint32_t *X, uint32_t *Z)
 {
+    REFUSE_WIDE(d, "gecm_dev_download_mont");
     HIPCHK(hipSetDevice(d->device));
+    if (download_soa(d, X, d->dX)) return -1;
+    if (download_soa(d, Z, d->dZ)) return -1;
+    HIPCHK(hipStreamSynchronize(d->stream));
+    return 0;
+}
+
+extern "C" int gecm_dev_download_raw(gecm_dev *d, uint32_t *X, uint32_t *Z)
+{
+    HIPCHK(hipSetDevice(d->device));
+    if (!d->stride) {
+        g_err = "gecm_dev_download_raw: no batch";
+        return -2;
+    }
     if (download_soa(d, X, d->dX)) return -1;
     if (download_soa(d, Z, d->dZ)) return -1;
     HIPCHK(hipStreamSynchronize(d->stream));
@@ -875,6 +974,7 @@ extern "C" int gecm_dev_download_mont(gecm_dev *d, uint32_t *X, uint32_t *Z)
 
 extern "C" int gecm_dev_download_plain(gecm_dev *d, uint32_t *x, uint32_t *z)
 {
+    REFUSE_WIDE(d, "gecm_dev_download_plain");
     HIPCHK(hipSetDevice(d->device));
     if (ready(d, "gecm_dev_download_plain", false)) return -2;
     gecm_modconst mc = modconst(d);
@@ -889,6 +989,7 @@ extern "C" int gecm_dev_download_plain(gecm_dev *d, uint32_t *x, uint32_t *z)
 extern "C" int gecm_dev_l0(gecm_dev *d, int op, const uint32_t *a, const uint32_t *b, uint32_t *c,
                            uint32_t *dd, size_t count, const uint32_t *fix)
 {
+    REFUSE_WIDE(d, "gecm_dev_l0");
     HIPCHK(hipSetDevice(d->device));
     if (d->multi) {
         g_err = "gecm_dev_l0: not available on a multi-modulus context";
@@ -910,6 +1011,7 @@ extern "C" int gecm_dev_l0(gecm_dev *d, int op, const uint32_t *a, const uint32_
 
 extern "C" int gecm_dev_l0_inv(gecm_dev *d, const uint32_t *a, uint32_t *inv, uint32_t *g, size_t count, const uint32_t *fix)
 {
+    REFUSE_WIDE(d, "gecm_dev_l0_inv");
     HIPCHK(hipSetDevice(d->device));
     if (d->multi || !d->mod.r3 || !fix) {
         g_err = "gecm_dev_l0_inv: needs a single-modulus context opened with its inversion constants (r3)";
@@ -936,6 +1038,7 @@ struct raw_planes {
 
 extern "C" int gecm_dev_l0_raw(gecm_dev *d, int op, int special, const uint32_t *a, const uint32_t *b, uint32_t *r, size_t count)
 {
+    REFUSE_WIDE(d, "gecm_dev_l0_raw");
     HIPCHK(hipSetDevice(d->device));
     const bool known = op == GECM_L0_MUL || op == GECM_L0_SQR || op == GECM_L0_ADD || op == GECM_L0_SUB || op == GECM_L0_CONDSUB;
     if (!known || !a || !r || !count) {
@@ -979,6 +1082,7 @@ extern "C" int gecm_dev_lane_packing_built(int nl)
 extern "C" int gecm_dev_set_groups(gecm_dev *d, uint32_t ngroups, const gecm_devmod *mods, const uint32_t *block_group,
                                    const uint32_t *curve_group)
 {
+    REFUSE_WIDE(d, "gecm_dev_set_groups");
     HIPCHK(hipSetDevice(d->device));
     const size_t blocks = d->stride / 64, gb = d->k1->group_bytes;
     if (!d->multi || !ngroups || !blocks || !mods || (!block_group && !curve_group)) {
@@ -1038,6 +1142,7 @@ extern "C" uint64_t gecm_dev_batch_bytes(gecm_dev *d, size_t curves, uint32_t np
 {
     const size_t stride = (curves + 63) / 64 * 64;
     const uint64_t coord = (uint64_t)d->nl * stride * sizeof(uint32_t);
+    if (d->wide) return npb ? 0 : 3 * coord;                  // X, Z, S; no stage 2
     uint64_t words = 5 + 1;                                   // X, Z, S, two scratch arrays; factor-scan gcds
     if (npb) {
         const uint64_t K = s2_subseq_for(d, stride), slices = s2_slices_for(d, stride);
@@ -1054,6 +1159,7 @@ extern "C" uint32_t gecm_dev_s2_subseq(gecm_dev *d) { return s2_subseq_for(d, d-
 
 extern "C" int gecm_dev_set_s2_subseq(gecm_dev *d, int k)
 {
+    REFUSE_WIDE(d, "gecm_dev_set_s2_subseq");
     if (k != 0 && k != -1 && (k < 1 || k > 32 || (k & (k - 1)))) return -2;
     d->s2_subseq_set = k;
     return 0;
@@ -1108,6 +1214,7 @@ static int unit_method_ok(const gecm_dev *d, const char *fn, int method)
 static int s2_init_any(gecm_dev *d, int method, const uint32_t *keep, size_t keep_words, uint32_t umax, uint32_t D,
                        uint32_t npb, uint32_t G, uint32_t ring_size, const uint32_t *tgt, const uint32_t *tgt_off, uint32_t K)
 {
+    REFUSE_WIDE(d, "gecm_dev_s2_init");
     HIPCHK(hipSetDevice(d->device));
     if (ready(d, "gecm_dev_s2_init", true)) return -2;
     const size_t coord = (size_t)d->nl * d->stride * sizeof(uint32_t);
@@ -1198,6 +1305,7 @@ extern "C" int gecm_dev_s2_init_unit(gecm_dev *d, int method, const uint32_t *ke
 static int s2_pair_any(gecm_dev *d, int method, const uint32_t *steps, uint32_t nsteps, uint32_t D, uint32_t G,
                        uint32_t ring_size, uint64_t A0, uint64_t tape_id)
 {
+    REFUSE_WIDE(d, "gecm_dev_s2_pair");
     HIPCHK(hipSetDevice(d->device));
     if (!d->dPbX || d->s2_G != G || d->s2_ring != ring_size || (ring_size & (ring_size - 1))) {
         g_err = "gecm_dev_s2_pair: stage-2 init has not run (or chunk/ring size changed)";
@@ -1254,6 +1362,7 @@ extern "C" int gecm_dev_s2_pair_unit(gecm_dev *d, int method, const uint32_t *st
 
 extern "C" int gecm_dev_s2_download(gecm_dev *d, uint32_t *acc, uint32_t *fail)
 {
+    REFUSE_WIDE(d, "gecm_dev_s2_download");
     HIPCHK(hipSetDevice(d->device));
     if (!d->dAcc) {
         g_err = "gecm_dev_s2_download: no stage-2 state";
@@ -1271,6 +1380,7 @@ extern "C" int gecm_dev_s2_download(gecm_dev *d, uint32_t *acc, uint32_t *fail)
 
 extern "C" int gecm_dev_gcd_scan(gecm_dev *d, int which, uint32_t *flags, uint32_t *g)
 {
+    REFUSE_WIDE(d, "gecm_dev_gcd_scan");
     HIPCHK(hipSetDevice(d->device));
     const uint32_t *src = which == 0 ? d->dZ : d->dAcc;
     if (!src) {
@@ -1292,6 +1402,7 @@ extern "C" int gecm_dev_gcd_scan(gecm_dev *d, int which, uint32_t *flags, uint32
 /* the factor scan of a P-1 / P+1 batch: gcd(x - off, N) for the residues in X, off = 1 or 2 */
 extern "C" int gecm_dev_gcd_scan_off(gecm_dev *d, uint32_t off, uint32_t *flags, uint32_t *g)
 {
+    REFUSE_WIDE(d, "gecm_dev_gcd_scan_off");
     HIPCHK(hipSetDevice(d->device));
     if (off != 1 && off != 2) {
         g_err = "gecm_dev_gcd_scan_off: the offset is 1 or 2";

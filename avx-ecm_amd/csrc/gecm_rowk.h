@@ -30,6 +30,15 @@ int gecm_launch_stage1_row(void *stream, int nq, int rows, const uint32_t *tape,
                            const uint32_t *S, size_t stride, uint32_t nl, const uint32_t *rc, uint32_t rho_n,
                            bool a_lds);
 
+/* The wide shapes: limb counts above gecm_launch.h's list, nl = 40, 43 and 47 (N up to 1115, 1199 and
+ * 1311 bits), which have no other kernel.  k_stage1_row<3, rows, false> alone is built for them (no multi-modulus form,
+ * no method kernel, no crossbar form), in an object of its own from gecm_rowk.hip.  The same arguments and the same lazy
+ * exit values as gecm_launch_stage1_row; nothing canonicalises them on the device: the entry multiply of the next launch
+ * takes them as they are, and the host reduces what it downloads.  Returns -1 if rows is not one of the list. */
+#define GECM_ROW_WIDE_SHAPES(X) X(3, 41) X(3, 44) X(3, 48)
+int gecm_launch_stage1_row_wide(void *stream, int rows, const uint32_t *tape, uint32_t tape_len, uint32_t *X, uint32_t *Z,
+                                const uint32_t *S, size_t stride, uint32_t nl, const uint32_t *rc, uint32_t rho_n);
+
 /* 32 lanes per curve on a multi-modulus batch (k_stage1_row_multi): the same kernel body, DPP form, with
  * the constants of every curve taken from a table.  rc = device table of one set per modulus, GECM_MROW_KINDS x
  * GECM_ROW_WORDS words each: the GECM_ROW_KINDS arrays above for that modulus ([0] N' = m*N with R' >= 32 N', [1] N,

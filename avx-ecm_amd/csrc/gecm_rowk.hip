@@ -1,6 +1,7 @@
 // gecm_rowk.hip — the 32-lanes-per-curve stage-1 kernels (gecm_row.hpp).  One translation unit for all limb
 // counts: the kernel is templated on the limbs per lane (NQ = 1, 2, 3 cover up to 16, 32, 48 limbs of 28 bits) and on
 // the rows of a multiply (ROWS = the limbs of N' = m*N); the limb count of the device buffers is a run-time argument.
+// With -DGECM_ROWK_WIDE the file compiles to the stage-1 kernels of the wide shapes and their launcher, nothing else.
 #include "gecm_row.hpp"
 #include <hip/hip_runtime.h>
 
@@ -21,6 +22,26 @@ k_stage1_row(const uint32_t *__restrict__ tape, uint32_t tape_len, uint32_t *__r
     stage1_row<NQ, ROWS, ALDS>(tape, tape_len, X, Z, S, stride, nl, rc, rho_n);
 }
 
+#ifdef GECM_ROWK_WIDE
+// The wide shapes (gecm_rowk.h) are an object of their own from this file (Makefile: gecm_rowk_wide.o):
+// three more NQ = 3 kernels next to the others would double the build time of the one object, and in a second
+// object they compile beside it.  Nothing but k_stage1_row<3, rows, false> is instantiated here.
+extern "C" int gecm_launch_stage1_row_wide(void *stream, int rows, const uint32_t *tape, uint32_t tape_len, uint32_t *X,
+                                           uint32_t *Z, const uint32_t *S, size_t stride, uint32_t nl, const uint32_t *rc,
+                                           uint32_t rho_n)
+{
+    const dim3 grid((unsigned)(stride / (2 * GECM_ROW_WG_WAVES))), block(64 * GECM_ROW_WG_WAVES);   // stride: a multiple of 64
+#define GECM_ROW_LAUNCH(q, r)                                                                                               \
+    if (rows == r) {                                                                                                        \
+        hipLaunchKernelGGL((k_stage1_row<q, r, false>), grid, block, 0, (hipStream_t)stream, tape, tape_len, X, Z, S,       \
+                           stride, nl, rc, rho_n);                                                                          \
+        return 0;                                                                                                           \
+    }
+    GECM_ROW_WIDE_SHAPES(GECM_ROW_LAUNCH)
+#undef GECM_ROW_LAUNCH
+    return -1;
+}
+#else
 /* rc = device array of GECM_ROW_KINDS x GECM_ROW_WORDS words (gecm_row.hpp).  Leaves lazy values (limbs < 2^28 + 4,
  * value < K + 2N) in X, Z: the caller runs k_canon afterwards.  a_lds: operand broadcasts through the LDS crossbar
  * (for launches of 3 or more wavefronts per SIMD), built for nq = 1 only.  (nq, rows) must be one of the built pairs —
@@ -112,8 +133,14 @@ extern "C" int gecm_launch_unit_row(void *stream, int nq, int rows, const uint32
     return -1;
 }
 
+#endif   // GECM_ROWK_WIDE
+
 // the hash of the sources this object was compiled from (Makefile: R_SHA)
 #ifndef GECM_MANIFEST
 #define GECM_MANIFEST "unset"
 #endif
+#ifdef GECM_ROWK_WIDE
+extern "C" const char *gecm_manifest_rowk_wide(void) { return GECM_MANIFEST; }
+#else
 extern "C" const char *gecm_manifest_rowk(void) { return GECM_MANIFEST; }
+#endif

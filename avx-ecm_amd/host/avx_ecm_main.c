@@ -887,11 +887,14 @@ static int parse_run(run_t *R, int argc, char **argv)
     return 0;
 }
 
-/* one context per GPU of a slot, on `modulus`, reporting against `report` if that is another number; 0 or 2 */
-static int make_contexts(gecm_ctx **ctx, int n, int devices, const char *modulus, const char *report)
+/* one context per GPU of a slot, on `modulus`, reporting against `report` if that is another number; 0 or 2.
+ * wide: a modulus above gecm_create's limit gets a wide context (include/gecm.h gecm_create_wide: stage 1 only), which
+ * the plain run takes; every other mode keeps gecm_create and its one-line refusal of such a number. */
+static int make_contexts(gecm_ctx **ctx, int n, int devices, const char *modulus, const char *report, int wide)
 {
     for (int g = 0; g < n; g++)
-        if (gecm_create(&ctx[g], g % devices, modulus, GECM_CLI_DIGITBITS) || (report && gecm_set_report_modulus(ctx[g], report)) ||
+        if ((wide ? gecm_create_wide : gecm_create)(&ctx[g], g % devices, modulus, GECM_CLI_DIGITBITS) ||
+            (report && gecm_set_report_modulus(ctx[g], report)) ||
             set_curve_build(ctx[g])) {
             fprintf(stderr, "%s\n", gecm_last_error());
             return 2;
@@ -1101,7 +1104,11 @@ static int run_single(int argc, char **argv)
         report = ndec;
     }
     static gecm_ctx *ctx[2][MAX_GPUS];
-    if (make_contexts(ctx[0], gpus, devices, modulus, report)) return 2;
+    if (make_contexts(ctx[0], gpus, devices, modulus, report, 1)) return 2;
+    /* a number above the ordinary contexts' limit: stage 1 and its files as for any input, no stage 2 */
+    const int wide = gecm_is_wide(ctx[0][0]);
+    const int skipped_stage2 = wide && R.do_stage2;
+    if (skipped_stage2) { R.do_stage2 = 0; R.B2 = R.B1; }
     uint64_t mem_free, budget;
     const size_t batches_per_pass = pass_batches(&R, ctx[0][0], gpus, per_gpu, &mem_free, &budget);
     const size_t npasses = (R.nbatches + batches_per_pass - 1) / batches_per_pass;
@@ -1113,7 +1120,7 @@ static int run_single(int argc, char **argv)
     /* (B1 in (99999989, 1e8] is one range WITH a checkpoint, ecm.c:1237: checkpoint.txt is appended to inside a pass's
      * turn on the GPU and put in order when the pass is written, which two passes in flight would do to each other) */
     const int slots = (npasses > 1 && R.nranges == 1 && R.B1 <= 99999989ULL && room && !getenv("GECM_NO_PIPELINE")) ? 2 : 1;
-    if (slots > 1 && make_contexts(ctx[1], gpus, devices, modulus, report)) return 2;
+    if (slots > 1 && make_contexts(ctx[1], gpus, devices, modulus, report, 1)) return 2;
     gecm_config cfg;
     gecm_get_config(ctx[0][0], &cfg);
     char devname[256];
@@ -1137,6 +1144,9 @@ static int run_single(int argc, char **argv)
         if (gecm_get_special_form(ctx[0][0], &fk, &fl) >= 1)
             printf("(batches that fill the GPU multiply modulo it with a special reduction, %d limbs; smaller ones by REDC)\n", fl);
     }
+    if (skipped_stage2)
+        printf("stage 2 is not run on this number (%d bits, a wide context of %d device limbs does stage 1 only): continue "
+               "with ecm -resume save_b1.txt\n", cfg.nbits, cfg.dev_limbs);
     printf("Initialization took %1.4f seconds.\n", now() - R.t_start);             /* main.c:776 */
     fflush(stdout);
 
@@ -1399,7 +1409,7 @@ static int resume_single(const rgroup_t *g, const rline_t *lines, char **rargv, 
         R.rd_rc = gecm_stage1_describe_range(R.B1, R.B2, (uint32_t)r, &R.rd[r]);
     if (R.rd_rc) { fprintf(stderr, "%s\n", gecm_last_error()); return 2; }
     static gecm_ctx *ctx[2][MAX_GPUS];
-    if (make_contexts(ctx[0], 1, 1, g->ndec, NULL)) return 2;
+    if (make_contexts(ctx[0], 1, 1, g->ndec, NULL, 0)) return 2;
     uint64_t mem_free, budget;
     const size_t batches_per_pass = pass_batches(&R, ctx[0][0], 1, 1, &mem_free, &budget);
     if (extend) printf("extending %zu curves on N = %s from B1 = %lu to %lu\n", g->count, g->ndec, (unsigned long)g->from, (unsigned long)R.B1);
@@ -1682,7 +1692,7 @@ static int run_param(int argc, char **argv)
     R.rd = (gecm_stage1_range_desc *)calloc((size_t)R.nranges, sizeof *R.rd);
     if (!R.rd) { fprintf(stderr, "out of memory\n"); return 2; }
     static gecm_ctx *ctx[2][MAX_GPUS];
-    if (make_contexts(ctx[0], 1, 1, ndec, NULL)) return 2;
+    if (make_contexts(ctx[0], 1, 1, ndec, NULL, 0)) return 2;
     uint64_t mem_free, budget;
     const size_t batches_per_pass = pass_batches(&R, ctx[0][0], 1, 1, &mem_free, &budget);
     printf("running %zu curves of PARAM %ld on N = %s in standard mode to B1 = %lu\n", R.nbatches * R.ub, param, ndec, (unsigned long)R.B1);

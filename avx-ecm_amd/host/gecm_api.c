@@ -157,6 +157,7 @@ struct gecm_ctx {
     int method_lanes;        /* gecm_set_method_lanes: 0 (as 1), 1, 16 or GECM_METHOD_LANES_AUTO; kept across builds */
     int urow_state;          /* the 16-lane method kernel's constants: 0 not made yet, 1 on the device, -1 none (unit_rows_setup) */
     int multi_rows;          /* gecm_set_multi_rows: GECM_MULTI_ROWS_OFF, _ON or _AUTO; kept across builds */
+    int wide;                /* gecm_create_wide made a wide context: stage 1 on the device, the rest on the host */
     int mrow_state;          /* the 32-lane kernel's constants for every modulus of a multi-modulus context, as urow_state (multi_rows_setup) */
 };
 
@@ -165,6 +166,15 @@ struct gecm_ctx {
 static int multi_refuse(const char *fn)
 {
     set_err("%s: not available on a multi-modulus context (gecm_create_multi)", fn);
+    return GECM_ERR_STATE;
+}
+
+/* what a wide context cannot do (include/gecm.h): its limb count has the 32-lane stage-1 kernel and no
+ * other, so everything that is not stage 1, or host work on its result, is refused before the batch is touched */
+static int wide_refuse(const char *fn)
+{
+    set_err("%s: not available on a wide context (gecm_create_wide): it runs curve build, stage 1 and what the host "
+            "makes of the result", fn);
     return GECM_ERR_STATE;
 }
 
@@ -370,84 +380,6 @@ static int ff_settle(gecm_ctx *c)
 /* the device the last stage-1 launch ran on */
 static inline gecm_dev *last_dev(const gecm_ctx *c) { return c->twin.ran_last ? c->twin.dev : c->dev; }
 
-/* Constants of the row kernels (csrc/gecm_row.hpp) for one number, at the shape of a context of nl limbs: L limbs in
- * use (nl + 1), R' = 2^(28 L).  Both kernels share the entry factor R'^2/R mod N, which turns the buffers' x*R into
- * x*R', and the exit multiply by R mod N (modulo N itself), which turns it back, with K' of N.
- *   w (GECM_ROW_KINDS x GECM_ROW_WORDS, or NULL): the 32-lanes-per-curve stage-1 kernel, which works modulo N' = m*N, the
- *     multiple of N that is -1 modulo 2^28 (the Montgomery digit is then the low limb itself), with R' >= 32 N'.
- *   u (GECM_UROW_SET words, or NULL): the 16-lanes-per-residue method kernel, which works modulo
- *     N'' = (m + t 2^28) N with the smallest t >= 0 that makes N'' >= 2^(28 (L - 1) + GECM_UROW_TOP_MIN_BITS): still -1
- *     modulo 2^28, below 2^(28 L - 5) (1 + 2^-3), and with a top limb that tells a value's quotient by N''; with it the
- *     float reciprocal of N'' / 2^(28 (L - 1)), 2 R' mod N'' nearest zero in balanced limbs, and N's own rho.
- * 1 if the constants asked for are made, 0 if this N has none (m->nl is not nl, or a bound does not hold). */
-static int row_consts(const gecm_mod *mod, int nl, int L, uint32_t *w, uint32_t *u)
-{
-    if (mod->nl != nl || L != nl + 1 || L < 3 || L > GECM_ROW_WORDS) return 0;
-    mpl_t two28, inv, m, np, cin;
-    mpl_set_u64(&two28, 1u << LIMB_BITS);
-    if (!mpl_invmod(&inv, &mod->N, &two28)) return 0;
-    mpl_sub(&m, &two28, &inv);                        /* m = -N^-1 mod 2^28, in [1, 2^28) */
-    mpl_mul(&np, &m, &mod->N);
-    gecm_mod_pow2(&cin, (unsigned)(2 * LIMB_BITS * L - LIMB_BITS * nl), &mod->N);
-    if (w) {
-        memset(w, 0, GECM_ROW_KINDS * GECM_ROW_WORDS * sizeof(uint32_t));
-        if (mpl_bits(&np) + 5 > LIMB_BITS * L) return 0;
-        mpl_to_limbs32(w + 0 * GECM_ROW_WORDS, 1, L, LIMB_BITS, &np);
-        if (w[0] != (1u << LIMB_BITS) - 1u) return 0;
-        memcpy(w + 1 * GECM_ROW_WORDS, mod->n28, (size_t)nl * sizeof(uint32_t));
-        mpl_to_limbs32(w + 2 * GECM_ROW_WORDS, 1, nl, LIMB_BITS, &cin);
-        memcpy(w + 3 * GECM_ROW_WORDS, mod->one28, (size_t)nl * sizeof(uint32_t));
-        memcpy(w + 4 * GECM_ROW_WORDS, mod->kp28, (size_t)nl * sizeof(uint32_t));
-    }
-    if (u) {
-        memset(u, 0, GECM_UROW_SET * sizeof(uint32_t));
-        mpl_t one, low, step, t, M, lim, v;
-        mpl_set_u64(&one, 1);
-        mpl_shl(&low, &one, (unsigned)(LIMB_BITS * (L - 1) + GECM_UROW_TOP_MIN_BITS));
-        M = np;
-        if (mpl_cmp(&M, &low) < 0) {                  /* t = ceil((low - m N) / (2^28 N)) */
-            mpl_shl(&step, &mod->N, LIMB_BITS);
-            mpl_sub(&t, &low, &M);
-            mpl_add(&t, &t, &step);
-            mpl_sub(&t, &t, &one);
-            mpl_divrem(&v, NULL, &t, &step);
-            mpl_mul(&t, &v, &step);
-            mpl_add(&M, &M, &t);
-        }
-        mpl_shl(&lim, &one, (unsigned)(LIMB_BITS * L - 5));
-        mpl_shr(&v, &lim, 3);
-        mpl_add(&lim, &lim, &v);
-        if (mpl_cmp(&M, &low) < 0 || mpl_cmp(&M, &lim) >= 0) return 0;
-        uint32_t *um = u + 0 * GECM_ROW_WORDS;
-        mpl_to_limbs32(um, 1, L, LIMB_BITS, &M);
-        if (um[0] != (1u << LIMB_BITS) - 1u) return 0;
-        memcpy(u + 1 * GECM_ROW_WORDS, mod->n28, (size_t)nl * sizeof(uint32_t));
-        mpl_to_limbs32(u + 2 * GECM_ROW_WORDS, 1, nl, LIMB_BITS, &cin);
-        memcpy(u + 3 * GECM_ROW_WORDS, mod->one28, (size_t)nl * sizeof(uint32_t));
-        memcpy(u + 4 * GECM_ROW_WORDS, mod->kp28, (size_t)nl * sizeof(uint32_t));
-        /* 2 R' mod N'', or that minus N'' if it is nearer zero, in balanced limbs: (-2^27, 2^27] below the top one */
-        gecm_mod_pow2(&v, (unsigned)(LIMB_BITS * L + 1), &M);
-        mpl_shl(&t, &v, 1);
-        const int neg = mpl_cmp(&t, &M) > 0;
-        if (neg) { mpl_sub(&t, &M, &v); v = t; }
-        uint32_t *two = u + 5 * GECM_ROW_WORDS;
-        mpl_to_limbs32(two, 1, L, LIMB_BITS, &v);
-        int32_t carry = 0;
-        for (int i = 0; i < L; i++) {
-            int32_t x = (int32_t)two[i] + carry;
-            carry = 0;
-            if (i < L - 1 && x > (1 << (LIMB_BITS - 1))) { x -= 1 << LIMB_BITS; carry = 1; }
-            two[i] = (uint32_t)(neg ? -x : x);
-        }
-        /* the reciprocal the reduction multiplies a top limb by: of N'' / 2^(28 (L - 1)) from its three top limbs */
-        const double scaled = (double)um[L - 1] + (double)um[L - 2] / 268435456.0 + (double)um[L - 3] / 72057594037927936.0;
-        const float rec = (float)(1.0 / scaled);
-        memcpy(u + 6 * GECM_ROW_WORDS, &rec, sizeof rec);
-        u[6 * GECM_ROW_WORDS + 1] = mod->rho28;
-    }
-    return 1;
-}
-
 /* The 32-lane stage-1 kernel's constants for the context's modulus.  Not an error if they cannot be set up: the other
  * layouts cover every N. */
 static void row_setup(gecm_ctx *c)
@@ -456,7 +388,7 @@ static void row_setup(gecm_ctx *c)
     gecm_row_shape(c->mod.nl, &nq, &L);
     if (nq > GECM_ROW_MAXNQ) return;
     uint32_t w[GECM_ROW_KINDS * GECM_ROW_WORDS];
-    if (row_consts(&c->mod, c->mod.nl, L, w, NULL)) (void)gecm_dev_set_rowconst(c->dev, nq, L, w);
+    if (gecm_mod_row_consts(&c->mod, c->mod.nl, L, w, NULL)) (void)gecm_dev_set_rowconst(c->dev, nq, L, w);
 }
 
 /* The 16-lane method kernel's constant sets on the device: one for the context's modulus, or one for every modulus of
@@ -474,7 +406,7 @@ static int unit_rows_setup(gecm_ctx *c)
     if (!u) return 0;
     int ok = 1;
     for (size_t g = 0; g < ng && ok; g++)
-        ok = row_consts(c->multi ? &c->grp[g] : &c->mod, c->mod.nl, L, NULL, u + g * GECM_UROW_SET);
+        ok = gecm_mod_row_consts(c->multi ? &c->grp[g] : &c->mod, c->mod.nl, L, NULL, u + g * GECM_UROW_SET);
     if (ok && !gecm_dev_set_unit_rowconst(c->dev, nq, L, (uint32_t)ng, u)) c->urow_state = 1;
     free(u);
     return c->urow_state > 0;
@@ -537,7 +469,7 @@ static int multi_rows_setup(gecm_ctx *c)
     uint32_t *w = (uint32_t *)calloc(c->ngroups * GECM_MROW_SET, sizeof(uint32_t));
     if (!w) return -2;
     for (size_t g = 0; g < c->ngroups; g++) {
-        if (!row_consts(&c->grp[g], c->mod.nl, L, w + g * GECM_MROW_SET, NULL)) { free(w); c->mrow_state = -1; return 0; }
+        if (!gecm_mod_row_consts(&c->grp[g], c->mod.nl, L, w + g * GECM_MROW_SET, NULL)) { free(w); c->mrow_state = -1; return 0; }
         w[g * GECM_MROW_SET + GECM_ROW_KINDS * GECM_ROW_WORDS] = c->grp[g].rho28;
     }
     const int failed = gecm_dev_set_multi_rowconst(c->dev, nq, L, (uint32_t)c->ngroups, w);
@@ -616,6 +548,44 @@ int gecm_create(gecm_ctx **out, int device, const char *n_str, int digitbits)
     *out = c;
     return GECM_OK;
 }
+
+/* Wide contexts.  Above the largest built limb count there is one kernel, the 32-lane stage-1 kernel at
+ * the wide shapes of csrc/gecm_rowk.h, and no kernel table: the device context is gecm_dev_open_wide's, the curves are built
+ * on the host as on any context, and what follows stage 1 — canonical residues, plain x and z, the factor gcds — is
+ * gecm_mod.c's work on the raw limbs (fetch_plain, gecm_scan_factors).  An N that gecm_create serves gets gecm_create's
+ * context: a caller may use this constructor for every number. */
+int gecm_create_wide(gecm_ctx **out, int device, const char *n_str, int digitbits)
+{
+    mpl_t n;
+    if (!out || !n_str || (digitbits != 52 && digitbits != 32) || mpl_set_str(&n, n_str) || pick_nl(mpl_bits(&n)))
+        return gecm_create(out, device, n_str, digitbits);          /* its answer, errors included */
+    gecm_ctx *c = (gecm_ctx *)calloc(1, sizeof *c);
+    if (!c) return GECM_ERR_NOMEM;
+    int rc = gecm_mod_setup(&c->mod, "gecm_create_wide", n_str, digitbits, 0, gecm_mod_wide_nl);
+    if (rc) { free(c); return rc; }
+    c->device = device;
+    c->wide = 1;
+    int nq, L;
+    gecm_row_shape(c->mod.nl, &nq, &L);
+    uint32_t w[GECM_ROW_KINDS * GECM_ROW_WORDS];
+    if (nq != GECM_ROW_MAXNQ || !gecm_mod_row_consts(&c->mod, c->mod.nl, L, w, NULL)) {
+        set_err("gecm_create_wide: the 32-lane kernel has no constants for this N at %d limbs", c->mod.nl);
+        rc = GECM_ERR_ARG;
+    } else if (gecm_dev_open_wide(&c->dev, device, c->mod.nl, c->mod.rho28) || gecm_dev_set_rowconst(c->dev, nq, L, w)) {
+        set_err("gecm_create_wide: %s", gecm_dev_error());
+        rc = GECM_ERR_DEVICE;
+    }
+    if (rc) {
+        gecm_dev_close(c->dev);
+        gecm_mod_free(&c->mod);
+        free(c);
+        return rc;
+    }
+    *out = c;
+    return GECM_OK;
+}
+
+int gecm_is_wide(const gecm_ctx *c) { return c ? c->wide : 0; }
 
 static void free_batch(gecm_ctx *c)
 {
@@ -717,7 +687,7 @@ int gecm_device_memory(gecm_ctx *c, uint64_t *free_bytes, uint64_t *total_bytes)
  * The same sums the device layer allocates by. */
 uint64_t gecm_batch_bytes(const gecm_ctx *c, size_t curves, int with_stage2, uint64_t B1, uint32_t D, uint32_t U)
 {
-    if (!c || !curves) return 0;
+    if (!c || !curves || (c->wide && with_stage2)) return 0;
     /* multi-modulus: every modulus's curves padded to whole wavefronts, at most 63 more per modulus that has curves;
      * lane-packed, the batch's tail only (gecm_multi_positions) */
     if (c->multi && c->packing == GECM_PACK_LANE) curves = gecm_multi_positions(&curves, 1, GECM_PACK_LANE);
@@ -759,6 +729,7 @@ static void vec_put(const gecm_mod *m, void *vec, size_t batch, size_t lane, con
 
 int gecm_get_one(const gecm_ctx *c, void *one_limbs)
 {
+    if (c && c->wide) return wide_refuse("gecm_get_one");
     if (!c || !one_limbs) return GECM_ERR_ARG;
     if (c && c->multi) return multi_refuse("gecm_get_one");
     vec_put(&c->mod, one_limbs, 1, 0, &c->mod.rref_mod_n);
@@ -778,6 +749,7 @@ static int l0_open(gecm_ctx *c)
 
 static int l0_call(gecm_ctx *c, int op, const void *a, const void *b, void *r0, void *r1, size_t batch)
 {
+    if (c && c->wide) return wide_refuse("the L0 operators");
     if (c && c->multi) return multi_refuse("the L0 operators");
     if (!c || !a || !r0 || batch == 0) { set_err("L0: bad argument"); return GECM_ERR_ARG; }
     if (l0_open(c)) return GECM_ERR_DEVICE;
@@ -836,6 +808,7 @@ int gecm_vecaddsubmod(gecm_ctx *c, const void *a, const void *b, void *sum, void
  * runs it.  Operands go to the device as they come, in the reference radix; finv28 brings the result back to it. */
 int gecm_vecinvmod(gecm_ctx *c, const void *a, void *inv, void *gcd, size_t batch)
 {
+    if (c && c->wide) return wide_refuse("gecm_vecinvmod");
     if (c && c->multi) return multi_refuse("the L0 operators");
     if (!c || !a || !inv || !gcd || batch == 0) { set_err("L0: bad argument"); return GECM_ERR_ARG; }
     if (l0_open(c)) return GECM_ERR_DEVICE;
@@ -866,6 +839,7 @@ int gecm_vecinvmod(gecm_ctx *c, const void *a, void *inv, void *gcd, size_t batc
  * not, and nothing is converted on the way in or out. */
 int gecm_vecrawop(gecm_ctx *c, int target, int op, const uint32_t *a, const uint32_t *b, uint32_t *r, size_t count)
 {
+    if (c && c->wide) return wide_refuse("gecm_vecrawop");
     const int one_operand = op == GECM_RAW_SQR || op == GECM_RAW_CONDSUB;
     if (!c || !a || !r || count == 0 || op < GECM_RAW_MUL || op > GECM_RAW_CONDSUB || (!b && !one_operand)) {
         set_err("gecm_vecrawop: bad argument");
@@ -1167,6 +1141,7 @@ int gecm_build_curves(gecm_ctx *c, const uint64_t *sigma, size_t batch)
     /* inputs are checked before the context takes the new batch: after an error it holds no batch at all (the
      * phase functions then return GECM_ERR_STATE instead of running on memory nothing was uploaded to) */
     int rc = sigma_args(c, "gecm_build_curves", sigma, batch);
+    if (!rc && c->wide && c->build_where == GECM_BUILD_DEVICE) rc = wide_refuse("gecm_build_curves on the device (gecm_set_curve_build)");
     if (!rc) rc = batch_build(c, &(batch_desc){.who = "gecm_build_curves", .batch = batch, .sigma = sigma, .param = c->next_param});
     return build_call_end(c, rc);
 }
@@ -1210,6 +1185,7 @@ static uint32_t *upload_planes(const gecm_ctx *c, const void *X, const void *Z, 
 /* the one build call a pending gecm_set_next_params setting passes by: it waits for the next of the others */
 int gecm_upload_points(gecm_ctx *c, const void *X, const void *Z, const void *s, size_t batch)
 {
+    if (c && c->wide) return wide_refuse("gecm_upload_points");
     if (!c || !X || !Z || !s || batch == 0) { set_err("gecm_upload_points: bad argument"); return GECM_ERR_ARG; }
     if (c->multi) return multi_refuse("gecm_upload_points");
     int rc;
@@ -1352,6 +1328,11 @@ int gecm_stage1_range(gecm_ctx *c, uint64_t B1, uint32_t range)
     if (method_refuse(c, "gecm_stage1", 0)) return GECM_ERR_STATE;
     if (B1 < 2 || B1 > GECM_B1_MAX) { set_err("gecm_stage1: B1 must be in [2, %llu]", (unsigned long long)GECM_B1_MAX); return GECM_ERR_ARG; }
     if (lane_packing_refuses(c)) return GECM_ERR_STATE;
+    if (c->wide && c->lanes_per_curve != 0 && c->lanes_per_curve != 32) {
+        set_err("gecm_stage1: a wide context (gecm_create_wide) runs 32 lanes per curve, and this context is set to %d "
+                "(gecm_set_lanes_per_curve)", c->lanes_per_curve);
+        return GECM_ERR_STATE;
+    }
     const uint32_t nranges = gecm_stage1_ranges_u(B1);
     if (range >= nranges) { set_err("gecm_stage1_range: B1 = %llu has %u prime range(s)", (unsigned long long)B1, nranges); return GECM_ERR_ARG; }
     const tape_key key = {0, B1, range}, next = {0, B1, (uint64_t)range + 1};
@@ -1388,6 +1369,7 @@ int gecm_stage1_describe_extend(uint64_t from, uint64_t to, uint32_t seg, gecm_e
 
 int gecm_stage1_extend_segment(gecm_ctx *c, uint64_t from, uint64_t to, uint32_t seg)
 {
+    if (c && c->wide) return wide_refuse("gecm_stage1_extend_segment");
     const int settled = ff_settle(c);
     if (settled) return settled;
     int rc = extend_args("gecm_stage1_extend", from, to);
@@ -1497,6 +1479,7 @@ int gecm_get_stage1_stats(const gecm_ctx *c, gecm_stage1_stats *st)
 
 int gecm_download_points(gecm_ctx *c, void *X, void *Z)
 {
+    if (c && c->wide) return wide_refuse("gecm_download_points");
     if (c && c->multi) return multi_refuse("gecm_download_points");
     const int settled = ff_settle(c);
     if (settled) return settled;
@@ -1519,6 +1502,7 @@ int gecm_download_points(gecm_ctx *c, void *X, void *Z)
 
 int gecm_download_s(gecm_ctx *c, void *s)
 {
+    if (c && c->wide) return wide_refuse("gecm_download_s");
     if (c && c->multi) return multi_refuse("gecm_download_s");
     if (method_refuse(c, "gecm_download_s", 0)) return GECM_ERR_STATE;
     if (!c || !s || c->batch == 0) return GECM_ERR_ARG;
@@ -1542,6 +1526,19 @@ static int fetch_plain(gecm_ctx *c)
     if (settled) return settled;
     if (c->have_plain) return GECM_OK;
     if (c->batch == 0) { set_err("no batch"); return GECM_ERR_STATE; }
+    if (c->wide) {
+        /* the kernel's lazy limbs, and on the worker threads: canonical modulo N, then out of Montgomery form */
+        const size_t words = (size_t)c->mod.nl * c->batch;
+        uint32_t *raw = (uint32_t *)malloc(words * 2 * sizeof(uint32_t));
+        if (!raw) return GECM_ERR_NOMEM;
+        if (gecm_dev_download_raw(c->dev, raw, raw + words)) { free(raw); set_err("%s", gecm_dev_error()); return GECM_ERR_DEVICE; }
+        gecm_mod_wide_job j = {.m = &c->mod, .batch = c->batch, .rawX = raw, .rawZ = raw + words, .hx = c->hx, .hz = c->hz};
+        mpl_invmod(&j.rinv, &c->mod.rint_mod_n, &c->mod.N);         /* N is odd: a power of two has an inverse */
+        run_slices(c->batch, gecm_mod_raw_slice, &j);
+        free(raw);
+        c->have_plain = 1;
+        return GECM_OK;
+    }
     if (gecm_dev_download_plain(c->dev, c->hx, c->hz)) { set_err("%s", gecm_dev_error()); return GECM_ERR_DEVICE; }
     c->have_plain = 1;
     return GECM_OK;
@@ -1642,6 +1639,7 @@ int gecm_stage1_factor(gecm_ctx *c, size_t k, char *dec, size_t declen, int *is_
 /* ---- normalisation and standard lines ---------------------------------------- */
 int gecm_normalize_points(gecm_ctx *c)
 {
+    if (c && c->wide) return wide_refuse("gecm_normalize_points");
     const int settled = ff_settle(c);
     if (settled) return settled;
     if (!c || c->batch == 0) { set_err("gecm_normalize_points: no curves uploaded"); return GECM_ERR_STATE; }
@@ -1698,6 +1696,7 @@ static int format_method_line(gecm_ctx *c, const gecm_mod *m, size_t pos, char *
 
 int gecm_format_save_line_std(gecm_ctx *c, size_t k, char *buf, size_t buflen)
 {
+    if (c && c->wide) return wide_refuse("gecm_format_save_line_std");
     size_t pos;
     const gecm_mod *m = c && buf ? curve_at(c, k, &pos) : NULL;
     if (!m) return GECM_ERR_ARG;
@@ -1736,6 +1735,7 @@ static uint64_t ladder_adds(uint64_t c)
 
 int gecm_stage2_init(gecm_ctx *c, uint32_t D, uint32_t U)
 {
+    if (c && c->wide) return wide_refuse("gecm_stage2_init");
     const int settled = ff_settle(c);
     if (settled) return settled;
     if (method_refuse(c, "gecm_stage2_init", 1)) return GECM_ERR_STATE;
@@ -1907,6 +1907,7 @@ static int s2_tape_for(gecm_ctx *c, uint32_t steps, const uint32_t *pm_v, const 
 
 int gecm_stage2_pair(gecm_ctx *c, uint32_t steps, const uint32_t *pm_v, const uint32_t *pm_u, uint32_t amin)
 {
+    if (c && c->wide) return wide_refuse("gecm_stage2_pair");
     if (method_refuse(c, "gecm_stage2_pair", 1)) return GECM_ERR_STATE;
     if (!c || !c->s2_ready) { set_err("gecm_stage2_pair: gecm_stage2_init has not run"); return GECM_ERR_STATE; }
     if (steps && (!pm_v || !pm_u)) return GECM_ERR_ARG;
@@ -1920,6 +1921,7 @@ int gecm_stage2_pair(gecm_ctx *c, uint32_t steps, const uint32_t *pm_v, const ui
 int gecm_stage2_pair_prepare(gecm_ctx *c, uint32_t D, uint32_t U, uint32_t steps, const uint32_t *pm_v, const uint32_t *pm_u,
                              uint32_t amin)
 {
+    if (c && c->wide) return wide_refuse("gecm_stage2_pair_prepare");
     if (method_refuse(c, "gecm_stage2_pair_prepare", 1)) return GECM_ERR_STATE;
     if (!c || (steps && (!pm_v || !pm_u))) return GECM_ERR_ARG;
     if (!D || !U || U > (S2_RING - S2_GIANT_CHUNK) / 4) { set_err("gecm_stage2_pair_prepare: bad D/U"); return GECM_ERR_ARG; }
@@ -1949,6 +1951,7 @@ static int keep_pairmap(gecm_ctx *c, gecm_pairs *pm, uint64_t lo, uint64_t hi)
  * (B2, D, U) finds them, and the device keeps its copy of the tape from one batch to the next. */
 int gecm_stage2_prepare(gecm_ctx *c, uint64_t B2, uint32_t D, uint32_t U)
 {
+    if (c && c->wide) return wide_refuse("gecm_stage2_prepare");
     const uint64_t PRIME_RANGE = 100000000ull;
     if (method_refuse(c, "gecm_stage2_prepare", 1)) return GECM_ERR_STATE;
     if (!c || c->B1 == 0 || B2 <= c->B1) { set_err("gecm_stage2_prepare: call gecm_stage1 first; B2 > B1"); return GECM_ERR_ARG; }
@@ -1970,6 +1973,7 @@ int gecm_stage2_prepare(gecm_ctx *c, uint64_t B2, uint32_t D, uint32_t U)
 
 int gecm_stage2(gecm_ctx *c, uint64_t B2, uint32_t D, uint32_t U)
 {
+    if (c && c->wide) return wide_refuse("gecm_stage2");
     const uint64_t PRIME_RANGE = 100000000ull;                           /* main.c:581 */
     if (method_refuse(c, "gecm_stage2", 1)) return GECM_ERR_STATE;
     if (!c || c->B1 == 0 || B2 <= c->B1) { set_err("gecm_stage2: need B2 > B1 and a finished stage 1"); return GECM_ERR_ARG; }
@@ -2029,6 +2033,7 @@ static int fetch_acc(gecm_ctx *c)
 
 int gecm_download_acc(gecm_ctx *c, void *acc)
 {
+    if (c && c->wide) return wide_refuse("gecm_download_acc");
     if (!c || !acc) return GECM_ERR_ARG;
     if (c && c->multi) return multi_refuse("gecm_download_acc");
     int rc = fetch_acc(c);
@@ -2044,6 +2049,7 @@ int gecm_download_acc(gecm_ctx *c, void *acc)
 
 int gecm_stage2_factor(gecm_ctx *c, size_t k, char *dec, size_t declen, int *is_prp)
 {
+    if (c && c->wide) return wide_refuse("gecm_stage2_factor");
     size_t pos;
     const gecm_mod *m = c ? curve_at(c, k, &pos) : NULL;
     if (!m) return GECM_ERR_ARG;
@@ -2071,12 +2077,19 @@ int gecm_scan_factors(gecm_ctx *c, int stage, size_t *first)
     const int settled = ff_settle(c);
     if (settled) return settled;
     if (!c || c->batch == 0 || (stage != 1 && stage != 2)) { set_err("gecm_scan_factors: bad argument"); return GECM_ERR_ARG; }
+    if (stage == 2 && c->wide) return wide_refuse("gecm_scan_factors(stage 2)");
     if (stage == 2 && method_refuse(c, "gecm_scan_factors(stage 2)", 1)) return GECM_ERR_STATE;
     if (stage == 2 && !c->s2_ready) { set_err("gecm_scan_factors: no stage-2 state"); return GECM_ERR_STATE; }
     uint32_t **f = &c->flags[stage - 1], **hg = &c->hg[stage - 1];
     if (!*f) *f = (uint32_t *)calloc(c->batch, sizeof(uint32_t));
     if (!*hg) *hg = (uint32_t *)calloc(c->batch * (size_t)c->mod.nl, sizeof(uint32_t));
     if (!*f || !*hg) return GECM_ERR_NOMEM;
+    if (c->wide) {                                     /* gcd(z, N) per curve on the worker threads, from the plain z */
+        const int rc = fetch_plain(c);
+        if (rc) return rc;
+        gecm_mod_wide_job j = {.m = &c->mod, .batch = c->batch, .hz = c->hz, .hg = *hg, .flags = *f};
+        run_slices(c->batch, gecm_mod_gcd_slice, &j);
+    } else
     /* stage 1 of a method batch tests x - 1 or x - 2; its stage-2 accumulator is scanned as any other */
     if (c->method && stage == 1 ? gecm_dev_gcd_scan_off(c->dev, c->method == GECM_METHOD_PP1 ? 2 : 1, *f, *hg)
                                 : gecm_dev_gcd_scan(c->dev, stage - 1, *f, *hg)) { set_err("gecm_scan_factors: %s", gecm_dev_error()); return GECM_ERR_DEVICE; }
@@ -2278,6 +2291,7 @@ static void stage1_restart(gecm_ctx *c, uint64_t b1_done)
 static int resume_points(gecm_ctx *c, const char *who, const uint64_t *sigma, const uint32_t *idx, const void *x,
                          const void *z, size_t batch, uint64_t b1_done)
 {
+    if (c && c->wide) return wide_refuse(who);
     if (!x || !z) { set_err("%s: bad argument", who); return GECM_ERR_ARG; }
     if (b1_done == 1 || b1_done > GECM_B1_MAX) { set_err("%s: b1_done must be 0 or a B1 in [2, %llu]", who, (unsigned long long)GECM_B1_MAX); return GECM_ERR_ARG; }
     uint32_t *planes = (uint32_t *)calloc((size_t)c->mod.nl * batch * 2, 4);
@@ -2318,6 +2332,7 @@ int gecm_resume_points_multi(gecm_ctx *c, const uint64_t *sigma, const uint32_t 
 static int build_seeds(gecm_ctx *c, const char *who, int method, const uint32_t *idx, const void *x0, const void *x,
                        size_t batch, uint64_t b1_done)
 {
+    if (c && c->wide) return wide_refuse(who);
     if (method != GECM_METHOD_PM1 && method != GECM_METHOD_PP1) {
         set_err("%s: the method must be GECM_METHOD_PM1 (P-1) or GECM_METHOD_PP1 (P+1)", who);
         return GECM_ERR_ARG;
@@ -2403,6 +2418,7 @@ int gecm_curve_modulus(const gecm_ctx *c, size_t k)
 
 int gecm_curve_acc(gecm_ctx *c, size_t k, char *hex, size_t hexlen)
 {
+    if (c && c->wide) return wide_refuse("gecm_curve_acc");
     size_t pos;
     const gecm_mod *m = c && hex ? curve_at(c, k, &pos) : NULL;
     if (!m) return GECM_ERR_ARG;

@@ -8,6 +8,7 @@
  */
 #include "gecm_mod.h"
 #include "../../include/gecm.h"
+#include "../csrc/gecm_rowk.h"
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -331,6 +332,144 @@ int gecm_mod_factor(const gecm_mod *m, mpl_t *g, const char *who, char *dec, siz
     }
     if (is_prp) *is_prp = mpl_probab_prime(g, 3);   /* ecm.c:1346 */
     return 1;
+}
+
+/* Constants of the row kernels (csrc/gecm_row.hpp) for one number, at the shape of a context of nl limbs: L limbs in
+ * use (nl + 1), R' = 2^(28 L).  Both kernels share the entry factor R'^2/R mod N, which turns the buffers' x*R into
+ * x*R', and the exit multiply by R mod N (modulo N itself), which turns it back, with K' of N.
+ *   w (GECM_ROW_KINDS x GECM_ROW_WORDS, or NULL): the 32-lanes-per-curve stage-1 kernel, which works modulo N' = m*N, the
+ *     multiple of N that is -1 modulo 2^28 (the Montgomery digit is then the low limb itself), with R' >= 32 N'.
+ *   u (GECM_UROW_SET words, or NULL): the 16-lanes-per-residue method kernel, which works modulo
+ *     N'' = (m + t 2^28) N with the smallest t >= 0 that makes N'' >= 2^(28 (L - 1) + GECM_UROW_TOP_MIN_BITS): still -1
+ *     modulo 2^28, below 2^(28 L - 5) (1 + 2^-3), and with a top limb that tells a value's quotient by N''; with it the
+ *     float reciprocal of N'' / 2^(28 (L - 1)), 2 R' mod N'' nearest zero in balanced limbs, and N's own rho.
+ * 1 if the constants asked for are made, 0 if this N has none (m->nl is not nl, or a bound does not hold). */
+int gecm_mod_row_consts(const gecm_mod *mod, int nl, int L, uint32_t *w, uint32_t *u)
+{
+    if (mod->nl != nl || L != nl + 1 || L < 3 || L > GECM_ROW_WORDS) return 0;
+    mpl_t two28, inv, m, np, cin;
+    mpl_set_u64(&two28, 1u << LIMB_BITS);
+    if (!mpl_invmod(&inv, &mod->N, &two28)) return 0;
+    mpl_sub(&m, &two28, &inv);                        /* m = -N^-1 mod 2^28, in [1, 2^28) */
+    mpl_mul(&np, &m, &mod->N);
+    gecm_mod_pow2(&cin, (unsigned)(2 * LIMB_BITS * L - LIMB_BITS * nl), &mod->N);
+    if (w) {
+        memset(w, 0, GECM_ROW_KINDS * GECM_ROW_WORDS * sizeof(uint32_t));
+        if (mpl_bits(&np) + 5 > LIMB_BITS * L) return 0;
+        mpl_to_limbs32(w + 0 * GECM_ROW_WORDS, 1, L, LIMB_BITS, &np);
+        if (w[0] != (1u << LIMB_BITS) - 1u) return 0;
+        memcpy(w + 1 * GECM_ROW_WORDS, mod->n28, (size_t)nl * sizeof(uint32_t));
+        mpl_to_limbs32(w + 2 * GECM_ROW_WORDS, 1, nl, LIMB_BITS, &cin);
+        memcpy(w + 3 * GECM_ROW_WORDS, mod->one28, (size_t)nl * sizeof(uint32_t));
+        memcpy(w + 4 * GECM_ROW_WORDS, mod->kp28, (size_t)nl * sizeof(uint32_t));
+    }
+    if (u) {
+        memset(u, 0, GECM_UROW_SET * sizeof(uint32_t));
+        mpl_t one, low, step, t, M, lim, v;
+        mpl_set_u64(&one, 1);
+        mpl_shl(&low, &one, (unsigned)(LIMB_BITS * (L - 1) + GECM_UROW_TOP_MIN_BITS));
+        M = np;
+        if (mpl_cmp(&M, &low) < 0) {                  /* t = ceil((low - m N) / (2^28 N)) */
+            mpl_shl(&step, &mod->N, LIMB_BITS);
+            mpl_sub(&t, &low, &M);
+            mpl_add(&t, &t, &step);
+            mpl_sub(&t, &t, &one);
+            mpl_divrem(&v, NULL, &t, &step);
+            mpl_mul(&t, &v, &step);
+            mpl_add(&M, &M, &t);
+        }
+        mpl_shl(&lim, &one, (unsigned)(LIMB_BITS * L - 5));
+        mpl_shr(&v, &lim, 3);
+        mpl_add(&lim, &lim, &v);
+        if (mpl_cmp(&M, &low) < 0 || mpl_cmp(&M, &lim) >= 0) return 0;
+        uint32_t *um = u + 0 * GECM_ROW_WORDS;
+        mpl_to_limbs32(um, 1, L, LIMB_BITS, &M);
+        if (um[0] != (1u << LIMB_BITS) - 1u) return 0;
+        memcpy(u + 1 * GECM_ROW_WORDS, mod->n28, (size_t)nl * sizeof(uint32_t));
+        mpl_to_limbs32(u + 2 * GECM_ROW_WORDS, 1, nl, LIMB_BITS, &cin);
+        memcpy(u + 3 * GECM_ROW_WORDS, mod->one28, (size_t)nl * sizeof(uint32_t));
+        memcpy(u + 4 * GECM_ROW_WORDS, mod->kp28, (size_t)nl * sizeof(uint32_t));
+        /* 2 R' mod N'', or that minus N'' if it is nearer zero, in balanced limbs: (-2^27, 2^27] below the top one */
+        gecm_mod_pow2(&v, (unsigned)(LIMB_BITS * L + 1), &M);
+        mpl_shl(&t, &v, 1);
+        const int neg = mpl_cmp(&t, &M) > 0;
+        if (neg) { mpl_sub(&t, &M, &v); v = t; }
+        uint32_t *two = u + 5 * GECM_ROW_WORDS;
+        mpl_to_limbs32(two, 1, L, LIMB_BITS, &v);
+        int32_t carry = 0;
+        for (int i = 0; i < L; i++) {
+            int32_t x = (int32_t)two[i] + carry;
+            carry = 0;
+            if (i < L - 1 && x > (1 << (LIMB_BITS - 1))) { x -= 1 << LIMB_BITS; carry = 1; }
+            two[i] = (uint32_t)(neg ? -x : x);
+        }
+        /* the reciprocal the reduction multiplies a top limb by: of N'' / 2^(28 (L - 1)) from its three top limbs */
+        const double scaled = (double)um[L - 1] + (double)um[L - 2] / 268435456.0 + (double)um[L - 3] / 72057594037927936.0;
+        const float rec = (float)(1.0 / scaled);
+        memcpy(u + 6 * GECM_ROW_WORDS, &rec, sizeof rec);
+        u[6 * GECM_ROW_WORDS + 1] = mod->rho28;
+    }
+    return 1;
+}
+
+/* ---- wide contexts ---- */
+int gecm_wide_max_bits(void) { return GECM_WIDE_MAX_BITS; }
+
+int gecm_mod_wide_nl(int nbits)
+{
+    static const int wide_nl[] = {40, 43, 47, 0};     /* rows 41, 44, 48 of csrc/gecm_rowk.h: GECM_ROW_WIDE_SHAPES */
+    if (nbits > GECM_WIDE_MAX_BITS) return 0;
+    for (const int *p = wide_nl; *p; p++)
+        if (LIMB_BITS * *p >= nbits + 5) return *p;
+    return 0;
+}
+
+void gecm_mod_raw_value(mpl_t *r, const uint32_t *limbs, size_t stride, int count)
+{
+    /* the parts below and from 2^28 of every limb are two numbers in disjoint 28-bit fields (the upper parts have 4 bits) */
+    uint32_t lo[MPL_MAXL], hi[MPL_MAXL];
+    mpl_t a, b;
+    if (count > MPL_MAXL) count = MPL_MAXL;
+    for (int i = 0; i < count; i++) {
+        const uint32_t w = limbs[(size_t)i * stride];
+        lo[i] = w & ((1u << LIMB_BITS) - 1);
+        hi[i] = w >> LIMB_BITS;
+    }
+    mpl_from_limbs32(&a, lo, 1, count, LIMB_BITS);
+    mpl_from_limbs32(&b, hi, 1, count, LIMB_BITS);
+    mpl_shl(&b, &b, LIMB_BITS);
+    mpl_add(r, &a, &b);
+}
+
+int gecm_mod_raw_slice(void *job, size_t lo, size_t hi)
+{
+    const gecm_mod_wide_job *j = (const gecm_mod_wide_job *)job;
+    const gecm_mod *m = j->m;
+    const uint32_t *src[2] = {j->rawX, j->rawZ};
+    uint32_t *dst[2] = {j->hx, j->hz};
+    for (size_t k = lo; k < hi; k++)
+        for (int w = 0; w < 2; w++) {
+            mpl_t v;
+            gecm_mod_raw_value(&v, src[w] + k, j->batch, m->nl);     /* t + K', t = x R mod N lazily */
+            mpl_mod(&v, &v, &m->N);                                  /* canonical Montgomery form */
+            mpl_mulmod(&v, &v, &j->rinv, &m->N);                     /* plain */
+            mpl_to_limbs32(dst[w] + k, j->batch, m->nl, LIMB_BITS, &v);
+        }
+    return 0;
+}
+
+int gecm_mod_gcd_slice(void *job, size_t lo, size_t hi)
+{
+    const gecm_mod_wide_job *j = (const gecm_mod_wide_job *)job;
+    const gecm_mod *m = j->m;
+    for (size_t k = lo; k < hi; k++) {
+        mpl_t z, g;
+        mpl_from_limbs32(&z, j->hz + k, j->batch, m->nl, LIMB_BITS);
+        mpl_gcd(&g, &z, &m->N);                                      /* z = 0: g = N, no factor (ecm.c:2542-2557) */
+        mpl_to_limbs32(j->hg + k, j->batch, m->nl, LIMB_BITS, &g);
+        j->flags[k] = mpl_cmp_u64(&g, 1) > 0 && mpl_cmp(&g, &m->N) != 0;
+    }
+    return 0;
 }
 
 /* ---- the position layout of a multi-modulus batch ---- */

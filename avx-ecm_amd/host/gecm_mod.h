@@ -79,6 +79,35 @@ void gecm_mod_fail_record(const gecm_mod *m, const uint32_t *hfail, uint32_t pla
  * else 0; GECM_ERR_ARG "<who>: buffer too small" */
 int gecm_mod_factor(const gecm_mod *m, mpl_t *g, const char *who, char *dec, size_t declen, int *is_prp);
 
+/* The constants of the row kernels for one number at the shape of a context of nl limbs (L = nl + 1 limbs in use): w, the
+ * 32-lanes-per-curve stage-1 kernel's GECM_ROW_KINDS x GECM_ROW_WORDS words, and u, the 16-lane method kernel's
+ * GECM_UROW_SET words (csrc/gecm_rowk.h); either may be NULL.  1 if made, 0 if this N has none.  See gecm_mod.c. */
+int gecm_mod_row_consts(const gecm_mod *mod, int nl, int L, uint32_t *w, uint32_t *u);
+
+/* ---- wide contexts (gecm_create_wide): numbers of up to GECM_WIDE_MAX_BITS bits on 40, 43 or 47 limbs ----
+ * The device runs stage 1 alone and leaves lazy residues; what follows is host work and lives here, away from any device.
+ * gecm_mod_wide_nl: the smallest wide limb count with 28 nl >= nbits + 5, or 0 above GECM_WIDE_MAX_BITS (the argument
+ * of gecm_mod_setup for a wide context).
+ * gecm_mod_raw_value: the integer sum of limb[i] 2^(28 i) over count limbs `stride` apart, the limbs being ANY 32-bit
+ * words (mpl_from_limbs32 wants them below 2^28).
+ * gecm_mod_raw_slice: curves [lo, hi) of a batch from the raw limbs of the kernel, rawX and rawZ ([nl][batch]), to the
+ * canonical plain residues hx, hz ([nl][batch]): the value modulo N (the canonical Montgomery form x R mod N) times
+ * rinv = R^-1 mod N.  gecm_mod_gcd_slice: g = gcd(z, N) of those curves from hz into hg ([nl][batch]), and
+ * flags[k] = 1 iff 1 < g < N.  Both are run_slices workers: they return 0. */
+#define GECM_WIDE_MAX_BITS 1311
+int gecm_mod_wide_nl(int nbits);
+void gecm_mod_raw_value(mpl_t *r, const uint32_t *limbs, size_t stride, int count);
+typedef struct {
+    const gecm_mod *m;
+    mpl_t rinv;                       /* R^-1 mod N, R = 2^(28 nl) */
+    size_t batch;
+    const uint32_t *rawX, *rawZ;      /* gecm_mod_raw_slice reads */
+    uint32_t *hx, *hz;                /* ... and writes; gecm_mod_gcd_slice reads hz */
+    uint32_t *hg, *flags;             /* gecm_mod_gcd_slice writes */
+} gecm_mod_wide_job;
+int gecm_mod_raw_slice(void *job, size_t lo, size_t hi);
+int gecm_mod_gcd_slice(void *job, size_t lo, size_t hi);
+
 /* The positions of a multi-modulus batch: the moduli in order, each one's curves in the caller's
  * order.  Wave packing pads every modulus that has curves to whole blocks of 64 positions; lane packing lays them back
  * to back and pads the batch's tail, on modulus 0.  gecm_multi_positions (include/gecm.h) is the padding rule.  A

@@ -245,6 +245,18 @@ def multi_rows_auto(positions, limbs, cus):
     return lib.gecm_multi_rows_auto(positions, limbs, cus)
 
 
+# wide contexts: stage 1 for numbers of 1032 to 1311 bits
+_sig("gecm_create_wide", c_int, ctypes.POINTER(c_void_p), c_int, c_char_p, c_int)
+_sig("gecm_is_wide", c_int, c_void_p)
+_sig("gecm_wide_max_bits", c_int)
+EXPORTS += ["gecm_create_wide", "gecm_is_wide", "gecm_wide_max_bits"]
+
+
+def wide_max_bits():
+    """the largest bit length Engine(n, wide=True) takes (1311)"""
+    return lib.gecm_wide_max_bits()
+
+
 class GecmError(RuntimeError):
     pass
 
@@ -385,9 +397,12 @@ def resume_line_std_bound(line, params=False):
 class Engine:
     """One gecm_ctx: N + limb format + device."""
 
-    def __init__(self, n, digitbits=52, device=0):
+    def __init__(self, n, digitbits=52, device=0, wide=False):
+        """wide: gecm_create_wide, which serves every N gecm_create serves (an ordinary context then) and, from 1032 to
+        wide_max_bits() bits, makes a wide context: curve build, stage 1 and its save lines and factors, nothing else."""
         self._h = c_void_p()
-        _chk(lib.gecm_create(ctypes.byref(self._h), device, str(n).encode(), digitbits), "gecm_create")
+        create = "gecm_create_wide" if wide else "gecm_create"
+        _chk(getattr(lib, create)(ctypes.byref(self._h), device, str(n).encode(), digitbits), create)
         self.cfg = Config()
         _chk(lib.gecm_get_config(self._h, ctypes.byref(self.cfg)), "gecm_get_config")
         self.n = int(str(n), 0) if isinstance(n, str) else int(n)
@@ -403,6 +418,9 @@ class Engine:
             self.close()
         except Exception:
             pass
+
+    def is_wide(self):
+        return bool(lib.gecm_is_wide(self._h))
 
     # ---- reference vec layout helpers: data[lane + limb*batch] ----
     def _ctype(self):

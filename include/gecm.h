@@ -652,6 +652,32 @@ int gecm_set_multi_rows(gecm_ctx *ctx, int rows);
 int gecm_get_multi_rows(const gecm_ctx *ctx);
 int gecm_multi_rows_auto(size_t positions, int dev_limbs, int cus);   /* 0 or 1; pure host code */
 
+/* ---- wide contexts: stage 1 for numbers of 1032 to 1311 bits ----
+ * gecm_create and gecm_create_multi serve numbers of up to 1031 bits.  gecm_create_wide serves those too — for an N
+ * gecm_create takes it returns what gecm_create returns, an ordinary context (gecm_is_wide == 0), so a caller may use it
+ * for every number — and for bitlen(N) from 1032 to gecm_wide_max_bits() = 1311 it makes a WIDE context: 40, 43 or 47
+ * device limbs (the smallest with 28 limbs >= bits + 5), the 32-lane stage-1 kernel k_stage1_row<3, limbs + 1, false> and
+ * no other kernel.  Above 1311 bits: GECM_ERR_ARG, "larger than this build supports".
+ * A wide context builds curves, runs stage 1 and hands out the result; the device does stage 1, the host the rest:
+ *   gecm_get_config (the reference's NWORDS/MAXBITS rule, dev_limbs 40, 43 or 47), gecm_device_name, gecm_device_memory,
+ *   gecm_batch_bytes (the stage-1 arrays; 0 with with_stage2), gecm_set_report_modulus;
+ *   gecm_build_curves on the host, with gecm_set_next_params for PARAM 0, 1 and 3;
+ *   gecm_stage1, gecm_stage1_range, gecm_sync, gecm_stage1_progress, gecm_last_kernel_name, gecm_last_kernel_ms,
+ *   gecm_get_stage1_stats; gecm_set_lanes_per_curve 0 and 32 run, with 1, 2 or 8 gecm_stage1 answers GECM_ERR_STATE;
+ *   gecm_get_lanes_per_curve answers 32, gecm_get_special_form 0 (no twin is opened);
+ *   gecm_download_points_plain, gecm_format_save_line, gecm_format_resume_line, gecm_stage1_factor,
+ *   gecm_scan_factors(ctx, 1, ..) and gecm_curve_flag(ctx, 1, k), with the meaning they have on any context: the host
+ *   reduces the kernel's lazy residues modulo N, takes them out of Montgomery form and computes gcd(Z, N) per curve.
+ * Everything else answers GECM_ERR_STATE, "not available on a wide context (gecm_create_wide): ...", and leaves the
+ * batch as it was: every gecm_stage2* call, gecm_scan_factors(ctx, 2, ..), gecm_download_acc, gecm_curve_acc; the L0
+ * operators, gecm_vecinvmod, gecm_vecrawop, gecm_get_one; gecm_upload_points, gecm_download_points, gecm_download_s;
+ * gecm_resume_points; gecm_stage1_extend*, gecm_normalize_points, gecm_format_save_line_std; gecm_build_seeds; and
+ * gecm_build_curves while gecm_set_curve_build is GECM_BUILD_DEVICE.  The save lines are what GMP-ECM resumes for stage 2.
+ * gecm_is_wide: 1 for a wide context, 0 for any other and for NULL.  gecm_wide_max_bits: 1311; pure host code. */
+int gecm_create_wide(gecm_ctx **out, int device, const char *n_str, int digitbits);
+int gecm_is_wide(const gecm_ctx *ctx);
+int gecm_wide_max_bits(void);
+
 #ifdef __cplusplus
 }
 #endif
