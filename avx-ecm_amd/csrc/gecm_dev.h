@@ -177,20 +177,18 @@ int gecm_dev_s2_download(gecm_dev *d, uint32_t *acc, uint32_t *fail);
  * 1 < gcd(value, N) < N; g = the gcds ([limb][curve]); either output may be NULL. */
 int gecm_dev_gcd_scan(gecm_dev *d, int which, uint32_t *flags, uint32_t *g);
 
-/* ---- P-1 and P+1 stage 1: one residue per lane, in X of the batch (gecm_dev_upload_plain with z = 1) ----
- * gecm_dev_stage1_unit: the tape of gecm_dev_set_tape on every residue, x <- x^E (P-1) or V_E(x) (P+1), canonical;
- * asynchronous like gecm_dev_stage1, one lane per residue, any kind of context (lane-packed where the per-lane kernels
- * are built).  gecm_dev_gcd_scan_off: gecm_dev_gcd_scan of x - off, off = 1 (P-1) or 2 (P+1). */
-#define GECM_UNIT_PM1 1
-#define GECM_UNIT_PP1 2
-int gecm_dev_stage1_unit(gecm_dev *d, int method);
-/* ---- the same with a residue per 16-lane DPP row (csrc/gecm_row.hpp: k_unit_row) ----
- * gecm_dev_set_unit_rowconst: the constant sets of the kernel, one per modulus (gecm_rowk.h: GECM_UROW_SET words each; a
+/* ---- P-1 and P+1 stage 1: the residues in X of the batch (gecm_dev_upload_plain with z = 1) ----
+ * gecm_dev_stage1_unit_lanes: the tape of gecm_dev_set_tape on every residue, x <- x^E (P-1) or V_E(x) (P+1), canonical;
+ * asynchronous and cut into launches like gecm_dev_stage1, on any kind of context (lane-packed where the per-lane kernels
+ * are built).  lanes = 1: a residue per lane.  lanes = 16: a residue per 16-lane DPP row (csrc/gecm_row.hpp:
+ * k_unit_row) and canon per launch, -2 without constants.  gecm_dev_last_lanes is then `lanes`.
+ * gecm_dev_set_unit_rowconst: the constant sets of k_unit_row, one per modulus (gecm_rowk.h: GECM_UROW_SET words each; a
  * single-N context has one, a multi-modulus context one for every modulus gecm_dev_set_groups names, in that order), with
  * nq limbs per lane and rows per multiply of the context's limb count (gecm_row_shape).  Host memory, copied before it
  * returns.  gecm_dev_unit_rows_ready: are there sets for the moduli of the batch?
- * gecm_dev_stage1_unit_lanes: lanes = 1 is gecm_dev_stage1_unit; lanes = 16 runs k_unit_row and canon per launch on any
- * kind of context (-2 without constants), cut as the one-lane path cuts the tape; gecm_dev_last_lanes is then 16. */
+ * gecm_dev_gcd_scan_off: gecm_dev_gcd_scan of x - off, off = 1 (P-1) or 2 (P+1). */
+#define GECM_UNIT_PM1 1
+#define GECM_UNIT_PP1 2
 int gecm_dev_set_unit_rowconst(gecm_dev *d, int nq, int rows, uint32_t ngroups, const uint32_t *words);
 int gecm_dev_unit_rows_ready(gecm_dev *d);
 int gecm_dev_stage1_unit_lanes(gecm_dev *d, int method, int lanes);

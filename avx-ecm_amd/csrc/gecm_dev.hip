@@ -59,6 +59,14 @@ extern "C" const int *gecm_dev_supported_nl(void)
 #define GECM_S2_WAVES_PER_SIMD 16         // wavefronts per SIMD a pair-walk launch is cut up for (gecm_dev_s2_init)
 #endif
 #define GECM_S2_MAX_SLICES 64
+// Constant sets of a row kernel in device memory, one per modulus: `sets` of them (0 = not available), for nq limbs per
+// lane and `rows` rows of a multiply.
+struct row_consts {
+    uint32_t *d = nullptr;
+    size_t cap = 0;
+    uint32_t sets = 0;
+    int nq = 0, rows = 0;
+};
 struct gecm_dev {
     int device = 0;
     int nl = 0;
@@ -91,17 +99,10 @@ struct gecm_dev {
     float last_ms = 0.f;
     bool timed = false;
     uint32_t *dModQ = nullptr;   // N and K' limbs padded to 40 each, for the eight-lane kernel
-    uint32_t *dRowC = nullptr;   // constants of the 32-lane kernel (gecm_dev_set_rowconst), GECM_ROW_KINDS x GECM_ROW_WORDS
-    int row_nq = 0, row_rows = 0; // limbs per lane and rows of a multiply there; 0 = not available
-    uint32_t *dURowC = nullptr;  // constant sets of the 16-lane method kernel (gecm_dev_set_unit_rowconst), one per modulus
-    size_t urow_cap = 0;
-    uint32_t urow_groups = 0;     // sets dURowC holds; 0 = not available
-    int urow_nq = 0, urow_rows = 0;
-    uint32_t *dMRowC = nullptr;  // constant sets of the 32-lane kernel on a multi-modulus batch (gecm_dev_set_multi_rowconst)
-    size_t mrow_cap = 0;
-    uint32_t mrow_groups = 0;     // sets dMRowC holds; 0 = not available
-    int mrow_nq = 0, mrow_rows = 0;
-    int fform = 0;        // +1 / -1 / 2: modulus is 2^k - 1 / 2^k + 1 / 2^k - c and stage 1 uses the special multiply (gecm_dev_set_fform)
+    // constant sets of the row kernels (set_row_consts): the 32-lane kernel's one set of a single N (gecm_dev_set_rowconst),
+    // the 16-lane method kernel's (_set_unit_rowconst) and the 32-lane kernel's on a multi-modulus batch (_set_multi_rowconst)
+    row_consts rowc, urowc, mrowc;
+    int fform = 0;       // +1 / -1 / 2: modulus is 2^k - 1 / 2^k + 1 / 2^k - c and stage 1 uses the special multiply (gecm_dev_set_fform)
     int cus = 0;          // compute units of the device (4 SIMDs each)
     int last_lanes = 0;   // lanes per curve the last stage-1 launch used
     std::string last_kernel;   // and the kernel's name as rocprofv3 prints it
@@ -170,27 +171,22 @@ static gecm_modconst modconst(const gecm_dev *d)
     return mc;
 }
 
-// Has the context what operation `fn` needs?  A batch, on a multi-modulus context the batch's moduli, and where the
-// operation inverts, r3.
-static int ready(const gecm_dev *d, const char *fn, bool inverts)
+// Has the context what operation `fn` needs?  NEEDS_TABLE: a kernel table of the limb count, which a wide context
+// (gecm_dev_open_wide) has not.  NEEDS_BATCH: a batch, and on a multi-modulus context the batch's moduli.  NEEDS_R3: those,
+// and r3 (the operation inverts).  Asked for together, they are looked at in that order.
+enum : unsigned { NEEDS_TABLE = 1, NEEDS_BATCH = 2, NEEDS_R3 = 4 };
+static int ready(const gecm_dev *d, const char *fn, unsigned needs)
 {
-    const char *lacks = !d->stride                   ? "no batch (gecm_dev_resize)"
-                        : d->multi && !d->have_groups ? "the moduli of the batch are not set (gecm_dev_set_groups)"
-                        : inverts && !d->mod.r3       ? "the context was opened without inversion constants (r3)"
-                                                      : nullptr;
+    const char *lacks = (needs & NEEDS_TABLE) && d->wide       ? "not available on a wide context (gecm_dev_open_wide)"
+                        : !(needs & (NEEDS_BATCH | NEEDS_R3))  ? nullptr
+                        : !d->stride                           ? "no batch (gecm_dev_resize)"
+                        : d->multi && !d->have_groups          ? "the moduli of the batch are not set (gecm_dev_set_groups)"
+                        : (needs & NEEDS_R3) && !d->mod.r3     ? "the context was opened without inversion constants (r3)"
+                                                               : nullptr;
     if (!lacks) return 0;
     g_err = std::string(fn) + ": " + lacks;
     return -2;
 }
-
-// What a wide context (gecm_dev_open_wide) does not serve: everything that needs a kernel table of the limb count.
-#define REFUSE_WIDE(d, fn)                                                                    \
-    do {                                                                                      \
-        if ((d)->wide) {                                                                      \
-            g_err = fn ": not available on a wide context (gecm_dev_open_wide)";              \
-            return -2;                                                                        \
-        }                                                                                     \
-    } while (0)
 
 // A device array that only grows: room for `want` elements at *p, of which *cap says how many it has.  What it held is
 // not kept.
@@ -206,6 +202,30 @@ static int grow(T **p, size_t *cap, size_t want)
     return 0;
 }
 
+// What every context starts from: the device checked and made current, its compute units, the stream and the two events.
+// fn names the caller in the error text.
+static int open_common(gecm_dev **out, const char *fn, int device, int nl)
+{
+    int cnt = 0;
+    HIPCHK(hipGetDeviceCount(&cnt));
+    if (device < 0 || device >= cnt) {
+        g_err = std::string(fn) + ": no such device";
+        return -2;
+    }
+    HIPCHK(hipSetDevice(device));
+    int cus = 0;
+    HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
+    gecm_dev *d = new gecm_dev;
+    d->device = device;
+    d->cus = cus;
+    d->nl = nl;
+    HIPCHK(hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking));
+    HIPCHK(hipEventCreate(&d->ev0));
+    HIPCHK(hipEventCreate(&d->ev1));
+    *out = d;
+    return 0;
+}
+
 extern "C" int gecm_dev_open(gecm_dev **out, int device, int nl, const gecm_devmod *m, int multi)
 {
     const auto *kt = kernels_for(nl);
@@ -217,19 +237,8 @@ extern "C" int gecm_dev_open(gecm_dev **out, int device, int nl, const gecm_devm
         g_err = "gecm_dev_open: the modulus constants are incomplete";
         return -2;
     }
-    int cnt = 0;
-    HIPCHK(hipGetDeviceCount(&cnt));
-    if (device < 0 || device >= cnt) {
-        g_err = "gecm_dev_open: no such device";
-        return -2;
-    }
-    HIPCHK(hipSetDevice(device));
-    int cus = 0;
-    HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
-    gecm_dev *d = new gecm_dev;
-    d->device = device;
-    d->cus = cus;
-    d->nl = nl;
+    gecm_dev *d = nullptr;
+    if (const int rc = open_common(&d, "gecm_dev_open", device, nl)) return rc;
     d->k1 = kt->p1();
     d->k2 = kt->p2();
     d->multi = multi != 0;
@@ -250,15 +259,12 @@ extern "C" int gecm_dev_open(gecm_dev **out, int device, int nl, const gecm_devm
         HIPCHK(hipMalloc(&d->dModQ, sizeof h));
         HIPCHK(hipMemcpy(d->dModQ, h, sizeof h, hipMemcpyHostToDevice));
     }
-    HIPCHK(hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking));
-    HIPCHK(hipEventCreate(&d->ev0));
-    HIPCHK(hipEventCreate(&d->ev1));
     *out = d;
     return 0;
 }
 
-// A wide context (gecm_dev.h): a limb count of the wide shapes, which kernels_for() does not know.  The stream, the
-// events and rho; the row kernel's constants come with gecm_dev_set_rowconst.
+// A wide context (gecm_dev.h): a limb count of the wide shapes, which kernels_for() does not know.  It has rho; the row
+// kernel's constants come with gecm_dev_set_rowconst.
 extern "C" int gecm_dev_open_wide(gecm_dev **out, int device, int nl, uint32_t rho)
 {
     bool shape = false;
@@ -269,98 +275,69 @@ extern "C" int gecm_dev_open_wide(gecm_dev **out, int device, int nl, uint32_t r
         g_err = "gecm_dev_open_wide: " + std::to_string(nl) + " limbs is not a limb count of the wide shapes";
         return -2;
     }
-    int cnt = 0;
-    HIPCHK(hipGetDeviceCount(&cnt));
-    if (device < 0 || device >= cnt) {
-        g_err = "gecm_dev_open_wide: no such device";
-        return -2;
-    }
-    HIPCHK(hipSetDevice(device));
-    int cus = 0;
-    HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
-    gecm_dev *d = new gecm_dev;
-    d->device = device;
-    d->cus = cus;
-    d->nl = nl;
-    d->wide = true;
-    d->mod.rho = rho;
-    HIPCHK(hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking));
-    HIPCHK(hipEventCreate(&d->ev0));
-    HIPCHK(hipEventCreate(&d->ev1));
-    *out = d;
+    if (const int rc = open_common(out, "gecm_dev_open_wide", device, nl)) return rc;
+    (*out)->wide = true;
+    (*out)->mod.rho = rho;
     return 0;
 }
 
 extern "C" int gecm_dev_is_wide(const gecm_dev *d) { return d && d->wide; }
 
-extern "C" int gecm_dev_set_rowconst(gecm_dev *d, int nq, int rows, const uint32_t *words)
+// `sets` constant sets of set_words words each into a store, for nq limbs per lane and `rows` rows of a multiply.
+// Synchronous: the host array may go away when this returns.
+static int set_row_consts(gecm_dev *d, const char *fn, row_consts *store, size_t set_words, uint32_t sets, int nq, int rows,
+                          const uint32_t *words)
 {
     HIPCHK(hipSetDevice(d->device));
-    if (nq < 1 || nq > GECM_ROW_MAXNQ || 16 * nq > GECM_ROW_WORDS || rows <= 16 * (nq - 1) || rows > 16 * nq) {
-        g_err = "gecm_dev_set_rowconst: limbs per lane out of range";
+    if (nq < 1 || nq > GECM_ROW_MAXNQ || 16 * nq > GECM_ROW_WORDS || rows <= 16 * (nq - 1) || rows > 16 * nq || !sets || !words) {
+        g_err = std::string(fn) + ": limbs per lane out of range, or no constants";
         return -2;
     }
+    store->sets = 0;
+    if (grow(&store->d, &store->cap, sets * set_words)) return -1;
+    HIPCHK(hipMemcpyAsync(store->d, words, sets * set_words * sizeof(uint32_t), hipMemcpyHostToDevice, d->stream));
+    HIPCHK(hipStreamSynchronize(d->stream));
+    store->nq = nq;
+    store->rows = rows;
+    store->sets = sets;
+    return 0;
+}
+
+extern "C" int gecm_dev_set_rowconst(gecm_dev *d, int nq, int rows, const uint32_t *words)
+{
     if (d->wide && (nq != 3 || rows != d->nl + 1)) {
         g_err = "gecm_dev_set_rowconst: a wide context takes three limbs per lane and its own limb count + 1 rows";
         return -2;
     }
-    if (!d->dRowC) HIPCHK(hipMalloc(&d->dRowC, GECM_ROW_KINDS * GECM_ROW_WORDS * sizeof(uint32_t)));
-    HIPCHK(hipMemcpy(d->dRowC, words, GECM_ROW_KINDS * GECM_ROW_WORDS * sizeof(uint32_t), hipMemcpyHostToDevice));
-    d->row_nq = nq;
-    d->row_rows = rows;
-    return 0;
+    return set_row_consts(d, "gecm_dev_set_rowconst", &d->rowc, GECM_ROW_KINDS * GECM_ROW_WORDS, 1, nq, rows, words);
 }
 
 extern "C" int gecm_dev_set_unit_rowconst(gecm_dev *d, int nq, int rows, uint32_t ngroups, const uint32_t *words)
 {
-    REFUSE_WIDE(d, "gecm_dev_set_unit_rowconst");
-    HIPCHK(hipSetDevice(d->device));
-    if (nq < 1 || nq > GECM_ROW_MAXNQ || 16 * nq > GECM_ROW_WORDS || rows <= 16 * (nq - 1) || rows > 16 * nq || !ngroups ||
-        !words) {
-        g_err = "gecm_dev_set_unit_rowconst: limbs per lane out of range, or no constants";
-        return -2;
-    }
-    d->urow_groups = 0;
-    if (grow(&d->dURowC, &d->urow_cap, (size_t)ngroups * GECM_UROW_SET)) return -1;
-    // synchronous: the host array may go away when this returns
-    HIPCHK(hipMemcpyAsync(d->dURowC, words, (size_t)ngroups * GECM_UROW_SET * sizeof(uint32_t), hipMemcpyHostToDevice,
-                          d->stream));
-    HIPCHK(hipStreamSynchronize(d->stream));
-    d->urow_nq = nq;
-    d->urow_rows = rows;
-    d->urow_groups = ngroups;
-    return 0;
+    if (ready(d, "gecm_dev_set_unit_rowconst", NEEDS_TABLE)) return -2;
+    return set_row_consts(d, "gecm_dev_set_unit_rowconst", &d->urowc, GECM_UROW_SET, ngroups, nq, rows, words);
 }
 
 extern "C" int gecm_dev_set_multi_rowconst(gecm_dev *d, int nq, int rows, uint32_t ngroups, const uint32_t *words)
 {
-    REFUSE_WIDE(d, "gecm_dev_set_multi_rowconst");
-    HIPCHK(hipSetDevice(d->device));
-    if (!d->multi || nq < 1 || nq > GECM_ROW_MAXNQ || 16 * nq > GECM_ROW_WORDS || rows <= 16 * (nq - 1) || rows > 16 * nq ||
-        !ngroups || !words) {
-        g_err = "gecm_dev_set_multi_rowconst: not a multi-modulus context, limbs per lane out of range, or no constants";
+    if (ready(d, "gecm_dev_set_multi_rowconst", NEEDS_TABLE)) return -2;
+    if (!d->multi) {
+        g_err = "gecm_dev_set_multi_rowconst: not a multi-modulus context";
         return -2;
     }
-    d->mrow_groups = 0;
-    if (grow(&d->dMRowC, &d->mrow_cap, (size_t)ngroups * GECM_MROW_SET)) return -1;
-    // synchronous: the host array may go away when this returns
-    HIPCHK(hipMemcpyAsync(d->dMRowC, words, (size_t)ngroups * GECM_MROW_SET * sizeof(uint32_t), hipMemcpyHostToDevice,
-                          d->stream));
-    HIPCHK(hipStreamSynchronize(d->stream));
-    d->mrow_nq = nq;
-    d->mrow_rows = rows;
-    d->mrow_groups = ngroups;
-    return 0;
+    return set_row_consts(d, "gecm_dev_set_multi_rowconst", &d->mrowc, GECM_MROW_SET, ngroups, nq, rows, words);
 }
 
 extern "C" int gecm_dev_cus(gecm_dev *d) { return d->cus; }
 
-extern "C" int gecm_dev_multi_rows_ready(gecm_dev *d) { return d->multi && d->mrow_groups != 0 && d->mrow_groups == d->ngroups; }
-
-extern "C" int gecm_dev_unit_rows_ready(gecm_dev *d)
+// are there sets in the store for the moduli of the batch?
+static bool row_consts_ready(const gecm_dev *d, const row_consts &store)
 {
-    return d->urow_groups != 0 && d->urow_groups == (d->multi ? d->ngroups : 1u);
+    return store.sets != 0 && store.sets == (d->multi ? d->ngroups : 1u);
 }
+
+extern "C" int gecm_dev_multi_rows_ready(gecm_dev *d) { return d->multi && row_consts_ready(d, d->mrowc); }
+extern "C" int gecm_dev_unit_rows_ready(gecm_dev *d) { return row_consts_ready(d, d->urowc); }
 
 static void free_state(gecm_dev *d)
 {
@@ -386,9 +363,7 @@ extern "C" void gecm_dev_close(gecm_dev *d)
     free_state(d);
     free_s2(d);
     (void)hipFree(d->dModQ);
-    (void)hipFree(d->dRowC);
-    (void)hipFree(d->dURowC);
-    (void)hipFree(d->dMRowC);
+    for (row_consts *store : {&d->rowc, &d->urowc, &d->mrowc}) (void)hipFree(store->d);
     (void)hipFree(d->dKeep);
     (void)hipFree(d->dSteps);
     (void)hipFree(d->dFlags);
@@ -478,7 +453,7 @@ extern "C" int gecm_dev_upload(gecm_dev *d, const uint32_t *X, const uint32_t *Z
 
 extern "C" int gecm_dev_upload_xz(gecm_dev *d, const uint32_t *X, const uint32_t *Z)
 {
-    REFUSE_WIDE(d, "gecm_dev_upload_xz");
+    if (ready(d, "gecm_dev_upload_xz", NEEDS_TABLE)) return -2;
     HIPCHK(hipSetDevice(d->device));
     if (upload_soa(d, d->dX, X)) return -1;
     if (upload_soa(d, d->dZ, Z)) return -1;
@@ -490,9 +465,8 @@ extern "C" int gecm_dev_upload_xz(gecm_dev *d, const uint32_t *X, const uint32_t
 // to_mont kernel, through the scratch planes the downloads use.  The padding lanes get x = z = 1.
 extern "C" int gecm_dev_upload_plain(gecm_dev *d, const uint32_t *x, const uint32_t *z)
 {
-    REFUSE_WIDE(d, "gecm_dev_upload_plain");
+    if (ready(d, "gecm_dev_upload_plain", NEEDS_TABLE | NEEDS_BATCH)) return -2;
     HIPCHK(hipSetDevice(d->device));
-    if (ready(d, "gecm_dev_upload_plain", false)) return -2;
     if (upload_soa(d, d->dT0, x)) return -1;
     if (upload_soa(d, d->dT1, z)) return -1;
     const size_t pad = d->stride - d->ncurves;        // at most 63: limb 0 of the padding lanes, set to 1
@@ -510,7 +484,7 @@ extern "C" int gecm_dev_upload_plain(gecm_dev *d, const uint32_t *x, const uint3
 
 extern "C" int gecm_dev_download_s(gecm_dev *d, uint32_t *S)
 {
-    REFUSE_WIDE(d, "gecm_dev_download_s");
+    if (ready(d, "gecm_dev_download_s", NEEDS_TABLE)) return -2;
     HIPCHK(hipSetDevice(d->device));
     if (!d->stride) {
         g_err = "gecm_dev_download_s: no batch";
@@ -524,23 +498,10 @@ extern "C" int gecm_dev_download_s(gecm_dev *d, uint32_t *S)
 // ---------------------------------------------------------------- curve construction
 extern "C" float gecm_dev_last_build_ms(gecm_dev *d) { return d->build_ms; }
 
-extern "C" int gecm_dev_build(gecm_dev *d, const uint64_t *sigma, size_t count, uint32_t *flags)
+// The end of gecm_dev_build, _build_param and _normalize, whose kernels ev0 precedes: their time into build_ms and the
+// flags of `count` positions to the host.  Synchronous.
+static int timed_flags(gecm_dev *d, uint32_t *flags, size_t count)
 {
-    REFUSE_WIDE(d, "gecm_dev_build");
-    HIPCHK(hipSetDevice(d->device));
-    if (!d->stride || count != d->ncurves || !sigma || !flags) {
-        g_err = "gecm_dev_build: no batch of that many curves (gecm_dev_resize)";
-        return -2;
-    }
-    if (ready(d, "gecm_dev_build", true)) return -2;
-    if (grow(&d->dSigma, &d->sigma_cap, d->stride) || grow(&d->dFlags, &d->flags_cap, d->stride)) return -1;
-    // the padding lanes build sigma = 0: computed, never flagged or read
-    HIPCHK(hipMemsetAsync(d->dSigma, 0, d->stride * sizeof(uint64_t), d->stream));
-    HIPCHK(hipMemcpyAsync(d->dSigma, sigma, count * sizeof(uint64_t), hipMemcpyHostToDevice, d->stream));
-    gecm_modconst mc = modconst(d);
-    HIPCHK(hipEventRecord(d->ev0, d->stream));
-    d->k1->build(d->stream, &mc, d->dSigma, d->dX, d->dZ, d->dS, d->dFlags, d->stride);
-    HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(d->ev1, d->stream));
     HIPCHK(hipMemcpyAsync(flags, d->dFlags, count * 4, hipMemcpyDeviceToHost, d->stream));
     HIPCHK(hipStreamSynchronize(d->stream));
@@ -549,9 +510,29 @@ extern "C" int gecm_dev_build(gecm_dev *d, const uint64_t *sigma, size_t count, 
     return 0;
 }
 
+extern "C" int gecm_dev_build(gecm_dev *d, const uint64_t *sigma, size_t count, uint32_t *flags)
+{
+    if (ready(d, "gecm_dev_build", NEEDS_TABLE)) return -2;
+    HIPCHK(hipSetDevice(d->device));
+    if (!d->stride || count != d->ncurves || !sigma || !flags) {
+        g_err = "gecm_dev_build: no batch of that many curves (gecm_dev_resize)";
+        return -2;
+    }
+    if (ready(d, "gecm_dev_build", NEEDS_R3)) return -2;
+    if (grow(&d->dSigma, &d->sigma_cap, d->stride) || grow(&d->dFlags, &d->flags_cap, d->stride)) return -1;
+    // the padding lanes build sigma = 0: computed, never flagged or read
+    HIPCHK(hipMemsetAsync(d->dSigma, 0, d->stride * sizeof(uint64_t), d->stream));
+    HIPCHK(hipMemcpyAsync(d->dSigma, sigma, count * sizeof(uint64_t), hipMemcpyHostToDevice, d->stream));
+    gecm_modconst mc = modconst(d);
+    HIPCHK(hipEventRecord(d->ev0, d->stream));
+    d->k1->build(d->stream, &mc, d->dSigma, d->dX, d->dZ, d->dS, d->dFlags, d->stride);
+    HIPCHK(hipGetLastError());
+    return timed_flags(d, flags, count);
+}
+
 extern "C" int gecm_dev_build_param(gecm_dev *d, const uint64_t *sigma, const uint8_t *param, size_t count, uint32_t *flags)
 {
-    REFUSE_WIDE(d, "gecm_dev_build_param");
+    if (ready(d, "gecm_dev_build_param", NEEDS_TABLE)) return -2;
     HIPCHK(hipSetDevice(d->device));
     if (!d->stride || count != d->ncurves || !sigma || !param || !flags) {
         g_err = "gecm_dev_build_param: no batch of that many curves (gecm_dev_resize)";
@@ -565,7 +546,7 @@ extern "C" int gecm_dev_build_param(gecm_dev *d, const uint64_t *sigma, const ui
         }
         (param[i] ? other : suyama) = true;
     }
-    if (ready(d, "gecm_dev_build_param", suyama)) return -2;
+    if (ready(d, "gecm_dev_build_param", suyama ? NEEDS_R3 : NEEDS_BATCH)) return -2;
     if (grow(&d->dSigma, &d->sigma_cap, d->stride) || grow(&d->dFlags, &d->flags_cap, d->stride) ||
         grow(&d->dParam, &d->param_cap, d->stride))
         return -1;
@@ -588,19 +569,13 @@ extern "C" int gecm_dev_build_param(gecm_dev *d, const uint64_t *sigma, const ui
     HIPCHK(hipGetLastError());
     if (other) d->k1->build_param(d->stream, &mc, d->dSigma, d->dParam, d->dX, d->dZ, d->dS, d->dFlags, d->stride);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(d->ev1, d->stream));
-    HIPCHK(hipMemcpyAsync(flags, d->dFlags, count * 4, hipMemcpyDeviceToHost, d->stream));
-    HIPCHK(hipStreamSynchronize(d->stream));
-    HIPCHK(hipEventElapsedTime(&d->build_ms, d->ev0, d->ev1));
-    d->timed = false;
-    return 0;
+    return timed_flags(d, flags, count);
 }
 
 extern "C" int gecm_dev_normalize(gecm_dev *d, uint32_t *flags)
 {
-    REFUSE_WIDE(d, "gecm_dev_normalize");
+    if (ready(d, "gecm_dev_normalize", NEEDS_TABLE | NEEDS_R3)) return -2;
     HIPCHK(hipSetDevice(d->device));
-    if (ready(d, "gecm_dev_normalize", true)) return -2;
     if (!d->ncurves || !flags) {
         g_err = "gecm_dev_normalize: no curves, or nowhere to put their flags";
         return -2;
@@ -610,18 +585,12 @@ extern "C" int gecm_dev_normalize(gecm_dev *d, uint32_t *flags)
     HIPCHK(hipEventRecord(d->ev0, d->stream));
     d->k1->normalize(d->stream, &mc, d->dX, d->dZ, d->dFlags, d->stride);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(d->ev1, d->stream));
-    HIPCHK(hipMemcpyAsync(flags, d->dFlags, d->ncurves * 4, hipMemcpyDeviceToHost, d->stream));
-    HIPCHK(hipStreamSynchronize(d->stream));
-    HIPCHK(hipEventElapsedTime(&d->build_ms, d->ev0, d->ev1));
-    d->timed = false;
-    return 0;
+    return timed_flags(d, flags, d->ncurves);
 }
 
 extern "C" int gecm_dev_fill_twin(gecm_dev *dst, gecm_dev *src)
 {
-    REFUSE_WIDE(dst, "gecm_dev_fill_twin");
-    REFUSE_WIDE(src, "gecm_dev_fill_twin");
+    if (ready(dst, "gecm_dev_fill_twin", NEEDS_TABLE) || ready(src, "gecm_dev_fill_twin", NEEDS_TABLE)) return -2;
     HIPCHK(hipSetDevice(src->device));
     if (dst->device != src->device || !src->stride || dst->stride != src->stride || dst->ncurves != src->ncurves ||
         src->multi || dst->multi) {
@@ -711,14 +680,14 @@ extern "C" int gecm_dev_auto_lanes(gecm_dev *d)
      * 12,288), the eight-lane layout at exactly one or two wavefronts per SIMD in between (8192 curves: 32.7k against
      * 30.6k). */
     if (d->wide) return 32;                           // the one layout it has
-    if (!d->multi && !d->fform && d->row_nq && d->nl >= 10 && d->stride) {
+    if (!d->multi && !d->fform && d->rowc.sets && d->nl >= 10 && d->stride) {
         const size_t s = d->stride, cu = (size_t)d->cus;
-        if (d->row_nq == 1 ? s <= cu * 56 : (s <= cu * 30 || (s > cu * 32 && s <= cu * 50))) return 32;
+        if (d->rowc.nq == 1 ? s <= cu * 56 : (s <= cu * 30 || (s > cu * 32 && s <= cu * 50))) return 32;
     }
     /* Below 10 limbs the 32-lane layout still has the shortest chain per curve (9 rows of 6 instructions): while the
      * batch leaves it at one wavefront per SIMD or less (8 curves per CU) it is latency that counts — 8 curves of a
      * 204-bit N at B1 = 3e6: 4.11 s against 7.15 s (eight lanes) and 8.42 s (two), tools/multirange_time.py. */
-    if (!d->multi && !d->fform && d->row_nq && d->nl < 10 && d->stride && d->stride <= (size_t)d->cus * 8) return 32;
+    if (!d->multi && !d->fform && d->rowc.sets && d->nl < 10 &&d->stride && d->stride <= (size_t)d->cus * 8) return 32;
     if (!d->multi && !d->fform && d->dModQ && d->stride && d->stride <= (size_t)d->cus * (d->nl >= 19 ? 64 : 32)) return 8;
     if (d->nl >= 26) return 2;
     const size_t full = (size_t)d->cus * 4 * 128;
@@ -733,7 +702,7 @@ extern "C" int gecm_dev_auto_lanes(gecm_dev *d)
  * 284 ms), the crossbar from there (6144: 363 against 373; equal from 8192 on, tools/row_check.py). */
 static bool row_a_lds(const gecm_dev *d)
 {
-    return d->row_nq == 1 && d->stride > (size_t)d->cus * 16;
+    return d->rowc.nq == 1 && d->stride > (size_t)d->cus * 16;
 }
 
 extern "C" int gecm_dev_last_lanes(gecm_dev *d) { return d->last_lanes; }
@@ -747,67 +716,111 @@ extern "C" int gecm_dev_fform_generic_limbs(int nl)
 
 extern "C" void gecm_dev_set_fform(gecm_dev *d, int form) { if (d->wide) return; d->fform = form == 2 ? 2 : form > 0 ? 1 : form < 0 ? -1 : 0; }
 
-/* multi_rows: the 32-lane layout on a multi-modulus batch of either packing (gecm_dev_stage1_multi_rows);
- * lanes_per_curve is then not looked at. */
-static int stage1_run(gecm_dev *d, int lanes_per_curve, bool multi_rows)
+/* ---- stage 1: one plan, made from the request, and one run of it over the cuts of the tape ----
+ * The request: a batch of curves with the lanes per curve asked for (0 = gecm_dev_auto_lanes), or with multi_rows the
+ * 32-lane layout on a multi-modulus batch of either packing (lanes is then not looked at); or a P-1 / P+1
+ * batch (unit; method GECM_UNIT_PM1 / _PP1) with 1 or 16 lanes per residue (§22). */
+struct s1_request {
+    bool unit;           // a P-1 / P+1 batch, of `method`
+    int method, lanes;
+    bool multi_rows;
+};
+enum s1_kind {
+    S1_TABLE,        // stage1 of the limb count's table: one, two or eight lanes per curve, every constants source
+    S1_TABLE_UNIT,   // its stage1_unit: a residue per lane
+    S1_ROW,          // 32 lanes per curve (gecm_rowk.h) ...
+    S1_ROW_WIDE,     // ... at the wide shapes
+    S1_ROW_MULTI,    // ... on a multi-modulus batch
+    S1_UNIT_ROW      // a residue per 16-lane row
+};
+struct s1_plan {
+    s1_kind kind;
+    const char *fn;      // the exported call, for the text of an error
+    int lanes;           // per curve or residue
+    bool a_lds, pp1;     // S1_ROW: operand limbs through the LDS crossbar (row_a_lds); the method is P+1
+    bool canon_after;    // the kernel leaves lazy values and canon follows every launch
+    char name[96];       // the kernel's name as rocprofv3 prints it
+};
+
+/* Every refusal of a stage-1 launch and every kernel name. */
+static int s1_make_plan(gecm_dev *d, const s1_request &rq, s1_plan *p)
 {
+    auto refuse = [](const char *why) { g_err = why; return -2; };
+    *p = {};                      // S1_TABLE, until a branch says otherwise
+    p->fn = rq.unit ? "gecm_dev_stage1_unit" : rq.multi_rows ? "gecm_dev_stage1_multi_rows" : "gecm_dev_stage1";
+    const char *entry = rq.unit ? "gecm_dev_stage1_unit" : "gecm_dev_stage1";
+    if (rq.unit && ready(d, "gecm_dev_stage1_unit_lanes", NEEDS_TABLE)) return -2;
+    if (rq.multi_rows && ready(d, p->fn, NEEDS_TABLE)) return -2;
     HIPCHK(hipSetDevice(d->device));
-    if (ready(d, "gecm_dev_stage1", false)) return -2;
+    if (ready(d, entry, NEEDS_BATCH)) return -2;
     if (!d->dTape) {
-        g_err = "gecm_dev_stage1: no tape";
+        g_err = std::string(entry) + ": no tape";
         return -2;
     }
-    int lanes = multi_rows ? 32 : lanes_per_curve ? lanes_per_curve : gecm_dev_auto_lanes(d);
-    char nm[96];   // the kernel's name as rocprofv3 prints it
-    if (d->wide) {
-        if (lanes != 32 || !d->row_nq) {
-            g_err = !d->row_nq ? "gecm_dev_stage1: the wide context has no constants (gecm_dev_set_rowconst)"
-                               : "gecm_dev_stage1: a wide context runs with 32 lanes per curve (0 or 32)";
-            return -2;
-        }
-        snprintf(nm, sizeof nm, "k_stage1_row<%d, %d, false>", d->row_nq, d->row_rows);
-    } else if (multi_rows) {
-        if (!gecm_dev_multi_rows_ready(d)) {
-            g_err = "gecm_dev_stage1_multi_rows: the 32-lane kernel has no constants for this batch's moduli "
-                    "(gecm_dev_set_multi_rowconst)";
-            return -2;
-        }
-        snprintf(nm, sizeof nm, "k_stage1_row_multi<%d, %d>", d->mrow_nq, d->mrow_rows);
+    int lanes = rq.unit ? rq.lanes : rq.multi_rows ? 32 : rq.lanes ? rq.lanes : gecm_dev_auto_lanes(d);
+    const char *base = nullptr;   // S1_TABLE, S1_TABLE_UNIT: the kernel is base<limbs>
+    if (rq.unit) {
+        if (rq.method != GECM_UNIT_PM1 && rq.method != GECM_UNIT_PP1) return refuse("gecm_dev_stage1_unit: the method must be P-1 or P+1");
+        if (lanes != 1 && lanes != 16) return refuse("gecm_dev_stage1_unit: lanes per residue must be 1 or 16");
+        if (lanes == 16 && !row_consts_ready(d, d->urowc))
+            return refuse("gecm_dev_stage1_unit: the 16-lane kernel has no constants for this batch's moduli (gecm_dev_set_unit_rowconst)");
+        if (d->multi && d->lane_packed && !d->k1->has_lane) return refuse("gecm_dev_stage1_unit: no per-lane kernels at this limb count");
+        p->kind = lanes == 16 ? S1_UNIT_ROW : S1_TABLE_UNIT;
+        p->pp1 = rq.method == GECM_UNIT_PP1;
+        base = !d->multi ? "k_unit" : d->lane_packed ? "k_unit_lane" : "k_unit_multi";
+    } else if (d->wide) {
+        if (!d->rowc.sets) return refuse("gecm_dev_stage1: the wide context has no constants (gecm_dev_set_rowconst)");
+        if (lanes != 32) return refuse("gecm_dev_stage1: a wide context runs with 32 lanes per curve (0 or 32)");
+        p->kind = S1_ROW_WIDE;
+    } else if (rq.multi_rows) {
+        if (!gecm_dev_multi_rows_ready(d))
+            return refuse("gecm_dev_stage1_multi_rows: the 32-lane kernel has no constants for this batch's moduli "
+                          "(gecm_dev_set_multi_rowconst)");
+        p->kind = S1_ROW_MULTI;
     } else if (d->multi && d->lane_packed) {
-        if (lanes_per_curve > 1) {
-            g_err = "gecm_dev_stage1: a lane-packed multi-modulus batch runs with one lane per curve";
-            return -2;
-        }
+        if (rq.lanes > 1) return refuse("gecm_dev_stage1: a lane-packed multi-modulus batch runs with one lane per curve");
         lanes = 1;
-        snprintf(nm, sizeof nm, "k_stage1_lane<%d>", d->nl);
+        base = "k_stage1_lane";
     } else if (d->multi) {
-        if (lanes != 1 && lanes != 2) {
-            g_err = "gecm_dev_stage1: a multi-modulus batch runs with 1 or 2 lanes per curve";
-            return -2;
-        }
-        snprintf(nm, sizeof nm, "%s<%d>", lanes == 2 ? "k_stage1_pair_multi" : "k_stage1_multi", d->nl);
+        if (lanes != 1 && lanes != 2) return refuse("gecm_dev_stage1: a multi-modulus batch runs with 1 or 2 lanes per curve");
+        base = lanes == 2 ? "k_stage1_pair_multi" : "k_stage1_multi";
     } else if (lanes == 32) {
-        if (d->fform || !d->row_nq) {
-            g_err = "gecm_dev_stage1: no 32-lane kernel for this modulus";
-            return -2;
-        }
-        snprintf(nm, sizeof nm, "k_stage1_row<%d, %d, %s>", d->row_nq, d->row_rows, row_a_lds(d) ? "true" : "false");
+        if (d->fform || !d->rowc.sets) return refuse("gecm_dev_stage1: no 32-lane kernel for this modulus");
+        p->kind = S1_ROW;
+        p->a_lds = row_a_lds(d);
     } else if (lanes == 8) {
-        if (d->fform || !d->dModQ) {
-            g_err = "gecm_dev_stage1: no eight-lane kernel for this modulus";
-            return -2;
-        }
-        snprintf(nm, sizeof nm, "k_stage1_quad<%d>", d->nl);
+        if (d->fform || !d->dModQ) return refuse("gecm_dev_stage1: no eight-lane kernel for this modulus");
+        base = "k_stage1_quad";
     } else if (lanes == 1 || lanes == 2) {
-        if (d->fform) snprintf(nm, sizeof nm, "%s<%d, Mod%c<%d> >", lanes == 2 ? "k_stage1_pair_f" : "k_stage1_f", d->nl,
-                               d->fform == 2 ? 'C' : d->fform > 0 ? 'F' : 'P', d->nl);
-        else snprintf(nm, sizeof nm, "%s<%d>", lanes == 2 ? "k_stage1_pair" : "k_stage1", d->nl);
-    } else {
-        g_err = "gecm_dev_stage1: lanes per curve must be 0 (auto), 1, 2, 8 or 32";
-        return -2;
+        base = d->fform ? (lanes == 2 ? "k_stage1_pair_f" : "k_stage1_f") : lanes == 2 ? "k_stage1_pair" : "k_stage1";
+    } else
+        return refuse("gecm_dev_stage1: lanes per curve must be 0 (auto), 1, 2, 8 or 32");
+    p->lanes = lanes;
+    p->canon_after = p->kind == S1_UNIT_ROW || (!rq.unit && lanes >= 8 && p->kind != S1_ROW_WIDE);
+    switch (p->kind) {
+    case S1_ROW:
+    case S1_ROW_WIDE:
+        snprintf(p->name, sizeof p->name, "k_stage1_row<%d, %d, %s>", d->rowc.nq, d->rowc.rows, p->a_lds ? "true" : "false");
+        break;
+    case S1_ROW_MULTI: snprintf(p->name, sizeof p->name, "k_stage1_row_multi<%d, %d>", d->mrowc.nq, d->mrowc.rows); break;
+    case S1_UNIT_ROW: snprintf(p->name, sizeof p->name, "k_unit_row<%d, %d>", d->urowc.nq, d->urowc.rows); break;
+    case S1_TABLE:
+        if (d->fform && !d->multi) {       // the special multiply (gecm_dev_set_fform)
+            snprintf(p->name, sizeof p->name, "%s<%d, Mod%c<%d> >", base, d->nl, d->fform == 2 ? 'C' : d->fform > 0 ? 'F' : 'P', d->nl);
+            break;
+        }
+        [[fallthrough]];
+    case S1_TABLE_UNIT: snprintf(p->name, sizeof p->name, "%s<%d>", base, d->nl); break;
     }
-    d->last_lanes = lanes;
-    d->last_kernel = nm;
+    return 0;
+}
+
+/* The plan's kernel over every cut of the tape (gecm_dev_set_tape), asynchronous on the context's stream: an event per
+ * launch (gecm_dev_stage1_progress), ev0 and ev1 around them all. */
+static int s1_run_plan(gecm_dev *d, const s1_plan &p)
+{
+    d->last_lanes = p.lanes;
+    d->last_kernel = p.name;
     gecm_modconst mc = modconst(d);
     HIPCHK(hipEventRecord(d->ev0, d->stream));
     d->cut_launches = d->tape_cuts.size() - 1;
@@ -819,29 +832,34 @@ static int stage1_run(gecm_dev *d, int lanes_per_curve, bool multi_rows)
     for (size_t cut = 0; cut + 1 < d->tape_cuts.size(); cut++) {
         const uint32_t *tp = d->dTape + d->tape_cuts[cut] / 4;
         const uint32_t tl = (uint32_t)(d->tape_cuts[cut + 1] - d->tape_cuts[cut]);
-        if (d->wide) {
+        int unbuilt = 0;     // a row launcher's answer where the shape is not built
+        switch (p.kind) {
+        case S1_TABLE: d->k1->stage1(d->stream, &mc, tp, tl, d->dX, d->dZ, d->dS, d->stride, d->dModQ, p.lanes, d->fform); break;
+        case S1_TABLE_UNIT: d->k1->stage1_unit(d->stream, &mc, tp, tl, d->dX, d->dZ, d->stride, p.pp1); break;
+        case S1_ROW:
+            unbuilt = gecm_launch_stage1_row(d->stream, d->rowc.nq, d->rowc.rows, tp, tl, d->dX, d->dZ, d->dS, d->stride,
+                                             (uint32_t)d->nl, d->rowc.d, d->mod.rho, p.a_lds);
+            break;
+        case S1_ROW_WIDE:
             // nothing canonicalises between the launches or after them: the exit value of a launch is inside the contract
             // of the next one's entry multiply, and the host reduces what it downloads
-            if (gecm_launch_stage1_row_wide(d->stream, d->row_rows, tp, tl, d->dX, d->dZ, d->dS, d->stride, (uint32_t)d->nl,
-                                            d->dRowC, d->mod.rho)) {
-                g_err = "gecm_dev_stage1: no 32-lane kernel for this limb count";
-                return -2;
-            }
-        } else if (multi_rows) {
-            if (gecm_launch_stage1_row_multi(d->stream, d->mrow_nq, d->mrow_rows, tp, tl, d->dX, d->dZ, d->dS, d->stride,
-                                             (uint32_t)d->nl, d->dMRowC, mc.curve_group, mc.block_group)) {
-                g_err = "gecm_dev_stage1_multi_rows: no 32-lane kernel for this limb count";
-                return -2;
-            }
-        } else if (lanes == 32) {
-            if (gecm_launch_stage1_row(d->stream, d->row_nq, d->row_rows, tp, tl, d->dX, d->dZ, d->dS, d->stride,
-                                       (uint32_t)d->nl, d->dRowC, d->mod.rho, row_a_lds(d))) {
-                g_err = "gecm_dev_stage1: no 32-lane kernel for this limb count";
-                return -2;
-            }
-        } else
-            d->k1->stage1(d->stream, &mc, tp, tl, d->dX, d->dZ, d->dS, d->stride, d->dModQ, lanes, d->fform);
-        if (lanes >= 8 && !d->wide) d->k1->canon(d->stream, &mc, d->dX, d->dZ, d->stride);   // the 8- and 32-lane kernels leave lazy values
+            unbuilt = gecm_launch_stage1_row_wide(d->stream, d->rowc.rows, tp, tl, d->dX, d->dZ, d->dS, d->stride, (uint32_t)d->nl,
+                                                  d->rowc.d, d->mod.rho);
+            break;
+        case S1_ROW_MULTI:
+            unbuilt = gecm_launch_stage1_row_multi(d->stream, d->mrowc.nq, d->mrowc.rows, tp, tl, d->dX, d->dZ, d->dS, d->stride,
+                                                   (uint32_t)d->nl, d->mrowc.d, mc.curve_group, mc.block_group);
+            break;
+        case S1_UNIT_ROW:
+            unbuilt = gecm_launch_unit_row(d->stream, d->urowc.nq, d->urowc.rows, tp, tl, d->dX, d->stride, (uint32_t)d->nl, p.pp1,
+                                           d->urowc.d, mc.curve_group, mc.block_group);
+            break;
+        }
+        if (unbuilt) {
+            g_err = std::string(p.fn) + ": no " + (p.kind == S1_UNIT_ROW ? "16" : "32") + "-lane kernel for this limb count";
+            return -2;
+        }
+        if (p.canon_after) d->k1->canon(d->stream, &mc, d->dX, d->dZ, d->stride);
         HIPCHK(hipEventRecord(d->cut_events[cut], d->stream));
     }
     HIPCHK(hipGetLastError());
@@ -850,77 +868,16 @@ static int stage1_run(gecm_dev *d, int lanes_per_curve, bool multi_rows)
     return 0;
 }
 
-extern "C" int gecm_dev_stage1(gecm_dev *d, int lanes_per_curve) { return stage1_run(d, lanes_per_curve, false); }
-
-extern "C" int gecm_dev_stage1_multi_rows(gecm_dev *d)
+static int stage1_any(gecm_dev *d, const s1_request &rq)
 {
-    REFUSE_WIDE(d, "gecm_dev_stage1_multi_rows");
-    return stage1_run(d, 0, true);
+    s1_plan p;
+    if (const int rc = s1_make_plan(d, rq, &p)) return rc;
+    return s1_run_plan(d, p);
 }
 
-/* P-1 / P+1 stage 1: the tape on one residue per lane, cut into launches as gecm_dev_stage1 cuts it
- * (between two prac() calls only A is live here too).  method: GECM_UNIT_PM1 or GECM_UNIT_PP1. */
-extern "C" int gecm_dev_stage1_unit(gecm_dev *d, int method) { return gecm_dev_stage1_unit_lanes(d, method, 1); }
-
-/* lanes = 1: one residue per lane (k_unit and its _multi / _lane forms).  lanes = 16: one residue per DPP row
- * (k_unit_row), on every kind of context; it leaves lazy values, so canon follows every launch. */
-extern "C" int gecm_dev_stage1_unit_lanes(gecm_dev *d, int method, int lanes)
-{
-    REFUSE_WIDE(d, "gecm_dev_stage1_unit_lanes");
-    HIPCHK(hipSetDevice(d->device));
-    if (ready(d, "gecm_dev_stage1_unit", false)) return -2;
-    if (!d->dTape) {
-        g_err = "gecm_dev_stage1_unit: no tape";
-        return -2;
-    }
-    if (method != GECM_UNIT_PM1 && method != GECM_UNIT_PP1) {
-        g_err = "gecm_dev_stage1_unit: the method must be P-1 or P+1";
-        return -2;
-    }
-    if (lanes != 1 && lanes != 16) {
-        g_err = "gecm_dev_stage1_unit: lanes per residue must be 1 or 16";
-        return -2;
-    }
-    if (lanes == 16 && !gecm_dev_unit_rows_ready(d)) {
-        g_err = "gecm_dev_stage1_unit: the 16-lane kernel has no constants for this batch's moduli (gecm_dev_set_unit_rowconst)";
-        return -2;
-    }
-    if (d->multi && d->lane_packed && !d->k1->has_lane) {
-        g_err = "gecm_dev_stage1_unit: no per-lane kernels at this limb count";
-        return -2;
-    }
-    char nm[96];
-    if (lanes == 16) snprintf(nm, sizeof nm, "k_unit_row<%d, %d>", d->urow_nq, d->urow_rows);
-    else snprintf(nm, sizeof nm, "%s<%d>", !d->multi ? "k_unit" : d->lane_packed ? "k_unit_lane" : "k_unit_multi", d->nl);
-    d->last_lanes = lanes;
-    d->last_kernel = nm;
-    gecm_modconst mc = modconst(d);
-    HIPCHK(hipEventRecord(d->ev0, d->stream));
-    d->cut_launches = d->tape_cuts.size() - 1;
-    while (d->cut_events.size() < d->cut_launches) {
-        hipEvent_t e;
-        HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        d->cut_events.push_back(e);
-    }
-    for (size_t cut = 0; cut + 1 < d->tape_cuts.size(); cut++) {
-        const uint32_t *tp = d->dTape + d->tape_cuts[cut] / 4;
-        const uint32_t tl = (uint32_t)(d->tape_cuts[cut + 1] - d->tape_cuts[cut]);
-        if (lanes == 16) {
-            if (gecm_launch_unit_row(d->stream, d->urow_nq, d->urow_rows, tp, tl, d->dX, d->stride, (uint32_t)d->nl,
-                                     method == GECM_UNIT_PP1, d->dURowC, mc.curve_group, mc.block_group)) {
-                g_err = "gecm_dev_stage1_unit: no 16-lane kernel for this limb count";
-                return -2;
-            }
-            d->k1->canon(d->stream, &mc, d->dX, d->dZ, d->stride);
-        } else
-            d->k1->stage1_unit(d->stream, &mc, tp, tl, d->dX, d->dZ, d->stride, method == GECM_UNIT_PP1);
-        HIPCHK(hipEventRecord(d->cut_events[cut], d->stream));
-    }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(d->ev1, d->stream));
-    d->timed = true;
-    return 0;
-}
+extern "C" int gecm_dev_stage1(gecm_dev *d, int lanes_per_curve) { return stage1_any(d, {false, 0, lanes_per_curve, false}); }
+extern "C" int gecm_dev_stage1_multi_rows(gecm_dev *d) { return stage1_any(d, {false, 0, 0, true}); }
+extern "C" int gecm_dev_stage1_unit_lanes(gecm_dev *d, int method, int lanes) { return stage1_any(d, {true, method, lanes, false}); }
 
 /* launches of the last gecm_dev_stage1 that have finished / that it made (a long tape runs as several) */
 extern "C" int gecm_dev_stage1_progress(gecm_dev *d, uint32_t *done, uint32_t *total)
@@ -951,7 +908,7 @@ extern "C" float gecm_dev_last_kernel_ms(gecm_dev *d) { return d->last_ms; }
 
 extern "C" int gecm_dev_download_mont(gecm_dev *d, uint32_t *X, uint32_t *Z)
 {
-    REFUSE_WIDE(d, "gecm_dev_download_mont");
+    if (ready(d, "gecm_dev_download_mont", NEEDS_TABLE)) return -2;
     HIPCHK(hipSetDevice(d->device));
     if (download_soa(d, X, d->dX)) return -1;
     if (download_soa(d, Z, d->dZ)) return -1;
@@ -974,9 +931,8 @@ extern "C" int gecm_dev_download_raw(gecm_dev *d, uint32_t *X, uint32_t *Z)
 
 extern "C" int gecm_dev_download_plain(gecm_dev *d, uint32_t *x, uint32_t *z)
 {
-    REFUSE_WIDE(d, "gecm_dev_download_plain");
+    if (ready(d, "gecm_dev_download_plain", NEEDS_TABLE | NEEDS_BATCH)) return -2;
     HIPCHK(hipSetDevice(d->device));
-    if (ready(d, "gecm_dev_download_plain", false)) return -2;
     gecm_modconst mc = modconst(d);
     d->k1->from_mont(d->stream, &mc, d->dX, d->dZ, d->dT0, d->dT1, d->stride);
     HIPCHK(hipGetLastError());
@@ -989,7 +945,7 @@ extern "C" int gecm_dev_download_plain(gecm_dev *d, uint32_t *x, uint32_t *z)
 extern "C" int gecm_dev_l0(gecm_dev *d, int op, const uint32_t *a, const uint32_t *b, uint32_t *c,
                            uint32_t *dd, size_t count, const uint32_t *fix)
 {
-    REFUSE_WIDE(d, "gecm_dev_l0");
+    if (ready(d, "gecm_dev_l0", NEEDS_TABLE)) return -2;
     HIPCHK(hipSetDevice(d->device));
     if (d->multi) {
         g_err = "gecm_dev_l0: not available on a multi-modulus context";
@@ -1011,7 +967,7 @@ extern "C" int gecm_dev_l0(gecm_dev *d, int op, const uint32_t *a, const uint32_
 
 extern "C" int gecm_dev_l0_inv(gecm_dev *d, const uint32_t *a, uint32_t *inv, uint32_t *g, size_t count, const uint32_t *fix)
 {
-    REFUSE_WIDE(d, "gecm_dev_l0_inv");
+    if (ready(d, "gecm_dev_l0_inv", NEEDS_TABLE)) return -2;
     HIPCHK(hipSetDevice(d->device));
     if (d->multi || !d->mod.r3 || !fix) {
         g_err = "gecm_dev_l0_inv: needs a single-modulus context opened with its inversion constants (r3)";
@@ -1038,7 +994,7 @@ struct raw_planes {
 
 extern "C" int gecm_dev_l0_raw(gecm_dev *d, int op, int special, const uint32_t *a, const uint32_t *b, uint32_t *r, size_t count)
 {
-    REFUSE_WIDE(d, "gecm_dev_l0_raw");
+    if (ready(d, "gecm_dev_l0_raw", NEEDS_TABLE)) return -2;
     HIPCHK(hipSetDevice(d->device));
     const bool known = op == GECM_L0_MUL || op == GECM_L0_SQR || op == GECM_L0_ADD || op == GECM_L0_SUB || op == GECM_L0_CONDSUB;
     if (!known || !a || !r || !count) {
@@ -1082,7 +1038,7 @@ extern "C" int gecm_dev_lane_packing_built(int nl)
 extern "C" int gecm_dev_set_groups(gecm_dev *d, uint32_t ngroups, const gecm_devmod *mods, const uint32_t *block_group,
                                    const uint32_t *curve_group)
 {
-    REFUSE_WIDE(d, "gecm_dev_set_groups");
+    if (ready(d, "gecm_dev_set_groups", NEEDS_TABLE)) return -2;
     HIPCHK(hipSetDevice(d->device));
     const size_t blocks = d->stride / 64, gb = d->k1->group_bytes;
     if (!d->multi || !ngroups || !blocks || !mods || (!block_group && !curve_group)) {
@@ -1159,7 +1115,7 @@ extern "C" uint32_t gecm_dev_s2_subseq(gecm_dev *d) { return s2_subseq_for(d, d-
 
 extern "C" int gecm_dev_set_s2_subseq(gecm_dev *d, int k)
 {
-    REFUSE_WIDE(d, "gecm_dev_set_s2_subseq");
+    if (ready(d, "gecm_dev_set_s2_subseq", NEEDS_TABLE)) return -2;
     if (k != 0 && k != -1 && (k < 1 || k > 32 || (k & (k - 1)))) return -2;
     d->s2_subseq_set = k;
     return 0;
@@ -1214,9 +1170,8 @@ static int unit_method_ok(const gecm_dev *d, const char *fn, int method)
 static int s2_init_any(gecm_dev *d, int method, const uint32_t *keep, size_t keep_words, uint32_t umax, uint32_t D,
                        uint32_t npb, uint32_t G, uint32_t ring_size, const uint32_t *tgt, const uint32_t *tgt_off, uint32_t K)
 {
-    REFUSE_WIDE(d, "gecm_dev_s2_init");
+    if (ready(d, "gecm_dev_s2_init", NEEDS_TABLE | NEEDS_R3)) return -2;
     HIPCHK(hipSetDevice(d->device));
-    if (ready(d, "gecm_dev_s2_init", true)) return -2;
     const size_t coord = (size_t)d->nl * d->stride * sizeof(uint32_t);
     if (K < 1 || K > 32 || (K & (K - 1)) || (K > 1 && (!tgt || !tgt_off))) {
         g_err = "gecm_dev_s2_init: bad number of sub-sequences";
@@ -1305,7 +1260,7 @@ extern "C" int gecm_dev_s2_init_unit(gecm_dev *d, int method, const uint32_t *ke
 static int s2_pair_any(gecm_dev *d, int method, const uint32_t *steps, uint32_t nsteps, uint32_t D, uint32_t G,
                        uint32_t ring_size, uint64_t A0, uint64_t tape_id)
 {
-    REFUSE_WIDE(d, "gecm_dev_s2_pair");
+    if (ready(d, "gecm_dev_s2_pair", NEEDS_TABLE)) return -2;
     HIPCHK(hipSetDevice(d->device));
     if (!d->dPbX || d->s2_G != G || d->s2_ring != ring_size || (ring_size & (ring_size - 1))) {
         g_err = "gecm_dev_s2_pair: stage-2 init has not run (or chunk/ring size changed)";
@@ -1362,7 +1317,7 @@ extern "C" int gecm_dev_s2_pair_unit(gecm_dev *d, int method, const uint32_t *st
 
 extern "C" int gecm_dev_s2_download(gecm_dev *d, uint32_t *acc, uint32_t *fail)
 {
-    REFUSE_WIDE(d, "gecm_dev_s2_download");
+    if (ready(d, "gecm_dev_s2_download", NEEDS_TABLE)) return -2;
     HIPCHK(hipSetDevice(d->device));
     if (!d->dAcc) {
         g_err = "gecm_dev_s2_download: no stage-2 state";
@@ -1380,14 +1335,14 @@ extern "C" int gecm_dev_s2_download(gecm_dev *d, uint32_t *acc, uint32_t *fail)
 
 extern "C" int gecm_dev_gcd_scan(gecm_dev *d, int which, uint32_t *flags, uint32_t *g)
 {
-    REFUSE_WIDE(d, "gecm_dev_gcd_scan");
+    if (ready(d, "gecm_dev_gcd_scan", NEEDS_TABLE)) return -2;
     HIPCHK(hipSetDevice(d->device));
     const uint32_t *src = which == 0 ? d->dZ : d->dAcc;
     if (!src) {
         g_err = "gecm_dev_gcd_scan: nothing to scan";
         return -2;
     }
-    if (ready(d, "gecm_dev_gcd_scan", true)) return -2;
+    if (ready(d, "gecm_dev_gcd_scan", NEEDS_R3)) return -2;
     if (grow(&d->dFlags, &d->flags_cap, d->stride)) return -1;
     gecm_modconst mc = modconst(d);
     d->k1->gcd_scan(d->stream, &mc, src, d->dT0, d->dFlags, d->stride);
@@ -1402,13 +1357,13 @@ extern "C" int gecm_dev_gcd_scan(gecm_dev *d, int which, uint32_t *flags, uint32
 /* the factor scan of a P-1 / P+1 batch: gcd(x - off, N) for the residues in X, off = 1 or 2 */
 extern "C" int gecm_dev_gcd_scan_off(gecm_dev *d, uint32_t off, uint32_t *flags, uint32_t *g)
 {
-    REFUSE_WIDE(d, "gecm_dev_gcd_scan_off");
+    if (ready(d, "gecm_dev_gcd_scan_off", NEEDS_TABLE)) return -2;
     HIPCHK(hipSetDevice(d->device));
     if (off != 1 && off != 2) {
         g_err = "gecm_dev_gcd_scan_off: the offset is 1 or 2";
         return -2;
     }
-    if (ready(d, "gecm_dev_gcd_scan_off", true)) return -2;
+    if (ready(d, "gecm_dev_gcd_scan_off", NEEDS_R3)) return -2;
     if (grow(&d->dFlags, &d->flags_cap, d->stride)) return -1;
     gecm_modconst mc = modconst(d);
     d->k1->gcd_scan_off(d->stream, &mc, d->dX, d->dT0, d->dFlags, d->stride, off);

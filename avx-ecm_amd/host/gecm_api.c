@@ -155,10 +155,10 @@ struct gecm_ctx {
     uint32_t *seed;
     int method_s2;           /* gecm_set_method_stage2: the stage-2 calls work on a method batch; kept across builds */
     int method_lanes;        /* gecm_set_method_lanes: 0 (as 1), 1, 16 or GECM_METHOD_LANES_AUTO; kept across builds */
-    int urow_state;          /* the 16-lane method kernel's constants: 0 not made yet, 1 on the device, -1 none (unit_rows_setup) */
+    int urow_state;          /* the 16-lane method kernel's constants: 0 not made yet, 1 on the device, -1 none (rows_on_device) */
     int multi_rows;          /* gecm_set_multi_rows: GECM_MULTI_ROWS_OFF, _ON or _AUTO; kept across builds */
     int wide;                /* gecm_create_wide made a wide context: stage 1 on the device, the rest on the host */
-    int mrow_state;          /* the 32-lane kernel's constants for every modulus of a multi-modulus context, as urow_state (multi_rows_setup) */
+    int mrow_state;          /* the 32-lane kernel's constants for every modulus of a multi-modulus context, as urow_state */
 };
 
 /* what a multi-modulus context cannot do: the reference radix (NWORDS) differs from modulus to modulus, and the L0
@@ -380,36 +380,69 @@ static int ff_settle(gecm_ctx *c)
 /* the device the last stage-1 launch ran on */
 static inline gecm_dev *last_dev(const gecm_ctx *c) { return c->twin.ran_last ? c->twin.dev : c->dev; }
 
+/* ---- constants of the row kernels (gecm_mod_row_consts) ------------------------------------------ */
+/* The kinds of set: the 32-lane stage-1 kernel's for a single N (gecm_dev_set_rowconst), the 16-lane method kernel's
+ *  and the 32-lane kernel's on a multi-modulus batch (§23: the first kind, and behind it the modulus's rho). */
+enum { ROWC_CURVE, ROWC_METHOD, ROWC_MULTI };
+typedef struct {
+    uint32_t *words;         /* the sets back to back; the caller frees them */
+    uint32_t sets;
+    int nq, rows;            /* gecm_row_shape of the context's limb count: rows = limbs in use, 28 (nl + 1) >= bits(N') + 5 */
+} row_sets;
+
+/* The sets of one kind for every modulus of the context: its one N, or the numbers of a multi-modulus context in the order
+ * gecm_dev_set_groups names them.  1 if made, 0 if some number has none at this limb count, -2 out of memory. */
+static int row_sets_build(const gecm_ctx *c, int kind, row_sets *out)
+{
+    const size_t set_words = kind == ROWC_CURVE ? GECM_ROW_KINDS * GECM_ROW_WORDS : kind == ROWC_METHOD ? GECM_UROW_SET : GECM_MROW_SET;
+    out->words = NULL;
+    out->sets = c->multi ? (uint32_t)c->ngroups : 1;
+    gecm_row_shape(c->mod.nl, &out->nq, &out->rows);
+    if (out->nq > GECM_ROW_MAXNQ) return 0;
+    uint32_t *s = (uint32_t *)calloc(out->sets * set_words, sizeof(uint32_t));
+    if (!s) return -2;
+    for (size_t g = 0; g < out->sets; g++) {
+        const gecm_mod *m = c->multi ? &c->grp[g] : &c->mod;
+        uint32_t *set = s + g * set_words;
+        if (!gecm_mod_row_consts(m, c->mod.nl, out->rows, kind == ROWC_METHOD ? NULL : set, kind == ROWC_METHOD ? set : NULL)) {
+            free(s);
+            return 0;
+        }
+        if (kind == ROWC_MULTI) set[GECM_ROW_KINDS * GECM_ROW_WORDS] = m->rho28;
+    }
+    out->words = s;
+    return 1;
+}
+
 /* The 32-lane stage-1 kernel's constants for the context's modulus.  Not an error if they cannot be set up: the other
  * layouts cover every N. */
 static void row_setup(gecm_ctx *c)
 {
-    int nq, L;                                        /* L = rows of a multiply = limbs in use: 28 (nl + 1) >= bits(N') + 5 */
-    gecm_row_shape(c->mod.nl, &nq, &L);
-    if (nq > GECM_ROW_MAXNQ) return;
-    uint32_t w[GECM_ROW_KINDS * GECM_ROW_WORDS];
-    if (gecm_mod_row_consts(&c->mod, c->mod.nl, L, w, NULL)) (void)gecm_dev_set_rowconst(c->dev, nq, L, w);
+    row_sets s;
+    if (row_sets_build(c, ROWC_CURVE, &s) > 0) (void)gecm_dev_set_rowconst(c->dev, s.nq, s.rows, s.words);
+    free(s.words);
 }
 
-/* The 16-lane method kernel's constant sets on the device: one for the context's modulus, or one for every modulus of
- * a multi-modulus context, in the order gecm_dev_set_groups names them.  They depend on the context's numbers alone, so
- * they are made once, when a launch first wants them.  1 if the device has them, 0 if they could not be set up. */
-static int unit_rows_setup(gecm_ctx *c)
+/* The method kernel's (ROWC_METHOD) or the multi-modulus curve kernel's (ROWC_MULTI) sets on the device.  They depend on
+ * the context's numbers alone, so they are made once, when a launch first wants them; urow_state and mrow_state say how
+ * that went: 0 not made yet, 1 on the device, -1 some number of the context has none.  1 if the device has them; 0 if there
+ * are none (remembered); -2 if host memory, -1 if the upload failed this time (not remembered: the next launch tries again). */
+static int rows_on_device(gecm_ctx *c, int kind)
 {
-    if (c->urow_state) return c->urow_state > 0;
-    c->urow_state = -1;
-    int nq, L;
-    gecm_row_shape(c->mod.nl, &nq, &L);
-    if (nq > GECM_ROW_MAXNQ) return 0;
-    const size_t ng = c->multi ? c->ngroups : 1;
-    uint32_t *u = (uint32_t *)calloc(ng * GECM_UROW_SET, sizeof(uint32_t));
-    if (!u) return 0;
-    int ok = 1;
-    for (size_t g = 0; g < ng && ok; g++)
-        ok = gecm_mod_row_consts(c->multi ? &c->grp[g] : &c->mod, c->mod.nl, L, NULL, u + g * GECM_UROW_SET);
-    if (ok && !gecm_dev_set_unit_rowconst(c->dev, nq, L, (uint32_t)ng, u)) c->urow_state = 1;
-    free(u);
-    return c->urow_state > 0;
+    int *state = kind == ROWC_METHOD ? &c->urow_state : &c->mrow_state;
+    if (*state) return *state > 0;
+    row_sets s;
+    const int made = row_sets_build(c, kind, &s);
+    if (made <= 0) {
+        if (!made) *state = -1;
+        return made;
+    }
+    const int failed = kind == ROWC_METHOD ? gecm_dev_set_unit_rowconst(c->dev, s.nq, s.rows, s.sets, s.words)
+                                           : gecm_dev_set_multi_rowconst(c->dev, s.nq, s.rows, s.sets, s.words);
+    free(s.words);
+    if (failed) return -1;
+    *state = 1;
+    return 1;
 }
 
 /* ---- lanes per residue of a method batch ---------------------------------------- */
@@ -448,7 +481,7 @@ static int method_lanes_for_launch(gecm_ctx *c)
     if (set == GECM_METHOD_LANES_AUTO &&
         gecm_method_lanes_auto(gecm_dev_stride(c->dev), c->mod.nl, gecm_dev_cus(c->dev)) != 16)
         return 1;
-    if (unit_rows_setup(c)) return 16;
+    if (rows_on_device(c, ROWC_METHOD) > 0) return 16;
     if (set == GECM_METHOD_LANES_AUTO) return 1;
     set_err("gecm_stage1_extend: the 16-lane method kernel has no constants for this context's numbers "
             "(gecm_set_method_lanes)");
@@ -456,29 +489,6 @@ static int method_lanes_for_launch(gecm_ctx *c)
 }
 
 /* ---- curve batches of a multi-modulus context in the 32-lane row layout ---------- */
-/* The 32-lane stage-1 kernel's constant sets on the device, one for every modulus of a multi-modulus context in the
- * order gecm_dev_set_groups names them: what row_setup makes for a single N, and that modulus's rho.  Made once, when a
- * launch first wants them.  1 if the device has them; 0 if some number of the context has none (remembered: mrow_state
- * -1); -2 if host memory, -1 if the upload failed this time (not remembered: the next launch tries again). */
-static int multi_rows_setup(gecm_ctx *c)
-{
-    if (c->mrow_state) return c->mrow_state > 0;
-    int nq, L;
-    gecm_row_shape(c->mod.nl, &nq, &L);
-    if (!c->multi || nq > GECM_ROW_MAXNQ) { c->mrow_state = -1; return 0; }
-    uint32_t *w = (uint32_t *)calloc(c->ngroups * GECM_MROW_SET, sizeof(uint32_t));
-    if (!w) return -2;
-    for (size_t g = 0; g < c->ngroups; g++) {
-        if (!gecm_mod_row_consts(&c->grp[g], c->mod.nl, L, w + g * GECM_MROW_SET, NULL)) { free(w); c->mrow_state = -1; return 0; }
-        w[g * GECM_MROW_SET + GECM_ROW_KINDS * GECM_ROW_WORDS] = c->grp[g].rho28;
-    }
-    const int failed = gecm_dev_set_multi_rowconst(c->dev, nq, L, (uint32_t)c->ngroups, w);
-    free(w);
-    if (failed) return -1;
-    c->mrow_state = 1;
-    return 1;
-}
-
 /* Rows up to 32 positions per compute unit, up to 64 at 37 limbs, the default layout beyond: read off the table of
  * DESIGN.md §23 (profiles/multi_rows/time_rows_on.txt against time_parent_default.txt, one MI355X of 256 compute units,
  * gecm_stage1(1e5), kernel time with the canon pass, 32 numbers).  The default launch (k_stage1_pair_multi, k_stage1_lane)
@@ -516,7 +526,7 @@ static int multi_rows_for_launch(gecm_ctx *c, const char *fn)
     if (c->multi_rows == GECM_MULTI_ROWS_AUTO &&
         !gecm_multi_rows_auto(gecm_dev_stride(c->dev), c->mod.nl, gecm_dev_cus(c->dev)))
         return 0;
-    const int have = multi_rows_setup(c);
+    const int have = rows_on_device(c, ROWC_MULTI);
     if (have > 0) return 1;
     if (c->multi_rows == GECM_MULTI_ROWS_AUTO) return 0;
     if (have == -2) set_err("%s: out of memory for the 32-lane kernel's constants", fn);
@@ -565,16 +575,17 @@ int gecm_create_wide(gecm_ctx **out, int device, const char *n_str, int digitbit
     if (rc) { free(c); return rc; }
     c->device = device;
     c->wide = 1;
-    int nq, L;
-    gecm_row_shape(c->mod.nl, &nq, &L);
-    uint32_t w[GECM_ROW_KINDS * GECM_ROW_WORDS];
-    if (nq != GECM_ROW_MAXNQ || !gecm_mod_row_consts(&c->mod, c->mod.nl, L, w, NULL)) {
+    row_sets s;
+    const int made = row_sets_build(c, ROWC_CURVE, &s);
+    if (made < 0) rc = GECM_ERR_NOMEM;
+    else if (!made || s.nq != GECM_ROW_MAXNQ) {
         set_err("gecm_create_wide: the 32-lane kernel has no constants for this N at %d limbs", c->mod.nl);
         rc = GECM_ERR_ARG;
-    } else if (gecm_dev_open_wide(&c->dev, device, c->mod.nl, c->mod.rho28) || gecm_dev_set_rowconst(c->dev, nq, L, w)) {
+    } else if (gecm_dev_open_wide(&c->dev, device, c->mod.nl, c->mod.rho28) || gecm_dev_set_rowconst(c->dev, s.nq, s.rows, s.words)) {
         set_err("gecm_create_wide: %s", gecm_dev_error());
         rc = GECM_ERR_DEVICE;
     }
+    free(s.words);
     if (rc) {
         gecm_dev_close(c->dev);
         gecm_mod_free(&c->mod);
@@ -1251,6 +1262,22 @@ static int lane_packing_refuses(const gecm_ctx *c)
     return 1;
 }
 
+/* a device call failed: its text is the error */
+static int dev_failed(void)
+{
+    set_err("%s", gecm_dev_error());
+    return GECM_ERR_DEVICE;
+}
+
+/* Does the next launch of the curve batch run on the special-form twin?  For a batch small enough for the eight-lane
+ * layout (generic moduli only) that layout beats the special multiply in its two-lane form: 1.5x against 1.4x at 15
+ * limbs, 2.2-2.4x at 30-37 limbs. */
+static int twin_takes_launch(const gecm_ctx *c)
+{
+    const int want = c->lanes_per_curve ? c->lanes_per_curve : gecm_dev_auto_lanes(c->dev);
+    return c->twin.dev && c->twin.on && c->twin.loaded && want != 8 && want != 32;
+}
+
 /* One stage-1 launch, of a reference range or of an extension segment: the tape of `key` onto the device (and onto the
  * special-form twin when it runs there), the counters (`first`: they start again), the context's B1 afterwards, every
  * cached result of the points dropped, the kernel started, and — next != NULL — the tape of the launch to follow
@@ -1267,7 +1294,7 @@ static int stage1_launch(gecm_ctx *c, const tape_key *key, uint64_t B1, int firs
     const int idle = key->kind == 1 && c->tape.len == 0;
     if (!idle && !key_eq(&c->dev_tape_k, key)) {
         /* stream-ordered after the kernel of the range before; returns when the copy is done */
-        if (gecm_dev_set_tape(c->dev, c->tape.ops, c->tape.len)) { set_err("%s", gecm_dev_error()); return GECM_ERR_DEVICE; }
+        if (gecm_dev_set_tape(c->dev, c->tape.ops, c->tape.len)) return dev_failed();
         c->dev_tape_k = *key;
     }
     if (first) c->s1_ptadds = c->s1_ptdups = 0;
@@ -1282,35 +1309,27 @@ static int stage1_launch(gecm_ctx *c, const tape_key *key, uint64_t B1, int firs
     c->normalized = 0;
     c->scan_valid[0] = c->scan_valid[1] = 0;
     if (idle) return GECM_OK;
+    int failed;
     if (c->method) {                 /* one residue per lane or per row, generic multiply: no curve layouts, no twin */
         c->twin.ran_last = 0;
-        if (unit_lanes == 1 ? gecm_dev_stage1_unit(c->dev, unit_method(c)) : gecm_dev_stage1_unit_lanes(c->dev, unit_method(c), unit_lanes)) {
-            set_err("%s", gecm_dev_error());
-            return GECM_ERR_DEVICE;
-        }
+        failed = gecm_dev_stage1_unit_lanes(c->dev, unit_method(c), unit_lanes);
     } else if (multi_rows) {         /* a multi-modulus context has no twin */
         c->twin.ran_last = 0;
-        if (gecm_dev_stage1_multi_rows(c->dev)) { set_err("%s", gecm_dev_error()); return GECM_ERR_DEVICE; }
-    } else {
-    /* For a batch small enough for the eight-lane layout (generic moduli only) that layout beats the special
-     * multiply in its two-lane form: 1.5x against 1.4x at 15 limbs, 2.2-2.4x at 30-37 limbs. */
-    const int want = c->lanes_per_curve ? c->lanes_per_curve : gecm_dev_auto_lanes(c->dev);
-    const int small_batch = want == 8 || want == 32;
-    if (c->twin.dev && c->twin.on && c->twin.loaded && !small_batch) {
+        failed = gecm_dev_stage1_multi_rows(c->dev);
+    } else if (twin_takes_launch(c)) {
         /* N | 2^k - 1: run the chain modulo 2^k - 1 with the F-form multiply; ff_settle brings X, Z back */
-        if (!key_eq(&c->twin.tape_k, key)) {
-            if (gecm_dev_set_tape(c->twin.dev, c->tape.ops, c->tape.len)) { set_err("%s", gecm_dev_error()); return GECM_ERR_DEVICE; }
+        failed = !key_eq(&c->twin.tape_k, key) && gecm_dev_set_tape(c->twin.dev, c->tape.ops, c->tape.len);
+        if (!failed) {
             c->twin.tape_k = *key;
+            failed = gecm_dev_stage1(c->twin.dev, c->lanes_per_curve);
         }
-        if (gecm_dev_stage1(c->twin.dev, c->lanes_per_curve)) { set_err("%s", gecm_dev_error()); return GECM_ERR_DEVICE; }
-        c->twin.pending = 1;
-        c->twin.ran_last = 1;
+        if (!failed) c->twin.pending = c->twin.ran_last = 1;
     } else {
         c->twin.ran_last = 0;
-        c->twin.loaded = 0;       /* the F-form copy of the points no longer matches */
-        if (gecm_dev_stage1(c->dev, c->lanes_per_curve)) { set_err("%s", gecm_dev_error()); return GECM_ERR_DEVICE; }
+        c->twin.loaded = 0;          /* the F-form copy of the points no longer matches */
+        failed = gecm_dev_stage1(c->dev, c->lanes_per_curve);
     }
-    }
+    if (failed) return dev_failed();
     if (next && !c->pf_active) {
         /* while the device runs this range: the next one's tape (2 s of host time per 1e8 primes on 8 threads) */
         c->pf_k = *next;

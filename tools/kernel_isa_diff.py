@@ -1,4 +1,4 @@
-"""Are the kernels of two builds the same instructions?  For every gecm_kernels_*_p?.o and gecm_rowk.o present in both
+"""Are the kernels of two builds the same instructions?  For every gecm_kernels_*_p?.o, gecm_rowk.o and gecm_rowk_wide.o present in both
 build directories: the gfx950 code object (taken as tools/kernel_resources.py takes it) is disassembled and every
 symbol's instruction stream compared.  Masked: the padding after a function, and the pc-relative literal of a call
 (s_getpc_b64 and the s_add_u32 / s_addc_u32 pair behind it), which moves with the layout of the object.
@@ -43,7 +43,7 @@ def symbols(obj):
 
 
 def main(dir_a, dir_b):
-    names = lambda d: {os.path.basename(p) for pat in ("gecm_kernels_*_p?.o", "gecm_rowk.o") for p in glob.glob(os.path.join(d, pat))}
+    names = lambda d: {os.path.basename(p) for pat in ("gecm_kernels_*_p?.o", "gecm_rowk.o", "gecm_rowk_wide.o") for p in glob.glob(os.path.join(d, pat))}
     both = sorted(names(dir_a) & names(dir_b), key=lambda n: [int(t) if t.isdigit() else t for t in re.split(r"(\d+)", n)])
     if not both:
         print("no kernel object is in both directories")
