@@ -24,7 +24,12 @@
 //     and the pre-multiplied operands stay inside 32 bits;
 //   * between the entry and the exit conversion the tape interpreter keeps every value pre-multiplied (times 4): a
 //     multiply delivers its result in that scale in the instructions it spent on the plain one, sums and differences
-//     keep it, and no multiply of a point operation shifts an operand.
+//     keep it, and no multiply of a point operation shifts an operand;
+//   * at one limb per lane in the DPP form a multiply can read a finished broadcast of its scanned operand (fer_scan,
+//     fer_mul_scanned), made while an X <-> Z exchange is in flight: the point addition (row_add_scanned, §5f) and the
+//     double (row_dup_scanned, §5g) are written for it, and that form has a tape interpreter of its own
+//     (run_tape_row_dpp: the rule-3 steps a tight loop, the begin, the end and the add-and-double step a path each, one
+//     scan of fA per event, renaming by conditional moves).
 // The residues are the same elements of Z/N as in every other layout (N | N'), so results are identical; the
 // kernel converts from and to the R = 2^(28*NL) Montgomery form of the device buffers at entry and exit
 // (R' = 2^(448*NQ) inside), and k_canon makes the exit values canonical.
@@ -468,6 +473,31 @@ __device__ __forceinline__ void row_dup(FeR<NQ> &own, const FeR<NQ> &fA, const F
     for (int i = 0; i < NQ; i++) own.v[i] = isZ ? t.v[i] : r1.v[i];
 }
 
+// row_dup for one limb per lane in the DPP form, on the caller's scan of fA (the one the addition of the same event has
+// read already), with VALU work in the shadow of its X <-> Z exchange: the second multiply scans p1, which does not wait
+// for the exchange (the Z rows' s4, the X rows' own square), and the third scans w, known since before the second.  The
+// products are the same residues whichever operand is scanned.  Bounds: fA is a sum or a difference
+// of two product limbs times 4 (at most 2^30 + 32 in absolute value), p1 a product limb times 4, w and r1 + q a
+// difference and a sum of two such: each inside fer_mul's 4 x 2^29 whether it is the scanned operand or the lane's own.
+template <int ROWS>
+__device__ __forceinline__ void row_dup_scanned(FeR<1> &own, const RowScan<ROWS> &sA, const FeR<1> &fA, const FeR<1> &s4,
+                                                bool isZ, const RowMod<1> &m)
+{
+    FeR<1> q, t, w, p1, p2, r1;
+    RowScan<ROWS> sP, sW;
+    fer_mul_scanned<ROWS>(q, sA, fA, m);                                // X: U = (x+z)^2    Z: V = (x-z)^2
+    fer_other<1>(t, q);                                                 // X: V              Z: U
+    p1.v[0] = isZ ? s4.v[0] : q.v[0];
+    fer_scan<ROWS>(sP, p1);
+    w.v[0] = t.v[0] - q.v[0];                                           // Z: w = U - V
+    p2.v[0] = isZ ? w.v[0] : t.v[0];
+    fer_mul_scanned<ROWS>(r1, sP, p2, m);                               // X: U*V            Z: s*w
+    t.v[0] = r1.v[0] + q.v[0];                                          // Z: s*w + V
+    fer_scan<ROWS>(sW, w);
+    fer_mul_scanned<ROWS>(t, sW, t, m);                                 // Z: (s*w + V)*w
+    own.v[0] = isZ ? t.v[0] : r1.v[0];
+}
+
 template <int NQ>
 __device__ __forceinline__ void fer_load(FeR<NQ> &r, const uint32_t *__restrict__ base, size_t stride, uint32_t cidx,
                                          uint32_t l, uint32_t nl)
@@ -479,11 +509,139 @@ __device__ __forceinline__ void fer_load(FeR<NQ> &r, const uint32_t *__restrict_
     }
 }
 
-// run_tape_quad of gecm_quad.hpp on rows: A, B, C are this lane's limbs of its coordinate (and their forms).
+// run_tape_row (below) for one limb per lane in the DPP form: the same events, the same operands in the same roles, every
+// event written the way the loop of rule-3 steps is.  A begin, an end and an add-and-double step are
+// three paths that meet only at the head of the tape loop; every path ends with the next tape byte and then the exchange
+// of its last result, and what it renames it renames by conditional moves on wave-uniform masks (row_pick) in chosen
+// places, so that no path has a join of its own where the compiler copies points (what is left: three copies where a path
+// returns to the head, five between the rule-3 loop and the other events).  One scan of fA serves the addition's first
+// multiply and the double's.  The rule-3 steps stay a loop of their own inside the tape loop: as one more path of a flat
+// loop every step took two jumps across the other paths' 11 KB, and the kernel was 2 % slower than before instead of 2 %
+// faster.  The fetch of the tape bytes, the rule-3 renaming and the meaning of every op byte are written
+// here and in run_tape_row: a change of the tape format (gecm_tape.h) touches both.
+template <int ROWS>
+__device__ __forceinline__ void run_tape_row_dpp(const uint32_t *__restrict__ tape, uint32_t tape_len, PtR<1> &A,
+                                                 const FeR<1> &s4, bool isZ, const RowSign &g, const RowMod<1> &m)
+{
+    // Of C only the other coordinate is kept between steps, as in run_tape_row.
+    PtR<1> B = A;
+    FeR<1> Coth = A.oth;
+    auto fetch = [&](uint32_t pc) -> uint32_t {
+        uint32_t w = tape[pc >> 2];
+        return __builtin_amdgcn_readfirstlane((w >> ((pc & 3u) * 8u)) & 0xffu);
+    };
+    uint32_t pc = 0;
+    uint32_t op = tape_len ? fetch(0) : GECM_OP_NOP;
+    uint32_t nxt = 1 < tape_len ? fetch(1) : GECM_OP_NOP;
+    // the tape byte before the exchange that ends an event: its scalar load and the wait for it would drain the exchange
+    auto advance = [&]() {
+        pc++;
+        op = nxt;
+        nxt = (pc + 1 < tape_len) ? fetch(pc + 1) : GECM_OP_NOP;
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    while (pc < tape_len) {
+        // rule 3: T = A + B (C); (A, B, C) <- (A, T, B), after a swap (B, T, A): the sum does not depend on the order of A
+        // and B (row_add), so the swap only says which of the two stays A and which becomes C.  Three conditional moves:
+        // what stays A is chosen before the addition (B's own register is then free), what becomes C behind the scan of the
+        // old C, and the new point is made in B's registers.  The exchange that brings B.oth was issued at the end of the
+        // event before, and what does not read it comes first: the form of the kept point, the pick that frees B's
+        // register and the scan of that form.  Only then fB, the wait, and the rows.
+        while ((op & ~GECM_OP_SWAP) == (GECM_OP_STEP | GECM_OP_RULE3)) {
+            const uint64_t swap = (op & GECM_OP_SWAP) ? ~(uint64_t)0 : 0;
+            FeR<1> fA, fB;
+            RowScan<ROWS> sA;
+            row_sd<1>(fA, A, g);
+            row_pick<1>(A.own, A.own, B.own, swap);
+            fer_scan<ROWS>(sA, fA);
+            row_ds<1>(fB, B, g);
+            row_add_scanned<ROWS>(B.own, sA, fB, Coth, g, m, [&]() {
+                row_pick<1>(Coth, B.oth, A.oth, swap);
+                row_pick<1>(A.oth, A.oth, B.oth, swap);
+            });
+            advance();
+            fer_other<1>(B.oth, B.own);
+        }
+        if (op == GECM_OP_NOP) {
+            advance();
+            continue;
+        }
+        FeR<1> fA, fB;
+        RowScan<ROWS> sA;
+        if (op == GECM_OP_PRAC_END) {                   // A <- A + B (C)
+            row_sd<1>(fA, A, g);
+            fer_scan<ROWS>(sA, fA);
+            row_ds<1>(fB, B, g);
+            row_add_scanned<ROWS>(A.own, sA, fB, Coth, g, m, []() {});
+            advance();
+            fer_other<1>(A.oth, A.own);
+            continue;
+        }
+        if (op == GECM_OP_PRAC_BEGIN) {                 // B <- A, C <- A, A <- 2A
+            row_sd<1>(fA, A, g);
+            fer_scan<ROWS>(sA, fA);
+            B = A;
+            Coth = A.oth;
+            row_dup_scanned<ROWS>(A.own, sA, fA, s4, isZ, m);
+            advance();
+            fer_other<1>(A.oth, A.own);
+            continue;
+        }
+        // An add-and-double step.  With a, b = A, B after the swap bit:
+        //   rule 4   T = a + b (C)    A <- 2a, B <- T
+        //   rule 5   T = a + C (b)    A <- 2a, B <- b, C <- T
+        //   rule 9   T = b + C (a)    A <- a, B <- 2b, C <- T: rule 5 with a and b exchanged before and A and B after; the
+        //            exchange before is the swap bit inverted, the one after a branch that 42 of a B1 = 1e6 tape's events take
+        // a, b by conditional moves; rules 5 and 9 put C in b's place as the addition's second point and b.oth in C's as its
+        // difference, by three more, and put b back behind the double, by another three.  C's own coordinate is fetched on
+        // rules 5 and 9 alone, as soon as the byte is known, and read behind the scan of fA.  T's exchange has the whole
+        // double behind it; the double's goes out behind the next tape byte, with the renaming behind it.
+        const bool r59 = (op & GECM_OP_RULE_MASK) != GECM_OP_RULE4, r9 = (op & GECM_OP_RULE_MASK) == GECM_OP_RULE9;
+        const uint64_t swap = (uint64_t)0 - (((op >> 2) ^ ((op >> 1) & op)) & 1u);  // SWAP is bit 2; rule 9 has bits 0 and 1
+        const uint64_t rot = (uint64_t)0 - ((op >> 1) & 1u);                      // rules 5 and 9 have bit 1
+        PtR<1> a, b, q;
+        FeR<1> Cown, c, T, Toth;
+        // Cown is written on rules 5 and 9 only.  The empty asm gives it a register without an instruction, so that the pick
+        // of q.own below has an operand on rule 4 too: rot is 0 there, the pick takes b.own and what the register holds is
+        // never selected.
+        asm volatile("" : "=v"(Cown.v[0]));
+        if (r59) fer_other<1>(Cown, Coth);
+        row_pick<1>(a.own, A.own, B.own, swap);
+        row_pick<1>(a.oth, A.oth, B.oth, swap);
+        row_sd<1>(fA, a, g);
+        fer_scan<ROWS>(sA, fA);
+        row_pick<1>(b.own, B.own, A.own, swap);
+        row_pick<1>(b.oth, B.oth, A.oth, swap);
+        row_pick<1>(q.own, b.own, Cown, rot);
+        row_pick<1>(q.oth, b.oth, Coth, rot);
+        row_pick<1>(c, Coth, b.oth, rot);
+        row_ds<1>(fB, q, g);
+        row_add_scanned<ROWS>(T, sA, fB, c, g, m, []() {});
+        fer_other<1>(Toth, T);
+        row_dup_scanned<ROWS>(A.own, sA, fA, s4, isZ, m);
+        advance();
+        fer_other<1>(A.oth, A.own);
+        row_pick<1>(B.own, T, b.own, rot);
+        row_pick<1>(B.oth, Toth, b.oth, rot);
+        row_pick<1>(Coth, Coth, Toth, rot);
+        if (r9) {
+            const PtR<1> t = A;
+            A = B;
+            B = t;
+        }
+    }
+}
+
+// run_tape_quad of gecm_quad.hpp on rows: A, B, C are this lane's limbs of its coordinate (and their forms).  The one-limb
+// DPP form goes to run_tape_row_dpp above, which reads the same tape: a change of the tape format touches both.
 template <int NQ, int ROWS, bool ALDS>
 __device__ __forceinline__ void run_tape_row(const uint32_t *__restrict__ tape, uint32_t tape_len, PtR<NQ> &A,
                                              const FeR<NQ> &s4, bool isZ, const RowSign &g, const RowMod<NQ> &m)
 {
+    if constexpr (NQ == 1 && !ALDS) {
+        run_tape_row_dpp<ROWS>(tape, tape_len, A, s4, isZ, g, m);
+        return;
+    }
     // Of C only the other coordinate is kept between steps: that is what C gives to an addition, and its own one is the
     // other row's (one more exchange, made in the steps that turn C into A or B: rules 5 and 9).
     PtR<NQ> B = A;
@@ -503,38 +661,16 @@ __device__ __forceinline__ void run_tape_row(const uint32_t *__restrict__ tape, 
         while ((op & ~GECM_OP_SWAP) == (GECM_OP_STEP | GECM_OP_RULE3)) {
             const uint64_t swap = (op & GECM_OP_SWAP) ? ~(uint64_t)0 : 0;
             FeR<NQ> fA, fB;
-            if constexpr (NQ == 1 && !ALDS) {
-                // One limb per lane, DPP form: the exchange that brings B.oth was issued at the end of the step before (below),
-                // and what does not read it comes first: the form of the kept point, the pick that frees B's register and
-                // the scan of that form.  Only then fB, the wait, and the rows.  The picks that read the old C follow its
-                // scan, in the shadow of the addition's own exchange (row_add_scanned).
-                RowScan<ROWS> sA;
-                row_sd<NQ>(fA, A, g);
-                row_pick<NQ>(A.own, A.own, B.own, swap);
-                fer_scan<ROWS>(sA, fA);
-                row_ds<NQ>(fB, B, g);
-                row_add_scanned<ROWS>(B.own, sA, fB, Coth, g, m, [&]() {
-                    row_pick<NQ>(Coth, B.oth, A.oth, swap);
-                    row_pick<NQ>(A.oth, A.oth, B.oth, swap);
-                });
-                // the tape byte first: its scalar load and the wait for it would drain the exchange as well
-                pc++;
-                op = nxt;
-                nxt = (pc + 1 < tape_len) ? fetch(pc + 1) : GECM_OP_NOP;
-                __builtin_amdgcn_sched_barrier(0);
-                fer_other<NQ>(B.oth, B.own);
-            } else {
-                row_sd<NQ>(fA, A, g);
-                row_ds<NQ>(fB, B, g);
-                row_pick<NQ>(A.own, A.own, B.own, swap);
-                row_add<NQ, ROWS, ALDS>(B.own, fB, fA, Coth, isZ, g, m);
-                row_pick<NQ>(Coth, B.oth, A.oth, swap);
-                row_pick<NQ>(A.oth, A.oth, B.oth, swap);
-                fer_other<NQ>(B.oth, B.own);
-                pc++;
-                op = nxt;
-                nxt = (pc + 1 < tape_len) ? fetch(pc + 1) : GECM_OP_NOP;
-            }
+            row_sd<NQ>(fA, A, g);
+            row_ds<NQ>(fB, B, g);
+            row_pick<NQ>(A.own, A.own, B.own, swap);
+            row_add<NQ, ROWS, ALDS>(B.own, fB, fA, Coth, isZ, g, m);
+            row_pick<NQ>(Coth, B.oth, A.oth, swap);
+            row_pick<NQ>(A.oth, A.oth, B.oth, swap);
+            fer_other<NQ>(B.oth, B.own);
+            pc++;
+            op = nxt;
+            nxt = (pc + 1 < tape_len) ? fetch(pc + 1) : GECM_OP_NOP;
         }
         if (op == GECM_OP_NOP) continue;
         const uint32_t rule = op & GECM_OP_RULE_MASK;
@@ -567,14 +703,7 @@ __device__ __forceinline__ void run_tape_row(const uint32_t *__restrict__ tape, 
         row_sd<NQ>(fA, A, g);
         row_ds<NQ>(fB, B, g);
         if (do_add) {
-            if constexpr (NQ == 1 && !ALDS) {
-                // (the scan of fA is not shared with the double's first multiply: it would stay live across the addition)
-                RowScan<ROWS> sA;
-                fer_scan<ROWS>(sA, fA);
-                row_add_scanned<ROWS>(T.own, sA, fB, C.oth, g, m, []() {});
-            } else {
-                row_add<NQ, ROWS, ALDS>(T.own, fB, fA, C.oth, isZ, g, m);
-            }
+            row_add<NQ, ROWS, ALDS>(T.own, fB, fA, C.oth, isZ, g, m);
             fer_other<NQ>(T.oth, T.own);
         }
         if (do_dup) {
